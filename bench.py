@@ -7,8 +7,15 @@ the step ends with the path's single all-gather of the depth decisions (SURVEY.m
   --scaling weak   (default) every rank owns its own GOP of --frames pictures (frames dealt to ranks, work grows with N)
   --scaling strong           ONE GOP of --frames pictures split over the ranks
   --bands                    CTU-row bands of every picture (BASELINE config 3: 3840x2160 unless --width/--height say otherwise)
-Prints ONE JSON line on rank 0.  The timed region (exactly --steps steps between barrier + synchronize) is repeated
---repeats times; `value` is the median region, min / median / max are reported next to it.
+Prints ONE JSON line on rank 0.  The timed region is exactly --steps steps between barrier + synchronize; `value` and
+`ms_per_step` come from it.  --repeats R runs R such regions (value = the median region, min / median / max next to it).
+
+A plain run does only what the headline needs: set-up, --prewarm + --warmup untimed steps, the timed region, the
+`roofline` of the depth kernel from HIP events inside that region, the BD-rate figures quoted from profiles/, and the line.
+--full adds everything that takes runs of its own: the CPU baseline and the GPU hook legs through the reference's
+compressSlice, the other arithmetic form ("variants"), the host-to-host leg, the other stages of the path, the network
+family members, and five regions instead of one.
+--dump-outputs DIR writes what the last timed step computed (depth maps and source Hadamards, as float .npy) into DIR.
 """
 import argparse
 import json
@@ -177,6 +184,27 @@ def gpu_hook_leg(width, height, bit_depth, crops, margins=None, first_pass=False
                 os.environ[k] = v
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6   # all dumped arrays together
+
+
+def dump_outputs(out_dir, arrays):
+    """write {name: (array, float dtype)} as out_dir/<name>.npy.  Above DUMP_LIMIT_BYTES every array keeps a fixed, seeded sample
+    of its rows (first axis), the same fraction of each, and <name>_rows.npy (float64) lists which rows they are."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.size * np.dtype(dt).itemsize for a, dt in arrays.values())
+    keep = min(1.0, 0.95 * DUMP_LIMIT_BYTES / max(1, total))
+    written = []
+    for name, (a, dt) in arrays.items():
+        if keep < 1.0:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], min(a.shape[0], max(1, int(a.shape[0] * keep))), replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+            written.append(f"{name}_rows.npy")
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=dt))
+        written.append(f"{name}.npy")
+    return {"dir": out_dir, "files": written, "sampled": keep < 1.0}
+
+
 def quoted_bd_rate():
     """the quality half of BASELINE's metric, quoted from the committed evaluations under profiles/ (tests/quality/eval_rd.py,
     eval_p.py: minutes of CPU each, not re-run here)"""
@@ -206,7 +234,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)   # the clocks of a fresh process take ~30 steps to settle
     ap.add_argument("--prewarm", type=int, default=30, help="untimed steps before the --warmup steps: a fresh process's GPU clocks settle over ~30 steps "
                                                             "(reported as prewarm_steps; 0 = none)")
-    ap.add_argument("--repeats", type=int, default=5, help="how many times the timed region of --steps steps is run (value = median)")
+    ap.add_argument("--repeats", type=int, default=None, help="how many times the timed region of --steps steps is run (value = median; "
+                                                              "default 1, 5 with --full)")
+    ap.add_argument("--full", action="store_true", help="also run the secondary measurements: CPU baseline and hook legs, variants, host path, "
+                                                        "stages, family members (each can still be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the depth maps and source Hadamards of the last timed step as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
     ap.add_argument("--frames", type=int, default=None, help="frames per GOP (default 64; 16 with --bands)")
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--height", type=int, default=None)
@@ -220,8 +253,8 @@ def main():
     ap.add_argument("--no-host-path", action="store_true", help="skip the host-to-host (PCIe-inclusive) leg")
     ap.add_argument("--cpu-procs", type=int, default=None, help="processes of the all-cores CPU baseline (default: host cores, at most 16)")
     ap.add_argument("--arith", choices=("i8", "f16"), default=None,
-                    help="arithmetic of the classifier's conv2 / conv3 for the headline (default: the library's, i8); the other form is timed "
-                         "beside it (\"variants\") unless --no-variants")
+                    help="arithmetic of the classifier's conv2 / conv3 for the headline (default: the library's, i8); with --full the other form is "
+                         "timed beside it (\"variants\") unless --no-variants")
     ap.add_argument("--no-variants", action="store_true")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse)")
     ap.add_argument("--one-device", action="store_true", help="rehearsal on a 1-GPU box: every rank uses cuda:0 (needs --backend gloo)")
@@ -229,6 +262,8 @@ def main():
                     help="only prove the N-rank launch: rendezvous, one barrier and one all-gather of the ranks over the host group, then exit "
                          "(no GPU is touched: the CPU test of the self-launcher uses this with --backend gloo)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Plain `python bench.py --gpus N`: start the N ranks ourselves, one process per GPU, exactly as the driver's launcher would
@@ -269,7 +304,7 @@ def main():
 
     # ---- CPU baseline first: its workers are children of a process that has not touched the GPU yet ----
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import oracle_py as op
         if op.have_ref():
             cpu = cpu_baseline_reference(1920, 1080, bd, procs=args.cpu_procs)
@@ -373,9 +408,16 @@ def main():
     cnn_ms, cnn_n = ctx.kernel_timing(0)
     had_ms, had_n = ctx.kernel_timing(1)
 
+    # what the last timed step delivered: the depth maps of the whole step (256 per CTU) and this rank's source Hadamards
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {
+            "depth_maps": (gathered.cpu().numpy().reshape(total_frames * n_ctus, 256), np.float32),
+            "src_hadamard": (had[:fg.local_ctus].cpu().numpy(), np.float64)})
+
     # ---- the other arithmetic form of the classifier, the same steps on the same box (one timed region): a second line, never `value` ----
     variants = None
-    if not args.no_variants:
+    if args.full and not args.no_variants:
         other = "f16" if arith == "i8" else "i8"
         ctx.set_cnn_arith(other)
         for i in range(args.warmup):
@@ -413,7 +455,7 @@ def main():
     # ---- host to host ("depth map delivered to host memory"): the same GOP from pinned host memory through
     # fhevc_predict_frames (chunks of 16 pictures over two streams), PCIe included; never `value` ----
     host = None
-    if rank == 0 and world == 1 and not args.no_host_path:
+    if rank == 0 and world == 1 and args.full and not args.no_host_path:
         host = {}
         torch.cuda.synchronize()
         for label, sb in (("uint8_planes", 1), ("int16_pel_planes", 2)):
@@ -451,7 +493,7 @@ def main():
 
     # the path's other stages, measured AFTER the timed region on the same GOP -- reported, never in `value`
     stages = None
-    if rank == 0 and not args.no_stages:
+    if rank == 0 and args.full and not args.no_stages:
         nb = min(nf_local, 8)
         nodes = torch.zeros((nb * n_ctus * 85, 2), dtype=torch.float64, device=dev)
         act = torch.zeros((nf_local, ctx.aq_layout(4)[-1]), dtype=torch.float64, device=dev)
@@ -554,7 +596,7 @@ def main():
 
     # ---- the reference's Bayesian-optimisation network family (NetworkDepth 1: 32 / 64 / 128) on the same GOP: its own line, never `value` ----
     family_line = None
-    if rank == 0 and world == 1 and not args.no_family:
+    if rank == 0 and world == 1 and args.full and not args.no_family:
         fblob = os.path.join(ROOT, "fasthevc_amd", "weights", "depthnet_family_d1.fhw")
         fw = weights.load_any(fblob) if os.path.exists(fblob) else weights.random_family((32, 64, 128), 1, seed=0)
         fctx = capi.Context(W, H, bd, fw, device=local, max_frames=max(1, min(NF, 16)))
@@ -685,6 +727,8 @@ def main():
         }
         if hbm:
             line["roofline_hbm_kernel"] = hbm
+        if dumped:
+            line["dump_outputs"] = dumped
         if family_line:
             line["family"] = family_line
         bdr = quoted_bd_rate()
@@ -701,7 +745,7 @@ def main():
             line["collective"] = fg.status
             # no SCALE record of an earlier round exists: the builder has no multi-GPU box, RCCL over xGMI runs for the first time in the driver's own run
             line["multi_gpu_note"] = "N > 1 unmeasured on hardware by the builder (gloo rehearsals only); this line is the first RCCL measurement"
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             if cpu is None:
                 cpu = cpu_baseline_port(1920, 1080, bd, w)
             else:

@@ -7,10 +7,11 @@ TAG=${1:-r03}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$GRAFT_REPO_ROOT"
-timeout -k 10 500 python3 bench.py > "$OUT/bench_default.log" 2> "$OUT/bench_default.err" || exit 1
+ROOT=$PWD
+timeout -k 10 500 python3 bench.py --full > "$OUT/bench_default.log" 2> "$OUT/bench_default.err" || exit 1
 timeout -k 10 200 python3 tools/bench_kernels.py > "$OUT/bench_kernels.json" 2> "$OUT/bench_kernels.err" || exit 1
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$GRAFT_REPO_ROOT/bench.py" --no-cpu-baseline --no-host-path --no-stages > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err" || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-host-path --no-stages > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err" || exit 1
 # the secondary kernels (first pass, pre-analysis, both motion searches ...) under the same profiler
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_kernels" -- python3 "$GRAFT_REPO_ROOT/tools/bench_kernels.py" > "$OUT/bench_kernels_under_rocprof.json" 2> "$OUT/bench_kernels_under_rocprof.err" || exit 1
 cd "$GRAFT_REPO_ROOT"
