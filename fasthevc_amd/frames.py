@@ -283,6 +283,24 @@ def to_pel_plane(luma_u8, internal_bit_depth=8, margin=HM_MARGIN):
     return buf, margin * stride + margin, stride
 
 
+def native_pel_plane(luma_u8, bit_depth, seed=0, margin=HM_MARGIN):
+    """uint8 luma -> int16 `Pel` plane of NATIVE bit_depth content (to_pel_plane's layout: stride W + 2*margin, origin at
+    (margin, margin)).  Unlike to_pel_plane's shift, the content is stretched over the whole range [0, 2^bd - 1] (its darkest
+    sample becomes 0, its brightest 2^bd - 1), and seeded noise of +-2^(bd-8) fills the low bits, clipped at both ends; the
+    darkest and brightest samples stay at the literal values 0 and 2^bd - 1.  Returns (buffer, origin_offset_in_samples, stride)."""
+    hi = (1 << bit_depth) - 1
+    h, w = luma_u8.shape
+    lo8, hi8 = int(luma_u8.min()), int(luma_u8.max())
+    v = (luma_u8.astype(np.int64) - lo8) * hi // max(hi8 - lo8, 1)
+    amp = 1 << max(bit_depth - 8, 0)
+    v = np.clip(v + np.random.default_rng(seed).integers(-amp, amp + 1, size=(h, w)), 0, hi)
+    v[luma_u8 == lo8], v[luma_u8 == hi8] = 0, hi
+    stride = w + 2 * margin
+    buf = np.zeros((h + 2 * margin, stride), np.int16)
+    buf[margin:margin + h, margin:margin + w] = v.astype(np.int16)
+    return buf, margin * stride + margin, stride
+
+
 def chroma_planes(kind, width, height):
     """(U, V) uint8 planes [H/2, W/2] of the pinned generators: U = 128, V a horizontal sinusoid."""
     _, xx = np.mgrid[0:height, 0:width]

@@ -204,3 +204,55 @@ def random_family(widths=(32, 64, 128), depth=1, seed=0):
         w[k] = rng.integers(-50000, 50000, size=2).astype(np.int32)
     w["qp_bias"] = rng.integers(-200000, 200000, size=(3, 52)).astype(np.int32)
     return w
+
+
+# ---- blobs at the requant limits (tests) ------------------------------------------------------------------------------------------------------------
+# The library picks requant4_i8's short form 2 (bytes 1-2 of the accumulator, exact below 2^23) for a shift-8 layer whose bound
+# |b + 128 sum w| + 128 sum |w| (the largest |accumulator| any input can produce, activations travelling as a - 128) is below 2^23.
+# These blobs put that bound at 2^23 - 1 ("edge") or just above it ("over") with all-positive weights behind a first layer that
+# saturates every channel at 255 (weights 0, bias 255 << shift): the realised accumulator 255 v K + b then sits within v K of the
+# bound, and the "over" bias makes it exactly 2^23, which the short form would wrap to 0 instead of 255.
+REQUANT_LIMIT = 1 << 23
+
+
+def requant_limit_layer(k, over=False, v=None):
+    """(weight value v, bias b) of a shift-8 layer with K = k taps per output: bound 2^23 - 1 (over: realised accumulator 2^23)."""
+    v = min(127, (REQUANT_LIMIT - 1) // (256 * k)) if v is None else v
+    b = REQUANT_LIMIT - 1 - 256 * v * k
+    return v, b + (v * k + 1 if over else 0)
+
+
+def requant_limit_weights(layer, over=False, seed=0):
+    """The 16 / 32 / 64 network with conv2 (layer 2) or conv3 (layer 3) at the requant limit; layer "high": conv3 at 127 on every tap
+    with bias 2^22 (accumulators near 13.5 M: the general form, and the f16 form's 2^24 exactness bound).
+    The depth kernel runs its short forms only as a pair, conv2 in form 1 (shift <= 7) and conv3 in form 2 (k_cnn.hip: cnn_arith): the
+    conv3 blobs keep conv2 at shift 7, so that the conv3 bound alone decides; a shift-8 conv2 runs the general forms on either side of 2^23."""
+    w = random_weights(seed)
+    w["w1"][:], w["b1"][:] = 0, 255 << 4
+    if layer == 2:
+        w["shift"] = np.array([4, 8, 8], np.int32)
+        v, b = requant_limit_layer(16 * 9, over)
+        w["w2"][:], w["b2"][:] = v, b
+    else:
+        w["shift"] = np.array([4, 7, 8], np.int32)
+        w["w2"][:], w["b2"][:] = 127, 0   # 127 * 255 * 144 >> 7 saturates at 255
+        v, b = (127, BIAS_LIMIT) if layer == "high" else requant_limit_layer(32 * 9, over)
+        w["w3"][:], w["b3"][:] = v, b
+    validate(w)
+    return w
+
+
+def requant_limit_family(widths=(23, 46, 92), depth=2, over=False, seed=0):
+    """A family member whose every convolution after the first sits at the requant limit (shift 8)."""
+    w = random_family(widths, depth, seed)
+    w["shift"][:] = 0
+    ci = 1
+    for b in range(3):
+        for j in range(depth):
+            if b == 0 and j == 0:
+                w["w00"][:], w["b00"][:], w["shift"][0, 0] = 0, 255 << 6, 6
+            else:
+                v, bias = requant_limit_layer(9 * ci, over)
+                w[f"w{b}{j}"][:], w[f"b{b}{j}"][:], w["shift"][b, j] = v, bias, 8
+            ci = widths[b]
+    return w

@@ -3,6 +3,7 @@
 (oracle/_ref/libhmref.so = objects compiled from /root/reference + oracle/ref_harness.cpp).
 
 Run in the build container only (needs /root/reference):  make -C oracle ref && python oracle/gen_golden.py
+(--bit-depths-only: tests/golden/ref_bit_depths.npz alone, bit_depths_golden)
 The fixture holds inputs and expected outputs (data), never reference source.
 """
 import os
@@ -189,14 +190,6 @@ def intra_lines_golden(ref):
     print("wrote", dst, os.path.getsize(dst), "bytes")
 
 
-if __name__ == "__main__":
-    if "--intra-lines-only" in sys.argv:
-        intra_lines_golden(op.load_ref())
-    elif "--preanalyze-only" in sys.argv:
-        preanalyze_golden(op.load_ref())
-    else:
-        main()
-
 
 PATTERN_SEARCH_CASES = (  # (bit depth, qp, range, clip seed, CTUs of the 7 x 4 grid of 416x240: corners, edges (32 wide / 48 tall), interior)
     (8, 38, 4, 15, (0, 3, 6, 10, 21, 27)),
@@ -260,3 +253,124 @@ def pattern_search_golden(ref, cases=None, name="ref_pattern_search.npz"):
     dst = os.path.join(os.path.dirname(HERE), "tests", "golden", name)
     np.savez_compressed(dst, **out)
     print("wrote", dst, os.path.getsize(dst), "bytes;", total, "nodes searched by the reference's xPatternSearch")
+
+
+def _pattern_nodes(ref, cur, refp, stride, W, H, bd, lam, rng, ctus):
+    """xPatternSearch on every in-picture CU node of the given CTUs -> [len(ctus), 85, 4] (mvx, mvy, SAD, cost; -1 outside)."""
+    import ctypes as C
+    cw = (W + 63) // 64
+    res = np.full((len(ctus), 85, 4), -1, np.int32)
+    for ci, c in enumerate(ctus):
+        cx, cy = c % cw, c // cw
+        blocks, where = [], []
+        idx = 0
+        for lvl in range(4):
+            n, cnt = 64 >> lvl, 1 << lvl
+            for by in range(cnt):
+                for bx in range(cnt):
+                    x0, y0 = cx * 64 + bx * n, cy * 64 + by * n
+                    if x0 + n <= W and y0 + n <= H:
+                        blocks.append((x0, y0, n)); where.append(idx)
+                    idx += 1
+        b = np.array(blocks, np.int32)
+        o = np.zeros((len(blocks), 4), np.int32)
+        assert ref.href_pattern_search(cur.ctypes.data, refp.ctypes.data, stride, W, H, bd, C.c_double(lam), rng, len(blocks),
+                                       b.ctypes.data, o.ctypes.data) == len(blocks)
+        res[ci, where] = o
+    return res
+
+
+def bit_depths_golden(ref):
+    """tests/golden/ref_bit_depths.npz: the reference's own SATD (calcHAD / xGetHADs), reference-sample fill, 35 predictors,
+    initIntraPatternChType lines, pre-analysis / xComputeQP and xPatternSearch at bit depths 9 to 12 and on full-swing samples
+    (0 against 2^bd - 1).  The inputs are regenerated from seeds (oracle/bd_cases.py); the file holds case lists and outputs.
+
+    HM was built with RExt__HIGH_BIT_DEPTH_SUPPORT 0 (Pel = 16 bit); every function here accepted every depth 9 to 12."""
+    import ctypes as C
+    from oracle import bd_cases as bc
+    oracle = op.load_oracle()
+    out = {"hm_version": np.frombuffer(ref.href_version(), np.uint8)}
+
+    meta, calc, get = [], [], []
+    for bd in bc.SATD_BIT_DEPTHS:
+        for (w, h) in bc.SATD_SHAPES:
+            for rep, kind in enumerate(bc.SATD_KINDS):
+                a, b = bc.satd_pair(bd, w, h, kind, rep)
+                get.append(ref.href_get_hads(bd, op.ptr(a), 64, op.ptr(b), 64, w, h))
+                calc.append(ref.href_calc_had(bd, op.ptr(a), 64, op.ptr(b), 64, w, h) if (w % 4 == 0 and h % 4 == 0) else 0xFFFFFFFF)
+                meta.append((bd, w, h, rep))
+    out["satd_meta"] = np.array(meta, np.int32)
+    out["satd_calchad"], out["satd_gethads"] = np.array(calc, np.uint32), np.array(get, np.uint32)
+
+    for bd in bc.INTRA_BIT_DEPTHS:
+        for n in bc.INTRA_SIZES:
+            lines = []
+            for rep in range(bc.FILL_REPS):
+                pic, flags = bc.fill_case(bd, n, rep)
+                roi = np.zeros((2 * n + 1) * (2 * n + 1), np.int16)
+                side = pic.shape[1]
+                ref.href_fill_ref(bd, op.ptr(pic.reshape(-1), 4 * side + 4), side, flags, n, roi)
+                lines.append(op.roi_to_ref_line(roi.reshape(2 * n + 1, 2 * n + 1), n))
+            out[f"fill_n{n}_bd{bd}"] = np.stack(lines)
+            for kind in ("sat", "flat"):
+                roi = np.ascontiguousarray(op.ref_line_to_roi(bc.pred_line(bd, n, kind), n).reshape(-1))
+                preds = np.zeros((35, n, n), np.int16)
+                for m in range(35):
+                    p = np.zeros(n * n, np.int16)
+                    ref.href_pred_intra(roi, n, m, bd, p)
+                    preds[m] = p.reshape(n, n)
+                out[f"pred_{kind}_n{n}_bd{bd}"] = preds
+
+    lib = op.bind_rdo(ref)
+    lib.href_intra_lines.argtypes = [C.c_int] * 7 + [C.c_void_p, C.c_void_p]
+    for k, (content, w, h, bd, qp, ctus) in enumerate(bc.INTRA_LINE_CASES):
+        buf, org, stride = bc.intra_line_plane(content, w, h, bd)
+        op.rdo_encode(lib, buf, org, stride, w, h, bd, qp)
+        cw = (w + 63) // 64
+        meta, unf, flt = [], [], []
+        first = True
+        for c in ctus:
+            for depth in range(4):
+                n = 64 >> depth
+                for by in range(1 << depth):
+                    for bx in range(1 << depth):
+                        x0, y0 = (c % cw) * 64 + bx * n, (c // cw) * 64 + by * n
+                        if x0 + n > w or y0 + n > h:
+                            continue
+                        a, b = np.zeros(4 * n + 1, np.int16), np.zeros(4 * n + 1, np.int16)
+                        rc = lib.href_intra_lines(w, h, bd, c, depth, (by * n // 4) * 16 + bx * n // 4, 1 if first else 0, a.ctypes.data, b.ctypes.data)
+                        assert rc == 4 * n + 1, rc
+                        first = False
+                        meta.append((c, depth, x0, y0, n)); unf.append(a); flt.append(b)
+        out[f"lines_meta{k}"], out[f"lines_unf{k}"], out[f"lines_flt{k}"] = np.array(meta, np.int32), np.concatenate(unf), np.concatenate(flt)
+
+    for k, (content, w, h, bd, depth) in enumerate(bc.PREANALYZE_CASES):
+        buf, org, stride = bc.preanalyze_plane(content, w, h, bd)
+        n = sum(((w + (64 >> d) - 1) // (64 >> d)) * ((h + (64 >> d) - 1) // (64 >> d)) for d in range(depth))
+        act, avg = np.zeros(n), np.zeros(depth)
+        assert ref.href_preanalyze(op.ptr(buf.reshape(-1), org), stride, w, h, bd, depth, act, avg) == n
+        out[f"pre_act{k}"], out[f"pre_avg{k}"] = act, avg
+        for s, (range_, qp) in enumerate(bc.AQ_SETTINGS):
+            q = np.zeros(n, np.int32)
+            assert ref.href_aq_qp(op.ptr(buf.reshape(-1), org), stride, w, h, bd, depth, range_, qp, q) == n
+            out[f"pre_qp{k}_{s}"] = q.astype(np.int8)
+
+    ref.href_pattern_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    for k, (bd, qp, rng, content, seed, ctus) in enumerate(bc.PATTERN_CASES):
+        cur, refp, stride = bc.pattern_planes(bd, content, seed)
+        out[f"ps_nodes{k}"] = _pattern_nodes(ref, cur, refp, stride, 416, 240, bd, oracle.fho_lambda_intra(qp, bd), rng, ctus)
+
+    dst = os.path.join(os.path.dirname(HERE), "tests", "golden", "ref_bit_depths.npz")
+    np.savez_compressed(dst, **out)
+    print("wrote", dst, os.path.getsize(dst), "bytes")
+
+
+if __name__ == "__main__":
+    if "--intra-lines-only" in sys.argv:
+        intra_lines_golden(op.load_ref())
+    elif "--preanalyze-only" in sys.argv:
+        preanalyze_golden(op.load_ref())
+    elif "--bit-depths-only" in sys.argv:
+        bit_depths_golden(op.load_ref())
+    else:
+        main()

@@ -1,6 +1,7 @@
 """The oracle's integer depth classifier against an independent float64 torch restatement of the same network
 (parity for this part is "unpinned" w.r.t. the reference: it ships no inference code or weights)."""
 import numpy as np
+import pytest
 import torch
 import torch.nn.functional as Fn
 
@@ -196,3 +197,102 @@ def test_family_oracle_reproduces_the_base_network_and_a_float64_restatement(ora
         exp[5:21] = l16.reshape(2, 16).numpy().T
         exp[0, 1] += w["qp_bias"][0, 32]; exp[1:5, 1] += w["qp_bias"][1, 32]; exp[5:, 1] += w["qp_bias"][2, 32]
         assert np.array_equal(got.reshape(21, 2), exp.astype(np.int64)), depth
+
+
+def _bound(wl, b, first=False):
+    """the library's requant bound (fhevc_api.hip, build_weight_image / the family loader): max over outputs of |b'| + 128 sum |w|"""
+    wl = np.asarray(wl, np.int64).reshape(len(b), -1)
+    bp = np.asarray(b, np.int64) + (0 if first else 128 * wl.sum(1))
+    return int((np.abs(bp) + 128 * np.abs(wl).sum(1)).max())
+
+
+def _torch_accumulators(layers, ctu, wrap=None):
+    """float64 restatement of a chain of conv3x3 layers [(w, b, shift, pool)]: -> (largest accumulator per layer, last map).
+    wrap = layer index whose requant takes bytes 1-2 of the accumulator (the short form) instead of the general one."""
+    t = lambda a: torch.from_numpy(np.asarray(a).astype(np.float64))
+    x = t(ctu).reshape(1, 1, 64, 64)
+    peaks = []
+    for i, (wk, bk, sh, pool) in enumerate(layers):
+        x = Fn.conv2d(x, t(wk), t(bk), padding=1)
+        if pool:
+            x = Fn.max_pool2d(x, 2)
+        peaks.append(float(x.max()))
+        if i == wrap:   # int16 of bits 8..23
+            x = torch.remainder(torch.floor(x / 256) + 32768, 65536) - 32768
+        else:
+            x = torch.floor(x / float(1 << int(sh)))
+        x = torch.clamp(x, 0, 255)
+    return peaks, x
+
+
+def _base_layers(w):
+    return [(w["w1"].reshape(16, 1, 3, 3), w["b1"], w["shift"][0], True), (w["w2"], w["b2"], w["shift"][1], True), (w["w3"], w["b3"], w["shift"][2], False)]
+
+
+def _family_layers(f):
+    d = int(f["depth"])
+    return [(f[f"w{b}{j}"], f[f"b{b}{j}"], f["shift"][b][j], j == d - 1 and b < 2) for b in range(3) for j in range(d)]
+
+
+@pytest.mark.parametrize("layer", [2, 3])
+def test_base_blobs_at_the_requant_limit(oracle, layer):
+    """Bound of conv2 / conv3 at 2^23 - 1 (short form 2 chosen) and one past it (general form); flat content realises > 99 % of it:
+    the edge blob's accumulator stays below 2^23, the over blob's reaches exactly 2^23, where the short form would give 0 instead of 255
+    -- and that changes the logits, so a wrong form cannot hide behind a later clamp."""
+    ctu = np.zeros((64, 64), np.int8)
+    li = layer - 1
+    for over in (False, True):
+        w = weights.requant_limit_weights(layer, over)
+        wl, bl = w[f"w{layer}"], w[f"b{layer}"]
+        bound = _bound(wl, bl)
+        assert int(w["shift"][li]) == 8 and (bound >= 1 << 23) == over
+        assert bound == (1 << 23) - 1 + (0 if not over else int(np.asarray(wl).reshape(len(bl), -1).sum(1).max()) + 1)
+        if layer == 3:  # conv2 keeps its short form 1 (shift 7): the conv3 bound alone decides between the kernel's short and general forms
+            assert int(w["shift"][1]) == 7
+        peaks, _ = _torch_accumulators(_base_layers(w), ctu)
+        assert peaks[li] >= 0.99 * bound and (peaks[li] == 1 << 23) == over and peaks[li] <= bound
+        acts, logits = torch_cnn(w, ctu)
+        ws = op.weights_from_arrays(w)
+        a1, a2, a3, lg = np.zeros(32 * 32 * 16, np.uint8), np.zeros(16 * 16 * 32, np.uint8), np.zeros(16 * 16 * 64, np.uint8), np.zeros(42, np.int32)
+        oracle.fho_cnn_ctu_debug(ws, np.ascontiguousarray(ctu.reshape(-1)), 27, a1, a2, a3, lg)
+        assert np.array_equal(lg.reshape(21, 2).astype(np.int64), logits)
+        assert acts[li].max() == 255
+        _, wrapped = _torch_accumulators(_base_layers(w), ctu, wrap=li)
+        _, plain = _torch_accumulators(_base_layers(w), ctu)
+        assert torch.equal(wrapped, plain) != over   # the short form is exact on the edge blob only
+        if over:  # ... and the wrapped activations reach the logits
+            a3w = wrapped[0].permute(1, 2, 0)
+            assert not torch.equal(a3w, torch.from_numpy(acts[2].astype(np.float64)))
+            assert int((a3w[:8, :8] * torch.from_numpy(w["wh32"][0].astype(np.float64))).sum()) + int(w["bh32"][0]) != logits[1, 0]
+
+
+def test_high_conv3_accumulators_stay_exact_in_f16_and_take_the_general_form():
+    w = weights.requant_limit_weights("high")
+    assert _bound(w["w3"], w["b3"]) >= 1 << 23
+    peaks, _ = _torch_accumulators(_base_layers(w), np.zeros((64, 64), np.int8))
+    assert 13_000_000 < peaks[2] < 1 << 24
+
+
+def test_family_blob_at_the_requant_limit(oracle):
+    """The 23 / 46 / 92 x 2 member (k_cnn_d2.inc; d2_short when every bound is below 2^23) with every convolution after the first at
+    the edge, and one past it."""
+    import ctypes as C
+    ctu = np.zeros((64, 64), np.int8)
+    for over in (False, True):
+        f = weights.requant_limit_family(over=over)
+        layers = _family_layers(f)
+        bounds = [_bound(wk, bk, first=(i == 0)) for i, (wk, bk, _, _) in enumerate(layers)]
+        assert all((b >= 1 << 23) == over for b in bounds[1:]) and bounds[0] < 1 << 23
+        peaks, _ = _torch_accumulators(layers, ctu)
+        for i in range(1, len(layers)):
+            assert peaks[i] >= 0.99 * bounds[i] and (peaks[i] == 1 << 23) == over, (i, peaks[i], bounds[i])
+        # all-positive weights re-saturate behind a wrapped layer; the last one feeds the heads directly
+        _, wrapped = _torch_accumulators(layers, ctu, wrap=len(layers) - 1)
+        _, plain = _torch_accumulators(layers, ctu)
+        assert torch.equal(wrapped, plain) != over
+        # the oracle's family network is the same chain
+        lg = np.zeros(42, np.int32)
+        oracle.fho_cnn_ctu_family(C.byref(op.family_from_arrays(f)), C.c_void_p(np.ascontiguousarray(ctu).ctypes.data), 27, C.c_void_p(lg.ctypes.data))
+        a3 = plain[0].permute(1, 2, 0)
+        exp16 = int((a3[:4, :4] * torch.from_numpy(f["wh16"][0].astype(np.float64))).sum()) + int(f["bh16"][0])
+        assert lg[2 * 5] == exp16

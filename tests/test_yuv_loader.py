@@ -36,7 +36,8 @@ def test_edge_replication_padding_and_16bit_files(tmp_path):
 
 
 @pytest.mark.parametrize("w,h,fbd,ibd,chroma", [(416, 240, 8, 8, 420), (420, 236, 10, 10, 420), (410, 234, 8, 10, 420), (100, 70, 8, 8, 400),
-                                                 (422, 238, 12, 12, 444), (64, 64, 8, 8, 422)])
+                                                 (422, 238, 12, 12, 444), (64, 64, 8, 8, 422),
+                                                 (418, 238, 9, 10, 420), (410, 236, 11, 12, 422)])
 def test_the_librarys_cpp_reader_equals_the_python_one(tmp_path, w, h, fbd, ibd, chroma):
     """fhevc_read_yuv_luma (host C++ inside the HIP library; no device needed) against YuvLumaReader, which restates TVideoIOYuv::read for the
     luma plane: 8- and 16-bit files, edge-replication padding to the conformance size, InputBitDepth -> InternalBitDepth shift, chroma of every
