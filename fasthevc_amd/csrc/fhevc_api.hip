@@ -53,7 +53,6 @@ struct fhevc_ctx {
   // kernel timing
   bool fuse_hadamard = true;  // FHEVC_FUSE_HADAMARD=0 keeps the stand-alone Hadamard launch (A/B measurements)
   bool motion_sad = false;    // fhevc_set_motion_distortion: SAD (HM's integer-search distortion) instead of Hadamard SATD
-  bool cnn_pipe = false;      // FHEVC_CNN_PIPE=1: the i8 form as the two-stage software pipeline over CTUs (k_cnn.hip: fhevc_cnn_depth_pipe_kernel)
   bool had_valu = true;       // FHEVC_HADAMARD_FORM=mfma: the fused Hadamard of 8-bit content on the bf16 MFMA from the staged tile instead of packed
                               // 16-bit VALU (parity-green, and measured 7 % SLOWER in round 3: profiles/r03_ab_hadamard_forms.log) -- kept for A/B and tests
   FhevcKnobs knobs;           // the environment's tuning / test switches, read once in fhevc_create
@@ -612,7 +611,6 @@ FhevcCnnWeights cnn_weights(const fhevc_ctx* c)
   w.requant_mode[0] = 0; w.requant_mode[1] = c->requant_mode[1]; w.requant_mode[2] = c->requant_mode[2];
   w.i8 = c->cnn_i8 ? 1 : 0;
   w.had_valu = c->had_valu ? 1 : 0;
-  w.pipe = c->cnn_pipe ? 1 : 0;
   return w;
 }
 
@@ -698,7 +696,6 @@ int fhevc_create(fhevc_ctx** out, const fhevc_cfg* cfg)
   c->num_cus = prop.multiProcessorCount;
   c->knobs = fhevc_read_knobs();   // every environment switch of the library is read here, once per context
   if (const char* fz = std::getenv("FHEVC_FUSE_HADAMARD")) c->fuse_hadamard = fz[0] != '0';
-  if (const char* pp = std::getenv("FHEVC_CNN_PIPE")) c->cnn_pipe = pp[0] == '1';
   if (const char* hf = std::getenv("FHEVC_HADAMARD_FORM")) c->had_valu = std::strcmp(hf, "mfma") != 0;
   // arithmetic of conv2 / conv3 in the depth kernel: "f16" (16-bit MFMAs) or "i8" (v_mfma_i32_32x32x32_i8); both are exact
   if (const char* ar = std::getenv("FHEVC_CNN_ARITH")) c->cnn_i8 = std::strcmp(ar, "f16") != 0;
@@ -1638,7 +1635,7 @@ int fhevc_debug_cnn_phase_cycles(fhevc_ctx* c, const void* d_luma, int sample_by
   out12[10] = mhz.empty() ? 0.0 : mhz[mhz.size() / 2];
   out12[11] = mhz.empty() ? 0.0 : mhz.front();
   // [12 + 9 * slot + k]: the same eight phase sums averaged over the workgroups of CU slot 0 / 1 / 2 (k = 8: how many workgroups that is) -- the caller's
-  // array holds 39 doubles (FHEVC_DEBUG_STAMPS_BY_SLOT=1; the i8 form's conv-phase priority differs by slot, k_cnn.hip FHEVC_SLOT_PRIO)
+  // array holds 39 doubles (FHEVC_DEBUG_STAMPS_BY_SLOT=1; the i8 form's conv-phase priority differs by slot, k_cnn.hip FHEVC_PRIO_ON)
   if (std::getenv("FHEVC_DEBUG_STAMPS_BY_SLOT")) {
     for (int k = 12; k < 39; ++k) out12[k] = 0;
     for (int b = 0; b < grid; ++b) {

@@ -30,7 +30,7 @@
 #define FHEVC_FRAGI8_TOTAL (6 * 64 + 2 * 9 * 64)
 
 // Tuning / test switches read from the environment ONCE, at fhevc_create (fhevc_read_knobs), and kept in the context: nothing on a launch path
-// calls getenv.  None of them changes results; FHEVC_CNN_ARITH / FHEVC_CNN_REQUANT / FHEVC_HADAMARD_FORM / FHEVC_CNN_PIPE / FHEVC_FUSE_HADAMARD
+// calls getenv.  None of them changes results; FHEVC_CNN_ARITH / FHEVC_CNN_REQUANT / FHEVC_HADAMARD_FORM / FHEVC_FUSE_HADAMARD
 // select between forms that the parity suite runs side by side.
 struct FhevcKnobs {
   int wg_per_cu = 0;            // FHEVC_CNN_WG_PER_CU=1..4: workgroups per CU of the depth kernel's persistent grid (0: the form's own)
@@ -73,7 +73,6 @@ struct FhevcCnnWeights {
   int requant_mode[3];       // per layer: 0 general, 1 shift <= 7 (packed 16-bit shift), 2 shift == 8 and |accumulator| < 2^23 (byte gather)
   int i8;                    // 1: run that variant
   int had_valu;              // 1: the fused source Hadamard on packed 16-bit VALU also for 8-bit content (default; FHEVC_HADAMARD_FORM=mfma: 0)
-  int pipe;                  // 1: the i8 form runs as the two-stage software pipeline over CTUs (fhevc_cnn_depth_pipe_kernel; FHEVC_CNN_PIPE)
 };
 
 // a member of the reference's Bayesian-optimisation network family with one convolution per block (k_cnn_family.inc; FHW3 blob)

@@ -21,13 +21,11 @@
 // into registers during conv3 and staged into LDS after the heads; four barriers per CTU.
 //   HAD = 1: the per-CTU source Hadamard (TEncCu::updateCtuDataISlice) on packed 16-bit VALU from the prefetched samples, at the tail of
 //     conv3 (default); HAD = 2: the same on the bf16 MFMA from the staged tile (8-bit content; measured slower, kept for A/B and tests).
-// Round 3 adds, after the kernel: fhevc_cnn_depth_pipe_kernel, the i8 form as a two-stage software pipeline over CTUs (opt-in, measured
-// slower), and k_cnn_family.inc, the reference's Bayesian-optimisation network family (NetworkDepth 1: 32 / 64 / 128 filters).
+// Round 3 adds, after the kernel: k_cnn_family.inc, the reference's Bayesian-optimisation network family (NetworkDepth 1: 32 / 64 / 128 filters).
 #include "fhevc_internal.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <type_traits>
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8;   // 8 x 16-bit operand slots of an MFMA fragment (bf16 for conv1, f16 for conv2/conv3)
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
@@ -35,17 +33,6 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(2))) unsigned short u16x2;
 
 namespace {
-
-// compile-time loop: f(std::integral_constant<int, I>) for I = B .. E-1 (a 36-step body with nested loops is past what `#pragma unroll`
-// unrolls; register arrays indexed by a loop variable that stays a variable go through v_movrel / scratch)
-template <int B, int E, typename F>
-__device__ __forceinline__ void static_for(F&& f)
-{
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    static_for<B + 1, E>(f);
-  }
-}
 
 // ---- LDS map (bytes) ---------------------------------------------------------------------------------------
 // conv1 output: 32x32 + 1 halo each side = 34 x 34 positions, 16 B per position and plane
@@ -64,9 +51,6 @@ constexpr int IN_PITCH = 68;                      // dwords per input row PAIR (
 //   I8 = false: f16 (16-bit MFMAs): A1 = 2 planes of 8 channels, A2 = 4 planes of 8 channels;
 //   I8 = true : signed bytes a - 128 (v_mfma_i32_32x32x32_i8 in conv2 and conv3): A1 = 1 plane of 16 channels (+ one phantom row that
 //               only zero weights meet), A2 = 2 planes of 16 channels -- half the LDS, which is what lets three workgroups share a CU
-#ifndef FHEVC_MFMA_HEADS_F16
-#define FHEVC_MFMA_HEADS_F16 0  // the 16-bit form keeps its v_dot4 heads: with the MFMA heads it measured the same (0.5756 against 0.5767 ms, parity green)
-#endif
 // Wave priority per phase (s_setprio 0..3), one hex digit each: 0x<heads><conv3><conv2><conv1>.  With three workgroups per CU the i8
 // form gains 4 % when its three conv phases outrank the heads / staging / depth phases of the other workgroups' waves on the same SIMD
 // (same-box A/B: none 0.4440, conv2+conv3 0.4336, +conv1 0.4285 at level 1 and 0.4262 at level 2, +heads 0.4355 ms); the 16-bit form
@@ -79,36 +63,16 @@ constexpr int IN_PITCH = 68;                      // dwords per input row PAIR (
 #endif                         // 0.5199 at 0x0122, 0.5093 at 0x0123 (0x0133 0.5124, 0x0022 0.5216, 0x0112 0.5251); the i8 form measures equal across these
 // phase: 0 conv1, 1 conv2, 2 conv3, 3 heads
 #define FHEVC_PRIO_OF(phase) (((I8 ? FHEVC_I8_PRIO : FHEVC_F16_PRIO) >> (4 * (phase))) & 3)
-// Round 4: the conv phases' level also depends on WHICH of the CU's three workgroups the wave belongs to (FHEVC_SLOT_PRIO = 2, the default of the i8
-// form: conv phases at 1 + slot = 1 / 2 / 3, everything else at 0).  With one level for all, two waves of a SIMD that are both in a conv phase tie and
+// Round 4: in the i8 form the conv phases' level also depends on WHICH of the CU's three workgroups the wave belongs to (conv phases at
+// 1 + slot = 1 / 2 / 3, everything else at 0).  With one level for all, two waves of a SIMD that are both in a conv phase tie and
 // the arbiter falls back to age; with the levels apart the matrix pipe goes to one of them outright and the other's chain runs in the gaps: same-box
 // A/B 0.3801 -> 0.3706 ms (-2.5 %, twice: profiles/r04_ab_slot_priority.log).  slot = the workgroup's LDS base / its LDS size (HW_REG_LDS_ALLOC): 0, 1, 2
 // whatever order the dispatcher fills the CUs in (tools/probes/probe_wg_slot.hip: under round-robin dispatch it equals blockIdx / 256).  Measured and
-// dropped: 1 = static slot level without phase levels (+4.6 %), 3 = conv phases at 1 + slot and the rest at slot (+2.8 %), 4 = tables: conv1 held at
+// dropped: static slot level without phase levels (+4.6 %), conv phases at 1 + slot and the rest at slot (+2.8 %), tables: conv1 held at
 // 1 (-1.0 %) or at 0 (+1.9 %), heads at 1 for slots 1, 2 (-1.0 %), levels by phase only 1 / 2 / 3 (-1.6 %).
-#ifndef FHEVC_SLOT_PRIO
-#define FHEVC_SLOT_PRIO 2
-#endif
 #define FHEVC_SETPRIO_DYN(p) { const int p_ = (p); if (p_ == 1) __builtin_amdgcn_s_setprio(1); else if (p_ == 2) __builtin_amdgcn_s_setprio(2); else if (p_ >= 3) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0); }
-#if FHEVC_SLOT_PRIO == 0
-#define FHEVC_PRIO_ON(phase)  if (FHEVC_PRIO_OF(phase)) __builtin_amdgcn_s_setprio(FHEVC_PRIO_OF(phase));
-#define FHEVC_PRIO_OFF(phase) if (FHEVC_PRIO_OF(phase)) __builtin_amdgcn_s_setprio(0);
-#elif FHEVC_SLOT_PRIO == 1
-#define FHEVC_PRIO_ON(phase)
-#define FHEVC_PRIO_OFF(phase)
-#elif FHEVC_SLOT_PRIO == 2
 #define FHEVC_PRIO_ON(phase)  if (FHEVC_PRIO_OF(phase)) { if (I8) FHEVC_SETPRIO_DYN(1 + prio_slot) else __builtin_amdgcn_s_setprio(FHEVC_PRIO_OF(phase)); }
 #define FHEVC_PRIO_OFF(phase) if (FHEVC_PRIO_OF(phase)) __builtin_amdgcn_s_setprio(0);
-#elif FHEVC_SLOT_PRIO == 3
-#define FHEVC_PRIO_ON(phase)  if (FHEVC_PRIO_OF(phase)) FHEVC_SETPRIO_DYN(1 + prio_slot)
-#define FHEVC_PRIO_OFF(phase) if (FHEVC_PRIO_OF(phase)) FHEVC_SETPRIO_DYN(prio_slot)
-#else  // 4: a table, one 16-bit group 0x<heads><conv3><conv2><conv1> per slot (slot 0 in the low bits)
-#ifndef FHEVC_SLOT_TABLE
-#define FHEVC_SLOT_TABLE 0x033302220111ULL
-#endif
-#define FHEVC_PRIO_ON(phase)  FHEVC_SETPRIO_DYN((int)((FHEVC_SLOT_TABLE >> (16 * prio_slot + 4 * (phase))) & 3))
-#define FHEVC_PRIO_OFF(phase) __builtin_amdgcn_s_setprio(0);
-#endif
 // tuning knobs of the i8 form's pipeline descriptions (VALU instructions offered per MFMA group of a chain; fences around the pools).
 // conv2 measured best with the chains pinned as (MFMA, DS read) groups only and the epilogue VALU left to the scheduler, without
 // fences: 0.4322 ms (fences, 2 / 5 VALU per group) -> 0.4226 (no fences) -> 0.4212 (no fences, no VALU groups), same-box A/B
@@ -139,9 +103,6 @@ constexpr int IN_PITCH = 68;                      // dwords per input row PAIR (
 #ifndef FHEVC_I8_C3_SCHED
 #define FHEVC_I8_C3_SCHED 0  // conv3 of the i8 form runs 0.7 % faster WITHOUT a pipeline description (0.4231 -> 0.4202 ms); conv2 needs its (MFMA, DS read)
 #endif                       // pairing: without it 0.4575 ms
-#ifndef FHEVC_CONV1_MFMA_FIRST
-#define FHEVC_CONV1_MFMA_FIRST 0
-#endif
 #ifndef FHEVC_F16_C3_SCHED
 #define FHEVC_F16_C3_SCHED 1
 #endif
@@ -367,20 +328,9 @@ __device__ __forceinline__ void conv1_store_i8(const f32x16& acc0, const f32x16&
   for (int k = 0; k < 8; ++k) m[k] = fmaxf(fmaxf(acc0[k], acc0[k + 8]), fmaxf(acc1[k], acc1[k + 8]));
   *reinterpret_cast<uint2*>(dst) = make_uint2(u8x4_floor_clamp(m[0], m[1], m[2], m[3]) ^ 0x80808080u, u8x4_floor_clamp(m[4], m[5], m[6], m[7]) ^ 0x80808080u);
 }
-#ifndef FHEVC_X_NOBIAS
-#define FHEVC_X_NOBIAS 0   // (sensitivity experiments, tools/experiments: 1 = no bias-tile reads, WRONG results, timing only)
-#endif
-#ifndef FHEVC_X_C3_HALF
-#define FHEVC_X_C3_HALF 0  // (sensitivity experiments: 1 = conv3 reads half of its fragments, WRONG results, timing only)
-#endif
 __device__ __forceinline__ i32x16 bias_tile_i8(const int* b32, int h)  // the integer twin of bias_tile
 {
   i32x16 acc;
-  if (FHEVC_X_NOBIAS) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0;
-    return acc;
-  }
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
     const int4 v = *reinterpret_cast<const int4*>(b32 + 8 * g + 4 * h);
@@ -586,8 +536,8 @@ __device__ __forceinline__ void conv3_pairs_i8(const unsigned char* base, const 
     const int g = 18 * S + 2 * t;
     acc0 = mfma_i8(wA3[t], ring[g % RING3], acc0);
     if (g + RING3 < 36) ring[g % RING3] = lds_frag(base + conv3_frag_off_i8(g + RING3));
-    acc1 = mfma_i8(wA3[t], ring[(g + (FHEVC_X_C3_HALF ? 2 : 1)) % RING3], acc1);
-    if (!FHEVC_X_C3_HALF && g + 1 + RING3 < 36) ring[(g + 1) % RING3] = lds_frag(base + conv3_frag_off_i8(g + 1 + RING3));
+    acc1 = mfma_i8(wA3[t], ring[(g + 1) % RING3], acc1);
+    if (g + 1 + RING3 < 36) ring[(g + 1) % RING3] = lds_frag(base + conv3_frag_off_i8(g + 1 + RING3));
   }
 }
 template <int VALU_PER_GROUP>
@@ -722,17 +672,11 @@ __device__ __forceinline__ void hadamard_samples(const Prefetched& pre, unsigned
     r[6] = __builtin_amdgcn_perm(0u, pre.a.w, 0x0C010C00u); r[7] = __builtin_amdgcn_perm(0u, pre.a.w, 0x0C030C02u);
   }
 }
-__device__ __forceinline__ int wave_src_hadamard_core(unsigned (&r)[8], int lane);
 template <int SB>
 __device__ __forceinline__ int wave_src_hadamard(const Prefetched& pre, int lane)
 {
   unsigned r[8];
   hadamard_samples<SB>(pre, r);
-  return wave_src_hadamard_core(r, lane);
-}
-// the transform itself: straight-line code (the pipelined kernel places it inside conv2's MFMA chain)
-__device__ __forceinline__ int wave_src_hadamard_core(unsigned (&r)[8], int lane)
-{
   int t[2];  // per block: 2 * (this lane's share of sum |coefficients| / 2) - (this lane's share of the block's sample sum)
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
@@ -832,7 +776,7 @@ __device__ __forceinline__ void stage_ctu(unsigned char* lds, int r2_off, const 
       dst[2 * j] = (unsigned short)(__float_as_uint((float)v) >> 16);
     }
   }
-  // input halo: 66*66 - 64*64 = 260 two-byte cells of bf16(128) (the pipelined kernel's tile region is never overwritten: it fills the halo once)
+  // input halo: 66*66 - 64*64 = 260 two-byte cells of bf16(128) (the family kernel's tile region is never overwritten: it fills the halo once)
   if (HALO) {
     asm volatile("" : "+v"(in_cells));
     *reinterpret_cast<unsigned short*>(lds + (in_cells & 0xFFFF)) = 0x4300;
@@ -947,16 +891,15 @@ __global__ __launch_bounds__(TRIO ? 768 : 256, TRIO ? 1 : (ARITH ? FHEVC_I8_WG_P
   const int tid = TRIO ? (int)(threadIdx.x & 255) : (int)threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   constexpr bool I8 = ARITH != 0, FASTRQ = ARITH == 2;
-  int prio_slot = 0;   // which of the CU's workgroups this is, from where its LDS allocation starts (see FHEVC_SLOT_PRIO)
-  if (FHEVC_SLOT_PRIO && I8) {
+  int prio_slot = 0;   // which of the CU's workgroups this is, from where its LDS allocation starts (see FHEVC_PRIO_ON)
+  if (I8) {
     const unsigned la = __builtin_amdgcn_s_getreg((31 << 11) | 6);   // HW_REG_LDS_ALLOC: base [11:0], size [20:12], both in 256-byte granules
     const unsigned base = la & 0xFFFu, sz = (la >> 12) & 0x1FFu;
     prio_slot = base >= 2 * sz && sz ? 2 : (base >= sz && sz ? 1 : 0);
     if (TRIO) prio_slot = group;
   }
   (void)prio_slot;
-  if (FHEVC_SLOT_PRIO == 1 || FHEVC_SLOT_PRIO == 3) FHEVC_SETPRIO_DYN(prio_slot)
-  constexpr bool MFMA_HEADS = FHEVC_MFMA_HEADS_F16 || I8;  // the two smaller FC heads as an i8 MFMA GEMM (P4)
+  constexpr bool MFMA_HEADS = I8;  // the two smaller FC heads as an i8 MFMA GEMM (P4)
   (void)FASTRQ;
   using L = Lds<I8>;
   const HaloCells hc = halo_cells<I8>(tid);  // three registers for the life of the kernel
@@ -1207,10 +1150,6 @@ __global__ __launch_bounds__(TRIO ? 768 : 256, TRIO ? 1 : (ARITH ? FHEVC_I8_WG_P
         if (I8) conv1_store_i8(acc0, acc1, dp);
         else conv1_store(acc0, acc1, dp);
         dp += 4 * A1_ROW;
-        if (FHEVC_CONV1_MFMA_FIRST && (i & 1)) {  // (experiment) both units' MFMAs of an unrolled pair ahead of their epilogues
-          __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, 60, 0);
-        }
       }
       FHEVC_PRIO_OFF(0)
     }
@@ -1604,49 +1543,7 @@ __global__ __launch_bounds__(TRIO ? 768 : 256, TRIO ? 1 : (ARITH ? FHEVC_I8_WG_P
 #undef FHEVC_HAD_FRAG_LOADS
 }
 
-
-// =====================================================================================================================================
-// The i8 form as a TWO-STAGE SOFTWARE PIPELINE over the CTUs of a workgroup (round 3; FHEVC_CNN_PIPE).  Same network, same arithmetic, same
-// per-wave work split as fhevc_cnn_depth_kernel<.., ARITH = 1 | 2>; what changes is WHEN each piece runs.  The kernel above runs a CTU
-// through five phases with four barriers, and in three of them (conv1's pooling / requant, the heads, staging + depth map) the matrix
-// pipe has nothing to do while in the other two the vector ALUs idle: the counters show matrix and vector instructions co-executing in
-// only a third of the matrix-busy cycles.  Here every barrier interval pairs an MFMA-bound piece of one CTU with VALU-bound pieces of
-// its neighbours IN THE SAME WAVE, so the vector work sits in the shadow of the wave's own MFMA chain:
-//     X(k):  conv2(k)   ||  heads(k-1)  +  staging(k+1)  +  source Hadamard(k+1)          barrier
-//     Y(k):  conv3(k)   ||  conv1(k+1)  +  depth map(k-1)  +  prefetch(k+2)               barrier
-// Two barriers per CTU instead of four.  Every activation map has a region of its own (tile, A1, A2, A3 are all live in both
-// intervals): 76 800 B of LDS, two workgroups per CU, up to 256 VGPRs (conv3's and conv1's accumulators are live together).  The halos
-// are written once per kernel (no region is ever recycled for another map).
-//   hazards: conv2(k) reads A1(k) (written in Y(k-1)) and writes A2 (last read by conv3(k-1) in Y(k-1)); staging(k+1) writes the tile
-//   (last read by conv1(k) in Y(k-1)); heads(k-1) read A3(k-1) (written in Y(k-1)); conv3(k) writes A3 (last read in X(k)); conv1(k+1)
-//   writes A1 (last read in X(k)).  Logits: set k & 1 is initialised in Y(k), summed by heads(k) in X(k+1), read by the depth map in Y(k+1).
-struct LdsPipe {
-  static constexpr int A1_OFF = 0;                                // conv1 output [35][36][16 B] (a - 128), parity-split columns
-  static constexpr int A3_OFF = A1_OFF + 35 * A1_ROW;             // 20160: conv3 output [256][64 B], swizzled chunks
-  static constexpr int A2_OFF = A3_OFF + 16384;                   // 36544: conv2 output, 2 planes [18][18][16 B]
-  static constexpr int T_OFF = A2_OFF + 2 * A2_PLANE;             // 47296: input tile bf16 [33 row pairs][68 dwords] (+ conv1's one fragment read past it)
-  static constexpr int BIAS_OFF = T_OFF + 37 * IN_PITCH * 4;      // 57360: b1 (float) b2 b3 (int32)
-  static constexpr int LOGIT_OFF = BIAS_OFF + 112 * 4;            // 57808: two sets of 64 ints (as Lds::LOGIT_OFF [0..51])
-  static constexpr int HADS_OFF = LOGIT_OFF + 2 * 64 * 4;         // 58320: four sets of the four waves' source-Hadamard sums
-  static constexpr int HEADW_OFF = HADS_OFF + 16 * 4;             // 58384: wh64 (8192 B) + the MFMA image of wh32 / wh16 (10240 B)
-  static constexpr int LDS_BYTES = HEADW_OFF + 18432;             // 76816
-  static_assert(A3_OFF % 16 == 0 && A2_OFF % 16 == 0 && T_OFF % 16 == 0 && BIAS_OFF % 16 == 0 && LOGIT_OFF % 16 == 0 && HEADW_OFF % 16 == 0, "");
-  static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
-};
-#ifndef FHEVC_PIPE_RING3
-#define FHEVC_PIPE_RING3 4
-#endif
-#ifndef FHEVC_PIPE_SCHED_X
-#define FHEVC_PIPE_SCHED_X 9    // VALU instructions offered per (MFMA, fragment read) group of conv2's chains in interval X: Hadamard, heads, pools, requant
-#endif
-#ifndef FHEVC_PIPE_FENCE_Y
-#define FHEVC_PIPE_FENCE_Y 0    // 1: a hard sched_barrier after every step of interval Y instead of the group description: the interleave then
-#endif                          // holds in the ISA (7-8 VALU behind every MFMA) and the kernel gains 1.7 % (0.4066 against 0.4135 ms; default kernel 0.3827)
-#ifndef FHEVC_PIPE_SCHED_Y
-#define FHEVC_PIPE_SCHED_Y 10   // VALU instructions offered per conv3 MFMA step of interval Y (0: no pipeline description)
-#endif
-
-// top-down depth map of one CTU from its logits (the depth phase of the kernel above, as a function: the pipelined kernel needs it twice)
+// top-down depth map of one CTU from its logits (the depth phase of the kernel above, as a function for the kernels of the .inc files below)
 __device__ __forceinline__ void depth_map_of_ctu(const FhevcFrames& F, const int* logitL, const int* hads, int tid, int lane, int wave, int f, int cy, int cx,
                                                  int band_rows, int hb64a, int hb64b, int margin_split, int margin_stop, uint8_t* __restrict__ d_depth,
                                                  uint8_t* __restrict__ d_depth_max, int32_t* __restrict__ d_logits, uint32_t* __restrict__ d_flags,
@@ -1702,337 +1599,6 @@ __device__ __forceinline__ void depth_map_of_ctu(const FhevcFrames& F, const int
   }
 }
 
-template <int HAD, int ARITH>
-__global__ __launch_bounds__(256, 2) void fhevc_cnn_depth_pipe_kernel(FhevcFrames F, FhevcCnnWeights W, uint8_t* __restrict__ d_depth, int32_t* __restrict__ d_had,
-                                                                       int32_t* __restrict__ d_logits, uint32_t* __restrict__ d_flags,
-                                                                       uint8_t* __restrict__ d_depth_max, int margin_split, int margin_stop)
-{
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  __builtin_amdgcn_s_setreg((1 << 11) | 1, 2);  // fp32 rounding toward -inf: v_cvt_pk_u8_f32 = floor + clamp (conv1's requant); see the kernel above
-  using P = LdsPipe;
-  constexpr bool FASTRQ = ARITH == 2;
-  constexpr int RING3P = FHEVC_PIPE_RING3;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int hb64a = W.bhead[0], hb64b = W.bhead[1] + W.bhead[6 + 0 * 52 + F.qp];
-  const int hb32a = W.bhead[2], hb32b = W.bhead[3] + W.bhead[6 + 1 * 52 + F.qp];
-  const int hb16a = W.bhead[4], hb16b = W.bhead[5] + W.bhead[6 + 2 * 52 + F.qp];
-  // ---- resident weight fragments: 8 + 24 + 36 registers ----
-  const bf16x8 wA1a = __builtin_bit_cast(bf16x8, W.frag[FHEVC_FRAG_CONV1 + lane]);
-  const bf16x8 wA1b = __builtin_bit_cast(bf16x8, W.frag[FHEVC_FRAG_CONV1 + 64 + lane]);
-  bf16x8 wA2[9], wA3[18];
-  const int tile3 = wave & 1;
-#pragma unroll
-  for (int s = 0; s < 6; ++s) wA2[s] = __builtin_bit_cast(bf16x8, W.frag_i8[FHEVC_FRAGI8_CONV2 + s * 64 + lane]);
-#pragma unroll
-  for (int s = 0; s < 9; ++s) wA3[s] = __builtin_bit_cast(bf16x8, W.frag_i8[FHEVC_FRAGI8_CONV3 + (tile3 * 9 + s) * 64 + lane]);
-  const int shift2 = W.shift[1], shift3 = W.shift[2];
-
-  float* biasL = reinterpret_cast<float*>(lds + P::BIAS_OFF);
-  int* logit0 = reinterpret_cast<int*>(lds + P::LOGIT_OFF);
-  int* hadsL = reinterpret_cast<int*>(lds + P::HADS_OFF);
-  if (tid < 112) {
-    if (tid >= 16) reinterpret_cast<int*>(biasL)[tid] = W.bias_i8[tid];
-    else biasL[tid] = W.bias[tid] * W.scale[0];
-  }
-  // wh64 with its chunk swizzle, and the MFMA image of wh32 / wh16 (as in the kernel above)
-  for (int i = tid; i < 8192 / 16; i += 256) {
-    const int row = i >> 2, c = i & 3, sw = (row >> 3) & 3;
-    *reinterpret_cast<uint4*>(lds + P::HEADW_OFF + row * 64 + ((c ^ sw) << 4)) = reinterpret_cast<const uint4*>(W.whead)[i];
-  }
-  for (int i = tid; i < HEADM_BYTES / 16; i += 256) {
-    const int j = i / 40, rem = i - j * 40, n = rem >> 2, kg = rem & 3;
-    int src;
-    if (n < 2) src = 16384 + (n * 16 + j) * 64;
-    else {
-      const int sub = (n - 2) >> 1, cls = n & 1, py = j >> 2, px = j & 3;
-      src = 8192 + (cls * 64 + ((sub >> 1) * 4 + py) * 8 + (sub & 1) * 4 + px) * 64;
-    }
-    *reinterpret_cast<uint4*>(lds + P::HEADW_OFF + HEADM_OFF + i * 16) = *reinterpret_cast<const uint4*>(W.whead + src + kg * 16);
-  }
-  // the halos, once: "activation 0" (0x80) everywhere in A1 and A2, bf16(128) everywhere in the tile; the interiors are rewritten per CTU
-  for (int i = tid; i < (35 * A1_ROW) / 16; i += 256) *reinterpret_cast<uint4*>(lds + P::A1_OFF + i * 16) = make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);
-  for (int i = tid; i < (2 * A2_PLANE) / 16; i += 256) *reinterpret_cast<uint4*>(lds + P::A2_OFF + i * 16) = make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);
-  for (int i = tid; i < (37 * IN_PITCH * 4) / 16; i += 256) *reinterpret_cast<uint4*>(lds + P::T_OFF + i * 16) = make_uint4(0x43004300u, 0x43004300u, 0x43004300u, 0x43004300u);
-  if (tid < 128 + 16) logit0[tid] = 0;
-  __syncthreads();  // the fills above and the first staging below write the same tile cells from different threads
-
-  const int band_rows = F.row_end - F.row_begin;
-  const int per_frame = band_rows * F.ctus_x;
-  const int total = per_frame * F.num_frames;
-  const int shift_in = F.bit_depth - 8;
-  const int ld_row = tid >> 2, ld_seg = tid & 3;
-  const int grid = (int)gridDim.x;
-  const int vblock = (grid & 7) ? (int)blockIdx.x : (int)((blockIdx.x & 7) * (grid >> 3) + (blockIdx.x >> 3));
-  CtuPos pos, step;
-  {
-    const int vb = min(vblock, total - 1);
-    pos.f = vb / per_frame; pos.ry = (vb - pos.f * per_frame) / F.ctus_x; pos.cx = (vb - pos.f * per_frame) - pos.ry * F.ctus_x;
-    step.f = grid / per_frame; step.ry = (grid - step.f * per_frame) / F.ctus_x; step.cx = (grid - step.f * per_frame) - step.ry * F.ctus_x;
-  }
-  // heads: per-thread LDS rows (as in the kernel above)
-  uint2 head_addr;
-  {
-    const int q = wave, blk = lane >> 4;
-    const int y = (q >> 1) * 8 + (blk >> 1) * 4 + ((lane >> 2) & 3), x = (q & 1) * 8 + (blk & 1) * 4 + (lane & 3);
-    const unsigned psw = (x >> 2) & 3, sw64 = (y >> 1) & 3;
-    const unsigned a_0 = (unsigned)(y * 16 + x) * 64 + (psw << 4);
-    const unsigned w64_0 = (unsigned)((y >> 1) * 8 + (x >> 1)) * 64 + (sw64 << 4);
-    head_addr = make_uint2(a_0, w64_0);
-  }
-  unsigned headm_addr;
-  {
-    const int m = lane & 15, kg = lane >> 4, by = m >> 2, bx = m & 3;
-    const unsigned am = (unsigned)((4 * by + wave) * 16 + 4 * bx) * 64 + ((unsigned)(kg ^ bx) << 4);
-    const unsigned bm = (unsigned)(HEADM_OFF + 4 * wave * HEADM_STEP + min(m, 9) * 64 + 16 * kg);
-    headm_addr = am | (bm << 16);
-  }
-  // ---- the pieces ----
-  // conv1 of the CTU whose samples sit in the tile: T -> A1 (8 units = pooled rows wave, wave + 4, ..: see P1 of the kernel above)
-  f32x16 bias1;
-  {
-    const float4 b0 = *reinterpret_cast<const float4*>(W.bias + 8 * h), b1 = *reinterpret_cast<const float4*>(W.bias + 8 * h + 4);
-    const float sc = W.scale[0];
-    bias1[0] = b0.x * sc; bias1[1] = b0.y * sc; bias1[2] = b0.z * sc; bias1[3] = b0.w * sc;
-    bias1[4] = b1.x * sc; bias1[5] = b1.y * sc; bias1[6] = b1.z * sc; bias1[7] = b1.w * sc;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) bias1[8 + i] = bias1[i];
-  }
-  auto frag1 = [](const unsigned char* p) {
-    const uint2 lo = *reinterpret_cast<const uint2*>(p);
-    const uint2 hi = *reinterpret_cast<const uint2*>(p + IN_PITCH * 4);
-    return __builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
-  };
-  const unsigned char* c1_in = lds + P::T_OFF + (2 * r + 2 * h) * 4 + wave * (IN_PITCH * 4);
-  unsigned char* c1_out = lds + P::A1_OFF + 8 * h + (wave + 1) * A1_ROW + (((r + 1) & 1) ? 0 : A1_EVEN) + ((r + 1) >> 1) * 16;
-#define FHEVC_PIPE_CONV1_UNIT(i)                                                                                   \
-  {                                                                                                                \
-    const bf16x8 bq_ = frag1(c1_in + (i) * (4 * IN_PITCH * 4));                                                    \
-    const f32x16 acc0_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wA1a, bq_, bias1, 0, 0, 0);                       \
-    const f32x16 acc1_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wA1b, bq_, bias1, 0, 0, 0);                       \
-    conv1_store_i8(acc0_, acc1_, c1_out + (i) * (4 * A1_ROW));                                                     \
-  }
-  // conv2: A1 -> A2 (lane -> pooled position and units as in P2 of the kernel above)
-  const int q2 = r >> 2;
-  const int pr2 = (q2 ^ (q2 >> 1) ^ (q2 >> 2)) & 1, pc2 = ((r >> 3) << 2) | (r & 3);
-  const unsigned char* a1p = lds + P::A1_OFF + (2 * pr2 + h) * A1_ROW + pc2 * 16;
-  unsigned char* a2dst = lds + P::A2_OFF + ((pr2 + 1) * A2_PITCH + pc2 + 1) * 16 + 4 * h;
-  const int* b2t = reinterpret_cast<const int*>(biasL) + 16;
-  // conv3: A2 -> A3 (B column n = lane & 31: row 8 rs of the pair, position x; lane half = activation plane)
-  const int x3 = lane & 15, rs3 = (lane >> 4) & 1, y03 = 2 * (wave >> 1);
-  const unsigned char* a2 = lds + P::A2_OFF + h * A2_PLANE + ((y03 + 8 * rs3) * A2_PITCH + x3) * 16;
-  const int psw3 = (x3 >> 2) & 3;
-  unsigned char* a3dst = lds + P::A3_OFF + ((y03 + 8 * rs3) * 16 + x3) * 64 + 4 * h;
-  const int* b3p = reinterpret_cast<const int*>(biasL) + 48 + 32 * tile3;
-
-  // ---- prologue: first CTU staged, its conv1 done, the second CTU's samples in flight ----
-  CtuPos p_prev = pos, p_cur = pos, p_next = advance(pos, step, band_rows, F.ctus_x);   // c(k-1), c(k), c(k+1)
-  Prefetched pre = prefetch_ctu<HAD == 1>(F, vblock < total, p_cur, ld_row, ld_seg);
-  if (vblock < total) {
-    stage_ctu<false>(lds, P::T_OFF, pre, F, p_cur, tid, ld_row, ld_seg, shift_in, 0u);
-    if (HAD == 1) {
-      const int hs = F.sample_bytes == 2 ? wave_src_hadamard<2>(pre, lane) : wave_src_hadamard<1>(pre, lane);
-      if (lane == 0) hadsL[wave] = hs;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 8; ++i) FHEVC_PIPE_CONV1_UNIT(i)
-  pre = prefetch_ctu<HAD == 1>(F, vblock + grid < total, p_next, ld_row, ld_seg);
-  __syncthreads();
-
-  int k = 0;
-  for (int work = vblock; work < total; work += grid, ++k) {
-    const CtuPos p_next2 = advance(p_next, step, band_rows, F.ctus_x);
-    const bool have_next = work + grid < total;
-    int* logit_prev = logit0 + 64 * ((k + 1) & 1);   // set (k - 1) & 1: heads(k-1) add to it in X(k), the depth map reads it in Y(k)
-    int* logit_cur = logit0 + 64 * (k & 1);          // set k & 1: initialised in Y(k)
-    // ================= X(k): staging(k+1) + Hadamard(k+1), then conv2(k) with heads(k-1) in its shadow =================
-    unsigned hr[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };  // the next CTU's samples for the source Hadamard (zeros: no next CTU, or not through the aligned path)
-    if (have_next) {
-      stage_ctu<false>(lds, P::T_OFF, pre, F, p_next, tid, ld_row, ld_seg, shift_in, 0u);
-      if (HAD == 1) {
-        if (F.sample_bytes == 2) hadamard_samples<2>(pre, hr); else hadamard_samples<1>(pre, hr);
-      }
-    }
-    {
-      // source Hadamard(k+1): straight-line VALU work in the shadow of conv2's MFMAs (the set's write is harmless without a next CTU)
-      if (HAD == 1) {
-        const int hs = wave_src_hadamard_core(hr, lane);
-        hadsL[4 * ((k + 1) & 3) + wave] = hs;   // every lane holds the wave's sum: 64 lanes, one address, one value
-      }
-      // heads(k-1): 16- and 32-level heads as ONE GEMM on v_mfma_i32_16x16x64_i8, 64-level head on v_dot4_i32_i8 (P4 of the kernel above)
-      const unsigned char* hw = lds + P::HEADW_OFF;
-      const unsigned char* ap = lds + P::A3_OFF + (headm_addr & 0xFFFFu);
-      const unsigned char* bp = hw + (headm_addr >> 16);
-      i32x4 hacc = { 0, 0, 0, 0 };
-#pragma unroll
-      for (int px = 0; px < 4; ++px)
-        hacc = __builtin_amdgcn_mfma_i32_16x16x64_i8(*reinterpret_cast<const i32x4*>(ap + px * 64), *reinterpret_cast<const i32x4*>(bp + px * HEADM_STEP), hacc, 0, 0, 0);
-      int s64a = 0, s64b = 0;
-#pragma unroll
-      for (int qq = 0; qq < 4; ++qq) {
-        const uint4 a = *reinterpret_cast<const uint4*>(lds + P::A3_OFF + (head_addr.x ^ (qq << 4)));
-        const unsigned char* w64 = hw + HEAD64_OFF + (head_addr.y ^ (qq << 4));
-        const uint4 d0 = *reinterpret_cast<const uint4*>(w64), d1 = *reinterpret_cast<const uint4*>(w64 + 4096);
-        s64a = sdot4(a.x, d0.x, s64a); s64a = sdot4(a.y, d0.y, s64a); s64a = sdot4(a.z, d0.z, s64a); s64a = sdot4(a.w, d0.w, s64a);
-        s64b = sdot4(a.x, d1.x, s64b); s64b = sdot4(a.y, d1.y, s64b); s64b = sdot4(a.z, d1.z, s64b); s64b = sdot4(a.w, d1.w, s64b);
-      }
-      // conv2(k): four half-chains (u0 dy 0, u0 dy 1, u1 dy 0, u1 dy 1), pools and requants under the following chains
-      const int u0 = wave, u1 = wave + 4;
-      const unsigned char* h00 = a1p + (4 * u0) * A1_ROW;
-      const unsigned char* h10 = a1p + (4 * u1) * A1_ROW;
-      i32x16 t0, t1, a0, a1;
-      bf16x8 ring[RINGI];
-      const int c2l = conv2_lane_i8(h);
-      conv2_half_i8<true, false, 0>(h00, h00 + A1_ROW, c2l, wA2, ring, b2t, h, t0, t1);
-      __builtin_amdgcn_sched_group_barrier(0x100, RINGI + 4, 0);
-      sched_chain12_i8<FHEVC_PIPE_SCHED_X>();
-      conv2_half_i8<false, false, C2F % RINGI>(h00 + A1_ROW, h10, c2l, wA2, ring, b2t, h, a0, a1);
-      pool_h_i8(t0, t1);
-      sched_chain12_i8<FHEVC_PIPE_SCHED_X>();
-      pool_v_i8(t0, a0, a1);
-      conv2_half_i8<false, false, (2 * C2F) % RINGI>(h10, h10 + A1_ROW, c2l, wA2, ring, b2t, h, t1, a0);
-      conv2_requant_store_i8m<FASTRQ ? 1 : 0>(t0, a2dst + (2 * u0) * A2_PITCH * 16, shift2);
-      sched_chain12_i8<FHEVC_PIPE_SCHED_X>();
-      conv2_half_i8<false, true, (3 * C2F) % RINGI>(h10 + A1_ROW, h10 + A1_ROW, c2l, wA2, ring, b2t, h, a1, t0);
-      pool_h_i8(t1, a0);
-      sched_chain12_i8<FHEVC_PIPE_SCHED_X>();
-      pool_v_i8(t1, a1, t0);
-      conv2_requant_store_i8m<FASTRQ ? 1 : 0>(t1, a2dst + (2 * u1) * A2_PITCH * 16, shift2);
-      // the heads' partial sums join the logits of set (k - 1) & 1
-      {
-        const int n = lane & 15, rg = lane >> 4, subn = (n - 2) >> 1;
-        const bool is16 = n < 2, is32 = n >= 2 && n < 10 && ((rg & 1) == (subn >> 1));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const bool act = is16 || (is32 && ((i & 1) == (subn & 1)));
-          const int idx = is16 ? 2 * (5 + 4 * rg + i) + n : 2 * (1 + (rg >> 1) * 2 + (i >> 1)) + (n & 1);
-          if (act) atomicAdd(logit_prev + idx, hacc[i]);
-        }
-      }
-      const int r64a = dpp_row_sum(s64a), r64b = dpp_row_sum(s64b);
-      const int q64a = __builtin_amdgcn_readlane(r64a, 0) + __builtin_amdgcn_readlane(r64a, 16) + __builtin_amdgcn_readlane(r64a, 32) + __builtin_amdgcn_readlane(r64a, 48);
-      const int q64b = __builtin_amdgcn_readlane(r64b, 0) + __builtin_amdgcn_readlane(r64b, 16) + __builtin_amdgcn_readlane(r64b, 32) + __builtin_amdgcn_readlane(r64b, 48);
-      if (lane == 0) *reinterpret_cast<int2*>(logit_prev + 44 + 2 * wave) = make_int2(q64a, q64b);
-    }
-    __syncthreads();
-    // ================= Y(k): depth map(k-1), prefetch(k+2), then conv3(k) with conv1(k+1) in its shadow =================
-    if (k >= 1)
-      depth_map_of_ctu(F, logit_prev, hadsL + 4 * ((k - 1) & 3), tid, lane, wave, p_prev.f, F.row_begin + p_prev.ry, p_prev.cx, band_rows, hb64a, hb64b,
-                       margin_split, margin_stop, d_depth, d_depth_max, d_logits, d_flags, d_had, HAD == 1);
-    if (tid < 40) logit_cur[2 + tid] = tid < 8 ? ((tid & 1) ? hb32b : hb32a) : ((tid & 1) ? hb16b : hb16a);
-    pre = prefetch_ctu<HAD == 1>(F, work + 2 * grid < total, p_next2, ld_row, ld_seg);
-    {
-      // conv3(k)'s 36 MFMAs in program order j = 0..35 (super-chain j / 18: accumulators p0 / p1, then q0 / q1; tap (j % 18) / 2), one
-      // fragment read ahead per MFMA.  conv1(k+1)'s eight units are cut into slices and dealt over those steps so that every MFMA has
-      // a few VALU instructions behind it: unit u's two MFMAs go out before step 9u / 2, its pooling (2 x 8 v_max3 / v_max) after the
-      // next two steps, requant + store after the third.  The requant of p0 / p1 (four 5-instruction groups each) follows their chain
-      // in the same way; only q0 / q1's requant is left for the tail of the interval.
-      bf16x8 ring[RING3P];
-      i32x16 p0, p1, q0, q1;
-      f32x16 c1a, c1b;
-      float c1m[8];
-#pragma unroll
-      for (int g = 0; g < RING3P; ++g) ring[g] = lds_frag(a2 + conv3_frag_off_i8(g));
-      static_for<0, 36>([&](auto J) {
-        constexpr int j = decltype(J)::value;
-        constexpr int t = (j % 18) >> 1;
-        if constexpr (j == 0) { const i32x16 binit = bias_tile_i8(b3p, h); p0 = binit; p1 = binit; }
-        if constexpr (j == 18) { const i32x16 binit = bias_tile_i8(b3p, h); q0 = binit; q1 = binit; }
-        static_for<0, 8>([&](auto U) {
-          constexpr int u = decltype(U)::value;
-          if constexpr (j == (9 * u) / 2) {
-            const bf16x8 bq_ = frag1(c1_in + u * (4 * IN_PITCH * 4));
-            c1a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wA1a, bq_, bias1, 0, 0, 0);
-            c1b = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wA1b, bq_, bias1, 0, 0, 0);
-          }
-        });
-        if constexpr (j < 18) { if constexpr (j & 1) p1 = mfma_i8(wA3[t], ring[j % RING3P], p1); else p0 = mfma_i8(wA3[t], ring[j % RING3P], p0); }
-        else { if constexpr (j & 1) q1 = mfma_i8(wA3[t], ring[j % RING3P], q1); else q0 = mfma_i8(wA3[t], ring[j % RING3P], q0); }
-        if constexpr (j + RING3P < 36) ring[j % RING3P] = lds_frag(a2 + conv3_frag_off_i8(j + RING3P));
-        static_for<0, 8>([&](auto U) {
-          constexpr int u = decltype(U)::value;
-          constexpr int j0 = (9 * u) / 2;
-          if constexpr (j == j0 + 1) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) c1m[c] = fmaxf(fmaxf(c1a[c], c1a[c + 8]), fmaxf(c1b[c], c1b[c + 8]));
-          }
-          if constexpr (j == j0 + 2) {
-#pragma unroll
-            for (int c = 4; c < 8; ++c) c1m[c] = fmaxf(fmaxf(c1a[c], c1a[c + 8]), fmaxf(c1b[c], c1b[c + 8]));
-          }
-          if constexpr (j == j0 + 3)
-            *reinterpret_cast<uint2*>(c1_out + u * (4 * A1_ROW)) = make_uint2(u8x4_floor_clamp(c1m[0], c1m[1], c1m[2], c1m[3]) ^ 0x80808080u,
-                                                                               u8x4_floor_clamp(c1m[4], c1m[5], c1m[6], c1m[7]) ^ 0x80808080u);
-        });
-        // requant of super-chain 0's accumulators, one group of four channels per step: p0 after steps 19..22, p1 after 23..26
-        if constexpr (j >= 19 && j < 27) {
-          constexpr int g = (j - 19) & 3;
-          const i32x16& acc = j < 23 ? p0 : p1;
-          unsigned char* dst = a3dst + conv3_pair_row_i8(j < 23 ? 0 : 1) * 1024;
-          *reinterpret_cast<unsigned*>(dst + (((2 * tile3 + (g >> 1)) ^ psw3) << 4) + 8 * (g & 1)) =
-              requant4_i8(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3], shift3, FASTRQ ? 2 : 0);
-        }
-        // the pipeline description of this step: its MFMA(s) and fragment read(s), then the slices' VALU work and their one LDS store
-        if (FHEVC_PIPE_FENCE_Y) __builtin_amdgcn_sched_barrier(0);  // nothing moves across a step boundary: the slices stay where they were dealt
-        else if (FHEVC_PIPE_SCHED_Y) {
-          constexpr bool issue = (j % 9 == 0) || (j % 9 == 4);  // steps 0, 4, 9, 13, 18, 22, 27, 31: a conv1 unit's two MFMAs and two ds_read_b64 go out first
-          __builtin_amdgcn_sched_group_barrier(0x100, issue ? 3 : 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, issue ? 3 : 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, FHEVC_PIPE_SCHED_Y, 0);
-          __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-        }
-      });
-      conv3_store_i8m<FASTRQ ? 2 : 0>(q0, a3dst + conv3_pair_row_i8(2) * 1024, tile3, psw3, shift3);
-      conv3_store_i8m<FASTRQ ? 2 : 0>(q1, a3dst + conv3_pair_row_i8(3) * 1024, tile3, psw3, shift3);
-    }
-    __syncthreads();
-    p_prev = p_cur; p_cur = p_next; p_next = p_next2;
-  }
-  // ================= drain: heads and depth map of the last CTU =================
-  if (k >= 1) {
-    int* logit_prev = logit0 + 64 * ((k + 1) & 1);
-    {
-      const unsigned char* hw = lds + P::HEADW_OFF;
-      const unsigned char* ap = lds + P::A3_OFF + (headm_addr & 0xFFFFu);
-      const unsigned char* bp = hw + (headm_addr >> 16);
-      i32x4 hacc = { 0, 0, 0, 0 };
-#pragma unroll
-      for (int px = 0; px < 4; ++px)
-        hacc = __builtin_amdgcn_mfma_i32_16x16x64_i8(*reinterpret_cast<const i32x4*>(ap + px * 64), *reinterpret_cast<const i32x4*>(bp + px * HEADM_STEP), hacc, 0, 0, 0);
-      int s64a = 0, s64b = 0;
-#pragma unroll
-      for (int qq = 0; qq < 4; ++qq) {
-        const uint4 a = *reinterpret_cast<const uint4*>(lds + P::A3_OFF + (head_addr.x ^ (qq << 4)));
-        const unsigned char* w64 = hw + HEAD64_OFF + (head_addr.y ^ (qq << 4));
-        const uint4 d0 = *reinterpret_cast<const uint4*>(w64), d1 = *reinterpret_cast<const uint4*>(w64 + 4096);
-        s64a = sdot4(a.x, d0.x, s64a); s64a = sdot4(a.y, d0.y, s64a); s64a = sdot4(a.z, d0.z, s64a); s64a = sdot4(a.w, d0.w, s64a);
-        s64b = sdot4(a.x, d1.x, s64b); s64b = sdot4(a.y, d1.y, s64b); s64b = sdot4(a.z, d1.z, s64b); s64b = sdot4(a.w, d1.w, s64b);
-      }
-      {
-        const int n = lane & 15, rg = lane >> 4, subn = (n - 2) >> 1;
-        const bool is16 = n < 2, is32 = n >= 2 && n < 10 && ((rg & 1) == (subn >> 1));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const bool act = is16 || (is32 && ((i & 1) == (subn & 1)));
-          const int idx = is16 ? 2 * (5 + 4 * rg + i) + n : 2 * (1 + (rg >> 1) * 2 + (i >> 1)) + (n & 1);
-          if (act) atomicAdd(logit_prev + idx, hacc[i]);
-        }
-      }
-      const int r64a = dpp_row_sum(s64a), r64b = dpp_row_sum(s64b);
-      const int q64a = __builtin_amdgcn_readlane(r64a, 0) + __builtin_amdgcn_readlane(r64a, 16) + __builtin_amdgcn_readlane(r64a, 32) + __builtin_amdgcn_readlane(r64a, 48);
-      const int q64b = __builtin_amdgcn_readlane(r64b, 0) + __builtin_amdgcn_readlane(r64b, 16) + __builtin_amdgcn_readlane(r64b, 32) + __builtin_amdgcn_readlane(r64b, 48);
-      if (lane == 0) *reinterpret_cast<int2*>(logit_prev + 44 + 2 * wave) = make_int2(q64a, q64b);
-    }
-    __syncthreads();
-    depth_map_of_ctu(F, logit_prev, hadsL + 4 * ((k - 1) & 3), tid, lane, wave, p_prev.f, F.row_begin + p_prev.ry, p_prev.cx, band_rows, hb64a, hb64b,
-                     margin_split, margin_stop, d_depth, d_depth_max, d_logits, d_flags, d_had, HAD == 1);
-  }
-#undef FHEVC_PIPE_CONV1_UNIT
-}
-
 #include "k_cnn_family.inc"
 #include "k_cnn_layers.inc"
 #include "k_cnn_d2.inc"
@@ -2083,11 +1649,7 @@ hipError_t fhevc_cnn_prepare_device()
   if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fhevc_cnn_depth_kernel<false, 2, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, Lds<false>::LDS_BYTES);
   if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fhevc_cnn_family_kernel<32, 64, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, LdsFam<32, 64, 128>::LDS_BYTES);
   if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fhevc_cnn_family_kernel<16, 32, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, LdsFam<16, 32, 64>::LDS_BYTES);
-  // (the i8 variant's 51 072 B need no opt-in; its pipelined form's 76 816 B do)
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fhevc_cnn_depth_pipe_kernel<0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, LdsPipe::LDS_BYTES);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fhevc_cnn_depth_pipe_kernel<1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, LdsPipe::LDS_BYTES);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fhevc_cnn_depth_pipe_kernel<0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, LdsPipe::LDS_BYTES);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fhevc_cnn_depth_pipe_kernel<1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, LdsPipe::LDS_BYTES);
+  // (the i8 variant's 51 072 B need no opt-in)
   // the layer kernels that stage a 32 x 32 map of up to 64 channels (+ halo) in LDS: 34 x 34 x 64 B = 73 984 B
 #define FHEVC_LAYER_LDS(KCV) \
   if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fhevc_layer_conv_kernel<KCV, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); \
@@ -2169,23 +1731,12 @@ hipError_t fhevc_launch_cnn(const FhevcFrames& fr, const FhevcCnnWeights& w, uin
   // the fused source Hadamard's form: on the MFMA from the staged tile for 8-bit content (the tile IS the samples), on packed
   // 16-bit VALU from the prefetched samples otherwise (the tile is rounded to 8 bits); w.had_valu forces the latter (A/B, tests)
   const int had = d_had == nullptr ? 0 : (fr.bit_depth == 8 && !w.had_valu) ? 2 : 1;
-  if (knobs.trio && !knobs.wg_per_cu && !w.pipe && cnn_arith(w) == 2 && had != 2) {  // three groups behind common barriers, one interval apart: one workgroup per CU
+  if (knobs.trio && !knobs.wg_per_cu && cnn_arith(w) == 2 && had != 2) {  // three groups behind common barriers, one interval apart: one workgroup per CU
     const int tgrid = (int)std::min<long long>(num_cus, (total + 2) / 3);
 #define FHEVC_LAUNCH_TRIO(HAD) hipLaunchKernelGGL((fhevc_cnn_depth_kernel<false, HAD, 2, 1>), dim3(tgrid), dim3(768), 3 * Lds<true>::LDS_BYTES, stream, fr, w, d_depth, d_had, \
                                                   d_logits, d_flags, nullptr, d_depth_max, margin_split, margin_stop)
     if (had) FHEVC_LAUNCH_TRIO(1); else FHEVC_LAUNCH_TRIO(0);
 #undef FHEVC_LAUNCH_TRIO
-    return hipGetLastError();
-  }
-  if (w.i8 && w.pipe && had != 2) {  // the software-pipelined form of the i8 kernel: two workgroups per CU
-    int pgrid = 2 * num_cus;
-    if (knobs.wg_per_cu == 1) pgrid = num_cus;
-    if (total < pgrid) pgrid = (int)total;
-#define FHEVC_LAUNCH_PIPE(HAD, ARITH) hipLaunchKernelGGL((fhevc_cnn_depth_pipe_kernel<HAD, ARITH>), dim3(pgrid), dim3(256), LdsPipe::LDS_BYTES, stream, fr, w, d_depth, d_had, \
-                                                         d_logits, d_flags, d_depth_max, margin_split, margin_stop)
-    if (cnn_arith(w) == 2) { if (had) FHEVC_LAUNCH_PIPE(1, 2); else FHEVC_LAUNCH_PIPE(0, 2); }
-    else { if (had) FHEVC_LAUNCH_PIPE(1, 1); else FHEVC_LAUNCH_PIPE(0, 1); }
-#undef FHEVC_LAUNCH_PIPE
     return hipGetLastError();
   }
 #define FHEVC_LAUNCH_HAD(ARITH) do { if (had == 2) FHEVC_LAUNCH(2, ARITH); else if (had == 1) FHEVC_LAUNCH(1, ARITH); else FHEVC_LAUNCH(0, ARITH); } while (0)

@@ -22,9 +22,6 @@
 #ifndef FHEVC_D2_RING
 #define FHEVC_D2_RING 6
 #endif
-#ifndef FHEVC_D2_SKIP
-#define FHEVC_D2_SKIP 0   // (timing experiments only, WRONG results: bit 0 conv1a, 1 conv1b, 2 conv2a, 3 conv2b, 4 conv3a, 5 conv3b, 6 heads skipped)
-#endif
 constexpr int D2_RING = FHEVC_D2_RING;
 constexpr int D2_TILE_PITCH = 96, D2_TILE_X0 = 16;   // sample x of tile row r (halo coordinates 0 .. 65) at byte r * 96 + 16 + x, x = -1 .. 64
 
@@ -34,9 +31,6 @@ __host__ __device__ constexpr int d2_pad(int kc, bool pool, int H, bool want_mas
   // the table of fhevc_layer_lds_image (k_cnn.hip; tools/lds_swizzle_search.py) as a constant expression: (pad bytes, mask) that make the B-fragment reads of a
   // (kc, pool, H) layer free of bank conflicts.  Unlike the layer path, EVERY image uses its entry: here all of a CTU's traffic is LDS traffic, and the plain
   // 32- and 96-channel images (two and four ways conflicted) made 35 % of the LDS-active cycles conflict cycles (profiles/r04_pmc_d2_kernel.json)
-#if defined(FHEVC_D2_PLAIN)
-  if (!(kc == 2 || kc == 4 || (kc == 3 && pool))) return 0;   // (A/B: the layer path's choice)
-#endif
   const int hi = H == 16 ? 0 : (H == 32 ? 1 : 2);
   constexpr int T[4][2][3][2] = {
     { { { 16, 0 }, { 0, 1 }, { 0, 1 } }, { { 192, 3 }, { 16, 1 }, { 0, 3 } } },
@@ -445,7 +439,7 @@ __global__ __launch_bounds__(512, 2) void fhevc_cnn_d2_kernel(FhevcFrames F, Fhe
     d2_weights<KC1, KC1>(L1b.frag, L1b.bias, w1b, b1b);           // the second convolution's weights travel under the first convolution's first strip
 #pragma unroll 1
     for (int s = 0; s < 2; ++s) {
-      if (!(FHEVC_D2_SKIP & 1)) {
+      {
         // rows y0 .. y0 + 33 (halo coordinates) of the first convolution's output into S.  The cells outside the map -- row 0 (first strip) or 65 (second strip)
         // and the two halo columns of every row -- are "activation 0", written by the first threads of the workgroup; the 33 rows inside the map are one MFMA
         // per 32 positions (K = the nine taps), requant, one 16-byte store per lane.  The tile loop is free of branches: the wave index is made scalar
@@ -491,15 +485,12 @@ __global__ __launch_bounds__(512, 2) void fhevc_cnn_d2_kernel(FhevcFrames F, Fhe
           // the window: rows r - 1 .. r + 1 (halo coordinates), columns x - 1 .. x + 1 = three bytes from byte a = X0 - 1 + x of three tile rows.  Read as the two
           // ALIGNED dwords around a per row + v_alignbyte (sub-dword LDS reads, ds_read_u8 / _u16, cost this phase ~750 cycles per tile: 22 k of its 23 k cycles
           // per CTU went away with them in a sensitivity build), then two v_perm put the nine taps into K slots 0 .. 8; what lands in slots 9 .. 15 meets zero weights
-#ifndef FHEVC_D2_C1A_X
-#define FHEVC_D2_C1A_X 0   // (sensitivity experiments, WRONG results: 1 no window reads, 2 no requant / store, 4 no MFMA)
-#endif
           const unsigned a = (unsigned)((r - 1) * D2_TILE_PITCH + D2_TILE_X0 - 1 + xs + n);
           const unsigned* qd = reinterpret_cast<const unsigned*>(tile + (a & ~3u));
           unsigned rw[3];
 #pragma unroll
           for (int k = 0; k < 3; ++k) {
-            const unsigned lo = (FHEVC_D2_C1A_X & 1) ? (unsigned)(n + k) : qd[k * (D2_TILE_PITCH / 4)], hi = (FHEVC_D2_C1A_X & 1) ? (unsigned)(n - k) : qd[k * (D2_TILE_PITCH / 4) + 1];
+            const unsigned lo = qd[k * (D2_TILE_PITCH / 4)], hi = qd[k * (D2_TILE_PITCH / 4) + 1];
             rw[k] = __builtin_amdgcn_alignbyte(hi, lo, a & 3u);
           }
           uint4 bq;
@@ -510,19 +501,15 @@ __global__ __launch_bounds__(512, 2) void fhevc_cnn_d2_kernel(FhevcFrames F, Fhe
           const unsigned row = (unsigned)lr * (unsigned)P::S_PITCH;
 #pragma unroll
           for (int m0 = 0; m0 < KC1; ++m0) {
-            i32x16 a0 = b0[m0];
-            if (FHEVC_D2_C1A_X & 4) { a0[0] += (int)bq.x; a0[5] += (int)bq.y; a0[9] += (int)bq.z; }
-            else a0 = mfma_i8(f0[m0], __builtin_bit_cast(bf16x8, bq), b0[m0]);
-            if (FHEVC_D2_C1A_X & 2) { if (a0[0] + a0[5] + a0[9] == 0x12345678) big[row] = 1; }
-            else layer_store16<RQA>(a0, big + d2_swz(row + (unsigned)(xs + n + 1) * P::PX1 + m0 * 32 + 16 * h, P::S_MASK), L1a.shift);
+            const i32x16 a0 = mfma_i8(f0[m0], __builtin_bit_cast(bf16x8, bq), b0[m0]);
+            layer_store16<RQA>(a0, big + d2_swz(row + (unsigned)(xs + n + 1) * P::PX1 + m0 * 32 + 16 * h, P::S_MASK), L1a.shift);
           }
         }
       }
       D2_STAMP(0)   // conv1a
       __syncthreads();
       D2_STAMP(1)   // barrier wait
-      if (!(FHEVC_D2_SKIP & 2))
-        d2_conv<KC1, KC1, true, 64, 32, P::S_PITCH, P::S_MASK, P::PX1, P::A1_PITCH, P::A1_MASK, true, RQB>(big, 32 * s, ra, 32 * s, w1b, b1b, L1b.shift, []() {});
+      d2_conv<KC1, KC1, true, 64, 32, P::S_PITCH, P::S_MASK, P::PX1, P::A1_PITCH, P::A1_MASK, true, RQB>(big, 32 * s, ra, 32 * s, w1b, b1b, L1b.shift, []() {});
       D2_STAMP(2)   // conv1b
       __syncthreads();
       D2_STAMP(1)
@@ -532,16 +519,13 @@ __global__ __launch_bounds__(512, 2) void fhevc_cnn_d2_kernel(FhevcFrames F, Fhe
     // the chains; in block 1 the hook fits only with the strip loop unrolled, and that build measured 3 % slower)
     d2_weights<KC1, KC2>(L2a.frag, L2a.bias, w2a, b2a);
     d2_fill_halo<32, P::PX2, P::A2A_PITCH, P::A2A_MASK>(big, tid);
-    if (!(FHEVC_D2_SKIP & 4))
-      d2_conv<KC1, KC2, false, 32, 32, P::A1_PITCH, P::A1_MASK, P::PX2, P::A2A_PITCH, P::A2A_MASK, true, RQB>(ra, 0, big, 0, w2a, b2a, L2a.shift,
-                                                                                                          [&]() { d2_weights<KC2, KC2>(L2b.frag, L2b.bias, w2b, b2b); });
-    else d2_weights<KC2, KC2>(L2b.frag, L2b.bias, w2b, b2b);
+    d2_conv<KC1, KC2, false, 32, 32, P::A1_PITCH, P::A1_MASK, P::PX2, P::A2A_PITCH, P::A2A_MASK, true, RQB>(ra, 0, big, 0, w2a, b2a, L2a.shift,
+                                                                                                        [&]() { d2_weights<KC2, KC2>(L2b.frag, L2b.bias, w2b, b2b); });
     D2_STAMP(3)   // conv2a
     __syncthreads();
     D2_STAMP(1)
     d2_fill_halo<16, P::PX2, P::A2_PITCH, P::A2_MASK>(ra, tid);
-    if (!(FHEVC_D2_SKIP & 8))
-      d2_conv<KC2, KC2, true, 32, 32, P::A2A_PITCH, P::A2A_MASK, P::PX2, P::A2_PITCH, P::A2_MASK, true, RQB>(big, 0, ra, 0, w2b, b2b, L2b.shift, []() {}, L2b.bias);
+    d2_conv<KC2, KC2, true, 32, 32, P::A2A_PITCH, P::A2A_MASK, P::PX2, P::A2_PITCH, P::A2_MASK, true, RQB>(big, 0, ra, 0, w2b, b2b, L2b.shift, []() {}, L2b.bias);
     D2_STAMP(4)   // conv2b
     __syncthreads();
     D2_STAMP(1)
@@ -563,20 +547,17 @@ __global__ __launch_bounds__(512, 2) void fhevc_cnn_d2_kernel(FhevcFrames F, Fhe
       }
     }
     d2_fill_halo<16, P::PX3, P::A3A_PITCH, P::A3A_MASK>(big, tid);
-    if (!(FHEVC_D2_SKIP & 16))
-      d2_conv_m3<KC2, false, 16, P::A2_PITCH, P::A2_MASK, P::PX3, P::A3A_PITCH, P::A3A_MASK, true, RQB>(ra, big, L3a.frag, L3a.bias, w3a, b3a, L3a.shift,
-                                                                                                     [&]() { d2_weights<KC3, KC3>(L3b.frag, L3b.bias, w3b, b3b); });
-    else d2_weights<KC3, KC3>(L3b.frag, L3b.bias, w3b, b3b);
+    d2_conv_m3<KC2, false, 16, P::A2_PITCH, P::A2_MASK, P::PX3, P::A3A_PITCH, P::A3A_MASK, true, RQB>(ra, big, L3a.frag, L3a.bias, w3a, b3a, L3a.shift,
+                                                                                                   [&]() { d2_weights<KC3, KC3>(L3b.frag, L3b.bias, w3b, b3b); });
     D2_STAMP(5)   // conv3a
     __syncthreads();
     D2_STAMP(1)
-    if (!(FHEVC_D2_SKIP & 32))
-      d2_conv_m3<KC3, false, 16, P::A3A_PITCH, P::A3A_MASK, P::PX3, P::PX3, 0, false, RQB>(big, ra, L3b.frag, L3b.bias, w3b, b3b, L3b.shift, []() {});
+    d2_conv_m3<KC3, false, 16, P::A3A_PITCH, P::A3A_MASK, P::PX3, P::PX3, 0, false, RQB>(big, ra, L3b.frag, L3b.bias, w3b, b3b, L3b.shift, []() {});
     D2_STAMP(6)   // conv3b
     __syncthreads();
     D2_STAMP(1)
     // ================= heads (waves 0-3: thread = position of the 16 x 16 map, DPP row = 16x16 block, wave = quadrant) | next CTU staged (waves 4-7) =================
-    if (tid < 256 && !(FHEVC_D2_SKIP & 64)) {
+    if (tid < 256) {
       unsigned t_ = threadIdx.x;
       asm volatile("" : "+v"(t_));
       const int lane = (int)(t_ & 63u), wave = (int)(t_ >> 6);

@@ -16,9 +16,6 @@
 //     32- and 64-level sums; the depth map, soft ranges, logits and split-flag words by the same depth_map_of_ctu as above.
 // The source Hadamard is not fused here (the stand-alone kernel runs).  Not tuned: round 3 adds the family to the kernel; its roofline
 // line is reported by bench.py --family.
-#ifndef FHEVC_FAM_SKIP
-#define FHEVC_FAM_SKIP 0   // (timing experiments only, WRONG results: bit 0 conv1, 1 conv2, 2 conv3, 3 heads skipped)
-#endif
 template <int C1, int C2, int C3>
 struct LdsFam {
   static constexpr int G1 = C1 / 16;                           // conv1 filter groups = A1 planes
@@ -55,17 +52,6 @@ __global__ __launch_bounds__(256, 2) void fhevc_cnn_family_kernel(FhevcFrames F,
   const int hb16a = W.bhead[4], hb16b = W.bhead[5] + W.bhead[6 + 2 * 52 + F.qp];
   int* biasL = reinterpret_cast<int*>(lds + P::BIAS_OFF);
   int* logitL = reinterpret_cast<int*>(lds + P::LOGIT_OFF);
-  // wave priority in the two MFMA phases (round 4; the depth kernel's scheme: level 1, or 1 + the workgroup's slot on its CU = LDS base / LDS size), 0 elsewhere
-#ifndef FHEVC_FAM_PRIO
-#define FHEVC_FAM_PRIO 1   // 0: none (round 3) 1.2468 ms, 1: one level for both workgroups 1.2372 (-0.8 %), 2: by slot 1.2587 (+1.0 %): profiles/r04_ab_family_priority.log
-#endif
-  int fam_slot = 0;
-  if (FHEVC_FAM_PRIO == 2) {
-    const unsigned la = __builtin_amdgcn_s_getreg((31 << 11) | 6);   // HW_REG_LDS_ALLOC: base [11:0], size [20:12], 256-byte granules
-    fam_slot = ((la & 0xFFFu) >= ((la >> 12) & 0x1FFu) && ((la >> 12) & 0x1FFu)) ? 1 : 0;
-  }
-#define FHEVC_FAM_PRIO_ON  { if (FHEVC_FAM_PRIO == 1 || (FHEVC_FAM_PRIO == 2 && fam_slot == 0)) __builtin_amdgcn_s_setprio(1); else if (FHEVC_FAM_PRIO == 2) __builtin_amdgcn_s_setprio(2); }
-#define FHEVC_FAM_PRIO_OFF { if (FHEVC_FAM_PRIO) __builtin_amdgcn_s_setprio(0); }
   for (int i = tid; i < C2 + C3; i += 256) biasL[i] = W.bias_i8[i];
   // "activation 0" everywhere in A1 and A2 (halos; the second plane of a 16-channel A1), bf16(128) everywhere in the tile
   for (int i = tid; i < (P::P1 * P::A1_PLANE_B) / 16; i += 256) *reinterpret_cast<uint4*>(lds + P::A1_OFF + i * 16) = make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);
@@ -113,7 +99,7 @@ __global__ __launch_bounds__(256, 2) void fhevc_cnn_family_kernel(FhevcFrames F,
   for (int work = vblock; work < total; work += grid) {
     const CtuPos next = advance(pos, step, band_rows, F.ctus_x);
     // ================= conv1 (1 -> C1): per group of 16 filters two MFMAs per pooled row, fused max-pool + requant =================
-    if (!(FHEVC_FAM_SKIP & 1)) {
+    {
       const unsigned char* c1_in = lds + P::T_OFF + (2 * r + 2 * h) * 4 + wave * (IN_PITCH * 4);
       unsigned char* c1_out = lds + P::A1_OFF + 8 * h + (wave + 1) * A1_ROW + (((r + 1) & 1) ? 0 : A1_EVEN) + ((r + 1) >> 1) * 16;
       bf16x8 wa[G1], wb[G1];
@@ -146,8 +132,10 @@ __global__ __launch_bounds__(256, 2) void fhevc_cnn_family_kernel(FhevcFrames F,
     for (int s = 0; s < K1 * 9; ++s) w2[s] = __builtin_bit_cast(bf16x8, W.frag2[s * 64 + lane]);
     __syncthreads();
     // ================= conv2 (C1 -> C2): K step = tap x 32 channels; lane = pooled position, four accumulators (dy, dx) =================
-    if (!(FHEVC_FAM_SKIP & 2)) {
-      FHEVC_FAM_PRIO_ON
+    {
+      // wave priority 1 in the two MFMA phases (round 4), 0 elsewhere.  Measured: none (round 3) 1.2468 ms, level 1 for both workgroups 1.2372 (-0.8 %),
+      // 1 + the workgroup's slot on its CU (the depth kernel's scheme) 1.2587 (+1.0 %): profiles/r04_ab_family_priority.log
+      __builtin_amdgcn_s_setprio(1);
       const int q = r >> 2;
       const int pr = (q ^ (q >> 1) ^ (q >> 2)) & 1, pc = ((r >> 3) << 2) | (r & 3);
       const unsigned char* a1p = lds + P::A1_OFF + h * P::A1_PLANE_B + (2 * pr) * A1_ROW + pc * 16;
@@ -189,7 +177,7 @@ __global__ __launch_bounds__(256, 2) void fhevc_cnn_family_kernel(FhevcFrames F,
         pool_v_i8(t1, a1, t0);
         conv2_requant_store_i8m<0>(t1, d1, shift2);
       }
-      FHEVC_FAM_PRIO_OFF
+      __builtin_amdgcn_s_setprio(0);
     }
     // conv3's weights (this wave's M tile) travel from L2 while the waves meet at the barrier
     constexpr int PER_WAVE = M3 * 8 / 4;              // (M tile, row pair) items per wave, M-tile-major: one M tile per wave
@@ -200,8 +188,8 @@ __global__ __launch_bounds__(256, 2) void fhevc_cnn_family_kernel(FhevcFrames F,
     __syncthreads();
     // ================= conv3 (C2 -> C3): K step = tap x 32 channels; an MFMA = 32 output channels x two output rows 8 apart =================
     pre = prefetch_ctu<false>(F, work + grid < total, next, ld_row, ld_seg);
-    if (!(FHEVC_FAM_SKIP & 4)) {
-      FHEVC_FAM_PRIO_ON
+    {
+      __builtin_amdgcn_s_setprio(1);
       const int x = lane & 15, rs = (lane >> 4) & 1;
       const int psw = (x / (16 / NC3)) % NC3;           // chunk swizzle of the map's rows: the heads' 16-lane reads hit 16 distinct slots
       const i32x16 binit = bias_tile_i8(biasL + C2 + 32 * mt3, h);
@@ -230,13 +218,11 @@ __global__ __launch_bounds__(256, 2) void fhevc_cnn_family_kernel(FhevcFrames F,
           *reinterpret_cast<unsigned*>(db + (((2 * mt3 + (g >> 1)) ^ psw) << 4) + 8 * (g & 1)) = requant4_i8(accb[4 * g], accb[4 * g + 1], accb[4 * g + 2], accb[4 * g + 3], shift3, 0);
         }
       }
-      FHEVC_FAM_PRIO_OFF
+      __builtin_amdgcn_s_setprio(0);
     }
     __syncthreads();
     // ================= heads: thread = position (y = tid >> 4, x = tid & 15), v_dot4 against its rows of the three FC weights =================
-    if (FHEVC_FAM_SKIP & 8) {
-      if (work + grid < total) stage_ctu<false>(lds, P::T_OFF, pre, F, next, tid, ld_row, ld_seg, shift_in, 0u);
-    } else {
+    {
       // 16- and 32-level heads as ONE GEMM on v_mfma_i32_16x16x64_i8 (as P4 of the tuned kernel): rows = the 16 blocks of the CTU, a K step =
       // one position (py = wave, px) of a block x 64 channels (C3 / 64 chunks), columns = the weight variants: 0, 1 the 16-level classes,
       // 2 + 2 sub + class the 32-level weights of a block at sub-position sub of its quadrant.  The B operands come from L2 (W.headm:
@@ -297,5 +283,3 @@ __global__ __launch_bounds__(256, 2) void fhevc_cnn_family_kernel(FhevcFrames F,
     pos = next;
   }
 }
-#undef FHEVC_FAM_PRIO_ON
-#undef FHEVC_FAM_PRIO_OFF

@@ -64,9 +64,6 @@ __global__ __launch_bounds__(256) void fhevc_layers_stage_kernel(FhevcFrames F, 
 // FUSE0 (LDS form of the SECOND convolution of a member with two or three convolutions per block): the strip of the first convolution's output is
 // not copied from HBM but computed into LDS from the CTU's sample tile (first.in0: [CTU][66][66] bytes) -- one MFMA per 32 positions and M tile --
 // so that the first convolution's launch, its 139 KB per CTU of output and their re-read disappear
-#ifndef FHEVC_LAYER_SKIP
-#define FHEVC_LAYER_SKIP 0   // (timing experiments, WRONG results: 1 = no MFMA loop / stores, 2 = no staging copy)
-#endif
 #ifndef FHEVC_LAYER_RING
 #define FHEVC_LAYER_RING 6   // B fragments in flight ahead of their MFMAs
 #endif
@@ -230,14 +227,14 @@ __global__ __launch_bounds__(256, 2) void fhevc_layer_conv_kernel(const int8_t* 
         }
       } else {
         const uint4* src = reinterpret_cast<const uint4*>(in + (size_t)ctu * in_ctu + (size_t)y0 * in_pitch);
-        for (int i = threadIdx.x; !(FHEVC_LAYER_SKIP & 2) && i < n16; i += 256) reinterpret_cast<uint4*>(lds_map)[SWZ ? i ^ ((i >> 4) & swz) : i] = src[i];
+        for (int i = threadIdx.x; i < n16; i += 256) reinterpret_cast<uint4*>(lds_map)[SWZ ? i ^ ((i >> 4) & swz) : i] = src[i];
       }
       __syncthreads();
     } else {
       ip = in + (size_t)ctu * in_ctu;
     }
     int8_t* op = out + (size_t)ctu * out_ctu;
-    for (int t = sidx * strip_tiles + sub * TS; !(FHEVC_LAYER_SKIP & 1) && active && t < (sidx + 1) * strip_tiles; t += nsub * TS) {
+    for (int t = sidx * strip_tiles + sub * TS; active && t < (sidx + 1) * strip_tiles; t += nsub * TS) {
       i32x16 acc[NA];
 #pragma unroll
       for (int a = 0; a < NA; ++a) acc[a] = binit;
