@@ -301,6 +301,53 @@ def native_pel_plane(luma_u8, bit_depth, seed=0, margin=HM_MARGIN):
     return buf, margin * stride + margin, stride
 
 
+def _poison(rng, n, dtype, bit_depth):
+    """n samples that hurt a kernel which reads them for their value: for int16 the type's limits, -1, 2^bd - 1, 2^bd and random in-range
+    values; for uint8 0, 255 and random bytes.  Never one value only."""
+    sel = rng.integers(0, 8, size=n)
+    if np.dtype(dtype) == np.uint8:
+        special, vals = np.array([0, 255], np.int64), rng.integers(0, 256, size=n)
+    else:
+        top = (1 << bit_depth) - 1
+        special, vals = np.array([-32768, 32767, -1, top, top + 1], np.int64), rng.integers(0, top + 1, size=n)
+    out = np.where(sel < len(special), special[np.minimum(sel, len(special) - 1)], vals).astype(dtype)
+    assert len(np.unique(out[:4096])) > 2
+    return out
+
+
+def guarded_plane(samples, bit_depth=8, dtype=np.int16, margin=HM_MARGIN, extra_stride=0, shift=0, frame_gap=0, poison=0, guard_bytes=4096):
+    """One picture [H, W] or a list of pictures (int16 at bit_depth, or uint8 content) -> (flat, origin, stride, frame_stride): a flat `dtype`
+    buffer (int16 Pel samples or uint8) in which frame f's sample (x, y) lies at flat[origin + f * frame_stride + y * stride + x].  The layout
+    is TComPicYuv's (to_pel_plane: `margin` samples on every side) with stride = W + 2 * margin + extra_stride, the origin moved by `shift`
+    samples and `frame_gap` samples between one frame's bottom margin and the next one's top margin; extra_stride, shift and frame_gap may be
+    odd.  flat starts on a 64-byte boundary, so shift = 0, extra_stride = 0, margin 80 reproduces HM's alignment (16-byte aligned rows for
+    widths that are multiples of 8) and anything else is off it by exactly what was asked for.
+
+    Everything that is not a picture sample is POISON drawn from the seeded generator `poison` (_poison): margins, stride padding, the gap
+    between frames and a guard zone of at least guard_bytes before the first and after the last frame, which keeps any over-read of a few
+    vector widths inside the allocation.  poison=None fills with zeros instead (the clean plane the references are computed on)."""
+    pics = [np.asarray(p) for p in (samples if isinstance(samples, (list, tuple)) else [samples])]
+    h, w = pics[0].shape
+    dtype = np.dtype(dtype)
+    assert dtype in (np.dtype(np.int16), np.dtype(np.uint8)) and all(p.shape == (h, w) for p in pics)
+    assert dtype == np.int16 or bit_depth == 8
+    assert all(int(p.min()) >= 0 and int(p.max()) < (1 << bit_depth) for p in pics)
+    assert margin >= 0 and extra_stride >= 0 and shift >= 0 and frame_gap >= 0
+    stride = w + 2 * margin + extra_stride
+    frame_stride = (h + 2 * margin) * stride + frame_gap
+    guard = -(-max(guard_bytes, 4096) // 64) * 64 // dtype.itemsize
+    total = 2 * guard + shift + len(pics) * frame_stride
+    raw = np.empty(total * dtype.itemsize + 64, np.uint8)
+    skip = (-raw.ctypes.data) % 64
+    flat = raw[skip:skip + total * dtype.itemsize].view(dtype)
+    flat[:] = 0 if poison is None else _poison(np.random.default_rng(poison), total, dtype, bit_depth)
+    origin = guard + shift + margin * stride + margin
+    for f, p in enumerate(pics):
+        rows = origin + f * frame_stride + np.arange(h)[:, None] * stride + np.arange(w)[None, :]
+        flat[rows] = p.astype(dtype)
+    return flat, origin, stride, frame_stride
+
+
 def chroma_planes(kind, width, height):
     """(U, V) uint8 planes [H/2, W/2] of the pinned generators: U = 128, V a horizontal sinusoid."""
     _, xx = np.mgrid[0:height, 0:width]

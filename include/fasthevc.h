@@ -90,7 +90,14 @@ int  fhevc_set_weights(fhevc_ctx* ctx, const void* blob, size_t bytes);
  * TEncCu::updateCtuDataISlice(ctu, w, h) (TEncCu.cpp:1324-1343) -- what TEncSlice::calCostSliceI sums
  * (TEncSlice.cpp:663-695).  qp is the slice QP: it selects a per-QP prior on the split decisions (the reference
  * stores QP in its labels, CShow_PredResiReco.h:93, but its MATLAB pipeline never reads it); slice_type is
- * reserved (I slices only this round). */
+ * reserved (I slices only this round).
+ * Plane contract of every entry point that takes luma / d_luma with stride_samples (tests/test_gpu_layouts.py): the pointer may have any
+ * alignment (the sample's own included: an int16 plane may start on an odd byte pair, a uint8 plane on any byte), stride_samples any value
+ * >= width, frame_stride_samples any value that keeps frames from overlapping; aligned layouts (16-byte aligned rows) are merely faster.
+ * Nothing outside the picture rectangle is read FOR ITS VALUE: margins, stride padding, rows below a ragged picture and the gap between
+ * frames may hold anything (HM's uninitialised or border-extended margins), results do not depend on them, and samples outside the
+ * picture are taken as 0 (classifier, first pass) or as the replicated border (motion search).  Outputs are written over exactly the
+ * extent stated per entry point; a band with ctu_row_begin == ctu_row_end writes nothing. */
 int  fhevc_predict_frame(fhevc_ctx* ctx, const int16_t* luma, int stride_samples, int qp, int slice_type,
                          uint8_t* depth_map, int32_t* ctu_src_hadamard);
 

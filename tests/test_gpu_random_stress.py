@@ -38,9 +38,10 @@ def test_random_configuration(oracle, seed):
     w = weights.random_weights(seed, extreme=bool(seed % 3 == 0))
     m = frames.HM_MARGIN
     stride = W + 2 * m + 8 * int(rng.integers(0, 3))           # strides other than HM's
-    buf = np.zeros((H + 2 * m, stride), np.int16)
-    buf[m:m + H, m:m + W] = _content(rng, W, H, bd)
-    org = m * stride + m
+    lay = np.random.default_rng(5000 + seed)                   # a second generator: the draws above and the content below stay what they were
+    shift, odd = int(lay.integers(0, 9)), int(lay.integers(0, 4))
+    # everything around the picture is poison, the origin and the rows on any alignment (frames.guarded_plane)
+    buf, org, stride, _ = frames.guarded_plane(_content(rng, W, H, bd), bd, extra_stride=stride - W - 2 * m + odd, shift=shift, poison=9000 + seed)
     cw, ch = frames.ctu_grid(W, H)
     n = cw * ch
     ctx = capi.Context(W, H, bd, w, arith=("i8", "f16")[seed & 1])  # both arithmetic forms of the classifier (the extreme blobs, seed % 3 == 0,
