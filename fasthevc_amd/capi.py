@@ -422,6 +422,13 @@ class Context:
         self._check(self.lib.fhevc_predict_frames_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames,
                                                          rb, re, qp, d_depth, d_hadamard, d_logits, d_flags, stream))
 
+    def predict_frames_device_range(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_depth, d_depth_max=None, d_hadamard=None,
+                                    d_logits=None, rows=None, stream=None, qp=32, d_flags=None, margin_split=0, margin_stop=0):
+        """predict_frames_device with soft decisions: d_depth receives depth_min, d_depth_max (optional) depth_max; asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_predict_frames_device_range(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp,
+                                                               margin_split, margin_stop, d_depth, d_depth_max, d_hadamard, d_logits, d_flags, stream))
+
     def expand_depth_flags_device(self, d_flags, num_frames, d_depth, stream=None):
         self._check(self.lib.fhevc_expand_depth_flags_device(self.h, d_flags, num_frames, d_depth, stream))
 

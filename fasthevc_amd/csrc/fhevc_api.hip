@@ -67,7 +67,6 @@ struct fhevc_ctx {
   FhevcNodeCost* d_cand_all = nullptr; uint8_t* d_cand = nullptr;   // fhevc_intra_first_pass_candidates: every (node, mode) cost, the lists
   uint32_t* d_mvtab = nullptr;        // vector costs of the wide search (k_motion_wide.hip), rebuilt when (qp, range) changes
   int mvtab_qp = -1, mvtab_range = -1;
-  hipEvent_t mvtab_used = nullptr;    // recorded behind every launch that reads d_mvtab, on whatever stream the caller passed: the rebuild waits for it
   std::vector<uint32_t> mvtab_host;
   // host-batch ring (fhevc_predict_frames): two slots, each with its own stream, device buffers and pinned staging
   struct Slot {
@@ -751,12 +750,12 @@ void fhevc_destroy(fhevc_ctx* c)
   for (fhevc_ctx* peer : c->peers) fhevc_destroy(peer);
   c->peers.clear();
   (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  // launches of the *_device entry points may still be queued on the callers' own streams: nothing below may be freed under them
+  (void)hipDeviceSynchronize();
   time_resolve(c);
   for (auto& p : c->pool) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
   for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
   if (c->lw_done) (void)hipEventDestroy(c->lw_done);
-  if (c->mvtab_used) (void)hipEventDestroy(c->mvtab_used);
   (void)hipFree(c->d_frag); (void)hipFree(c->d_bias); (void)hipFree(c->d_whead); (void)hipFree(c->d_bhead);
   (void)hipFree(c->d_frag_i8); (void)hipFree(c->d_bias_i8);
   (void)hipFree(c->f_frag1); (void)hipFree(c->f_bias1); (void)hipFree(c->f_frag2); (void)hipFree(c->f_frag3); (void)hipFree(c->f_bias_i8); (void)hipFree(c->f_whead); (void)hipFree(c->f_headm); (void)hipFree(c->f_bhead);
@@ -791,6 +790,9 @@ int fhevc_set_weights(fhevc_ctx* c, const void* blob, size_t bytes)
     return (int)FHEVC_OK;
   };
   (void)hipSetDevice(c->device);
+  // The images below are overwritten in place or freed.  Launches issued earlier, on ANY stream (a caller's non-blocking stream is not
+  // ordered with the synchronous copies), still read them: wait for the device first, so that they see the old weights to the end
+  HIP_TRY(c, hipDeviceSynchronize());
   if (bytes >= 4 && std::memcmp(blob, "FHW3", 4) == 0) {  // a member of the reference's Bayesian-optimisation network family
     const int rc = build_family_image(c, static_cast<const uint8_t*>(blob), bytes);
     return rc != FHEVC_OK ? rc : push_to_peers();
@@ -1450,7 +1452,9 @@ int fhevc_motion_search_device(fhevc_ctx* c, const void* d_luma, int sample_byte
     auto eg = [](int v) { unsigned len = 1, u = (v <= 0) ? (((unsigned)(-v)) << 1) + 1 : ((unsigned)v) << 1; while (u != 1) { u >>= 1; len += 2; } return len; };
     const int side = 2 * search_range + 1;
     if (!c->d_mvtab) HIP_TRY(c, hipMalloc(&c->d_mvtab, sizeof(uint32_t) * (2 * FHEVC_MOTION_WIDE_MAX_RANGE + 1) * (2 * FHEVC_MOTION_WIDE_MAX_RANGE + 1)));
-    if (c->mvtab_used) HIP_TRY(c, hipEventSynchronize(c->mvtab_used));  // the last launch that read the old table, on ANY stream (the per-call stream may differ)
+    // EVERY launch that reads the old table has to be through, on whatever streams the callers passed (an event behind the latest launch would
+    // cover that one stream only).  A rebuild happens only when (qp, range) changes: off the hot path
+    HIP_TRY(c, hipDeviceSynchronize());
     c->mvtab_host.resize((size_t)side * side);
     for (int m = 0; m < side * side; ++m)
       c->mvtab_host[m] = (uint32_t)((motion_lambda * (eg(((m % side) - search_range) << 2) + eg(((m / side) - search_range) << 2))) / 65536.0);
@@ -1461,8 +1465,6 @@ int fhevc_motion_search_device(fhevc_ctx* c, const void* d_luma, int sample_byte
   if (wide) {
     if (big) HIP_TRY(c, fhevc_launch_motion_big(fr, search_range, c->d_mvtab, reinterpret_cast<FhevcMotionNode*>(d_out), c->num_cus, st));
     else HIP_TRY(c, fhevc_launch_motion_wide(fr, search_range, c->d_mvtab, reinterpret_cast<FhevcMotionNode*>(d_out), c->num_cus, st));
-    if (!c->mvtab_used) HIP_TRY(c, hipEventCreateWithFlags(&c->mvtab_used, hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->mvtab_used, st));
   }
   else HIP_TRY(c, fhevc_launch_motion(fr, search_range, mv_cost_table(qp, search_range), reinterpret_cast<FhevcMotionNode*>(d_out), c->num_cus, c->motion_sad, st));
   time_end(c, st);

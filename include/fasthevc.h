@@ -80,8 +80,12 @@ typedef struct {
 } fhevc_stats;
 
 int  fhevc_create(fhevc_ctx** out, const fhevc_cfg* cfg);
+/* waits for the device first: launches of the *_device entry points still queued on any stream finish before anything is freed */
 void fhevc_destroy(fhevc_ctx* ctx);
-/* weights from memory instead of cfg.weights_path (same FHW1 bytes) */
+/* weights from memory instead of cfg.weights_path (same FHW1 bytes, or an FHW3 family member).  Ordering against the *_device entry points, on any
+ * stream (the context's own, the default stream, a caller's non-blocking stream): launches issued BEFORE this call use the old weights, launches
+ * issued after it the new ones.  The call waits for the device before the first byte of a weight image is overwritten or freed, so it blocks the
+ * host until the work queued so far has finished: not for the hot path. */
 int  fhevc_set_weights(fhevc_ctx* ctx, const void* blob, size_t bytes);
 
 /* One picture, host buffers, synchronous.  Called once per picture before the CTU loop of
@@ -228,6 +232,9 @@ int  fhevc_preanalyze_frames_device(fhevc_ctx* ctx, const void* d_luma, int samp
  * window -- 8-bit content on a kernel laid out for 16 641 vectors per node around v_qsad_pk_u16_u8 (k_motion_wide.hip), content above
  * 8 bit (16-bit planes; cfg/encoder_lowdelay_P_main10.cfg) on the 16-bit SAD kernel laid out for the wide window (k_motion.hip, round 4;
  * ~20 x slower than the byte kernel, still ~100 x HM's own search per core); 9..64 in the SATD mode: FHEVC_E_INVALID.
+ * The vector costs of a wide search live in one table per context, rebuilt when (qp, search_range) differs from the previous wide call's: that call
+ * waits for the device first (every earlier wide search, on any stream, still reads the old table), so it blocks the host; calls that repeat the
+ * previous (qp, search_range) stay asynchronous.
  * (HM's P configuration itself runs the TZ search, cfg/encoder_lowdelay_P_main.cfg:34 FastSearch 1 -> xPatternSearchFast,
  * TEncSearch.cpp:3850: the exhaustive twin is a superset of what TZ visits and serves as a source-only feature.) */
 #define FHEVC_MOTION_SATD 0
