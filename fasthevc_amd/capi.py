@@ -26,8 +26,12 @@ SYMBOLS = [
     "fhevc_predict_frame_range", "fhevc_predict_frames_device_range",
     "fhevc_motion_search", "fhevc_motion_search_device", "fhevc_intra_first_pass_all", "fhevc_intra_first_pass_candidates", "fhevc_p_rule_default", "fhevc_p_rule_default_wide", "fhevc_p_depth_range", "fhevc_p_motion_compensated_depth", "fhevc_p_node_depth",
     "fhevc_predict_frames", "fhevc_alloc_host", "fhevc_free_host", "fhevc_set_cnn_arith", "fhevc_get_cnn_arith", "fhevc_set_motion_distortion", "fhevc_read_yuv_luma",
+    "fhevc_p_depth_range_device", "fhevc_p_predict_frame",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
+# where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
+P_PREV_COLOCATED, P_PREV_UNIT, P_PREV_NODE = 0, 1, 2
+P_PREV = {"colocated": P_PREV_COLOCATED, "unit": P_PREV_UNIT, "node": P_PREV_NODE}
 
 
 class Cfg(C.Structure):
@@ -133,6 +137,8 @@ def load_library(path=None):
     lib.fhevc_p_depth_range.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PRule), vp, vp]
     lib.fhevc_p_motion_compensated_depth.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
     lib.fhevc_p_node_depth.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.fhevc_p_depth_range_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PRule), vp, vp, vp]
+    lib.fhevc_p_predict_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(PRule), vp, vp]
     lib.fhevc_predict_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, vp, vp]
     lib.fhevc_alloc_host.argtypes = [vp, C.c_size_t]
     lib.fhevc_alloc_host.restype = vp
@@ -356,6 +362,30 @@ class Context:
         rb, re = rows if rows is not None else (0, self.ctus_y)
         self._check(self.lib.fhevc_motion_search_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp,
                                                         search_range, d_out, stream))
+
+    def p_depth_range_device(self, d_nodes, d_prev_maps, num_pictures, d_depth_min, d_depth_max=None, rows=None, stream=None, qp=32,
+                             prev_mode="colocated", rule=None):
+        """config 4 on the device: the depth ranges of num_pictures P pictures from d_nodes (what motion_search_device wrote for the same rows)
+        and d_prev_maps (num_pictures whole-picture maps, numCtus * 256 bytes each); d_depth_min / d_depth_max: num_pictures * band CTUs * 256
+        bytes.  prev_mode: "colocated", "unit", "node" or a P_PREV_* value; rule: a PRule (None: the shipped one).  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_p_depth_range_device(self.h, d_nodes, d_prev_maps, num_pictures, rb, re, qp, P_PREV.get(prev_mode, prev_mode),
+                                                        C.byref(rule) if rule is not None else None, d_depth_min, d_depth_max, stream))
+
+    def p_predict_frame(self, cur_plane, ref_plane, prev_map, origin=0, stride=None, qp=32, search_range=4, prev_mode="colocated", rule=None):
+        """config 4, one picture pair from host buffers: motion search of cur in ref (as motion_search) and the depth ranges decided on the
+        device against prev_map [numCtus, 256], the reference picture's depths -> (depth_min, depth_max), each [numCtus, 256]."""
+        cur = np.ascontiguousarray(cur_plane).reshape(-1)
+        ref = np.ascontiguousarray(ref_plane).reshape(-1)
+        assert cur.dtype == np.int16 and ref.dtype == np.int16
+        prev = np.ascontiguousarray(prev_map, np.uint8).reshape(-1)
+        assert prev.size == self.num_ctus * 256
+        stride = stride if stride is not None else cur_plane.shape[-1]
+        dmin, dmax = np.zeros(self.num_ctus * 256, np.uint8), np.zeros(self.num_ctus * 256, np.uint8)
+        self._check(self.lib.fhevc_p_predict_frame(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, search_range,
+                                                   prev.ctypes.data, P_PREV.get(prev_mode, prev_mode), C.byref(rule) if rule is not None else None,
+                                                   dmin.ctypes.data, dmax.ctypes.data))
+        return dmin.reshape(self.num_ctus, 256), dmax.reshape(self.num_ctus, 256)
 
     def intra_first_pass_all(self, plane, origin=0, stride=None, qp=32):
         """(best [numCtus, 85], all [numCtus, 85, 35]): every mode's SATD and cost per node (parity entry point)"""

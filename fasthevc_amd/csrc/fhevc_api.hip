@@ -1,5 +1,5 @@
 // fhevc_api.hip -- the C ABI of include/fasthevc.h: context, weight image, staging buffers, launches.
-// Host-side C++ only; all device work is in k_cnn.hip / k_hadamard.hip / k_firstpass.hip.
+// Host-side C++ only; all device work is in the k_*.hip files.
 #include "../../include/fasthevc.h"
 #include "fhevc_internal.h"
 
@@ -59,11 +59,12 @@ struct fhevc_ctx {
   bool timing = false;
   std::vector<TimedLaunch> pending;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-  double sum_ms[5] = { 0, 0, 0, 0, 0 };
-  uint64_t launches[5] = { 0, 0, 0, 0, 0 };
+  double sum_ms[6] = { 0, 0, 0, 0, 0, 0 };
+  uint64_t launches[6] = { 0, 0, 0, 0, 0, 0 };
   double* d_act = nullptr;
   int16_t* d_pair = nullptr;          // two staging planes (reference, current) of fhevc_motion_search
   FhevcMotionNode* d_motion = nullptr;
+  uint8_t* d_p_maps = nullptr;        // fhevc_p_predict_frame: the reference picture's map, depth_min, depth_max (numCtus * 256 each)
   FhevcNodeCost* d_cand_all = nullptr; uint8_t* d_cand = nullptr;   // fhevc_intra_first_pass_candidates: every (node, mode) cost, the lists
   uint32_t* d_mvtab = nullptr;        // vector costs of the wide search (k_motion_wide.hip), rebuilt when (qp, range) changes
   int mvtab_qp = -1, mvtab_range = -1;
@@ -759,7 +760,7 @@ void fhevc_destroy(fhevc_ctx* c)
   (void)hipFree(c->d_frag); (void)hipFree(c->d_bias); (void)hipFree(c->d_whead); (void)hipFree(c->d_bhead);
   (void)hipFree(c->d_frag_i8); (void)hipFree(c->d_bias_i8);
   (void)hipFree(c->f_frag1); (void)hipFree(c->f_bias1); (void)hipFree(c->f_frag2); (void)hipFree(c->f_frag3); (void)hipFree(c->f_bias_i8); (void)hipFree(c->f_whead); (void)hipFree(c->f_headm); (void)hipFree(c->f_bhead);
-  (void)hipFree(c->d_luma); (void)hipFree(c->d_depth); (void)hipFree(c->d_had); (void)hipFree(c->d_nodes); (void)hipFree(c->d_satd); (void)hipFree(c->d_satd_out); (void)hipFree(c->d_act); (void)hipFree(c->d_depth_max); (void)hipFree(c->d_pair); (void)hipFree(c->d_motion); (void)hipFree(c->d_mvtab); (void)hipFree(c->d_cand_all); (void)hipFree(c->d_cand);
+  (void)hipFree(c->d_luma); (void)hipFree(c->d_depth); (void)hipFree(c->d_had); (void)hipFree(c->d_nodes); (void)hipFree(c->d_satd); (void)hipFree(c->d_satd_out); (void)hipFree(c->d_act); (void)hipFree(c->d_depth_max); (void)hipFree(c->d_pair); (void)hipFree(c->d_motion); (void)hipFree(c->d_p_maps); (void)hipFree(c->d_mvtab); (void)hipFree(c->d_cand_all); (void)hipFree(c->d_cand);
   for (void* q : c->lw_bufs) (void)hipFree(q);
   for (auto& sl : c->slot) {  // the host-batch ring of fhevc_predict_frames: stream, device buffers, pinned staging
     if (sl.st) { (void)hipStreamSynchronize(sl.st); (void)hipStreamDestroy(sl.st); }
@@ -817,7 +818,7 @@ int fhevc_enable_kernel_timing(fhevc_ctx* c, int on)
 
 int fhevc_kernel_timing(fhevc_ctx* c, int which, int reset, double* avg_ms, uint64_t* launches)
 {
-  if (!c || which < 0 || which > 4) return FHEVC_E_INVALID;
+  if (!c || which < 0 || which > 5) return FHEVC_E_INVALID;
   time_resolve(c);
   if (avg_ms) *avg_ms = c->launches[which] ? c->sum_ms[which] / (double)c->launches[which] : 0.0;
   if (launches) *launches = c->launches[which];
@@ -1598,6 +1599,61 @@ int fhevc_p_depth_range(const fhevc_motion_node* nodes, const uint8_t* prev_dept
       depth_min[uy * 16 + ux] = (uint8_t)lo;
       depth_max[uy * 16 + ux] = (uint8_t)hi;
     }
+  return FHEVC_OK;
+}
+
+// ---- the same decision over a device-resident batch (k_p_rule.hip) ----
+int fhevc_p_depth_range_device(fhevc_ctx* c, const fhevc_motion_node* d_nodes, const uint8_t* d_prev_maps, int num_pictures, int ctu_row_begin,
+                               int ctu_row_end, int qp, int prev_mode, const fhevc_p_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, void* stream)
+{
+  if (!c || !d_nodes || !d_prev_maps || !d_depth_min) return FHEVC_E_INVALID;
+  if (num_pictures < 1 || qp < 0 || qp > 51 || ctu_row_begin < 0 || ctu_row_end > c->ctus_y || ctu_row_begin > ctu_row_end)
+    return fail(c, FHEVC_E_INVALID, "bad P-rule arguments");
+  if (prev_mode != FHEVC_P_PREV_COLOCATED && prev_mode != FHEVC_P_PREV_UNIT && prev_mode != FHEVC_P_PREV_NODE)
+    return fail(c, FHEVC_E_INVALID, "prev_mode: FHEVC_P_PREV_COLOCATED, FHEVC_P_PREV_UNIT or FHEVC_P_PREV_NODE");
+  if ((long long)num_pictures * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "bad P-rule arguments");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;
+  static_assert(sizeof(fhevc_p_rule) == sizeof(FhevcPRule), "P rule layout");
+  FhevcPRule r;   // read here, handed to the kernel by value: the caller's struct is free again when this call returns
+  if (rule) std::memcpy(&r, rule, sizeof r);
+  else { fhevc_p_rule d; fhevc_p_rule_default(&d); std::memcpy(&r, &d, sizeof r); }
+  (void)hipSetDevice(c->device);
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  const FhevcFrames fr = frames_of(c, nullptr, 1, c->cfg.width, 0, num_pictures, ctu_row_begin, ctu_row_end, qp);
+  time_begin(c, st, 5);
+  HIP_TRY(c, fhevc_launch_p_rule(fr, prev_mode, r, reinterpret_cast<const FhevcMotionNode*>(d_nodes), d_prev_maps, d_depth_min, d_depth_max, c->num_cus, st));
+  time_end(c, st);
+  c->stats.kernels_launched++;
+  return FHEVC_OK;
+}
+
+int fhevc_p_predict_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                          const uint8_t* prev_map, int prev_mode, const fhevc_p_rule* rule, uint8_t* depth_min, uint8_t* depth_max)
+{
+  if (!c || !cur_luma || !ref_luma || !prev_map || !depth_min || !depth_max || stride_samples < c->cfg.width) return FHEVC_E_INVALID;
+  if (prev_mode != FHEVC_P_PREV_COLOCATED && prev_mode != FHEVC_P_PREV_UNIT && prev_mode != FHEVC_P_PREV_NODE)
+    return fail(c, FHEVC_E_INVALID, "prev_mode: FHEVC_P_PREV_COLOCATED, FHEVC_P_PREV_UNIT or FHEVC_P_PREV_NODE");
+  (void)hipSetDevice(c->device);
+  const size_t plane = (size_t)c->dev_stride * c->ctus_y * 64, maps = (size_t)c->num_ctus * 256;
+  if (!c->d_pair) HIP_TRY(c, hipMalloc(&c->d_pair, 2 * plane * sizeof(int16_t)));
+  if (!c->d_motion) HIP_TRY(c, hipMalloc(&c->d_motion, (size_t)c->num_ctus * FHEVC_NODES * sizeof(FhevcMotionNode)));
+  if (!c->d_p_maps) HIP_TRY(c, hipMalloc(&c->d_p_maps, 3 * maps));
+  HIP_TRY(c, hipMemcpy2DAsync(c->d_pair, (size_t)c->dev_stride * 2, ref_luma, (size_t)stride_samples * 2, (size_t)c->cfg.width * 2,
+                              (size_t)c->cfg.height, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpy2DAsync(c->d_pair + plane, (size_t)c->dev_stride * 2, cur_luma, (size_t)stride_samples * 2, (size_t)c->cfg.width * 2,
+                              (size_t)c->cfg.height, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_p_maps, prev_map, maps, hipMemcpyHostToDevice, c->stream));
+  c->stats.bytes_h2d += (uint64_t)c->cfg.width * c->cfg.height * 4 + maps;
+  int rc = fhevc_motion_search_device(c, c->d_pair, 2, c->dev_stride, (long long)plane, 2, 0, c->ctus_y, qp, search_range,
+                                      reinterpret_cast<fhevc_motion_node*>(c->d_motion), c->stream);
+  if (rc == FHEVC_OK)
+    rc = fhevc_p_depth_range_device(c, reinterpret_cast<const fhevc_motion_node*>(c->d_motion), c->d_p_maps, 1, 0, c->ctus_y, qp, prev_mode, rule,
+                                    c->d_p_maps + maps, c->d_p_maps + 2 * maps, c->stream);
+  if (rc != FHEVC_OK) { (void)hipStreamSynchronize(c->stream); return rc; }   // the uploads read the caller's buffers: through before the call returns
+  HIP_TRY(c, hipMemcpyAsync(depth_min, c->d_p_maps + maps, maps, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(depth_max, c->d_p_maps + 2 * maps, maps, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->stats.bytes_d2h += 2 * maps;
   return FHEVC_OK;
 }
 

@@ -178,6 +178,14 @@ hipError_t fhevc_launch_motion_big(const FhevcFrames& fr, int range, const uint3
                                     { 1152, -30, -842, -103, 866, 1285, 415, -455, -48, 19539 },     \
                                     { 255, 36, -3, 16, 643, 1206, 0, -243, -177, 342124 } }
 
+// ---- P-picture depth ranges on the device (k_p_rule.hip; config 4) --------------------------------------------
+// fhevc_p_rule of fasthevc.h; travels by value as a kernel argument, so every launch has its own rule
+struct FhevcPRule { int32_t w[3][10]; int32_t t_split[3], t_stop[3]; int32_t window; };
+// fr: geometry, band, num_frames = the P pictures of the batch, qp (luma is not read).  d_nodes: num_frames * band CTUs * 85 as fhevc_launch_motion* writes
+// them; d_prev_maps: num_frames whole-picture depth maps; prev_mode: FHEVC_P_PREV_*; d_depth_min / d_depth_max (may be null): compact over the band
+hipError_t fhevc_launch_p_rule(const FhevcFrames& fr, int prev_mode, const FhevcPRule& rule, const FhevcMotionNode* d_nodes, const uint8_t* d_prev_maps,
+                               uint8_t* d_depth_min, uint8_t* d_depth_max, int num_cus, hipStream_t stream);
+
 // ---- adaptive-QP pre-analysis (k_preanalyze.hip) -----------------------------------------------------------
 // d_activity: per frame parts_per_frame doubles, layers concatenated (layer d: ceil(H/P) x ceil(W/P), P = 64 >> d)
 hipError_t fhevc_launch_preanalyze(const FhevcFrames& fr, int layers, long long parts_per_frame, double* d_activity,

@@ -272,7 +272,7 @@ int  fhevc_motion_search_device(fhevc_ctx* ctx, const void* d_luma, int sample_b
  * score = sum w[level][i] * f_i + w[level][9]   (Q18).  depth_min follows the splits with score > t_split[level] top-down,
  * depth_max those with score >= -t_stop[level]; CUs crossing the picture edge are split in both, units outside get 0; then
  * both are clipped to the co-located depth +- window when window < 4.  The xCompressCU hook forces a split while depth <
- * depth_min and forbids one at depth >= depth_max (as for I pictures). */
+ * depth_min and forbids one at depth >= depth_max (as for I pictures).  Device form: fhevc_p_depth_range_device. */
 typedef struct {
   int32_t w[3][10];
   int32_t t_split[3], t_stop[3];
@@ -290,7 +290,7 @@ int  fhevc_p_depth_range(const fhevc_motion_node* nodes /* 85 */, const uint8_t*
  * of the 16x16 node the unit lies in (a node crossing the picture edge: the vector of its 32x32 node, then of the CTU, then zero),
  * positions clamped to the picture.  prev_map: numCtus * 256 depths of the reference picture (raster per CTU, as fhevc_predict_frame writes
  * them and TComDataCU::getDepth holds them); out: 256, the prev_depth argument of fhevc_p_depth_range.  With zero vectors this is the
- * co-located map.  Host-side integer logic, no device work, no context. */
+ * co-located map.  Host-side integer logic, no device work, no context.  Device form: fhevc_p_depth_range_device with FHEVC_P_PREV_UNIT. */
 int  fhevc_p_motion_compensated_depth(const fhevc_motion_node* nodes /* 85 */, const uint8_t* prev_map, int width, int height, int ctu,
                                       uint8_t* out /* 256 */);
 
@@ -300,14 +300,43 @@ int  fhevc_p_motion_compensated_depth(const fhevc_motion_node* nodes /* 85 */, c
  * parent's vector; the CTU node: zero): a node whose answer is not deeper than its own level becomes one CU of that depth, otherwise its four children are
  * asked (16x16 nodes: depth 2, or 3 when the answer is 3).  out is a quadtree-consistent partition on the CURRENT grid.  With zero vectors and a prev_map
  * that is itself a partition this is the co-located map.  Measured (profiles/r04_p_slice_node_*.json): one global pan of 32 samples per picture
- * -0.26 % BD-rate with the +-1 window where the per-unit form costs +1.76 % and the co-located map -0.10 %; elsewhere equal to the co-located map. */
+ * -0.26 % BD-rate with the +-1 window where the per-unit form costs +1.76 % and the co-located map -0.10 %; elsewhere equal to the co-located map.
+ * Device form: fhevc_p_depth_range_device with FHEVC_P_PREV_NODE. */
 int  fhevc_p_node_depth(const fhevc_motion_node* nodes /* 85 */, const uint8_t* prev_map, int width, int height, int ctu, uint8_t* out /* 256 */);
+
+/* The P-picture decision over a device-resident batch (k_p_rule.hip): one launch turns the motion nodes of num_pictures P pictures into their depth
+ * ranges, without the host in between.  Per CTU the same bits as the host functions above: the reference picture's depths as prev_mode says,
+ *   FHEVC_P_PREV_COLOCATED  the CTU's own 256 bytes of the reference map,
+ *   FHEVC_P_PREV_UNIT       fhevc_p_motion_compensated_depth,
+ *   FHEVC_P_PREV_NODE       fhevc_p_node_depth,
+ * then fhevc_p_depth_range with the valid width / height the context's geometry gives the CTU.
+ * d_nodes: num_pictures * band CTUs * 85 nodes, compact over the band: what fhevc_motion_search_device writes for the same (ctu_row_begin, ctu_row_end);
+ * its output for num_frames frames is the input for num_pictures = num_frames - 1.  d_prev_maps: WHOLE pictures, num_pictures * numCtus * 256 bytes
+ * (values 0..3), picture p of the batch is decided against map p; the two displaced modes read outside the band.  It must not overlap the outputs: a
+ * caller that chains picture by picture issues one call per picture on one stream.  d_depth_min / d_depth_max (may be NULL): compact over the band,
+ * entry ((p * band_rows + row - ctu_row_begin) * ctus_per_row + col) * 256, written over exactly that extent; an empty band writes nothing.
+ * rule: HOST memory, read during the call (it travels to the kernel by value, so calls with different rules may follow each other on any streams
+ * without synchronisation); NULL = fhevc_p_rule_default.  Stream semantics as fhevc_predict_frames_device (NULL = the context's blocking stream);
+ * asynchronous with respect to the host; runs on device_ids[0].  FHEVC_E_INVALID (nothing is launched or written): a null pointer other than rule
+ * and d_depth_max, num_pictures < 1, qp outside 0..51, an unknown prev_mode, a bad band. */
+#define FHEVC_P_PREV_COLOCATED 0
+#define FHEVC_P_PREV_UNIT      1
+#define FHEVC_P_PREV_NODE      2
+int  fhevc_p_depth_range_device(fhevc_ctx* ctx, const fhevc_motion_node* d_nodes, const uint8_t* d_prev_maps, int num_pictures,
+                                int ctu_row_begin, int ctu_row_end, int qp, int prev_mode, const fhevc_p_rule* rule,
+                                uint8_t* d_depth_min, uint8_t* d_depth_max, void* stream);
+/* One picture pair, host buffers, synchronous: uploads both planes (same stride) and prev_map (numCtus * 256, the reference picture's depths),
+ * searches (search_range and distortion as fhevc_motion_search), decides on the device and downloads only the two maps (numCtus * 256 each):
+ * 512 bytes per CTU come back instead of the 1 360 bytes of nodes. */
+int  fhevc_p_predict_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                           const uint8_t* prev_map, int prev_mode, const fhevc_p_rule* rule, uint8_t* depth_min, uint8_t* depth_max);
 
 /* CTU-row band of rank `rank` out of `world`: rows [begin, end) */
 int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
 
 /* average duration in ms of the dominant kernels over launches since the last reset, measured with HIP
- * events on the launch stream; which: 0 = depth CNN, 1 = source Hadamard, 2 = first pass, 3 = pre-analysis, 4 = motion search */
+ * events on the launch stream; which: 0 = depth CNN, 1 = source Hadamard, 2 = first pass, 3 = pre-analysis, 4 = motion search,
+ * 5 = P-picture depth ranges (fhevc_p_depth_range_device) */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
 int  fhevc_enable_kernel_timing(fhevc_ctx* ctx, int on);
 
