@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(HERE, "lib", "libfasthevc_hip.so")
 OK, E_INVALID, E_NO_DEVICE, E_HIP, E_WEIGHTS, E_NOMEM, E_STATE = 0, -1, -2, -3, -4, -5, -6
 BACKEND_HIP = 1
 NODES_PER_CTU = 85
+PUS4_PER_CTU = 256  # 4x4 PUs of a CTU, raster 16x16: the depth map's unit order
 LOGITS_PER_CTU = 42
 
 # every symbol include/fasthevc.h declares (tests/test_host_logic.py::test_c_abi_exports_every_declared_symbol checks header <-> this list <-> the .so)
@@ -27,6 +28,7 @@ SYMBOLS = [
     "fhevc_motion_search", "fhevc_motion_search_device", "fhevc_intra_first_pass_all", "fhevc_intra_first_pass_candidates", "fhevc_p_rule_default", "fhevc_p_rule_default_wide", "fhevc_p_depth_range", "fhevc_p_motion_compensated_depth", "fhevc_p_node_depth",
     "fhevc_predict_frames", "fhevc_alloc_host", "fhevc_free_host", "fhevc_set_cnn_arith", "fhevc_get_cnn_arith", "fhevc_set_motion_distortion", "fhevc_read_yuv_luma",
     "fhevc_p_depth_range_device", "fhevc_p_predict_frame",
+    "fhevc_intra_first_pass_4x4", "fhevc_intra_first_pass_4x4_all", "fhevc_intra_first_pass_4x4_device", "fhevc_intra_first_pass_candidates_device",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -114,6 +116,12 @@ def load_library(path=None):
     lib.fhevc_intra_first_pass_candidates.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
     lib.fhevc_intra_first_pass_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int,
                                                   C.c_int, vp, vp]
+    lib.fhevc_intra_first_pass_4x4.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.fhevc_intra_first_pass_4x4_all.argtypes = [vp, vp, C.c_int, C.c_int, vp]
+    lib.fhevc_intra_first_pass_4x4_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int,
+                                                      C.c_int, C.c_int, vp, vp, vp]
+    lib.fhevc_intra_first_pass_candidates_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int,
+                                                             C.c_int, C.c_int, vp, vp]
     lib.fhevc_predict_frames_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int,
                                                 C.c_int, vp, vp, vp, vp, vp]
     lib.fhevc_expand_depth_flags_device.argtypes = [vp, vp, C.c_int, vp, vp]
@@ -404,6 +412,24 @@ class Context:
         self._check(self.lib.fhevc_intra_first_pass_candidates(self.h, flat.ctypes.data + 2 * origin, stride, qp, num_candidates, out.ctypes.data))
         return out.reshape(self.num_ctus, NODES_PER_CTU, num_candidates)
 
+    def intra_first_pass_4x4(self, plane, origin=0, stride=None, qp=32, num_candidates=8):
+        """The first pass of the 4x4 PUs of NxN CUs: (best [numCtus, 256] NODE_DTYPE, modes [numCtus, 256, num_candidates] uint8), PUs in raster
+        16x16 order per CTU; PUs whose 8x8 CU crosses the picture edge carry mode 255"""
+        flat = np.ascontiguousarray(plane).reshape(-1)
+        stride = stride if stride is not None else plane.shape[-1]
+        best = np.zeros(self.num_ctus * PUS4_PER_CTU, NODE_DTYPE)
+        modes = np.zeros(self.num_ctus * PUS4_PER_CTU * num_candidates, np.uint8)
+        self._check(self.lib.fhevc_intra_first_pass_4x4(self.h, flat.ctypes.data + 2 * origin, stride, qp, num_candidates, best.ctypes.data, modes.ctypes.data))
+        return best.reshape(self.num_ctus, PUS4_PER_CTU), modes.reshape(self.num_ctus, PUS4_PER_CTU, num_candidates)
+
+    def intra_first_pass_4x4_all(self, plane, origin=0, stride=None, qp=32):
+        """all [numCtus, 256, 35]: every mode's SATD and cost per 4x4 PU (parity entry point)"""
+        flat = np.ascontiguousarray(plane).reshape(-1)
+        stride = stride if stride is not None else plane.shape[-1]
+        allm = np.zeros(self.num_ctus * PUS4_PER_CTU * 35, NODE_DTYPE)
+        self._check(self.lib.fhevc_intra_first_pass_4x4_all(self.h, flat.ctypes.data + 2 * origin, stride, qp, allm.ctypes.data))
+        return allm.reshape(self.num_ctus, PUS4_PER_CTU, 35)
+
     def aq_layout(self, max_aq_depth):
         """Offsets of the AQ layers in the concatenated activity array (max_aq_depth + 1 entries)."""
         off = (C.c_longlong * (max_aq_depth + 1))()
@@ -444,6 +470,21 @@ class Context:
         rb, re = rows if rows is not None else (0, self.ctus_y)
         self._check(self.lib.fhevc_intra_first_pass_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames,
                                                            rb, re, qp, d_out, stream))
+
+    def intra_first_pass_4x4_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_best=None, d_modes=None, rows=None,
+                                    stream=None, qp=32, num_candidates=8):
+        """d_best: device buffer of num_frames * band CTUs * 256 NODE_DTYPE entries, d_modes: num_frames * band CTUs * 256 * num_candidates
+        bytes; either may be None, not both; asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_intra_first_pass_4x4_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames,
+                                                               rb, re, qp, num_candidates, d_best, d_modes, stream))
+
+    def intra_first_pass_candidates_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_modes, rows=None,
+                                           stream=None, qp=32, num_candidates=8):
+        """d_modes: device buffer of num_frames * band CTUs * 85 * num_candidates bytes (intra_first_pass_candidates per picture); asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_intra_first_pass_candidates_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames,
+                                                                      rb, re, qp, num_candidates, d_modes, stream))
 
     def predict_frames_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_depth, d_hadamard=None,
                               d_logits=None, rows=None, stream=None, qp=32, d_flags=None):

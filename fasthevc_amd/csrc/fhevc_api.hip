@@ -59,13 +59,14 @@ struct fhevc_ctx {
   bool timing = false;
   std::vector<TimedLaunch> pending;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-  double sum_ms[6] = { 0, 0, 0, 0, 0, 0 };
-  uint64_t launches[6] = { 0, 0, 0, 0, 0, 0 };
+  double sum_ms[7] = { 0, 0, 0, 0, 0, 0, 0 };
+  uint64_t launches[7] = { 0, 0, 0, 0, 0, 0, 0 };
   double* d_act = nullptr;
   int16_t* d_pair = nullptr;          // two staging planes (reference, current) of fhevc_motion_search
   FhevcMotionNode* d_motion = nullptr;
   uint8_t* d_p_maps = nullptr;        // fhevc_p_predict_frame: the reference picture's map, depth_min, depth_max (numCtus * 256 each)
   FhevcNodeCost* d_cand_all = nullptr; uint8_t* d_cand = nullptr;   // fhevc_intra_first_pass_candidates: every (node, mode) cost, the lists
+  FhevcNodeCost* d_best4 = nullptr; uint8_t* d_modes4 = nullptr;    // fhevc_intra_first_pass_4x4: the best mode and the list of every 4x4 PU
   uint32_t* d_mvtab = nullptr;        // vector costs of the wide search (k_motion_wide.hip), rebuilt when (qp, range) changes
   int mvtab_qp = -1, mvtab_range = -1;
   std::vector<uint32_t> mvtab_host;
@@ -760,7 +761,7 @@ void fhevc_destroy(fhevc_ctx* c)
   (void)hipFree(c->d_frag); (void)hipFree(c->d_bias); (void)hipFree(c->d_whead); (void)hipFree(c->d_bhead);
   (void)hipFree(c->d_frag_i8); (void)hipFree(c->d_bias_i8);
   (void)hipFree(c->f_frag1); (void)hipFree(c->f_bias1); (void)hipFree(c->f_frag2); (void)hipFree(c->f_frag3); (void)hipFree(c->f_bias_i8); (void)hipFree(c->f_whead); (void)hipFree(c->f_headm); (void)hipFree(c->f_bhead);
-  (void)hipFree(c->d_luma); (void)hipFree(c->d_depth); (void)hipFree(c->d_had); (void)hipFree(c->d_nodes); (void)hipFree(c->d_satd); (void)hipFree(c->d_satd_out); (void)hipFree(c->d_act); (void)hipFree(c->d_depth_max); (void)hipFree(c->d_pair); (void)hipFree(c->d_motion); (void)hipFree(c->d_p_maps); (void)hipFree(c->d_mvtab); (void)hipFree(c->d_cand_all); (void)hipFree(c->d_cand);
+  (void)hipFree(c->d_luma); (void)hipFree(c->d_depth); (void)hipFree(c->d_had); (void)hipFree(c->d_nodes); (void)hipFree(c->d_satd); (void)hipFree(c->d_satd_out); (void)hipFree(c->d_act); (void)hipFree(c->d_depth_max); (void)hipFree(c->d_pair); (void)hipFree(c->d_motion); (void)hipFree(c->d_p_maps); (void)hipFree(c->d_mvtab); (void)hipFree(c->d_cand_all); (void)hipFree(c->d_cand); (void)hipFree(c->d_best4); (void)hipFree(c->d_modes4);
   for (void* q : c->lw_bufs) (void)hipFree(q);
   for (auto& sl : c->slot) {  // the host-batch ring of fhevc_predict_frames: stream, device buffers, pinned staging
     if (sl.st) { (void)hipStreamSynchronize(sl.st); (void)hipStreamDestroy(sl.st); }
@@ -818,7 +819,7 @@ int fhevc_enable_kernel_timing(fhevc_ctx* c, int on)
 
 int fhevc_kernel_timing(fhevc_ctx* c, int which, int reset, double* avg_ms, uint64_t* launches)
 {
-  if (!c || which < 0 || which > 5) return FHEVC_E_INVALID;
+  if (!c || which < 0 || which > 6) return FHEVC_E_INVALID;
   time_resolve(c);
   if (avg_ms) *avg_ms = c->launches[which] ? c->sum_ms[which] / (double)c->launches[which] : 0.0;
   if (launches) *launches = c->launches[which];
@@ -1409,6 +1410,97 @@ int fhevc_intra_first_pass_device(fhevc_ctx* c, const void* d_luma, int sample_b
   const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end);
   time_begin(c, st, 2);
   HIP_TRY(c, fhevc_launch_first_pass(fr, sqrt_lambda, reinterpret_cast<FhevcNodeCost*>(d_out), nullptr, st));
+  time_end(c, st);
+  c->stats.kernels_launched++;
+  return FHEVC_OK;
+}
+
+// ---- first pass of the 4x4 PUs of NxN CUs (k_firstpass4.hip) ----
+
+// what every first-pass entry point over a device-resident batch checks before it launches anything
+static bool first_pass_batch_ok(const fhevc_ctx* c, int sample_bytes, int stride_samples, int num_frames, int ctu_row_begin, int ctu_row_end, int qp)
+{
+  return (sample_bytes == 1 || sample_bytes == 2) && stride_samples >= c->cfg.width && num_frames >= 1 && qp >= 0 && qp <= 51 &&
+         ctu_row_begin >= 0 && ctu_row_end <= c->ctus_y && ctu_row_begin <= ctu_row_end;
+}
+
+int fhevc_intra_first_pass_4x4_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                      int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int num_candidates, fhevc_node_cost* d_best,
+                                      uint8_t* d_modes, void* stream)
+{
+  if (!c || !d_luma || (!d_best && !d_modes)) return FHEVC_E_INVALID;
+  if (!first_pass_batch_ok(c, sample_bytes, stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp) || (d_modes && (num_candidates < 1 || num_candidates > 8)))
+    return fail(c, FHEVC_E_INVALID, "bad 4x4 first-pass arguments");
+  if (sample_bytes == 1 && c->cfg.bit_depth != 8) return fail(c, FHEVC_E_INVALID, "uint8 samples need bit depth 8");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
+  (void)hipSetDevice(c->device);
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  const double sqrt_lambda = std::sqrt(0.57 * std::pow(2.0, ((double)qp - 12.0) / 3.0));
+  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end);
+  time_begin(c, st, 6);
+  HIP_TRY(c, fhevc_launch_first_pass4(fr, sqrt_lambda, d_modes ? num_candidates : 0, reinterpret_cast<FhevcNodeCost*>(d_best), d_modes, nullptr, st));
+  time_end(c, st);
+  c->stats.kernels_launched++;
+  return FHEVC_OK;
+}
+
+int fhevc_intra_first_pass_4x4(fhevc_ctx* c, const int16_t* luma, int stride_samples, int qp, int num_candidates, fhevc_node_cost* best, uint8_t* modes)
+{
+  if (!c || !luma || (!best && !modes) || stride_samples < c->cfg.width || qp < 0 || qp > 51 || (modes && (num_candidates < 1 || num_candidates > 8)))
+    return FHEVC_E_INVALID;
+  (void)hipSetDevice(c->device);
+  const size_t pus = (size_t)c->num_ctus * FHEVC_PUS4_PER_CTU;
+  if (!c->d_best4) HIP_TRY(c, hipMalloc(&c->d_best4, pus * sizeof(FhevcNodeCost)));
+  if (!c->d_modes4) HIP_TRY(c, hipMalloc(&c->d_modes4, pus * 8));
+  int rc = upload_frame(c, luma, stride_samples);
+  if (rc != FHEVC_OK) return rc;
+  rc = fhevc_intra_first_pass_4x4_device(c, c->d_luma, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, num_candidates, best ? reinterpret_cast<fhevc_node_cost*>(c->d_best4) : nullptr,
+                                         modes ? c->d_modes4 : nullptr, c->stream);
+  if (rc != FHEVC_OK) return rc;
+  if (best) HIP_TRY(c, hipMemcpyAsync(best, c->d_best4, pus * sizeof(FhevcNodeCost), hipMemcpyDeviceToHost, c->stream));
+  if (modes) HIP_TRY(c, hipMemcpyAsync(modes, c->d_modes4, pus * num_candidates, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->stats.bytes_d2h += (best ? pus * sizeof(FhevcNodeCost) : 0) + (modes ? pus * num_candidates : 0);
+  return FHEVC_OK;
+}
+
+int fhevc_intra_first_pass_4x4_all(fhevc_ctx* c, const int16_t* luma, int stride_samples, int qp, fhevc_node_cost* all)
+{
+  if (!c || !luma || !all || stride_samples < c->cfg.width || qp < 0 || qp > 51) return FHEVC_E_INVALID;
+  (void)hipSetDevice(c->device);
+  const size_t n_all = (size_t)c->num_ctus * FHEVC_PUS4_PER_CTU * 35;
+  FhevcNodeCost* d_all = nullptr;  // a parity entry point: allocated per call
+  HIP_TRY(c, hipMalloc(&d_all, n_all * sizeof(FhevcNodeCost)));
+  int rc = upload_frame(c, luma, stride_samples);
+  if (rc == FHEVC_OK) {
+    const double sqrt_lambda = std::sqrt(0.57 * std::pow(2.0, ((double)qp - 12.0) / 3.0));
+    const FhevcFrames fr = frames_of(c, c->d_luma, 2, c->dev_stride, 0, 1, 0, c->ctus_y);
+    hipError_t e = fhevc_launch_first_pass4(fr, sqrt_lambda, 0, nullptr, nullptr, d_all, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(all, d_all, n_all * sizeof(FhevcNodeCost), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) rc = fail(c, FHEVC_E_HIP, "4x4 first pass (all modes)", e);
+  }
+  (void)hipFree(d_all);
+  c->stats.kernels_launched++;
+  return rc;
+}
+
+// the lists of the 85 nodes over a device-resident batch: selected inside the 85-node kernel, so no (node, mode) table and nothing that two
+// streams could share
+int fhevc_intra_first_pass_candidates_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                             int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int num_candidates, uint8_t* d_modes, void* stream)
+{
+  if (!c || !d_luma || !d_modes) return FHEVC_E_INVALID;
+  if (!first_pass_batch_ok(c, sample_bytes, stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp) || num_candidates < 1 || num_candidates > 8)
+    return fail(c, FHEVC_E_INVALID, "bad first-pass arguments");
+  if (sample_bytes == 1 && c->cfg.bit_depth != 8) return fail(c, FHEVC_E_INVALID, "uint8 samples need bit depth 8");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
+  (void)hipSetDevice(c->device);
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  const double sqrt_lambda = std::sqrt(0.57 * std::pow(2.0, ((double)qp - 12.0) / 3.0));
+  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end);
+  time_begin(c, st, 2);
+  HIP_TRY(c, fhevc_launch_first_pass(fr, sqrt_lambda, nullptr, nullptr, st, d_modes, num_candidates));
   time_end(c, st);
   c->stats.kernels_launched++;
   return FHEVC_OK;

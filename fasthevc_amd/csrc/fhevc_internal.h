@@ -140,10 +140,17 @@ hipError_t fhevc_launch_satd(const int16_t* d_org, int org_stride, const int16_t
 // ---- 35-mode first pass (k_firstpass.hip) ------------------------------------------------------------------
 struct FhevcNodeCost { uint32_t satd; uint32_t mode; double cost; };
 // d_all (optional): every (node, mode) pair, [CTU][85][35] -- the parity output behind fhevc_intra_first_pass_all
-hipError_t fhevc_launch_first_pass(const FhevcFrames& fr, double sqrt_lambda, FhevcNodeCost* d_out, FhevcNodeCost* d_all, hipStream_t stream);
+// d_modes (optional): the candidate lists, [CTU][85][num_modes], selected inside the kernel (no table in HBM); d_out may then be null
+hipError_t fhevc_launch_first_pass(const FhevcFrames& fr, double sqrt_lambda, FhevcNodeCost* d_out, FhevcNodeCost* d_all, hipStream_t stream,
+                                   uint8_t* d_modes = nullptr, int num_modes = 0);
 
 // the K (<= 8) cheapest modes per node out of d_all, best first (candidate lists of fhevc_intra_first_pass_candidates)
 hipError_t fhevc_launch_first_pass_topk(const FhevcNodeCost* d_all, long long nodes, int k, uint8_t* d_modes, hipStream_t stream);
+
+// ---- 35-mode first pass of the 256 4x4 PUs of a CTU (k_firstpass4.hip) ---------------------------------------
+// d_best [CTU][256], d_modes [CTU][256][num_modes] (1..8), d_all [CTU][256][35]: each may be null; PUs in raster 16x16 order
+hipError_t fhevc_launch_first_pass4(const FhevcFrames& fr, double sqrt_lambda, int num_modes, FhevcNodeCost* d_best, uint8_t* d_modes, FhevcNodeCost* d_all,
+                                    hipStream_t stream);
 
 // ---- source-only motion search per CU node (k_motion.hip; config 4) -----------------------------------------
 #define FHEVC_NODES 85

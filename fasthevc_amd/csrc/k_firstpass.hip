@@ -23,8 +23,15 @@
 //   * negative-angle modes read a per-wave projected main reference (HM's refMain extension) built once per
 //     (mode, level); tile SATDs meet per node through lane shuffles, no atomics.
 #include "fhevc_internal.h"
+#include "k_firstpass_common.h"
 
 namespace {
+
+using fhevc_fp::cand_init;
+using fhevc_fp::cand_insert;
+using fhevc_fp::stage_ctu;
+using fhevc_fp::staged;
+using fhevc_fp::unit_available;
 
 typedef __attribute__((ext_vector_type(2))) unsigned short u16x2;
 typedef __attribute__((ext_vector_type(2))) short i16x2;
@@ -42,23 +49,6 @@ __constant__ int c_angTable[9] = { 0, 2, 5, 9, 13, 17, 21, 26, 32 };
 __constant__ int c_invAngTable[9] = { 0, 4096, 1638, 910, 630, 482, 390, 315, 256 };
 __constant__ int c_filterThr[5] = { 10, 7, 1, 0, 10 };  // TComPrediction.cpp:50-58 (4,8,16,32,64)
 
-// raster 16x16 -> z-order (Morton) of the 4x4 units of a CTU (TComRom.cpp:290-323)
-__device__ __forceinline__ int zorder_of(int ux, int uy)
-{
-  int z = 0;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) z |= (((ux >> b) & 1) << (2 * b)) | (((uy >> b) & 1) << (2 * b + 1));
-  return z;
-}
-
-__device__ __forceinline__ bool unit_available(int ux, int uy, int x0, int y0, int width, int height, int ctus_x)
-{
-  if (ux < 0 || uy < 0 || ux >= width || uy >= height) return false;
-  const int ca = (uy >> 6) * ctus_x + (ux >> 6), cb = (y0 >> 6) * ctus_x + (x0 >> 6);
-  if (ca != cb) return ca < cb;
-  return zorder_of((ux & 63) >> 2, (uy & 63) >> 2) < zorder_of((x0 & 63) >> 2, (y0 & 63) >> 2);
-}
-
 // position (ux, uy) of 4-sample unit u of a node at (x0, y0) of size n, in HM's walk order: bottom-left unit first,
 // then up the left column, the top-left corner (one sample), then the row above left to right
 __device__ __forceinline__ void unit_pos(int u, int n, int x0, int y0, int& ux, int& uy)
@@ -67,14 +57,6 @@ __device__ __forceinline__ void unit_pos(int u, int n, int x0, int y0, int& ux, 
   if (u < L) { ux = x0 - 4; uy = y0 + 4 * (L - 1 - u); }
   else if (u == L) { ux = x0 - 4; uy = y0 - 4; }
   else { ux = x0 + 4 * (u - L - 1); uy = y0 - 4; }
-}
-
-// a sample that an AVAILABLE unit covers: inside this CTU, in the row above it, or in the column left of it
-__device__ __forceinline__ short staged(const short* s_org, const short* s_above, const short* s_left, int px, int py, int ox, int oy)
-{
-  if (py >= oy && px >= ox) return s_org[(py - oy) * 64 + (px - ox)];
-  if (py < oy) return s_above[px - ox + 1];
-  return s_left[py - oy];
 }
 
 __device__ __forceinline__ void wht8x8(int d[64])
@@ -222,9 +204,11 @@ __device__ __forceinline__ int satd8x8(const unsigned (&o)[32], const unsigned (
   return PACKED ? satd8x8_packed(o, p) : satd8x8_wide(o, p);
 }
 
-template <typename T, bool PACKED>
+// LISTS: the candidate lists are selected here (out_modes); without it the two arguments are dead and the kernel is the one it was before they existed
+template <typename T, bool PACKED, bool LISTS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKED ? 3 : 1, PACKED ? 3 : 2))) void fhevc_first_pass_kernel(FhevcFrames F, double sqrt_lambda,
-                                                                FhevcNodeCost* __restrict__ out, FhevcNodeCost* __restrict__ out_all)
+                                                                FhevcNodeCost* __restrict__ out, FhevcNodeCost* __restrict__ out_all,
+                                                                uint8_t* __restrict__ out_modes, int num_modes)
 {
   // s_org holds the CTU while the lines are built; afterwards the same bytes are the four per-wave projected references
   __shared__ __attribute__((aligned(16))) short s_org[4 * kMainPerWave];
@@ -257,33 +241,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKED ? 3 
 
     // ---- A1: stage the CTU (16 samples per thread), the row above (129 samples) and the left column (64) ----
     {
-      const int row = tid >> 2, seg = (tid & 3) * 16;
-      const int y = oy + row;
-      const T* src = frame + (long long)y * F.stride + ox + seg;
-      short* dst = &s_org[row * 64 + seg];
-      const bool whole = y < F.height && ox + seg + 16 <= F.width;
-      if (whole && sizeof(T) == 2 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
-        reinterpret_cast<uint4*>(dst)[0] = reinterpret_cast<const uint4*>(src)[0];
-        reinterpret_cast<uint4*>(dst)[1] = reinterpret_cast<const uint4*>(src)[1];
-      } else if (whole && sizeof(T) == 1 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
-        const uint4 q = *reinterpret_cast<const uint4*>(src);
-        const unsigned w[4] = { q.x, q.y, q.z, q.w };
-        unsigned o8[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o8[k] = ((w[k >> 1] >> (16 * (k & 1))) & 0xFF) | (((w[k >> 1] >> (16 * (k & 1) + 8)) & 0xFF) << 16);
-        reinterpret_cast<uint4*>(dst)[0] = make_uint4(o8[0], o8[1], o8[2], o8[3]);
-        reinterpret_cast<uint4*>(dst)[1] = make_uint4(o8[4], o8[5], o8[6], o8[7]);
-      } else {
-#pragma unroll 4
-        for (int k = 0; k < 16; ++k) dst[k] = (y < F.height && ox + seg + k < F.width) ? (short)src[k] : (short)0;
-      }
-      if (tid < 129) {
-        const int x = ox - 1 + tid;
-        s_above[tid] = (oy > 0 && x >= 0 && x < F.width) ? (short)frame[(long long)(oy - 1) * F.stride + x] : (short)0;
-      } else if (tid >= 192) {
-        const int yl = oy + tid - 192;
-        s_left[tid - 192] = (ox > 0 && yl < F.height) ? (short)frame[(long long)yl * F.stride + ox - 1] : (short)0;
-      }
+      stage_ctu<T>(frame, F, ox, oy, tid, s_org, s_above, s_left);
       if (tid < 85) {
         const int level = tid < 1 ? 0 : (tid < 5 ? 1 : (tid < 21 ? 2 : 3));
         const int n = 64 >> level, cnt = 1 << level, ni = tid - node_off(level);
@@ -518,7 +476,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKED ? 3 
         }
       }
       const long long o = (long long)(f * band_rows + (cy - F.row_begin)) * F.ctus_x + cx;
-      out[o * 85 + tid] = r;
+      if (out != nullptr) out[o * 85 + tid] = r;
+      if (LISTS && out_modes != nullptr) {  // the node's candidate list, selected here from LDS: no (node, mode) table in HBM, nothing shared between launches
+        double cost[8];
+        uint8_t mode[8];
+        cand_init(cost, mode);
+        for (int m = 0; m < 35 && s_valid[tid]; ++m) {
+          const unsigned sd = (unsigned)s_satd[tid * 35 + m] >> (bd - 8);
+          const int bits = (m == 0) ? 2 : ((m == 1 || m == 26) ? 3 : 6);
+          cand_insert(cost, mode, __dadd_rn((double)sd, __dmul_rn((double)bits, sqrt_lambda)), m);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) if (i < num_modes) out_modes[(o * 85 + tid) * num_modes + i] = mode[i];
+      }
     }
     if (out_all != nullptr) {  // parity output: every (node, mode) pair, not only the winner
       const long long o = (long long)(f * band_rows + (cy - F.row_begin)) * F.ctus_x + cx;
@@ -548,19 +518,9 @@ __global__ __launch_bounds__(256) void fhevc_first_pass_topk_kernel(const FhevcN
   const FhevcNodeCost* a = all + n * 35;
   double cost[8];
   uint8_t mode[8];
-  for (int i = 0; i < 8; ++i) { cost[i] = 1e300; mode[i] = 255; }
+  cand_init(cost, mode);
   const bool edge = a[0].satd == 0xFFFFFFFFu;
-  for (int m = 0; m < 35 && !edge; ++m) {
-    const double c = a[m].cost;
-    // insert behind every entry of smaller or EQUAL cost: the earlier mode keeps its place
-    int pos = 8;
-#pragma unroll
-    for (int i = 7; i >= 0; --i) if (c < cost[i]) pos = i;
-#pragma unroll
-    for (int i = 7; i > 0; --i) if (i > pos) { cost[i] = cost[i - 1]; mode[i] = mode[i - 1]; }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) if (i == pos) { cost[i] = c; mode[i] = (uint8_t)m; }
-  }
+  for (int m = 0; m < 35 && !edge; ++m) cand_insert(cost, mode, a[m].cost, m);
   for (int i = 0; i < k; ++i) modes[n * k + i] = mode[i];
 }
 
@@ -573,17 +533,22 @@ hipError_t fhevc_launch_first_pass_topk(const FhevcNodeCost* d_all, long long no
   return hipGetLastError();
 }
 
-hipError_t fhevc_launch_first_pass(const FhevcFrames& fr, double sqrt_lambda, FhevcNodeCost* d_out, FhevcNodeCost* d_all, hipStream_t stream)
+hipError_t fhevc_launch_first_pass(const FhevcFrames& fr, double sqrt_lambda, FhevcNodeCost* d_out, FhevcNodeCost* d_all, hipStream_t stream, uint8_t* d_modes,
+                                   int num_modes)
 {
   const long long total = (long long)(fr.row_end - fr.row_begin) * fr.ctus_x * fr.num_frames;
   if (total <= 0) return hipSuccess;
   const int grid = (int)(total < 2048 ? total : 2048);
   const bool packed = fr.bit_depth <= 10;
+  const bool lists = d_modes != nullptr;
+#define FHEVC_FP_LAUNCH(T, PACKED, LISTS) \
+  hipLaunchKernelGGL((fhevc_first_pass_kernel<T, PACKED, LISTS>), dim3(grid), dim3(256), 0, stream, fr, sqrt_lambda, d_out, d_all, d_modes, num_modes)
   if (fr.sample_bytes == 2) {
-    if (packed) hipLaunchKernelGGL((fhevc_first_pass_kernel<int16_t, true>), dim3(grid), dim3(256), 0, stream, fr, sqrt_lambda, d_out, d_all);
-    else hipLaunchKernelGGL((fhevc_first_pass_kernel<int16_t, false>), dim3(grid), dim3(256), 0, stream, fr, sqrt_lambda, d_out, d_all);
+    if (packed) { if (lists) FHEVC_FP_LAUNCH(int16_t, true, true); else FHEVC_FP_LAUNCH(int16_t, true, false); }
+    else { if (lists) FHEVC_FP_LAUNCH(int16_t, false, true); else FHEVC_FP_LAUNCH(int16_t, false, false); }
   } else {
-    hipLaunchKernelGGL((fhevc_first_pass_kernel<uint8_t, true>), dim3(grid), dim3(256), 0, stream, fr, sqrt_lambda, d_out, d_all);
+    if (lists) FHEVC_FP_LAUNCH(uint8_t, true, true); else FHEVC_FP_LAUNCH(uint8_t, true, false);
   }
+#undef FHEVC_FP_LAUNCH
   return hipGetLastError();
 }

@@ -170,6 +170,37 @@ int  fhevc_intra_first_pass_device(fhevc_ctx* ctx, const void* d_luma, int sampl
                                    long long frame_stride_samples, int num_frames, int ctu_row_begin, int ctu_row_end,
                                    int qp, fhevc_node_cost* d_out, void* stream);
 
+/* The same first pass one level down: the four 4x4 PUs of every 8x8 CU, what HM's xCheckRDCostIntra(SIZE_NxN) runs through estIntraPredLumaQT
+ * (35 modes per PU with xCalcHADs4x4, eight candidates kept: TEncSearch.cpp:2271-2320).  Per CTU 256 PUs in the depth map's unit order: PU
+ * (ux, uy), raster 16x16, is the 4x4 block at (64 cx + 4 ux, 64 cy + 4 uy).  A PU is valid iff the 8x8 CU that holds it lies wholly inside the
+ * picture (HM codes NxN only in whole 8x8 CUs); the others carry satd 0xFFFFFFFF, mode 255, cost -1 and 255 in every list slot.  Reference
+ * samples (17 per PU) from the ORIGINAL plane with coding-order availability per 4-sample unit -- so inside one 8x8 CU PU 1 has no below-left,
+ * PU 3 no above-right, and PU 2's above-right is PU 1 --; no smoothed line at this size; SATD, cost, mode-bit model and tie rule as above.
+ * The lists are selected inside the kernel: per CTU 4 KB (best) and 256 * num_candidates bytes (lists) reach HBM.  The xCompressCU hook of
+ * hm_patch/ does not consume these lists yet. */
+#define FHEVC_PUS4_PER_CTU 256   /* raster 16x16 of 4x4 units: the depth map's unit order */
+
+/* one picture, host buffers, synchronous.  best: numCtus * 256, or NULL; modes: numCtus * 256 * num_candidates
+ * bytes, or NULL (then num_candidates is ignored); both NULL: FHEVC_E_INVALID */
+int  fhevc_intra_first_pass_4x4(fhevc_ctx* ctx, const int16_t* luma, int stride_samples, int qp, int num_candidates,
+                                fhevc_node_cost* best, uint8_t* modes);
+/* parity entry point: all = numCtus * 256 * 35 entries [CTU][PU][mode], as fhevc_intra_first_pass_all */
+int  fhevc_intra_first_pass_4x4_all(fhevc_ctx* ctx, const int16_t* luma, int stride_samples, int qp, fhevc_node_cost* all);
+/* device-resident batch, layout / band / stream arguments as fhevc_intra_first_pass_device; outputs compact over
+ * the band: d_best (num_frames * band CTUs) * 256 entries, d_modes (num_frames * band CTUs) * 256 * num_candidates bytes, written over exactly
+ * that extent; d_best or d_modes may be NULL, not both; asynchronous with respect to the host, no allocation.  FHEVC_E_INVALID (nothing is
+ * launched or written): a null plane, both outputs NULL, num_candidates outside 1..8 when d_modes is given, qp outside 0..51,
+ * stride_samples < width, num_frames < 1, a bad band, uint8 planes on a context above 8 bit */
+int  fhevc_intra_first_pass_4x4_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples,
+                                       long long frame_stride_samples, int num_frames, int ctu_row_begin, int ctu_row_end,
+                                       int qp, int num_candidates, fhevc_node_cost* d_best, uint8_t* d_modes, void* stream);
+/* the lists of the 85 nodes for a device-resident batch (the device form of fhevc_intra_first_pass_candidates, same bytes picture by
+ * picture): d_modes = num_frames * band CTUs * 85 * num_candidates bytes, compact over the band.  Selected inside the first-pass kernel: no
+ * scratch in HBM, so calls on different streams may be in flight together.  Arguments, errors and stream semantics as above */
+int  fhevc_intra_first_pass_candidates_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples,
+                                              long long frame_stride_samples, int num_frames, int ctu_row_begin, int ctu_row_end,
+                                              int qp, int num_candidates, uint8_t* d_modes, void* stream);
+
 /* Device-resident batch: num_frames pictures already in HBM, CTU rows [ctu_row_begin, ctu_row_end) of each.
  * d_luma: sample_bytes = 2 -> int16 Pel plane(s) as HM lays them out, 1 -> uint8 (8-bit content);
  * frame f starts at d_luma + f * frame_stride_samples.  Outputs are device pointers, compact over the band:
@@ -336,7 +367,7 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
 
 /* average duration in ms of the dominant kernels over launches since the last reset, measured with HIP
  * events on the launch stream; which: 0 = depth CNN, 1 = source Hadamard, 2 = first pass, 3 = pre-analysis, 4 = motion search,
- * 5 = P-picture depth ranges (fhevc_p_depth_range_device) */
+ * 5 = P-picture depth ranges (fhevc_p_depth_range_device), 6 = first pass of the 4x4 PUs (fhevc_intra_first_pass_4x4*) */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
 int  fhevc_enable_kernel_timing(fhevc_ctx* ctx, int on);
 
