@@ -29,6 +29,7 @@ SYMBOLS = [
     "fhevc_predict_frames", "fhevc_alloc_host", "fhevc_free_host", "fhevc_set_cnn_arith", "fhevc_get_cnn_arith", "fhevc_set_motion_distortion", "fhevc_read_yuv_luma",
     "fhevc_p_depth_range_device", "fhevc_p_predict_frame",
     "fhevc_intra_first_pass_4x4", "fhevc_intra_first_pass_4x4_all", "fhevc_intra_first_pass_4x4_device", "fhevc_intra_first_pass_candidates_device",
+    "fhevc_motion_refine", "fhevc_motion_refine_device",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -59,6 +60,8 @@ class Stats(C.Structure):
 
 NODE_DTYPE = np.dtype([("satd", np.uint32), ("mode", np.uint32), ("cost", np.float64)])
 MOTION_DTYPE = np.dtype([("satd_zero", np.uint32), ("satd_best", np.uint32), ("cost_best", np.uint32), ("mvx", np.int16), ("mvy", np.int16)])
+# fhevc_motion_qpel_node: the vector in QUARTER samples
+MOTION_QPEL_DTYPE = np.dtype([("satd_int", np.uint32), ("satd_best", np.uint32), ("cost_best", np.uint32), ("mvx", np.int16), ("mvy", np.int16)])
 
 
 class FastHevcError(RuntimeError):
@@ -138,6 +141,8 @@ def load_library(path=None):
     lib.fhevc_get_cnn_arith.argtypes = [vp]
     lib.fhevc_motion_search.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     lib.fhevc_motion_search_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.fhevc_motion_refine.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.fhevc_motion_refine_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     lib.fhevc_p_rule_default.argtypes = [C.POINTER(PRule)]
     lib.fhevc_p_rule_default.restype = None
     lib.fhevc_p_rule_default_wide.argtypes = [C.POINTER(PRule)]
@@ -370,6 +375,28 @@ class Context:
         rb, re = rows if rows is not None else (0, self.ctus_y)
         self._check(self.lib.fhevc_motion_search_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp,
                                                         search_range, d_out, stream))
+
+    def motion_refine(self, cur_plane, ref_plane, nodes, origin=0, stride=None, qp=32, max_range=4):
+        """config 4: the quarter-sample refinement of nodes [numCtus, 85] (MOTION_DTYPE, as motion_search returns them for the same planes; only
+        mvx / mvy are read) -> [numCtus, 85] MOTION_QPEL_DTYPE.  max_range: the search's range (a longer vector gets the marker)."""
+        cur = np.ascontiguousarray(cur_plane).reshape(-1)
+        ref = np.ascontiguousarray(ref_plane).reshape(-1)
+        assert cur.dtype == np.int16 and ref.dtype == np.int16
+        nodes = np.ascontiguousarray(nodes).reshape(-1)
+        assert nodes.dtype.itemsize == 16 and nodes.size == self.num_ctus * NODES_PER_CTU
+        stride = stride if stride is not None else cur_plane.shape[-1]
+        out = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_QPEL_DTYPE)
+        self._check(self.lib.fhevc_motion_refine(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, max_range,
+                                                 nodes.ctypes.data, out.ctypes.data))
+        return out.reshape(self.num_ctus, NODES_PER_CTU)
+
+    def motion_refine_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_nodes, d_out, rows=None, stream=None, qp=32,
+                             max_range=4):
+        """frames 1.. of the batch, each refined in the frame before it, around the vectors of d_nodes (what motion_search_device wrote for the same
+        rows); d_out: (num_frames - 1) * band CTUs * 85 quarter-sample nodes (16 B).  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_motion_refine_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range,
+                                                        d_nodes, d_out, stream))
 
     def p_depth_range_device(self, d_nodes, d_prev_maps, num_pictures, d_depth_min, d_depth_max=None, rows=None, stream=None, qp=32,
                              prev_mode="colocated", rule=None):

@@ -59,11 +59,12 @@ struct fhevc_ctx {
   bool timing = false;
   std::vector<TimedLaunch> pending;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-  double sum_ms[7] = { 0, 0, 0, 0, 0, 0, 0 };
-  uint64_t launches[7] = { 0, 0, 0, 0, 0, 0, 0 };
+  double sum_ms[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+  uint64_t launches[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
   double* d_act = nullptr;
   int16_t* d_pair = nullptr;          // two staging planes (reference, current) of fhevc_motion_search
   FhevcMotionNode* d_motion = nullptr;
+  FhevcMotionQpelNode* d_qpel = nullptr;   // the output of fhevc_motion_refine (host form); its input nodes go through d_motion
   uint8_t* d_p_maps = nullptr;        // fhevc_p_predict_frame: the reference picture's map, depth_min, depth_max (numCtus * 256 each)
   FhevcNodeCost* d_cand_all = nullptr; uint8_t* d_cand = nullptr;   // fhevc_intra_first_pass_candidates: every (node, mode) cost, the lists
   FhevcNodeCost* d_best4 = nullptr; uint8_t* d_modes4 = nullptr;    // fhevc_intra_first_pass_4x4: the best mode and the list of every 4x4 PU
@@ -761,7 +762,7 @@ void fhevc_destroy(fhevc_ctx* c)
   (void)hipFree(c->d_frag); (void)hipFree(c->d_bias); (void)hipFree(c->d_whead); (void)hipFree(c->d_bhead);
   (void)hipFree(c->d_frag_i8); (void)hipFree(c->d_bias_i8);
   (void)hipFree(c->f_frag1); (void)hipFree(c->f_bias1); (void)hipFree(c->f_frag2); (void)hipFree(c->f_frag3); (void)hipFree(c->f_bias_i8); (void)hipFree(c->f_whead); (void)hipFree(c->f_headm); (void)hipFree(c->f_bhead);
-  (void)hipFree(c->d_luma); (void)hipFree(c->d_depth); (void)hipFree(c->d_had); (void)hipFree(c->d_nodes); (void)hipFree(c->d_satd); (void)hipFree(c->d_satd_out); (void)hipFree(c->d_act); (void)hipFree(c->d_depth_max); (void)hipFree(c->d_pair); (void)hipFree(c->d_motion); (void)hipFree(c->d_p_maps); (void)hipFree(c->d_mvtab); (void)hipFree(c->d_cand_all); (void)hipFree(c->d_cand); (void)hipFree(c->d_best4); (void)hipFree(c->d_modes4);
+  (void)hipFree(c->d_luma); (void)hipFree(c->d_depth); (void)hipFree(c->d_had); (void)hipFree(c->d_nodes); (void)hipFree(c->d_satd); (void)hipFree(c->d_satd_out); (void)hipFree(c->d_act); (void)hipFree(c->d_depth_max); (void)hipFree(c->d_pair); (void)hipFree(c->d_motion); (void)hipFree(c->d_qpel); (void)hipFree(c->d_p_maps); (void)hipFree(c->d_mvtab); (void)hipFree(c->d_cand_all); (void)hipFree(c->d_cand); (void)hipFree(c->d_best4); (void)hipFree(c->d_modes4);
   for (void* q : c->lw_bufs) (void)hipFree(q);
   for (auto& sl : c->slot) {  // the host-batch ring of fhevc_predict_frames: stream, device buffers, pinned staging
     if (sl.st) { (void)hipStreamSynchronize(sl.st); (void)hipStreamDestroy(sl.st); }
@@ -819,7 +820,7 @@ int fhevc_enable_kernel_timing(fhevc_ctx* c, int on)
 
 int fhevc_kernel_timing(fhevc_ctx* c, int which, int reset, double* avg_ms, uint64_t* launches)
 {
-  if (!c || which < 0 || which > 6) return FHEVC_E_INVALID;
+  if (!c || which < 0 || which > 7) return FHEVC_E_INVALID;
   time_resolve(c);
   if (avg_ms) *avg_ms = c->launches[which] ? c->sum_ms[which] / (double)c->launches[which] : 0.0;
   if (launches) *launches = c->launches[which];
@@ -1584,6 +1585,66 @@ int fhevc_motion_search(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* re
   HIP_TRY(c, hipMemcpyAsync(out, c->d_motion, (size_t)c->num_ctus * FHEVC_NODES * sizeof(FhevcMotionNode), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->stats.bytes_d2h += (uint64_t)c->num_ctus * FHEVC_NODES * sizeof(FhevcMotionNode);
+  return FHEVC_OK;
+}
+
+// ---- quarter-sample refinement of the search's vectors (k_motion_refine.hip) ----
+// getCost of every number of bits a quarter-sample vector can take, with HM's own arithmetic as mv_cost_table
+static FhevcMvBitCost mv_bit_cost_table(int qp)
+{
+  FhevcMvBitCost t;
+  const double motion_lambda = 65536.0 * std::sqrt(0.57 * std::pow(2.0, ((double)qp - 12.0) / 3.0));
+  for (int b = 0; b < FHEVC_MV_BIT_COSTS; ++b) t.c[b] = (uint32_t)((motion_lambda * (unsigned)b) / 65536.0);
+  return t;
+}
+
+int fhevc_motion_refine_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                               int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_node* d_nodes,
+                               fhevc_motion_qpel_node* d_out, void* stream)
+{
+  if (!c || !d_luma || !d_nodes || !d_out) return c ? fail(c, FHEVC_E_INVALID, "bad motion-refinement arguments") : FHEVC_E_INVALID;
+  if ((sample_bytes != 1 && sample_bytes != 2) || stride_samples < c->cfg.width || num_frames < 2 || qp < 0 || qp > 51 ||
+      ctu_row_begin < 0 || ctu_row_end > c->ctus_y || ctu_row_begin > ctu_row_end || max_range < 1 || max_range > FHEVC_MOTION_WIDE_MAX_RANGE)
+    return fail(c, FHEVC_E_INVALID, "bad motion-refinement arguments");
+  if (sample_bytes == 1 && c->cfg.bit_depth != 8) return fail(c, FHEVC_E_INVALID, "uint8 samples need bit depth 8");
+  if (frame_stride_samples < (long long)stride_samples * (c->cfg.height - 1) + c->cfg.width) return fail(c, FHEVC_E_INVALID, "frames overlap");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
+  (void)hipSetDevice(c->device);
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
+  static_assert(sizeof(fhevc_motion_qpel_node) == sizeof(FhevcMotionQpelNode) && sizeof(FhevcMotionQpelNode) == 16, "quarter-sample node layout");
+  time_begin(c, st, 7);
+  HIP_TRY(c, fhevc_launch_motion_refine(fr, max_range, mv_bit_cost_table(qp), reinterpret_cast<const FhevcMotionNode*>(d_nodes),
+                                        reinterpret_cast<FhevcMotionQpelNode*>(d_out), c->num_cus, st));
+  time_end(c, st);
+  c->stats.kernels_launched++;
+  return FHEVC_OK;
+}
+
+int fhevc_motion_refine(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                        const fhevc_motion_node* nodes, fhevc_motion_qpel_node* out)
+{
+  if (!c || !cur_luma || !ref_luma || !nodes || !out || stride_samples < c->cfg.width)
+    return c ? fail(c, FHEVC_E_INVALID, "bad motion-refinement arguments") : FHEVC_E_INVALID;
+  if (qp < 0 || qp > 51 || max_range < 1 || max_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad motion-refinement arguments");
+  (void)hipSetDevice(c->device);
+  const size_t plane = (size_t)c->dev_stride * c->ctus_y * 64;
+  const size_t nbytes = (size_t)c->num_ctus * FHEVC_NODES * sizeof(FhevcMotionNode);
+  if (!c->d_pair) HIP_TRY(c, hipMalloc(&c->d_pair, 2 * plane * sizeof(int16_t)));
+  if (!c->d_motion) HIP_TRY(c, hipMalloc(&c->d_motion, nbytes));
+  if (!c->d_qpel) HIP_TRY(c, hipMalloc(&c->d_qpel, nbytes));
+  HIP_TRY(c, hipMemcpy2DAsync(c->d_pair, (size_t)c->dev_stride * 2, ref_luma, (size_t)stride_samples * 2, (size_t)c->cfg.width * 2,
+                              (size_t)c->cfg.height, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpy2DAsync(c->d_pair + plane, (size_t)c->dev_stride * 2, cur_luma, (size_t)stride_samples * 2, (size_t)c->cfg.width * 2,
+                              (size_t)c->cfg.height, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_motion, nodes, nbytes, hipMemcpyHostToDevice, c->stream));
+  c->stats.bytes_h2d += (uint64_t)c->cfg.width * c->cfg.height * 4 + nbytes;
+  const int rc = fhevc_motion_refine_device(c, c->d_pair, 2, c->dev_stride, (long long)plane, 2, 0, c->ctus_y, qp, max_range,
+                                            reinterpret_cast<const fhevc_motion_node*>(c->d_motion), reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel), c->stream);
+  if (rc != FHEVC_OK) return rc;
+  HIP_TRY(c, hipMemcpyAsync(out, c->d_qpel, nbytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->stats.bytes_d2h += (uint64_t)nbytes;
   return FHEVC_OK;
 }
 

@@ -168,6 +168,17 @@ hipError_t fhevc_launch_motion_wide(const FhevcFrames& fr, int range, const uint
 // ... and for content ABOVE 8 bit (16-bit planes; round 4): fhevc_motion_kernel itself laid out for the +-64 window (k_motion.hip), the same d_mvtab
 hipError_t fhevc_launch_motion_big(const FhevcFrames& fr, int range, const uint32_t* d_mvtab, FhevcMotionNode* d_out, int num_cus, hipStream_t stream);
 
+// ---- quarter-sample refinement of the search's vectors (k_motion_refine.hip; config 4) --------------------------
+struct FhevcMotionQpelNode { uint32_t satd_int, satd_best, cost_best; int16_t mvx, mvy; };
+// getCost(bits) for every number of bits two exp-Golomb components of a quarter-sample vector up to +-(4 * 64 + 3) can take (at most 38), tabulated by
+// the host with HM's doubles; travels by value as a kernel argument, so every launch has its own lambda
+#define FHEVC_MV_BIT_COSTS 40
+struct FhevcMvBitCost { uint32_t c[FHEVC_MV_BIT_COSTS]; };
+// fr as fhevc_launch_motion; d_nodes: what it wrote for the same frames and band (only mvx / mvy are read; |component| > max_range: the marker);
+// d_out: (num_frames - 1) * band CTUs * 85
+hipError_t fhevc_launch_motion_refine(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_nodes, FhevcMotionQpelNode* d_out,
+                                      int num_cus, hipStream_t stream);
+
 // the shipped P-picture rule (fhevc_p_rule_default): see fasthevc.h; regenerate with tests/quality/fit_p_rule.py
 #define FHEVC_P_RULE_WEIGHTS { { 3101, 188, -94, 80, 1149, 1149, 3174, -138, 15748, -351620 }, \
                                { 594, 101, 375, -8, 1078, 1078, -197, 436, 3462, 256745 },      \

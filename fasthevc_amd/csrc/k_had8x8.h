@@ -1,0 +1,88 @@
+// k_had8x8.h -- the 8x8 Hadamard of a block held in one lane's registers, shared by the motion kernels (k_motion.hip: the integer search,
+// k_motion_refine.hip: the quarter-sample refinement).  Packed-16 form of k_hadamard.hip (|coefficients| stay below 2^15 through five stages
+// up to 10 bit; the sixth, inside a packed pair, is folded into the absolute sum: |a+b| + |a-b| = 2 max(|a|,|b|)) and its 32-bit twin.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace {
+
+typedef __attribute__((ext_vector_type(2))) short i16x2;
+__device__ __forceinline__ unsigned pk_add(unsigned a, unsigned b)
+{
+  return __builtin_bit_cast(unsigned, (i16x2)(__builtin_bit_cast(i16x2, a) + __builtin_bit_cast(i16x2, b)));
+}
+__device__ __forceinline__ unsigned pk_sub(unsigned a, unsigned b)
+{
+  return __builtin_bit_cast(unsigned, (i16x2)(__builtin_bit_cast(i16x2, a) - __builtin_bit_cast(i16x2, b)));
+}
+__device__ __forceinline__ unsigned pk_abs(unsigned a)
+{
+  const i16x2 v = __builtin_bit_cast(i16x2, a);
+  return __builtin_bit_cast(unsigned, __builtin_elementwise_max(v, (i16x2)(-v)));
+}
+// sum of |WHT8x8(d)| of a block held as 8 rows x 4 packed pairs (low half = even column), |samples| < 2^10
+__device__ __forceinline__ unsigned had8x8_packed(unsigned (&d)[32])
+{
+#pragma unroll
+  for (int hs = 1; hs < 8; hs <<= 1)  // vertical: rows y, y + hs
+#pragma unroll
+    for (int i = 0; i < 8; i += hs << 1)
+#pragma unroll
+      for (int y = i; y < i + hs; ++y)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const unsigned a = d[y * 4 + j], b = d[(y + hs) * 4 + j];
+          d[y * 4 + j] = pk_add(a, b); d[(y + hs) * 4 + j] = pk_sub(a, b);
+        }
+#pragma unroll
+  for (int hs = 1; hs < 4; hs <<= 1)  // horizontal distance 2 and 4: pairs j, j + hs
+#pragma unroll
+    for (int y = 0; y < 8; ++y)
+#pragma unroll
+      for (int i = 0; i < 4; i += hs << 1)
+#pragma unroll
+        for (int j = i; j < i + hs; ++j) {
+          const unsigned a = d[y * 4 + j], b = d[y * 4 + j + hs];
+          d[y * 4 + j] = pk_add(a, b); d[y * 4 + j + hs] = pk_sub(a, b);
+        }
+  unsigned acc = 0;
+#pragma unroll
+  for (int i = 0; i < 32; ++i) {  // horizontal distance 1, inside a pair: |a + b| + |a - b| = 2 max(|a|, |b|)
+    const unsigned a = pk_abs(d[i]);
+    acc += max(a & 0xFFFFu, a >> 16);
+  }
+  return 2 * acc;
+}
+// 32-bit twin (12-bit content): d[64] row-major
+__device__ __forceinline__ unsigned had8x8_wide(int (&v)[64])
+{
+#pragma unroll
+  for (int y = 0; y < 8; ++y)
+#pragma unroll
+    for (int hs = 1; hs < 8; hs <<= 1)
+#pragma unroll
+      for (int i = 0; i < 8; i += hs << 1)
+#pragma unroll
+        for (int j = i; j < i + hs; ++j) {
+          const int a = v[8 * y + j], b = v[8 * y + j + hs];
+          v[8 * y + j] = a + b; v[8 * y + j + hs] = a - b;
+        }
+#pragma unroll
+  for (int x = 0; x < 8; ++x)
+#pragma unroll
+    for (int hs = 1; hs < 8; hs <<= 1)
+#pragma unroll
+      for (int i = 0; i < 8; i += hs << 1)
+#pragma unroll
+        for (int j = i; j < i + hs; ++j) {
+          const int a = v[8 * j + x], b = v[8 * (j + hs) + x];
+          v[8 * j + x] = a + b; v[8 * (j + hs) + x] = a - b;
+        }
+  unsigned s = 0;
+#pragma unroll
+  for (int i = 0; i < 64; ++i) s += (unsigned)abs(v[i]);
+  return s;
+}
+
+}  // namespace

@@ -1,0 +1,302 @@
+// k_motion_refine.hip -- source-only quarter-sample refinement of the motion search per CU node (config 4: P slices), gfx950 only.
+//
+// Twin of TEncSearch::xPatternSearchFracDIF + xPatternRefinement (TEncSearch.cpp:4370-4406, :823-877; candidate tables :51-75): around the
+// integer vector of every CU node (85 per CTU, as k_motion.hip writes them) a half-sample and then a quarter-sample stage of nine candidates
+// each, strict "<" in the order of s_acMvRefineH / s_acMvRefineQ, cost = Hadamard distortion (TComRdCost::xGetHADs: the node's 8x8 tile
+// Hadamards, (sum + 2) >> 2 each, the node's sum >> (bit depth - 8) once) + getCostOfVectorWithPredictor (zero predictor; bits of the vector in
+// QUARTER units in both stages: cost scale 1 on half units, 0 on quarter units), on HEVC's 8-tap luma interpolation of the PREVIOUS ORIGINAL
+// picture with coordinates clamped to the picture (TComPicYuv::extendPicBorder).
+//
+// Interpolation (TComInterpolationFilter::filter, xExtDIFUpSamplingH / Q): ONE form serves the four cases.  With c_0 = {0,0,0,64,0,0,0,0}
+//   t = (sum c_fx s >> (bd - 8)) - 8192 over rows y-3 .. y+4,  sample = clip((sum c_fy t + (1 << (19 - bd)) + (8192 << 6)) >> (20 - bd))
+// is what the reference computes when both fractions are non-zero, and for fy = 0 it collapses to ((sum c_fx s >> (bd - 8)) + (1 << (13 - bd)))
+// >> (14 - bd) = (sum c_fx s + 32) >> 6 (nested floors of integers), for fx = 0 to the reference's own vertical pass behind its 14-bit copy,
+// for fx = fy = 0 to the sample itself.  So the fractions are DATA (two packed coefficient vectors per lane), not control flow: the
+// quarter stage starts from each node's own half-sample winner, and the lanes of a wave need not agree on a phase.
+//
+// Mapping: workgroup (4 waves) = one CTU at a time, grid-stride; wave = level (64x64, 32x32, 16x16, 8x8), lane = one 8x8 tile: every level
+// covers the same 64 tiles, so the waves are balanced.  A lane keeps its 64 original samples as 32 packed pairs, reads the window of ITS node's
+// candidate from LDS (the reference window of (64 + 2 MR + 8)^2 samples, border replicated, staged once per CTU; aligned dword reads +
+// v_alignbit, as k_motion.hip), filters it with v_dot2_i32_i16 (two taps per instruction: horizontally on pairs of neighbouring samples,
+// vertically on pairs of rows of the 16-bit intermediates), runs the Hadamard of k_had8x8.h, and the tiles of a node meet through lane
+// shuffles.  The candidate loop is wave-uniform; a wave whose lanes all have a zero fraction in one direction skips that filter's arithmetic.
+// No scratch, no HBM state between calls: the vector costs travel by value (cost by number of bits, 40 entries).
+#include "fhevc_internal.h"
+#include "k_had8x8.h"
+
+namespace {
+
+template <int MR> struct RefineGeom {
+  static constexpr int RP = 64 + 2 * MR + 8;    // LDS row pitch in samples: the CTU, the range, and 4 samples each side for the taps (x-3 .. x+4 around x-1 .. x)
+  static constexpr int ROWS = 64 + 2 * MR + 8;
+  static constexpr int SAMPLES = ROWS * RP + 8; // a lane's ninth dword of a row may lie behind the window's last sample: never used for its value
+};
+
+// c_f as four packed pairs (low half = the tap of the lower coordinate)
+#define FHEVC_PK(a, b) (((unsigned)(a) & 0xFFFFu) | ((unsigned)(b) << 16))
+__constant__ unsigned kLumaTaps[16] = {
+  FHEVC_PK(0, 0), FHEVC_PK(0, 64), FHEVC_PK(0, 0), FHEVC_PK(0, 0),
+  FHEVC_PK(-1, 4), FHEVC_PK(-10, 58), FHEVC_PK(17, -5), FHEVC_PK(1, 0),
+  FHEVC_PK(-1, 4), FHEVC_PK(-11, 40), FHEVC_PK(40, -11), FHEVC_PK(4, -1),
+  FHEVC_PK(0, 1), FHEVC_PK(-5, 17), FHEVC_PK(58, -10), FHEVC_PK(4, -1) };
+#undef FHEVC_PK
+// s_acMvRefineH, then s_acMvRefineQ (TEncSearch.cpp:51-75): (x, y) as two signed nibbles
+__constant__ signed char kRefineX[18] = { 0, 0, 0, -1, 1, -1, 1, -1, 1,   0, 0, 0, -1, 1, -1, 1, -1, 1 };
+__constant__ signed char kRefineY[18] = { 0, -1, 1, 0, 0, -1, -1, 1, 1,   0, -1, 1, -1, -1, 0, 0, 1, 1 };
+
+__device__ __forceinline__ int dot2(unsigned a, unsigned b, int c)
+{
+  return __builtin_amdgcn_sdot2(__builtin_bit_cast(i16x2, a), __builtin_bit_cast(i16x2, b), c, false);
+}
+__device__ __forceinline__ int eg_bits(int v)  // xGetExpGolombNumberOfBits (TComRdCost.h:177-190)
+{
+  const unsigned u = (v <= 0) ? (((unsigned)(-v)) << 1) + 1u : ((unsigned)v) << 1;
+  return 1 + 2 * (31 - __builtin_clz(u));
+}
+
+template <typename T>
+__device__ __forceinline__ int sample_of(const T* plane, long long off) { return (int)plane[off]; }
+
+// T = int16_t (HM Pel planes) or uint8_t; PACKED = bit depth <= 10 (the packed Hadamard); MR = 8 or 64: the largest integer vector the window is laid out for
+template <typename T, bool PACKED, int MR>
+__global__ __launch_bounds__(256) void fhevc_motion_refine_kernel(FhevcFrames F, int max_range, FhevcMvBitCost cost, const FhevcMotionNode* __restrict__ nodes,
+                                                                  FhevcMotionQpelNode* __restrict__ out)
+{
+  constexpr int RP = RefineGeom<MR>::RP;
+  constexpr bool BIG = MR > FHEVC_MOTION_MAX_RANGE;
+  extern __shared__ __attribute__((aligned(16))) short s_dyn[];
+  __shared__ __attribute__((aligned(16))) short s_small[BIG ? 8 : RefineGeom<MR>::SAMPLES];
+  short* const s_ref = BIG ? s_dyn : s_small;
+  __shared__ unsigned s_cost[FHEVC_MV_BIT_COSTS], s_taps[16];
+  const int tid = threadIdx.x, lane = tid & 63, lvl = tid >> 6;
+  const int tx = lane & 7, ty = lane >> 3;
+  const int band_rows = F.row_end - F.row_begin;
+  const int per_frame = band_rows * F.ctus_x;
+  const int total = per_frame * (F.num_frames - 1);  // frame f >= 1 is refined in frame f - 1
+  const int bd = F.bit_depth;
+  const int shift = bd - 8;
+  const int v_off = (1 << (19 - bd)) + (8192 << 6), v_shift = 20 - bd, top = (1 << bd) - 1;
+  const T* plane = reinterpret_cast<const T*>(F.luma);
+  if (tid < FHEVC_MV_BIT_COSTS) s_cost[tid] = cost.c[tid];
+  if (tid < 16) s_taps[tid] = kLumaTaps[tid];
+  // this lane's node: level lvl, (nbx, nby) in the CTU
+  const int nsize = 64 >> lvl, ncnt = 1 << lvl;
+  const int nbx = tx >> (3 - lvl), nby = ty >> (3 - lvl);
+  const int nidx = ((1 << (2 * lvl)) - 1) / 3 + nby * ncnt + nbx;
+  const bool writer = (tx & ((8 >> lvl) - 1)) == 0 && (ty & ((8 >> lvl) - 1)) == 0;
+
+  for (int work = blockIdx.x; work < total; work += gridDim.x) {
+    const int f = 1 + work / per_frame;
+    const int rem = work % per_frame;
+    const int cy = F.row_begin + rem / F.ctus_x, cx = rem % F.ctus_x;
+    const long long cur_base = (long long)f * F.frame_stride, ref_base = (long long)(f - 1) * F.frame_stride;
+    const long long oc = (long long)((f - 1) * band_rows + (cy - F.row_begin)) * F.ctus_x + cx;
+    // ---- stage the reference window: rows cy*64 - MR - 4 .., columns cx*64 - MR - 4 .., coordinates clamped to the picture ----
+    __syncthreads();  // the previous CTU's readers are done
+    {
+      // chunks of 4 samples: the window's first column is a multiple of 4, so a chunk inside the picture is ONE 8-byte (uint8 planes: 4-byte) load
+      // where the plane allows it, and one 8-byte LDS store
+      constexpr int CH = RP / 4;
+      for (int it = tid; it < RefineGeom<MR>::ROWS * CH; it += 256) {
+        const int wr = it / CH, wc = (it - wr * CH) * 4;
+        const int py = min(max(cy * 64 - MR - 4 + wr, 0), F.height - 1);
+        const int px0 = cx * 64 - MR - 4 + wc;
+        const long long row = ref_base + (long long)py * F.stride;
+        const T* src = plane + row + px0;
+        uint2 q;
+        if (px0 >= 0 && px0 + 4 <= F.width && (reinterpret_cast<uintptr_t>(src) & (4 * sizeof(T) - 1)) == 0) {
+          if (sizeof(T) == 2) q = *reinterpret_cast<const uint2*>(src);
+          else {
+            const unsigned b = *reinterpret_cast<const unsigned*>(src);
+            q.x = (b & 0xFFu) | ((b & 0xFF00u) << 8); q.y = ((b >> 16) & 0xFFu) | ((b >> 24) << 16);
+          }
+        } else {
+          int v[4];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) v[k] = sample_of(plane, row + min(max(px0 + k, 0), F.width - 1));
+          q.x = ((unsigned)v[0] & 0xFFFFu) | ((unsigned)v[1] << 16); q.y = ((unsigned)v[2] & 0xFFFFu) | ((unsigned)v[3] << 16);
+        }
+        *reinterpret_cast<uint2*>(s_ref + wr * RP + wc) = q;
+      }
+    }
+    // ---- this lane's original 8x8 tile (all four waves hold the same 64 tiles) ----
+    const int px = cx * 64 + tx * 8, py = cy * 64 + ty * 8;
+    const bool inside = (px + 8 <= F.width) && (py + 8 <= F.height);
+    unsigned O[32];
+    if (inside) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const long long row = cur_base + (long long)(py + j) * F.stride + px;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          O[4 * j + k] = ((unsigned)sample_of(plane, row + 2 * k) & 0xFFFFu) | ((unsigned)sample_of(plane, row + 2 * k + 1) << 16);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 32; ++i) O[i] = 0;
+    }
+    // ---- its node's integer vector: only mvx / mvy of the input are read, validity comes from the geometry and from max_range ----
+    const bool node_in = cx * 64 + nbx * nsize + nsize <= F.width && cy * 64 + nby * nsize + nsize <= F.height;
+    int mx = 0, my = 0;
+    bool valid = false;
+    if (node_in) {
+      const unsigned w = reinterpret_cast<const unsigned*>(nodes)[(oc * FHEVC_NODES + nidx) * 4 + 3];
+      mx = (int)(short)(w & 0xFFFFu); my = (int)(short)(w >> 16);
+      valid = abs(mx) <= max_range && abs(my) <= max_range;
+      if (!valid) { mx = 0; my = 0; }  // the arithmetic below stays inside the window; its result is dropped
+    }
+    __syncthreads();
+
+    int base_x = 4 * mx, base_y = 4 * my;      // quarter units
+    int best_x = base_x, best_y = base_y;
+    unsigned best_c = 0xFFFFFFFFu, best_s = 0, satd_int = 0;
+#pragma unroll 1
+    for (int i = 0; i < 18; ++i) {
+      if (i == 9) { base_x = best_x; base_y = best_y; best_c = 0xFFFFFFFFu; }  // the quarter stage starts from the half stage's winner
+      const int step = i < 9 ? 2 : 1;
+      const int qx = base_x + step * (int)kRefineX[i], qy = base_y + step * (int)kRefineY[i];
+      const int fx = qx & 3, fy = qy & 3;
+      const int col = tx * 8 + MR + 4 + (qx >> 2) - 3, row0 = ty * 8 + MR + 4 + (qy >> 2) - 3;  // first tap of sample (0, 0)
+      const unsigned sh = (unsigned)(col & 1) * 16u;
+      const bool hor = __builtin_amdgcn_ballot_w64(fx != 0) != 0, ver = __builtin_amdgcn_ballot_w64(fy != 0) != 0;  // wave-uniform
+      unsigned cxp[4], cyp[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { cxp[j] = s_taps[4 * fx + j]; cyp[j] = s_taps[4 * fy + j]; }
+      // ---- horizontal: rows row0 .. + 14, 8 intermediates each, kept as pairs of rows: Pe[r / 2][x] = (t[r][x], t[r + 1][x]) ----
+      unsigned Pe[8][8];
+      if (ver) {
+#pragma unroll
+        for (int r = 0; r < 15; ++r) {
+          const unsigned* q = reinterpret_cast<const unsigned*>(s_ref) + (((row0 + r) * RP + col) >> 1);
+          int t[8];
+          if (hor) {
+            unsigned d[9], N[8], M[7];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) d[k] = q[k];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) N[k] = __builtin_amdgcn_alignbit(d[k + 1], d[k], sh);    // pairs starting at col, col + 2, ..
+#pragma unroll
+            for (int k = 0; k < 7; ++k) M[k] = __builtin_amdgcn_alignbit(N[k + 1], N[k], 16u);   // pairs starting at col + 1, col + 3, ..
+#pragma unroll
+            for (int x = 0; x < 8; ++x) {
+              int a = 0;
+#pragma unroll
+              for (int j = 0; j < 4; ++j) a = dot2((x & 1) ? M[(x >> 1) + j] : N[(x >> 1) + j], cxp[j], a);
+              t[x] = (a >> shift) - 8192;
+            }
+          } else {  // fx = 0 in every lane: (64 s >> (bd - 8)) - 8192 of samples col + 3 .. col + 10
+            unsigned d[7], N[6];
+#pragma unroll
+            for (int k = 1; k < 7; ++k) d[k] = q[k];
+#pragma unroll
+            for (int k = 1; k < 6; ++k) N[k] = __builtin_amdgcn_alignbit(d[k + 1], d[k], sh);     // pairs starting at col + 2 k
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              const unsigned pr = __builtin_amdgcn_alignbit(N[k + 2], N[k + 1], 16u);              // samples col + 3 + 2 k, + 1
+              t[2 * k] = (int)((pr & 0xFFFFu) << (14 - bd)) - 8192; t[2 * k + 1] = (int)((pr >> 16) << (14 - bd)) - 8192;
+            }
+          }
+#pragma unroll
+          for (int x = 0; x < 8; ++x) {
+            if (r & 1) Pe[r >> 1][x] = (Pe[r >> 1][x] & 0xFFFFu) | ((unsigned)t[x] << 16);
+            else Pe[r >> 1][x] = (unsigned)t[x] & 0xFFFFu;
+          }
+        }
+      }
+      // ---- vertical, difference to the original, Hadamard ----
+      unsigned t8;
+      {
+        unsigned D[32];
+        int v[64];
+#pragma unroll
+        for (int y = 0; y < 8; ++y) {
+          int p[8];
+          if (ver) {
+#pragma unroll
+            for (int x = 0; x < 8; ++x) {
+              int a = v_off;
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                const int m = (y >> 1) + j;
+                a = dot2((y & 1) ? __builtin_amdgcn_alignbit(Pe[m + 1][x], Pe[m][x], 16u) : Pe[m][x], cyp[j], a);
+              }
+              p[x] = min(max(a >> v_shift, 0), top);
+            }
+          } else {  // fy = 0 in every lane: row row0 + 3 + y, filtered horizontally to the final sample
+            const unsigned* q = reinterpret_cast<const unsigned*>(s_ref) + (((row0 + 3 + y) * RP + col) >> 1);
+            unsigned d[9], N[8], M[7];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) d[k] = q[k];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) N[k] = __builtin_amdgcn_alignbit(d[k + 1], d[k], sh);
+#pragma unroll
+            for (int k = 0; k < 7; ++k) M[k] = __builtin_amdgcn_alignbit(N[k + 1], N[k], 16u);
+#pragma unroll
+            for (int x = 0; x < 8; ++x) {
+              int a = 32;
+#pragma unroll
+              for (int j = 0; j < 4; ++j) a = dot2((x & 1) ? M[(x >> 1) + j] : N[(x >> 1) + j], cxp[j], a);
+              p[x] = min(max(a >> 6, 0), top);
+            }
+          }
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const unsigned o = O[4 * y + k];
+            if constexpr (PACKED) D[4 * y + k] = pk_sub(o, ((unsigned)p[2 * k] & 0xFFFFu) | ((unsigned)p[2 * k + 1] << 16));
+            else { v[8 * y + 2 * k] = (int)(o & 0xFFFFu) - p[2 * k]; v[8 * y + 2 * k + 1] = (int)(o >> 16) - p[2 * k + 1]; }
+          }
+        }
+        if constexpr (PACKED) t8 = had8x8_packed(D);
+        else t8 = had8x8_wide(v);
+      }
+      t8 = inside ? ((t8 + 2) >> 2) : 0u;  // xCalcHADs8x8: (sum + 2) >> 2 (TComRdCost.cpp:1747)
+      // the node's sum: 16x16 = tiles (tx ^ 1, ty ^ 1), 32x32 = + bits 1, 64x64 = + bits 2 (wave-uniform depth)
+      unsigned s = t8;
+      for (int k = 0; k < 3 - lvl; ++k) {
+        s += __shfl_xor(s, 1 << k);
+        s += __shfl_xor(s, 8 << k);
+      }
+      const unsigned sd = s >> shift;  // DISTORTION_PRECISION_ADJUSTMENT on the block's sum (TComRdCost.cpp:1823)
+      const unsigned c = sd + s_cost[eg_bits(qx) + eg_bits(qy)];
+      if (i == 0) satd_int = sd;
+      if (c < best_c) { best_c = c; best_s = sd; best_x = qx; best_y = qy; }
+    }
+    if (writer) {
+      FhevcMotionQpelNode o;
+      if (valid) { o.satd_int = satd_int; o.satd_best = best_s; o.cost_best = best_c; o.mvx = (short)best_x; o.mvy = (short)best_y; }
+      else { o.satd_int = o.satd_best = o.cost_best = 0xFFFFFFFFu; o.mvx = 0; o.mvy = 0; }
+      out[oc * FHEVC_NODES + nidx] = o;
+    }
+  }
+}
+
+template <typename T, bool PACKED>
+hipError_t launch_refine(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_nodes, FhevcMotionQpelNode* d_out, int num_cus,
+                         long long total, hipStream_t stream)
+{
+  if (max_range <= FHEVC_MOTION_MAX_RANGE) {
+    const int grid = (int)(total < 4LL * num_cus ? total : 4LL * num_cus);
+    hipLaunchKernelGGL((fhevc_motion_refine_kernel<T, PACKED, FHEVC_MOTION_MAX_RANGE>), dim3(grid), dim3(256), 0, stream, fr, max_range, cost, d_nodes, d_out);
+  } else {
+    constexpr int MRB = FHEVC_MOTION_WIDE_MAX_RANGE;
+    const size_t lds = (size_t)RefineGeom<MRB>::SAMPLES * sizeof(short);  // 80 016 B: one workgroup per CU beside another kernel's, two alone
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fhevc_motion_refine_kernel<T, PACKED, MRB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    const int grid = (int)(total < 2LL * num_cus ? total : 2LL * num_cus);
+    hipLaunchKernelGGL((fhevc_motion_refine_kernel<T, PACKED, MRB>), dim3(grid), dim3(256), lds, stream, fr, max_range, cost, d_nodes, d_out);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t fhevc_launch_motion_refine(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_nodes, FhevcMotionQpelNode* d_out,
+                                      int num_cus, hipStream_t stream)
+{
+  const long long total = (long long)(fr.row_end - fr.row_begin) * fr.ctus_x * (fr.num_frames - 1);
+  if (total <= 0) return hipSuccess;
+  if (max_range < 1 || max_range > FHEVC_MOTION_WIDE_MAX_RANGE) return hipErrorInvalidValue;
+  if (fr.sample_bytes == 2 && fr.bit_depth <= 10) return launch_refine<int16_t, true>(fr, max_range, cost, d_nodes, d_out, num_cus, total, stream);
+  if (fr.sample_bytes == 2) return launch_refine<int16_t, false>(fr, max_range, cost, d_nodes, d_out, num_cus, total, stream);
+  return launch_refine<uint8_t, true>(fr, max_range, cost, d_nodes, d_out, num_cus, total, stream);
+}

@@ -288,6 +288,36 @@ int  fhevc_motion_search_device(fhevc_ctx* ctx, const void* d_luma, int sample_b
                                 long long frame_stride_samples, int num_frames, int ctu_row_begin, int ctu_row_end,
                                 int qp, int search_range, fhevc_motion_node* d_out, void* stream);
 
+/* Quarter-sample refinement of the search's vectors (k_motion_refine.hip): the source-only twin of what HM's xMotionEstimation always runs behind
+ * its integer search, TEncSearch::xPatternSearchFracDIF + xPatternRefinement (TEncSearch.cpp:4370-4406, :823-877).  Per CU node, around the node's
+ * integer vector (mvx, mvy): the nine half-sample candidates of s_acMvRefineH (centre first, TEncSearch.cpp:51-62), then the nine quarter-sample
+ * candidates of s_acMvRefineQ (in ITS order, :64-75) around the half stage's winner, strict "<" in both.  A candidate costs its Hadamard distortion
+ * (TComRdCost::xGetHADs, HadamardME: ALWAYS SATD here, whatever fhevc_set_motion_distortion says) on HEVC's 8-tap luma interpolation
+ * (TComInterpolationFilter; 14-bit intermediates when both fractions are non-zero) of the PREVIOUS ORIGINAL picture with coordinates clamped to the
+ * picture, plus getCostOfVectorWithPredictor of the candidate in quarter units (zero predictor, lambda of slice QP qp as the search).
+ * nodes: what fhevc_motion_search[_device] wrote for the same pictures and band, in either distortion mode, any search range up to 64; only mvx and
+ * mvy are read.  Validity comes from the context's geometry: a node crossing the picture edge gets 0xFFFFFFFF in the three distortion fields and a
+ * zero vector, and so does a node whose |mvx| or |mvy| exceeds max_range (1..64; pass the search's range), so no content of `nodes` can send a read
+ * outside the staged window.  max_range <= 8 runs on a 15.5 KB window per CTU, above on an 80 KB one. */
+typedef struct {
+  uint32_t satd_int;        /* SATD at the integer vector (candidate 0 of the half stage) */
+  uint32_t satd_best;       /* SATD at the final vector */
+  uint32_t cost_best;       /* its SATD + vector cost: what xPatternSearchFracDIF returns in ruiCost; 0xFFFFFFFF in all three: see above */
+  int16_t  mvx, mvy;        /* the final vector in QUARTER samples: 4 * integer + 2 * half + quarter */
+} fhevc_motion_qpel_node;
+/* one picture pair, host buffers (both planes with the same stride), synchronous; nodes, out: numCtus * 85 */
+int  fhevc_motion_refine(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                         const fhevc_motion_node* nodes, fhevc_motion_qpel_node* out);
+/* device-resident batch: layout, band and stream arguments as fhevc_motion_search_device; frame f = 1 .. num_frames-1 is refined in frame f-1;
+ * d_nodes, d_out: (num_frames - 1) * band CTUs * 85 entries in HBM, compact over the band; d_out is written over exactly that extent, an empty band
+ * writes nothing.  Asynchronous with respect to the host, allocates nothing, keeps no state in HBM between calls: calls on different streams may be
+ * in flight together, and a search and its refinement may follow each other on one stream without a synchronisation.  FHEVC_E_INVALID (nothing is
+ * launched or written): a null pointer, num_frames < 2, qp outside 0..51, max_range outside 1..64, stride_samples < width, a bad band, uint8 planes
+ * on a context above 8 bit. */
+int  fhevc_motion_refine_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples,
+                                long long frame_stride_samples, int num_frames, int ctu_row_begin, int ctu_row_end,
+                                int qp, int max_range, const fhevc_motion_node* d_nodes, fhevc_motion_qpel_node* d_out, void* stream);
+
 /* Depth range of every 4x4 unit of a P picture's CTU from its motion nodes and the co-located depths of its reference picture
  * ("inter-CU depth reuse", BASELINE config 4).  Host-side integer arithmetic, no device work.  Per split decision (64->32,
  * 32->16, 16->8) a linear score over nine features of the node, all in 1/256 units (L(x) = floor(256 log2 x) by integer
@@ -367,7 +397,8 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
 
 /* average duration in ms of the dominant kernels over launches since the last reset, measured with HIP
  * events on the launch stream; which: 0 = depth CNN, 1 = source Hadamard, 2 = first pass, 3 = pre-analysis, 4 = motion search,
- * 5 = P-picture depth ranges (fhevc_p_depth_range_device), 6 = first pass of the 4x4 PUs (fhevc_intra_first_pass_4x4*) */
+ * 5 = P-picture depth ranges (fhevc_p_depth_range_device), 6 = first pass of the 4x4 PUs (fhevc_intra_first_pass_4x4*),
+ * 7 = quarter-sample motion refinement (fhevc_motion_refine*) */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
 int  fhevc_enable_kernel_timing(fhevc_ctx* ctx, int on);
 
