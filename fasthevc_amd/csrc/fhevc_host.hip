@@ -1,0 +1,281 @@
+// fhevc_host.hip -- the functions of include/fasthevc.h that take no context and never touch the device: the band split, the YUV reader, the AQ
+// partition / QP arithmetic, the host form of the P-picture rule and the two motion-compensated depth maps.  Plain C++.
+#include "../../include/fasthevc.h"
+#include "fhevc_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+// ---- P-picture depth range from motion nodes + co-located depths (host-side integer rule; spec in include/fasthevc.h) ----
+namespace {
+inline int32_t ilog2_q8(uint32_t x)  // floor(256 log2 x) by integer squaring
+{
+  const int msb = 31 - __builtin_clz(x | 1u);
+  uint64_t y = ((uint64_t)x << 31) >> msb;
+  int32_t r = msb << 8;
+  for (int b = 7; b >= 0; --b) {
+    y = (y * y) >> 31;
+    if (y >> 32) { r |= 1 << b; y >>= 1; }
+  }
+  return r;
+}
+struct PNodeRef { int first, per_row; };
+constexpr PNodeRef kLevel[4] = { { 0, 1 }, { 1, 2 }, { 5, 4 }, { 21, 8 } };
+int64_t p_split_score(const fhevc_motion_node* nodes, const uint8_t* prev, int lvl, int nx, int ny, int qp, const fhevc_p_rule& r)
+{
+  const fhevc_motion_node& n = nodes[kLevel[lvl].first + ny * kLevel[lvl].per_row + nx];
+  int64_t child_cost = 0, child_satd = 0;
+  int moved = 0;
+  for (int k = 0; k < 4; ++k) {
+    const fhevc_motion_node& c = nodes[kLevel[lvl + 1].first + (2 * ny + (k >> 1)) * kLevel[lvl + 1].per_row + 2 * nx + (k & 1)];
+    child_cost += c.cost_best; child_satd += c.satd_best;
+    moved += (c.mvx != n.mvx) || (c.mvy != n.mvy);
+  }
+  const int units = 16 >> lvl;
+  int deepest = 0, shallowest = 3;
+  for (int y = 0; y < units; ++y)
+    for (int x = 0; x < units; ++x) {
+      const int d = prev[(ny * units + y) * 16 + nx * units + x];
+      deepest = std::max(deepest, d); shallowest = std::min(shallowest, d);
+    }
+  const int64_t gain = std::max<int64_t>(0, (int64_t)n.cost_best - child_cost);
+  const int norm = 512 * (6 - lvl) + (qp * 256) / 6;
+  const int64_t f[9] = { ilog2_q8(n.satd_best + 1u) - norm, ilog2_q8((uint32_t)gain + 1u) - norm, ilog2_q8((uint32_t)child_satd + 1u) - norm,
+                         ilog2_q8(n.satd_zero + 1u) - ilog2_q8(n.satd_best + 1u), deepest > lvl ? 256 : 0, shallowest > lvl ? 256 : 0,
+                         deepest > lvl + 1 ? 256 : 0, 64 * moved, 8 * qp };
+  int64_t s = r.w[lvl][9];
+  for (int i = 0; i < 9; ++i) s += (int64_t)r.w[lvl][i] * f[i];
+  return s;
+}
+}  // namespace
+
+extern "C" {
+
+const char* fhevc_version(void) { return "fasthevc_amd 0.1.0 (gfx950)"; }
+
+int fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end)
+{
+  if (ctu_rows < 0 || world <= 0 || rank < 0 || rank >= world || !begin || !end) return FHEVC_E_INVALID;
+  *begin = (int)(((long long)rank * ctu_rows) / world);
+  *end = (int)(((long long)(rank + 1) * ctu_rows) / world);
+  return FHEVC_OK;
+}
+
+int fhevc_read_yuv_luma(const char* path, int file_width, int file_height, int file_bit_depth, int chroma_format, long long first_frame,
+                        int num_frames, int dst_width, int dst_height, int internal_bit_depth, int dst_sample_bytes, void* dst,
+                        long long dst_stride_samples, long long dst_frame_stride_samples)
+{
+  if (!path || !dst || file_width < 1 || file_height < 1 || num_frames < 0 || first_frame < 0) return FHEVC_E_INVALID;
+  if (file_bit_depth < 8 || file_bit_depth > 16 || internal_bit_depth < file_bit_depth || internal_bit_depth > 12) return FHEVC_E_INVALID;
+  if (dst_width < file_width || dst_height < file_height || dst_stride_samples < dst_width) return FHEVC_E_INVALID;
+  if (dst_sample_bytes != 1 && dst_sample_bytes != 2) return FHEVC_E_INVALID;
+  if (dst_sample_bytes == 1 && (file_bit_depth != 8 || internal_bit_depth != 8)) return FHEVC_E_INVALID;
+  if (num_frames > 1 && dst_frame_stride_samples < dst_stride_samples * (dst_height - 1) + dst_width) return FHEVC_E_INVALID;
+  const long long bps = file_bit_depth > 8 ? 2 : 1;
+  long long chroma_samples;  // both chroma planes of the FILE's format
+  const long long cw = (file_width + 1) / 2, chh = (file_height + 1) / 2;
+  switch (chroma_format) {
+    case 400: chroma_samples = 0; break;
+    case 420: chroma_samples = 2 * cw * chh; break;
+    case 422: chroma_samples = 2 * cw * file_height; break;
+    case 444: chroma_samples = 2LL * file_width * file_height; break;
+    default: return FHEVC_E_INVALID;
+  }
+  const long long luma_bytes = (long long)file_width * file_height * bps, frame_bytes = luma_bytes + chroma_samples * bps;
+  FILE* fp = std::fopen(path, "rb");
+  if (!fp) return FHEVC_E_STATE;
+  const int shift = internal_bit_depth - file_bit_depth;
+  std::vector<uint8_t> row8;
+  int done = 0;
+  for (; done < num_frames; ++done) {
+    if (fseeko(fp, (off_t)((first_frame + done) * frame_bytes), SEEK_SET) != 0) break;
+    bool ok = true;
+    if (dst_sample_bytes == 1) {
+      uint8_t* plane = static_cast<uint8_t*>(dst) + (size_t)done * (size_t)dst_frame_stride_samples;
+      if (dst_width == file_width && dst_stride_samples == file_width) ok = std::fread(plane, 1, (size_t)luma_bytes, fp) == (size_t)luma_bytes;  // one read, file -> destination
+      else
+        for (int y = 0; y < file_height && ok; ++y) ok = std::fread(plane + (size_t)y * dst_stride_samples, 1, (size_t)file_width, fp) == (size_t)file_width;
+      if (!ok) break;
+      for (int y = 0; y < file_height; ++y) {
+        uint8_t* r = plane + (size_t)y * dst_stride_samples;
+        for (int x = file_width; x < dst_width; ++x) r[x] = r[file_width - 1];
+      }
+      for (int y = file_height; y < dst_height; ++y) std::memcpy(plane + (size_t)y * dst_stride_samples, plane + (size_t)(file_height - 1) * dst_stride_samples, (size_t)dst_width);
+    } else {
+      int16_t* plane = static_cast<int16_t*>(dst) + (size_t)done * (size_t)dst_frame_stride_samples;
+      if (bps == 1) row8.resize((size_t)file_width);
+      for (int y = 0; y < file_height && ok; ++y) {
+        int16_t* r = plane + (size_t)y * dst_stride_samples;
+        if (bps == 2) {  // two little-endian bytes per sample: the host is little-endian (x86-64), read them in place
+          ok = std::fread(r, 2, (size_t)file_width, fp) == (size_t)file_width;
+          if (shift) for (int x = 0; x < file_width; ++x) r[x] = (int16_t)(r[x] << shift);
+        } else {
+          ok = std::fread(row8.data(), 1, (size_t)file_width, fp) == (size_t)file_width;
+          for (int x = 0; x < file_width; ++x) r[x] = (int16_t)((int)row8[(size_t)x] << shift);
+        }
+        for (int x = file_width; x < dst_width; ++x) r[x] = r[file_width - 1];
+      }
+      if (!ok) break;
+      for (int y = file_height; y < dst_height; ++y) std::memcpy(plane + (size_t)y * dst_stride_samples, plane + (size_t)(file_height - 1) * dst_stride_samples, (size_t)dst_width * 2);
+    }
+  }
+  std::fclose(fp);
+  if (done == 0 && num_frames > 0) return FHEVC_E_STATE;
+  return done;
+}
+
+int fhevc_aq_parts(int width, int height, int max_aq_depth, long long* layer_offsets)
+{
+  if (width <= 0 || height <= 0 || max_aq_depth < 1 || max_aq_depth > 4) return FHEVC_E_INVALID;
+  long long off = 0;
+  for (int d = 0; d < max_aq_depth; ++d) {
+    if (layer_offsets) layer_offsets[d] = off;
+    const int p = 64 >> d;
+    off += (long long)((width + p - 1) / p) * ((height + p - 1) / p);
+  }
+  if (layer_offsets) layer_offsets[max_aq_depth] = off;
+  return (int)off;
+}
+
+int fhevc_aq_qp(const double* activity, const double* avg_activity, int width, int height, int max_aq_depth,
+                int qp_adaptation_range, int base_qp, int qp_bd_offset, int8_t* qp)
+{
+  long long off[5];
+  if (!activity || !avg_activity || !qp || fhevc_aq_parts(width, height, max_aq_depth, off) < 0) return FHEVC_E_INVALID;
+  if (base_qp < -qp_bd_offset || base_qp > 51 || qp_bd_offset < 0 || qp_bd_offset > 48) return FHEVC_E_INVALID;
+  const double max_q_scale = std::pow(2.0, qp_adaptation_range / 6.0);
+  for (int d = 0; d < max_aq_depth; ++d) {
+    const double avg = avg_activity[d];
+    for (long long i = off[d]; i < off[d + 1]; ++i) {
+      const double act = activity[i];
+      const double norm = (max_q_scale * act + avg) / (act + max_q_scale * avg);
+      const double qoff = std::log(norm) / std::log(2.0) * 6.0;
+      const int v = base_qp + (int)std::floor(qoff + 0.49999);
+      qp[i] = (int8_t)std::min(51, std::max(-qp_bd_offset, v));
+    }
+  }
+  return FHEVC_OK;
+}
+
+void fhevc_p_rule_default(fhevc_p_rule* rule)
+{
+  if (!rule) return;
+  // logistic fit of HM-16.14's own P-picture split decisions (vanilla decision path, tests/quality/make_labels_p.py +
+  // p_features.py + fit_p_rule.py) on seeded pan clips of all synthetic families; weights Q10, bias and thresholds Q18
+  static const int32_t w[3][10] = FHEVC_P_RULE_WEIGHTS;
+  std::memcpy(rule->w, w, sizeof w);
+  const int32_t ts[3] = FHEVC_P_RULE_T_SPLIT, tp[3] = FHEVC_P_RULE_T_STOP;
+  std::memcpy(rule->t_split, ts, sizeof ts);
+  std::memcpy(rule->t_stop, tp, sizeof tp);
+  rule->window = FHEVC_P_RULE_WINDOW;
+}
+
+void fhevc_p_rule_default_wide(fhevc_p_rule* rule)
+{
+  if (!rule) return;
+  fhevc_p_rule_default(rule);   // thresholds and window as the default rule: same score semantics (a logit)
+  static const int32_t w[3][10] = FHEVC_P_RULE_WIDE_WEIGHTS;
+  std::memcpy(rule->w, w, sizeof w);
+}
+
+int fhevc_p_depth_range(const fhevc_motion_node* nodes, const uint8_t* prev_depth, int valid_w, int valid_h, int qp, const fhevc_p_rule* rule,
+                        uint8_t* depth_min, uint8_t* depth_max)
+{
+  if (!nodes || !prev_depth || !rule || !depth_min || !depth_max || valid_w < 8 || valid_w > 64 || valid_h < 8 || valid_h > 64 || qp < 0 || qp > 51)
+    return FHEVC_E_INVALID;
+  std::memset(depth_min, 0, 256);
+  std::memset(depth_max, 0, 256);
+  // split decisions of the 21 nodes, both thresholds, evaluated lazily top-down; -1 = not evaluated
+  int8_t sure[21], maybe[21];
+  std::memset(sure, -1, sizeof sure);
+  std::memset(maybe, -1, sizeof maybe);
+  auto decide = [&](int lvl, int nx, int ny) {
+    const int id = kLevel[lvl].first + ny * kLevel[lvl].per_row + nx, n = 64 >> lvl;
+    if (sure[id] >= 0) return id;
+    if (nx * n + n > valid_w || ny * n + n > valid_h) { sure[id] = maybe[id] = 1; return id; }  // crosses the picture edge
+    const int64_t s = p_split_score(nodes, prev_depth, lvl, nx, ny, qp, *rule);
+    sure[id] = s > rule->t_split[lvl];
+    maybe[id] = s >= -(int64_t)rule->t_stop[lvl];
+    return id;
+  };
+  for (int uy = 0; uy * 4 < valid_h; ++uy)
+    for (int ux = 0; ux * 4 < valid_w; ++ux) {
+      int lo = 0, hi = 0;
+      bool lo_open = true, hi_open = true;
+      for (int lvl = 0; lvl < 3 && (lo_open || hi_open); ++lvl) {
+        const int id = decide(lvl, ux >> (4 - lvl), uy >> (4 - lvl));
+        lo_open = lo_open && sure[id];
+        hi_open = hi_open && maybe[id];
+        if (lo_open) lo = lvl + 1;
+        if (hi_open) hi = lvl + 1;
+      }
+      if (rule->window < 4) {
+        const int p = prev_depth[uy * 16 + ux];
+        lo = std::min(3, std::max(0, std::max(lo, p - rule->window)));
+        hi = std::min(3, std::max(0, std::min(hi, p + rule->window)));
+        if (lo > hi) lo = hi;
+      }
+      depth_min[uy * 16 + ux] = (uint8_t)lo;
+      depth_max[uy * 16 + ux] = (uint8_t)hi;
+    }
+  return FHEVC_OK;
+}
+
+int fhevc_p_motion_compensated_depth(const fhevc_motion_node* nodes, const uint8_t* prev_map, int width, int height, int ctu, uint8_t* out)
+{
+  if (!nodes || !prev_map || !out || width < 8 || height < 8 || ctu < 0) return FHEVC_E_INVALID;
+  const int cw = (width + 63) / 64, chh = (height + 63) / 64;
+  if (ctu >= cw * chh) return FHEVC_E_INVALID;
+  const int x0 = (ctu % cw) * 64, y0 = (ctu / cw) * 64;
+  for (int by = 0; by < 4; ++by)
+    for (int bx = 0; bx < 4; ++bx) {
+      // the vector of the smallest valid node around the block: 16x16, 32x32, the CTU
+      const fhevc_motion_node* cand[3] = { &nodes[5 + by * 4 + bx], &nodes[1 + (by >> 1) * 2 + (bx >> 1)], &nodes[0] };
+      int mvx = 0, mvy = 0;
+      for (int k = 0; k < 3; ++k)
+        if (cand[k]->cost_best != 0xFFFFFFFFu) { mvx = cand[k]->mvx; mvy = cand[k]->mvy; break; }
+      for (int uy = 0; uy < 4; ++uy)
+        for (int ux = 0; ux < 4; ++ux) {
+          const int px = std::min(std::max(x0 + bx * 16 + ux * 4 + 2 + mvx, 0), width - 1);
+          const int py = std::min(std::max(y0 + by * 16 + uy * 4 + 2 + mvy, 0), height - 1);
+          const int sc = (py >> 6) * cw + (px >> 6);
+          out[(by * 4 + uy) * 16 + bx * 4 + ux] = prev_map[(size_t)sc * 256 + ((py & 63) >> 2) * 16 + ((px & 63) >> 2)];
+        }
+    }
+  return FHEVC_OK;
+}
+
+int fhevc_p_node_depth(const fhevc_motion_node* nodes, const uint8_t* prev_map, int width, int height, int ctu, uint8_t* out)
+{
+  if (!nodes || !prev_map || !out || width < 8 || height < 8 || ctu < 0) return FHEVC_E_INVALID;
+  const int cw = (width + 63) / 64, chh = (height + 63) / 64;
+  if (ctu >= cw * chh) return FHEVC_E_INVALID;
+  const int x0 = (ctu % cw) * 64, y0 = (ctu / cw) * 64;
+  auto ref_depth = [&](int x, int y) {
+    x = std::min(std::max(x, 0), width - 1); y = std::min(std::max(y, 0), height - 1);
+    return (int)prev_map[(size_t)((y >> 6) * cw + (x >> 6)) * 256 + ((y & 63) >> 2) * 16 + ((x & 63) >> 2)];
+  };
+  auto fill = [&](int ux, int uy, int units, int depth) {
+    for (int y = uy; y < uy + units; ++y) std::memset(out + y * 16 + ux, depth, (size_t)units);
+  };
+  struct Mv { int x, y; };
+  auto vector_of = [](const fhevc_motion_node& n, Mv parent) { return n.cost_best != 0xFFFFFFFFu ? Mv{ n.mvx, n.mvy } : parent; };
+  const Mv v0 = vector_of(nodes[0], Mv{ 0, 0 });
+  if (ref_depth(x0 + 32 + v0.x, y0 + 32 + v0.y) == 0) { fill(0, 0, 16, 0); return FHEVC_OK; }
+  for (int q = 0; q < 4; ++q) {
+    const int qx = q & 1, qy = q >> 1;
+    const Mv v1 = vector_of(nodes[1 + q], v0);
+    if (ref_depth(x0 + qx * 32 + 16 + v1.x, y0 + qy * 32 + 16 + v1.y) <= 1) { fill(qx * 8, qy * 8, 8, 1); continue; }
+    for (int b = 0; b < 4; ++b) {
+      const int bx = 2 * qx + (b & 1), by = 2 * qy + (b >> 1);
+      const Mv v2 = vector_of(nodes[5 + by * 4 + bx], v1);
+      fill(bx * 4, by * 4, 4, ref_depth(x0 + bx * 16 + 8 + v2.x, y0 + by * 16 + 8 + v2.y) <= 2 ? 2 : 3);
+    }
+  }
+  return FHEVC_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// fhevc_internal.h -- shared declarations between the C-ABI layer (fhevc_api.hip) and the gfx950 kernels.
+// fhevc_internal.h -- shared declarations between the C-ABI layer (fhevc_api.hip, fhevc_weights.hip, fhevc_host.hip) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -6,7 +6,7 @@
 #define FHEVC_CTU 64
 
 // ---- depth CNN (k_cnn.hip) -------------------------------------------------------------------------------
-// Packed weight image in HBM, built once by fhevc_set_weights (fhevc_api.hip: build_weight_image):
+// Packed weight image in HBM, built once by fhevc_set_weights (fhevc_weights.hip: build_weight_image):
 //   frag  : MFMA A-operand fragments, one uint4 (8 bf16) per lane: conv1 [2][64], conv2 [9][64], conv3 [2][18][64], all scaled
 //           by their layer's 2^-shift
 //   bias  : float b1[16], b2[32], b3[64]

@@ -208,7 +208,7 @@ __device__ __forceinline__ f32x16 bias_tile(const float* b32, int h)
 }
 
 // one sample as the network sees it: rounded to 8 bits, clamped to 0..255.  The oracle centres it (x - 128); here the LDS
-// image keeps x itself and conv1's bias carries -128 * (sum of the filter's weights) (fhevc_api.hip), which is the same
+// image keeps x itself and conv1's bias carries -128 * (sum of the filter's weights) (fhevc_weights.hip: conv1_bias), which is the same
 // integer arithmetic: the halo and everything outside the picture hold 128
 template <typename T>
 __device__ __forceinline__ int load_sample8(const T* p, int shift)
@@ -284,7 +284,7 @@ __device__ __forceinline__ void conv3_store(const f32x4& acc0, const f32x4& acc1
     d0 = __builtin_amdgcn_cvt_pk_u8_f32(acc0[k], k, d0);
     d1 = __builtin_amdgcn_cvt_pk_u8_f32(acc1[k], k, d1);
   }
-  // stored as a - 128 (signed bytes) for the heads' v_dot4_i32_i8; their biases carry + 128 * sum of weights (fhevc_api.hip)
+  // stored as a - 128 (signed bytes) for the heads' v_dot4_i32_i8; their biases carry + 128 * sum of weights (fhevc_weights.hip: head_biases)
   *reinterpret_cast<unsigned*>(dst + (((2 * tile + 0) ^ psw) << 4)) = d0 ^ 0x80808080u;
   *reinterpret_cast<unsigned*>(dst + (((2 * tile + 1) ^ psw) << 4)) = d1 ^ 0x80808080u;
 }

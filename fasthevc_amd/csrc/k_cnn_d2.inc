@@ -13,7 +13,7 @@
 // Two LDS regions carry the six maps: R_big = S | A2a | A3a, R_a = A1 | A2 | A3 (each map is dead before its region's next tenant is written); every image
 // is [row][position][Cpad bytes] with the halo part of it ("activation 0" = 0x80), the row pitch padded and the 16-byte slots XOR-ed exactly as the layer
 // path's staged images (fhevc_layer_lds_image: conflict-free B-fragment reads for 64-channel inputs).  All arithmetic is the layer path's: v_mfma_i32_32x32x32_i8,
-// A = the layer's weight fragments (fhevc_api.hip: build_layers_image -- rows permuted so that a lane's 16 accumulators are 16 consecutive channels), B = 16 bytes
+// A = the layer's weight fragments (fhevc_weights.hip: build_layers_image -- rows permuted so that a lane's 16 accumulators are 16 consecutive channels), B = 16 bytes
 // per lane from the image, requant4_i8, activations a - 128.  Bit-exact with oracle/fhevc_oracle.c: fho_cnn_ctu_family (tests/test_gpu_family.py).
 //
 // Work split (8 waves): a wave keeps ONE M tile (32 output channels) per layer, its A fragments in registers for the layer (9 x Cin / 32 fragments, from L2);

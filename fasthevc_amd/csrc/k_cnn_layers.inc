@@ -203,7 +203,7 @@ __global__ __launch_bounds__(256, 2) void fhevc_layer_conv_kernel(const int8_t* 
           }
           // the 3 x 3 window as the two ALIGNED dwords around each of its three rows + v_alignbyte, packed by two v_perm (round 4: sub-dword LDS reads --
           // the nine ds_read_u8 this replaces -- cost the fused two-convolution kernel ~750 cycles per tile, k_cnn_d2.inc).  Every lane reads: lanes 32-63 the
-          // same bytes as lanes 0-31; their K slots, like slots 9 .. 15, meet zero weights (build_layers_image)
+          // same bytes as lanes 0-31; their K slots, like slots 9 .. 15, meet zero weights (fhevc_weights.hip: build_layers_image)
           uint4 bq;
           {
             const unsigned char* q = t0 + (r - 1) * 66 + xs + n;

@@ -1,6 +1,6 @@
 // k_p_rule.hip -- P-picture depth ranges on the device (config 4), gfx950 only.
 //
-// The device form of the host rule in fhevc_api.hip ("P-picture depth range"): per CTU the 85 motion nodes that fhevc_motion_search_device
+// The device form of the host rule in fhevc_host.hip (fhevc_p_depth_range): per CTU the 85 motion nodes that fhevc_motion_search_device
 // wrote, the reference picture's depths obtained in one of three ways (co-located; exactly fhevc_p_motion_compensated_depth; exactly
 // fhevc_p_node_depth), then exactly fhevc_p_depth_range.  Integer arithmetic throughout, the same bits as the host code for any 32-bit field
 // values and any int16 vectors -- including where the host code wraps ((uint32_t)gain + 1u and (uint32_t)child_satd + 1u truncate 64-bit sums).

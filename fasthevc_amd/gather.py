@@ -181,7 +181,7 @@ def init_groups(world, rank, device, backend="nccl", timeout_s=120):
 # ---- SURVEY 8(e)'s literal form: the 256-byte depth maps themselves on the wire (CTU-row bands), kept for the band parity test; bench.py and the
 # library's callers use FlagGather above (4 B per CTU) ----
 def band(ctu_rows, rank, world):
-    """rows [begin, end) of rank `rank`: same arithmetic as fhevc_band (fasthevc_amd/csrc/fhevc_api.hip) = span()"""
+    """rows [begin, end) of rank `rank`: same arithmetic as fhevc_band (fasthevc_amd/csrc/fhevc_host.hip) = span()"""
     return span(ctu_rows, rank, world)
 
 

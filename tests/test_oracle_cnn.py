@@ -200,7 +200,7 @@ def test_family_oracle_reproduces_the_base_network_and_a_float64_restatement(ora
 
 
 def _bound(wl, b, first=False):
-    """the library's requant bound (fhevc_api.hip, build_weight_image / the family loader): max over outputs of |b'| + 128 sum |w|"""
+    """the library's requant bound (fhevc_weights.hip: folded_bias, for build_weight_image and the family loaders): max over outputs of |b'| + 128 sum |w|"""
     wl = np.asarray(wl, np.int64).reshape(len(b), -1)
     bp = np.asarray(b, np.int64) + (0 if first else 128 * wl.sum(1))
     return int((np.abs(bp) + 128 * np.abs(wl).sum(1)).max())

@@ -2,7 +2,7 @@
 """The LDS image of the layer path (k_cnn_layers.inc): which row-pitch padding and XOR mask make the B-fragment reads (ds_read_b128, lane (n, h) = 16 bytes
 of position n) free of bank conflicts.  Model: /opt/skills/guides/MI355X_MICROARCH.md, LDS table: a ds_read_b128 is served in four groups of 16 lanes, a
 16-byte slot = 4 of the 64 banks, N distinct addresses on one slot within a group = N cycles.  Image: byte a of the staged map lives at
-a ^ (((a >> 8) & mask) << 4).  Prints the table fhevc_api.hip (layer_lds_image) carries.  usage: python tools/lds_swizzle_search.py"""
+a ^ (((a >> 8) & mask) << 4).  Prints the table k_cnn.hip (fhevc_layer_lds_image) carries; fhevc_weights.hip (build_layers_image) applies it to the layer images.  usage: python tools/lds_swizzle_search.py"""
 GROUPS = [list(range(0, 4)) + list(range(12, 16)) + list(range(20, 28)), list(range(4, 12)) + list(range(16, 20)) + list(range(28, 32)),
           [32, 33, 34, 35] + list(range(44, 48)) + list(range(52, 60)), list(range(36, 44)) + list(range(48, 52)) + list(range(60, 64))]
 
