@@ -17,6 +17,7 @@ BACKEND_HIP = 1
 NODES_PER_CTU = 85
 PUS4_PER_CTU = 256  # 4x4 PUs of a CTU, raster 16x16: the depth map's unit order
 LOGITS_PER_CTU = 42
+PUS_PER_CTU = 124  # rectangular PUs of a CTU whose sides are multiples of 8 (FHEVC_PUS_PER_CTU; order: motion_pu_index)
 
 # every symbol include/fasthevc.h declares (tests/test_host_logic.py::test_c_abi_exports_every_declared_symbol checks header <-> this list <-> the .so)
 SYMBOLS = [
@@ -30,6 +31,7 @@ SYMBOLS = [
     "fhevc_p_depth_range_device", "fhevc_p_predict_frame",
     "fhevc_intra_first_pass_4x4", "fhevc_intra_first_pass_4x4_all", "fhevc_intra_first_pass_4x4_device", "fhevc_intra_first_pass_candidates_device",
     "fhevc_motion_refine", "fhevc_motion_refine_device",
+    "fhevc_motion_search_pu", "fhevc_motion_search_pu_device", "fhevc_motion_pu_index",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -62,6 +64,18 @@ NODE_DTYPE = np.dtype([("satd", np.uint32), ("mode", np.uint32), ("cost", np.flo
 MOTION_DTYPE = np.dtype([("satd_zero", np.uint32), ("satd_best", np.uint32), ("cost_best", np.uint32), ("mvx", np.int16), ("mvy", np.int16)])
 # fhevc_motion_qpel_node: the vector in QUARTER samples
 MOTION_QPEL_DTYPE = np.dtype([("satd_int", np.uint32), ("satd_best", np.uint32), ("cost_best", np.uint32), ("mvx", np.int16), ("mvy", np.int16)])
+
+
+def motion_pu_index(node, shape, part):
+    """fhevc_motion_pu_index: the entry of a CTU's PUS_PER_CTU that holds `part` (0, 1) of `shape` (0 2NxN, 1 Nx2N, 2 2NxnU, 3 2NxnD, 4 nLx2N, 5 nRx2N) of
+    CU node `node`; -1 where the combination is not covered.  Pure arithmetic, the same as the library's."""
+    if node < 0 or shape < 0 or part not in (0, 1):
+        return -1
+    if node < 5:
+        return node * 12 + shape * 2 + part if shape < 6 else -1
+    if node < 21:
+        return 60 + (node - 5) * 4 + shape * 2 + part if shape < 2 else -1
+    return -1
 
 
 class FastHevcError(RuntimeError):
@@ -143,6 +157,9 @@ def load_library(path=None):
     lib.fhevc_motion_search_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.fhevc_motion_refine.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.fhevc_motion_refine_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.fhevc_motion_search_pu.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.fhevc_motion_search_pu_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.fhevc_motion_pu_index.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.fhevc_p_rule_default.argtypes = [C.POINTER(PRule)]
     lib.fhevc_p_rule_default.restype = None
     lib.fhevc_p_rule_default_wide.argtypes = [C.POINTER(PRule)]
@@ -397,6 +414,28 @@ class Context:
         rb, re = rows if rows is not None else (0, self.ctus_y)
         self._check(self.lib.fhevc_motion_refine_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range,
                                                         d_nodes, d_out, stream))
+
+    def motion_search_pu(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=4, with_nodes=False):
+        """config 4: the search of motion_search for the rectangular PUs -> [numCtus, 124] MOTION_DTYPE in the order of motion_pu_index; with_nodes:
+        (nodes [numCtus, 85], pus), the nodes as motion_search returns them, from the same pass.  search_range 1..8."""
+        cur = np.ascontiguousarray(cur_plane).reshape(-1)
+        ref = np.ascontiguousarray(ref_plane).reshape(-1)
+        assert cur.dtype == np.int16 and ref.dtype == np.int16
+        stride = stride if stride is not None else cur_plane.shape[-1]
+        pus = np.zeros(self.num_ctus * PUS_PER_CTU, MOTION_DTYPE)
+        nodes = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_DTYPE) if with_nodes else None
+        self._check(self.lib.fhevc_motion_search_pu(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, search_range,
+                                                    nodes.ctypes.data if with_nodes else None, pus.ctypes.data))
+        pus = pus.reshape(self.num_ctus, PUS_PER_CTU)
+        return (nodes.reshape(self.num_ctus, NODES_PER_CTU), pus) if with_nodes else pus
+
+    def motion_search_pu_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_pus, d_nodes=None, rows=None, stream=None, qp=32,
+                                search_range=4):
+        """frames 1.. of the batch, each searched in the frame before it; d_pus: (num_frames - 1) * band CTUs * 124 entries (16 B); d_nodes (optional):
+        (num_frames - 1) * band CTUs * 85, what motion_search_device writes for the same arguments.  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_motion_search_pu_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, search_range,
+                                                           d_nodes, d_pus, stream))
 
     def p_depth_range_device(self, d_nodes, d_prev_maps, num_pictures, d_depth_min, d_depth_max=None, rows=None, stream=None, qp=32,
                              prev_mode="colocated", rule=None):

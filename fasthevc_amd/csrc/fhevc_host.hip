@@ -160,6 +160,16 @@ int fhevc_aq_qp(const double* activity, const double* avg_activity, int width, i
   return FHEVC_OK;
 }
 
+// the entry of a CTU's FHEVC_PUS_PER_CTU that holds part `part` of shape `shape` of CU node `node`: the 64x64 and 32x32 nodes carry all six shapes, the 16x16
+// nodes the two symmetric ones (their AMP parts are 4 samples wide, below the 8x8 tiles)
+int fhevc_motion_pu_index(int node, int shape, int part)
+{
+  if (node < 0 || shape < 0 || part < 0 || part > 1) return -1;
+  if (node < 5) return shape < 6 ? node * 12 + shape * 2 + part : -1;
+  if (node < 21) return shape < 2 ? 60 + (node - 5) * 4 + shape * 2 + part : -1;
+  return -1;
+}
+
 void fhevc_p_rule_default(fhevc_p_rule* rule)
 {
   if (!rule) return;

@@ -168,6 +168,13 @@ hipError_t fhevc_launch_motion_wide(const FhevcFrames& fr, int range, const uint
 // ... and for content ABOVE 8 bit (16-bit planes; round 4): fhevc_motion_kernel itself laid out for the +-64 window (k_motion.hip), the same d_mvtab
 hipError_t fhevc_launch_motion_big(const FhevcFrames& fr, int range, const uint32_t* d_mvtab, FhevcMotionNode* d_out, int num_cus, hipStream_t stream);
 
+// ---- the same search for the rectangular PUs of the 64x64, 32x32 and 16x16 nodes (k_motion_pu.hip; config 4) ------
+#define FHEVC_PUS 124   // FHEVC_PUS_PER_CTU of fasthevc.h: 5 nodes x 6 shapes x 2 parts + 16 nodes x 2 shapes x 2 parts
+// fr, range (1 .. FHEVC_MOTION_MAX_RANGE), mvc, sad as fhevc_launch_motion; d_pus: (num_frames - 1) * band CTUs * 124 entries in the order of
+// fhevc_motion_pu_index; d_nodes (may be null): the 85 nodes of fhevc_launch_motion for the same arguments, byte for byte
+hipError_t fhevc_launch_motion_pu(const FhevcFrames& fr, int range, const FhevcMvCost& mvc, FhevcMotionNode* d_nodes, FhevcMotionNode* d_pus, int num_cus, bool sad,
+                                  hipStream_t stream);
+
 // ---- quarter-sample refinement of the search's vectors (k_motion_refine.hip; config 4) --------------------------
 struct FhevcMotionQpelNode { uint32_t satd_int, satd_best, cost_best; int16_t mvx, mvy; };
 // getCost(bits) for every number of bits two exp-Golomb components of a quarter-sample vector up to +-(4 * 64 + 3) can take (at most 38), tabulated by

@@ -318,6 +318,40 @@ int  fhevc_motion_refine_device(fhevc_ctx* ctx, const void* d_luma, int sample_b
                                 long long frame_stride_samples, int num_frames, int ctu_row_begin, int ctu_row_end,
                                 int qp, int max_range, const fhevc_motion_node* d_nodes, fhevc_motion_qpel_node* d_out, void* stream);
 
+/* The same integer search for the rectangular prediction units (k_motion_pu.hip): what HM's P configuration (AMP : 1) checks per CU after 2Nx2N,
+ * xCheckRDCostInter for SIZE_2NxN, SIZE_Nx2N and the four AMP shapes, each a predInterSearch with one xMotionEstimation per PU.  Per PU exactly the
+ * search fhevc_motion_search defines per node: full search over [-search_range, search_range]^2 in the previous original picture, raster order,
+ * strict "<", SAD or SATD as fhevc_set_motion_distortion says -- summed over the PU's 8x8 tiles and shifted ONCE by bit_depth - 8, as
+ * TComRdCost::xGetHADs does for any block whose sides are multiples of 8 --, getCostOfVectorWithPredictor with a zero predictor, border replicated.
+ * PU geometry as TComDataCU::getPartIndexAndSize, for a CU of size S:
+ *   shape 0  SIZE_2NxN   S x S/2 top,    S x S/2 bottom        shape 3  SIZE_2NxnD  S x 3S/4 top,   S x S/4 bottom
+ *   shape 1  SIZE_Nx2N   S/2 x S left,   S/2 x S right         shape 4  SIZE_nLx2N  S/4 x S left,   3S/4 x S right
+ *   shape 2  SIZE_2NxnU  S x S/4 top,    S x 3S/4 bottom       shape 5  SIZE_nRx2N  3S/4 x S left,  S/4 x S right
+ * Covered are the PUs whose sides are multiples of 8: shapes 0 and 1 of the 64x64, 32x32 and 16x16 nodes (nodes 0..20 of the 85), shapes 2..5 of
+ * the 64x64 and 32x32 nodes (nodes 0..4): FHEVC_PUS_PER_CTU entries per CTU,
+ *   nodes k = 0..4:   entry k * 12 + shape * 2 + part             nodes k = 5..20:  entry 60 + (k - 5) * 4 + shape * 2 + part
+ * which is what fhevc_motion_pu_index returns (-1 for a combination that is not covered; it needs no context).
+ * NOT covered, on purpose: AMP of 16x16 CUs (16x4 PUs need 4x4 Hadamards); the 8x4 and 4x8 PUs of 8x8 CUs; search ranges above 8 (the wide kernels
+ * serve squares only); a predictor other than zero (HM's second PU sees the first PU's vector as a candidate, this source-only twin does not).
+ * An entry is a fhevc_motion_node.  A PU is valid iff its CU NODE lies wholly inside the picture (HM never codes a partitioned CU that crosses the
+ * edge); otherwise the three distortion fields hold 0xFFFFFFFF and the vector is zero, as for nodes.  The encoder hook does not consume this
+ * output yet: a rule that turns it into a shape mask has to be fitted on the reference's own decisions first. */
+#define FHEVC_PUS_PER_CTU 124
+int  fhevc_motion_pu_index(int node, int shape, int part);
+/* device-resident batch; layout, band and stream arguments as fhevc_motion_search_device; frame f >= 1 searched in f-1.
+ * d_pus: (num_frames-1) * band CTUs * FHEVC_PUS_PER_CTU entries, compact over the band, written over exactly that extent.
+ * d_nodes: optional, (num_frames-1) * band CTUs * 85, the bytes fhevc_motion_search_device writes for the same arguments: a caller that wants both
+ * pays for the tile distortions once.  Asynchronous with respect to the host, allocates nothing, keeps no state in HBM between calls (the vector
+ * costs travel by value): calls on different streams may be in flight together.  An empty band writes nothing.  FHEVC_E_INVALID (nothing is
+ * launched or written): a null d_luma, d_pus or context, num_frames < 2, qp outside 0..51, search_range outside 1..8, stride_samples < width, a bad
+ * band, uint8 planes on a context above 8 bit. */
+int  fhevc_motion_search_pu_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                   int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range,
+                                   fhevc_motion_node* d_nodes, fhevc_motion_node* d_pus, void* stream);
+/* one picture pair, host buffers, synchronous; nodes may be NULL */
+int  fhevc_motion_search_pu(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                            fhevc_motion_node* nodes, fhevc_motion_node* pus);
+
 /* Depth range of every 4x4 unit of a P picture's CTU from its motion nodes and the co-located depths of its reference picture
  * ("inter-CU depth reuse", BASELINE config 4).  Host-side integer arithmetic, no device work.  Per split decision (64->32,
  * 32->16, 16->8) a linear score over nine features of the node, all in 1/256 units (L(x) = floor(256 log2 x) by integer
@@ -398,7 +432,7 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
 /* average duration in ms of the dominant kernels over launches since the last reset, measured with HIP
  * events on the launch stream; which: 0 = depth CNN, 1 = source Hadamard, 2 = first pass, 3 = pre-analysis, 4 = motion search,
  * 5 = P-picture depth ranges (fhevc_p_depth_range_device), 6 = first pass of the 4x4 PUs (fhevc_intra_first_pass_4x4*),
- * 7 = quarter-sample motion refinement (fhevc_motion_refine*) */
+ * 7 = quarter-sample motion refinement (fhevc_motion_refine*), 8 = motion search of the rectangular PUs (fhevc_motion_search_pu*) */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
 int  fhevc_enable_kernel_timing(fhevc_ctx* ctx, int on);
 
