@@ -17,6 +17,7 @@ BACKEND_HIP = 1
 NODES_PER_CTU = 85
 PUS4_PER_CTU = 256  # 4x4 PUs of a CTU, raster 16x16: the depth map's unit order
 LOGITS_PER_CTU = 42
+PUS_SMALL_PER_CTU = 384  # PUs with a 4-sample side: AMP of the 16x16 nodes, 8x4 / 4x8 of the 8x8 nodes (FHEVC_PUS_SMALL_PER_CTU; order: motion_pu_small_index)
 PUS_PER_CTU = 124  # rectangular PUs of a CTU whose sides are multiples of 8 (FHEVC_PUS_PER_CTU; order: motion_pu_index)
 
 # every symbol include/fasthevc.h declares (tests/test_host_logic.py::test_c_abi_exports_every_declared_symbol checks header <-> this list <-> the .so)
@@ -32,6 +33,7 @@ SYMBOLS = [
     "fhevc_intra_first_pass_4x4", "fhevc_intra_first_pass_4x4_all", "fhevc_intra_first_pass_4x4_device", "fhevc_intra_first_pass_candidates_device",
     "fhevc_motion_refine", "fhevc_motion_refine_device",
     "fhevc_motion_search_pu", "fhevc_motion_search_pu_device", "fhevc_motion_pu_index",
+    "fhevc_motion_search_pu_small", "fhevc_motion_search_pu_small_device", "fhevc_motion_pu_small_index",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -75,6 +77,18 @@ def motion_pu_index(node, shape, part):
         return node * 12 + shape * 2 + part if shape < 6 else -1
     if node < 21:
         return 60 + (node - 5) * 4 + shape * 2 + part if shape < 2 else -1
+    return -1
+
+
+def motion_pu_small_index(node, shape, part):
+    """fhevc_motion_pu_small_index: the entry of a CTU's PUS_SMALL_PER_CTU that holds `part` (0, 1) of `shape` (numbers of motion_pu_index) of CU node `node`:
+    shapes 2..5 of the 16x16 nodes 5..20, then shapes 0..1 of the 8x8 nodes 21..84; -1 for anything else.  Pure arithmetic, the same as the library's."""
+    if part not in (0, 1):
+        return -1
+    if 5 <= node < 21:
+        return (node - 5) * 8 + (shape - 2) * 2 + part if 2 <= shape < 6 else -1
+    if 21 <= node < 85:
+        return 128 + (node - 21) * 4 + shape * 2 + part if 0 <= shape < 2 else -1
     return -1
 
 
@@ -160,6 +174,9 @@ def load_library(path=None):
     lib.fhevc_motion_search_pu.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.fhevc_motion_search_pu_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     lib.fhevc_motion_pu_index.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.fhevc_motion_search_pu_small.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.fhevc_motion_search_pu_small_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.fhevc_motion_pu_small_index.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.fhevc_p_rule_default.argtypes = [C.POINTER(PRule)]
     lib.fhevc_p_rule_default.restype = None
     lib.fhevc_p_rule_default_wide.argtypes = [C.POINTER(PRule)]
@@ -436,6 +453,24 @@ class Context:
         rb, re = rows if rows is not None else (0, self.ctus_y)
         self._check(self.lib.fhevc_motion_search_pu_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, search_range,
                                                            d_nodes, d_pus, stream))
+
+    def motion_search_pu_small(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=4):
+        """config 4: the search of motion_search for the PUs with a 4-sample side (AMP of 16x16 CUs, 8x4 / 4x8) -> [numCtus, 384] MOTION_DTYPE in the order
+        of motion_pu_small_index.  search_range 1..8."""
+        cur = np.ascontiguousarray(cur_plane).reshape(-1)
+        ref = np.ascontiguousarray(ref_plane).reshape(-1)
+        assert cur.dtype == np.int16 and ref.dtype == np.int16
+        stride = stride if stride is not None else cur_plane.shape[-1]
+        pus = np.zeros(self.num_ctus * PUS_SMALL_PER_CTU, MOTION_DTYPE)
+        self._check(self.lib.fhevc_motion_search_pu_small(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, search_range,
+                                                          pus.ctypes.data))
+        return pus.reshape(self.num_ctus, PUS_SMALL_PER_CTU)
+
+    def motion_search_pu_small_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_pus, rows=None, stream=None, qp=32, search_range=4):
+        """frames 1.. of the batch, each searched in the frame before it; d_pus: (num_frames - 1) * band CTUs * 384 entries (16 B).  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_motion_search_pu_small_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, search_range,
+                                                                 d_pus, stream))
 
     def p_depth_range_device(self, d_nodes, d_prev_maps, num_pictures, d_depth_min, d_depth_max=None, rows=None, stream=None, qp=32,
                              prev_mode="colocated", rule=None):

@@ -267,7 +267,7 @@ void fhevc_destroy(fhevc_ctx* c)
   if (c->lw_done) (void)hipEventDestroy(c->lw_done);
   void* const bufs[] = { c->d_frag, c->d_bias, c->d_whead, c->d_bhead, c->d_frag_i8, c->d_bias_i8,                                  // the base image
                          c->f_frag1, c->f_bias1, c->f_frag2, c->f_frag3, c->f_bias_i8, c->f_whead, c->f_headm, c->f_bhead,          // a fused family member's
-                         c->d_luma, c->d_depth, c->d_had, c->d_nodes, c->d_satd, c->d_satd_out, c->d_act, c->d_depth_max, c->d_pair, c->d_motion, c->d_qpel, c->d_motion_pu,
+                         c->d_luma, c->d_depth, c->d_had, c->d_nodes, c->d_satd, c->d_satd_out, c->d_act, c->d_depth_max, c->d_pair, c->d_motion, c->d_qpel, c->d_motion_pu, c->d_motion_pu_small,
                          c->d_p_maps, c->d_mvtab, c->d_cand_all, c->d_cand, c->d_best4, c->d_modes4 };
   for (void* q : bufs) (void)hipFree(q);
   for (void* q : c->lw_bufs) (void)hipFree(q);
@@ -292,7 +292,7 @@ int fhevc_enable_kernel_timing(fhevc_ctx* c, int on)
 
 int fhevc_kernel_timing(fhevc_ctx* c, int which, int reset, double* avg_ms, uint64_t* launches)
 {
-  if (!c || which < 0 || which > 8) return FHEVC_E_INVALID;
+  if (!c || which < 0 || which > 9) return FHEVC_E_INVALID;
   time_resolve(c);
   if (avg_ms) *avg_ms = c->launches[which] ? c->sum_ms[which] / (double)c->launches[which] : 0.0;
   if (launches) *launches = c->launches[which];
@@ -868,6 +868,43 @@ int fhevc_motion_search_pu(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
   HIP_TRY(c, hipMemcpyAsync(pus, c->d_motion_pu, pu_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->stats.bytes_d2h += (uint64_t)pu_bytes + (nodes ? (uint64_t)motion_bytes(c) : 0);
+  return FHEVC_OK;
+}
+
+// ---- the search of the PUs with a 4-sample side (k_motion_pu_small.hip) ----
+
+int fhevc_motion_search_pu_small_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                        int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range,
+                                        fhevc_motion_node* d_pus, void* stream)
+{
+  if (!c || !d_luma || !d_pus) return c ? fail(c, FHEVC_E_INVALID, "bad small-PU motion-search arguments") : FHEVC_E_INVALID;
+  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
+  if (search_range < 1 || search_range > FHEVC_MOTION_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "the small-PU motion search covers search ranges 1..8");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
+  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
+  static_assert(FHEVC_PUS_SMALL_PER_CTU == FHEVC_PUS_SMALL, "small-PU count");
+  return launch_on(c, stream, 9, "fhevc_launch_motion_pu_small", [&](hipStream_t s) {
+    return fhevc_launch_motion_pu_small(fr, search_range, mv_cost_table(qp, search_range), reinterpret_cast<FhevcMotionNode*>(d_pus), c->num_cus, c->motion_sad, s);
+  });
+}
+
+int fhevc_motion_search_pu_small(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                                 fhevc_motion_node* pus)
+{
+  if (!c || !cur_luma || !ref_luma || !pus || stride_samples < c->cfg.width)
+    return c ? fail(c, FHEVC_E_INVALID, "bad small-PU motion-search arguments") : FHEVC_E_INVALID;
+  if (qp < 0 || qp > 51 || search_range < 1 || search_range > FHEVC_MOTION_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad small-PU motion-search arguments");
+  (void)hipSetDevice(c->device);
+  const size_t pu_bytes = (size_t)c->num_ctus * FHEVC_PUS_SMALL * sizeof(FhevcMotionNode);
+  HIP_TRY(c, ensure(c->d_motion_pu_small, pu_bytes));
+  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
+  if (rc != FHEVC_OK) return rc;
+  rc = fhevc_motion_search_pu_small_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, search_range,
+                                           reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu_small), c->stream);
+  if (rc != FHEVC_OK) return rc;
+  HIP_TRY(c, hipMemcpyAsync(pus, c->d_motion_pu_small, pu_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->stats.bytes_d2h += (uint64_t)pu_bytes;
   return FHEVC_OK;
 }
 

@@ -170,6 +170,15 @@ int fhevc_motion_pu_index(int node, int shape, int part)
   return -1;
 }
 
+// the entry of a CTU's FHEVC_PUS_SMALL_PER_CTU: the four AMP shapes of the 16x16 nodes first, then the two symmetric shapes of the 8x8 nodes
+int fhevc_motion_pu_small_index(int node, int shape, int part)
+{
+  if (part < 0 || part > 1) return -1;
+  if (node >= 5 && node < 21) return shape >= 2 && shape < 6 ? (node - 5) * 8 + (shape - 2) * 2 + part : -1;
+  if (node >= 21 && node < 85) return shape >= 0 && shape < 2 ? 128 + (node - 21) * 4 + shape * 2 + part : -1;
+  return -1;
+}
+
 void fhevc_p_rule_default(fhevc_p_rule* rule)
 {
   if (!rule) return;

@@ -175,6 +175,12 @@ hipError_t fhevc_launch_motion_big(const FhevcFrames& fr, int range, const uint3
 hipError_t fhevc_launch_motion_pu(const FhevcFrames& fr, int range, const FhevcMvCost& mvc, FhevcMotionNode* d_nodes, FhevcMotionNode* d_pus, int num_cus, bool sad,
                                   hipStream_t stream);
 
+// ---- ... and for the PUs with a 4-sample side: AMP of the 16x16 nodes, 8x4 / 4x8 of the 8x8 nodes (k_motion_pu_small.hip; config 4) ------
+#define FHEVC_PUS_SMALL 384   // FHEVC_PUS_SMALL_PER_CTU of fasthevc.h: 16 nodes x 4 shapes x 2 parts + 64 nodes x 2 shapes x 2 parts
+// fr, range (1 .. FHEVC_MOTION_MAX_RANGE), mvc, sad as fhevc_launch_motion; d_pus: (num_frames - 1) * band CTUs * 384 entries in the order of
+// fhevc_motion_pu_small_index
+hipError_t fhevc_launch_motion_pu_small(const FhevcFrames& fr, int range, const FhevcMvCost& mvc, FhevcMotionNode* d_pus, int num_cus, bool sad, hipStream_t stream);
+
 // ---- quarter-sample refinement of the search's vectors (k_motion_refine.hip; config 4) --------------------------
 struct FhevcMotionQpelNode { uint32_t satd_int, satd_best, cost_best; int16_t mvx, mvy; };
 // getCost(bits) for every number of bits two exp-Golomb components of a quarter-sample vector up to +-(4 * 64 + 3) can take (at most 38), tabulated by

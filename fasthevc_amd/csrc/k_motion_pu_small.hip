@@ -1,0 +1,297 @@
+// k_motion_pu_small.hip -- source-only integer motion search of the PUs with a 4-sample side: the AMP shapes of the 16x16 CUs (16x4, 16x12, 4x16,
+// 12x16) and the 2NxN / Nx2N PUs of the 8x8 CUs (8x4, 4x8), gfx950 only.
+//
+// What k_motion_pu.hip delivers for the 124 PUs whose sides are multiples of 8, for the 384 that are left (layout: fhevc_motion_pu_small_index of
+// fasthevc.h): full search over [-R, R]^2 in the PREVIOUS ORIGINAL picture, raster order and strict "<", SAD or Hadamard SATD, the vector cost of
+// getCostOfVectorWithPredictor with a zero predictor, reference samples outside the picture replicated from the border.  TComRdCost::xGetHADs
+// tiles a block by 8x8 only if BOTH sides are multiples of 8; every other block goes WHOLLY through xCalcHADs4x4 (TComRdCost.cpp:1771-1803).  So
+// these PUs are not sums of the 8x8 tile distortions of the other two kernels: a 16x12 PU is twelve 4x4 Hadamards, each with its own
+// (sum + 1) >> 1, and the block's sum is shifted ONCE by bit_depth - 8.  SAD is additive and shifted once as well.
+//
+// Mapping as fhevc_motion_kernel at MR = 8: workgroup (4 waves) = one CTU at a time, grid-stride; lane = one 8x8 tile with its original samples
+// packed in registers; the reference window staged once per CTU in LDS; the waves split the vectors and are merged by (cost, raster index).
+// New: per tile and vector the lane computes the four QUADRANT distortions q00 q01 / q10 q11 (4x4 SAD or 4x4 Hadamard), and the lanes are
+// numbered so that the four tiles of a 16x16 node sit on one lane quad (lane = node * 4 + ty1 * 2 + tx1), which makes the node's reduction three
+// DPP quad permutes and no LDS:
+//   the tile's own PUs      8x4 top = q00 + q01    8x4 bottom = q10 + q11    4x8 left = q00 + q10    4x8 right = q01 + q11
+//   the node's AMP PUs      quarter strip = the two tiles' halves on that side; three-quarter part = the node's sixteen quadrants minus the strip
+// Lane p of the quad keeps one AMP shape of its node, the one whose quarter strip passes through its tile and its neighbour's in ONE permute:
+//   p = 0: 2NxnU (top strip, + lane 1's top)      p = 1: nRx2N (right strip, + lane 3's right)
+//   p = 2: nLx2N (left strip, + lane 0's left)    p = 3: 2NxnD (bottom strip, + lane 2's bottom)
+// so every lane keeps six running (cost, vector index) pairs, all of entries it alone owns; the distortion at the best vector is cost - vector cost.
+#include "fhevc_internal.h"
+#include "k_had8x8.h"
+
+namespace {
+
+constexpr int MR = FHEVC_MOTION_MAX_RANGE;
+constexpr int RP = 64 + 2 * MR + 8;            // LDS row pitch of the reference window in samples (multiple of 8: 16-byte row starts)
+constexpr int REF_SAMPLES = (64 + 2 * MR) * RP + 8;
+constexpr int NMV_MAX = (2 * MR + 1) * (2 * MR + 1);
+constexpr int SLOTS = 6;                       // per lane: 8x4 top, 8x4 bottom, 4x8 left, 4x8 right of its tile; part 0 and part 1 of its AMP shape
+constexpr int ENTRIES = FHEVC_PUS_SMALL;
+constexpr int AMP_ENTRIES = 128;               // 16 nodes x 4 shapes x 2 parts, then 64 tiles x 2 shapes x 2 parts
+
+template <typename T>
+__device__ __forceinline__ int sample_at(const T* plane, long long off) { return (int)plane[off]; }
+
+// lane (i & ~3) | P_(i & 3) of the same quad (DPP quad_perm: a VALU operand modifier, no LDS); every lane of the wave is active where this is used
+template <int P0, int P1, int P2, int P3>
+__device__ __forceinline__ unsigned quad(unsigned v)
+{
+  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, P0 | (P1 << 2) | (P2 << 4) | (P3 << 6), 0xF, 0xF, false);
+}
+
+// xCalcHADs4x4 of the quadrant at rows r0 .., packed pairs j0, j0 + 1 of a block of differences held as 8 rows x 4 packed pairs: (sum |H4 d H4| + 1) >> 1.
+// |coefficients| stay below 2^15 through three stages up to 10 bit (8 * 1023); the fourth, inside a packed pair, is folded into the absolute sum:
+// |a + b| + |a - b| = 2 max(|a|, |b|), so the sum is even and the rounding shift is exact
+__device__ __forceinline__ unsigned had4x4_packed(const unsigned (&d)[32], int r0, int j0)
+{
+  unsigned a[4][2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {  // vertical
+    const unsigned s0 = pk_add(d[(r0 + 0) * 4 + j0 + j], d[(r0 + 1) * 4 + j0 + j]), d0 = pk_sub(d[(r0 + 0) * 4 + j0 + j], d[(r0 + 1) * 4 + j0 + j]);
+    const unsigned s1 = pk_add(d[(r0 + 2) * 4 + j0 + j], d[(r0 + 3) * 4 + j0 + j]), d1 = pk_sub(d[(r0 + 2) * 4 + j0 + j], d[(r0 + 3) * 4 + j0 + j]);
+    a[0][j] = pk_add(s0, s1); a[1][j] = pk_sub(s0, s1); a[2][j] = pk_add(d0, d1); a[3][j] = pk_sub(d0, d1);
+  }
+  unsigned acc = 0;
+#pragma unroll
+  for (int y = 0; y < 4; ++y) {  // horizontal distance 2: pair 0 +- pair 1; distance 1: inside the pair
+    const unsigned p = pk_abs(pk_add(a[y][0], a[y][1])), q = pk_abs(pk_sub(a[y][0], a[y][1]));
+    acc += max(p & 0xFFFFu, p >> 16) + max(q & 0xFFFFu, q >> 16);
+  }
+  return (2 * acc + 1) >> 1;
+}
+// 32-bit twin (12-bit content): v[64] row-major, the quadrant at (r0, c0)
+__device__ __forceinline__ unsigned had4x4_wide(const int (&v)[64], int r0, int c0)
+{
+  int a[16];
+#pragma unroll
+  for (int y = 0; y < 4; ++y) {
+    const int x0 = v[8 * (r0 + y) + c0], x1 = v[8 * (r0 + y) + c0 + 1], x2 = v[8 * (r0 + y) + c0 + 2], x3 = v[8 * (r0 + y) + c0 + 3];
+    const int s0 = x0 + x1, d0 = x0 - x1, s1 = x2 + x3, d1 = x2 - x3;
+    a[4 * y + 0] = s0 + s1; a[4 * y + 1] = s0 - s1; a[4 * y + 2] = d0 + d1; a[4 * y + 3] = d0 - d1;
+  }
+  unsigned s = 0;
+#pragma unroll
+  for (int x = 0; x < 4; ++x) {
+    const int s0 = a[x] + a[4 + x], d0 = a[x] - a[4 + x], s1 = a[8 + x] + a[12 + x], d1 = a[8 + x] - a[12 + x];
+    s += (unsigned)abs(s0 + s1) + (unsigned)abs(s0 - s1) + (unsigned)abs(d0 + d1) + (unsigned)abs(d0 - d1);
+  }
+  return (s + 1) >> 1;
+}
+
+// T = int16_t (HM Pel planes) or uint8_t; PACKED = bit depth <= 10; SAD: as fhevc_motion_kernel
+template <typename T, bool PACKED, bool SAD>
+__global__ __launch_bounds__(256, (PACKED ? 4 : 3)) void fhevc_motion_pu_small_kernel(FhevcFrames F, int range, FhevcMvCost mvc, FhevcMotionNode* __restrict__ out_pus)
+{
+  __shared__ __attribute__((aligned(16))) short s_ref[REF_SAMPLES];
+  __shared__ unsigned s_cost[4][ENTRIES], s_idx[4][ENTRIES], s_zero[ENTRIES], s_vc[NMV_MAX];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int quad_pos = lane & 3, node16 = lane >> 2;  // the tile's place in its 16x16 node (bit 0: right, bit 1: lower), the node (raster 4x4)
+  const int tx = (node16 & 3) * 2 + (quad_pos & 1), ty = (node16 >> 2) * 2 + (quad_pos >> 1);
+  // this lane's six entries: four of its tile (8x8 node 21 + ty * 8 + tx), two of its node's AMP shape (0: 2NxnU, 1: 2NxnD, 2: nLx2N, 3: nRx2N)
+  const int amp_shape = quad_pos == 0 ? 0 : quad_pos == 1 ? 3 : quad_pos == 2 ? 2 : 1;
+  const int e_tile = AMP_ENTRIES + (ty * 8 + tx) * 4, e_amp = node16 * 8 + amp_shape * 2;
+  const bool strip_is_part0 = (quad_pos & 1) == 0;  // 2NxnU and nLx2N: the quarter strip comes first
+  const int band_rows = F.row_end - F.row_begin;
+  const int per_frame = band_rows * F.ctus_x;
+  const int total = per_frame * (F.num_frames - 1);  // frame f >= 1 is searched in frame f - 1
+  const int side = 2 * range + 1, nmv = side * side, centre = (nmv - 1) >> 1;
+  const int win = 64 + 2 * range;
+  const int shift = F.bit_depth - 8;
+  const int delta = (8 - (range & 7)) & 7;  // the window starts at column 64 cx - range: delta samples after a multiple of 8
+  const T* plane = reinterpret_cast<const T*>(F.luma);
+
+  for (int work = blockIdx.x; work < total; work += gridDim.x) {
+    const int f = 1 + work / per_frame;
+    const int rem = work % per_frame;
+    const int cy = F.row_begin + rem / F.ctus_x, cx = rem % F.ctus_x;
+    const long long cur_base = (long long)f * F.frame_stride, ref_base = (long long)(f - 1) * F.frame_stride;
+    // ---- stage the reference window (the staging loop of fhevc_motion_kernel): rows cy*64 - R .. + win, columns cx*64 - R .. + win, clamped ----
+    __syncthreads();  // the previous CTU's readers are done
+    {
+      const int chunks = (win + delta + 7) >> 3;
+      for (int it = tid; it < win * chunks; it += 256) {
+        const int wr = it / chunks, wc = (it - wr * chunks) * 8;
+        const int py = min(max(cy * 64 - range + wr, 0), F.height - 1);
+        const int px0 = cx * 64 - range - delta + wc;
+        short v[8];
+        const long long row = ref_base + (long long)py * F.stride;
+        const T* src = plane + row + px0;
+        if (px0 >= 0 && px0 + 8 <= F.width && (reinterpret_cast<uintptr_t>(src) & (8 * sizeof(T) - 1)) == 0) {
+          if (sizeof(T) == 2) {
+            const uint4 q = *reinterpret_cast<const uint4*>(src);
+            *reinterpret_cast<uint4*>(s_ref + wr * RP + wc) = q;
+            continue;
+          } else {
+            const uint2 q = *reinterpret_cast<const uint2*>(src);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { v[k] = (short)((q.x >> (8 * k)) & 0xFF); v[4 + k] = (short)((q.y >> (8 * k)) & 0xFF); }
+          }
+        } else if (px0 >= 0 && px0 + 8 <= F.width) {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) v[k] = (short)sample_at(plane, row + px0 + k);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) v[k] = (short)sample_at(plane, row + min(max(px0 + k, 0), F.width - 1));
+        }
+        // one 16-byte store of whole dwords (no sub-dword LDS access): wc is a multiple of 8, the row pitch too
+        uint4 q;
+        q.x = ((unsigned)v[0] & 0xFFFFu) | ((unsigned)v[1] << 16); q.y = ((unsigned)v[2] & 0xFFFFu) | ((unsigned)v[3] << 16);
+        q.z = ((unsigned)v[4] & 0xFFFFu) | ((unsigned)v[5] << 16); q.w = ((unsigned)v[6] & 0xFFFFu) | ((unsigned)v[7] << 16);
+        *reinterpret_cast<uint4*>(s_ref + wr * RP + wc) = q;
+      }
+    }
+    // ---- this lane's original 8x8 tile (all four waves hold the same 64 tiles) ----
+    const int px = cx * 64 + tx * 8, py = cy * 64 + ty * 8;
+    const bool inside = (px + 8 <= F.width) && (py + 8 <= F.height);
+    unsigned O[32];
+    if (inside) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const long long row = cur_base + (long long)(py + j) * F.stride + px;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          O[4 * j + k] = ((unsigned)sample_at(plane, row + 2 * k) & 0xFFFFu) | ((unsigned)sample_at(plane, row + 2 * k + 1) << 16);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 32; ++i) O[i] = 0;
+    }
+    __syncthreads();
+
+    unsigned bc[SLOTS], bi[SLOTS];
+#pragma unroll
+    for (int k = 0; k < SLOTS; ++k) { bc[k] = 0xFFFFFFFFu; bi[k] = 0; }
+    for (int m = wave; m < nmv; m += 4) {  // raster order inside a wave; the waves interleave and are merged by (cost, index)
+      const int dy = m / side - range, dx = m % side - range;
+      const int col = tx * 8 + range + dx + delta, row0 = ty * 8 + range + dy;
+      const unsigned sh = (unsigned)(col & 1) * 16u;  // uniform: R + dx
+      unsigned q[4] = { 0, 0, 0, 0 };  // q00 q01 / q10 q11
+      if (PACKED && SAD) {  // sum |org - ref| on pairs of unsigned 16-bit samples: v_sad_u16
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const unsigned* r = reinterpret_cast<const unsigned*>(s_ref) + (((row0 + j) * RP + col) >> 1);
+          const unsigned d0 = r[0], d1 = r[1], d2 = r[2], d3 = r[3], d4 = r[4];
+          unsigned& l = q[(j >> 2) * 2], &rr = q[(j >> 2) * 2 + 1];
+          l = __builtin_amdgcn_sad_u16(O[4 * j + 0], __builtin_amdgcn_alignbit(d1, d0, sh), l);
+          l = __builtin_amdgcn_sad_u16(O[4 * j + 1], __builtin_amdgcn_alignbit(d2, d1, sh), l);
+          rr = __builtin_amdgcn_sad_u16(O[4 * j + 2], __builtin_amdgcn_alignbit(d3, d2, sh), rr);
+          rr = __builtin_amdgcn_sad_u16(O[4 * j + 3], __builtin_amdgcn_alignbit(d4, d3, sh), rr);
+        }
+      } else if (PACKED) {
+        unsigned D[32];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const unsigned* r = reinterpret_cast<const unsigned*>(s_ref) + (((row0 + j) * RP + col) >> 1);
+          const unsigned d0 = r[0], d1 = r[1], d2 = r[2], d3 = r[3], d4 = r[4];
+          D[4 * j + 0] = pk_sub(O[4 * j + 0], __builtin_amdgcn_alignbit(d1, d0, sh));
+          D[4 * j + 1] = pk_sub(O[4 * j + 1], __builtin_amdgcn_alignbit(d2, d1, sh));
+          D[4 * j + 2] = pk_sub(O[4 * j + 2], __builtin_amdgcn_alignbit(d3, d2, sh));
+          D[4 * j + 3] = pk_sub(O[4 * j + 3], __builtin_amdgcn_alignbit(d4, d3, sh));
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = had4x4_packed(D, (k >> 1) * 4, (k & 1) * 2);
+      } else {
+        int v[64];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          // whole dwords from LDS, as the packed forms read them
+          const unsigned* r = reinterpret_cast<const unsigned*>(s_ref) + (((row0 + j) * RP + col) >> 1);
+          const unsigned d0 = r[0], d1 = r[1], d2 = r[2], d3 = r[3], d4 = r[4];
+          const unsigned w[4] = { __builtin_amdgcn_alignbit(d1, d0, sh), __builtin_amdgcn_alignbit(d2, d1, sh), __builtin_amdgcn_alignbit(d3, d2, sh),
+                                  __builtin_amdgcn_alignbit(d4, d3, sh) };
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            v[8 * j + 2 * k] = (int)(short)(O[4 * j + k] & 0xFFFFu) - (int)(short)(w[k] & 0xFFFFu);
+            v[8 * j + 2 * k + 1] = (int)(short)(O[4 * j + k] >> 16) - (int)(short)(w[k] >> 16);
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (SAD) {
+#pragma unroll
+            for (int y = 0; y < 4; ++y)
+#pragma unroll
+              for (int x = 0; x < 4; ++x) q[k] += (unsigned)abs(v[8 * ((k >> 1) * 4 + y) + (k & 1) * 4 + x]);
+          } else q[k] = had4x4_wide(v, (k >> 1) * 4, (k & 1) * 4);
+        }
+      }
+      // ---- the tile's four PUs, then the node's AMP shape this lane keeps (quad_pos = lane bits 0..1) ----
+      unsigned d[SLOTS];
+      const unsigned top = inside ? q[0] + q[1] : 0u, bottom = inside ? q[2] + q[3] : 0u;
+      const unsigned left = inside ? q[0] + q[2] : 0u, right = inside ? q[1] + q[3] : 0u;
+      d[0] = top; d[1] = bottom; d[2] = left; d[3] = right;
+      const unsigned t8 = top + bottom;
+      const unsigned h = t8 + quad<1, 0, 3, 2>(t8);
+      const unsigned s16 = h + quad<2, 3, 0, 1>(h);  // the node's sixteen quadrants
+      // each lane hands the half its partner's strip needs: 0 <- 1: top, 1 <- 3: right, 2 <- 0: left, 3 <- 2: bottom
+      const unsigned give = quad_pos == 1 ? top : quad_pos == 3 ? right : quad_pos == 0 ? left : bottom;
+      const unsigned own = quad_pos == 0 ? top : quad_pos == 1 ? right : quad_pos == 2 ? left : bottom;
+      const unsigned strip = own + quad<1, 3, 0, 2>(give);
+      d[4] = strip_is_part0 ? strip : s16 - strip;
+      d[5] = s16 - d[4];
+      const unsigned vc = mvc.c[m];
+      if (lane == 0) s_vc[m] = vc;  // the merge looks the winner's vector cost up by a per-thread index (every m is one wave's)
+#pragma unroll
+      for (int k = 0; k < SLOTS; ++k) {
+        const unsigned c = (d[k] >> shift) + vc;  // DISTORTION_PRECISION_ADJUSTMENT on the block's sum, once (TComRdCost.cpp:1823)
+        if (c < bc[k]) { bc[k] = c; bi[k] = (unsigned)m; }
+      }
+      if (m == centre) {  // uniform: one wave, once per CTU
+#pragma unroll
+        for (int k = 0; k < SLOTS; ++k) s_zero[k < 4 ? e_tile + k : e_amp + k - 4] = d[k] >> shift;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < SLOTS; ++k) {
+      const int e = k < 4 ? e_tile + k : e_amp + k - 4;
+      s_cost[wave][e] = bc[k]; s_idx[wave][e] = bi[k];
+    }
+    __syncthreads();
+    for (int e = tid; e < ENTRIES; e += 256) {
+      // the CU node this entry belongs to: a PU is valid iff its node lies wholly inside the picture
+      const int n = e < AMP_ENTRIES ? 16 : 8, cnt = 64 / n;
+      const int ni = e < AMP_ENTRIES ? e >> 3 : (e - AMP_ENTRIES) >> 2;
+      const int bx = ni % cnt, by = ni / cnt;
+      uint4 o;
+      if (cx * 64 + bx * n + n > F.width || cy * 64 + by * n + n > F.height) {
+        o.x = o.y = o.z = 0xFFFFFFFFu; o.w = 0;
+      } else {
+        unsigned c = s_cost[0][e], ix = s_idx[0][e];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) {
+          const unsigned c2 = s_cost[w][e], i2 = s_idx[w][e];
+          if (c2 < c || (c2 == c && i2 < ix)) { c = c2; ix = i2; }
+        }
+        const int mvx = (int)(ix % side) - range, mvy = (int)(ix / side) - range;
+        o.x = s_zero[e]; o.y = c - s_vc[ix]; o.z = c;
+        o.w = ((unsigned)mvx & 0xFFFFu) | ((unsigned)mvy << 16);
+      }
+      const long long oc = (long long)((f - 1) * band_rows + (cy - F.row_begin)) * F.ctus_x + cx;
+      *reinterpret_cast<uint4*>(out_pus + oc * ENTRIES + e) = o;  // one 16-byte store per entry
+    }
+  }
+}
+
+}  // namespace
+
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage): 29 076 B of LDS per workgroup (window 14 096 B, merge 13 824 B, vector costs
+// 1 156 B), no scratch; the packed forms take 95 (SAD) and 115 (SATD) VGPRs and are held to four waves per SIMD (four workgroups per CU, 116 KB of
+// its LDS), the 32-bit forms 147 and 131 (three workgroups per CU).  The persistent grid is sized to exactly that residency
+hipError_t fhevc_launch_motion_pu_small(const FhevcFrames& fr, int range, const FhevcMvCost& mvc, FhevcMotionNode* d_pus, int num_cus, bool sad, hipStream_t stream)
+{
+  const long long total = (long long)(fr.row_end - fr.row_begin) * fr.ctus_x * (fr.num_frames - 1);
+  if (total <= 0) return hipSuccess;
+  if (range < 1 || range > FHEVC_MOTION_MAX_RANGE || !d_pus) return hipErrorInvalidValue;
+  const long long resident = (fr.sample_bytes == 2 && fr.bit_depth > 10 ? 3LL : 4LL) * num_cus;
+  const int grid = (int)(total < resident ? total : resident);
+#define FHEVC_MOTION_PU_SMALL(T, P) do { if (sad) hipLaunchKernelGGL((fhevc_motion_pu_small_kernel<T, P, true>), dim3(grid), dim3(256), 0, stream, fr, range, mvc, d_pus); \
+                                         else hipLaunchKernelGGL((fhevc_motion_pu_small_kernel<T, P, false>), dim3(grid), dim3(256), 0, stream, fr, range, mvc, d_pus); } while (0)
+  if (fr.sample_bytes == 2 && fr.bit_depth <= 10) FHEVC_MOTION_PU_SMALL(int16_t, true);
+  else if (fr.sample_bytes == 2) FHEVC_MOTION_PU_SMALL(int16_t, false);
+  else FHEVC_MOTION_PU_SMALL(uint8_t, true);
+#undef FHEVC_MOTION_PU_SMALL
+  return hipGetLastError();
+}

@@ -331,8 +331,9 @@ int  fhevc_motion_refine_device(fhevc_ctx* ctx, const void* d_luma, int sample_b
  * the 64x64 and 32x32 nodes (nodes 0..4): FHEVC_PUS_PER_CTU entries per CTU,
  *   nodes k = 0..4:   entry k * 12 + shape * 2 + part             nodes k = 5..20:  entry 60 + (k - 5) * 4 + shape * 2 + part
  * which is what fhevc_motion_pu_index returns (-1 for a combination that is not covered; it needs no context).
- * NOT covered, on purpose: AMP of 16x16 CUs (16x4 PUs need 4x4 Hadamards); the 8x4 and 4x8 PUs of 8x8 CUs; search ranges above 8 (the wide kernels
- * serve squares only); a predictor other than zero (HM's second PU sees the first PU's vector as a candidate, this source-only twin does not).
+ * NOT covered by this entry point: AMP of 16x16 CUs (16x4 PUs need 4x4 Hadamards) and the 8x4 and 4x8 PUs of 8x8 CUs -- those are
+ * fhevc_motion_search_pu_small's, below.  NOT covered by either, on purpose: search ranges above 8 (the wide kernels serve squares only); a
+ * predictor other than zero (HM's second PU sees the first PU's vector as a candidate, this source-only twin does not).
  * An entry is a fhevc_motion_node.  A PU is valid iff its CU NODE lies wholly inside the picture (HM never codes a partitioned CU that crosses the
  * edge); otherwise the three distortion fields hold 0xFFFFFFFF and the vector is zero, as for nodes.  The encoder hook does not consume this
  * output yet: a rule that turns it into a shape mask has to be fitted on the reference's own decisions first. */
@@ -351,6 +352,38 @@ int  fhevc_motion_search_pu_device(fhevc_ctx* ctx, const void* d_luma, int sampl
 /* one picture pair, host buffers, synchronous; nodes may be NULL */
 int  fhevc_motion_search_pu(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
                             fhevc_motion_node* nodes, fhevc_motion_node* pus);
+
+/* ... and for the PUs with a side of 4 or 12 samples (k_motion_pu_small.hip), the shapes HM's P configuration checks at the deepest levels of the
+ * quad-tree: AMP of the 16x16 CUs (TEncCu.cpp:685 opens AMP for the 64x64, 32x32 AND 16x16 CUs: PUs of 16x4, 16x12, 4x16, 12x16) and the 2NxN /
+ * Nx2N PUs of the 8x8 CUs (8x4, 4x8: the smallest inter PUs of HEVC).  Per PU exactly the search fhevc_motion_search defines per node: full search
+ * over [-search_range, search_range]^2 (search_range 1..8) in the previous ORIGINAL picture, border replicated, raster order, strict "<", cost =
+ * distortion + getCostOfVectorWithPredictor with a zero predictor and the lambda of slice QP qp, SAD or SATD as fhevc_set_motion_distortion says.
+ * The distortion of a w x h PU with a side that is not a multiple of 8:
+ *   SAD   the plain sum of absolute differences over the block, >> (bit_depth - 8) once;
+ *   SATD  TComRdCost::xGetHADs tiles a block by 8x8 only if BOTH sides are multiples of 8; otherwise the WHOLE block goes through xCalcHADs4x4:
+ *         the sum over ALL (w/4) (h/4) 4x4 tiles of the PU of (sum |H4 d H4| + 1) >> 1, shifted ONCE by bit_depth - 8.  A 16x12 PU is twelve 4x4
+ *         Hadamards, not one row of 8x8 plus one of 4x4.  Consequence: the three-quarter part of an AMP shape is NOT "the node's SATD minus the
+ *         quarter" -- the node's SATD (fhevc_motion_search) is built from 8x8 Hadamards; the three-quarter part is the sum of the node's sixteen
+ *         4x4 Hadamards minus the quarter's four.  (In SAD mode at 8 bit the two parts of a shape do sum to the node's SAD.)
+ * PU geometry and shape numbers as above (TComDataCU::getPartIndexAndSize).  FHEVC_PUS_SMALL_PER_CTU entries per CTU, each a fhevc_motion_node:
+ *   nodes k = 5..20 (16x16), shapes 2..5:  entry (k - 5) * 8 + (shape - 2) * 2 + part            0..127
+ *   nodes k = 21..84 (8x8),  shapes 0..1:  entry 128 + (k - 21) * 4 + shape * 2 + part           128..383
+ * which is what fhevc_motion_pu_small_index returns (-1 for anything else; it needs no context).  A PU is valid iff its CU NODE lies wholly inside
+ * the picture; otherwise the three distortion fields hold 0xFFFFFFFF and the vector is zero, as for nodes and for the 124 PUs.  Still left out, on
+ * purpose: search ranges above 8, predictors other than zero, quarter-sample refinement of PUs.  The encoder hook does not consume this output. */
+#define FHEVC_PUS_SMALL_PER_CTU 384
+int  fhevc_motion_pu_small_index(int node, int shape, int part);
+/* device-resident batch; layout, band and stream arguments as fhevc_motion_search_pu_device; frame f >= 1 searched in f-1.
+ * d_pus: (num_frames-1) * band CTUs * FHEVC_PUS_SMALL_PER_CTU entries, compact over the band, written over exactly that extent.  Asynchronous with
+ * respect to the host, allocates nothing, keeps no state in HBM between calls (the vector costs travel by value): calls on different streams may
+ * be in flight together.  An empty band writes nothing.  FHEVC_E_INVALID (nothing is launched or written): a null d_luma, d_pus or context,
+ * num_frames < 2, qp outside 0..51, search_range outside 1..8, stride_samples < width, a bad band, uint8 planes on a context above 8 bit. */
+int  fhevc_motion_search_pu_small_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                         int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range,
+                                         fhevc_motion_node* d_pus, void* stream);
+/* one picture pair, host buffers, synchronous */
+int  fhevc_motion_search_pu_small(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                                  fhevc_motion_node* pus);
 
 /* Depth range of every 4x4 unit of a P picture's CTU from its motion nodes and the co-located depths of its reference picture
  * ("inter-CU depth reuse", BASELINE config 4).  Host-side integer arithmetic, no device work.  Per split decision (64->32,
@@ -432,7 +465,8 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
 /* average duration in ms of the dominant kernels over launches since the last reset, measured with HIP
  * events on the launch stream; which: 0 = depth CNN, 1 = source Hadamard, 2 = first pass, 3 = pre-analysis, 4 = motion search,
  * 5 = P-picture depth ranges (fhevc_p_depth_range_device), 6 = first pass of the 4x4 PUs (fhevc_intra_first_pass_4x4*),
- * 7 = quarter-sample motion refinement (fhevc_motion_refine*), 8 = motion search of the rectangular PUs (fhevc_motion_search_pu*) */
+ * 7 = quarter-sample motion refinement (fhevc_motion_refine*), 8 = motion search of the rectangular PUs (fhevc_motion_search_pu*),
+ * 9 = motion search of the PUs with a 4-sample side (fhevc_motion_search_pu_small*) */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
 int  fhevc_enable_kernel_timing(fhevc_ctx* ctx, int on);
 
