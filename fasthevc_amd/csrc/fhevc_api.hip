@@ -267,7 +267,7 @@ void fhevc_destroy(fhevc_ctx* c)
   if (c->lw_done) (void)hipEventDestroy(c->lw_done);
   void* const bufs[] = { c->d_frag, c->d_bias, c->d_whead, c->d_bhead, c->d_frag_i8, c->d_bias_i8,                                  // the base image
                          c->f_frag1, c->f_bias1, c->f_frag2, c->f_frag3, c->f_bias_i8, c->f_whead, c->f_headm, c->f_bhead,          // a fused family member's
-                         c->d_luma, c->d_depth, c->d_had, c->d_nodes, c->d_satd, c->d_satd_out, c->d_act, c->d_depth_max, c->d_pair, c->d_motion, c->d_qpel, c->d_motion_pu, c->d_motion_pu_small,
+                         c->d_luma, c->d_depth, c->d_had, c->d_nodes, c->d_satd, c->d_satd_out, c->d_act, c->d_depth_max, c->d_pair, c->d_motion, c->d_qpel, c->d_motion_pu, c->d_motion_pu_small, c->d_qpel_pu, c->d_qpel_pu_small,
                          c->d_p_maps, c->d_mvtab, c->d_cand_all, c->d_cand, c->d_best4, c->d_modes4 };
   for (void* q : bufs) (void)hipFree(q);
   for (void* q : c->lw_bufs) (void)hipFree(q);
@@ -292,7 +292,7 @@ int fhevc_enable_kernel_timing(fhevc_ctx* c, int on)
 
 int fhevc_kernel_timing(fhevc_ctx* c, int which, int reset, double* avg_ms, uint64_t* launches)
 {
-  if (!c || which < 0 || which > 9) return FHEVC_E_INVALID;
+  if (!c || which < 0 || which > 10) return FHEVC_E_INVALID;
   time_resolve(c);
   if (avg_ms) *avg_ms = c->launches[which] ? c->sum_ms[which] / (double)c->launches[which] : 0.0;
   if (launches) *launches = c->launches[which];
@@ -944,6 +944,56 @@ int fhevc_motion_refine(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* re
   HIP_TRY(c, hipMemcpyAsync(out, c->d_qpel, nbytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->stats.bytes_d2h += (uint64_t)nbytes;
+  return FHEVC_OK;
+}
+
+// ---- quarter-sample refinement of the PUs' vectors (k_motion_refine_pu.hip) ----
+
+int fhevc_motion_refine_pu_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                  int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range,
+                                  const fhevc_motion_node* d_pus, fhevc_motion_qpel_node* d_out_pus,
+                                  const fhevc_motion_node* d_pus_small, fhevc_motion_qpel_node* d_out_pus_small, void* stream)
+{
+  if (!c) return FHEVC_E_INVALID;
+  // either family's pair may be null together, not both pairs and not half a pair
+  if (!d_luma || (!d_pus && !d_pus_small) || !d_pus != !d_out_pus || !d_pus_small != !d_out_pus_small) return fail(c, FHEVC_E_INVALID, "bad PU motion-refinement arguments");
+  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
+  if (max_range < 1 || max_range > FHEVC_MOTION_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "the PU motion refinement covers vectors of the search ranges 1..8");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
+  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
+  return launch_on(c, stream, 10, "fhevc_launch_motion_refine_pu", [&](hipStream_t s) {
+    return fhevc_launch_motion_refine_pu(fr, max_range, mv_bit_cost_table(qp), reinterpret_cast<const FhevcMotionNode*>(d_pus), reinterpret_cast<FhevcMotionQpelNode*>(d_out_pus),
+                                         reinterpret_cast<const FhevcMotionNode*>(d_pus_small), reinterpret_cast<FhevcMotionQpelNode*>(d_out_pus_small), c->num_cus, s);
+  });
+}
+
+int fhevc_motion_refine_pu(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                           const fhevc_motion_node* pus, fhevc_motion_qpel_node* out_pus, const fhevc_motion_node* pus_small, fhevc_motion_qpel_node* out_pus_small)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!cur_luma || !ref_luma || (!pus && !pus_small) || !pus != !out_pus || !pus_small != !out_pus_small || stride_samples < c->cfg.width)
+    return fail(c, FHEVC_E_INVALID, "bad PU motion-refinement arguments");
+  if (qp < 0 || qp > 51 || max_range < 1 || max_range > FHEVC_MOTION_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad PU motion-refinement arguments");
+  (void)hipSetDevice(c->device);
+  // a quarter-sample entry is as large as an entry of the search
+  const size_t pu_bytes = pus ? (size_t)c->num_ctus * FHEVC_PUS * sizeof(FhevcMotionNode) : 0;
+  const size_t small_bytes = pus_small ? (size_t)c->num_ctus * FHEVC_PUS_SMALL * sizeof(FhevcMotionNode) : 0;
+  if (pus) { HIP_TRY(c, ensure(c->d_motion_pu, pu_bytes)); HIP_TRY(c, ensure(c->d_qpel_pu, pu_bytes)); }
+  if (pus_small) { HIP_TRY(c, ensure(c->d_motion_pu_small, small_bytes)); HIP_TRY(c, ensure(c->d_qpel_pu_small, small_bytes)); }
+  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
+  if (rc != FHEVC_OK) return rc;
+  if (pus) HIP_TRY(c, hipMemcpyAsync(c->d_motion_pu, pus, pu_bytes, hipMemcpyHostToDevice, c->stream));
+  if (pus_small) HIP_TRY(c, hipMemcpyAsync(c->d_motion_pu_small, pus_small, small_bytes, hipMemcpyHostToDevice, c->stream));
+  c->stats.bytes_h2d += pu_bytes + small_bytes;
+  rc = fhevc_motion_refine_pu_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, max_range,
+                                     pus ? reinterpret_cast<const fhevc_motion_node*>(c->d_motion_pu) : nullptr, pus ? reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu) : nullptr,
+                                     pus_small ? reinterpret_cast<const fhevc_motion_node*>(c->d_motion_pu_small) : nullptr,
+                                     pus_small ? reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu_small) : nullptr, c->stream);
+  if (rc != FHEVC_OK) return rc;
+  if (pus) HIP_TRY(c, hipMemcpyAsync(out_pus, c->d_qpel_pu, pu_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (pus_small) HIP_TRY(c, hipMemcpyAsync(out_pus_small, c->d_qpel_pu_small, small_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->stats.bytes_d2h += (uint64_t)(pu_bytes + small_bytes);
   return FHEVC_OK;
 }
 

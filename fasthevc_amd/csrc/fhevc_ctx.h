@@ -49,14 +49,16 @@ struct fhevc_ctx {
   bool timing = false;
   std::vector<TimedLaunch> pending;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-  double sum_ms[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-  uint64_t launches[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+  double sum_ms[11] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+  uint64_t launches[11] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
   double* d_act = nullptr;
   int16_t* d_pair = nullptr;          // two staging planes (reference, current) of fhevc_motion_search
   FhevcMotionNode* d_motion = nullptr;
   FhevcMotionQpelNode* d_qpel = nullptr;   // the output of fhevc_motion_refine (host form); its input nodes go through d_motion
   FhevcMotionNode* d_motion_pu = nullptr;  // the output of fhevc_motion_search_pu (host form); its optional nodes go through d_motion
   FhevcMotionNode* d_motion_pu_small = nullptr;  // the output of fhevc_motion_search_pu_small (host form)
+  FhevcMotionQpelNode* d_qpel_pu = nullptr;        // the outputs of fhevc_motion_refine_pu (host form); its input PUs go through d_motion_pu /
+  FhevcMotionQpelNode* d_qpel_pu_small = nullptr;  // d_motion_pu_small
   uint8_t* d_p_maps = nullptr;       // fhevc_p_predict_frame: the reference picture's map, depth_min, depth_max (numCtus * 256 each)
   FhevcNodeCost* d_cand_all = nullptr; uint8_t* d_cand = nullptr;   // fhevc_intra_first_pass_candidates: every (node, mode) cost, the lists
   FhevcNodeCost* d_best4 = nullptr; uint8_t* d_modes4 = nullptr;    // fhevc_intra_first_pass_4x4: the best mode and the list of every 4x4 PU

@@ -192,6 +192,12 @@ struct FhevcMvBitCost { uint32_t c[FHEVC_MV_BIT_COSTS]; };
 hipError_t fhevc_launch_motion_refine(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_nodes, FhevcMotionQpelNode* d_out,
                                       int num_cus, hipStream_t stream);
 
+// ---- ... and of the PUs' vectors (k_motion_refine_pu.hip; config 4) --------------------------------------------------
+// fr, max_range (1 .. FHEVC_MOTION_MAX_RANGE), cost as fhevc_launch_motion_refine; d_pus / d_out_pus: (num_frames - 1) * band CTUs * 124 entries in the order of
+// fhevc_motion_pu_index, d_pus_small / d_out_small: ... * 384 in the order of fhevc_motion_pu_small_index; either pair may be null together
+hipError_t fhevc_launch_motion_refine_pu(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_pus, FhevcMotionQpelNode* d_out_pus,
+                                         const FhevcMotionNode* d_pus_small, FhevcMotionQpelNode* d_out_small, int num_cus, hipStream_t stream);
+
 // the shipped P-picture rule (fhevc_p_rule_default): see fasthevc.h; regenerate with tests/quality/fit_p_rule.py
 #define FHEVC_P_RULE_WEIGHTS { { 3101, 188, -94, 80, 1149, 1149, 3174, -138, 15748, -351620 }, \
                                { 594, 101, 375, -8, 1078, 1078, -197, 436, 3462, 256745 },      \

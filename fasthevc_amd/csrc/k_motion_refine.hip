@@ -23,39 +23,9 @@
 // No scratch, no HBM state between calls: the vector costs travel by value (cost by number of bits, 40 entries).
 #include "fhevc_internal.h"
 #include "k_had8x8.h"
+#include "k_refine_tile.h"
 
 namespace {
-
-template <int MR> struct RefineGeom {
-  static constexpr int RP = 64 + 2 * MR + 8;    // LDS row pitch in samples: the CTU, the range, and 4 samples each side for the taps (x-3 .. x+4 around x-1 .. x)
-  static constexpr int ROWS = 64 + 2 * MR + 8;
-  static constexpr int SAMPLES = ROWS * RP + 8; // a lane's ninth dword of a row may lie behind the window's last sample: never used for its value
-};
-
-// c_f as four packed pairs (low half = the tap of the lower coordinate)
-#define FHEVC_PK(a, b) (((unsigned)(a) & 0xFFFFu) | ((unsigned)(b) << 16))
-__constant__ unsigned kLumaTaps[16] = {
-  FHEVC_PK(0, 0), FHEVC_PK(0, 64), FHEVC_PK(0, 0), FHEVC_PK(0, 0),
-  FHEVC_PK(-1, 4), FHEVC_PK(-10, 58), FHEVC_PK(17, -5), FHEVC_PK(1, 0),
-  FHEVC_PK(-1, 4), FHEVC_PK(-11, 40), FHEVC_PK(40, -11), FHEVC_PK(4, -1),
-  FHEVC_PK(0, 1), FHEVC_PK(-5, 17), FHEVC_PK(58, -10), FHEVC_PK(4, -1) };
-#undef FHEVC_PK
-// s_acMvRefineH, then s_acMvRefineQ (TEncSearch.cpp:51-75): (x, y) as two signed nibbles
-__constant__ signed char kRefineX[18] = { 0, 0, 0, -1, 1, -1, 1, -1, 1,   0, 0, 0, -1, 1, -1, 1, -1, 1 };
-__constant__ signed char kRefineY[18] = { 0, -1, 1, 0, 0, -1, -1, 1, 1,   0, -1, 1, -1, -1, 0, 0, 1, 1 };
-
-__device__ __forceinline__ int dot2(unsigned a, unsigned b, int c)
-{
-  return __builtin_amdgcn_sdot2(__builtin_bit_cast(i16x2, a), __builtin_bit_cast(i16x2, b), c, false);
-}
-__device__ __forceinline__ int eg_bits(int v)  // xGetExpGolombNumberOfBits (TComRdCost.h:177-190)
-{
-  const unsigned u = (v <= 0) ? (((unsigned)(-v)) << 1) + 1u : ((unsigned)v) << 1;
-  return 1 + 2 * (31 - __builtin_clz(u));
-}
-
-template <typename T>
-__device__ __forceinline__ int sample_of(const T* plane, long long off) { return (int)plane[off]; }
 
 // T = int16_t (HM Pel planes) or uint8_t; PACKED = bit depth <= 10 (the packed Hadamard); MR = 8 or 64: the largest integer vector the window is laid out for
 template <typename T, bool PACKED, int MR>
@@ -75,7 +45,7 @@ __global__ __launch_bounds__(256) void fhevc_motion_refine_kernel(FhevcFrames F,
   const int total = per_frame * (F.num_frames - 1);  // frame f >= 1 is refined in frame f - 1
   const int bd = F.bit_depth;
   const int shift = bd - 8;
-  const int v_off = (1 << (19 - bd)) + (8192 << 6), v_shift = 20 - bd, top = (1 << bd) - 1;
+  const RefineArith arith(bd);
   const T* plane = reinterpret_cast<const T*>(F.luma);
   if (tid < FHEVC_MV_BIT_COSTS) s_cost[tid] = cost.c[tid];
   if (tid < 16) s_taps[tid] = kLumaTaps[tid];
@@ -93,48 +63,12 @@ __global__ __launch_bounds__(256) void fhevc_motion_refine_kernel(FhevcFrames F,
     const long long oc = (long long)((f - 1) * band_rows + (cy - F.row_begin)) * F.ctus_x + cx;
     // ---- stage the reference window: rows cy*64 - MR - 4 .., columns cx*64 - MR - 4 .., coordinates clamped to the picture ----
     __syncthreads();  // the previous CTU's readers are done
-    {
-      // chunks of 4 samples: the window's first column is a multiple of 4, so a chunk inside the picture is ONE 8-byte (uint8 planes: 4-byte) load
-      // where the plane allows it, and one 8-byte LDS store
-      constexpr int CH = RP / 4;
-      for (int it = tid; it < RefineGeom<MR>::ROWS * CH; it += 256) {
-        const int wr = it / CH, wc = (it - wr * CH) * 4;
-        const int py = min(max(cy * 64 - MR - 4 + wr, 0), F.height - 1);
-        const int px0 = cx * 64 - MR - 4 + wc;
-        const long long row = ref_base + (long long)py * F.stride;
-        const T* src = plane + row + px0;
-        uint2 q;
-        if (px0 >= 0 && px0 + 4 <= F.width && (reinterpret_cast<uintptr_t>(src) & (4 * sizeof(T) - 1)) == 0) {
-          if (sizeof(T) == 2) q = *reinterpret_cast<const uint2*>(src);
-          else {
-            const unsigned b = *reinterpret_cast<const unsigned*>(src);
-            q.x = (b & 0xFFu) | ((b & 0xFF00u) << 8); q.y = ((b >> 16) & 0xFFu) | ((b >> 24) << 16);
-          }
-        } else {
-          int v[4];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) v[k] = sample_of(plane, row + min(max(px0 + k, 0), F.width - 1));
-          q.x = ((unsigned)v[0] & 0xFFFFu) | ((unsigned)v[1] << 16); q.y = ((unsigned)v[2] & 0xFFFFu) | ((unsigned)v[3] << 16);
-        }
-        *reinterpret_cast<uint2*>(s_ref + wr * RP + wc) = q;
-      }
-    }
+    refine_stage_window<T, MR>(s_ref, plane, ref_base, F, cx, cy, tid);
     // ---- this lane's original 8x8 tile (all four waves hold the same 64 tiles) ----
     const int px = cx * 64 + tx * 8, py = cy * 64 + ty * 8;
     const bool inside = (px + 8 <= F.width) && (py + 8 <= F.height);
     unsigned O[32];
-    if (inside) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const long long row = cur_base + (long long)(py + j) * F.stride + px;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          O[4 * j + k] = ((unsigned)sample_of(plane, row + 2 * k) & 0xFFFFu) | ((unsigned)sample_of(plane, row + 2 * k + 1) << 16);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 32; ++i) O[i] = 0;
-    }
+    refine_load_tile(plane, cur_base, F, px, py, inside, O);
     // ---- its node's integer vector: only mvx / mvy of the input are read, validity comes from the geometry and from max_range ----
     const bool node_in = cx * 64 + nbx * nsize + nsize <= F.width && cy * 64 + nby * nsize + nsize <= F.height;
     int mx = 0, my = 0;
@@ -157,95 +91,12 @@ __global__ __launch_bounds__(256) void fhevc_motion_refine_kernel(FhevcFrames F,
       const int qx = base_x + step * (int)kRefineX[i], qy = base_y + step * (int)kRefineY[i];
       const int fx = qx & 3, fy = qy & 3;
       const int col = tx * 8 + MR + 4 + (qx >> 2) - 3, row0 = ty * 8 + MR + 4 + (qy >> 2) - 3;  // first tap of sample (0, 0)
-      const unsigned sh = (unsigned)(col & 1) * 16u;
-      const bool hor = __builtin_amdgcn_ballot_w64(fx != 0) != 0, ver = __builtin_amdgcn_ballot_w64(fy != 0) != 0;  // wave-uniform
-      unsigned cxp[4], cyp[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { cxp[j] = s_taps[4 * fx + j]; cyp[j] = s_taps[4 * fy + j]; }
-      // ---- horizontal: rows row0 .. + 14, 8 intermediates each, kept as pairs of rows: Pe[r / 2][x] = (t[r][x], t[r + 1][x]) ----
-      unsigned Pe[8][8];
-      if (ver) {
-#pragma unroll
-        for (int r = 0; r < 15; ++r) {
-          const unsigned* q = reinterpret_cast<const unsigned*>(s_ref) + (((row0 + r) * RP + col) >> 1);
-          int t[8];
-          if (hor) {
-            unsigned d[9], N[8], M[7];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) d[k] = q[k];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) N[k] = __builtin_amdgcn_alignbit(d[k + 1], d[k], sh);    // pairs starting at col, col + 2, ..
-#pragma unroll
-            for (int k = 0; k < 7; ++k) M[k] = __builtin_amdgcn_alignbit(N[k + 1], N[k], 16u);   // pairs starting at col + 1, col + 3, ..
-#pragma unroll
-            for (int x = 0; x < 8; ++x) {
-              int a = 0;
-#pragma unroll
-              for (int j = 0; j < 4; ++j) a = dot2((x & 1) ? M[(x >> 1) + j] : N[(x >> 1) + j], cxp[j], a);
-              t[x] = (a >> shift) - 8192;
-            }
-          } else {  // fx = 0 in every lane: (64 s >> (bd - 8)) - 8192 of samples col + 3 .. col + 10
-            unsigned d[7], N[6];
-#pragma unroll
-            for (int k = 1; k < 7; ++k) d[k] = q[k];
-#pragma unroll
-            for (int k = 1; k < 6; ++k) N[k] = __builtin_amdgcn_alignbit(d[k + 1], d[k], sh);     // pairs starting at col + 2 k
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              const unsigned pr = __builtin_amdgcn_alignbit(N[k + 2], N[k + 1], 16u);              // samples col + 3 + 2 k, + 1
-              t[2 * k] = (int)((pr & 0xFFFFu) << (14 - bd)) - 8192; t[2 * k + 1] = (int)((pr >> 16) << (14 - bd)) - 8192;
-            }
-          }
-#pragma unroll
-          for (int x = 0; x < 8; ++x) {
-            if (r & 1) Pe[r >> 1][x] = (Pe[r >> 1][x] & 0xFFFFu) | ((unsigned)t[x] << 16);
-            else Pe[r >> 1][x] = (unsigned)t[x] & 0xFFFFu;
-          }
-        }
-      }
-      // ---- vertical, difference to the original, Hadamard ----
+      // ---- the tile's prediction at the candidate, its difference to the original (k_refine_tile.h), Hadamard ----
       unsigned t8;
       {
         unsigned D[32];
         int v[64];
-#pragma unroll
-        for (int y = 0; y < 8; ++y) {
-          int p[8];
-          if (ver) {
-#pragma unroll
-            for (int x = 0; x < 8; ++x) {
-              int a = v_off;
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                const int m = (y >> 1) + j;
-                a = dot2((y & 1) ? __builtin_amdgcn_alignbit(Pe[m + 1][x], Pe[m][x], 16u) : Pe[m][x], cyp[j], a);
-              }
-              p[x] = min(max(a >> v_shift, 0), top);
-            }
-          } else {  // fy = 0 in every lane: row row0 + 3 + y, filtered horizontally to the final sample
-            const unsigned* q = reinterpret_cast<const unsigned*>(s_ref) + (((row0 + 3 + y) * RP + col) >> 1);
-            unsigned d[9], N[8], M[7];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) d[k] = q[k];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) N[k] = __builtin_amdgcn_alignbit(d[k + 1], d[k], sh);
-#pragma unroll
-            for (int k = 0; k < 7; ++k) M[k] = __builtin_amdgcn_alignbit(N[k + 1], N[k], 16u);
-#pragma unroll
-            for (int x = 0; x < 8; ++x) {
-              int a = 32;
-#pragma unroll
-              for (int j = 0; j < 4; ++j) a = dot2((x & 1) ? M[(x >> 1) + j] : N[(x >> 1) + j], cxp[j], a);
-              p[x] = min(max(a >> 6, 0), top);
-            }
-          }
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const unsigned o = O[4 * y + k];
-            if constexpr (PACKED) D[4 * y + k] = pk_sub(o, ((unsigned)p[2 * k] & 0xFFFFu) | ((unsigned)p[2 * k + 1] << 16));
-            else { v[8 * y + 2 * k] = (int)(o & 0xFFFFu) - p[2 * k]; v[8 * y + 2 * k + 1] = (int)(o >> 16) - p[2 * k + 1]; }
-          }
-        }
+        refine_tile_diff<PACKED, RP>(s_ref, s_taps, arith, col, row0, fx, fy, O, D, v);
         if constexpr (PACKED) t8 = had8x8_packed(D);
         else t8 = had8x8_wide(v);
       }

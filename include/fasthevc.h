@@ -370,7 +370,7 @@ int  fhevc_motion_search_pu(fhevc_ctx* ctx, const int16_t* cur_luma, const int16
  *   nodes k = 21..84 (8x8),  shapes 0..1:  entry 128 + (k - 21) * 4 + shape * 2 + part           128..383
  * which is what fhevc_motion_pu_small_index returns (-1 for anything else; it needs no context).  A PU is valid iff its CU NODE lies wholly inside
  * the picture; otherwise the three distortion fields hold 0xFFFFFFFF and the vector is zero, as for nodes and for the 124 PUs.  Still left out, on
- * purpose: search ranges above 8, predictors other than zero, quarter-sample refinement of PUs.  The encoder hook does not consume this output. */
+ * purpose: search ranges above 8, predictors other than zero.  The encoder hook does not consume this output. */
 #define FHEVC_PUS_SMALL_PER_CTU 384
 int  fhevc_motion_pu_small_index(int node, int shape, int part);
 /* device-resident batch; layout, band and stream arguments as fhevc_motion_search_pu_device; frame f >= 1 searched in f-1.
@@ -384,6 +384,39 @@ int  fhevc_motion_search_pu_small_device(fhevc_ctx* ctx, const void* d_luma, int
 /* one picture pair, host buffers, synchronous */
 int  fhevc_motion_search_pu_small(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
                                   fhevc_motion_node* pus);
+
+/* Quarter-sample refinement of the PUs' vectors (k_motion_refine_pu.hip): HM never compares partition shapes at integer positions -- every
+ * xMotionEstimation runs TEncSearch::xPatternSearchFracDIF behind the integer search, for every PU, 8x4 and 4x8 included, and xCheckRDCostInter sees each
+ * PU's Hadamard cost at its quarter-sample vector.  This is the definition of fhevc_motion_refine per PU instead of per node, for all 508 PUs of a CTU:
+ * around the PU's integer vector (mvx, mvy) the nine half-sample candidates of s_acMvRefineH (centre first), then the nine quarter-sample candidates
+ * of s_acMvRefineQ (in ITS order) around the half stage's winner, strict "<" in both; prediction by HEVC's 8-tap luma interpolation of the PREVIOUS
+ * ORIGINAL picture with coordinates clamped to the picture (14-bit intermediates when both fractions are non-zero); vector cost
+ * getCostOfVectorWithPredictor of the candidate in quarter units (zero predictor, lambda of slice QP qp).  Distortion: ALWAYS TComRdCost::xGetHADs on the
+ * whole w x h PU, whatever fhevc_set_motion_distortion says, through the branch xGetHADs itself takes:
+ *   both sides multiples of 8 (all 124 PUs of fhevc_motion_pu_index):  the sum over the PU's 8x8 tiles of (sum |H8 d H8| + 2) >> 2;
+ *   otherwise (all 384 PUs of fhevc_motion_pu_small_index, the 16x12 and 12x16 parts included):  the sum over ALL (w/4) (h/4) 4x4 tiles of
+ *   (sum |H4 d H4| + 1) >> 1 -- a 16x12 part is twelve 4x4 Hadamards, not the node minus the quarter;
+ * in both cases the PU's sum is shifted ONCE by bit_depth - 8.  PU geometry and entry order are exactly those of fhevc_motion_pu_index (pus, out_pus:
+ * FHEVC_PUS_PER_CTU entries per CTU) and fhevc_motion_pu_small_index (pus_small, out_pus_small: FHEVC_PUS_SMALL_PER_CTU).  Input entries are what the
+ * two PU searches wrote for the same pictures and band, in either distortion mode; only mvx and mvy are read.  A PU is valid iff its CU node lies
+ * wholly inside the picture and |mvx|, |mvy| <= max_range (1..8: no PU search writes longer vectors, so the 15.5 KB window serves); an invalid PU gets
+ * 0xFFFFFFFF in the three distortion fields and a zero vector, so no content of the input can send a read outside the staged window.  Output entries
+ * are fhevc_motion_qpel_node.  Either family's in / out pair may be NULL together: that family's work is then not done at all.
+ * One picture pair, host buffers (both planes with the same stride), synchronous: */
+int  fhevc_motion_refine_pu(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                            const fhevc_motion_node* pus, fhevc_motion_qpel_node* out_pus,
+                            const fhevc_motion_node* pus_small, fhevc_motion_qpel_node* out_pus_small);
+/* device-resident batch: layout, band and stream arguments as fhevc_motion_refine_device and fhevc_motion_search_pu_device; frame f = 1 .. num_frames-1
+ * is refined in frame f-1; d_pus, d_out_pus: (num_frames - 1) * band CTUs * 124 entries, d_pus_small, d_out_pus_small: ... * 384, compact over the band;
+ * the outputs are written over exactly that extent, an empty band writes nothing.  Asynchronous with respect to the host, allocates nothing, keeps no
+ * state in HBM between calls (the vector costs travel by value): calls on different streams may be in flight together, and a PU search and its
+ * refinement may follow each other on one stream without a host synchronisation.  FHEVC_E_INVALID (nothing is launched or written): a null context or
+ * d_luma, both pairs null, a pair with exactly one null member, num_frames < 2, qp outside 0..51, max_range outside 1..8, stride_samples < width, a bad
+ * band, uint8 planes on a context above 8 bit. */
+int  fhevc_motion_refine_pu_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                   int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range,
+                                   const fhevc_motion_node* d_pus, fhevc_motion_qpel_node* d_out_pus,
+                                   const fhevc_motion_node* d_pus_small, fhevc_motion_qpel_node* d_out_pus_small, void* stream);
 
 /* Depth range of every 4x4 unit of a P picture's CTU from its motion nodes and the co-located depths of its reference picture
  * ("inter-CU depth reuse", BASELINE config 4).  Host-side integer arithmetic, no device work.  Per split decision (64->32,
@@ -466,7 +499,8 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
  * events on the launch stream; which: 0 = depth CNN, 1 = source Hadamard, 2 = first pass, 3 = pre-analysis, 4 = motion search,
  * 5 = P-picture depth ranges (fhevc_p_depth_range_device), 6 = first pass of the 4x4 PUs (fhevc_intra_first_pass_4x4*),
  * 7 = quarter-sample motion refinement (fhevc_motion_refine*), 8 = motion search of the rectangular PUs (fhevc_motion_search_pu*),
- * 9 = motion search of the PUs with a 4-sample side (fhevc_motion_search_pu_small*) */
+ * 9 = motion search of the PUs with a 4-sample side (fhevc_motion_search_pu_small*), 10 = quarter-sample refinement of the PUs
+ * (fhevc_motion_refine_pu*) */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
 int  fhevc_enable_kernel_timing(fhevc_ctx* ctx, int on);
 
