@@ -7,9 +7,8 @@
 // of 8 into 8x8 Hadamards and SAD is additive, so the per-vector 8x8 tile distortions of k_motion.hip give every such rectangle exactly: the
 // sum of its tiles, shifted ONCE by bit_depth - 8.
 //
-// Mapping as fhevc_motion_kernel at MR = 8: workgroup (4 waves) = one CTU at a time, grid-stride; lane = one 8x8 tile (lane = ty * 8 + tx) with
-// its original samples packed in registers; the reference window staged once per CTU in LDS; the waves split the vectors and are merged by
-// (cost, raster index).  New is the reduction.  The butterfly to 16x16 / 32x32 / 64x64 already passes through the symmetric halves:
+// Mapping: k_search_tile.h, at MR = 8 (lane = ty * 8 + tx).  Own to this kernel is the reduction.  The butterfly to 16x16 / 32x32 / 64x64 already
+// passes through the symmetric halves:
 //   t8 + xor 1 = 16x8     t8 + xor 8 = 8x16     s16 + xor 2 = 32x16     s16 + xor 16 = 16x32     s32 + xor 4 = 64x32     s32 + xor 32 = 32x64
 // the AMP quarter strips are one more step on those (16x8 + xor 2 = 32x8, 8x16 + xor 16 = 8x32, 32x16 + xor 4 = 64x16, 16x32 + xor 32 = 16x64),
 // fetched from the node's first / last strip by a lane broadcast (32x32 nodes: ds_swizzle; the 64x64 node: v_readlane), and the three-quarter
@@ -17,19 +16,14 @@
 // of its 14 shapes, next to the four squares; the distortion at the best vector is cost - vector cost, so it has no register of its own.
 // When d_nodes is given the 85 square nodes are written too, byte for byte what fhevc_motion_kernel writes.
 #include "fhevc_internal.h"
-#include "k_had8x8.h"
+#include "k_search_tile.h"
 
 namespace {
 
-constexpr int MR = FHEVC_MOTION_MAX_RANGE;
-constexpr int RP = 64 + 2 * MR + 8;            // LDS row pitch of the reference window in samples (multiple of 8: 16-byte row starts)
-constexpr int REF_SAMPLES = (64 + 2 * MR) * RP + 8;
-constexpr int NMV_MAX = (2 * MR + 1) * (2 * MR + 1);
+using Geom = SearchGeom<FHEVC_MOTION_MAX_RANGE>;
+constexpr int RP = Geom::RP;
 constexpr int SLOTS = 18;                      // per lane: 4 squares, 6 shapes of the 64x64 node, 6 of its 32x32 node, 2 of its 16x16 node
 constexpr int ENTRIES = FHEVC_NODES + FHEVC_PUS;  // per CTU in the merge arrays: the nodes, then the PUs in output order
-
-template <typename T>
-__device__ __forceinline__ int sample_at(const T* plane, long long off) { return (int)plane[off]; }
 
 // lane j = ((i & AND) | OR) ^ XOR inside each half of the wave (ds_swizzle, bit-mask mode): no address register, no LDS traffic
 template <int AND, int OR, int XOR>
@@ -65,125 +59,35 @@ template <typename T, bool PACKED, bool SAD>
 __global__ __launch_bounds__(256, (PACKED ? 3 : 2)) void fhevc_motion_pu_kernel(FhevcFrames F, int range, FhevcMvCost mvc, FhevcMotionNode* __restrict__ out_nodes,
                                                              FhevcMotionNode* __restrict__ out_pus)
 {
-  __shared__ __attribute__((aligned(16))) short s_ref[REF_SAMPLES];
-  __shared__ unsigned s_cost[4][ENTRIES], s_idx[4][ENTRIES], s_zero[ENTRIES], s_vc[NMV_MAX];
+  __shared__ __attribute__((aligned(16))) short s_ref[Geom::REF_SAMPLES];
+  __shared__ unsigned s_cost[4][ENTRIES], s_idx[4][ENTRIES], s_zero[ENTRIES], s_vc[Geom::NMV_MAX];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int tx = lane & 7, ty = lane >> 3;
-  const int band_rows = F.row_end - F.row_begin;
-  const int per_frame = band_rows * F.ctus_x;
-  const int total = per_frame * (F.num_frames - 1);  // frame f >= 1 is searched in frame f - 1
-  const int side = 2 * range + 1, nmv = side * side, centre = (nmv - 1) >> 1;
-  const int win = 64 + 2 * range;
+  const SearchRange R(range);
+  const int total = SearchWork::total(F), nmv = R.nmv, centre = R.centre;
   const int shift = F.bit_depth - 8;
-  const int delta = (8 - (range & 7)) & 7;  // the window starts at column 64 cx - range: delta samples after a multiple of 8
   const bool want_nodes = out_nodes != nullptr;
   const T* plane = reinterpret_cast<const T*>(F.luma);
 
   for (int work = blockIdx.x; work < total; work += gridDim.x) {
-    const int f = 1 + work / per_frame;
-    const int rem = work % per_frame;
-    const int cy = F.row_begin + rem / F.ctus_x, cx = rem % F.ctus_x;
-    const long long cur_base = (long long)f * F.frame_stride, ref_base = (long long)(f - 1) * F.frame_stride;
-    // ---- stage the reference window (the staging loop of fhevc_motion_kernel): rows cy*64 - R .. + win, columns cx*64 - R .. + win, clamped ----
+    const SearchWork W(F, work);
+    const int cx = W.cx, cy = W.cy;
     __syncthreads();  // the previous CTU's readers are done
-    {
-      const int chunks = (win + delta + 7) >> 3;
-      for (int it = tid; it < win * chunks; it += 256) {
-        const int wr = it / chunks, wc = (it - wr * chunks) * 8;
-        const int py = min(max(cy * 64 - range + wr, 0), F.height - 1);
-        const int px0 = cx * 64 - range - delta + wc;
-        short v[8];
-        const long long row = ref_base + (long long)py * F.stride;
-        const T* src = plane + row + px0;
-        if (px0 >= 0 && px0 + 8 <= F.width && (reinterpret_cast<uintptr_t>(src) & (8 * sizeof(T) - 1)) == 0) {
-          if (sizeof(T) == 2) {
-            const uint4 q = *reinterpret_cast<const uint4*>(src);
-            *reinterpret_cast<uint4*>(s_ref + wr * RP + wc) = q;
-            continue;
-          } else {
-            const uint2 q = *reinterpret_cast<const uint2*>(src);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { v[k] = (short)((q.x >> (8 * k)) & 0xFF); v[4 + k] = (short)((q.y >> (8 * k)) & 0xFF); }
-          }
-        } else if (px0 >= 0 && px0 + 8 <= F.width) {
-#pragma unroll
-          for (int k = 0; k < 8; ++k) v[k] = (short)sample_at(plane, row + px0 + k);
-        } else {
-#pragma unroll
-          for (int k = 0; k < 8; ++k) v[k] = (short)sample_at(plane, row + min(max(px0 + k, 0), F.width - 1));
-        }
-        short* dst = s_ref + wr * RP + wc;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) dst[k] = v[k];
-      }
-    }
+    search_stage_window<T, RP>(s_ref, plane, W.ref_base, F, cx, cy, R, tid);
     // ---- this lane's original 8x8 tile (all four waves hold the same 64 tiles) ----
     const int px = cx * 64 + tx * 8, py = cy * 64 + ty * 8;
     const bool inside = (px + 8 <= F.width) && (py + 8 <= F.height);
     unsigned O[32];
-    if (inside) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const long long row = cur_base + (long long)(py + j) * F.stride + px;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          O[4 * j + k] = ((unsigned)sample_at(plane, row + 2 * k) & 0xFFFFu) | ((unsigned)sample_at(plane, row + 2 * k + 1) << 16);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 32; ++i) O[i] = 0;
-    }
+    load_tile8x8(plane, W.cur_base, F, px, py, inside, O);
     __syncthreads();
 
     unsigned bc[SLOTS], bi[SLOTS];
 #pragma unroll
     for (int k = 0; k < SLOTS; ++k) { bc[k] = 0xFFFFFFFFu; bi[k] = 0; }
     for (int m = wave; m < nmv; m += 4) {  // raster order inside a wave; the waves interleave and are merged by (cost, index)
-      const int dy = m / side - range, dx = m % side - range;
-      const int col = tx * 8 + range + dx + delta, row0 = ty * 8 + range + dy;
-      const unsigned sh = (unsigned)(col & 1) * 16u;  // uniform: R + dx
-      unsigned t8;
-      if (PACKED && SAD) {  // sum |org - ref| on pairs of unsigned 16-bit samples: v_sad_u16
-        t8 = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const unsigned* q = reinterpret_cast<const unsigned*>(s_ref) + (((row0 + j) * RP + col) >> 1);
-          const unsigned d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3], d4 = q[4];
-          t8 = __builtin_amdgcn_sad_u16(O[4 * j + 0], __builtin_amdgcn_alignbit(d1, d0, sh), t8);
-          t8 = __builtin_amdgcn_sad_u16(O[4 * j + 1], __builtin_amdgcn_alignbit(d2, d1, sh), t8);
-          t8 = __builtin_amdgcn_sad_u16(O[4 * j + 2], __builtin_amdgcn_alignbit(d3, d2, sh), t8);
-          t8 = __builtin_amdgcn_sad_u16(O[4 * j + 3], __builtin_amdgcn_alignbit(d4, d3, sh), t8);
-        }
-      } else if (PACKED) {
-        unsigned D[32];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const unsigned* q = reinterpret_cast<const unsigned*>(s_ref) + (((row0 + j) * RP + col) >> 1);
-          const unsigned d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3], d4 = q[4];
-          D[4 * j + 0] = pk_sub(O[4 * j + 0], __builtin_amdgcn_alignbit(d1, d0, sh));
-          D[4 * j + 1] = pk_sub(O[4 * j + 1], __builtin_amdgcn_alignbit(d2, d1, sh));
-          D[4 * j + 2] = pk_sub(O[4 * j + 2], __builtin_amdgcn_alignbit(d3, d2, sh));
-          D[4 * j + 3] = pk_sub(O[4 * j + 3], __builtin_amdgcn_alignbit(d4, d3, sh));
-        }
-        t8 = had8x8_packed(D);
-      } else {
-        int v[64];
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-#pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            const unsigned o = O[4 * j + (k >> 1)];
-            const int os = (k & 1) ? (int)(short)(o >> 16) : (int)(short)(o & 0xFFFFu);
-            v[8 * j + k] = os - (int)s_ref[(row0 + j) * RP + col + k];
-          }
-        if (SAD) {
-          t8 = 0;
-#pragma unroll
-          for (int i = 0; i < 64; ++i) t8 += (unsigned)abs(v[i]);
-        } else t8 = had8x8_wide(v);
-      }
-      if (SAD) t8 = inside ? t8 : 0u;
-      else t8 = inside ? ((t8 + 2) >> 2) : 0u;  // xCalcHADs8x8: (sum + 2) >> 2 (TComRdCost.cpp:1747)
+      int col, row0;
+      R.at(m, tx, ty, col, row0);
+      const unsigned t8 = search_tile8x8<PACKED, SAD, RP>(s_ref, row0, col, O, inside);
 
       // ---- the sums of every square and rectangle that holds this lane's tile (tx = lane bits 0..2, ty = bits 3..5) ----
       unsigned d[SLOTS];
@@ -244,25 +148,15 @@ __global__ __launch_bounds__(256, (PACKED ? 3 : 2)) void fhevc_motion_pu_kernel(
       const int p = tid - FHEVC_NODES;
       const int node = p < 0 ? tid : p < 60 ? p / 12 : 5 + (p - 60) / 4;
       int l, ni;
-      if (node == 0) { l = 0; ni = 0; } else if (node < 5) { l = 1; ni = node - 1; } else if (node < 21) { l = 2; ni = node - 5; } else { l = 3; ni = node - 21; }
+      search_node_level(node, l, ni);
       const int n = 64 >> l, cnt = 1 << l;
-      const int bx = ni % cnt, by = ni / cnt;
-      uint4 o;
-      if (cx * 64 + bx * n + n > F.width || cy * 64 + by * n + n > F.height) {
-        o.x = o.y = o.z = 0xFFFFFFFFu; o.w = 0;
-      } else {
-        unsigned c = s_cost[0][tid], ix = s_idx[0][tid];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) {
-          const unsigned c2 = s_cost[w][tid], i2 = s_idx[w][tid];
-          if (c2 < c || (c2 == c && i2 < ix)) { c = c2; ix = i2; }
-        }
-        const int mvx = (int)(ix % side) - range, mvy = (int)(ix / side) - range;
-        o.x = s_zero[tid]; o.y = c - s_vc[ix]; o.z = c;
-        o.w = ((unsigned)mvx & 0xFFFFu) | ((unsigned)mvy << 16);
+      uint4 o = search_record_outside();
+      if (search_node_inside(F, cx, cy, ni % cnt, ni / cnt, n)) {
+        unsigned c, ix;
+        search_merge(&s_cost[0][0], &s_idx[0][0], ENTRIES, tid, c, ix);
+        o = search_record(s_zero[tid], c, s_vc[ix], ix, R);
       }
-      const long long oc = (long long)((f - 1) * band_rows + (cy - F.row_begin)) * F.ctus_x + cx;
-      FhevcMotionNode* dst = p < 0 ? out_nodes + oc * FHEVC_NODES + tid : out_pus + oc * FHEVC_PUS + p;
+      FhevcMotionNode* dst = p < 0 ? out_nodes + W.oc(F) * FHEVC_NODES + tid : out_pus + W.oc(F) * FHEVC_PUS + p;
       *reinterpret_cast<uint4*>(dst) = o;  // one 16-byte store per entry
     }
   }
@@ -276,16 +170,8 @@ __global__ __launch_bounds__(256, (PACKED ? 3 : 2)) void fhevc_motion_pu_kernel(
 hipError_t fhevc_launch_motion_pu(const FhevcFrames& fr, int range, const FhevcMvCost& mvc, FhevcMotionNode* d_nodes, FhevcMotionNode* d_pus, int num_cus, bool sad,
                                   hipStream_t stream)
 {
-  const long long total = (long long)(fr.row_end - fr.row_begin) * fr.ctus_x * (fr.num_frames - 1);
-  if (total <= 0) return hipSuccess;
-  if (range < 1 || range > FHEVC_MOTION_MAX_RANGE || !d_pus) return hipErrorInvalidValue;
-  const long long resident = (fr.sample_bytes == 2 && fr.bit_depth > 10 ? 2LL : 3LL) * num_cus;
-  const int grid = (int)(total < resident ? total : resident);
-#define FHEVC_MOTION_PU(T, P) do { if (sad) hipLaunchKernelGGL((fhevc_motion_pu_kernel<T, P, true>), dim3(grid), dim3(256), 0, stream, fr, range, mvc, d_nodes, d_pus); \
-                                   else hipLaunchKernelGGL((fhevc_motion_pu_kernel<T, P, false>), dim3(grid), dim3(256), 0, stream, fr, range, mvc, d_nodes, d_pus); } while (0)
-  if (fr.sample_bytes == 2 && fr.bit_depth <= 10) FHEVC_MOTION_PU(int16_t, true);
-  else if (fr.sample_bytes == 2) FHEVC_MOTION_PU(int16_t, false);
-  else FHEVC_MOTION_PU(uint8_t, true);
-#undef FHEVC_MOTION_PU
-  return hipGetLastError();
+  return search_launch(fr, range >= 1 && range <= FHEVC_MOTION_MAX_RANGE && d_pus, num_cus, 3, 2, sad, [&](auto t, auto packed, auto sad_c, int grid) {
+    hipLaunchKernelGGL((fhevc_motion_pu_kernel<decltype(t), decltype(packed)::value, decltype(sad_c)::value>), dim3(grid), dim3(256), 0, stream, fr, range, mvc, d_nodes, d_pus);
+    return hipSuccess;
+  });
 }

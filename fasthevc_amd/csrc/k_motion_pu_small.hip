@@ -8,9 +8,8 @@
 // these PUs are not sums of the 8x8 tile distortions of the other two kernels: a 16x12 PU is twelve 4x4 Hadamards, each with its own
 // (sum + 1) >> 1, and the block's sum is shifted ONCE by bit_depth - 8.  SAD is additive and shifted once as well.
 //
-// Mapping as fhevc_motion_kernel at MR = 8: workgroup (4 waves) = one CTU at a time, grid-stride; lane = one 8x8 tile with its original samples
-// packed in registers; the reference window staged once per CTU in LDS; the waves split the vectors and are merged by (cost, raster index).
-// New: per tile and vector the lane computes the four QUADRANT distortions q00 q01 / q10 q11 (4x4 SAD or 4x4 Hadamard), and the lanes are
+// Mapping: k_search_tile.h, at MR = 8.  Own to this kernel: per tile and vector the lane computes the four QUADRANT distortions q00 q01 / q10 q11
+// (4x4 SAD or 4x4 Hadamard) on that header's displaced rows and packed differences, and the lanes are
 // numbered so that the four tiles of a 16x16 node sit on one lane quad (lane = node * 4 + ty1 * 2 + tx1), which makes the node's reduction three
 // DPP quad permutes and no LDS:
 //   the tile's own PUs      8x4 top = q00 + q01    8x4 bottom = q10 + q11    4x8 left = q00 + q10    4x8 right = q01 + q11
@@ -20,20 +19,15 @@
 //   p = 2: nLx2N (left strip, + lane 0's left)    p = 3: 2NxnD (bottom strip, + lane 2's bottom)
 // so every lane keeps six running (cost, vector index) pairs, all of entries it alone owns; the distortion at the best vector is cost - vector cost.
 #include "fhevc_internal.h"
-#include "k_had8x8.h"
+#include "k_search_tile.h"
 
 namespace {
 
-constexpr int MR = FHEVC_MOTION_MAX_RANGE;
-constexpr int RP = 64 + 2 * MR + 8;            // LDS row pitch of the reference window in samples (multiple of 8: 16-byte row starts)
-constexpr int REF_SAMPLES = (64 + 2 * MR) * RP + 8;
-constexpr int NMV_MAX = (2 * MR + 1) * (2 * MR + 1);
+using Geom = SearchGeom<FHEVC_MOTION_MAX_RANGE>;
+constexpr int RP = Geom::RP;
 constexpr int SLOTS = 6;                       // per lane: 8x4 top, 8x4 bottom, 4x8 left, 4x8 right of its tile; part 0 and part 1 of its AMP shape
 constexpr int ENTRIES = FHEVC_PUS_SMALL;
 constexpr int AMP_ENTRIES = 128;               // 16 nodes x 4 shapes x 2 parts, then 64 tiles x 2 shapes x 2 parts
-
-template <typename T>
-__device__ __forceinline__ int sample_at(const T* plane, long long off) { return (int)plane[off]; }
 
 // lane (i & ~3) | P_(i & 3) of the same quad (DPP quad_perm: a VALU operand modifier, no LDS); every lane of the wave is active where this is used
 template <int P0, int P1, int P2, int P3>
@@ -46,8 +40,8 @@ __device__ __forceinline__ unsigned quad(unsigned v)
 template <typename T, bool PACKED, bool SAD>
 __global__ __launch_bounds__(256, (PACKED ? 4 : 3)) void fhevc_motion_pu_small_kernel(FhevcFrames F, int range, FhevcMvCost mvc, FhevcMotionNode* __restrict__ out_pus)
 {
-  __shared__ __attribute__((aligned(16))) short s_ref[REF_SAMPLES];
-  __shared__ unsigned s_cost[4][ENTRIES], s_idx[4][ENTRIES], s_zero[ENTRIES], s_vc[NMV_MAX];
+  __shared__ __attribute__((aligned(16))) short s_ref[Geom::REF_SAMPLES];
+  __shared__ unsigned s_cost[4][ENTRIES], s_idx[4][ENTRIES], s_zero[ENTRIES], s_vc[Geom::NMV_MAX];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int quad_pos = lane & 3, node16 = lane >> 2;  // the tile's place in its 16x16 node (bit 0: right, bit 1: lower), the node (raster 4x4)
   const int tx = (node16 & 3) * 2 + (quad_pos & 1), ty = (node16 >> 2) * 2 + (quad_pos >> 1);
@@ -55,118 +49,52 @@ __global__ __launch_bounds__(256, (PACKED ? 4 : 3)) void fhevc_motion_pu_small_k
   const int amp_shape = quad_pos == 0 ? 0 : quad_pos == 1 ? 3 : quad_pos == 2 ? 2 : 1;
   const int e_tile = AMP_ENTRIES + (ty * 8 + tx) * 4, e_amp = node16 * 8 + amp_shape * 2;
   const bool strip_is_part0 = (quad_pos & 1) == 0;  // 2NxnU and nLx2N: the quarter strip comes first
-  const int band_rows = F.row_end - F.row_begin;
-  const int per_frame = band_rows * F.ctus_x;
-  const int total = per_frame * (F.num_frames - 1);  // frame f >= 1 is searched in frame f - 1
-  const int side = 2 * range + 1, nmv = side * side, centre = (nmv - 1) >> 1;
-  const int win = 64 + 2 * range;
+  const SearchRange R(range);
+  const int total = SearchWork::total(F), nmv = R.nmv, centre = R.centre;
   const int shift = F.bit_depth - 8;
-  const int delta = (8 - (range & 7)) & 7;  // the window starts at column 64 cx - range: delta samples after a multiple of 8
   const T* plane = reinterpret_cast<const T*>(F.luma);
 
   for (int work = blockIdx.x; work < total; work += gridDim.x) {
-    const int f = 1 + work / per_frame;
-    const int rem = work % per_frame;
-    const int cy = F.row_begin + rem / F.ctus_x, cx = rem % F.ctus_x;
-    const long long cur_base = (long long)f * F.frame_stride, ref_base = (long long)(f - 1) * F.frame_stride;
-    // ---- stage the reference window (the staging loop of fhevc_motion_kernel): rows cy*64 - R .. + win, columns cx*64 - R .. + win, clamped ----
+    const SearchWork W(F, work);
+    const int cx = W.cx, cy = W.cy;
     __syncthreads();  // the previous CTU's readers are done
-    {
-      const int chunks = (win + delta + 7) >> 3;
-      for (int it = tid; it < win * chunks; it += 256) {
-        const int wr = it / chunks, wc = (it - wr * chunks) * 8;
-        const int py = min(max(cy * 64 - range + wr, 0), F.height - 1);
-        const int px0 = cx * 64 - range - delta + wc;
-        short v[8];
-        const long long row = ref_base + (long long)py * F.stride;
-        const T* src = plane + row + px0;
-        if (px0 >= 0 && px0 + 8 <= F.width && (reinterpret_cast<uintptr_t>(src) & (8 * sizeof(T) - 1)) == 0) {
-          if (sizeof(T) == 2) {
-            const uint4 q = *reinterpret_cast<const uint4*>(src);
-            *reinterpret_cast<uint4*>(s_ref + wr * RP + wc) = q;
-            continue;
-          } else {
-            const uint2 q = *reinterpret_cast<const uint2*>(src);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { v[k] = (short)((q.x >> (8 * k)) & 0xFF); v[4 + k] = (short)((q.y >> (8 * k)) & 0xFF); }
-          }
-        } else if (px0 >= 0 && px0 + 8 <= F.width) {
-#pragma unroll
-          for (int k = 0; k < 8; ++k) v[k] = (short)sample_at(plane, row + px0 + k);
-        } else {
-#pragma unroll
-          for (int k = 0; k < 8; ++k) v[k] = (short)sample_at(plane, row + min(max(px0 + k, 0), F.width - 1));
-        }
-        // one 16-byte store of whole dwords (no sub-dword LDS access): wc is a multiple of 8, the row pitch too
-        uint4 q;
-        q.x = ((unsigned)v[0] & 0xFFFFu) | ((unsigned)v[1] << 16); q.y = ((unsigned)v[2] & 0xFFFFu) | ((unsigned)v[3] << 16);
-        q.z = ((unsigned)v[4] & 0xFFFFu) | ((unsigned)v[5] << 16); q.w = ((unsigned)v[6] & 0xFFFFu) | ((unsigned)v[7] << 16);
-        *reinterpret_cast<uint4*>(s_ref + wr * RP + wc) = q;
-      }
-    }
+    search_stage_window<T, RP>(s_ref, plane, W.ref_base, F, cx, cy, R, tid);
     // ---- this lane's original 8x8 tile (all four waves hold the same 64 tiles) ----
     const int px = cx * 64 + tx * 8, py = cy * 64 + ty * 8;
     const bool inside = (px + 8 <= F.width) && (py + 8 <= F.height);
     unsigned O[32];
-    if (inside) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const long long row = cur_base + (long long)(py + j) * F.stride + px;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          O[4 * j + k] = ((unsigned)sample_at(plane, row + 2 * k) & 0xFFFFu) | ((unsigned)sample_at(plane, row + 2 * k + 1) << 16);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 32; ++i) O[i] = 0;
-    }
+    load_tile8x8(plane, W.cur_base, F, px, py, inside, O);
     __syncthreads();
 
     unsigned bc[SLOTS], bi[SLOTS];
 #pragma unroll
     for (int k = 0; k < SLOTS; ++k) { bc[k] = 0xFFFFFFFFu; bi[k] = 0; }
     for (int m = wave; m < nmv; m += 4) {  // raster order inside a wave; the waves interleave and are merged by (cost, index)
-      const int dy = m / side - range, dx = m % side - range;
-      const int col = tx * 8 + range + dx + delta, row0 = ty * 8 + range + dy;
-      const unsigned sh = (unsigned)(col & 1) * 16u;  // uniform: R + dx
+      int col, row0;
+      R.at(m, tx, ty, col, row0);
       unsigned q[4] = { 0, 0, 0, 0 };  // q00 q01 / q10 q11
       if (PACKED && SAD) {  // sum |org - ref| on pairs of unsigned 16-bit samples: v_sad_u16
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const unsigned* r = reinterpret_cast<const unsigned*>(s_ref) + (((row0 + j) * RP + col) >> 1);
-          const unsigned d0 = r[0], d1 = r[1], d2 = r[2], d3 = r[3], d4 = r[4];
-          unsigned& l = q[(j >> 2) * 2], &rr = q[(j >> 2) * 2 + 1];
-          l = __builtin_amdgcn_sad_u16(O[4 * j + 0], __builtin_amdgcn_alignbit(d1, d0, sh), l);
-          l = __builtin_amdgcn_sad_u16(O[4 * j + 1], __builtin_amdgcn_alignbit(d2, d1, sh), l);
-          rr = __builtin_amdgcn_sad_u16(O[4 * j + 2], __builtin_amdgcn_alignbit(d3, d2, sh), rr);
-          rr = __builtin_amdgcn_sad_u16(O[4 * j + 3], __builtin_amdgcn_alignbit(d4, d3, sh), rr);
+          const SearchRefRow w = search_ref_row<RP>(s_ref, row0 + j, col);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) q[(j >> 2) * 2 + (k >> 1)] = __builtin_amdgcn_sad_u16(O[4 * j + k], w.pair(k), q[(j >> 2) * 2 + (k >> 1)]);
         }
       } else if (PACKED) {
         unsigned D[32];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const unsigned* r = reinterpret_cast<const unsigned*>(s_ref) + (((row0 + j) * RP + col) >> 1);
-          const unsigned d0 = r[0], d1 = r[1], d2 = r[2], d3 = r[3], d4 = r[4];
-          D[4 * j + 0] = pk_sub(O[4 * j + 0], __builtin_amdgcn_alignbit(d1, d0, sh));
-          D[4 * j + 1] = pk_sub(O[4 * j + 1], __builtin_amdgcn_alignbit(d2, d1, sh));
-          D[4 * j + 2] = pk_sub(O[4 * j + 2], __builtin_amdgcn_alignbit(d3, d2, sh));
-          D[4 * j + 3] = pk_sub(O[4 * j + 3], __builtin_amdgcn_alignbit(d4, d3, sh));
-        }
+        search_tile_diff<RP>(s_ref, row0, col, O, D);
 #pragma unroll
         for (int k = 0; k < 4; ++k) q[k] = had4x4_packed(D, (k >> 1) * 4, (k & 1) * 2);
       } else {
         int v[64];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          // whole dwords from LDS, as the packed forms read them
-          const unsigned* r = reinterpret_cast<const unsigned*>(s_ref) + (((row0 + j) * RP + col) >> 1);
-          const unsigned d0 = r[0], d1 = r[1], d2 = r[2], d3 = r[3], d4 = r[4];
-          const unsigned w[4] = { __builtin_amdgcn_alignbit(d1, d0, sh), __builtin_amdgcn_alignbit(d2, d1, sh), __builtin_amdgcn_alignbit(d3, d2, sh),
-                                  __builtin_amdgcn_alignbit(d4, d3, sh) };
+          const SearchRefRow w = search_ref_row<RP>(s_ref, row0 + j, col);  // whole dwords from LDS, as the packed forms read them
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            v[8 * j + 2 * k] = (int)(short)(O[4 * j + k] & 0xFFFFu) - (int)(short)(w[k] & 0xFFFFu);
-            v[8 * j + 2 * k + 1] = (int)(short)(O[4 * j + k] >> 16) - (int)(short)(w[k] >> 16);
+            const unsigned p = w.pair(k);
+            v[8 * j + 2 * k] = (int)(short)(O[4 * j + k] & 0xFFFFu) - (int)(short)(p & 0xFFFFu);
+            v[8 * j + 2 * k + 1] = (int)(short)(O[4 * j + k] >> 16) - (int)(short)(p >> 16);
           }
         }
 #pragma unroll
@@ -215,23 +143,13 @@ __global__ __launch_bounds__(256, (PACKED ? 4 : 3)) void fhevc_motion_pu_small_k
       // the CU node this entry belongs to: a PU is valid iff its node lies wholly inside the picture
       const int n = e < AMP_ENTRIES ? 16 : 8, cnt = 64 / n;
       const int ni = e < AMP_ENTRIES ? e >> 3 : (e - AMP_ENTRIES) >> 2;
-      const int bx = ni % cnt, by = ni / cnt;
-      uint4 o;
-      if (cx * 64 + bx * n + n > F.width || cy * 64 + by * n + n > F.height) {
-        o.x = o.y = o.z = 0xFFFFFFFFu; o.w = 0;
-      } else {
-        unsigned c = s_cost[0][e], ix = s_idx[0][e];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) {
-          const unsigned c2 = s_cost[w][e], i2 = s_idx[w][e];
-          if (c2 < c || (c2 == c && i2 < ix)) { c = c2; ix = i2; }
-        }
-        const int mvx = (int)(ix % side) - range, mvy = (int)(ix / side) - range;
-        o.x = s_zero[e]; o.y = c - s_vc[ix]; o.z = c;
-        o.w = ((unsigned)mvx & 0xFFFFu) | ((unsigned)mvy << 16);
+      uint4 o = search_record_outside();
+      if (search_node_inside(F, cx, cy, ni % cnt, ni / cnt, n)) {
+        unsigned c, ix;
+        search_merge(&s_cost[0][0], &s_idx[0][0], ENTRIES, e, c, ix);
+        o = search_record(s_zero[e], c, s_vc[ix], ix, R);
       }
-      const long long oc = (long long)((f - 1) * band_rows + (cy - F.row_begin)) * F.ctus_x + cx;
-      *reinterpret_cast<uint4*>(out_pus + oc * ENTRIES + e) = o;  // one 16-byte store per entry
+      *reinterpret_cast<uint4*>(out_pus + W.oc(F) * ENTRIES + e) = o;  // one 16-byte store per entry
     }
   }
 }
@@ -239,20 +157,12 @@ __global__ __launch_bounds__(256, (PACKED ? 4 : 3)) void fhevc_motion_pu_small_k
 }  // namespace
 
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage): 29 076 B of LDS per workgroup (window 14 096 B, merge 13 824 B, vector costs
-// 1 156 B), no scratch; the packed forms take 95 (SAD) and 115 (SATD) VGPRs and are held to four waves per SIMD (four workgroups per CU, 116 KB of
-// its LDS), the 32-bit forms 147 and 131 (three workgroups per CU).  The persistent grid is sized to exactly that residency
+// 1 156 B), no scratch; the packed forms take 95 (SAD) and 117 (SATD) VGPRs and are held to four waves per SIMD (four workgroups per CU, 116 KB of
+// its LDS), the 32-bit forms 150 and 130 (three workgroups per CU).  The persistent grid is sized to exactly that residency
 hipError_t fhevc_launch_motion_pu_small(const FhevcFrames& fr, int range, const FhevcMvCost& mvc, FhevcMotionNode* d_pus, int num_cus, bool sad, hipStream_t stream)
 {
-  const long long total = (long long)(fr.row_end - fr.row_begin) * fr.ctus_x * (fr.num_frames - 1);
-  if (total <= 0) return hipSuccess;
-  if (range < 1 || range > FHEVC_MOTION_MAX_RANGE || !d_pus) return hipErrorInvalidValue;
-  const long long resident = (fr.sample_bytes == 2 && fr.bit_depth > 10 ? 3LL : 4LL) * num_cus;
-  const int grid = (int)(total < resident ? total : resident);
-#define FHEVC_MOTION_PU_SMALL(T, P) do { if (sad) hipLaunchKernelGGL((fhevc_motion_pu_small_kernel<T, P, true>), dim3(grid), dim3(256), 0, stream, fr, range, mvc, d_pus); \
-                                         else hipLaunchKernelGGL((fhevc_motion_pu_small_kernel<T, P, false>), dim3(grid), dim3(256), 0, stream, fr, range, mvc, d_pus); } while (0)
-  if (fr.sample_bytes == 2 && fr.bit_depth <= 10) FHEVC_MOTION_PU_SMALL(int16_t, true);
-  else if (fr.sample_bytes == 2) FHEVC_MOTION_PU_SMALL(int16_t, false);
-  else FHEVC_MOTION_PU_SMALL(uint8_t, true);
-#undef FHEVC_MOTION_PU_SMALL
-  return hipGetLastError();
+  return search_launch(fr, range >= 1 && range <= FHEVC_MOTION_MAX_RANGE && d_pus, num_cus, 4, 3, sad, [&](auto t, auto packed, auto sad_c, int grid) {
+    hipLaunchKernelGGL((fhevc_motion_pu_small_kernel<decltype(t), decltype(packed)::value, decltype(sad_c)::value>), dim3(grid), dim3(256), 0, stream, fr, range, mvc, d_pus);
+    return hipSuccess;
+  });
 }

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void fhevc_motion_refine_kernel(FhevcFrames F,
     const int px = cx * 64 + tx * 8, py = cy * 64 + ty * 8;
     const bool inside = (px + 8 <= F.width) && (py + 8 <= F.height);
     unsigned O[32];
-    refine_load_tile(plane, cur_base, F, px, py, inside, O);
+    load_tile8x8(plane, cur_base, F, px, py, inside, O);
     // ---- its node's integer vector: only mvx / mvy of the input are read, validity comes from the geometry and from max_range ----
     const bool node_in = cx * 64 + nbx * nsize + nsize <= F.width && cy * 64 + nby * nsize + nsize <= F.height;
     int mx = 0, my = 0;

@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void fhevc_motion_refine_pu_kernel(FhevcFrames
     const int px = cx * 64 + tx * 8, py = cy * 64 + ty * 8;
     const bool inside = (px + 8 <= F.width) && (py + 8 <= F.height);
     unsigned O[32];
-    refine_load_tile(plane, cur_base, F, px, py, inside, O);
+    load_tile8x8(plane, cur_base, F, px, py, inside, O);
     __syncthreads();
 
 #pragma unroll 1

@@ -1,10 +1,11 @@
 // k_refine_tile.h -- what the two quarter-sample refinement kernels share (k_motion_refine.hip: the 85 square CU nodes; k_motion_refine_pu.hip: the
-// 508 PUs): the reference window in LDS, a lane's original 8x8 tile, the candidate tables, and the prediction of one 8x8 tile at one quarter-sample
+// 508 PUs): the reference window in LDS, the candidate tables, and the prediction of one 8x8 tile at one quarter-sample
 // candidate as a block of differences to the original.  The interpolation form is the one k_motion_refine.hip's header comment derives: the
 // fractions are DATA (two packed coefficient vectors per lane), so the lanes of a wave need not agree on a phase.
 #pragma once
 #include "fhevc_internal.h"
 #include "k_had8x8.h"
+#include "k_search_tile.h"  // sample_of, load_tile8x8: one definition for the searches and the refinements
 
 namespace {
 
@@ -35,9 +36,6 @@ __device__ __forceinline__ int eg_bits(int v)  // xGetExpGolombNumberOfBits (TCo
   const unsigned u = (v <= 0) ? (((unsigned)(-v)) << 1) + 1u : ((unsigned)v) << 1;
   return 1 + 2 * (31 - __builtin_clz(u));
 }
-
-template <typename T>
-__device__ __forceinline__ int sample_of(const T* plane, long long off) { return (int)plane[off]; }
 
 // the constants of the interpolation at one bit depth
 struct RefineArith {
@@ -74,24 +72,6 @@ __device__ __forceinline__ void refine_stage_window(short* s_ref, const T* plane
       q.x = ((unsigned)v[0] & 0xFFFFu) | ((unsigned)v[1] << 16); q.y = ((unsigned)v[2] & 0xFFFFu) | ((unsigned)v[3] << 16);
     }
     *reinterpret_cast<uint2*>(s_ref + wr * RP + wc) = q;
-  }
-}
-
-// ---- a lane's original 8x8 tile at (px, py) as 32 packed pairs (zeros where the tile is not wholly inside the picture) ----
-template <typename T>
-__device__ __forceinline__ void refine_load_tile(const T* plane, long long cur_base, const FhevcFrames& F, int px, int py, bool inside, unsigned (&O)[32])
-{
-  if (inside) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const long long row = cur_base + (long long)(py + j) * F.stride + px;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        O[4 * j + k] = ((unsigned)sample_of(plane, row + 2 * k) & 0xFFFFu) | ((unsigned)sample_of(plane, row + 2 * k + 1) << 16);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 32; ++i) O[i] = 0;
   }
 }
 

@@ -10,7 +10,7 @@ import motion_pu_small_ref as ps
 import motion_refine_pu_ref as rp
 import motion_refine_ref as mr
 from fasthevc_amd import capi, frames
-from test_gpu_motion_pu_small import CANARY, Guarded, clip_planes, pel, pel_batch, to_dev, torch_cuda  # noqa: F401
+from motion_gpu_helpers import CANARY, Guarded, clip_planes, pel, pel_batch, to_dev, torch_cuda  # noqa: F401
 from test_motion_refine_ref import textured
 
 pytestmark = pytest.mark.gpu
