@@ -3,7 +3,8 @@
 (oracle/_ref/libhmref.so = objects compiled from /root/reference + oracle/ref_harness.cpp).
 
 Run in the build container only (needs /root/reference):  make -C oracle ref && python oracle/gen_golden.py
-(--bit-depths-only: tests/golden/ref_bit_depths.npz alone, bit_depths_golden)
+(--bit-depths-only: tests/golden/ref_bit_depths.npz alone, bit_depths_golden;
+ --motion-pu-only: tests/golden/ref_pattern_search_pu.npz and ref_frac_search.npz alone, motion_pu_golden)
 The fixture holds inputs and expected outputs (data), never reference source.
 """
 import os
@@ -365,8 +366,185 @@ def bit_depths_golden(ref):
     print("wrote", dst, os.path.getsize(dst), "bytes")
 
 
+# ---- config 4: the searches of the rectangular PUs and the quarter-sample stage (tests/golden/ref_pattern_search_pu.npz, ref_frac_search.npz) --------
+# One ragged picture, 176 x 144 = 3 x 3 CTUs with a last column 48 wide and a last row 16 tall; whole CTUs: corner, ragged right, interior, ragged
+# bottom, both.  Entries per CTU: the 85 nodes, the 124 PUs (motion_pu_ref.covered), the 384 small PUs (motion_pu_small_ref.covered).
+PU_W, PU_H, PU_CTUS = 176, 144, (0, 2, 4, 6, 8)
+PU_PAN_SPEEDS = ((2, -3), (-4, 6))   # (v_structure, v_noise) of the two pan clips
+# (bit depth, QP, range, content): content 0 / 1 = the pan clip at that speed; every bit depth, QP and range with each of the others' values once
+PU_PAN_CASES = ((8, 0, 1, 0), (8, 32, 5, 1), (8, 51, 8, 0), (10, 0, 5, 0), (10, 32, 8, 1), (10, 51, 1, 0), (12, 0, 8, 1), (12, 32, 1, 0), (12, 51, 5, 1))
+# "white": the current picture 2^bd - 1 everywhere over a black reference (every vector has the same SAD); "checker": a one-sample checkerboard
+# of 0 and 2^bd - 1 against its inverse (every vector with an odd x + y has SAD 0 away from the border: (0, -1) is the first of the cheapest in raster order)
+PU_SEARCH_CASES = PU_PAN_CASES + ((10, 32, 5, "white"), (12, 0, 8, "checker"))
+# "blend": the current picture is the reference blended with itself one sample away, direction and weight drawn per 8x8 cell (motion of about a half
+# or a quarter sample: most winners are fractional); "flat": two different flat pictures (every candidate has the same distortion: the centre wins
+# both stages); "swing": random samples of 0 and 2^bd - 1 (the filters overshoot both ends: the clip works)
+PU_FRAC_CASES = PU_PAN_CASES + ((8, 27, 3, "blend"), (10, 22, 4, "blend"), (10, 32, 2, "flat"), (8, 12, 8, "swing"), (12, 37, 6, "swing"))
+
+
+_PU_ENTRIES = []
+
+
+def _pu_entries():
+    """(rectangles (x0, y0, w, h), CU nodes (x0, y0, n)) of the 593 entries of one CTU in file order: 85 + 124 + 384, coordinates inside the CTU"""
+    if _PU_ENTRIES:
+        return _PU_ENTRIES
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+    import motion_pu_ref as mp
+    import motion_pu_small_ref as ps
+    rects = [mp.node_rect(k)[:2] + (mp.node_rect(k)[2],) * 2 for k in range(85)] + [mp.pu_rect(*e) for e in mp.covered()] + [mp.pu_rect(*e) for e in ps.covered()]
+    nodes = list(range(85)) + [e[0] for e in mp.covered()] + [e[0] for e in ps.covered()]
+    _PU_ENTRIES.extend((rects, [mp.node_rect(k) for k in nodes]))
+    return _PU_ENTRIES
+
+
+def _pu_planes(bd, content):
+    """-> (cur, ref) int16 [H, W]"""
+    hi = (1 << bd) - 1
+    if content in (0, 1):
+        ys = frames.pan_clip(PU_W, PU_H, 2, seed=70 + content, v_structure=PU_PAN_SPEEDS[content][0], v_noise=PU_PAN_SPEEDS[content][1])
+        ref, cur = (y.astype(np.int64) << (bd - 8) for y in ys)
+        if bd > 8:  # use the low bits too
+            cur = cur + np.random.default_rng(bd).integers(0, 1 << (bd - 8), size=cur.shape)
+            ref = ref + np.random.default_rng(bd + 1).integers(0, 1 << (bd - 8), size=ref.shape)
+    elif content == "white":
+        cur, ref = np.full((PU_H, PU_W), hi), np.zeros((PU_H, PU_W), np.int64)
+    elif content == "checker":
+        yy, xx = np.mgrid[0:PU_H, 0:PU_W]
+        ref = ((yy + xx) % 2) * hi
+        cur = hi - ref
+    elif content == "flat":
+        cur, ref = np.full((PU_H, PU_W), hi // 3), np.full((PU_H, PU_W), hi // 2)
+    elif content == "swing":
+        rng = np.random.default_rng(900 + bd)
+        ref = rng.integers(0, 2, size=(PU_H, PU_W)) * hi
+        cur = np.where(rng.random((PU_H, PU_W)) < 0.1, hi - ref, ref)
+    else:  # "blend"
+        rng = np.random.default_rng(800 + bd)
+        ref = frames.pan_clip(PU_W, PU_H, 1, seed=72)[0].astype(np.int64) << (bd - 8)
+        if bd > 8:
+            ref = ref + rng.integers(0, 1 << (bd - 8), size=ref.shape)
+        p = np.pad(ref, 1, mode="edge")
+        cells = (PU_H // 8, PU_W // 8)
+        dx, dy, wt = (rng.integers(lo, hi_, size=cells).repeat(8, 0).repeat(8, 1) for lo, hi_ in ((-1, 2), (-1, 2), (1, 3)))
+        yy, xx = np.mgrid[0:PU_H, 0:PU_W]
+        far = p[yy + 1 + dy, xx + 1 + dx]
+        cur = np.where(wt == 2, (ref + far + 1) >> 1, (3 * ref + far + 2) >> 2)
+    return np.ascontiguousarray(cur, np.int16), np.ascontiguousarray(ref, np.int16)
+
+
+def _pu_blocks(c):
+    """the entries of CTU c whose CU node lies wholly inside the picture -> (indices into the 593, [n, 4] picture rectangles)"""
+    rects, nodes = _pu_entries()
+    cx, cy = c % 3, c // 3
+    where = [i for i, (nx, ny, n) in enumerate(nodes) if 64 * cx + nx + n <= PU_W and 64 * cy + ny + n <= PU_H]
+    return where, np.array([(64 * cx + rects[i][0], 64 * cy + rects[i][1], rects[i][2], rects[i][3]) for i in where], np.int32)
+
+
+def _pu_search_case(ref, oracle, cur, refp, bd, qp, R):
+    """xPatternSearch on every valid entry of the five CTUs -> [5, 593, 5] int32: mvx, mvy, SAD, cost, SAD at the zero vector; -1 = outside"""
+    import ctypes as C
+    lam = C.c_double(oracle.fho_lambda_intra(qp, bd))
+    res = np.full((len(PU_CTUS), 593, 5), -1, np.int32)
+    for ci, c in enumerate(PU_CTUS):
+        where, blocks = _pu_blocks(c)
+        o, z = np.zeros((len(where), 4), np.int32), np.zeros((len(where), 4), np.int32)
+        for rng, dst in ((R, o), (0, z)):
+            assert ref.href_pattern_search_rect(cur.ctypes.data, refp.ctypes.data, PU_W, PU_W, PU_H, bd, lam, rng, len(where), blocks.reshape(-1), dst.reshape(-1)) == len(where)
+        assert not z[:, :2].any()
+        res[ci, where, :4], res[ci, where, 4] = o, z[:, 2]
+    return res
+
+
+def _pu_family_counts(valid):
+    """valid [.., 593] -> valid entries per family: nodes, PUs, small PUs"""
+    return [int(valid[..., :85].sum()), int(valid[..., 85:209].sum()), int(valid[..., 209:].sum())]
+
+
+def _pu_save(name, out):
+    dst = os.path.join(os.path.dirname(HERE), "tests", "golden", name)
+    np.savez_compressed(dst, **out)
+    size = os.path.getsize(dst)
+    assert size < 1044550, (name, size)   # below the largest committed golden (ref_vectors.npz)
+    print("wrote", dst, size, "bytes")
+
+
+def motion_pu_golden(ref):
+    """What the reference's OWN xPatternSearch (SAD, on w x h patterns) and xPatternSearchFracDIF (Hadamard, quarter-sample stage fed the integer
+    search's vectors: HM's chain) return for every node and PU of five CTUs of a ragged picture.  Planes and integers only."""
+    import ctypes as C
+    oracle = op.load_oracle()
+    planes, plane_of = [], {}
+
+    def plane_index(bd, content):
+        if (bd, content) not in plane_of:
+            plane_of[(bd, content)] = len(planes)
+            planes.append(_pu_planes(bd, content))
+        return plane_of[(bd, content)]
+
+    # ---- integer search
+    out = {"size": np.array([PU_W, PU_H], np.int32), "ctus": np.array(PU_CTUS, np.int32)}
+    cases, counts = [], np.zeros(3, np.int64)
+    for k, (bd, qp, R, content) in enumerate(PU_SEARCH_CASES):
+        p = plane_index(bd, content)
+        res = _pu_search_case(ref, oracle, *planes[p], bd, qp, R)
+        out[f"res{k}"] = res
+        cases.append((bd, qp, R, p))
+        counts += _pu_family_counts(res[..., 3] != -1)
+    for p, (cur, refp) in enumerate(planes):
+        out[f"cur{p}"], out[f"ref{p}"] = cur, refp
+    out["cases"], out["counts"] = np.array(cases, np.int32), counts.astype(np.int32)
+    print("integer search, valid entries (nodes, PUs, small PUs):", counts.tolist(), "in", len(cases), "cases")
+    _pu_save("ref_pattern_search_pu.npz", out)
+
+    # ---- fractional search around the integer search's own vectors; every 7th entry a seeded random vector instead, in the corner CTUs the
+    # window's own corners: the replicated border is read
+    planes, plane_of = [], {}
+    out = {"size": np.array([PU_W, PU_H], np.int32), "ctus": np.array(PU_CTUS, np.int32)}
+    cases, counts = [], np.zeros(3, np.int64)
+    half_wins, quarter_wins = np.zeros((3, 3), np.int64), np.zeros((3, 3), np.int64)
+    for k, (bd, qp, R, content) in enumerate(PU_FRAC_CASES):
+        p = plane_index(bd, content)
+        cur, refp = planes[p]
+        ints = _pu_search_case(ref, oracle, cur, refp, bd, qp, R)
+        rng = np.random.default_rng(1000 + k)
+        vin = np.zeros((len(PU_CTUS), 593, 2), np.int16)
+        res = np.full((len(PU_CTUS), 593, 5), -1, np.int32)
+        for ci, c in enumerate(PU_CTUS):
+            where, blocks = _pu_blocks(c)
+            v = ints[ci, where, :2].copy()
+            rnd = rng.integers(-R, R + 1, size=v.shape)
+            if c == 0:
+                rnd[:] = -R
+            if c == 8:
+                rnd[:] = R
+            seventh = np.array(where) % 7 == 0
+            v[seventh] = rnd[seventh]
+            b = np.ascontiguousarray(np.concatenate([blocks, v], axis=1), np.int32)
+            o = np.zeros((len(where), 7), np.int32)
+            assert ref.href_frac_search(cur.ctypes.data, refp.ctypes.data, PU_W, PU_W, PU_H, bd, C.c_double(oracle.fho_lambda_intra(qp, bd)), len(where),
+                                        b.reshape(-1), o.reshape(-1)) == len(where)
+            vin[ci, where] = v
+            res[ci, where] = o[:, [4, 3, 2, 0, 1]]    # satd_int, satd_best, cost_best, mvx, mvy: the library's record
+            q = o[:, :2] - 4 * v - 2 * o[:, 5:7]
+            np.add.at(half_wins, (o[:, 6] + 1, o[:, 5] + 1), 1)
+            np.add.at(quarter_wins, (q[:, 1] + 1, q[:, 0] + 1), 1)
+        out[f"in{k}"], out[f"out{k}"] = vin, res
+        cases.append((bd, qp, R, p))
+        counts += _pu_family_counts(res[..., 2] != -1)
+    assert half_wins.all() and quarter_wins.all(), (half_wins, quarter_wins)   # every candidate of both tables wins somewhere
+    for p, (cur, refp) in enumerate(planes):
+        out[f"cur{p}"], out[f"ref{p}"] = cur, refp
+    out["cases"], out["counts"] = np.array(cases, np.int32), counts.astype(np.int32)
+    print("fractional search, valid entries (nodes, PUs, small PUs):", counts.tolist(), "in", len(cases), "cases")
+    print("half-stage winners [dy + 1][dx + 1]:", half_wins.tolist(), "quarter-stage winners:", quarter_wins.tolist())
+    _pu_save("ref_frac_search.npz", out)
+
+
 if __name__ == "__main__":
-    if "--intra-lines-only" in sys.argv:
+    if "--motion-pu-only" in sys.argv:
+        motion_pu_golden(op.load_ref())
+    elif "--intra-lines-only" in sys.argv:
         intra_lines_golden(op.load_ref())
     elif "--preanalyze-only" in sys.argv:
         preanalyze_golden(op.load_ref())

@@ -167,6 +167,12 @@ def load_ref(hook=False):
         lib.href_aq_qp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")]
         lib.href_aq_qp.restype = C.c_int
+    if hasattr(lib, "href_frac_search"):
+        # cur, ref, stride, width, height, bit depth, lambda, [range,] number of blocks, blocks, out (oracle/ref_rdo_harness.cpp)
+        lib.href_pattern_search_rect.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _i32p, _i32p]
+        lib.href_pattern_search_rect.restype = C.c_int
+        lib.href_frac_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _i32p, _i32p]
+        lib.href_frac_search.restype = C.c_int
     return lib
 
 

@@ -708,6 +708,95 @@ int href_pattern_search(const int16_t* cur, const int16_t* ref, int stride, int 
   return nblocks;
 }
 
+// a luma plane in a TComPicYuv with HM's margins, extended by the reference's own extendPicBorder: what href_pattern_search sets up
+struct RefPlane {
+  TComPicYuv yuv;
+  Pel* origin;
+  int stride;
+  RefPlane(const int16_t* ref, int ref_stride, int width, int height)
+  {
+    yuv.create(width, height, CHROMA_420, 64, 64, 4, true);
+    origin = yuv.getAddr(COMPONENT_Y);
+    stride = yuv.getStride(COMPONENT_Y);
+    for (int y = 0; y < height; y++) std::memcpy(origin + (size_t)y * stride, ref + (size_t)y * ref_stride, (size_t)width * sizeof(Pel));
+    yuv.extendPicBorder();
+  }
+  ~RefPlane() { yuv.destroy(); }
+};
+
+// ---- href_pattern_search for rectangular blocks (the PUs of 2NxN, Nx2N and AMP): the same set-up -- 4-argument setDistParam (DF_SAD + the
+// width's own function, TComRdCost.cpp:205-236: widths 12, 24 and 48 have theirs), zero predictor, iCostScale 2 -- on a w x h pattern.
+// range 0 searches the zero vector alone: the reference's SAD there.  out per block: mvx, mvy, SAD, cost.
+int href_pattern_search_rect(const int16_t* cur, const int16_t* ref, int stride, int width, int height, int bit_depth, double lambda, int range,
+                             int nblocks, const int* blocks /* x0, y0, w, h per block */, int* out /* mvx, mvy, sad, cost per block */)
+{
+  if (range < 0 || range > 64) return -1;
+  Encoder* e = get_encoder(width, height, bit_depth);
+  RefPlane rp(ref, stride, width, height);
+  e->rd.setLambda(lambda, e->sps.getBitDepths());
+  e->rd.selectMotionLambda(true, 0, false);
+  TComMv zero(0, 0);
+  e->rd.setPredictor(zero);
+  e->rd.setCostScale(2);
+  for (int b = 0; b < nblocks; b++) {
+    const int x0 = blocks[4 * b], y0 = blocks[4 * b + 1], w = blocks[4 * b + 2], h = blocks[4 * b + 3];
+    if (x0 < 0 || y0 < 0 || w <= 0 || h <= 0 || x0 + w > width || y0 + h > height) return -1;
+    TComPattern pattern;
+    pattern.initPattern(const_cast<Pel*>(cur) + (size_t)y0 * stride + x0, w, h, stride, bit_depth);
+    TComMv lt(-range, -range), rb(range, range), mv;
+    Distortion sad = 0;
+    e->search.xPatternSearch(&pattern, rp.origin + (size_t)y0 * rp.stride + x0, rp.stride, &lt, &rb, mv, sad);
+    out[4 * b] = mv.getHor(); out[4 * b + 1] = mv.getVer(); out[4 * b + 2] = (int)sad;
+    out[4 * b + 3] = (int)(sad + e->rd.getCostOfVectorWithPredictor(mv.getHor(), mv.getVer()));
+  }
+  return nblocks;
+}
+
+uint32_t href_get_hads(int bit_depth, const int16_t* a, int sa, const int16_t* b, int sb, int w, int h);  // ref_harness.cpp
+
+// ---- config 4: the reference's OWN fractional search, TEncSearch::xPatternSearchFracDIF (TEncSearch.cpp:4370-4406: xExtDIFUpSamplingH / Q,
+// xPatternRefinement twice), around a given integer vector, on ORIGINAL planes set up as for href_pattern_search.  As xMotionEstimation calls
+// it (TEncSearch.cpp:3743-3749): lossy, selectMotionLambda(true, ..), iCostScale 1 on entry (the function itself goes to 0 for the quarter
+// stage); UseHADME on for the call (cfg/encoder_lowdelay_P_main.cfg), so the distortion is xGetHADs; zero predictor.
+// out per block: the vector in quarter samples (4 int + 2 half + quarter), the cost the function returns, that cost minus the vector's cost at
+// scale 0 (the Hadamard distortion at the winner), the reference's xGetHADs of the block displaced by the integer vector, the half-stage offset.
+int href_frac_search(const int16_t* cur, const int16_t* ref, int stride, int width, int height, int bit_depth, double lambda,
+                     int nblocks, const int* blocks /* x0, y0, w, h, mvx, mvy per block */,
+                     int* out /* qmvx, qmvy, cost, satd_best, satd_int, halfx, halfy per block */)
+{
+  Encoder* e = get_encoder(width, height, bit_depth);
+  RefPlane rp(ref, stride, width, height);
+  const bool hadme_was = e->cfg.getUseHADME();
+  e->cfg.setUseHADME(true);
+  e->rd.setLambda(lambda, e->sps.getBitDepths());
+  e->rd.selectMotionLambda(true, 0, false);
+  TComMv zero(0, 0);
+  e->rd.setPredictor(zero);
+  int done = 0;
+  for (int b = 0; b < nblocks; b++, done++) {
+    const int* k = blocks + 6 * b;
+    const int x0 = k[0], y0 = k[1], w = k[2], h = k[3], mx = k[4], my = k[5];
+    if (x0 < 0 || y0 < 0 || w <= 0 || h <= 0 || x0 + w > width || y0 + h > height || mx < -64 || mx > 64 || my < -64 || my > 64) break;
+    Pel* org = const_cast<Pel*>(cur) + (size_t)y0 * stride + x0;
+    Pel* at = rp.origin + (ptrdiff_t)y0 * rp.stride + x0;
+    TComPattern pattern;
+    pattern.initPattern(org, w, h, stride, bit_depth);
+    TComMv mv(mx, my), half, quarter;
+    Distortion cost = 0;
+    e->rd.setCostScale(1);
+    e->search.xPatternSearchFracDIF(false, &pattern, at, rp.stride, &mv, half, quarter, cost);
+    e->rd.setCostScale(0);
+    const int qx = 4 * mx + 2 * half.getHor() + quarter.getHor(), qy = 4 * my + 2 * half.getVer() + quarter.getVer();
+    int* o = out + 7 * b;
+    o[0] = qx; o[1] = qy; o[2] = (int)cost;
+    o[3] = (int)(cost - e->rd.getCostOfVectorWithPredictor(qx, qy));
+    o[4] = (int)href_get_hads(bit_depth, org, stride, at + (ptrdiff_t)my * rp.stride + mx, rp.stride, w, h);
+    o[5] = half.getHor(); o[6] = half.getVer();
+  }
+  e->cfg.setUseHADME(hadme_was);
+  return done == nblocks ? nblocks : -1;
+}
+
 // md5 (16 bytes) of the slice-data bytes written by the reference's encodeSlice in the last href_rdo_encode_frame* call of that geometry
 // (FHREF_ENCODE_SLICE=1); -1 when there is none
 int href_slice_md5(int width, int height, int bit_depth, unsigned char* digest16)
