@@ -35,6 +35,7 @@ SYMBOLS = [
     "fhevc_motion_search_pu", "fhevc_motion_search_pu_device", "fhevc_motion_pu_index",
     "fhevc_motion_search_pu_small", "fhevc_motion_search_pu_small_device", "fhevc_motion_pu_small_index",
     "fhevc_motion_refine_pu", "fhevc_motion_refine_pu_device",
+    "fhevc_motion_search_pu_wide", "fhevc_motion_search_pu_wide_device",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -178,6 +179,8 @@ def load_library(path=None):
     lib.fhevc_motion_search_pu_small.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     lib.fhevc_motion_search_pu_small_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.fhevc_motion_pu_small_index.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.fhevc_motion_search_pu_wide.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.fhevc_motion_search_pu_wide_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.fhevc_motion_refine_pu.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.fhevc_motion_refine_pu_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     lib.fhevc_p_rule_default.argtypes = [C.POINTER(PRule)]
@@ -474,6 +477,28 @@ class Context:
         rb, re = rows if rows is not None else (0, self.ctus_y)
         self._check(self.lib.fhevc_motion_search_pu_small_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, search_range,
                                                                  d_pus, stream))
+
+    def motion_search_pu_wide(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=64, nodes=True, pus=True, pus_small=True):
+        """config 4: the SAD search of motion_search, motion_search_pu and motion_search_pu_small at search_range 1..64 from one call ->
+        (nodes [numCtus, 85], pus [numCtus, 124], pus_small [numCtus, 384]) of MOTION_DTYPE, None for a family not asked for (at least one must be)."""
+        cur = np.ascontiguousarray(cur_plane).reshape(-1)
+        ref = np.ascontiguousarray(ref_plane).reshape(-1)
+        assert cur.dtype == np.int16 and ref.dtype == np.int16
+        stride = stride if stride is not None else cur_plane.shape[-1]
+        outs = [np.zeros(self.num_ctus * per_ctu, MOTION_DTYPE) if want else None
+                for want, per_ctu in ((nodes, NODES_PER_CTU), (pus, PUS_PER_CTU), (pus_small, PUS_SMALL_PER_CTU))]
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._check(self.lib.fhevc_motion_search_pu_wide(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, search_range,
+                                                         ptr(outs[0]), ptr(outs[1]), ptr(outs[2])))
+        return tuple(None if o is None else o.reshape(self.num_ctus, -1) for o in outs)
+
+    def motion_search_pu_wide_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_nodes=None, d_pus=None, d_pus_small=None, rows=None,
+                                     stream=None, qp=32, search_range=64):
+        """frames 1.. of the batch, each searched in the frame before it, SAD, search_range 1..64; d_nodes / d_pus / d_pus_small: (num_frames - 1) * band
+        CTUs * 85 / 124 / 384 entries (16 B), each optional (not all three).  Asynchronous; keeps no state between calls."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_motion_search_pu_wide_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, search_range,
+                                                                d_nodes, d_pus, d_pus_small, stream))
 
     def motion_refine_pu(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, max_range=4, pus=None, pus_small=None):
         """config 4: the quarter-sample refinement of the PUs' vectors: pus [numCtus, 124] and / or pus_small [numCtus, 384] (MOTION_DTYPE, as

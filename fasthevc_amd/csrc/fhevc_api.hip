@@ -292,7 +292,7 @@ int fhevc_enable_kernel_timing(fhevc_ctx* c, int on)
 
 int fhevc_kernel_timing(fhevc_ctx* c, int which, int reset, double* avg_ms, uint64_t* launches)
 {
-  if (!c || which < 0 || which > 10) return FHEVC_E_INVALID;
+  if (!c || which < 0 || which > 11) return FHEVC_E_INVALID;
   time_resolve(c);
   if (avg_ms) *avg_ms = c->launches[which] ? c->sum_ms[which] / (double)c->launches[which] : 0.0;
   if (launches) *launches = c->launches[which];
@@ -905,6 +905,68 @@ int fhevc_motion_search_pu_small(fhevc_ctx* c, const int16_t* cur_luma, const in
   HIP_TRY(c, hipMemcpyAsync(pus, c->d_motion_pu_small, pu_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->stats.bytes_d2h += (uint64_t)pu_bytes;
+  return FHEVC_OK;
+}
+
+// ---- the three searches at HM's own SearchRange, SAD (the MR = 64 layouts of k_motion_pu.hip and k_motion_pu_small.hip) ----
+
+int fhevc_motion_search_pu_wide_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                       int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range,
+                                       fhevc_motion_node* d_nodes, fhevc_motion_node* d_pus, fhevc_motion_node* d_pus_small, void* stream)
+{
+  if (!c || !d_luma || (!d_nodes && !d_pus && !d_pus_small)) return c ? fail(c, FHEVC_E_INVALID, "bad wide PU motion-search arguments") : FHEVC_E_INVALID;
+  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
+  if (search_range < 1 || search_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "the wide PU motion search covers search ranges 1..64");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
+  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
+  FhevcMotionNode* nodes = reinterpret_cast<FhevcMotionNode*>(d_nodes);
+  FhevcMotionNode* pus = reinterpret_cast<FhevcMotionNode*>(d_pus);
+  FhevcMotionNode* small = reinterpret_cast<FhevcMotionNode*>(d_pus_small);
+  // Always SAD, and every vector cost travels with its launch: the window's table up to +-8 (the MR = 8 layouts, several workgroups per CU), the 40 bit
+  // costs above.  Nothing of the context is read or written by the launches: calls on different streams may be in flight together.  Above +-8: 8-bit
+  // contexts take the byte-SAD kernel (k_motion_pu_wide.hip: one launch for whatever is asked for), contexts above 8 bit -- and 8-bit int16 planes under
+  // FHEVC_PU_WIDE=generic -- the MR = 64 layouts of the generic kernels (one launch for nodes and PUs, one for the small PUs).  Timed under slot 11
+  const bool big = search_range > FHEVC_MOTION_MAX_RANGE;
+  if (big && c->cfg.bit_depth == 8 && !(c->knobs.pu_wide_generic && sample_bytes == 2))
+    return launch_on(c, stream, 11, "fhevc_launch_motion_pu_wide", [&](hipStream_t s) {
+      return fhevc_launch_motion_pu_wide(fr, search_range, mv_bit_cost_table(qp), nodes, pus, small, c->num_cus, s);
+    });
+  if (nodes || pus) {
+    const int rc = launch_on(c, stream, 11, "fhevc_motion_search_pu_wide (nodes, PUs)", [&](hipStream_t s) {
+      if (big) return fhevc_launch_motion_pu_big(fr, search_range, mv_bit_cost_table(qp), nodes, pus, c->num_cus, s);
+      if (!pus) return fhevc_launch_motion(fr, search_range, mv_cost_table(qp, search_range), nodes, c->num_cus, true, s);
+      return fhevc_launch_motion_pu(fr, search_range, mv_cost_table(qp, search_range), nodes, pus, c->num_cus, true, s);
+    });
+    if (rc != FHEVC_OK) return rc;
+  }
+  if (!small) return FHEVC_OK;
+  return launch_on(c, stream, 11, "fhevc_motion_search_pu_wide (small PUs)", [&](hipStream_t s) {
+    if (big) return fhevc_launch_motion_pu_small_big(fr, search_range, mv_bit_cost_table(qp), small, c->num_cus, s);
+    return fhevc_launch_motion_pu_small(fr, search_range, mv_cost_table(qp, search_range), small, c->num_cus, true, s);
+  });
+}
+
+int fhevc_motion_search_pu_wide(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                                fhevc_motion_node* nodes, fhevc_motion_node* pus, fhevc_motion_node* pus_small)
+{
+  if (!c || !cur_luma || !ref_luma || (!nodes && !pus && !pus_small) || stride_samples < c->cfg.width)
+    return c ? fail(c, FHEVC_E_INVALID, "bad wide PU motion-search arguments") : FHEVC_E_INVALID;
+  if (qp < 0 || qp > 51 || search_range < 1 || search_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad wide PU motion-search arguments");
+  (void)hipSetDevice(c->device);
+  const size_t pu_bytes = (size_t)c->num_ctus * FHEVC_PUS * sizeof(FhevcMotionNode), small_bytes = (size_t)c->num_ctus * FHEVC_PUS_SMALL * sizeof(FhevcMotionNode);
+  if (pus) HIP_TRY(c, ensure(c->d_motion_pu, pu_bytes));
+  if (pus_small) HIP_TRY(c, ensure(c->d_motion_pu_small, small_bytes));
+  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
+  if (rc != FHEVC_OK) return rc;
+  rc = fhevc_motion_search_pu_wide_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, search_range,
+                                          nodes ? reinterpret_cast<fhevc_motion_node*>(c->d_motion) : nullptr, pus ? reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu) : nullptr,
+                                          pus_small ? reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu_small) : nullptr, c->stream);
+  if (rc != FHEVC_OK) return rc;
+  if (nodes) HIP_TRY(c, hipMemcpyAsync(nodes, c->d_motion, motion_bytes(c), hipMemcpyDeviceToHost, c->stream));
+  if (pus) HIP_TRY(c, hipMemcpyAsync(pus, c->d_motion_pu, pu_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (pus_small) HIP_TRY(c, hipMemcpyAsync(pus_small, c->d_motion_pu_small, small_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->stats.bytes_d2h += (nodes ? (uint64_t)motion_bytes(c) : 0) + (pus ? (uint64_t)pu_bytes : 0) + (pus_small ? (uint64_t)small_bytes : 0);
   return FHEVC_OK;
 }
 

@@ -49,8 +49,8 @@ struct fhevc_ctx {
   bool timing = false;
   std::vector<TimedLaunch> pending;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-  double sum_ms[11] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-  uint64_t launches[11] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+  double sum_ms[12] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+  uint64_t launches[12] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
   double* d_act = nullptr;
   int16_t* d_pair = nullptr;          // two staging planes (reference, current) of fhevc_motion_search
   FhevcMotionNode* d_motion = nullptr;

@@ -44,6 +44,7 @@ struct FhevcKnobs {
   bool layers_no_dbuf = false;  // FHEVC_LAYERS_NO_DBUF: the layer path's single-buffered staging (tests)
   size_t layers_lds_limit = 80 * 1024;  // FHEVC_LAYERS_LDS_KB (experiments)
   int layers_grid = 2048;       // FHEVC_LAYERS_GRID (experiments)
+  bool pu_wide_generic = false; // FHEVC_PU_WIDE=generic: fhevc_motion_search_pu_wide sends 8-bit int16 planes down the generic MR = 64 kernels instead of k_motion_pu_wide.hip (tests, A/B)
 };
 FhevcKnobs fhevc_read_knobs();
 
@@ -181,12 +182,32 @@ hipError_t fhevc_launch_motion_pu(const FhevcFrames& fr, int range, const FhevcM
 // fhevc_motion_pu_small_index
 hipError_t fhevc_launch_motion_pu_small(const FhevcFrames& fr, int range, const FhevcMvCost& mvc, FhevcMotionNode* d_pus, int num_cus, bool sad, hipStream_t stream);
 
-// ---- quarter-sample refinement of the search's vectors (k_motion_refine.hip; config 4) --------------------------
-struct FhevcMotionQpelNode { uint32_t satd_int, satd_best, cost_best; int16_t mvx, mvy; };
 // getCost(bits) for every number of bits two exp-Golomb components of a quarter-sample vector up to +-(4 * 64 + 3) can take (at most 38), tabulated by
 // the host with HM's doubles; travels by value as a kernel argument, so every launch has its own lambda
 #define FHEVC_MV_BIT_COSTS 40
 struct FhevcMvBitCost { uint32_t c[FHEVC_MV_BIT_COSTS]; };
+// the exp-Golomb bits of a WHOLE-sample vector component v at iCostScale 2 (TComRdCost.h:166-174, xGetComponentBits of v << 2): 2 floor(log2 t) + 1 with
+// t = v <= 0 ? (-v << 3) + 1 : v << 3; at most 19 for +-64.  The cost of a whole-sample vector with a zero predictor is c[bits(dx) + bits(dy)]: the searches
+// at HM's SearchRange need no table of (2 R + 1)^2 vector costs
+__host__ __device__ inline int fhevc_mv_component_bits(int v)
+{
+  const unsigned t = v <= 0 ? ((unsigned)(-v) << 3) + 1u : (unsigned)v << 3;
+  return 2 * (31 - __builtin_clz(t)) + 1;
+}
+
+// ---- the three searches at HM's own SearchRange, SAD, any bit depth (the MR = 64 layouts of k_motion_pu.hip and k_motion_pu_small.hip; behind
+// fhevc_motion_search_pu_wide).  range 1 .. FHEVC_MOTION_WIDE_MAX_RANGE; cost: the bit costs of the launch's QP, by value -- no table in HBM, nothing kept
+// between calls.  d_nodes / d_pus: as fhevc_launch_motion_pu, either may be null (not both); d_pus of the small form as fhevc_launch_motion_pu_small ----
+hipError_t fhevc_launch_motion_pu_big(const FhevcFrames& fr, int range, const FhevcMvBitCost& cost, FhevcMotionNode* d_nodes, FhevcMotionNode* d_pus, int num_cus,
+                                      hipStream_t stream);
+hipError_t fhevc_launch_motion_pu_small_big(const FhevcFrames& fr, int range, const FhevcMvBitCost& cost, FhevcMotionNode* d_pus, int num_cus, hipStream_t stream);
+// ... and for 8-bit content on byte SADs (k_motion_pu_wide.hip, the layout of k_motion_wide.hip): range 3 .. 64; any of the three outputs may be null (not all);
+// one launch, instantiated for the families asked for
+hipError_t fhevc_launch_motion_pu_wide(const FhevcFrames& fr, int range, const FhevcMvBitCost& cost, FhevcMotionNode* d_nodes, FhevcMotionNode* d_pus, FhevcMotionNode* d_pus_small,
+                                       int num_cus, hipStream_t stream);
+
+// ---- quarter-sample refinement of the search's vectors (k_motion_refine.hip; config 4) --------------------------
+struct FhevcMotionQpelNode { uint32_t satd_int, satd_best, cost_best; int16_t mvx, mvy; };
 // fr as fhevc_launch_motion; d_nodes: what it wrote for the same frames and band (only mvx / mvy are read; |component| > max_range: the marker);
 // d_out: (num_frames - 1) * band CTUs * 85
 hipError_t fhevc_launch_motion_refine(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_nodes, FhevcMotionQpelNode* d_out,

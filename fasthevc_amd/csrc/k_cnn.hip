@@ -1710,6 +1710,7 @@ FhevcKnobs fhevc_read_knobs()
   if (const char* lg = std::getenv("FHEVC_LAYERS_GRID")) k.layers_grid = std::atoi(lg);
   if (const char* tr = std::getenv("FHEVC_CNN_TRIO")) k.trio = tr[0] != '0';
   if (const char* rq = std::getenv("FHEVC_D2_REQUANT")) k.d2_requant_general = std::strcmp(rq, "general") == 0;
+  if (const char* pw = std::getenv("FHEVC_PU_WIDE")) k.pu_wide_generic = std::strcmp(pw, "generic") == 0;
   return k;
 }
 

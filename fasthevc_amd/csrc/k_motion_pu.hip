@@ -15,13 +15,17 @@
 // part is the node's sum minus the quarter.  Every lane keeps the running best (cost, vector index) of the PU that CONTAINS ITS TILE, for each
 // of its 14 shapes, next to the four squares; the distortion at the best vector is cost - vector cost, so it has no register of its own.
 // When d_nodes is given the 85 square nodes are written too, byte for byte what fhevc_motion_kernel writes.
+//
+// MR = 64 (fhevc_launch_motion_pu_big; SAD only, behind fhevc_motion_search_pu_wide): the same kernel laid out for HM's own SearchRange, as
+// fhevc_motion_kernel<.., 64> of k_motion.hip is -- the window in 76.8 KB of dynamic LDS, and no table of (2 R + 1)^2 vector costs anywhere: the cost of
+// a vector comes from the bits of its components (search_vector_bits) and the 40 bit costs that travel with the launch, so nothing is kept between
+// calls.  Which of the two families (the 85 nodes, the 124 PUs) a launch delivers is a template argument there (FAM): the slots of a family that is
+// not asked for do not exist.
 #include "fhevc_internal.h"
 #include "k_search_tile.h"
 
 namespace {
 
-using Geom = SearchGeom<FHEVC_MOTION_MAX_RANGE>;
-constexpr int RP = Geom::RP;
 constexpr int SLOTS = 18;                      // per lane: 4 squares, 6 shapes of the 64x64 node, 6 of its 32x32 node, 2 of its 16x16 node
 constexpr int ENTRIES = FHEVC_NODES + FHEVC_PUS;  // per CTU in the merge arrays: the nodes, then the PUs in output order
 
@@ -54,20 +58,33 @@ __device__ __forceinline__ int slot_entry(int slot, int tx, int ty, bool& rep)
   return FHEVC_NODES + (L < 2 ? k * 12 : 60 + (k - 5) * 4) + s * 2 + part;
 }
 
-// T = int16_t (HM Pel planes) or uint8_t; PACKED = bit depth <= 10; SAD: as fhevc_motion_kernel
-template <typename T, bool PACKED, bool SAD>
-__global__ __launch_bounds__(256, (PACKED ? 3 : 2)) void fhevc_motion_pu_kernel(FhevcFrames F, int range, FhevcMvCost mvc, FhevcMotionNode* __restrict__ out_nodes,
-                                                             FhevcMotionNode* __restrict__ out_pus)
+// the vector costs of a launch: the window's own table at MR = 8, the cost of every number of bits at MR = 64 (by value either way)
+template <int MR> using SearchCosts = typename std::conditional<(MR > FHEVC_MOTION_MAX_RANGE), FhevcMvBitCost, FhevcMvCost>::type;
+
+// T = int16_t (HM Pel planes) or uint8_t; PACKED = bit depth <= 10; SAD: as fhevc_motion_kernel; MR: the largest range the layout holds (8 or 64);
+// FAM: 0 = the 124 PUs, and the 85 nodes where out_nodes is given (MR = 8); otherwise the families of this instantiation, 1 = nodes | 2 = PUs
+template <typename T, bool PACKED, bool SAD, int MR = FHEVC_MOTION_MAX_RANGE, int FAM = 0>
+__global__ __launch_bounds__(256, (MR > FHEVC_MOTION_MAX_RANGE ? 1 : PACKED ? 3 : 2)) void fhevc_motion_pu_kernel(FhevcFrames F, int range, SearchCosts<MR> mvc,
+                                                             FhevcMotionNode* __restrict__ out_nodes, FhevcMotionNode* __restrict__ out_pus)
 {
-  __shared__ __attribute__((aligned(16))) short s_ref[Geom::REF_SAMPLES];
-  __shared__ unsigned s_cost[4][ENTRIES], s_idx[4][ENTRIES], s_zero[ENTRIES], s_vc[Geom::NMV_MAX];
+  using Geom = SearchGeom<MR>;
+  constexpr int RP = Geom::RP;
+  constexpr bool BIG = MR > FHEVC_MOTION_MAX_RANGE;
+  extern __shared__ __attribute__((aligned(16))) short s_dyn[];
+  __shared__ __attribute__((aligned(16))) short s_small[BIG ? 8 : Geom::REF_SAMPLES];
+  short* const s_ref = BIG ? s_dyn : s_small;
+  __shared__ unsigned s_cost[4][ENTRIES], s_idx[4][ENTRIES], s_zero[ENTRIES], s_vc[BIG ? FHEVC_MV_BIT_COSTS : Geom::NMV_MAX];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int tx = lane & 7, ty = lane >> 3;
   const SearchRange R(range);
   const int total = SearchWork::total(F), nmv = R.nmv, centre = R.centre;
   const int shift = F.bit_depth - 8;
-  const bool want_nodes = out_nodes != nullptr;
+  const bool want_nodes = FAM ? (FAM & 1) != 0 : out_nodes != nullptr;
+  constexpr bool want_pus = FAM == 0 || (FAM & 2) != 0;
   const T* plane = reinterpret_cast<const T*>(F.luma);
+  if constexpr (BIG) {
+    if (tid < FHEVC_MV_BIT_COSTS) s_vc[tid] = mvc.c[tid];  // visible behind the first barrier of the CTU loop
+  }
 
   for (int work = blockIdx.x; work < total; work += gridDim.x) {
     const SearchWork W(F, work);
@@ -115,11 +132,15 @@ __global__ __launch_bounds__(256, (PACKED ? 3 : 2)) void fhevc_motion_pu_kernel(
         d[14] = (tx & 3) == 0 ? left : s32 - left;   d[15] = (tx & 3) == 3 ? right : s32 - right;
       }
       d[16] = h16x8; d[17] = v8x16;
-      const unsigned vc = mvc.c[m];
-      if (lane == 0) s_vc[m] = vc;  // the merge looks the winner's vector cost up by a per-thread index (every m is one wave's)
+      unsigned vc;
+      if constexpr (BIG) vc = s_vc[search_vector_bits(m, R)];
+      else {
+        vc = mvc.c[m];
+        if (lane == 0) s_vc[m] = vc;  // the merge looks the winner's vector cost up by a per-thread index (every m is one wave's)
+      }
 #pragma unroll
       for (int k = 0; k < SLOTS; ++k) {
-        if (k < 4 && !want_nodes) continue;
+        if (k < 4 ? !want_nodes : !want_pus) continue;
         const unsigned c = (d[k] >> shift) + vc;  // DISTORTION_PRECISION_ADJUSTMENT on the block's sum, once (TComRdCost.cpp:1823)
         if (c < bc[k]) { bc[k] = c; bi[k] = (unsigned)m; }
       }
@@ -130,6 +151,7 @@ __global__ __launch_bounds__(256, (PACKED ? 3 : 2)) void fhevc_motion_pu_kernel(
         for (int k = 0; k < SLOTS; ++k) {
           bool rep;
           const int e = slot_entry(k, txo, tyo, rep);
+          if (FAM && (k < 4 ? !want_nodes : !want_pus)) continue;
           if (rep) s_zero[e] = d[k] >> shift;
         }
       }
@@ -140,10 +162,11 @@ __global__ __launch_bounds__(256, (PACKED ? 3 : 2)) void fhevc_motion_pu_kernel(
     for (int k = 0; k < SLOTS; ++k) {
       bool rep;
       const int e = slot_entry(k, txo, tyo, rep);
+      if (FAM && (k < 4 ? !want_nodes : !want_pus)) continue;
       if (rep) { s_cost[wave][e] = bc[k]; s_idx[wave][e] = bi[k]; }
     }
     __syncthreads();
-    if (tid < ENTRIES && (want_nodes || tid >= FHEVC_NODES)) {
+    if (tid < ENTRIES && (tid < FHEVC_NODES ? want_nodes : want_pus)) {
       // the CU node this entry belongs to: a PU is valid iff its node lies wholly inside the picture
       const int p = tid - FHEVC_NODES;
       const int node = p < 0 ? tid : p < 60 ? p / 12 : 5 + (p - 60) / 4;
@@ -154,7 +177,7 @@ __global__ __launch_bounds__(256, (PACKED ? 3 : 2)) void fhevc_motion_pu_kernel(
       if (search_node_inside(F, cx, cy, ni % cnt, ni / cnt, n)) {
         unsigned c, ix;
         search_merge(&s_cost[0][0], &s_idx[0][0], ENTRIES, tid, c, ix);
-        o = search_record(s_zero[tid], c, s_vc[ix], ix, R);
+        o = search_record(s_zero[tid], c, s_vc[BIG ? search_vector_bits((int)ix, R) : (int)ix], ix, R);
       }
       FhevcMotionNode* dst = p < 0 ? out_nodes + W.oc(F) * FHEVC_NODES + tid : out_pus + W.oc(F) * FHEVC_PUS + p;
       *reinterpret_cast<uint4*>(dst) = o;  // one 16-byte store per entry
@@ -173,5 +196,28 @@ hipError_t fhevc_launch_motion_pu(const FhevcFrames& fr, int range, const FhevcM
   return search_launch(fr, range >= 1 && range <= FHEVC_MOTION_MAX_RANGE && d_pus, num_cus, 3, 2, sad, [&](auto t, auto packed, auto sad_c, int grid) {
     hipLaunchKernelGGL((fhevc_motion_pu_kernel<decltype(t), decltype(packed)::value, decltype(sad_c)::value>), dim3(grid), dim3(256), 0, stream, fr, range, mvc, d_nodes, d_pus);
     return hipSuccess;
+  });
+}
+
+// search ranges up to 64 in the SAD mode (HM's integer-search distortion), any bit depth: the MR = 64 layout.  The window (76 816 B) and the merge
+// arrays are more than half of a CU's 160 KB of LDS: one workgroup per CU.  Either output may be null, not both
+hipError_t fhevc_launch_motion_pu_big(const FhevcFrames& fr, int range, const FhevcMvBitCost& cost, FhevcMotionNode* d_nodes, FhevcMotionNode* d_pus, int num_cus,
+                                      hipStream_t stream)
+{
+  constexpr int MRB = FHEVC_MOTION_WIDE_MAX_RANGE;
+  const size_t lds = (size_t)SearchGeom<MRB>::REF_SAMPLES * sizeof(short);
+  return search_launch(fr, range >= 1 && range <= MRB && (d_nodes || d_pus), num_cus, 1, 1, true, [&](auto t, auto packed, auto sad_c, int grid) {
+    if constexpr (decltype(sad_c)::value) {
+      auto go = [&](auto kernel) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, stream, fr, range, cost, d_nodes, d_pus);
+        return hipSuccess;
+      };
+      using T = decltype(t);
+      constexpr bool P = decltype(packed)::value;
+      if (d_nodes && d_pus) return go(&fhevc_motion_pu_kernel<T, P, true, MRB, 3>);
+      return d_pus ? go(&fhevc_motion_pu_kernel<T, P, true, MRB, 2>) : go(&fhevc_motion_pu_kernel<T, P, true, MRB, 1>);
+    } else return hipErrorInvalidValue;
   });
 }

@@ -18,13 +18,14 @@
 //   p = 0: 2NxnU (top strip, + lane 1's top)      p = 1: nRx2N (right strip, + lane 3's right)
 //   p = 2: nLx2N (left strip, + lane 0's left)    p = 3: 2NxnD (bottom strip, + lane 2's bottom)
 // so every lane keeps six running (cost, vector index) pairs, all of entries it alone owns; the distortion at the best vector is cost - vector cost.
+//
+// MR = 64 (fhevc_launch_motion_pu_small_big; SAD only, behind fhevc_motion_search_pu_wide): the same kernel laid out for HM's own SearchRange, as
+// k_motion_pu.hip's -- the window in dynamic LDS, the vector cost from the bits of the components and the 40 bit costs of the launch.
 #include "fhevc_internal.h"
 #include "k_search_tile.h"
 
 namespace {
 
-using Geom = SearchGeom<FHEVC_MOTION_MAX_RANGE>;
-constexpr int RP = Geom::RP;
 constexpr int SLOTS = 6;                       // per lane: 8x4 top, 8x4 bottom, 4x8 left, 4x8 right of its tile; part 0 and part 1 of its AMP shape
 constexpr int ENTRIES = FHEVC_PUS_SMALL;
 constexpr int AMP_ENTRIES = 128;               // 16 nodes x 4 shapes x 2 parts, then 64 tiles x 2 shapes x 2 parts
@@ -36,12 +37,21 @@ __device__ __forceinline__ unsigned quad(unsigned v)
   return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, P0 | (P1 << 2) | (P2 << 4) | (P3 << 6), 0xF, 0xF, false);
 }
 
-// T = int16_t (HM Pel planes) or uint8_t; PACKED = bit depth <= 10; SAD: as fhevc_motion_kernel
-template <typename T, bool PACKED, bool SAD>
-__global__ __launch_bounds__(256, (PACKED ? 4 : 3)) void fhevc_motion_pu_small_kernel(FhevcFrames F, int range, FhevcMvCost mvc, FhevcMotionNode* __restrict__ out_pus)
+// the vector costs of a launch: the window's own table at MR = 8, the cost of every number of bits at MR = 64 (by value either way)
+template <int MR> using SearchCosts = typename std::conditional<(MR > FHEVC_MOTION_MAX_RANGE), FhevcMvBitCost, FhevcMvCost>::type;
+
+// T = int16_t (HM Pel planes) or uint8_t; PACKED = bit depth <= 10; SAD: as fhevc_motion_kernel; MR: the largest range the layout holds (8 or 64)
+template <typename T, bool PACKED, bool SAD, int MR = FHEVC_MOTION_MAX_RANGE>
+__global__ __launch_bounds__(256, (MR > FHEVC_MOTION_MAX_RANGE ? 1 : PACKED ? 4 : 3)) void fhevc_motion_pu_small_kernel(FhevcFrames F, int range, SearchCosts<MR> mvc,
+                                                                                                         FhevcMotionNode* __restrict__ out_pus)
 {
-  __shared__ __attribute__((aligned(16))) short s_ref[Geom::REF_SAMPLES];
-  __shared__ unsigned s_cost[4][ENTRIES], s_idx[4][ENTRIES], s_zero[ENTRIES], s_vc[Geom::NMV_MAX];
+  using Geom = SearchGeom<MR>;
+  constexpr int RP = Geom::RP;
+  constexpr bool BIG = MR > FHEVC_MOTION_MAX_RANGE;
+  extern __shared__ __attribute__((aligned(16))) short s_dyn[];
+  __shared__ __attribute__((aligned(16))) short s_small[BIG ? 8 : Geom::REF_SAMPLES];
+  short* const s_ref = BIG ? s_dyn : s_small;
+  __shared__ unsigned s_cost[4][ENTRIES], s_idx[4][ENTRIES], s_zero[ENTRIES], s_vc[BIG ? FHEVC_MV_BIT_COSTS : Geom::NMV_MAX];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int quad_pos = lane & 3, node16 = lane >> 2;  // the tile's place in its 16x16 node (bit 0: right, bit 1: lower), the node (raster 4x4)
   const int tx = (node16 & 3) * 2 + (quad_pos & 1), ty = (node16 >> 2) * 2 + (quad_pos >> 1);
@@ -53,6 +63,9 @@ __global__ __launch_bounds__(256, (PACKED ? 4 : 3)) void fhevc_motion_pu_small_k
   const int total = SearchWork::total(F), nmv = R.nmv, centre = R.centre;
   const int shift = F.bit_depth - 8;
   const T* plane = reinterpret_cast<const T*>(F.luma);
+  if constexpr (BIG) {
+    if (tid < FHEVC_MV_BIT_COSTS) s_vc[tid] = mvc.c[tid];  // visible behind the first barrier of the CTU loop
+  }
 
   for (int work = blockIdx.x; work < total; work += gridDim.x) {
     const SearchWork W(F, work);
@@ -121,8 +134,12 @@ __global__ __launch_bounds__(256, (PACKED ? 4 : 3)) void fhevc_motion_pu_small_k
       const unsigned strip = own + quad<1, 3, 0, 2>(give);
       d[4] = strip_is_part0 ? strip : s16 - strip;
       d[5] = s16 - d[4];
-      const unsigned vc = mvc.c[m];
-      if (lane == 0) s_vc[m] = vc;  // the merge looks the winner's vector cost up by a per-thread index (every m is one wave's)
+      unsigned vc;
+      if constexpr (BIG) vc = s_vc[search_vector_bits(m, R)];
+      else {
+        vc = mvc.c[m];
+        if (lane == 0) s_vc[m] = vc;  // the merge looks the winner's vector cost up by a per-thread index (every m is one wave's)
+      }
 #pragma unroll
       for (int k = 0; k < SLOTS; ++k) {
         const unsigned c = (d[k] >> shift) + vc;  // DISTORTION_PRECISION_ADJUSTMENT on the block's sum, once (TComRdCost.cpp:1823)
@@ -147,7 +164,7 @@ __global__ __launch_bounds__(256, (PACKED ? 4 : 3)) void fhevc_motion_pu_small_k
       if (search_node_inside(F, cx, cy, ni % cnt, ni / cnt, n)) {
         unsigned c, ix;
         search_merge(&s_cost[0][0], &s_idx[0][0], ENTRIES, e, c, ix);
-        o = search_record(s_zero[e], c, s_vc[ix], ix, R);
+        o = search_record(s_zero[e], c, s_vc[BIG ? search_vector_bits((int)ix, R) : (int)ix], ix, R);
       }
       *reinterpret_cast<uint4*>(out_pus + W.oc(F) * ENTRIES + e) = o;  // one 16-byte store per entry
     }
@@ -164,5 +181,21 @@ hipError_t fhevc_launch_motion_pu_small(const FhevcFrames& fr, int range, const 
   return search_launch(fr, range >= 1 && range <= FHEVC_MOTION_MAX_RANGE && d_pus, num_cus, 4, 3, sad, [&](auto t, auto packed, auto sad_c, int grid) {
     hipLaunchKernelGGL((fhevc_motion_pu_small_kernel<decltype(t), decltype(packed)::value, decltype(sad_c)::value>), dim3(grid), dim3(256), 0, stream, fr, range, mvc, d_pus);
     return hipSuccess;
+  });
+}
+
+// search ranges up to 64 in the SAD mode, any bit depth: the MR = 64 layout (window 76 816 B + merge 13 824 B of LDS: one workgroup per CU)
+hipError_t fhevc_launch_motion_pu_small_big(const FhevcFrames& fr, int range, const FhevcMvBitCost& cost, FhevcMotionNode* d_pus, int num_cus, hipStream_t stream)
+{
+  constexpr int MRB = FHEVC_MOTION_WIDE_MAX_RANGE;
+  const size_t lds = (size_t)SearchGeom<MRB>::REF_SAMPLES * sizeof(short);
+  return search_launch(fr, range >= 1 && range <= MRB && d_pus, num_cus, 1, 1, true, [&](auto t, auto packed, auto sad_c, int grid) {
+    if constexpr (decltype(sad_c)::value) {
+      const auto kernel = &fhevc_motion_pu_small_kernel<decltype(t), decltype(packed)::value, true, MRB>;
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, stream, fr, range, cost, d_pus);
+      return hipSuccess;
+    } else return hipErrorInvalidValue;
   });
 }

@@ -36,6 +36,13 @@ struct SearchRange {
   }
 };
 
+// ---- the vector cost without a table per window (the MR = 64 layouts: (2 * 64 + 1)^2 entries would be 66 KB): the bits of vector m of the window in
+// raster order, the index into the launch's FhevcMvBitCost (fhevc_mv_component_bits) ----
+__device__ __forceinline__ int search_vector_bits(int m, const SearchRange& R)
+{
+  return fhevc_mv_component_bits(m % R.side - R.range) + fhevc_mv_component_bits(m / R.side - R.range);
+}
+
 // work item = one CTU of frame f >= 1 of the band, searched in frame f - 1; oc(): its index in the outputs
 struct SearchWork {
   int f, cy, cx;

@@ -332,7 +332,8 @@ int  fhevc_motion_refine_device(fhevc_ctx* ctx, const void* d_luma, int sample_b
  *   nodes k = 0..4:   entry k * 12 + shape * 2 + part             nodes k = 5..20:  entry 60 + (k - 5) * 4 + shape * 2 + part
  * which is what fhevc_motion_pu_index returns (-1 for a combination that is not covered; it needs no context).
  * NOT covered by this entry point: AMP of 16x16 CUs (16x4 PUs need 4x4 Hadamards) and the 8x4 and 4x8 PUs of 8x8 CUs -- those are
- * fhevc_motion_search_pu_small's, below.  NOT covered by either, on purpose: search ranges above 8 (the wide kernels serve squares only); a
+ * fhevc_motion_search_pu_small's, below.  NOT covered by either: search ranges above 8 -- those are fhevc_motion_search_pu_wide's, further below
+ * (SAD only, up to HM's own SearchRange 64); a
  * predictor other than zero (HM's second PU sees the first PU's vector as a candidate, this source-only twin does not).
  * An entry is a fhevc_motion_node.  A PU is valid iff its CU NODE lies wholly inside the picture (HM never codes a partitioned CU that crosses the
  * edge); otherwise the three distortion fields hold 0xFFFFFFFF and the vector is zero, as for nodes.  The encoder hook does not consume this
@@ -370,7 +371,8 @@ int  fhevc_motion_search_pu(fhevc_ctx* ctx, const int16_t* cur_luma, const int16
  *   nodes k = 21..84 (8x8),  shapes 0..1:  entry 128 + (k - 21) * 4 + shape * 2 + part           128..383
  * which is what fhevc_motion_pu_small_index returns (-1 for anything else; it needs no context).  A PU is valid iff its CU NODE lies wholly inside
  * the picture; otherwise the three distortion fields hold 0xFFFFFFFF and the vector is zero, as for nodes and for the 124 PUs.  Still left out, on
- * purpose: search ranges above 8, predictors other than zero.  The encoder hook does not consume this output. */
+ * purpose: search ranges above 8, predictors other than zero.  (The ranges above 8 are fhevc_motion_search_pu_wide's, below, in SAD mode.)  The
+ * encoder hook does not consume this output. */
 #define FHEVC_PUS_SMALL_PER_CTU 384
 int  fhevc_motion_pu_small_index(int node, int shape, int part);
 /* device-resident batch; layout, band and stream arguments as fhevc_motion_search_pu_device; frame f >= 1 searched in f-1.
@@ -384,6 +386,36 @@ int  fhevc_motion_search_pu_small_device(fhevc_ctx* ctx, const void* d_luma, int
 /* one picture pair, host buffers, synchronous */
 int  fhevc_motion_search_pu_small(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
                                   fhevc_motion_node* pus);
+
+/* The three integer searches at HM's own SearchRange: the 85 nodes, the 124 PUs and the 384 small PUs of every CTU from ONE entry point, for
+ * search_range 1..64.  Per entry exactly the search fhevc_motion_search defines in its SAD mode: full search over [-search_range, search_range]^2 in
+ * the previous ORIGINAL picture, border replicated, raster order, strict "<", zero predictor (iCostScale 2, the lambda of slice QP qp), distortion =
+ * the SAD of the whole w x h block shifted ONCE by bit_depth - 8.  The distortion is ALWAYS SAD, whatever fhevc_set_motion_distortion says: that
+ * is HM's integer-search distortion (xPatternSearch's setDistParam selects DF_SAD), the only one the reference pins, and what the square search
+ * requires above +-8 too.  Each of the three outputs may be NULL, at least one must be given; a family that is not asked for is not computed:
+ *   d_nodes      85 per CTU, byte for byte what fhevc_motion_search_device writes in SAD mode for the same arguments
+ *   d_pus        FHEVC_PUS_PER_CTU per CTU in fhevc_motion_pu_index order, what fhevc_motion_search_pu_device writes in SAD mode up to range 8
+ *   d_pus_small  FHEVC_PUS_SMALL_PER_CTU per CTU in fhevc_motion_pu_small_index order, likewise
+ * Validity, markers, the compact-over-band layout and the exact write extent are those of the PU searches above.  Ranges up to 8 run the kernels of
+ * those entry points.  Above, 8-bit contexts (int16 or uint8 planes) run k_motion_pu_wide.hip, the byte-SAD layout of the square wide search
+ * (v_qsad_pk_u16_u8; quadrant SADs per tile, running sums per level), in one launch instantiated for the families asked for; contexts above 8 bit
+ * run the kernels of the PU searches laid out for a window of up to 192 x 192 samples in LDS (k_motion_pu.hip, k_motion_pu_small.hip at MR = 64),
+ * one launch for nodes and PUs and one for the small PUs; FHEVC_PU_WIDE=generic in the environment of fhevc_create sends 8-bit int16 planes down
+ * that path too (tests, A/B timing; the bytes are the same).  NO state is kept between
+ * calls and nothing is synchronised: the vector cost depends only on the exp-Golomb bits of the two components, 2 floor(log2 t) + 1 with
+ * t = v <= 0 ? (-v << 3) + 1 : v << 3, and the cost of every number of bits travels by value with the launch -- unlike fhevc_motion_search_device
+ * above +-8, whose per-context table of vector costs blocks the host when (qp, search_range) changes.  Two calls with different QPs and ranges may be
+ * in flight on two streams.  Asynchronous with respect to the host, allocates nothing.  An empty band writes nothing.  FHEVC_E_INVALID with a
+ * fhevc_last_error text (nothing is launched or written): a null context or d_luma, all three outputs null, num_frames < 2, qp outside 0..51,
+ * search_range outside 1..64, stride_samples < width, a bad band, uint8 planes on a context above 8 bit.  Not covered: the quarter-sample refinement
+ * of PU vectors beyond +-8 (fhevc_motion_refine_pu marks them), SATD at integer positions above +-8, predictors other than zero.  The encoder hook
+ * does not consume this output. */
+int  fhevc_motion_search_pu_wide_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                        int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range,
+                                        fhevc_motion_node* d_nodes, fhevc_motion_node* d_pus, fhevc_motion_node* d_pus_small, void* stream);
+/* one picture pair, host buffers, synchronous; each output may be NULL, not all three */
+int  fhevc_motion_search_pu_wide(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                                 fhevc_motion_node* nodes, fhevc_motion_node* pus, fhevc_motion_node* pus_small);
 
 /* Quarter-sample refinement of the PUs' vectors (k_motion_refine_pu.hip): HM never compares partition shapes at integer positions -- every
  * xMotionEstimation runs TEncSearch::xPatternSearchFracDIF behind the integer search, for every PU, 8x4 and 4x8 included, and xCheckRDCostInter sees each
@@ -500,7 +532,8 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
  * 5 = P-picture depth ranges (fhevc_p_depth_range_device), 6 = first pass of the 4x4 PUs (fhevc_intra_first_pass_4x4*),
  * 7 = quarter-sample motion refinement (fhevc_motion_refine*), 8 = motion search of the rectangular PUs (fhevc_motion_search_pu*),
  * 9 = motion search of the PUs with a 4-sample side (fhevc_motion_search_pu_small*), 10 = quarter-sample refinement of the PUs
- * (fhevc_motion_refine_pu*) */
+ * (fhevc_motion_refine_pu*), 11 = the searches at HM's SearchRange (fhevc_motion_search_pu_wide*: one launch for nodes and PUs, one for the
+ * small PUs, each counted) */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
 int  fhevc_enable_kernel_timing(fhevc_ctx* ctx, int on);
 
