@@ -36,6 +36,7 @@ SYMBOLS = [
     "fhevc_motion_search_pu_small", "fhevc_motion_search_pu_small_device", "fhevc_motion_pu_small_index",
     "fhevc_motion_refine_pu", "fhevc_motion_refine_pu_device",
     "fhevc_motion_search_pu_wide", "fhevc_motion_search_pu_wide_device",
+    "fhevc_motion_refine_pu_wide", "fhevc_motion_refine_pu_wide_device",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -197,6 +198,8 @@ def load_library(path=None):
     lib.fhevc_alloc_host.restype = vp
     lib.fhevc_free_host.argtypes = [vp, vp]
     lib.fhevc_free_host.restype = None
+    lib.fhevc_motion_refine_pu_wide.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.fhevc_motion_refine_pu_wide_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     lib.fhevc_kernel_timing.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     lib.fhevc_enable_kernel_timing.argtypes = [vp, C.c_int]
     lib.fhevc_get_stats.argtypes = [vp, vp, C.c_size_t]
@@ -528,6 +531,35 @@ class Context:
         rb, re = rows if rows is not None else (0, self.ctus_y)
         self._check(self.lib.fhevc_motion_refine_pu_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range,
                                                            d_pus, d_out_pus, d_pus_small, d_out_pus_small, stream))
+
+    def motion_refine_pu_wide(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, max_range=64, nodes=None, pus=None, pus_small=None):
+        """config 4: the quarter-sample refinements of motion_refine and motion_refine_pu at max_range 1..64 from one call: nodes [numCtus, 85], pus
+        [numCtus, 124] and / or pus_small [numCtus, 384] (MOTION_DTYPE, as motion_search_pu_wide returns them for the same planes; only mvx / mvy are
+        read) -> (out_nodes, out_pus, out_pus_small) of MOTION_QPEL_DTYPE in the same layouts, None for a family not given (at least one must be)."""
+        cur = np.ascontiguousarray(cur_plane).reshape(-1)
+        ref = np.ascontiguousarray(ref_plane).reshape(-1)
+        assert cur.dtype == np.int16 and ref.dtype == np.int16
+        stride = stride if stride is not None else cur_plane.shape[-1]
+        ins, outs = [], []
+        for a, per_ctu in ((nodes, NODES_PER_CTU), (pus, PUS_PER_CTU), (pus_small, PUS_SMALL_PER_CTU)):
+            if a is not None:
+                a = np.ascontiguousarray(a).reshape(-1)
+                assert a.dtype.itemsize == 16 and a.size == self.num_ctus * per_ctu
+            ins.append(a)
+            outs.append(None if a is None else np.zeros(self.num_ctus * per_ctu, MOTION_QPEL_DTYPE))
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._check(self.lib.fhevc_motion_refine_pu_wide(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, max_range,
+                                                         ptr(ins[0]), ptr(outs[0]), ptr(ins[1]), ptr(outs[1]), ptr(ins[2]), ptr(outs[2])))
+        return tuple(None if o is None else o.reshape(self.num_ctus, -1) for o in outs)
+
+    def motion_refine_pu_wide_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_nodes=None, d_out_nodes=None, d_pus=None, d_out_pus=None,
+                                     d_pus_small=None, d_out_pus_small=None, rows=None, stream=None, qp=32, max_range=64):
+        """frames 1.. of the batch, each refined in the frame before it, max_range 1..64, around the vectors of d_nodes / d_pus / d_pus_small (what
+        motion_search_pu_wide_device wrote for the same rows; 85 / 124 / 384 per CTU); the outputs hold as many quarter-sample entries (16 B).  Each
+        family's pair may be None together (not all three).  Asynchronous; keeps no state between calls."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_motion_refine_pu_wide_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range,
+                                                                d_nodes, d_out_nodes, d_pus, d_out_pus, d_pus_small, d_out_pus_small, stream))
 
     def p_depth_range_device(self, d_nodes, d_prev_maps, num_pictures, d_depth_min, d_depth_max=None, rows=None, stream=None, qp=32,
                              prev_mode="colocated", rule=None):

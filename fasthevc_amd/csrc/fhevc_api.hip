@@ -292,7 +292,7 @@ int fhevc_enable_kernel_timing(fhevc_ctx* c, int on)
 
 int fhevc_kernel_timing(fhevc_ctx* c, int which, int reset, double* avg_ms, uint64_t* launches)
 {
-  if (!c || which < 0 || which > 11) return FHEVC_E_INVALID;
+  if (!c || which < 0 || which > 12) return FHEVC_E_INVALID;
   time_resolve(c);
   if (avg_ms) *avg_ms = c->launches[which] ? c->sum_ms[which] / (double)c->launches[which] : 0.0;
   if (launches) *launches = c->launches[which];
@@ -1025,7 +1025,7 @@ int fhevc_motion_refine_pu_device(fhevc_ctx* c, const void* d_luma, int sample_b
   const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
   return launch_on(c, stream, 10, "fhevc_launch_motion_refine_pu", [&](hipStream_t s) {
     return fhevc_launch_motion_refine_pu(fr, max_range, mv_bit_cost_table(qp), reinterpret_cast<const FhevcMotionNode*>(d_pus), reinterpret_cast<FhevcMotionQpelNode*>(d_out_pus),
-                                         reinterpret_cast<const FhevcMotionNode*>(d_pus_small), reinterpret_cast<FhevcMotionQpelNode*>(d_out_pus_small), c->num_cus, s);
+                                         reinterpret_cast<const FhevcMotionNode*>(d_pus_small), reinterpret_cast<FhevcMotionQpelNode*>(d_out_pus_small), c->num_cus, false, s);
   });
 }
 
@@ -1056,6 +1056,88 @@ int fhevc_motion_refine_pu(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
   if (pus_small) HIP_TRY(c, hipMemcpyAsync(out_pus_small, c->d_qpel_pu_small, small_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->stats.bytes_d2h += (uint64_t)(pu_bytes + small_bytes);
+  return FHEVC_OK;
+}
+
+// ---- the two refinements at HM's own SearchRange: what fhevc_motion_search_pu_wide writes feeds straight in (k_motion_refine.hip, k_motion_refine_pu.hip) ----
+
+int fhevc_motion_refine_pu_wide_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                       int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range,
+                                       const fhevc_motion_node* d_nodes, fhevc_motion_qpel_node* d_out_nodes,
+                                       const fhevc_motion_node* d_pus, fhevc_motion_qpel_node* d_out_pus,
+                                       const fhevc_motion_node* d_pus_small, fhevc_motion_qpel_node* d_out_pus_small, void* stream)
+{
+  if (!c) return FHEVC_E_INVALID;
+  // each family's pair may be null together, not all three pairs and not half a pair
+  if (!d_luma || (!d_nodes && !d_pus && !d_pus_small) || !d_nodes != !d_out_nodes || !d_pus != !d_out_pus || !d_pus_small != !d_out_pus_small)
+    return fail(c, FHEVC_E_INVALID, "bad wide PU motion-refinement arguments");
+  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
+  if (max_range < 1 || max_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "the wide PU motion refinement covers vectors of the search ranges 1..64");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
+  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
+  // Nothing of the context is read or written by the launches (the 40 bit costs travel by value): calls on different streams may be in flight together.
+  // The nodes: the square kernel, the launch of fhevc_motion_refine_device; the PUs: one launch for both families, the MR = 8 layout up to +-8 (the launch
+  // of fhevc_motion_refine_pu_device), the MR = 64 layout above.  Each launch is timed and counted under slot 12
+  if (d_nodes) {
+    const int rc = launch_on(c, stream, 12, "fhevc_motion_refine_pu_wide (nodes)", [&](hipStream_t s) {
+      return fhevc_launch_motion_refine(fr, max_range, mv_bit_cost_table(qp), reinterpret_cast<const FhevcMotionNode*>(d_nodes), reinterpret_cast<FhevcMotionQpelNode*>(d_out_nodes),
+                                        c->num_cus, s);
+    });
+    if (rc != FHEVC_OK) return rc;
+  }
+  if (!d_pus && !d_pus_small) return FHEVC_OK;
+  return launch_on(c, stream, 12, "fhevc_motion_refine_pu_wide (PUs)", [&](hipStream_t s) {
+    return fhevc_launch_motion_refine_pu(fr, max_range, mv_bit_cost_table(qp), reinterpret_cast<const FhevcMotionNode*>(d_pus), reinterpret_cast<FhevcMotionQpelNode*>(d_out_pus),
+                                         reinterpret_cast<const FhevcMotionNode*>(d_pus_small), reinterpret_cast<FhevcMotionQpelNode*>(d_out_pus_small), c->num_cus,
+                                         c->knobs.refine_pu_stage_full, s);
+  });
+}
+
+int fhevc_motion_refine_pu_wide(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                                const fhevc_motion_node* nodes, fhevc_motion_qpel_node* out_nodes,
+                                const fhevc_motion_node* pus, fhevc_motion_qpel_node* out_pus,
+                                const fhevc_motion_node* pus_small, fhevc_motion_qpel_node* out_pus_small)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!cur_luma || !ref_luma || (!nodes && !pus && !pus_small) || !nodes != !out_nodes || !pus != !out_pus || !pus_small != !out_pus_small || stride_samples < c->cfg.width)
+    return fail(c, FHEVC_E_INVALID, "bad wide PU motion-refinement arguments");
+  if (qp < 0 || qp > 51 || max_range < 1 || max_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad wide PU motion-refinement arguments");
+  (void)hipSetDevice(c->device);
+  // a quarter-sample entry is as large as an entry of the search; the nodes go in through d_motion (upload_pair allocates it) and come out of d_qpel
+  const size_t node_bytes = nodes ? motion_bytes(c) : 0;
+  const size_t pu_bytes = pus ? (size_t)c->num_ctus * FHEVC_PUS * sizeof(FhevcMotionNode) : 0;
+  const size_t small_bytes = pus_small ? (size_t)c->num_ctus * FHEVC_PUS_SMALL * sizeof(FhevcMotionNode) : 0;
+  if (nodes) HIP_TRY(c, ensure(c->d_qpel, node_bytes));
+  if (pus) { HIP_TRY(c, ensure(c->d_motion_pu, pu_bytes)); HIP_TRY(c, ensure(c->d_qpel_pu, pu_bytes)); }
+  if (pus_small) { HIP_TRY(c, ensure(c->d_motion_pu_small, small_bytes)); HIP_TRY(c, ensure(c->d_qpel_pu_small, small_bytes)); }
+  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
+  if (rc != FHEVC_OK) return rc;
+  if (nodes) HIP_TRY(c, hipMemcpyAsync(c->d_motion, nodes, node_bytes, hipMemcpyHostToDevice, c->stream));
+  if (pus) HIP_TRY(c, hipMemcpyAsync(c->d_motion_pu, pus, pu_bytes, hipMemcpyHostToDevice, c->stream));
+  if (pus_small) HIP_TRY(c, hipMemcpyAsync(c->d_motion_pu_small, pus_small, small_bytes, hipMemcpyHostToDevice, c->stream));
+  c->stats.bytes_h2d += node_bytes + pu_bytes + small_bytes;
+  rc = fhevc_motion_refine_pu_wide_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, max_range,
+                                          nodes ? reinterpret_cast<const fhevc_motion_node*>(c->d_motion) : nullptr, nodes ? reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel) : nullptr,
+                                          pus ? reinterpret_cast<const fhevc_motion_node*>(c->d_motion_pu) : nullptr, pus ? reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu) : nullptr,
+                                          pus_small ? reinterpret_cast<const fhevc_motion_node*>(c->d_motion_pu_small) : nullptr,
+                                          pus_small ? reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu_small) : nullptr, c->stream);
+  if (rc != FHEVC_OK) return rc;
+  if (nodes) HIP_TRY(c, hipMemcpyAsync(out_nodes, c->d_qpel, node_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (pus) HIP_TRY(c, hipMemcpyAsync(out_pus, c->d_qpel_pu, pu_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (pus_small) HIP_TRY(c, hipMemcpyAsync(out_pus_small, c->d_qpel_pu_small, small_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->stats.bytes_d2h += (uint64_t)(node_bytes + pu_bytes + small_bytes);
+  return FHEVC_OK;
+}
+
+// measurement tools only (tools/motion_refine_pu_wide_bench.py; not in fasthevc.h): what hipOccupancyMaxActiveBlocksPerMultiprocessor answers for the MR = 64
+// instance of k_motion_refine_pu.hip that planes of sample_bytes take on this context, and the cap of its persistent grid
+int fhevc_debug_refine_pu_wide_residency(fhevc_ctx* c, int sample_bytes, int* blocks_per_cu, int* grid_cap)
+{
+  if (!c || !blocks_per_cu || !grid_cap || (sample_bytes != 1 && sample_bytes != 2)) return FHEVC_E_INVALID;
+  (void)hipSetDevice(c->device);
+  HIP_TRY(c, fhevc_motion_refine_pu_big_residency(sample_bytes, c->cfg.bit_depth, blocks_per_cu));
+  *grid_cap = (*blocks_per_cu < 2 ? *blocks_per_cu : 2) * c->num_cus;
   return FHEVC_OK;
 }
 

@@ -44,6 +44,7 @@ struct FhevcKnobs {
   bool layers_no_dbuf = false;  // FHEVC_LAYERS_NO_DBUF: the layer path's single-buffered staging (tests)
   size_t layers_lds_limit = 80 * 1024;  // FHEVC_LAYERS_LDS_KB (experiments)
   int layers_grid = 2048;       // FHEVC_LAYERS_GRID (experiments)
+  bool refine_pu_stage_full = false; // FHEVC_REFINE_PU_STAGE=full: the MR = 64 layout of k_motion_refine_pu.hip stages its whole window whatever max_range is (tests, A/B)
   bool pu_wide_generic = false; // FHEVC_PU_WIDE=generic: fhevc_motion_search_pu_wide sends 8-bit int16 planes down the generic MR = 64 kernels instead of k_motion_pu_wide.hip (tests, A/B)
 };
 FhevcKnobs fhevc_read_knobs();
@@ -214,10 +215,15 @@ hipError_t fhevc_launch_motion_refine(const FhevcFrames& fr, int max_range, cons
                                       int num_cus, hipStream_t stream);
 
 // ---- ... and of the PUs' vectors (k_motion_refine_pu.hip; config 4) --------------------------------------------------
-// fr, max_range (1 .. FHEVC_MOTION_MAX_RANGE), cost as fhevc_launch_motion_refine; d_pus / d_out_pus: (num_frames - 1) * band CTUs * 124 entries in the order of
-// fhevc_motion_pu_index, d_pus_small / d_out_small: ... * 384 in the order of fhevc_motion_pu_small_index; either pair may be null together
+// fr, max_range (1 .. FHEVC_MOTION_WIDE_MAX_RANGE: up to FHEVC_MOTION_MAX_RANGE the MR = 8 layout, above it the MR = 64 layout with its window in dynamic LDS),
+// cost as fhevc_launch_motion_refine; d_pus / d_out_pus: (num_frames - 1) * band CTUs * 124 entries in the order of fhevc_motion_pu_index, d_pus_small /
+// d_out_small: ... * 384 in the order of fhevc_motion_pu_small_index; either pair may be null together.  stage_full: the MR = 64 layout stages its whole
+// window instead of the part max_range reaches (FhevcKnobs::refine_pu_stage_full; the bytes are the same)
 hipError_t fhevc_launch_motion_refine_pu(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_pus, FhevcMotionQpelNode* d_out_pus,
-                                         const FhevcMotionNode* d_pus_small, FhevcMotionQpelNode* d_out_small, int num_cus, hipStream_t stream);
+                                         const FhevcMotionNode* d_pus_small, FhevcMotionQpelNode* d_out_small, int num_cus, bool stage_full, hipStream_t stream);
+// workgroups of its MR = 64 instance that the device keeps on one CU (hipOccupancyMaxActiveBlocksPerMultiprocessor), for the form that planes of
+// sample_bytes at bit_depth take: the launcher sizes the persistent grid by it, at most two
+hipError_t fhevc_motion_refine_pu_big_residency(int sample_bytes, int bit_depth, int* per_cu);
 
 // the shipped P-picture rule (fhevc_p_rule_default): see fasthevc.h; regenerate with tests/quality/fit_p_rule.py
 #define FHEVC_P_RULE_WEIGHTS { { 3101, 188, -94, 80, 1149, 1149, 3174, -138, 15748, -351620 }, \

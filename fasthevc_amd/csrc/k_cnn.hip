@@ -1711,6 +1711,7 @@ FhevcKnobs fhevc_read_knobs()
   if (const char* tr = std::getenv("FHEVC_CNN_TRIO")) k.trio = tr[0] != '0';
   if (const char* rq = std::getenv("FHEVC_D2_REQUANT")) k.d2_requant_general = std::strcmp(rq, "general") == 0;
   if (const char* pw = std::getenv("FHEVC_PU_WIDE")) k.pu_wide_generic = std::strcmp(pw, "generic") == 0;
+  if (const char* rs = std::getenv("FHEVC_REFINE_PU_STAGE")) k.refine_pu_stage_full = std::strcmp(rs, "full") == 0;
   return k;
 }
 

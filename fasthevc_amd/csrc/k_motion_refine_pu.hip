@@ -22,17 +22,26 @@
 //                  different vectors: in the pass of part p every lane predicts its tile at part p's candidate, takes the four quadrant Hadamards
 //                  (had4x4_* of k_had8x8.h) and sums only the quadrants that belong to part p; the 16x16 CU's four tiles meet over lane bits 0 and 3
 // Wave w takes passes w, w + 4, .. of the families asked for: 7 + 7 + 6 + 6 of the 26, so the waves finish within one pass of each other.
-// No scratch, no HBM state between calls: the vector costs travel by value.  Static LDS is the square refinement's (window 15 504 B + tables).
+// No scratch, no HBM state between calls: the vector costs travel by value.
+//
+// Two layouts, as k_motion_refine.hip: MR = 8 (max_range 1..8; the static window of 15 504 B + tables, the square refinement's) and MR = 64 (max_range
+// 9..64, behind fhevc_motion_refine_pu_wide: the window of (64 + 2 * 64 + 8)^2 samples = 80 016 B as dynamic LDS, + 224 B of tables).  Passes, pu_sum, the
+// quadrant path, the validity rule and the cost table are one code for both; only RP, the window's origin (MR + 4) and where the window lives differ.
+// Residency at MR = 64: the VGPRs allow two workgroups per CU and so does the LDS, just: 2 * (80 016 + 224) = 160 480 of 163 840 B.  The launcher asks
+// hipOccupancyMaxActiveBlocksPerMultiprocessor and sizes the persistent grid by its answer.  The MR = 64 layout stages only the part of the window that
+// max_range can reach (refine_stage_window_reach: rows and columns within max_range + 4 of the CTU, columns widened to the 4-sample chunks): at
+// max_range 64 that is the whole window, at 9 a quarter of it.  The addressing is that of the whole window and the results are bit-identical;
+// FHEVC_REFINE_PU_STAGE=full in the environment of fhevc_create stages the whole window whatever max_range is (tests, A/B timing).
 #include "fhevc_internal.h"
 #include "k_had8x8.h"
 #include "k_refine_tile.h"
 
+#include <atomic>
+
 namespace {
 
-constexpr int MR = FHEVC_MOTION_MAX_RANGE;
-constexpr int RP = RefineGeom<MR>::RP;
 constexpr int PASSES_PU = 14, PASSES = 26;
-constexpr int WG_PER_CU = 2;   // 210 (packed) / 238 (32-bit) VGPRs: two waves per SIMD, and the persistent grid is sized to that residency
+constexpr int WG_PER_CU = 2;   // 210 (packed) / 238 (32-bit) VGPRs at MR = 8, 218 / 246 at MR = 64: two waves per SIMD, and the persistent grid is sized to that residency
 
 // the sum over the tiles of this lane's PU of shape s (0 2NxN, 1 Nx2N, 2 2NxnU, 3 2NxnD, 4 nLx2N, 5 nRx2N) of a CU of 2^n x 2^n tiles; n and s are
 // wave-uniform.  horiz: the CU is cut by a horizontal line; along: the tile's row (column) inside the CU; part: the part that holds the tile
@@ -51,13 +60,18 @@ __device__ __forceinline__ unsigned pu_sum(unsigned t8, int lane, int n, int s, 
   return part == qpart ? quarter : cu - quarter;
 }
 
-// T = int16_t (HM Pel planes) or uint8_t; PACKED = bit depth <= 10 (the packed Hadamards)
-template <typename T, bool PACKED>
+// T = int16_t (HM Pel planes) or uint8_t; PACKED = bit depth <= 10 (the packed Hadamards); MR = 8 or 64: the largest integer vector the window is laid
+// out for; stage_full (MR = 64 only): stage the whole window, not only what max_range reaches
+template <typename T, bool PACKED, int MR>
 __global__ __launch_bounds__(256) void fhevc_motion_refine_pu_kernel(FhevcFrames F, int max_range, FhevcMvBitCost cost, const FhevcMotionNode* __restrict__ pus,
                                                                      FhevcMotionQpelNode* __restrict__ out_pus, const FhevcMotionNode* __restrict__ pus_small,
-                                                                     FhevcMotionQpelNode* __restrict__ out_small)
+                                                                     FhevcMotionQpelNode* __restrict__ out_small, bool stage_full)
 {
-  __shared__ __attribute__((aligned(16))) short s_ref[RefineGeom<MR>::SAMPLES];
+  constexpr int RP = RefineGeom<MR>::RP;
+  constexpr bool BIG = MR > FHEVC_MOTION_MAX_RANGE;
+  extern __shared__ __attribute__((aligned(16))) short s_dyn[];
+  __shared__ __attribute__((aligned(16))) short s_small[BIG ? 8 : RefineGeom<MR>::SAMPLES];
+  short* const s_ref = BIG ? s_dyn : s_small;
   __shared__ unsigned s_cost[FHEVC_MV_BIT_COSTS], s_taps[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int tx = lane & 7, ty = lane >> 3;
@@ -79,7 +93,8 @@ __global__ __launch_bounds__(256) void fhevc_motion_refine_pu_kernel(FhevcFrames
     const long long cur_base = (long long)f * F.frame_stride, ref_base = (long long)(f - 1) * F.frame_stride;
     const long long oc = (long long)((f - 1) * band_rows + (cy - F.row_begin)) * F.ctus_x + cx;
     __syncthreads();  // the previous CTU's readers are done
-    refine_stage_window<T, MR>(s_ref, plane, ref_base, F, cx, cy, tid);
+    if (BIG && !stage_full) refine_stage_window_reach<T, MR>(s_ref, plane, ref_base, F, cx, cy, tid, max_range);
+    else refine_stage_window<T, MR>(s_ref, plane, ref_base, F, cx, cy, tid);
     // ---- this lane's original 8x8 tile (all four waves hold the same 64 tiles) ----
     const int px = cx * 64 + tx * 8, py = cy * 64 + ty * 8;
     const bool inside = (px + 8 <= F.width) && (py + 8 <= F.height);
@@ -178,20 +193,69 @@ __global__ __launch_bounds__(256) void fhevc_motion_refine_pu_kernel(FhevcFrames
   }
 }
 
+// the MR = 64 instance of one (T, PACKED) form: its dynamic LDS, and how many of its workgroups the device keeps on one CU (asked once per instance)
+template <typename T, bool PACKED> struct RefinePuBig {
+  static constexpr int MRB = FHEVC_MOTION_WIDE_MAX_RANGE;
+  static constexpr size_t LDS = (size_t)RefineGeom<MRB>::SAMPLES * sizeof(short);  // 80 016 B
+  static const void* kernel() { return reinterpret_cast<const void*>(&fhevc_motion_refine_pu_kernel<T, PACKED, MRB>); }
+  static hipError_t resident(int* per_cu)
+  {
+    const hipError_t e = hipFuncSetAttribute(kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
+    if (e != hipSuccess) return e;
+    static std::atomic<int> asked{0};   // every device of a context is a gfx950: one answer per instance
+    int n = asked.load(std::memory_order_relaxed);
+    if (n == 0) {
+      const hipError_t q = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fhevc_motion_refine_pu_kernel<T, PACKED, MRB>, 256, LDS);
+      if (q != hipSuccess) return q;
+      asked.store(n, std::memory_order_relaxed);
+    }
+    *per_cu = n;
+    return hipSuccess;
+  }
+};
+
+template <typename T, bool PACKED>
+hipError_t launch_refine_pu(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_pus, FhevcMotionQpelNode* d_out_pus,
+                            const FhevcMotionNode* d_pus_small, FhevcMotionQpelNode* d_out_small, int num_cus, bool stage_full, long long total, hipStream_t stream)
+{
+  if (max_range <= FHEVC_MOTION_MAX_RANGE) {
+    const long long resident = (long long)WG_PER_CU * num_cus;
+    const int grid = (int)(total < resident ? total : resident);
+    hipLaunchKernelGGL((fhevc_motion_refine_pu_kernel<T, PACKED, FHEVC_MOTION_MAX_RANGE>), dim3(grid), dim3(256), 0, stream, fr, max_range, cost, d_pus, d_out_pus,
+                       d_pus_small, d_out_small, false);
+  } else {
+    using Big = RefinePuBig<T, PACKED>;
+    int per_cu = 0;
+    const hipError_t e = Big::resident(&per_cu);
+    if (e != hipSuccess) return e;
+    if (per_cu < 1) return hipErrorLaunchOutOfResources;
+    const long long resident = (long long)(per_cu < WG_PER_CU ? per_cu : WG_PER_CU) * num_cus;   // what is actually resident, at most what the VGPRs allow
+    const int grid = (int)(total < resident ? total : resident);
+    hipLaunchKernelGGL((fhevc_motion_refine_pu_kernel<T, PACKED, Big::MRB>), dim3(grid), dim3(256), Big::LDS, stream, fr, max_range, cost, d_pus, d_out_pus,
+                       d_pus_small, d_out_small, stage_full);
+  }
+  return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t fhevc_launch_motion_refine_pu(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_pus, FhevcMotionQpelNode* d_out_pus,
-                                         const FhevcMotionNode* d_pus_small, FhevcMotionQpelNode* d_out_small, int num_cus, hipStream_t stream)
+                                         const FhevcMotionNode* d_pus_small, FhevcMotionQpelNode* d_out_small, int num_cus, bool stage_full, hipStream_t stream)
 {
   const long long total = (long long)(fr.row_end - fr.row_begin) * fr.ctus_x * (fr.num_frames - 1);
   if (total <= 0) return hipSuccess;
-  if (max_range < 1 || max_range > FHEVC_MOTION_MAX_RANGE || (!d_pus && !d_pus_small) || !d_pus != !d_out_pus || !d_pus_small != !d_out_small) return hipErrorInvalidValue;
-  const long long resident = (long long)WG_PER_CU * num_cus;
-  const int grid = (int)(total < resident ? total : resident);
-#define FHEVC_REFINE_PU(T, P) hipLaunchKernelGGL((fhevc_motion_refine_pu_kernel<T, P>), dim3(grid), dim3(256), 0, stream, fr, max_range, cost, d_pus, d_out_pus, d_pus_small, d_out_small)
+  if (max_range < 1 || max_range > FHEVC_MOTION_WIDE_MAX_RANGE || (!d_pus && !d_pus_small) || !d_pus != !d_out_pus || !d_pus_small != !d_out_small) return hipErrorInvalidValue;
+#define FHEVC_REFINE_PU(T, P) return launch_refine_pu<T, P>(fr, max_range, cost, d_pus, d_out_pus, d_pus_small, d_out_small, num_cus, stage_full, total, stream)
   if (fr.sample_bytes == 2 && fr.bit_depth <= 10) FHEVC_REFINE_PU(int16_t, true);
   else if (fr.sample_bytes == 2) FHEVC_REFINE_PU(int16_t, false);
   else FHEVC_REFINE_PU(uint8_t, true);
 #undef FHEVC_REFINE_PU
-  return hipGetLastError();
+}
+
+// workgroups of the MR = 64 instance that the device keeps on one CU, for the form that planes of sample_bytes at bit_depth take (measurement tools)
+hipError_t fhevc_motion_refine_pu_big_residency(int sample_bytes, int bit_depth, int* per_cu)
+{
+  if (sample_bytes == 2 && bit_depth <= 10) return RefinePuBig<int16_t, true>::resident(per_cu);
+  if (sample_bytes == 2) return RefinePuBig<int16_t, false>::resident(per_cu);
+  return RefinePuBig<uint8_t, true>::resident(per_cu);
 }

@@ -44,34 +44,57 @@ struct RefineArith {
     : bd(bit_depth), shift(bit_depth - 8), v_off((1 << (19 - bit_depth)) + (8192 << 6)), v_shift(20 - bit_depth), top((1 << bit_depth) - 1) {}
 };
 
-// ---- stage the reference window of CTU (cx, cy): rows cy*64 - MR - 4 .., columns cx*64 - MR - 4 .., coordinates clamped to the picture ----
+// ---- one chunk of 4 samples of the reference window of CTU (cx, cy): window row wr, columns wc .. wc + 3 = picture row cy*64 - MR - 4 + wr, columns
+// cx*64 - MR - 4 + wc .., coordinates clamped to the picture.  The window's first column is a multiple of 4, so a chunk inside the picture is ONE 8-byte
+// (uint8 planes: 4-byte) load where the plane allows it, and one 8-byte LDS store ----
+template <typename T, int MR>
+__device__ __forceinline__ void refine_stage_chunk(short* s_ref, const T* plane, long long ref_base, const FhevcFrames& F, int cx, int cy, int wr, int wc)
+{
+  constexpr int RP = RefineGeom<MR>::RP;
+  const int py = min(max(cy * 64 - MR - 4 + wr, 0), F.height - 1);
+  const int px0 = cx * 64 - MR - 4 + wc;
+  const long long row = ref_base + (long long)py * F.stride;
+  const T* src = plane + row + px0;
+  uint2 q;
+  if (px0 >= 0 && px0 + 4 <= F.width && (reinterpret_cast<uintptr_t>(src) & (4 * sizeof(T) - 1)) == 0) {
+    if (sizeof(T) == 2) q = *reinterpret_cast<const uint2*>(src);
+    else {
+      const unsigned b = *reinterpret_cast<const unsigned*>(src);
+      q.x = (b & 0xFFu) | ((b & 0xFF00u) << 8); q.y = ((b >> 16) & 0xFFu) | ((b >> 24) << 16);
+    }
+  } else {
+    int v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = sample_of(plane, row + min(max(px0 + k, 0), F.width - 1));
+    q.x = ((unsigned)v[0] & 0xFFFFu) | ((unsigned)v[1] << 16); q.y = ((unsigned)v[2] & 0xFFFFu) | ((unsigned)v[3] << 16);
+  }
+  *reinterpret_cast<uint2*>(s_ref + wr * RP + wc) = q;
+}
+
+// ---- stage the whole reference window of CTU (cx, cy): rows cy*64 - MR - 4 .., columns cx*64 - MR - 4 .. ----
 template <typename T, int MR>
 __device__ __forceinline__ void refine_stage_window(short* s_ref, const T* plane, long long ref_base, const FhevcFrames& F, int cx, int cy, int tid)
 {
-  constexpr int RP = RefineGeom<MR>::RP;
-  // chunks of 4 samples: the window's first column is a multiple of 4, so a chunk inside the picture is ONE 8-byte (uint8 planes: 4-byte) load
-  // where the plane allows it, and one 8-byte LDS store
-  constexpr int CH = RP / 4;
+  constexpr int CH = RefineGeom<MR>::RP / 4;
   for (int it = tid; it < RefineGeom<MR>::ROWS * CH; it += 256) {
     const int wr = it / CH, wc = (it - wr * CH) * 4;
-    const int py = min(max(cy * 64 - MR - 4 + wr, 0), F.height - 1);
-    const int px0 = cx * 64 - MR - 4 + wc;
-    const long long row = ref_base + (long long)py * F.stride;
-    const T* src = plane + row + px0;
-    uint2 q;
-    if (px0 >= 0 && px0 + 4 <= F.width && (reinterpret_cast<uintptr_t>(src) & (4 * sizeof(T) - 1)) == 0) {
-      if (sizeof(T) == 2) q = *reinterpret_cast<const uint2*>(src);
-      else {
-        const unsigned b = *reinterpret_cast<const unsigned*>(src);
-        q.x = (b & 0xFFu) | ((b & 0xFF00u) << 8); q.y = ((b >> 16) & 0xFFu) | ((b >> 24) << 16);
-      }
-    } else {
-      int v[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] = sample_of(plane, row + min(max(px0 + k, 0), F.width - 1));
-      q.x = ((unsigned)v[0] & 0xFFFFu) | ((unsigned)v[1] << 16); q.y = ((unsigned)v[2] & 0xFFFFu) | ((unsigned)v[3] << 16);
-    }
-    *reinterpret_cast<uint2*>(s_ref + wr * RP + wc) = q;
+    refine_stage_chunk<T, MR>(s_ref, plane, ref_base, F, cx, cy, wr, wc);
+  }
+}
+
+// ---- ... or only the part of it that vectors of up to max_range can reach: a candidate's first tap lies (qx >> 2) - 3 >= -max_range - 4 samples before
+// the tile and its last one (qx >> 2) + 4 <= max_range + 4 behind it, so window rows and columns MR - max_range .. RP - 1 - (MR - max_range) hold every
+// sample that is read for its value; the columns are widened to whole chunks.  Same addresses, same values: the rest of the window is never staged and
+// never used ----
+template <typename T, int MR>
+__device__ __forceinline__ void refine_stage_window_reach(short* s_ref, const T* plane, long long ref_base, const FhevcFrames& F, int cx, int cy, int tid, int max_range)
+{
+  constexpr int CH = RefineGeom<MR>::RP / 4;
+  const int skip = MR - max_range, c0 = skip >> 2;       // rows skipped at either end; chunks skipped at either end (RP is a multiple of 4)
+  const int rows = RefineGeom<MR>::ROWS - 2 * skip, ch = CH - 2 * c0;
+  for (int it = tid; it < rows * ch; it += 256) {
+    const int r = it / ch;
+    refine_stage_chunk<T, MR>(s_ref, plane, ref_base, F, cx, cy, skip + r, (c0 + it - r * ch) * 4);
   }
 }
 

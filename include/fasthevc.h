@@ -409,7 +409,7 @@ int  fhevc_motion_search_pu_small(fhevc_ctx* ctx, const int16_t* cur_luma, const
  * fhevc_last_error text (nothing is launched or written): a null context or d_luma, all three outputs null, num_frames < 2, qp outside 0..51,
  * search_range outside 1..64, stride_samples < width, a bad band, uint8 planes on a context above 8 bit.  Not covered: the quarter-sample refinement
  * of PU vectors beyond +-8 (fhevc_motion_refine_pu marks them), SATD at integer positions above +-8, predictors other than zero.  The encoder hook
- * does not consume this output. */
+ * does not consume this output.  (Since then: fhevc_motion_refine_pu_wide, below, refines the vectors of all three outputs at max_range 1..64.) */
 int  fhevc_motion_search_pu_wide_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
                                         int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range,
                                         fhevc_motion_node* d_nodes, fhevc_motion_node* d_pus, fhevc_motion_node* d_pus_small, void* stream);
@@ -433,7 +433,8 @@ int  fhevc_motion_search_pu_wide(fhevc_ctx* ctx, const int16_t* cur_luma, const 
  * two PU searches wrote for the same pictures and band, in either distortion mode; only mvx and mvy are read.  A PU is valid iff its CU node lies
  * wholly inside the picture and |mvx|, |mvy| <= max_range (1..8: no PU search writes longer vectors, so the 15.5 KB window serves); an invalid PU gets
  * 0xFFFFFFFF in the three distortion fields and a zero vector, so no content of the input can send a read outside the staged window.  Output entries
- * are fhevc_motion_qpel_node.  Either family's in / out pair may be NULL together: that family's work is then not done at all.
+ * are fhevc_motion_qpel_node.  Either family's in / out pair may be NULL together: that family's work is then not done at all.  Vectors of the search
+ * ranges above 8 (fhevc_motion_search_pu_wide) are fhevc_motion_refine_pu_wide's, below.
  * One picture pair, host buffers (both planes with the same stride), synchronous: */
 int  fhevc_motion_refine_pu(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
                             const fhevc_motion_node* pus, fhevc_motion_qpel_node* out_pus,
@@ -449,6 +450,38 @@ int  fhevc_motion_refine_pu_device(fhevc_ctx* ctx, const void* d_luma, int sampl
                                    int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range,
                                    const fhevc_motion_node* d_pus, fhevc_motion_qpel_node* d_out_pus,
                                    const fhevc_motion_node* d_pus_small, fhevc_motion_qpel_node* d_out_pus_small, void* stream);
+
+/* The quarter-sample refinements at HM's own SearchRange: the counterpart of fhevc_motion_search_pu_wide, whose three outputs feed straight in.  max_range 1..64.
+ * Per entry the definition is exactly that of fhevc_motion_refine for the 85 nodes and of fhevc_motion_refine_pu for the 124 PUs and the 384 small PUs: the
+ * half-sample stage of s_acMvRefineH, then the quarter-sample stage of s_acMvRefineQ around its winner, strict "<" in both; TComRdCost::xGetHADs on the whole
+ * block through the branch xGetHADs itself takes (8x8 tiles where both sides are multiples of 8, otherwise 4x4 tiles), shifted ONCE by bit_depth - 8; ALWAYS
+ * SATD, whatever fhevc_set_motion_distortion says; zero predictor, the lambda of slice QP qp; coordinates clamped to the picture.  An entry is valid iff its
+ * CU node lies wholly inside the picture and |mvx|, |mvy| <= max_range; an invalid one gets 0xFFFFFFFF in the three distortion fields and a zero vector, so no
+ * content of the input can send a read outside the staged window.  Only mvx and mvy of the input entries are read.
+ *   d_nodes, d_out_nodes          85 per CTU: a second launch on the same stream of the kernel behind fhevc_motion_refine_device; the result is byte for byte
+ *                                 what that entry point writes for the same arguments
+ *   d_pus, d_out_pus              FHEVC_PUS_PER_CTU per CTU in fhevc_motion_pu_index order
+ *   d_pus_small, d_out_pus_small  FHEVC_PUS_SMALL_PER_CTU per CTU in fhevc_motion_pu_small_index order; both PU families in one launch.  At max_range <= 8
+ *                                 the PU outputs are byte for byte what fhevc_motion_refine_pu_device writes; above, k_motion_refine_pu.hip runs laid out for
+ *                                 vectors up to +-64 (a window of 200 x 200 samples, 80 016 B of LDS, of which the part max_range reaches is staged)
+ * Each in / out pair may be NULL together: a family that is not asked for is neither computed nor written.  All three pairs NULL, or a pair with exactly
+ * one NULL member, is FHEVC_E_INVALID.  Entry order, the compact-over-band layout ((num_frames - 1) * band CTUs * 85 / 124 / 384 entries; frame
+ * f = 1 .. num_frames-1 is refined in frame f-1), the exact write extent and the empty band that writes nothing are those of the existing refinements.
+ * Asynchronous with respect to the host, allocates nothing, keeps NO state in HBM between calls (the vector costs travel by value) and synchronises nothing:
+ * calls with different QPs and ranges may be in flight on two streams, and a wide search and its refinement may follow each other on one stream without a host
+ * synchronisation.  FHEVC_E_INVALID with a fhevc_last_error text (nothing is launched or written): a null context or d_luma, all three pairs null, a pair
+ * with exactly one null member, num_frames < 2, qp outside 0..51, max_range outside 1..64, stride_samples < width, a bad band, uint8 planes on a context above
+ * 8 bit.  Timed under slot 12 of fhevc_kernel_timing, each launch counted.  The encoder hook does not consume this output. */
+int  fhevc_motion_refine_pu_wide_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                        int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range,
+                                        const fhevc_motion_node* d_nodes, fhevc_motion_qpel_node* d_out_nodes,
+                                        const fhevc_motion_node* d_pus, fhevc_motion_qpel_node* d_out_pus,
+                                        const fhevc_motion_node* d_pus_small, fhevc_motion_qpel_node* d_out_pus_small, void* stream);
+/* one picture pair, host buffers (both planes with the same stride), synchronous; each in / out pair may be NULL together, not all three */
+int  fhevc_motion_refine_pu_wide(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                                 const fhevc_motion_node* nodes, fhevc_motion_qpel_node* out_nodes,
+                                 const fhevc_motion_node* pus, fhevc_motion_qpel_node* out_pus,
+                                 const fhevc_motion_node* pus_small, fhevc_motion_qpel_node* out_pus_small);
 
 /* Depth range of every 4x4 unit of a P picture's CTU from its motion nodes and the co-located depths of its reference picture
  * ("inter-CU depth reuse", BASELINE config 4).  Host-side integer arithmetic, no device work.  Per split decision (64->32,
@@ -533,7 +566,8 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
  * 7 = quarter-sample motion refinement (fhevc_motion_refine*), 8 = motion search of the rectangular PUs (fhevc_motion_search_pu*),
  * 9 = motion search of the PUs with a 4-sample side (fhevc_motion_search_pu_small*), 10 = quarter-sample refinement of the PUs
  * (fhevc_motion_refine_pu*), 11 = the searches at HM's SearchRange (fhevc_motion_search_pu_wide*: one launch for nodes and PUs, one for the
- * small PUs, each counted) */
+ * small PUs, each counted), 12 = the refinements at HM's SearchRange (fhevc_motion_refine_pu_wide*: one launch for the nodes, one for the PUs,
+ * each counted) */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
 int  fhevc_enable_kernel_timing(fhevc_ctx* ctx, int on);
 
