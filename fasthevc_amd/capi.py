@@ -37,11 +37,14 @@ SYMBOLS = [
     "fhevc_motion_refine_pu", "fhevc_motion_refine_pu_device",
     "fhevc_motion_search_pu_wide", "fhevc_motion_search_pu_wide_device",
     "fhevc_motion_refine_pu_wide", "fhevc_motion_refine_pu_wide_device",
+    "fhevc_pu_shape_rule_default", "fhevc_pu_shape_select", "fhevc_pu_shape_select_device", "fhevc_p_shape_frame",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
 P_PREV_COLOCATED, P_PREV_UNIT, P_PREV_NODE = 0, 1, 2
 P_PREV = {"colocated": P_PREV_COLOCATED, "unit": P_PREV_UNIT, "node": P_PREV_NODE}
+# partition sizes of fhevc_pu_shape_select*: HM's PartSize numbers (FHEVC_PART_*; 3, NxN, is never produced)
+PART_2Nx2N, PART_2NxN, PART_Nx2N, PART_2NxnU, PART_2NxnD, PART_nLx2N, PART_nRx2N = 0, 1, 2, 4, 5, 6, 7
 
 
 class Cfg(C.Structure):
@@ -52,6 +55,11 @@ class Cfg(C.Structure):
 
 class PRule(C.Structure):
     _fields_ = [("w", (C.c_int32 * 10) * 3), ("t_split", C.c_int32 * 3), ("t_stop", C.c_int32 * 3), ("window", C.c_int32)]
+
+
+class PuShapeRule(C.Structure):
+    """fhevc_pu_shape_rule: margins per level (64, 32, 16, 8) and the AMP gate"""
+    _fields_ = [("margin_q8", C.c_int32 * 4), ("margin_abs", C.c_int32 * 4), ("amp_mode", C.c_int32)]
 
 
 class NodeCost(C.Structure):
@@ -69,6 +77,9 @@ NODE_DTYPE = np.dtype([("satd", np.uint32), ("mode", np.uint32), ("cost", np.flo
 MOTION_DTYPE = np.dtype([("satd_zero", np.uint32), ("satd_best", np.uint32), ("cost_best", np.uint32), ("mvx", np.int16), ("mvy", np.int16)])
 # fhevc_motion_qpel_node: the vector in QUARTER samples
 MOTION_QPEL_DTYPE = np.dtype([("satd_int", np.uint32), ("satd_best", np.uint32), ("cost_best", np.uint32), ("mvx", np.int16), ("mvy", np.int16)])
+# fhevc_pu_shape_node: one record per CU node
+SHAPE_DTYPE = np.dtype([("cost_2Nx2N", np.uint32), ("cost_best", np.uint32), ("cost_second", np.uint32), ("best", np.uint8), ("second", np.uint8),
+                        ("mask", np.uint8), ("avail", np.uint8)])
 
 
 def motion_pu_index(node, shape, part):
@@ -193,6 +204,11 @@ def load_library(path=None):
     lib.fhevc_p_node_depth.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
     lib.fhevc_p_depth_range_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PRule), vp, vp, vp]
     lib.fhevc_p_predict_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(PRule), vp, vp]
+    lib.fhevc_pu_shape_rule_default.argtypes = [C.POINTER(PuShapeRule)]
+    lib.fhevc_pu_shape_rule_default.restype = None
+    lib.fhevc_pu_shape_select.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(PuShapeRule), vp, vp]
+    lib.fhevc_pu_shape_select_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), vp, vp, vp]
+    lib.fhevc_p_shape_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), vp]
     lib.fhevc_predict_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, vp, vp]
     lib.fhevc_alloc_host.argtypes = [vp, C.c_size_t]
     lib.fhevc_alloc_host.restype = vp
@@ -235,6 +251,40 @@ def p_rule_default_wide():
     r = PRule()
     load_library().fhevc_p_rule_default_wide(C.byref(r))
     return r
+
+
+def pu_shape_rule_default():
+    r = PuShapeRule()
+    load_library().fhevc_pu_shape_rule_default(C.byref(r))
+    return r
+
+
+def pu_shape_rule(margin_q8=0, margin_abs=0, amp_mode=1):
+    """a PuShapeRule from scalars (the same margin at every level) or sequences of four"""
+    q8 = [margin_q8] * 4 if np.isscalar(margin_q8) else list(margin_q8)
+    ab = [margin_abs] * 4 if np.isscalar(margin_abs) else list(margin_abs)
+    return PuShapeRule((C.c_int32 * 4)(*q8), (C.c_int32 * 4)(*ab), amp_mode)
+
+
+def pu_shape_select(nodes, pus, pus_small, width, height, rule=None, with_costs=False):
+    """config 4, host side: the partition-size records [numCtus, 85] SHAPE_DTYPE of a P picture from its refined nodes [numCtus, 85], PUs [numCtus, 124]
+    and small PUs [numCtus, 384] or None (MOTION_QPEL_DTYPE; only cost_best is read); with_costs: (records, costs [numCtus, 85, 8] uint32)"""
+    lib = load_library()
+    rule = rule if rule is not None else pu_shape_rule_default()
+    nodes, pus = np.ascontiguousarray(nodes), np.ascontiguousarray(pus)
+    small = None if pus_small is None else np.ascontiguousarray(pus_small)
+    assert nodes.dtype.itemsize == 16 and pus.dtype.itemsize == 16 and (small is None or small.dtype.itemsize == 16)
+    cw = (width + 63) // 64
+    n = nodes.shape[0]
+    out = np.zeros((n, NODES_PER_CTU), SHAPE_DTYPE)
+    costs = np.zeros((n, NODES_PER_CTU, 8), np.uint32) if with_costs else None
+    for c in range(n):
+        vw, vh = min(64, width - (c % cw) * 64), min(64, height - (c // cw) * 64)
+        rc = lib.fhevc_pu_shape_select(nodes[c].ctypes.data, pus[c].ctypes.data, None if small is None else small[c].ctypes.data, vw, vh, C.byref(rule),
+                                       out[c].ctypes.data, costs[c].ctypes.data if with_costs else None)
+        if rc != OK:
+            raise FastHevcError(rc, "fhevc_pu_shape_select")
+    return (out, costs) if with_costs else out
 
 
 def p_depth_range(nodes, prev_depth, width, height, qp, rule=None):
@@ -584,6 +634,26 @@ class Context:
                                                    prev.ctypes.data, P_PREV.get(prev_mode, prev_mode), C.byref(rule) if rule is not None else None,
                                                    dmin.ctypes.data, dmax.ctypes.data))
         return dmin.reshape(self.num_ctus, 256), dmax.reshape(self.num_ctus, 256)
+
+    def pu_shape_select_device(self, d_nodes, d_pus, d_pus_small, num_pictures, d_shapes, d_costs=None, rows=None, stream=None, rule=None):
+        """config 4 on the device: the partition-size records of num_pictures P pictures from their refined entries (what motion_refine_pu_wide_device
+        wrote for the same rows: 85 / 124 / 384 per CTU; d_pus_small may be None); d_shapes: num_pictures * band CTUs * 85 records (16 B), d_costs
+        (optional): ... * 85 * 8 uint32.  rule: a PuShapeRule (None: the unfitted default).  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_pu_shape_select_device(self.h, d_nodes, d_pus, d_pus_small, num_pictures, rb, re, C.byref(rule) if rule is not None else None,
+                                                          d_shapes, d_costs, stream))
+
+    def p_shape_frame(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=64, rule=None):
+        """config 4, one picture pair from host buffers: the wide SAD search of all three families, their quarter-sample refinement and the partition-size
+        selection on the device -> [numCtus, 85] SHAPE_DTYPE; only the records come back."""
+        cur = np.ascontiguousarray(cur_plane).reshape(-1)
+        ref = np.ascontiguousarray(ref_plane).reshape(-1)
+        assert cur.dtype == np.int16 and ref.dtype == np.int16
+        stride = stride if stride is not None else cur_plane.shape[-1]
+        out = np.zeros(self.num_ctus * NODES_PER_CTU, SHAPE_DTYPE)
+        self._check(self.lib.fhevc_p_shape_frame(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, search_range,
+                                                 C.byref(rule) if rule is not None else None, out.ctypes.data))
+        return out.reshape(self.num_ctus, NODES_PER_CTU)
 
     def intra_first_pass_all(self, plane, origin=0, stride=None, qp=32):
         """(best [numCtus, 85], all [numCtus, 85, 35]): every mode's SATD and cost per node (parity entry point)"""

@@ -292,7 +292,7 @@ int fhevc_enable_kernel_timing(fhevc_ctx* c, int on)
 
 int fhevc_kernel_timing(fhevc_ctx* c, int which, int reset, double* avg_ms, uint64_t* launches)
 {
-  if (!c || which < 0 || which > 12) return FHEVC_E_INVALID;
+  if (!c || which < 0 || which > 13) return FHEVC_E_INVALID;
   time_resolve(c);
   if (avg_ms) *avg_ms = c->launches[which] ? c->sum_ms[which] / (double)c->launches[which] : 0.0;
   if (launches) *launches = c->launches[which];
@@ -1185,6 +1185,67 @@ int fhevc_p_predict_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* 
   HIP_TRY(c, hipMemcpyAsync(depth_max, c->d_p_maps + 2 * maps, maps, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->stats.bytes_d2h += 2 * maps;
+  return FHEVC_OK;
+}
+
+// ---- partition sizes per CU from the refined PU costs over a device-resident batch (k_pu_shape.hip; the host form: fhevc_host.hip) ----
+int fhevc_pu_shape_select_device(fhevc_ctx* c, const fhevc_motion_qpel_node* d_nodes, const fhevc_motion_qpel_node* d_pus, const fhevc_motion_qpel_node* d_pus_small,
+                                 int num_pictures, int ctu_row_begin, int ctu_row_end, const fhevc_pu_shape_rule* rule, fhevc_pu_shape_node* d_shapes,
+                                 uint32_t* d_costs, void* stream)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!d_nodes || !d_pus || !d_shapes) return fail(c, FHEVC_E_INVALID, "bad partition-size selection arguments");
+  // (refined entries have no sample layout: the checks of the pictures' number and the band)
+  if (const char* bad = batch_error(c, 2, c->cfg.width, 0, num_pictures, 1, ctu_row_begin, ctu_row_end, 0, false)) return fail(c, FHEVC_E_INVALID, bad);
+  static_assert(sizeof(fhevc_pu_shape_rule) == sizeof(FhevcPuShapeRule) && sizeof(fhevc_pu_shape_node) == sizeof(FhevcPuShapeNode), "partition-size layouts");
+  FhevcPuShapeRule r;   // read here, handed to the kernel by value: the caller's struct is free again when this call returns
+  if (rule) std::memcpy(&r, rule, sizeof r);
+  else { fhevc_pu_shape_rule d; fhevc_pu_shape_rule_default(&d); std::memcpy(&r, &d, sizeof r); }
+  if (const char* bad = fhevc_pu_shape_rule_error(r)) return fail(c, FHEVC_E_INVALID, bad);
+  if ((long long)num_pictures * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "more than 2^31 - 1 CTUs");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
+  const FhevcFrames fr = frames_of(c, nullptr, 1, c->cfg.width, 0, num_pictures, ctu_row_begin, ctu_row_end);
+  return launch_on(c, stream, 13, "fhevc_launch_pu_shape", [&](hipStream_t s) {
+    return fhevc_launch_pu_shape(fr, r, reinterpret_cast<const FhevcMotionQpelNode*>(d_nodes), reinterpret_cast<const FhevcMotionQpelNode*>(d_pus),
+                                 reinterpret_cast<const FhevcMotionQpelNode*>(d_pus_small), reinterpret_cast<FhevcPuShapeNode*>(d_shapes), d_costs, c->num_cus, s);
+  });
+}
+
+int fhevc_p_shape_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                        const fhevc_pu_shape_rule* rule, fhevc_pu_shape_node* shapes)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!cur_luma || !ref_luma || !shapes || stride_samples < c->cfg.width) return fail(c, FHEVC_E_INVALID, "bad partition-size frame arguments");
+  if (qp < 0 || qp > 51 || search_range < 1 || search_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad partition-size frame arguments");
+  if (rule)
+    if (const char* bad = fhevc_pu_shape_rule_error(*rule)) return fail(c, FHEVC_E_INVALID, bad);
+  (void)hipSetDevice(c->device);
+  // the buffers of the host forms of the wide search and its refinement; the records go where the integer nodes were once the refinement has read them
+  const size_t node_bytes = motion_bytes(c), pu_bytes = (size_t)c->num_ctus * FHEVC_PUS * sizeof(FhevcMotionNode),
+               small_bytes = (size_t)c->num_ctus * FHEVC_PUS_SMALL * sizeof(FhevcMotionNode);
+  HIP_TRY(c, ensure(c->d_qpel, node_bytes));
+  HIP_TRY(c, ensure(c->d_motion_pu, pu_bytes));
+  HIP_TRY(c, ensure(c->d_qpel_pu, pu_bytes));
+  HIP_TRY(c, ensure(c->d_motion_pu_small, small_bytes));
+  HIP_TRY(c, ensure(c->d_qpel_pu_small, small_bytes));
+  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
+  if (rc != FHEVC_OK) return rc;
+  fhevc_motion_node* nodes = reinterpret_cast<fhevc_motion_node*>(c->d_motion);
+  fhevc_motion_node* pus = reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu);
+  fhevc_motion_node* small = reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu_small);
+  fhevc_motion_qpel_node* q_nodes = reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel);
+  fhevc_motion_qpel_node* q_pus = reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu);
+  fhevc_motion_qpel_node* q_small = reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu_small);
+  rc = fhevc_motion_search_pu_wide_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, search_range, nodes, pus, small, c->stream);
+  if (rc == FHEVC_OK)
+    rc = fhevc_motion_refine_pu_wide_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, search_range, nodes, q_nodes, pus, q_pus,
+                                            small, q_small, c->stream);
+  if (rc == FHEVC_OK)
+    rc = fhevc_pu_shape_select_device(c, q_nodes, q_pus, q_small, 1, 0, c->ctus_y, rule, reinterpret_cast<fhevc_pu_shape_node*>(c->d_motion), nullptr, c->stream);
+  if (rc != FHEVC_OK) { (void)hipStreamSynchronize(c->stream); return rc; }   // the uploads read the caller's buffers: through before the call returns
+  HIP_TRY(c, hipMemcpyAsync(shapes, c->d_motion, node_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->stats.bytes_d2h += (uint64_t)node_bytes;
   return FHEVC_OK;
 }
 

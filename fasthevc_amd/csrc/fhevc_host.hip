@@ -1,5 +1,6 @@
 // fhevc_host.hip -- the functions of include/fasthevc.h that take no context and never touch the device: the band split, the YUV reader, the AQ
-// partition / QP arithmetic, the host form of the P-picture rule and the two motion-compensated depth maps.  Plain C++.
+// partition / QP arithmetic, the host form of the P-picture rule, the two motion-compensated depth maps and the host form of the
+// partition-size selection.  Plain C++.
 #include "../../include/fasthevc.h"
 #include "fhevc_internal.h"
 
@@ -240,6 +241,78 @@ int fhevc_p_depth_range(const fhevc_motion_node* nodes, const uint8_t* prev_dept
       depth_min[uy * 16 + ux] = (uint8_t)lo;
       depth_max[uy * 16 + ux] = (uint8_t)hi;
     }
+  return FHEVC_OK;
+}
+
+// ---- partition sizes per CU from the refined PU costs (spec in include/fasthevc.h; the device form is k_pu_shape.hip) ----
+
+void fhevc_pu_shape_rule_default(fhevc_pu_shape_rule* rule)
+{
+  if (!rule) return;
+  std::memset(rule, 0, sizeof *rule);   // the unfitted hard decision: no margins
+  rule->amp_mode = 1;
+}
+
+int fhevc_pu_shape_select(const fhevc_motion_qpel_node* nodes, const fhevc_motion_qpel_node* pus, const fhevc_motion_qpel_node* pus_small, int valid_w,
+                          int valid_h, const fhevc_pu_shape_rule* rule, fhevc_pu_shape_node* out, uint32_t* costs)
+{
+  if (!nodes || !pus || !rule || !out || valid_w < 8 || valid_w > 64 || valid_h < 8 || valid_h > 64 || fhevc_pu_shape_rule_error(*rule)) return FHEVC_E_INVALID;
+  const uint32_t none = 0xFFFFFFFFu;
+  static const int order[7] = { FHEVC_PART_2Nx2N, FHEVC_PART_Nx2N, FHEVC_PART_2NxN, FHEVC_PART_2NxnU, FHEVC_PART_2NxnD, FHEVC_PART_nLx2N, FHEVC_PART_nRx2N };
+  for (int k = 0; k < FHEVC_NODES; ++k) {
+    const int lvl = k < 1 ? 0 : (k < 5 ? 1 : (k < 21 ? 2 : 3));
+    const int size = 64 >> lvl, idx = k - kLevel[lvl].first, nx = idx % kLevel[lvl].per_row, ny = idx / kLevel[lvl].per_row;
+    const bool valid = nx * size + size <= valid_w && ny * size + size <= valid_h;
+    uint32_t cost[8];
+    for (int p = 0; p < 8; ++p) cost[p] = none;
+    if (valid) {
+      cost[0] = nodes[k].cost_best;
+      for (int p = 1; p < 8; ++p) {
+        if (p == 3) continue;
+        const int shape = p < 3 ? p - 1 : p - 2;
+        // the two parts: in pus where fhevc_motion_pu_index covers the combination, otherwise in pus_small where fhevc_motion_pu_small_index does
+        const fhevc_motion_qpel_node* src = pus;
+        int e0 = fhevc_motion_pu_index(k, shape, 0);
+        if (e0 < 0) { src = pus_small; e0 = fhevc_motion_pu_small_index(k, shape, 0); }
+        if (e0 < 0 || !src) continue;
+        const uint32_t a = src[e0].cost_best, b = src[e0 + 1].cost_best;   // part 1 follows part 0 in both orders
+        if (a == none || b == none) continue;
+        cost[p] = (uint32_t)std::min<uint64_t>((uint64_t)a + b, 0xFFFFFFFEu);
+      }
+    }
+    if (costs) std::memcpy(costs + k * 8, cost, sizeof cost);
+    fhevc_pu_shape_node& o = out[k];
+    o.cost_2Nx2N = cost[0]; o.cost_best = o.cost_second = none;
+    o.best = o.second = 255; o.mask = o.avail = 0;
+    if (!valid) continue;
+    for (int i = 0; i < 7; ++i) {
+      const int p = order[i];
+      if (cost[p] == none) continue;
+      o.avail |= (uint8_t)(1 << p);
+      if (cost[p] < o.cost_best) { o.cost_best = cost[p]; o.best = (uint8_t)p; }
+    }
+    for (int i = 0; i < 7; ++i) {
+      const int p = order[i];
+      if (cost[p] == none || p == o.best) continue;
+      if (cost[p] < o.cost_second) { o.cost_second = cost[p]; o.second = (uint8_t)p; }
+    }
+    unsigned mask = 1;   // HM always checks 2Nx2N
+    if (o.best != 255) {
+      const uint64_t limit = (uint64_t)o.cost_best + (uint64_t)rule->margin_abs[lvl] + (((uint64_t)o.cost_best * (uint64_t)rule->margin_q8[lvl]) >> 8);
+      for (int p = 0; p < 8; ++p)
+        if (cost[p] != none && cost[p] <= limit) mask |= 1u << p;
+    }
+    if (rule->amp_mode == 1) {
+      // TEncCu::deriveTestModeAMP without the merge / skip conditions (not visible to a source-only pass): the best of 2Nx2N, Nx2N, 2NxN decides which AMP pair stays
+      int b3 = -1;
+      uint32_t c3 = none;
+      for (int i = 0; i < 3; ++i)
+        if (cost[order[i]] < c3) { c3 = cost[order[i]]; b3 = order[i]; }
+      if (!(b3 == FHEVC_PART_2Nx2N || b3 == FHEVC_PART_2NxN)) mask &= ~0x30u;
+      if (!(b3 == FHEVC_PART_2Nx2N || b3 == FHEVC_PART_Nx2N)) mask &= ~0xC0u;
+    }
+    o.mask = (uint8_t)mask;
+  }
   return FHEVC_OK;
 }
 

@@ -250,6 +250,24 @@ struct FhevcPRule { int32_t w[3][10]; int32_t t_split[3], t_stop[3]; int32_t win
 hipError_t fhevc_launch_p_rule(const FhevcFrames& fr, int prev_mode, const FhevcPRule& rule, const FhevcMotionNode* d_nodes, const uint8_t* d_prev_maps,
                                uint8_t* d_depth_min, uint8_t* d_depth_max, int num_cus, hipStream_t stream);
 
+// ---- partition sizes per CU from the refined PU costs (k_pu_shape.hip; config 4) ------------------------------------
+// fhevc_pu_shape_rule of fasthevc.h; travels by value as a kernel argument, so every launch has its own rule
+struct FhevcPuShapeRule { int32_t margin_q8[4]; int32_t margin_abs[4]; int32_t amp_mode; };
+// what is wrong with a rule (host form and device form reject the same rules); null: nothing
+template <class R> inline const char* fhevc_pu_shape_rule_error(const R& r)
+{
+  for (int l = 0; l < 4; ++l) {
+    if (r.margin_q8[l] < 0 || r.margin_q8[l] > 65535) return "margin_q8 out of range (0..65535)";
+    if (r.margin_abs[l] < 0) return "margin_abs out of range (>= 0)";
+  }
+  return r.amp_mode < 0 || r.amp_mode > 1 ? "amp_mode out of range (0..1)" : nullptr;
+}
+struct FhevcPuShapeNode { uint32_t cost_2Nx2N, cost_best, cost_second; uint8_t best, second, mask, avail; };
+// fr: geometry, band, num_frames = the P pictures of the batch (luma is not read).  d_nodes / d_pus / d_pus_small (may be null): num_frames * band CTUs * 85 / 124 /
+// 384 refined entries; d_shapes: num_frames * band CTUs * 85; d_costs (may be null): ... * 85 * 8 dwords; all compact over the band
+hipError_t fhevc_launch_pu_shape(const FhevcFrames& fr, const FhevcPuShapeRule& rule, const FhevcMotionQpelNode* d_nodes, const FhevcMotionQpelNode* d_pus,
+                                 const FhevcMotionQpelNode* d_pus_small, FhevcPuShapeNode* d_shapes, uint32_t* d_costs, int num_cus, hipStream_t stream);
+
 // ---- adaptive-QP pre-analysis (k_preanalyze.hip) -----------------------------------------------------------
 // d_activity: per frame parts_per_frame doubles, layers concatenated (layer d: ceil(H/P) x ceil(W/P), P = 64 >> d)
 hipError_t fhevc_launch_preanalyze(const FhevcFrames& fr, int layers, long long parts_per_frame, double* d_activity,

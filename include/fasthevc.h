@@ -471,7 +471,8 @@ int  fhevc_motion_refine_pu_device(fhevc_ctx* ctx, const void* d_luma, int sampl
  * calls with different QPs and ranges may be in flight on two streams, and a wide search and its refinement may follow each other on one stream without a host
  * synchronisation.  FHEVC_E_INVALID with a fhevc_last_error text (nothing is launched or written): a null context or d_luma, all three pairs null, a pair
  * with exactly one null member, num_frames < 2, qp outside 0..51, max_range outside 1..64, stride_samples < width, a bad band, uint8 planes on a context above
- * 8 bit.  Timed under slot 12 of fhevc_kernel_timing, each launch counted.  The encoder hook does not consume this output. */
+ * 8 bit.  Timed under slot 12 of fhevc_kernel_timing, each launch counted.  The encoder hook does not consume this output.  (Since then:
+ * fhevc_pu_shape_select_device, further below, adds these costs up per partition size and turns them into a mask, on the device.) */
 int  fhevc_motion_refine_pu_wide_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
                                         int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range,
                                         const fhevc_motion_node* d_nodes, fhevc_motion_qpel_node* d_out_nodes,
@@ -557,6 +558,83 @@ int  fhevc_p_depth_range_device(fhevc_ctx* ctx, const fhevc_motion_node* d_nodes
 int  fhevc_p_predict_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
                            const uint8_t* prev_map, int prev_mode, const fhevc_p_rule* rule, uint8_t* depth_min, uint8_t* depth_max);
 
+/* ---- config 4 (P slices): partition sizes per CU from the refined PU costs (k_pu_shape.hip) ---------------------------------------
+ * HM's xCompressCU runs one xCheckRDCostInter, with a motion estimation per PU, for up to seven partition sizes per CU.  What this library offers per
+ * partition size is the sum of its PUs' refined costs; this entry point adds the parts up per partition size on the device and decides which sizes HM
+ * should check.  Partition sizes carry HM's PartSize numbers (TypeDef.h), so a hook can use the mask as it is; 3 (SIZE_NxN) is never produced.  The
+ * library's shape number of fhevc_motion_pu_index is p - 1 for p = 1, 2 and p - 2 for p = 4..7. */
+#define FHEVC_PART_2Nx2N 0
+#define FHEVC_PART_2NxN  1
+#define FHEVC_PART_Nx2N  2
+#define FHEVC_PART_2NxnU 4
+#define FHEVC_PART_2NxnD 5
+#define FHEVC_PART_nLx2N 6
+#define FHEVC_PART_nRx2N 7
+/* Cost table: cost[k][p] per CU node k (0..84, node order as everywhere) and partition size p (0..7), u32, 0xFFFFFFFF = unavailable.
+ *   p = 0             cost_best of refined node k (nodes[k])
+ *   p = 1, 2, 4..7    cost_best(part 0) + cost_best(part 1) of that shape's two PUs: unavailable if either part carries the 0xFFFFFFFF marker, otherwise
+ *                     the 64-bit sum saturated at 0xFFFFFFFE (so a sum is never mistaken for the marker).  The parts, by the formulas of
+ *                     fhevc_motion_pu_index (pus) and fhevc_motion_pu_small_index (pus_small), shape = p - 1 (p <= 2) or p - 2:
+ *                       k = 0..4     pus[k * 12 + shape * 2 + part]
+ *                       k = 5..20    p = 1, 2: pus[60 + (k - 5) * 4 + shape * 2 + part];  p = 4..7: pus_small[(k - 5) * 8 + (shape - 2) * 2 + part]
+ *                       k = 21..84   p = 1, 2: pus_small[128 + (k - 21) * 4 + shape * 2 + part];  p = 4..7 unavailable (HM opens AMP only above the
+ *                                    smallest CU)
+ *   p = 3             always unavailable
+ * With pus_small == NULL everything taken from it is unavailable.  Level l = 0, 1, 2, 3 for k = 0, 1..4, 5..20, 21..84.
+ * A node is valid iff it lies wholly inside the picture, as for every motion entry point; an invalid node gets all eight costs 0xFFFFFFFF,
+ * best = second = 255, mask = avail = 0 and 0xFFFFFFFF in the three cost fields of its record.
+ * best / second are selected in HM's checking order 0, 2, 1, 4, 5, 6, 7 with strict "<": the order of the inter checks in TEncCu::xCompressCU as
+ * hm_patch/restore_inter.py puts them back (Nx2N before 2NxN, then the AMP pairs), and xCheckBestMode replaces only on a strictly smaller cost.
+ * second runs the same scan with best removed. */
+typedef struct {
+  uint32_t cost_2Nx2N;      /* cost[k][0] */
+  uint32_t cost_best;       /* smallest available cost */
+  uint32_t cost_second;     /* smallest available cost among the other sizes, 0xFFFFFFFF if none */
+  uint8_t  best, second;    /* their PartSize numbers, 255 if none */
+  uint8_t  mask;            /* bit p: HM should check PartSize p */
+  uint8_t  avail;           /* bit p: cost[k][p] is available */
+} fhevc_pu_shape_node;      /* 16 bytes */
+/* Mask of a valid node: bit 0 is always set (HM always checks 2Nx2N, even when cost[k][0] is the marker); bit p of an available p is set iff
+ *   cost[k][p] <= cost_best + margin_abs[l] + ((cost_best * margin_q8[l]) >> 8)        evaluated in 64 bits.
+ * With amp_mode == 1 the gate of TEncCu::deriveTestModeAMP (TEncCu.cpp:426-438) is applied afterwards: let b3 be the argmin over p in {0, 2, 1}, in that
+ * order, strict "<", available ones only; bits 4 and 5 are cleared unless b3 is 0 or 1, bits 6 and 7 unless b3 is 0 or 2; none of the three available:
+ * all four AMP bits are cleared.  HM's extra conditions on the merge and skip flags of the best mode are not visible to a source-only pass and are
+ * not modelled. */
+typedef struct {
+  int32_t margin_q8[4];     /* per level, 0..65535: relative margin in 1/256 of cost_best */
+  int32_t margin_abs[4];    /* per level, cost units, >= 0 */
+  int32_t amp_mode;         /* 0 or 1 */
+} fhevc_pu_shape_rule;
+/* margins 0, amp_mode 1: the UNFITTED hard decision (only the sizes that tie with the cheapest one, behind HM's AMP gate) -- not a tuned default; margins
+ * have to be fitted on the reference's own partition choices first */
+void fhevc_pu_shape_rule_default(fhevc_pu_shape_rule* rule);
+/* One CTU, host-side integer logic, no context, no device work (the twin of the kernel, as fhevc_p_depth_range is of k_p_rule.hip).  nodes / pus / pus_small:
+ * the refined entries of the CTU (fhevc_motion_refine*, fhevc_motion_refine_pu*); only cost_best is read.  valid_w / valid_h: the CTU's samples inside the
+ * picture (8..64).  out: 85 records; costs: the 85 x 8 table, or NULL.  FHEVC_E_INVALID: a null nodes, pus, rule or out, valid_w / valid_h outside 8..64, a
+ * margin outside its range, amp_mode outside 0..1. */
+int  fhevc_pu_shape_select(const fhevc_motion_qpel_node* nodes /* 85 */, const fhevc_motion_qpel_node* pus /* 124 */,
+                           const fhevc_motion_qpel_node* pus_small /* 384 or NULL */, int valid_w, int valid_h, const fhevc_pu_shape_rule* rule,
+                           fhevc_pu_shape_node* out /* 85 */, uint32_t* costs /* 85 * 8 or NULL */);
+/* Device form (k_pu_shape.hip): the same bits per CTU with the valid width / height the context's geometry gives it.  d_nodes / d_pus / d_pus_small (may be
+ * NULL): num_pictures * band CTUs * 85 / 124 / 384 entries, compact over the band: exactly what fhevc_motion_refine_pu_wide_device writes for
+ * num_frames = num_pictures + 1 (or the MR = 8 refinements plus fhevc_motion_refine_device).  d_shapes: num_pictures * band CTUs * 85 records; d_costs (may be
+ * NULL): ... * 85 * 8 dwords; both written over exactly that extent, an empty band writes nothing.  rule: HOST memory, read during the call (it travels to the
+ * kernel by value); NULL = fhevc_pu_shape_rule_default.  Asynchronous with respect to the host, allocates nothing, keeps no state: calls with different rules
+ * may be in flight on two streams.  Stream semantics as fhevc_p_depth_range_device (NULL = the context's blocking stream), so a wide search, its refinement
+ * and the selection may follow each other on one stream without a host synchronisation.  The entries may have any alignment their type allows (4 bytes);
+ * where d_shapes and d_costs are 16-byte aligned the outputs leave as 16-byte stores, as dwords otherwise; the bytes written are the same.  Timed under slot 13 of
+ * fhevc_kernel_timing.  FHEVC_E_INVALID with a fhevc_last_error text (nothing is launched or written): a null context, d_nodes, d_pus or d_shapes,
+ * num_pictures < 1, a bad band, a margin outside its range, amp_mode outside 0..1, more than 2^31 - 1 CTUs.  The encoder hook does not consume the mask yet
+ * (INTEGRATION.md). */
+int  fhevc_pu_shape_select_device(fhevc_ctx* ctx, const fhevc_motion_qpel_node* d_nodes, const fhevc_motion_qpel_node* d_pus,
+                                  const fhevc_motion_qpel_node* d_pus_small, int num_pictures, int ctu_row_begin, int ctu_row_end,
+                                  const fhevc_pu_shape_rule* rule, fhevc_pu_shape_node* d_shapes, uint32_t* d_costs, void* stream);
+/* One picture pair, host buffers (both planes with the same stride), synchronous: uploads the pair and runs, on the context's stream,
+ * fhevc_motion_search_pu_wide_device for all three families (search_range 1..64, SAD), fhevc_motion_refine_pu_wide_device with max_range = search_range and the
+ * selection; downloads only the shapes (numCtus * 85 records): 1 360 bytes per CTU come back instead of the 9 488 bytes of refined entries. */
+int  fhevc_p_shape_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                         const fhevc_pu_shape_rule* rule, fhevc_pu_shape_node* shapes /* numCtus * 85 */);
+
 /* CTU-row band of rank `rank` out of `world`: rows [begin, end) */
 int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
 
@@ -567,7 +645,7 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
  * 9 = motion search of the PUs with a 4-sample side (fhevc_motion_search_pu_small*), 10 = quarter-sample refinement of the PUs
  * (fhevc_motion_refine_pu*), 11 = the searches at HM's SearchRange (fhevc_motion_search_pu_wide*: one launch for nodes and PUs, one for the
  * small PUs, each counted), 12 = the refinements at HM's SearchRange (fhevc_motion_refine_pu_wide*: one launch for the nodes, one for the PUs,
- * each counted) */
+ * each counted), 13 = the partition-size selection (fhevc_pu_shape_select_device) */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
 int  fhevc_enable_kernel_timing(fhevc_ctx* ctx, int on);
 
