@@ -38,6 +38,8 @@ SYMBOLS = [
     "fhevc_motion_search_pu_wide", "fhevc_motion_search_pu_wide_device",
     "fhevc_motion_refine_pu_wide", "fhevc_motion_refine_pu_wide_device",
     "fhevc_pu_shape_rule_default", "fhevc_pu_shape_select", "fhevc_pu_shape_select_device", "fhevc_p_shape_frame",
+    "fhevc_motion_centres", "fhevc_motion_centres_device", "fhevc_motion_search_pu_centred", "fhevc_motion_search_pu_centred_device",
+    "fhevc_motion_refine_pu_centred", "fhevc_motion_refine_pu_centred_device",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -216,6 +218,12 @@ def load_library(path=None):
     lib.fhevc_free_host.restype = None
     lib.fhevc_motion_refine_pu_wide.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.fhevc_motion_refine_pu_wide_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    lib.fhevc_motion_centres.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.fhevc_motion_centres_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.fhevc_motion_search_pu_centred.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.fhevc_motion_search_pu_centred_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    lib.fhevc_motion_refine_pu_centred.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    lib.fhevc_motion_refine_pu_centred_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.fhevc_kernel_timing.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     lib.fhevc_enable_kernel_timing.argtypes = [vp, C.c_int]
     lib.fhevc_get_stats.argtypes = [vp, vp, C.c_size_t]
@@ -552,6 +560,79 @@ class Context:
         rb, re = rows if rows is not None else (0, self.ctus_y)
         self._check(self.lib.fhevc_motion_search_pu_wide_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, search_range,
                                                                 d_nodes, d_pus, d_pus_small, stream))
+
+    def motion_centres(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, coarse_range=14):
+        """config 4: one coarse motion centre per CTU from the 4:1 decimated pair (coarse_range 1..14 cells) -> [numCtus] of MOTION_DTYPE; mvx / mvy are
+        multiples of 4 within +-56 whole samples.  This library's own definition (include/fasthevc.h), no HM counterpart."""
+        cur = np.ascontiguousarray(cur_plane).reshape(-1)
+        ref = np.ascontiguousarray(ref_plane).reshape(-1)
+        assert cur.dtype == np.int16 and ref.dtype == np.int16
+        stride = stride if stride is not None else cur_plane.shape[-1]
+        out = np.zeros(self.num_ctus, MOTION_DTYPE)
+        self._check(self.lib.fhevc_motion_centres(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, coarse_range, out.ctypes.data))
+        return out
+
+    def motion_centres_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_centres, rows=None, stream=None, qp=32, coarse_range=14):
+        """frames 1.. of the batch, each searched in the frame before it; d_centres: (num_frames - 1) * band CTUs entries (16 B), one per CTU.
+        Asynchronous; keeps no state between calls."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_motion_centres_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, coarse_range,
+                                                         d_centres, stream))
+
+    def motion_search_pu_centred(self, cur_plane, ref_plane, centres, origin=0, stride=None, qp=32, search_range=8, nodes=True, pus=True, pus_small=True):
+        """config 4: the SAD searches of motion_search_pu_wide in a window of +-search_range (1..8) around one centre per CTU (centres: [numCtus] of
+        MOTION_DTYPE, as motion_centres returns them; only mvx / mvy are read) -> (nodes, pus, pus_small) with ABSOLUTE vectors, None for a family not asked for."""
+        cur = np.ascontiguousarray(cur_plane).reshape(-1)
+        ref = np.ascontiguousarray(ref_plane).reshape(-1)
+        cen = np.ascontiguousarray(centres).reshape(-1)
+        assert cur.dtype == np.int16 and ref.dtype == np.int16 and cen.dtype == MOTION_DTYPE and cen.size == self.num_ctus
+        stride = stride if stride is not None else cur_plane.shape[-1]
+        outs = [np.zeros(self.num_ctus * per_ctu, MOTION_DTYPE) if want else None
+                for want, per_ctu in ((nodes, NODES_PER_CTU), (pus, PUS_PER_CTU), (pus_small, PUS_SMALL_PER_CTU))]
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._check(self.lib.fhevc_motion_search_pu_centred(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, search_range,
+                                                            cen.ctypes.data, ptr(outs[0]), ptr(outs[1]), ptr(outs[2])))
+        return tuple(None if o is None else o.reshape(self.num_ctus, -1) for o in outs)
+
+    def motion_search_pu_centred_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_centres, d_nodes=None, d_pus=None, d_pus_small=None,
+                                        rows=None, stream=None, qp=32, search_range=8):
+        """frames 1.. of the batch, each searched in the frame before it around d_centres ((num_frames - 1) * band CTUs entries, as motion_centres_device
+        writes them); outputs as motion_search_pu_wide_device.  Asynchronous; keeps no state between calls."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_motion_search_pu_centred_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, search_range,
+                                                                   d_centres, d_nodes, d_pus, d_pus_small, stream))
+
+    def motion_refine_pu_centred(self, cur_plane, ref_plane, centres, origin=0, stride=None, qp=32, max_range=8, nodes=None, pus=None, pus_small=None):
+        """config 4: the quarter-sample refinement of motion_search_pu_centred's vectors, priced against the CTU's centre: nodes [numCtus, 85], pus
+        [numCtus, 124], pus_small [numCtus, 384] (MOTION_DTYPE, absolute vectors; only mvx / mvy are read), centres [numCtus] -> (out_nodes, out_pus,
+        out_pus_small) of MOTION_QPEL_DTYPE, None for a family not given.  max_range 1..8 around the centre."""
+        cur = np.ascontiguousarray(cur_plane).reshape(-1)
+        ref = np.ascontiguousarray(ref_plane).reshape(-1)
+        cen = np.ascontiguousarray(centres).reshape(-1)
+        assert cur.dtype == np.int16 and ref.dtype == np.int16 and cen.dtype == MOTION_DTYPE and cen.size == self.num_ctus
+        stride = stride if stride is not None else cur_plane.shape[-1]
+        ins, outs = [], []
+        for a, per_ctu in ((nodes, NODES_PER_CTU), (pus, PUS_PER_CTU), (pus_small, PUS_SMALL_PER_CTU)):
+            if a is None:
+                ins.append(None)
+                outs.append(None)
+            else:
+                a = np.ascontiguousarray(a).reshape(-1)
+                assert a.dtype == MOTION_DTYPE and a.size == self.num_ctus * per_ctu
+                ins.append(a)
+                outs.append(np.zeros(a.size, MOTION_QPEL_DTYPE))
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._check(self.lib.fhevc_motion_refine_pu_centred(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, max_range, cen.ctypes.data,
+                                                            ptr(ins[0]), ptr(outs[0]), ptr(ins[1]), ptr(outs[1]), ptr(ins[2]), ptr(outs[2])))
+        return tuple(None if o is None else o.reshape(self.num_ctus, -1) for o in outs)
+
+    def motion_refine_pu_centred_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_centres, d_nodes=None, d_out_nodes=None, d_pus=None,
+                                        d_out_pus=None, d_pus_small=None, d_out_pus_small=None, rows=None, stream=None, qp=32, max_range=8):
+        """frames 1.. of the batch, each refined in the frame before it around d_centres; inputs as motion_search_pu_centred_device wrote them for the same
+        rows, outputs as many quarter-sample entries (16 B).  Each in / out pair is optional (not all three).  Asynchronous; keeps no state between calls."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_motion_refine_pu_centred_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range, d_centres,
+                                                                   d_nodes, d_out_nodes, d_pus, d_out_pus, d_pus_small, d_out_pus_small, stream))
 
     def motion_refine_pu(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, max_range=4, pus=None, pus_small=None):
         """config 4: the quarter-sample refinement of the PUs' vectors: pus [numCtus, 124] and / or pus_small [numCtus, 384] (MOTION_DTYPE, as

@@ -267,7 +267,7 @@ void fhevc_destroy(fhevc_ctx* c)
   if (c->lw_done) (void)hipEventDestroy(c->lw_done);
   void* const bufs[] = { c->d_frag, c->d_bias, c->d_whead, c->d_bhead, c->d_frag_i8, c->d_bias_i8,                                  // the base image
                          c->f_frag1, c->f_bias1, c->f_frag2, c->f_frag3, c->f_bias_i8, c->f_whead, c->f_headm, c->f_bhead,          // a fused family member's
-                         c->d_luma, c->d_depth, c->d_had, c->d_nodes, c->d_satd, c->d_satd_out, c->d_act, c->d_depth_max, c->d_pair, c->d_motion, c->d_qpel, c->d_motion_pu, c->d_motion_pu_small, c->d_qpel_pu, c->d_qpel_pu_small,
+                         c->d_luma, c->d_depth, c->d_had, c->d_nodes, c->d_satd, c->d_satd_out, c->d_act, c->d_depth_max, c->d_pair, c->d_motion, c->d_qpel, c->d_motion_pu, c->d_motion_pu_small, c->d_centres, c->d_qpel_pu, c->d_qpel_pu_small,
                          c->d_p_maps, c->d_mvtab, c->d_cand_all, c->d_cand, c->d_best4, c->d_modes4 };
   for (void* q : bufs) (void)hipFree(q);
   for (void* q : c->lw_bufs) (void)hipFree(q);
@@ -292,7 +292,7 @@ int fhevc_enable_kernel_timing(fhevc_ctx* c, int on)
 
 int fhevc_kernel_timing(fhevc_ctx* c, int which, int reset, double* avg_ms, uint64_t* launches)
 {
-  if (!c || which < 0 || which > 13) return FHEVC_E_INVALID;
+  if (!c || which < 0 || which > 15 || which == 14) return FHEVC_E_INVALID;   // 14 stays rejected: callers probe it as the first number behind the slots of the partition-size selection
   time_resolve(c);
   if (avg_ms) *avg_ms = c->launches[which] ? c->sum_ms[which] / (double)c->launches[which] : 0.0;
   if (launches) *launches = c->launches[which];
@@ -970,6 +970,100 @@ int fhevc_motion_search_pu_wide(fhevc_ctx* c, const int16_t* cur_luma, const int
   return FHEVC_OK;
 }
 
+// ---- one coarse motion centre per CTU from the 4:1 decimated picture pair (k_motion_coarse.hip) ----
+
+int fhevc_motion_centres_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int coarse_range, fhevc_motion_node* d_centres, void* stream)
+{
+  if (!c || !d_luma || !d_centres) return c ? fail(c, FHEVC_E_INVALID, "bad motion-centre arguments") : FHEVC_E_INVALID;
+  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
+  if (coarse_range < 1 || coarse_range > FHEVC_MOTION_COARSE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "the motion centres cover coarse ranges 1..14");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
+  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
+  // the bit costs travel with the launch: nothing of the context is read or written by it.  Timed under slot 15
+  return launch_on(c, stream, 15, "fhevc_launch_motion_coarse", [&](hipStream_t s) {
+    return fhevc_launch_motion_coarse(fr, coarse_range, mv_bit_cost_table(qp), reinterpret_cast<FhevcMotionNode*>(d_centres), c->num_cus, s);
+  });
+}
+
+int fhevc_motion_centres(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int coarse_range, fhevc_motion_node* centres)
+{
+  if (!c || !cur_luma || !ref_luma || !centres || stride_samples < c->cfg.width)
+    return c ? fail(c, FHEVC_E_INVALID, "bad motion-centre arguments") : FHEVC_E_INVALID;
+  if (qp < 0 || qp > 51 || coarse_range < 1 || coarse_range > FHEVC_MOTION_COARSE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad motion-centre arguments");
+  (void)hipSetDevice(c->device);
+  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
+  if (rc != FHEVC_OK) return rc;
+  // one entry per CTU, through the head of the nodes' staging buffer (85 entries per CTU)
+  rc = fhevc_motion_centres_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, coarse_range,
+                                   reinterpret_cast<fhevc_motion_node*>(c->d_motion), c->stream);
+  if (rc != FHEVC_OK) return rc;
+  const size_t bytes = (size_t)c->num_ctus * sizeof(FhevcMotionNode);
+  HIP_TRY(c, hipMemcpyAsync(centres, c->d_motion, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->stats.bytes_d2h += (uint64_t)bytes;
+  return FHEVC_OK;
+}
+
+// ---- the three integer searches around one centre per CTU (the MR = 8 layouts of k_motion_pu.hip and k_motion_pu_small.hip, centred) ----
+
+int fhevc_motion_search_pu_centred_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                          int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range, const fhevc_motion_node* d_centres,
+                                          fhevc_motion_node* d_nodes, fhevc_motion_node* d_pus, fhevc_motion_node* d_pus_small, void* stream)
+{
+  if (!c || !d_luma || !d_centres || (!d_nodes && !d_pus && !d_pus_small)) return c ? fail(c, FHEVC_E_INVALID, "bad centred PU motion-search arguments") : FHEVC_E_INVALID;
+  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
+  if (search_range < 1 || search_range > FHEVC_MOTION_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "the centred PU motion search covers search ranges 1..8");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
+  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
+  const FhevcMotionNode* centres = reinterpret_cast<const FhevcMotionNode*>(d_centres);
+  FhevcMotionNode* nodes = reinterpret_cast<FhevcMotionNode*>(d_nodes);
+  FhevcMotionNode* pus = reinterpret_cast<FhevcMotionNode*>(d_pus);
+  FhevcMotionNode* small = reinterpret_cast<FhevcMotionNode*>(d_pus_small);
+  // Always SAD.  The window's table of vector costs travels with the launch and prices d = v - P, the vector relative to the centre: exactly
+  // getCostOfVectorWithPredictor with the predictor 4 P.  Whether a centre is in range is the kernel's to decide (the host cannot see device centres).  Nothing of the
+  // context is read or written by the launches.  One launch for nodes and PUs, one for the small PUs, each timed and counted under slot 15
+  if (nodes || pus) {
+    const int rc = launch_on(c, stream, 15, "fhevc_motion_search_pu_centred (nodes, PUs)", [&](hipStream_t s) {
+      return fhevc_launch_motion_pu_centred(fr, search_range, mv_cost_table(qp, search_range), centres, nodes, pus, c->num_cus, s);
+    });
+    if (rc != FHEVC_OK) return rc;
+  }
+  if (!small) return FHEVC_OK;
+  return launch_on(c, stream, 15, "fhevc_motion_search_pu_centred (small PUs)", [&](hipStream_t s) {
+    return fhevc_launch_motion_pu_small_centred(fr, search_range, mv_cost_table(qp, search_range), centres, small, c->num_cus, s);
+  });
+}
+
+int fhevc_motion_search_pu_centred(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                                   const fhevc_motion_node* centres, fhevc_motion_node* nodes, fhevc_motion_node* pus, fhevc_motion_node* pus_small)
+{
+  if (!c || !cur_luma || !ref_luma || !centres || (!nodes && !pus && !pus_small) || stride_samples < c->cfg.width)
+    return c ? fail(c, FHEVC_E_INVALID, "bad centred PU motion-search arguments") : FHEVC_E_INVALID;
+  if (qp < 0 || qp > 51 || search_range < 1 || search_range > FHEVC_MOTION_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad centred PU motion-search arguments");
+  (void)hipSetDevice(c->device);
+  const size_t pu_bytes = (size_t)c->num_ctus * FHEVC_PUS * sizeof(FhevcMotionNode), small_bytes = (size_t)c->num_ctus * FHEVC_PUS_SMALL * sizeof(FhevcMotionNode);
+  const size_t centre_bytes = (size_t)c->num_ctus * sizeof(FhevcMotionNode);
+  if (pus) HIP_TRY(c, ensure(c->d_motion_pu, pu_bytes));
+  if (pus_small) HIP_TRY(c, ensure(c->d_motion_pu_small, small_bytes));
+  HIP_TRY(c, ensure(c->d_centres, centre_bytes));
+  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
+  if (rc != FHEVC_OK) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->d_centres, centres, centre_bytes, hipMemcpyHostToDevice, c->stream));
+  c->stats.bytes_h2d += (uint64_t)centre_bytes;
+  rc = fhevc_motion_search_pu_centred_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, search_range,
+                                             reinterpret_cast<const fhevc_motion_node*>(c->d_centres), nodes ? reinterpret_cast<fhevc_motion_node*>(c->d_motion) : nullptr,
+                                             pus ? reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu) : nullptr,
+                                             pus_small ? reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu_small) : nullptr, c->stream);
+  if (rc != FHEVC_OK) return rc;
+  if (nodes) HIP_TRY(c, hipMemcpyAsync(nodes, c->d_motion, motion_bytes(c), hipMemcpyDeviceToHost, c->stream));
+  if (pus) HIP_TRY(c, hipMemcpyAsync(pus, c->d_motion_pu, pu_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (pus_small) HIP_TRY(c, hipMemcpyAsync(pus_small, c->d_motion_pu_small, small_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->stats.bytes_d2h += (nodes ? (uint64_t)motion_bytes(c) : 0) + (pus ? (uint64_t)pu_bytes : 0) + (pus_small ? (uint64_t)small_bytes : 0);
+  return FHEVC_OK;
+}
+
 // ---- quarter-sample refinement of the search's vectors (k_motion_refine.hip) ----
 
 int fhevc_motion_refine_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
@@ -1127,6 +1221,74 @@ int fhevc_motion_refine_pu_wide(fhevc_ctx* c, const int16_t* cur_luma, const int
   if (pus_small) HIP_TRY(c, hipMemcpyAsync(out_pus_small, c->d_qpel_pu_small, small_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->stats.bytes_d2h += (uint64_t)(node_bytes + pu_bytes + small_bytes);
+  return FHEVC_OK;
+}
+
+// ---- the two refinements around one centre per CTU: what fhevc_motion_search_pu_centred writes feeds straight in (k_motion_refine.hip, k_motion_refine_pu.hip, centred) ----
+
+int fhevc_motion_refine_pu_centred_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                          int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_node* d_centres,
+                                          const fhevc_motion_node* d_nodes, fhevc_motion_qpel_node* d_out_nodes,
+                                          const fhevc_motion_node* d_pus, fhevc_motion_qpel_node* d_out_pus,
+                                          const fhevc_motion_node* d_pus_small, fhevc_motion_qpel_node* d_out_pus_small, void* stream)
+{
+  if (!c || !d_luma || !d_centres || (!d_nodes && !d_pus && !d_pus_small) || !d_nodes != !d_out_nodes || !d_pus != !d_out_pus || !d_pus_small != !d_out_pus_small)
+    return c ? fail(c, FHEVC_E_INVALID, "bad centred PU motion-refinement arguments") : FHEVC_E_INVALID;
+  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
+  if (max_range < 1 || max_range > FHEVC_MOTION_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "the centred PU motion refinement covers max_range 1..8");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
+  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
+  const FhevcMotionNode* centres = reinterpret_cast<const FhevcMotionNode*>(d_centres);
+  // the MR = 8 layouts with the window staged around each CTU's centre; one launch for the nodes, one for both PU families, each timed and counted under slot 15
+  if (d_nodes) {
+    const int rc = launch_on(c, stream, 15, "fhevc_motion_refine_pu_centred (nodes)", [&](hipStream_t s) {
+      return fhevc_launch_motion_refine_centred(fr, max_range, mv_bit_cost_table(qp), centres, reinterpret_cast<const FhevcMotionNode*>(d_nodes),
+                                                reinterpret_cast<FhevcMotionQpelNode*>(d_out_nodes), c->num_cus, s);
+    });
+    if (rc != FHEVC_OK) return rc;
+  }
+  if (!d_pus && !d_pus_small) return FHEVC_OK;
+  return launch_on(c, stream, 15, "fhevc_motion_refine_pu_centred (PUs)", [&](hipStream_t s) {
+    return fhevc_launch_motion_refine_pu_centred(fr, max_range, mv_bit_cost_table(qp), centres, reinterpret_cast<const FhevcMotionNode*>(d_pus), reinterpret_cast<FhevcMotionQpelNode*>(d_out_pus),
+                                                 reinterpret_cast<const FhevcMotionNode*>(d_pus_small), reinterpret_cast<FhevcMotionQpelNode*>(d_out_pus_small), c->num_cus, s);
+  });
+}
+
+int fhevc_motion_refine_pu_centred(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                                   const fhevc_motion_node* centres, const fhevc_motion_node* nodes, fhevc_motion_qpel_node* out_nodes,
+                                   const fhevc_motion_node* pus, fhevc_motion_qpel_node* out_pus,
+                                   const fhevc_motion_node* pus_small, fhevc_motion_qpel_node* out_pus_small)
+{
+  if (!c || !cur_luma || !ref_luma || !centres || stride_samples < c->cfg.width || (!nodes && !pus && !pus_small) || !nodes != !out_nodes || !pus != !out_pus ||
+      !pus_small != !out_pus_small)
+    return c ? fail(c, FHEVC_E_INVALID, "bad centred PU motion-refinement arguments") : FHEVC_E_INVALID;
+  if (qp < 0 || qp > 51 || max_range < 1 || max_range > FHEVC_MOTION_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad centred PU motion-refinement arguments");
+  (void)hipSetDevice(c->device);
+  const size_t pu_bytes = (size_t)c->num_ctus * FHEVC_PUS * sizeof(FhevcMotionNode), small_bytes = (size_t)c->num_ctus * FHEVC_PUS_SMALL * sizeof(FhevcMotionNode);
+  const size_t centre_bytes = (size_t)c->num_ctus * sizeof(FhevcMotionNode);
+  if (nodes) HIP_TRY(c, ensure(c->d_qpel, motion_bytes(c)));
+  if (pus) { HIP_TRY(c, ensure(c->d_motion_pu, pu_bytes)); HIP_TRY(c, ensure(c->d_qpel_pu, pu_bytes)); }
+  if (pus_small) { HIP_TRY(c, ensure(c->d_motion_pu_small, small_bytes)); HIP_TRY(c, ensure(c->d_qpel_pu_small, small_bytes)); }
+  HIP_TRY(c, ensure(c->d_centres, centre_bytes));
+  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
+  if (rc != FHEVC_OK) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->d_centres, centres, centre_bytes, hipMemcpyHostToDevice, c->stream));
+  if (nodes) HIP_TRY(c, hipMemcpyAsync(c->d_motion, nodes, motion_bytes(c), hipMemcpyHostToDevice, c->stream));
+  if (pus) HIP_TRY(c, hipMemcpyAsync(c->d_motion_pu, pus, pu_bytes, hipMemcpyHostToDevice, c->stream));
+  if (pus_small) HIP_TRY(c, hipMemcpyAsync(c->d_motion_pu_small, pus_small, small_bytes, hipMemcpyHostToDevice, c->stream));
+  c->stats.bytes_h2d += (uint64_t)centre_bytes + (nodes ? (uint64_t)motion_bytes(c) : 0) + (pus ? (uint64_t)pu_bytes : 0) + (pus_small ? (uint64_t)small_bytes : 0);
+  rc = fhevc_motion_refine_pu_centred_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, max_range,
+                                             reinterpret_cast<const fhevc_motion_node*>(c->d_centres),
+                                             nodes ? reinterpret_cast<const fhevc_motion_node*>(c->d_motion) : nullptr, nodes ? reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel) : nullptr,
+                                             pus ? reinterpret_cast<const fhevc_motion_node*>(c->d_motion_pu) : nullptr, pus ? reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu) : nullptr,
+                                             pus_small ? reinterpret_cast<const fhevc_motion_node*>(c->d_motion_pu_small) : nullptr,
+                                             pus_small ? reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu_small) : nullptr, c->stream);
+  if (rc != FHEVC_OK) return rc;
+  if (nodes) HIP_TRY(c, hipMemcpyAsync(out_nodes, c->d_qpel, motion_bytes(c), hipMemcpyDeviceToHost, c->stream));
+  if (pus) HIP_TRY(c, hipMemcpyAsync(out_pus, c->d_qpel_pu, pu_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (pus_small) HIP_TRY(c, hipMemcpyAsync(out_pus_small, c->d_qpel_pu_small, small_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->stats.bytes_d2h += (nodes ? (uint64_t)motion_bytes(c) : 0) + (pus ? (uint64_t)pu_bytes : 0) + (pus_small ? (uint64_t)small_bytes : 0);
   return FHEVC_OK;
 }
 

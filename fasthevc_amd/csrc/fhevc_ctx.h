@@ -49,14 +49,15 @@ struct fhevc_ctx {
   bool timing = false;
   std::vector<TimedLaunch> pending;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-  double sum_ms[14] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-  uint64_t launches[14] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+  double sum_ms[16] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };     // slot 14 is not in use (fhevc_kernel_timing rejects it)
+  uint64_t launches[16] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
   double* d_act = nullptr;
   int16_t* d_pair = nullptr;          // two staging planes (reference, current) of fhevc_motion_search
   FhevcMotionNode* d_motion = nullptr;     // ... and, once the refinement has read them, the records of fhevc_p_shape_frame (an entry is as large)
   FhevcMotionQpelNode* d_qpel = nullptr;   // the output of fhevc_motion_refine and the nodes' output of fhevc_motion_refine_pu_wide (host forms); the input nodes go through d_motion
   FhevcMotionNode* d_motion_pu = nullptr;  // the output of fhevc_motion_search_pu (host form); its optional nodes go through d_motion
   FhevcMotionNode* d_motion_pu_small = nullptr;  // the output of fhevc_motion_search_pu_small (host form)
+  FhevcMotionNode* d_centres = nullptr;    // the centres of fhevc_motion_search_pu_centred (host form): one entry per CTU
   FhevcMotionQpelNode* d_qpel_pu = nullptr;        // the outputs of fhevc_motion_refine_pu (host form); its input PUs go through d_motion_pu /
   FhevcMotionQpelNode* d_qpel_pu_small = nullptr;  // d_motion_pu_small
   uint8_t* d_p_maps = nullptr;       // fhevc_p_predict_frame: the reference picture's map, depth_min, depth_max (numCtus * 256 each)

@@ -207,6 +207,22 @@ hipError_t fhevc_launch_motion_pu_small_big(const FhevcFrames& fr, int range, co
 hipError_t fhevc_launch_motion_pu_wide(const FhevcFrames& fr, int range, const FhevcMvBitCost& cost, FhevcMotionNode* d_nodes, FhevcMotionNode* d_pus, FhevcMotionNode* d_pus_small,
                                        int num_cus, hipStream_t stream);
 
+// ---- one coarse motion centre per CTU from the 4:1 decimated picture pair (k_motion_coarse.hip; config 4) --------------------------
+// fr as fhevc_launch_motion; coarse_range 1 .. FHEVC_MOTION_COARSE_MAX_RANGE in decimated cells (vector components of up to +-56 samples); cost: the bit
+// costs of the launch's QP, by value; d_centres: (num_frames - 1) * band CTUs entries, compact over the band
+#define FHEVC_MOTION_COARSE_MAX_RANGE 14
+#define FHEVC_MOTION_CENTRE_MAX 56   // the largest centre component the centred search and refinement take: 56 + 8 stays within HM's SearchRange 64
+hipError_t fhevc_launch_motion_coarse(const FhevcFrames& fr, int coarse_range, const FhevcMvBitCost& cost, FhevcMotionNode* d_centres, int num_cus, hipStream_t stream);
+
+// ---- the integer searches around one centre per CTU (the MR = 8 layouts of k_motion_pu.hip and k_motion_pu_small.hip with a per-CTU window origin; behind
+// fhevc_motion_search_pu_centred).  SAD; range 1 .. FHEVC_MOTION_MAX_RANGE; mvc: the window's table, which prices the vector RELATIVE to the centre;
+// d_centres: (num_frames - 1) * band CTUs entries of which mvx / mvy are read (4-byte aligned); a component outside +-FHEVC_MOTION_CENTRE_MAX marks the CTU's entries.
+// d_nodes / d_pus: either may be null (not both); records hold absolute vectors and, as satd_zero, the SAD at the centre ----
+hipError_t fhevc_launch_motion_pu_centred(const FhevcFrames& fr, int range, const FhevcMvCost& mvc, const FhevcMotionNode* d_centres, FhevcMotionNode* d_nodes,
+                                          FhevcMotionNode* d_pus, int num_cus, hipStream_t stream);
+hipError_t fhevc_launch_motion_pu_small_centred(const FhevcFrames& fr, int range, const FhevcMvCost& mvc, const FhevcMotionNode* d_centres, FhevcMotionNode* d_pus, int num_cus,
+                                                hipStream_t stream);
+
 // ---- quarter-sample refinement of the search's vectors (k_motion_refine.hip; config 4) --------------------------
 struct FhevcMotionQpelNode { uint32_t satd_int, satd_best, cost_best; int16_t mvx, mvy; };
 // fr as fhevc_launch_motion; d_nodes: what it wrote for the same frames and band (only mvx / mvy are read; |component| > max_range: the marker);
@@ -224,6 +240,14 @@ hipError_t fhevc_launch_motion_refine_pu(const FhevcFrames& fr, int max_range, c
 // workgroups of its MR = 64 instance that the device keeps on one CU (hipOccupancyMaxActiveBlocksPerMultiprocessor), for the form that planes of
 // sample_bytes at bit_depth take: the launcher sizes the persistent grid by it, at most two
 hipError_t fhevc_motion_refine_pu_big_residency(int sample_bytes, int bit_depth, int* per_cu);
+
+// ---- the two refinements around one centre per CTU (the MR = 8 layouts with the window staged around the centre; behind fhevc_motion_refine_pu_centred).
+// max_range 1 .. FHEVC_MOTION_MAX_RANGE; d_centres as fhevc_launch_motion_pu_centred; an entry is valid iff its node is inside, the centre in range and
+// |mv - centre| <= max_range; the vector cost of a candidate q is that of q - 4 centre ----
+hipError_t fhevc_launch_motion_refine_centred(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_centres, const FhevcMotionNode* d_nodes,
+                                              FhevcMotionQpelNode* d_out, int num_cus, hipStream_t stream);
+hipError_t fhevc_launch_motion_refine_pu_centred(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_centres, const FhevcMotionNode* d_pus,
+                                                 FhevcMotionQpelNode* d_out_pus, const FhevcMotionNode* d_pus_small, FhevcMotionQpelNode* d_out_small, int num_cus, hipStream_t stream);
 
 // the shipped P-picture rule (fhevc_p_rule_default): see fasthevc.h; regenerate with tests/quality/fit_p_rule.py
 #define FHEVC_P_RULE_WEIGHTS { { 3101, 188, -94, 80, 1149, 1149, 3174, -138, 15748, -351620 }, \

@@ -63,9 +63,11 @@ template <int MR> using SearchCosts = typename std::conditional<(MR > FHEVC_MOTI
 
 // T = int16_t (HM Pel planes) or uint8_t; PACKED = bit depth <= 10; SAD: as fhevc_motion_kernel; MR: the largest range the layout holds (8 or 64);
 // FAM: 0 = the 124 PUs, and the 85 nodes where out_nodes is given (MR = 8); otherwise the families of this instantiation, 1 = nodes | 2 = PUs
-template <typename T, bool PACKED, bool SAD, int MR = FHEVC_MOTION_MAX_RANGE, int FAM = 0>
+// CENTRED (fhevc_motion_search_pu_centred; MR = 8, SAD): the window of every CTU lies around that CTU's entry of `centres` (k_search_tile.h: SearchCentre)
+template <typename T, bool PACKED, bool SAD, int MR = FHEVC_MOTION_MAX_RANGE, int FAM = 0, bool CENTRED = false>
 __global__ __launch_bounds__(256, (MR > FHEVC_MOTION_MAX_RANGE ? 1 : PACKED ? 3 : 2)) void fhevc_motion_pu_kernel(FhevcFrames F, int range, SearchCosts<MR> mvc,
-                                                             FhevcMotionNode* __restrict__ out_nodes, FhevcMotionNode* __restrict__ out_pus)
+                                                             FhevcMotionNode* __restrict__ out_nodes, FhevcMotionNode* __restrict__ out_pus,
+                                                             SearchCentres<CENTRED> centres)
 {
   using Geom = SearchGeom<MR>;
   constexpr int RP = Geom::RP;
@@ -76,7 +78,7 @@ __global__ __launch_bounds__(256, (MR > FHEVC_MOTION_MAX_RANGE ? 1 : PACKED ? 3 
   __shared__ unsigned s_cost[4][ENTRIES], s_idx[4][ENTRIES], s_zero[ENTRIES], s_vc[BIG ? FHEVC_MV_BIT_COSTS : Geom::NMV_MAX];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int tx = lane & 7, ty = lane >> 3;
-  const SearchRange R(range);
+  SearchRange R(range);
   const int total = SearchWork::total(F), nmv = R.nmv, centre = R.centre;
   const int shift = F.bit_depth - 8;
   const bool want_nodes = FAM ? (FAM & 1) != 0 : out_nodes != nullptr;
@@ -89,8 +91,19 @@ __global__ __launch_bounds__(256, (MR > FHEVC_MOTION_MAX_RANGE ? 1 : PACKED ? 3 
   for (int work = blockIdx.x; work < total; work += gridDim.x) {
     const SearchWork W(F, work);
     const int cx = W.cx, cy = W.cy;
+    SearchCentre P;
+    if constexpr (CENTRED) {
+      P = SearchCentre(centres, W.oc(F));
+      if (!P.in_range()) {  // uniform: every entry of this CTU gets the marker, nothing is read for it
+        if (tid < ENTRIES && (tid < FHEVC_NODES ? want_nodes : want_pus))
+          *reinterpret_cast<uint4*>(tid < FHEVC_NODES ? out_nodes + W.oc(F) * FHEVC_NODES + tid : out_pus + W.oc(F) * FHEVC_PUS + (tid - FHEVC_NODES)) = search_record_outside();
+        continue;
+      }
+      R.centre_on(P.x);
+    }
     __syncthreads();  // the previous CTU's readers are done
-    search_stage_window<T, RP>(s_ref, plane, W.ref_base, F, cx, cy, R, tid);
+    if constexpr (CENTRED) search_stage_window<T, RP>(s_ref, plane, W.ref_base, F, cx, cy, R, tid, P.x, P.y);
+    else search_stage_window<T, RP>(s_ref, plane, W.ref_base, F, cx, cy, R, tid);
     // ---- this lane's original 8x8 tile (all four waves hold the same 64 tiles) ----
     const int px = cx * 64 + tx * 8, py = cy * 64 + ty * 8;
     const bool inside = (px + 8 <= F.width) && (py + 8 <= F.height);
@@ -178,6 +191,7 @@ __global__ __launch_bounds__(256, (MR > FHEVC_MOTION_MAX_RANGE ? 1 : PACKED ? 3 
         unsigned c, ix;
         search_merge(&s_cost[0][0], &s_idx[0][0], ENTRIES, tid, c, ix);
         o = search_record(s_zero[tid], c, s_vc[BIG ? search_vector_bits((int)ix, R) : (int)ix], ix, R);
+        if constexpr (CENTRED) o = P.absolute(o);
       }
       FhevcMotionNode* dst = p < 0 ? out_nodes + W.oc(F) * FHEVC_NODES + tid : out_pus + W.oc(F) * FHEVC_PUS + p;
       *reinterpret_cast<uint4*>(dst) = o;  // one 16-byte store per entry
@@ -194,8 +208,25 @@ hipError_t fhevc_launch_motion_pu(const FhevcFrames& fr, int range, const FhevcM
                                   hipStream_t stream)
 {
   return search_launch(fr, range >= 1 && range <= FHEVC_MOTION_MAX_RANGE && d_pus, num_cus, 3, 2, sad, [&](auto t, auto packed, auto sad_c, int grid) {
-    hipLaunchKernelGGL((fhevc_motion_pu_kernel<decltype(t), decltype(packed)::value, decltype(sad_c)::value>), dim3(grid), dim3(256), 0, stream, fr, range, mvc, d_nodes, d_pus);
+    hipLaunchKernelGGL((fhevc_motion_pu_kernel<decltype(t), decltype(packed)::value, decltype(sad_c)::value>), dim3(grid), dim3(256), 0, stream, fr, range, mvc, d_nodes, d_pus, SearchNoCentres{});
     return hipSuccess;
+  });
+}
+
+// the same layout and residency around one centre per CTU (SAD; the window's table prices d, the vector relative to the centre): the families asked for are
+// instantiated (FAM), so a call for the nodes alone runs this kernel too -- its nodes are byte for byte fhevc_motion_kernel's
+hipError_t fhevc_launch_motion_pu_centred(const FhevcFrames& fr, int range, const FhevcMvCost& mvc, const FhevcMotionNode* d_centres, FhevcMotionNode* d_nodes,
+                                          FhevcMotionNode* d_pus, int num_cus, hipStream_t stream)
+{
+  return search_launch(fr, range >= 1 && range <= FHEVC_MOTION_MAX_RANGE && d_centres && (d_nodes || d_pus), num_cus, 3, 2, true, [&](auto t, auto packed, auto sad_c, int grid) {
+    if constexpr (decltype(sad_c)::value) {
+      using T = decltype(t);
+      constexpr bool P = decltype(packed)::value;
+      if (d_nodes && d_pus) hipLaunchKernelGGL((fhevc_motion_pu_kernel<T, P, true, FHEVC_MOTION_MAX_RANGE, 3, true>), dim3(grid), dim3(256), 0, stream, fr, range, mvc, d_nodes, d_pus, d_centres);
+      else if (d_pus) hipLaunchKernelGGL((fhevc_motion_pu_kernel<T, P, true, FHEVC_MOTION_MAX_RANGE, 2, true>), dim3(grid), dim3(256), 0, stream, fr, range, mvc, d_nodes, d_pus, d_centres);
+      else hipLaunchKernelGGL((fhevc_motion_pu_kernel<T, P, true, FHEVC_MOTION_MAX_RANGE, 1, true>), dim3(grid), dim3(256), 0, stream, fr, range, mvc, d_nodes, d_pus, d_centres);
+      return hipSuccess;
+    } else return hipErrorInvalidValue;
   });
 }
 
@@ -211,7 +242,7 @@ hipError_t fhevc_launch_motion_pu_big(const FhevcFrames& fr, int range, const Fh
       auto go = [&](auto kernel) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, stream, fr, range, cost, d_nodes, d_pus);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, stream, fr, range, cost, d_nodes, d_pus, SearchNoCentres{});
         return hipSuccess;
       };
       using T = decltype(t);

@@ -41,9 +41,10 @@ __device__ __forceinline__ unsigned quad(unsigned v)
 template <int MR> using SearchCosts = typename std::conditional<(MR > FHEVC_MOTION_MAX_RANGE), FhevcMvBitCost, FhevcMvCost>::type;
 
 // T = int16_t (HM Pel planes) or uint8_t; PACKED = bit depth <= 10; SAD: as fhevc_motion_kernel; MR: the largest range the layout holds (8 or 64)
-template <typename T, bool PACKED, bool SAD, int MR = FHEVC_MOTION_MAX_RANGE>
+// CENTRED (fhevc_motion_search_pu_centred; MR = 8, SAD): the window of every CTU lies around that CTU's entry of `centres` (k_search_tile.h: SearchCentre)
+template <typename T, bool PACKED, bool SAD, int MR = FHEVC_MOTION_MAX_RANGE, bool CENTRED = false>
 __global__ __launch_bounds__(256, (MR > FHEVC_MOTION_MAX_RANGE ? 1 : PACKED ? 4 : 3)) void fhevc_motion_pu_small_kernel(FhevcFrames F, int range, SearchCosts<MR> mvc,
-                                                                                                         FhevcMotionNode* __restrict__ out_pus)
+                                                                                                         FhevcMotionNode* __restrict__ out_pus, SearchCentres<CENTRED> centres)
 {
   using Geom = SearchGeom<MR>;
   constexpr int RP = Geom::RP;
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(256, (MR > FHEVC_MOTION_MAX_RANGE ? 1 : PACKED ? 4 
   const int amp_shape = quad_pos == 0 ? 0 : quad_pos == 1 ? 3 : quad_pos == 2 ? 2 : 1;
   const int e_tile = AMP_ENTRIES + (ty * 8 + tx) * 4, e_amp = node16 * 8 + amp_shape * 2;
   const bool strip_is_part0 = (quad_pos & 1) == 0;  // 2NxnU and nLx2N: the quarter strip comes first
-  const SearchRange R(range);
+  SearchRange R(range);
   const int total = SearchWork::total(F), nmv = R.nmv, centre = R.centre;
   const int shift = F.bit_depth - 8;
   const T* plane = reinterpret_cast<const T*>(F.luma);
@@ -70,8 +71,18 @@ __global__ __launch_bounds__(256, (MR > FHEVC_MOTION_MAX_RANGE ? 1 : PACKED ? 4 
   for (int work = blockIdx.x; work < total; work += gridDim.x) {
     const SearchWork W(F, work);
     const int cx = W.cx, cy = W.cy;
+    SearchCentre P;
+    if constexpr (CENTRED) {
+      P = SearchCentre(centres, W.oc(F));
+      if (!P.in_range()) {  // uniform: every entry of this CTU gets the marker, nothing is read for it
+        for (int e = tid; e < ENTRIES; e += 256) *reinterpret_cast<uint4*>(out_pus + W.oc(F) * ENTRIES + e) = search_record_outside();
+        continue;
+      }
+      R.centre_on(P.x);
+    }
     __syncthreads();  // the previous CTU's readers are done
-    search_stage_window<T, RP>(s_ref, plane, W.ref_base, F, cx, cy, R, tid);
+    if constexpr (CENTRED) search_stage_window<T, RP>(s_ref, plane, W.ref_base, F, cx, cy, R, tid, P.x, P.y);
+    else search_stage_window<T, RP>(s_ref, plane, W.ref_base, F, cx, cy, R, tid);
     // ---- this lane's original 8x8 tile (all four waves hold the same 64 tiles) ----
     const int px = cx * 64 + tx * 8, py = cy * 64 + ty * 8;
     const bool inside = (px + 8 <= F.width) && (py + 8 <= F.height);
@@ -165,6 +176,7 @@ __global__ __launch_bounds__(256, (MR > FHEVC_MOTION_MAX_RANGE ? 1 : PACKED ? 4 
         unsigned c, ix;
         search_merge(&s_cost[0][0], &s_idx[0][0], ENTRIES, e, c, ix);
         o = search_record(s_zero[e], c, s_vc[BIG ? search_vector_bits((int)ix, R) : (int)ix], ix, R);
+        if constexpr (CENTRED) o = P.absolute(o);
       }
       *reinterpret_cast<uint4*>(out_pus + W.oc(F) * ENTRIES + e) = o;  // one 16-byte store per entry
     }
@@ -179,8 +191,21 @@ __global__ __launch_bounds__(256, (MR > FHEVC_MOTION_MAX_RANGE ? 1 : PACKED ? 4 
 hipError_t fhevc_launch_motion_pu_small(const FhevcFrames& fr, int range, const FhevcMvCost& mvc, FhevcMotionNode* d_pus, int num_cus, bool sad, hipStream_t stream)
 {
   return search_launch(fr, range >= 1 && range <= FHEVC_MOTION_MAX_RANGE && d_pus, num_cus, 4, 3, sad, [&](auto t, auto packed, auto sad_c, int grid) {
-    hipLaunchKernelGGL((fhevc_motion_pu_small_kernel<decltype(t), decltype(packed)::value, decltype(sad_c)::value>), dim3(grid), dim3(256), 0, stream, fr, range, mvc, d_pus);
+    hipLaunchKernelGGL((fhevc_motion_pu_small_kernel<decltype(t), decltype(packed)::value, decltype(sad_c)::value>), dim3(grid), dim3(256), 0, stream, fr, range, mvc, d_pus, SearchNoCentres{});
     return hipSuccess;
+  });
+}
+
+// the same layout and residency around one centre per CTU (SAD; the window's table prices d, the vector relative to the centre)
+hipError_t fhevc_launch_motion_pu_small_centred(const FhevcFrames& fr, int range, const FhevcMvCost& mvc, const FhevcMotionNode* d_centres, FhevcMotionNode* d_pus, int num_cus,
+                                                hipStream_t stream)
+{
+  return search_launch(fr, range >= 1 && range <= FHEVC_MOTION_MAX_RANGE && d_centres && d_pus, num_cus, 4, 3, true, [&](auto t, auto packed, auto sad_c, int grid) {
+    if constexpr (decltype(sad_c)::value) {
+      hipLaunchKernelGGL((fhevc_motion_pu_small_kernel<decltype(t), decltype(packed)::value, true, FHEVC_MOTION_MAX_RANGE, true>), dim3(grid), dim3(256), 0, stream, fr, range, mvc, d_pus,
+                         d_centres);
+      return hipSuccess;
+    } else return hipErrorInvalidValue;
   });
 }
 
@@ -194,7 +219,7 @@ hipError_t fhevc_launch_motion_pu_small_big(const FhevcFrames& fr, int range, co
       const auto kernel = &fhevc_motion_pu_small_kernel<decltype(t), decltype(packed)::value, true, MRB>;
       const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, stream, fr, range, cost, d_pus);
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, stream, fr, range, cost, d_pus, SearchNoCentres{});
       return hipSuccess;
     } else return hipErrorInvalidValue;
   });

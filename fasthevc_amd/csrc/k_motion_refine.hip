@@ -28,9 +28,12 @@
 namespace {
 
 // T = int16_t (HM Pel planes) or uint8_t; PACKED = bit depth <= 10 (the packed Hadamard); MR = 8 or 64: the largest integer vector the window is laid out for
-template <typename T, bool PACKED, int MR>
+// CENTRED (fhevc_motion_refine_pu_centred; MR = 8): the window of every CTU is staged around that CTU's centre P (k_search_tile.h: SearchCentre) and the kernel
+// works on vectors RELATIVE to P -- an input vector is valid iff |mv - P| <= max_range, the cost of a candidate q is that of q - 4 P, which is
+// getCostOfVectorWithPredictor with the predictor 4 P -- and adds 4 P to the winner.  The samples a candidate reads are those of the absolute vector
+template <typename T, bool PACKED, int MR, bool CENTRED = false>
 __global__ __launch_bounds__(256) void fhevc_motion_refine_kernel(FhevcFrames F, int max_range, FhevcMvBitCost cost, const FhevcMotionNode* __restrict__ nodes,
-                                                                  FhevcMotionQpelNode* __restrict__ out)
+                                                                  FhevcMotionQpelNode* __restrict__ out, SearchCentres<CENTRED> centres)
 {
   constexpr int RP = RefineGeom<MR>::RP;
   constexpr bool BIG = MR > FHEVC_MOTION_MAX_RANGE;
@@ -61,9 +64,18 @@ __global__ __launch_bounds__(256) void fhevc_motion_refine_kernel(FhevcFrames F,
     const int cy = F.row_begin + rem / F.ctus_x, cx = rem % F.ctus_x;
     const long long cur_base = (long long)f * F.frame_stride, ref_base = (long long)(f - 1) * F.frame_stride;
     const long long oc = (long long)((f - 1) * band_rows + (cy - F.row_begin)) * F.ctus_x + cx;
+    SearchCentre P;
+    if constexpr (CENTRED) {
+      P = SearchCentre(centres, oc);
+      if (!P.in_range()) {  // uniform: every node of this CTU gets the marker, nothing is read for it
+        if (writer) { FhevcMotionQpelNode o; o.satd_int = o.satd_best = o.cost_best = 0xFFFFFFFFu; o.mvx = 0; o.mvy = 0; out[oc * FHEVC_NODES + nidx] = o; }
+        continue;
+      }
+    }
     // ---- stage the reference window: rows cy*64 - MR - 4 .., columns cx*64 - MR - 4 .., coordinates clamped to the picture ----
     __syncthreads();  // the previous CTU's readers are done
-    refine_stage_window<T, MR>(s_ref, plane, ref_base, F, cx, cy, tid);
+    if constexpr (CENTRED) refine_stage_window<T, MR>(s_ref, plane, ref_base, F, cx, cy, tid, P.x, P.y);
+    else refine_stage_window<T, MR>(s_ref, plane, ref_base, F, cx, cy, tid);
     // ---- this lane's original 8x8 tile (all four waves hold the same 64 tiles) ----
     const int px = cx * 64 + tx * 8, py = cy * 64 + ty * 8;
     const bool inside = (px + 8 <= F.width) && (py + 8 <= F.height);
@@ -76,6 +88,7 @@ __global__ __launch_bounds__(256) void fhevc_motion_refine_kernel(FhevcFrames F,
     if (node_in) {
       const unsigned w = reinterpret_cast<const unsigned*>(nodes)[(oc * FHEVC_NODES + nidx) * 4 + 3];
       mx = (int)(short)(w & 0xFFFFu); my = (int)(short)(w >> 16);
+      if constexpr (CENTRED) { mx -= P.x; my -= P.y; }
       valid = abs(mx) <= max_range && abs(my) <= max_range;
       if (!valid) { mx = 0; my = 0; }  // the arithmetic below stays inside the window; its result is dropped
     }
@@ -114,6 +127,7 @@ __global__ __launch_bounds__(256) void fhevc_motion_refine_kernel(FhevcFrames F,
     }
     if (writer) {
       FhevcMotionQpelNode o;
+      if constexpr (CENTRED) { best_x += 4 * P.x; best_y += 4 * P.y; }
       if (valid) { o.satd_int = satd_int; o.satd_best = best_s; o.cost_best = best_c; o.mvx = (short)best_x; o.mvy = (short)best_y; }
       else { o.satd_int = o.satd_best = o.cost_best = 0xFFFFFFFFu; o.mvx = 0; o.mvy = 0; }
       out[oc * FHEVC_NODES + nidx] = o;
@@ -127,19 +141,40 @@ hipError_t launch_refine(const FhevcFrames& fr, int max_range, const FhevcMvBitC
 {
   if (max_range <= FHEVC_MOTION_MAX_RANGE) {
     const int grid = (int)(total < 4LL * num_cus ? total : 4LL * num_cus);
-    hipLaunchKernelGGL((fhevc_motion_refine_kernel<T, PACKED, FHEVC_MOTION_MAX_RANGE>), dim3(grid), dim3(256), 0, stream, fr, max_range, cost, d_nodes, d_out);
+    hipLaunchKernelGGL((fhevc_motion_refine_kernel<T, PACKED, FHEVC_MOTION_MAX_RANGE>), dim3(grid), dim3(256), 0, stream, fr, max_range, cost, d_nodes, d_out, SearchNoCentres{});
   } else {
     constexpr int MRB = FHEVC_MOTION_WIDE_MAX_RANGE;
     const size_t lds = (size_t)RefineGeom<MRB>::SAMPLES * sizeof(short);  // 80 016 B: one workgroup per CU beside another kernel's, two alone
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fhevc_motion_refine_kernel<T, PACKED, MRB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     const int grid = (int)(total < 2LL * num_cus ? total : 2LL * num_cus);
-    hipLaunchKernelGGL((fhevc_motion_refine_kernel<T, PACKED, MRB>), dim3(grid), dim3(256), lds, stream, fr, max_range, cost, d_nodes, d_out);
+    hipLaunchKernelGGL((fhevc_motion_refine_kernel<T, PACKED, MRB>), dim3(grid), dim3(256), lds, stream, fr, max_range, cost, d_nodes, d_out, SearchNoCentres{});
   }
   return hipGetLastError();
 }
 
+template <typename T, bool PACKED>
+hipError_t launch_refine_centred(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_centres, const FhevcMotionNode* d_nodes,
+                                 FhevcMotionQpelNode* d_out, int num_cus, long long total, hipStream_t stream)
+{
+  const int grid = (int)(total < 4LL * num_cus ? total : 4LL * num_cus);
+  hipLaunchKernelGGL((fhevc_motion_refine_kernel<T, PACKED, FHEVC_MOTION_MAX_RANGE, true>), dim3(grid), dim3(256), 0, stream, fr, max_range, cost, d_nodes, d_out, d_centres);
+  return hipGetLastError();
+}
+
 }  // namespace
+
+// the MR = 8 layout around one centre per CTU (behind fhevc_motion_refine_pu_centred): max_range 1 .. FHEVC_MOTION_MAX_RANGE
+hipError_t fhevc_launch_motion_refine_centred(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_centres, const FhevcMotionNode* d_nodes,
+                                              FhevcMotionQpelNode* d_out, int num_cus, hipStream_t stream)
+{
+  const long long total = (long long)(fr.row_end - fr.row_begin) * fr.ctus_x * (fr.num_frames - 1);
+  if (total <= 0) return hipSuccess;
+  if (max_range < 1 || max_range > FHEVC_MOTION_MAX_RANGE || !d_centres) return hipErrorInvalidValue;
+  if (fr.sample_bytes == 2 && fr.bit_depth <= 10) return launch_refine_centred<int16_t, true>(fr, max_range, cost, d_centres, d_nodes, d_out, num_cus, total, stream);
+  if (fr.sample_bytes == 2) return launch_refine_centred<int16_t, false>(fr, max_range, cost, d_centres, d_nodes, d_out, num_cus, total, stream);
+  return launch_refine_centred<uint8_t, true>(fr, max_range, cost, d_centres, d_nodes, d_out, num_cus, total, stream);
+}
 
 hipError_t fhevc_launch_motion_refine(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_nodes, FhevcMotionQpelNode* d_out,
                                       int num_cus, hipStream_t stream)

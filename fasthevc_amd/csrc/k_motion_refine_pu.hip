@@ -62,10 +62,12 @@ __device__ __forceinline__ unsigned pu_sum(unsigned t8, int lane, int n, int s, 
 
 // T = int16_t (HM Pel planes) or uint8_t; PACKED = bit depth <= 10 (the packed Hadamards); MR = 8 or 64: the largest integer vector the window is laid
 // out for; stage_full (MR = 64 only): stage the whole window, not only what max_range reaches
-template <typename T, bool PACKED, int MR>
+// CENTRED (fhevc_motion_refine_pu_centred; MR = 8): as fhevc_motion_refine_kernel's -- the window staged around the CTU's centre P, vectors relative to P inside,
+// 4 P added to the winner
+template <typename T, bool PACKED, int MR, bool CENTRED = false>
 __global__ __launch_bounds__(256) void fhevc_motion_refine_pu_kernel(FhevcFrames F, int max_range, FhevcMvBitCost cost, const FhevcMotionNode* __restrict__ pus,
                                                                      FhevcMotionQpelNode* __restrict__ out_pus, const FhevcMotionNode* __restrict__ pus_small,
-                                                                     FhevcMotionQpelNode* __restrict__ out_small, bool stage_full)
+                                                                     FhevcMotionQpelNode* __restrict__ out_small, bool stage_full, SearchCentres<CENTRED> centres)
 {
   constexpr int RP = RefineGeom<MR>::RP;
   constexpr bool BIG = MR > FHEVC_MOTION_MAX_RANGE;
@@ -92,8 +94,21 @@ __global__ __launch_bounds__(256) void fhevc_motion_refine_pu_kernel(FhevcFrames
     const int cy = F.row_begin + rem / F.ctus_x, cx = rem % F.ctus_x;
     const long long cur_base = (long long)f * F.frame_stride, ref_base = (long long)(f - 1) * F.frame_stride;
     const long long oc = (long long)((f - 1) * band_rows + (cy - F.row_begin)) * F.ctus_x + cx;
+    SearchCentre P;
+    if constexpr (CENTRED) {
+      P = SearchCentre(centres, oc);
+      if (!P.in_range()) {  // uniform: every entry of this CTU gets the marker, nothing is read for it
+        FhevcMotionQpelNode o;
+        o.satd_int = o.satd_best = o.cost_best = 0xFFFFFFFFu; o.mvx = 0; o.mvy = 0;
+        if (pus && tid < FHEVC_PUS) out_pus[oc * FHEVC_PUS + tid] = o;
+        if (pus_small)
+          for (int e = tid; e < FHEVC_PUS_SMALL; e += 256) out_small[oc * FHEVC_PUS_SMALL + e] = o;
+        continue;
+      }
+    }
     __syncthreads();  // the previous CTU's readers are done
-    if (BIG && !stage_full) refine_stage_window_reach<T, MR>(s_ref, plane, ref_base, F, cx, cy, tid, max_range);
+    if constexpr (CENTRED) refine_stage_window<T, MR>(s_ref, plane, ref_base, F, cx, cy, tid, P.x, P.y);
+    else if (BIG && !stage_full) refine_stage_window_reach<T, MR>(s_ref, plane, ref_base, F, cx, cy, tid, max_range);
     else refine_stage_window<T, MR>(s_ref, plane, ref_base, F, cx, cy, tid);
     // ---- this lane's original 8x8 tile (all four waves hold the same 64 tiles) ----
     const int px = cx * 64 + tx * 8, py = cy * 64 + ty * 8;
@@ -141,6 +156,7 @@ __global__ __launch_bounds__(256) void fhevc_motion_refine_pu_kernel(FhevcFrames
       if (node_in) {
         const unsigned w = reinterpret_cast<const unsigned*>(small ? pus_small : pus)[e * 4 + 3];
         mx = (int)(short)(w & 0xFFFFu); my = (int)(short)(w >> 16);
+        if constexpr (CENTRED) { mx -= P.x; my -= P.y; }
         valid = abs(mx) <= max_range && abs(my) <= max_range;
         if (!valid) { mx = 0; my = 0; }  // the arithmetic below stays inside the window; its result is dropped
       }
@@ -185,6 +201,7 @@ __global__ __launch_bounds__(256) void fhevc_motion_refine_pu_kernel(FhevcFrames
       }
       if (rep) {
         FhevcMotionQpelNode o;
+        if constexpr (CENTRED) { best_x += 4 * P.x; best_y += 4 * P.y; }
         if (valid) { o.satd_int = satd_int; o.satd_best = best_s; o.cost_best = best_c; o.mvx = (short)best_x; o.mvy = (short)best_y; }
         else { o.satd_int = o.satd_best = o.cost_best = 0xFFFFFFFFu; o.mvx = 0; o.mvy = 0; }
         (small ? out_small : out_pus)[e] = o;
@@ -222,7 +239,7 @@ hipError_t launch_refine_pu(const FhevcFrames& fr, int max_range, const FhevcMvB
     const long long resident = (long long)WG_PER_CU * num_cus;
     const int grid = (int)(total < resident ? total : resident);
     hipLaunchKernelGGL((fhevc_motion_refine_pu_kernel<T, PACKED, FHEVC_MOTION_MAX_RANGE>), dim3(grid), dim3(256), 0, stream, fr, max_range, cost, d_pus, d_out_pus,
-                       d_pus_small, d_out_small, false);
+                       d_pus_small, d_out_small, false, SearchNoCentres{});
   } else {
     using Big = RefinePuBig<T, PACKED>;
     int per_cu = 0;
@@ -232,7 +249,7 @@ hipError_t launch_refine_pu(const FhevcFrames& fr, int max_range, const FhevcMvB
     const long long resident = (long long)(per_cu < WG_PER_CU ? per_cu : WG_PER_CU) * num_cus;   // what is actually resident, at most what the VGPRs allow
     const int grid = (int)(total < resident ? total : resident);
     hipLaunchKernelGGL((fhevc_motion_refine_pu_kernel<T, PACKED, Big::MRB>), dim3(grid), dim3(256), Big::LDS, stream, fr, max_range, cost, d_pus, d_out_pus,
-                       d_pus_small, d_out_small, stage_full);
+                       d_pus_small, d_out_small, stage_full, SearchNoCentres{});
   }
   return hipGetLastError();
 }
@@ -250,6 +267,25 @@ hipError_t fhevc_launch_motion_refine_pu(const FhevcFrames& fr, int max_range, c
   else if (fr.sample_bytes == 2) FHEVC_REFINE_PU(int16_t, false);
   else FHEVC_REFINE_PU(uint8_t, true);
 #undef FHEVC_REFINE_PU
+}
+
+// the MR = 8 layout around one centre per CTU (behind fhevc_motion_refine_pu_centred): max_range 1 .. FHEVC_MOTION_MAX_RANGE, the same residency
+hipError_t fhevc_launch_motion_refine_pu_centred(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_centres, const FhevcMotionNode* d_pus,
+                                                 FhevcMotionQpelNode* d_out_pus, const FhevcMotionNode* d_pus_small, FhevcMotionQpelNode* d_out_small, int num_cus, hipStream_t stream)
+{
+  const long long total = (long long)(fr.row_end - fr.row_begin) * fr.ctus_x * (fr.num_frames - 1);
+  if (total <= 0) return hipSuccess;
+  if (max_range < 1 || max_range > FHEVC_MOTION_MAX_RANGE || !d_centres || (!d_pus && !d_pus_small) || !d_pus != !d_out_pus || !d_pus_small != !d_out_small) return hipErrorInvalidValue;
+  const long long resident = (long long)WG_PER_CU * num_cus;
+  const int grid = (int)(total < resident ? total : resident);
+#define FHEVC_REFINE_PU_CENTRED(T, P)                                                                                                                              \
+  hipLaunchKernelGGL((fhevc_motion_refine_pu_kernel<T, P, FHEVC_MOTION_MAX_RANGE, true>), dim3(grid), dim3(256), 0, stream, fr, max_range, cost, d_pus, d_out_pus, \
+                     d_pus_small, d_out_small, false, d_centres)
+  if (fr.sample_bytes == 2 && fr.bit_depth <= 10) FHEVC_REFINE_PU_CENTRED(int16_t, true);
+  else if (fr.sample_bytes == 2) FHEVC_REFINE_PU_CENTRED(int16_t, false);
+  else FHEVC_REFINE_PU_CENTRED(uint8_t, true);
+#undef FHEVC_REFINE_PU_CENTRED
+  return hipGetLastError();
 }
 
 // workgroups of the MR = 64 instance that the device keeps on one CU, for the form that planes of sample_bytes at bit_depth take (measurement tools)

@@ -46,13 +46,15 @@ struct RefineArith {
 
 // ---- one chunk of 4 samples of the reference window of CTU (cx, cy): window row wr, columns wc .. wc + 3 = picture row cy*64 - MR - 4 + wr, columns
 // cx*64 - MR - 4 + wc .., coordinates clamped to the picture.  The window's first column is a multiple of 4, so a chunk inside the picture is ONE 8-byte
-// (uint8 planes: 4-byte) load where the plane allows it, and one 8-byte LDS store ----
+// (uint8 planes: 4-byte) load where the plane allows it, and one 8-byte LDS store.  The centred refinements move the window by their centre (ox, oy): the
+// coarse centres are multiples of 4, so their chunks keep the one-load form; any other centre goes through the per-sample form ----
 template <typename T, int MR>
-__device__ __forceinline__ void refine_stage_chunk(short* s_ref, const T* plane, long long ref_base, const FhevcFrames& F, int cx, int cy, int wr, int wc)
+__device__ __forceinline__ void refine_stage_chunk(short* s_ref, const T* plane, long long ref_base, const FhevcFrames& F, int cx, int cy, int wr, int wc,
+                                                   int ox = 0, int oy = 0)
 {
   constexpr int RP = RefineGeom<MR>::RP;
-  const int py = min(max(cy * 64 - MR - 4 + wr, 0), F.height - 1);
-  const int px0 = cx * 64 - MR - 4 + wc;
+  const int py = min(max(cy * 64 - MR - 4 + oy + wr, 0), F.height - 1);
+  const int px0 = cx * 64 - MR - 4 + ox + wc;
   const long long row = ref_base + (long long)py * F.stride;
   const T* src = plane + row + px0;
   uint2 q;
@@ -73,12 +75,13 @@ __device__ __forceinline__ void refine_stage_chunk(short* s_ref, const T* plane,
 
 // ---- stage the whole reference window of CTU (cx, cy): rows cy*64 - MR - 4 .., columns cx*64 - MR - 4 .. ----
 template <typename T, int MR>
-__device__ __forceinline__ void refine_stage_window(short* s_ref, const T* plane, long long ref_base, const FhevcFrames& F, int cx, int cy, int tid)
+__device__ __forceinline__ void refine_stage_window(short* s_ref, const T* plane, long long ref_base, const FhevcFrames& F, int cx, int cy, int tid,
+                                                    int ox = 0, int oy = 0)
 {
   constexpr int CH = RefineGeom<MR>::RP / 4;
   for (int it = tid; it < RefineGeom<MR>::ROWS * CH; it += 256) {
     const int wr = it / CH, wc = (it - wr * CH) * 4;
-    refine_stage_chunk<T, MR>(s_ref, plane, ref_base, F, cx, cy, wr, wc);
+    refine_stage_chunk<T, MR>(s_ref, plane, ref_base, F, cx, cy, wr, wc, ox, oy);
   }
 }
 

@@ -22,12 +22,15 @@ template <int MR> struct SearchGeom {
 template <typename T>
 __device__ __forceinline__ int sample_of(const T* plane, long long off) { return (int)plane[off]; }
 
-// the window of one launch: (2 range + 1)^2 vectors in raster order, the zero vector in the middle
+// the window of one launch: (2 range + 1)^2 vectors in raster order, the zero vector in the middle -- or, in the centred searches, the CTU's centre:
+// every vector of the window is then relative to the centre, and the kernel calls centre_on() per CTU
 struct SearchRange {
   int range, side, nmv, centre, win, delta;
   __device__ __forceinline__ explicit SearchRange(int r)
     : range(r), side(2 * r + 1), nmv(side * side), centre((nmv - 1) >> 1), win(64 + 2 * r),
       delta((8 - (r & 7)) & 7) {}  // the window starts at column 64 cx - range: delta samples after a multiple of 8
+  // ... at column 64 cx - range + px where the window lies around a centre whose horizontal component is px (px = 0: the value above)
+  __device__ __forceinline__ void centre_on(int px) { delta = (px - range) & 7; }
   // vector m seen from tile (tx, ty): window column and row of the displaced block's first sample
   __device__ __forceinline__ void at(int m, int tx, int ty, int& col, int& row0) const
   {
@@ -58,17 +61,19 @@ struct SearchWork {
   __device__ __forceinline__ long long oc(const FhevcFrames& F) const { return (long long)((f - 1) * (F.row_end - F.row_begin) + (cy - F.row_begin)) * F.ctus_x + cx; }
 };
 
-// ---- stage the reference window of CTU (cx, cy): rows cy*64 - R .. + win, columns cx*64 - R .. + win, coordinates clamped to the picture ----
+// ---- stage the reference window of CTU (cx, cy): rows cy*64 - R .. + win, columns cx*64 - R .. + win, coordinates clamped to the picture; the centred
+// searches move the window by their centre (ox, oy), after R.centre_on(ox) ----
 template <typename T, int RP>
-__device__ __forceinline__ void search_stage_window(short* s_ref, const T* plane, long long ref_base, const FhevcFrames& F, int cx, int cy, const SearchRange& R, int tid)
+__device__ __forceinline__ void search_stage_window(short* s_ref, const T* plane, long long ref_base, const FhevcFrames& F, int cx, int cy, const SearchRange& R, int tid,
+                                                    int ox = 0, int oy = 0)
 {
   // chunks of 8 samples starting at a column that is a multiple of 8 (delta = what the window's first column lacks to one): a chunk
   // inside the picture is ONE 16-byte (uint8 planes: 8-byte) load where the plane allows it, and one 16-byte LDS store
   const int chunks = (R.win + R.delta + 7) >> 3;
   for (int it = tid; it < R.win * chunks; it += 256) {
     const int wr = it / chunks, wc = (it - wr * chunks) * 8;
-    const int py = min(max(cy * 64 - R.range + wr, 0), F.height - 1);
-    const int px0 = cx * 64 - R.range - R.delta + wc;
+    const int py = min(max(cy * 64 - R.range + oy + wr, 0), F.height - 1);
+    const int px0 = cx * 64 - R.range + ox - R.delta + wc;
     short v[8];
     const long long row = ref_base + (long long)py * F.stride;
     const T* src = plane + row + px0;
@@ -212,6 +217,29 @@ __device__ __forceinline__ uint4 search_record(unsigned zero, unsigned c, unsign
   return make_uint4(zero, c - vc, c, ((unsigned)mvx & 0xFFFFu) | ((unsigned)mvy << 16));
 }
 __device__ __forceinline__ uint4 search_record_outside() { return make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u); }
+
+// ---- the centred searches (fhevc_motion_search_pu_centred): the CTU's centre P, of which only mvx / mvy are read (one dword: an entry is 4-byte aligned by its
+// type, whatever else the caller's pointer is).  Candidates are P + d, d in [-R, R]^2; the vector cost is that of d (the predictor is P), so the window's table of
+// the zero-centred search serves; a centre with a component outside +-FHEVC_MOTION_CENTRE_MAX marks every entry of its CTU and nothing is read for it ----
+struct SearchNoCentres {};
+template <bool CENTRED> using SearchCentres = typename std::conditional<CENTRED, const FhevcMotionNode*, SearchNoCentres>::type;
+struct SearchCentre {
+  int x, y;
+  __device__ __forceinline__ SearchCentre() : x(0), y(0) {}
+  __device__ __forceinline__ SearchCentre(const FhevcMotionNode* centres, long long oc)
+  {
+    const unsigned v = reinterpret_cast<const unsigned*>(centres + oc)[3];
+    x = (int)(short)(v & 0xFFFFu); y = (int)(short)(v >> 16);
+  }
+  __device__ __forceinline__ bool in_range() const { return abs(x) <= FHEVC_MOTION_CENTRE_MAX && abs(y) <= FHEVC_MOTION_CENTRE_MAX; }
+  // the record of a searched entry with its vector made absolute
+  __device__ __forceinline__ uint4 absolute(uint4 rec) const
+  {
+    const int mvx = (int)(short)(rec.w & 0xFFFFu) + x, mvy = (int)(short)(rec.w >> 16) + y;
+    rec.w = ((unsigned)mvx & 0xFFFFu) | ((unsigned)mvy << 16);
+    return rec;
+  }
+};
 
 // ---- launch: a persistent grid of k workgroups per CU (k_packed: the forms up to 10 bit, k_wide: the 32-bit form), no more than there are CTUs;
 // launch(T(), packed, sad, grid) with T = int16_t (HM Pel planes) or uint8_t and the two switches as std::true_type / std::false_type ----

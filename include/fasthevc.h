@@ -484,6 +484,96 @@ int  fhevc_motion_refine_pu_wide(fhevc_ctx* ctx, const int16_t* cur_luma, const 
                                  const fhevc_motion_node* pus, fhevc_motion_qpel_node* out_pus,
                                  const fhevc_motion_node* pus_small, fhevc_motion_qpel_node* out_pus_small);
 
+/* One coarse motion centre per CTU (k_motion_coarse.hip): where a search around a predictor would start.  Every search and refinement above looks around
+ * the ZERO vector and prices vectors against a zero predictor, so real motion is reachable only by widening the window (the +-64 search costs about twenty
+ * times the +-8 one).  HM centres its window on the motion-vector predictor (xSetSearchRange, TComRdCost::setPredictor), which comes from the neighbouring
+ * PUs' CODED vectors; a source-only pass has none.  This definition therefore has NO HM counterpart and is pinned to no reference: it is this library's
+ * own, restated in tests/motion_centred_ref.py.  Per CTU (cx, cy) of the current picture p, searched in the previous ORIGINAL picture:
+ *   decimated picture  D_p(X, Y) = (sum of the 4x4 samples at (4X.., 4Y..) + 8) >> 4 for the floor(width / 4) x floor(height / 4) cells that lie wholly
+ *                      inside the picture; a cell coordinate outside that grid is clamped to it (border replication on the decimated grid)
+ *   current cells      the CTU owns cells (16 cx + i, 16 cy + j), i, j < 16; only those inside the grid count (a ragged CTU has fewer)
+ *   candidates         d in [-coarse_range, coarse_range]^2 in raster order (dy outer, dx inner), strict "<":
+ *                        sad(d)  = (16 * sum over the counted cells of |D_cur(X, Y) - D_ref(X + dx, Y + dy)|) >> (bit_depth - 8)
+ *                        cost(d) = sad(d) + c[bits(4 dx) + bits(4 dy)]
+ *                      with c[b] = getCost(b) at the lambda of slice QP qp and bits(v) = 2 floor(log2 t) + 1, t = v <= 0 ? (-v << 3) + 1 : v << 3: the
+ *                      whole-sample vector 4 d against a zero predictor at iCostScale 2, as fhevc_motion_search_pu_wide prices it.  Flat content lands on zero
+ *   record             satd_zero = sad(0), satd_best = sad at the winner, cost_best, (mvx, mvy) = 4 d in whole samples: multiples of 4 within +-56
+ * coarse_range is 1..14, in cells.  A CTU that owns no cell (picture width or height of 1..3 modulo 64) has nothing to compare: it gets 0xFFFFFFFF in the
+ * three distortion fields and a zero vector.  int16 or uint8 planes, 8 to 12 bit.
+ * Device form: layout, band and stream arguments as fhevc_motion_search_pu_wide_device; frame f >= 1 is searched in frame f-1.  d_centres:
+ * (num_frames-1) * band CTUs entries (ONE per CTU), compact over the band, written over exactly that extent; an empty band writes nothing.  Asynchronous with
+ * respect to the host, allocates nothing, keeps NO state between calls (the bit costs travel by value): calls with different QPs and ranges may be in flight on
+ * two streams.  FHEVC_E_INVALID with a fhevc_last_error text (nothing is launched or written): a null context, d_luma or d_centres, num_frames < 2, qp
+ * outside 0..51, coarse_range outside 1..14, stride_samples < width, a bad band, uint8 planes on a context above 8 bit.  Timed under slot 15 of
+ * fhevc_kernel_timing.
+ * NOT covered: per-32x32 centres; anything but fhevc_motion_search_pu_centred and fhevc_motion_refine_pu_centred, below, consuming them (the encoder hook,
+ * the P rule -- fitted on zero-predictor features --, fhevc_p_shape_frame keep the zero predictor). */
+int  fhevc_motion_centres_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                 int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int coarse_range, fhevc_motion_node* d_centres, void* stream);
+/* one picture pair, host buffers (both planes with the same stride), synchronous; centres: numCtus entries */
+int  fhevc_motion_centres(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int coarse_range,
+                          fhevc_motion_node* centres);
+
+/* The three integer searches AROUND A CENTRE per CTU: what fhevc_motion_search_pu_wide does around the zero vector, in a window of +-search_range (1..8) around
+ * the CTU's entry of d_centres -- fhevc_motion_centres' output, or any vectors of the caller's.  This is HM's arrangement: xMotionEstimation centres its
+ * window on the predictor (xSetSearchRange) and prices vectors against it (TComRdCost::setPredictor); here the predictor of every entry of a CTU is the CTU's
+ * centre P.  Arguments, optional outputs (each may be NULL, not all three), entry order, layouts, validity, markers and the exact write extent are those of
+ * fhevc_motion_search_pu_wide_device.  Per entry:
+ *   candidates    v = P + d for d in [-search_range, search_range]^2, in raster order over d, strict "<"
+ *   distortion    ALWAYS the SAD of the whole w x h block at v, reference coordinates clamped to the picture, the sum shifted ONCE by bit_depth - 8
+ *   cost          SAD + c[bits(dx) + bits(dy)]: exactly getCostOfVectorWithPredictor with the predictor 4 P in quarter units at iCostScale 2 (the lambda of
+ *                 slice QP qp)
+ *   record        mvx, mvy = v, ABSOLUTE; satd_best, cost_best; satd_zero = the SAD AT THE CENTRE (d = 0), not at the zero vector -- with a zero centre
+ *                 the two are the same, and the whole output is byte for byte fhevc_motion_search_pu_wide_device's for the same search_range
+ * d_centres: (num_frames-1) * band CTUs entries, compact over the band, never NULL, 4-byte aligned; only mvx / mvy are read.  If a component of a CTU's
+ * centre lies outside [-56, 56], all 593 entries of that CTU get the marker (0xFFFFFFFF three times, a zero vector) and nothing is read for it: 56 + 8 stays
+ * within HM's SearchRange 64, which is what the refinement's layouts hold.  The kernels decide this, the host never sees device centres.  The marker record
+ * fhevc_motion_centres writes for a CTU that owns no cell carries a zero vector, and only the vector is read: such a CTU is searched around (0, 0).
+ * The MR = 8 layouts of k_motion_pu.hip and k_motion_pu_small.hip with the window's origin and its 8-sample phase taken per CTU; one launch for nodes and
+ * PUs, one for the small PUs.  Asynchronous with respect to the host, allocates nothing, keeps NO state between calls (the window's vector costs travel by
+ * value): calls with different QPs, ranges and centres may be in flight on two streams, and fhevc_motion_centres_device and this search may follow each other
+ * on one stream without a host synchronisation.  An empty band writes nothing.  FHEVC_E_INVALID with a fhevc_last_error text (nothing is launched or
+ * written): what fhevc_motion_search_pu_wide_device rejects, a null d_centres, search_range outside 1..8.  Timed under slot 15 of fhevc_kernel_timing, each
+ * launch counted.
+ * NOT covered: search ranges above 8 around a centre; a centred fhevc_p_shape_frame; the encoder hook; the P rule.  (The refinement priced against 4 P is
+ * fhevc_motion_refine_pu_centred, below.) */
+int  fhevc_motion_search_pu_centred_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                           int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range, const fhevc_motion_node* d_centres,
+                                           fhevc_motion_node* d_nodes, fhevc_motion_node* d_pus, fhevc_motion_node* d_pus_small, void* stream);
+/* one picture pair, host buffers, synchronous; centres: numCtus entries; each output may be NULL, not all three */
+int  fhevc_motion_search_pu_centred(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                                    const fhevc_motion_node* centres, fhevc_motion_node* nodes, fhevc_motion_node* pus, fhevc_motion_node* pus_small);
+
+/* The quarter-sample refinements AROUND A CENTRE per CTU: the counterpart of fhevc_motion_search_pu_centred, whose three outputs feed straight in.  The contract is
+ * that of fhevc_motion_refine_pu_wide_device -- the half-sample stage of s_acMvRefineH, then the quarter-sample stage of s_acMvRefineQ around its winner, strict
+ * "<" in both; TComRdCost::xGetHADs on the whole block through the branch xGetHADs itself takes, shifted ONCE by bit_depth - 8; ALWAYS SATD; HEVC's 8-tap
+ * interpolation of the previous ORIGINAL picture with coordinates clamped to the picture; the three in / out pairs, each NULL together, not all three; entry
+ * order, layouts, the exact write extent -- with max_range 1..8 and three differences, P being the CTU's entry of d_centres:
+ *   validity     an entry is valid iff its CU node lies wholly inside the picture, both components of P lie in [-56, 56], and |mvx - Px|, |mvy - Py| <=
+ *                max_range; any other entry gets 0xFFFFFFFF in the three distortion fields and a zero vector (an out-of-range centre: all 593 entries of its
+ *                CTU, and nothing is read for it)
+ *   vector cost  of a candidate q in quarter units: c[bits_q(qx - 4 Px) + bits_q(qy - 4 Py)], bits_q the exp-Golomb bits fhevc_motion_refine counts:
+ *                getCostOfVectorWithPredictor with the predictor 4 P
+ *   vectors      input and output vectors are ABSOLUTE (the output in quarter units), as fhevc_motion_search_pu_centred writes them
+ * With zero centres the output is byte for byte fhevc_motion_refine_pu_wide_device's for the same max_range, so fhevc_pu_shape_select_device consumes it
+ * unchanged.  The MR = 8 layouts of k_motion_refine.hip and k_motion_refine_pu.hip with the window staged around P and vectors relative to P inside the kernel
+ * (DESIGN.md says why not the MR = 64 layouts on absolute vectors); one launch for the nodes, one for both PU families.  d_centres as for the centred search (never
+ * NULL, 4-byte aligned, only mvx / mvy read).  Asynchronous with respect to the host, allocates nothing, keeps NO state between calls: calls with different QPs, ranges
+ * and centres may be in flight on two streams; centres, centred search, this refinement and fhevc_pu_shape_select_device may follow each other on one stream
+ * without a host synchronisation.  FHEVC_E_INVALID with a fhevc_last_error text (nothing is launched or written): what fhevc_motion_refine_pu_wide_device
+ * rejects, a null d_centres, max_range outside 1..8.  Timed under slot 15 of fhevc_kernel_timing, each launch counted.
+ * NOT covered: max_range above 8 around a centre; a centred fhevc_p_shape_frame; the encoder hook; the P rule. */
+int  fhevc_motion_refine_pu_centred_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                           int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_node* d_centres,
+                                           const fhevc_motion_node* d_nodes, fhevc_motion_qpel_node* d_out_nodes,
+                                           const fhevc_motion_node* d_pus, fhevc_motion_qpel_node* d_out_pus,
+                                           const fhevc_motion_node* d_pus_small, fhevc_motion_qpel_node* d_out_pus_small, void* stream);
+/* one picture pair, host buffers (both planes with the same stride), synchronous; centres: numCtus entries; each in / out pair may be NULL together, not all three */
+int  fhevc_motion_refine_pu_centred(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                                    const fhevc_motion_node* centres, const fhevc_motion_node* nodes, fhevc_motion_qpel_node* out_nodes,
+                                    const fhevc_motion_node* pus, fhevc_motion_qpel_node* out_pus,
+                                    const fhevc_motion_node* pus_small, fhevc_motion_qpel_node* out_pus_small);
+
 /* Depth range of every 4x4 unit of a P picture's CTU from its motion nodes and the co-located depths of its reference picture
  * ("inter-CU depth reuse", BASELINE config 4).  Host-side integer arithmetic, no device work.  Per split decision (64->32,
  * 32->16, 16->8) a linear score over nine features of the node, all in 1/256 units (L(x) = floor(256 log2 x) by integer
@@ -645,7 +735,8 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
  * 9 = motion search of the PUs with a 4-sample side (fhevc_motion_search_pu_small*), 10 = quarter-sample refinement of the PUs
  * (fhevc_motion_refine_pu*), 11 = the searches at HM's SearchRange (fhevc_motion_search_pu_wide*: one launch for nodes and PUs, one for the
  * small PUs, each counted), 12 = the refinements at HM's SearchRange (fhevc_motion_refine_pu_wide*: one launch for the nodes, one for the PUs,
- * each counted), 13 = the partition-size selection (fhevc_pu_shape_select_device) */
+ * each counted), 13 = the partition-size selection (fhevc_pu_shape_select_device), 15 = the coarse motion centres (fhevc_motion_centres*), the searches around them
+ * (fhevc_motion_search_pu_centred*) and their refinements (fhevc_motion_refine_pu_centred*), each launch counted; 14 is not a slot and is rejected like any number above 15 */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
 int  fhevc_enable_kernel_timing(fhevc_ctx* ctx, int on);
 
