@@ -40,6 +40,7 @@ SYMBOLS = [
     "fhevc_pu_shape_rule_default", "fhevc_pu_shape_select", "fhevc_pu_shape_select_device", "fhevc_p_shape_frame",
     "fhevc_motion_centres", "fhevc_motion_centres_device", "fhevc_motion_search_pu_centred", "fhevc_motion_search_pu_centred_device",
     "fhevc_motion_refine_pu_centred", "fhevc_motion_refine_pu_centred_device",
+    "fhevc_p_tree_rule_default", "fhevc_p_tree_select", "fhevc_p_tree_select_device", "fhevc_p_tree_frame",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -64,6 +65,11 @@ class PuShapeRule(C.Structure):
     _fields_ = [("margin_q8", C.c_int32 * 4), ("margin_abs", C.c_int32 * 4), ("amp_mode", C.c_int32)]
 
 
+class PTreeRule(C.Structure):
+    """fhevc_p_tree_rule: the margins of the two decisions and the split cost per level (64, 32, 16)"""
+    _fields_ = [("split_q8", C.c_int32 * 3), ("split_abs", C.c_int32 * 3), ("stop_q8", C.c_int32 * 3), ("stop_abs", C.c_int32 * 3), ("split_cost", C.c_int32 * 3)]
+
+
 class NodeCost(C.Structure):
     _fields_ = [("satd", C.c_uint32), ("mode", C.c_uint32), ("cost", C.c_double)]
 
@@ -82,6 +88,9 @@ MOTION_QPEL_DTYPE = np.dtype([("satd_int", np.uint32), ("satd_best", np.uint32),
 # fhevc_pu_shape_node: one record per CU node
 SHAPE_DTYPE = np.dtype([("cost_2Nx2N", np.uint32), ("cost_best", np.uint32), ("cost_second", np.uint32), ("best", np.uint8), ("second", np.uint8),
                         ("mask", np.uint8), ("avail", np.uint8)])
+
+# fhevc_p_tree_node: one record per CU node (flags: 1 split_sure, 2 stop_sure, 4 CROSSING, 8 ABSENT, 16 own available, 32 kids available)
+TREE_DTYPE = np.dtype([("cost_own", np.uint32), ("cost_kids", np.uint32), ("cost_tree", np.uint32), ("flags", np.uint8), ("level", np.uint8), ("pad", np.uint8, (2,))])
 
 
 def motion_pu_index(node, shape, part):
@@ -211,6 +220,11 @@ def load_library(path=None):
     lib.fhevc_pu_shape_select.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(PuShapeRule), vp, vp]
     lib.fhevc_pu_shape_select_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), vp, vp, vp]
     lib.fhevc_p_shape_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), vp]
+    lib.fhevc_p_tree_rule_default.argtypes = [C.POINTER(PTreeRule)]
+    lib.fhevc_p_tree_rule_default.restype = None
+    lib.fhevc_p_tree_select.argtypes = [vp, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp]
+    lib.fhevc_p_tree_select_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp, vp]
+    lib.fhevc_p_tree_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), vp, vp, vp]
     lib.fhevc_predict_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, vp, vp]
     lib.fhevc_alloc_host.argtypes = [vp, C.c_size_t]
     lib.fhevc_alloc_host.restype = vp
@@ -272,6 +286,37 @@ def pu_shape_rule(margin_q8=0, margin_abs=0, amp_mode=1):
     q8 = [margin_q8] * 4 if np.isscalar(margin_q8) else list(margin_q8)
     ab = [margin_abs] * 4 if np.isscalar(margin_abs) else list(margin_abs)
     return PuShapeRule((C.c_int32 * 4)(*q8), (C.c_int32 * 4)(*ab), amp_mode)
+
+
+def p_tree_rule_default():
+    r = PTreeRule()
+    load_library().fhevc_p_tree_rule_default(C.byref(r))
+    return r
+
+
+def p_tree_rule(split_q8=0, split_abs=0, stop_q8=0, stop_abs=0, split_cost=0):
+    """a PTreeRule from scalars (the same value at every level) or sequences of three"""
+    three = lambda v: (C.c_int32 * 3)(*([v] * 3 if np.isscalar(v) else list(v)))
+    return PTreeRule(three(split_q8), three(split_abs), three(stop_q8), three(stop_abs), three(split_cost))
+
+
+def p_tree_select(shapes, width, height, rule=None, with_tree=False):
+    """config 4, host side: (depth_min, depth_max) [numCtus, 256] of a P picture from the selection's records [numCtus, 85] SHAPE_DTYPE (only cost_best is
+    read), decided bottom-up over the quad-tree; with_tree: (depth_min, depth_max, records [numCtus, 85] TREE_DTYPE)"""
+    lib = load_library()
+    rule = rule if rule is not None else p_tree_rule_default()
+    shapes = np.ascontiguousarray(shapes)
+    assert shapes.dtype.itemsize == 16
+    cw = (width + 63) // 64
+    n = shapes.shape[0]
+    dmin, dmax = np.zeros((n, 256), np.uint8), np.zeros((n, 256), np.uint8)
+    tree = np.zeros((n, NODES_PER_CTU), TREE_DTYPE) if with_tree else None
+    for c in range(n):
+        vw, vh = min(64, width - (c % cw) * 64), min(64, height - (c // cw) * 64)
+        rc = lib.fhevc_p_tree_select(shapes[c].ctypes.data, vw, vh, C.byref(rule), dmin[c].ctypes.data, dmax[c].ctypes.data, tree[c].ctypes.data if with_tree else None)
+        if rc != OK:
+            raise FastHevcError(rc, "fhevc_p_tree_select")
+    return (dmin, dmax, tree) if with_tree else (dmin, dmax)
 
 
 def pu_shape_select(nodes, pus, pus_small, width, height, rule=None, with_costs=False):
@@ -735,6 +780,30 @@ class Context:
         self._check(self.lib.fhevc_p_shape_frame(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, search_range,
                                                  C.byref(rule) if rule is not None else None, out.ctypes.data))
         return out.reshape(self.num_ctus, NODES_PER_CTU)
+
+    def p_tree_select_device(self, d_shapes, num_pictures, d_depth_min=None, d_depth_max=None, d_tree=None, rows=None, stream=None, rule=None):
+        """config 4 on the device: the depth ranges of num_pictures P pictures from the selection's records (what pu_shape_select_device wrote for the same
+        rows: 85 per CTU), decided bottom-up over the quad-tree; d_depth_min / d_depth_max: num_pictures * band CTUs * 256 bytes, d_tree: ... * 85 records
+        (16 B); each may be None, not all three.  rule: a PTreeRule (None: the unfitted default).  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_p_tree_select_device(self.h, d_shapes, num_pictures, rb, re, C.byref(rule) if rule is not None else None, d_depth_min,
+                                                        d_depth_max, d_tree, stream))
+
+    def p_tree_frame(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=8, coarse_range=0, shape_rule=None, tree_rule=None, with_shapes=False):
+        """config 4, one picture pair from host buffers: coarse_range 0: the wide SAD search of all three families, their quarter-sample refinement, the
+        partition-size selection and the tree decision on the device; coarse_range 1..14: the same chain around one coarse centre per CTU (search_range
+        1..8) -> (depth_min, depth_max) [numCtus, 256]; with_shapes: (depth_min, depth_max, records [numCtus, 85] SHAPE_DTYPE)"""
+        cur = np.ascontiguousarray(cur_plane).reshape(-1)
+        ref = np.ascontiguousarray(ref_plane).reshape(-1)
+        assert cur.dtype == np.int16 and ref.dtype == np.int16
+        stride = stride if stride is not None else cur_plane.shape[-1]
+        dmin, dmax = np.zeros(self.num_ctus * 256, np.uint8), np.zeros(self.num_ctus * 256, np.uint8)
+        shapes = np.zeros(self.num_ctus * NODES_PER_CTU, SHAPE_DTYPE) if with_shapes else None
+        self._check(self.lib.fhevc_p_tree_frame(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, search_range, coarse_range,
+                                                C.byref(shape_rule) if shape_rule is not None else None, C.byref(tree_rule) if tree_rule is not None else None,
+                                                dmin.ctypes.data, dmax.ctypes.data, shapes.ctypes.data if with_shapes else None))
+        out = (dmin.reshape(self.num_ctus, 256), dmax.reshape(self.num_ctus, 256))
+        return out + (shapes.reshape(self.num_ctus, NODES_PER_CTU),) if with_shapes else out
 
     def intra_first_pass_all(self, plane, origin=0, stride=None, qp=32):
         """(best [numCtus, 85], all [numCtus, 85, 35]): every mode's SATD and cost per node (parity entry point)"""

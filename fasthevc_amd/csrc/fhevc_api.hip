@@ -292,7 +292,8 @@ int fhevc_enable_kernel_timing(fhevc_ctx* c, int on)
 
 int fhevc_kernel_timing(fhevc_ctx* c, int which, int reset, double* avg_ms, uint64_t* launches)
 {
-  if (!c || which < 0 || which > 15 || which == 14) return FHEVC_E_INVALID;   // 14 stays rejected: callers probe it as the first number behind the slots of the partition-size selection
+  // 14 and 16 stay rejected: callers probe them as the first numbers behind the slots of the partition-size selection and of the centred chain
+  if (!c || which < 0 || which > 17 || which == 14 || which == 16) return FHEVC_E_INVALID;
   time_resolve(c);
   if (avg_ms) *avg_ms = c->launches[which] ? c->sum_ms[which] / (double)c->launches[which] : 0.0;
   if (launches) *launches = c->launches[which];
@@ -1408,6 +1409,86 @@ int fhevc_p_shape_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* re
   HIP_TRY(c, hipMemcpyAsync(shapes, c->d_motion, node_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->stats.bytes_d2h += (uint64_t)node_bytes;
+  return FHEVC_OK;
+}
+
+// ---- P-picture depth ranges from the selection's records over a device-resident batch (k_p_tree.hip; the host form: fhevc_host.hip) ----
+int fhevc_p_tree_select_device(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, int num_pictures, int ctu_row_begin, int ctu_row_end, const fhevc_p_tree_rule* rule,
+                               uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!d_shapes || (!d_depth_min && !d_depth_max && !d_tree)) return fail(c, FHEVC_E_INVALID, "bad tree-decision arguments");
+  // (records have no sample layout: the checks of the pictures' number and the band)
+  if (const char* bad = batch_error(c, 2, c->cfg.width, 0, num_pictures, 1, ctu_row_begin, ctu_row_end, 0, false)) return fail(c, FHEVC_E_INVALID, bad);
+  static_assert(sizeof(fhevc_p_tree_rule) == sizeof(FhevcPTreeRule) && sizeof(fhevc_p_tree_node) == sizeof(FhevcPTreeNode), "tree-decision layouts");
+  FhevcPTreeRule r;   // read here, handed to the kernel by value: the caller's struct is free again when this call returns
+  if (rule) std::memcpy(&r, rule, sizeof r);
+  else std::memset(&r, 0, sizeof r);   // fhevc_p_tree_rule_default
+  if (const char* bad = fhevc_p_tree_rule_error(r)) return fail(c, FHEVC_E_INVALID, bad);
+  if ((long long)num_pictures * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "more than 2^31 - 1 CTUs");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
+  const FhevcFrames fr = frames_of(c, nullptr, 1, c->cfg.width, 0, num_pictures, ctu_row_begin, ctu_row_end);
+  return launch_on(c, stream, 17, "fhevc_launch_p_tree", [&](hipStream_t s) {
+    return fhevc_launch_p_tree(fr, r, reinterpret_cast<const FhevcPuShapeNode*>(d_shapes), d_depth_min, d_depth_max, reinterpret_cast<FhevcPTreeNode*>(d_tree), c->num_cus, s);
+  });
+}
+
+int fhevc_p_tree_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                       const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!cur_luma || !ref_luma || !depth_min || !depth_max || stride_samples < c->cfg.width) return fail(c, FHEVC_E_INVALID, "bad tree-decision frame arguments");
+  if (qp < 0 || qp > 51 || coarse_range < 0 || coarse_range > FHEVC_MOTION_COARSE_MAX_RANGE || search_range < 1 ||
+      search_range > (coarse_range ? FHEVC_MOTION_MAX_RANGE : FHEVC_MOTION_WIDE_MAX_RANGE))
+    return fail(c, FHEVC_E_INVALID, "bad tree-decision frame arguments (around a centre the search covers ranges 1..8, coarse ranges 1..14)");
+  if (shape_rule)
+    if (const char* bad = fhevc_pu_shape_rule_error(*shape_rule)) return fail(c, FHEVC_E_INVALID, bad);
+  if (tree_rule)
+    if (const char* bad = fhevc_p_tree_rule_error(*tree_rule)) return fail(c, FHEVC_E_INVALID, bad);
+  (void)hipSetDevice(c->device);
+  // the buffers of the host forms of the searches and their refinements; the records go where the integer nodes were once the refinement has read them (as in
+  // fhevc_p_shape_frame), the maps where fhevc_p_predict_frame keeps its own
+  const size_t node_bytes = motion_bytes(c), pu_bytes = (size_t)c->num_ctus * FHEVC_PUS * sizeof(FhevcMotionNode),
+               small_bytes = (size_t)c->num_ctus * FHEVC_PUS_SMALL * sizeof(FhevcMotionNode), maps = (size_t)c->num_ctus * 256;
+  HIP_TRY(c, ensure(c->d_qpel, node_bytes));
+  HIP_TRY(c, ensure(c->d_motion_pu, pu_bytes));
+  HIP_TRY(c, ensure(c->d_qpel_pu, pu_bytes));
+  HIP_TRY(c, ensure(c->d_motion_pu_small, small_bytes));
+  HIP_TRY(c, ensure(c->d_qpel_pu_small, small_bytes));
+  HIP_TRY(c, ensure(c->d_p_maps, 3 * maps));
+  if (coarse_range) HIP_TRY(c, ensure(c->d_centres, (size_t)c->num_ctus * sizeof(FhevcMotionNode)));
+  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
+  if (rc != FHEVC_OK) return rc;
+  fhevc_motion_node* nodes = reinterpret_cast<fhevc_motion_node*>(c->d_motion);
+  fhevc_motion_node* pus = reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu);
+  fhevc_motion_node* small = reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu_small);
+  fhevc_motion_node* centres = reinterpret_cast<fhevc_motion_node*>(c->d_centres);
+  fhevc_motion_qpel_node* q_nodes = reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel);
+  fhevc_motion_qpel_node* q_pus = reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu);
+  fhevc_motion_qpel_node* q_small = reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu_small);
+  fhevc_pu_shape_node* d_shapes = reinterpret_cast<fhevc_pu_shape_node*>(c->d_motion);
+  const long long plane = (long long)pair_plane(c);
+  if (coarse_range) {
+    rc = fhevc_motion_centres_device(c, c->d_pair, 2, c->dev_stride, plane, 2, 0, c->ctus_y, qp, coarse_range, centres, c->stream);
+    if (rc == FHEVC_OK)
+      rc = fhevc_motion_search_pu_centred_device(c, c->d_pair, 2, c->dev_stride, plane, 2, 0, c->ctus_y, qp, search_range, centres, nodes, pus, small, c->stream);
+    if (rc == FHEVC_OK)
+      rc = fhevc_motion_refine_pu_centred_device(c, c->d_pair, 2, c->dev_stride, plane, 2, 0, c->ctus_y, qp, search_range, centres, nodes, q_nodes, pus, q_pus, small,
+                                                 q_small, c->stream);
+  } else {
+    rc = fhevc_motion_search_pu_wide_device(c, c->d_pair, 2, c->dev_stride, plane, 2, 0, c->ctus_y, qp, search_range, nodes, pus, small, c->stream);
+    if (rc == FHEVC_OK)
+      rc = fhevc_motion_refine_pu_wide_device(c, c->d_pair, 2, c->dev_stride, plane, 2, 0, c->ctus_y, qp, search_range, nodes, q_nodes, pus, q_pus, small, q_small,
+                                              c->stream);
+  }
+  if (rc == FHEVC_OK) rc = fhevc_pu_shape_select_device(c, q_nodes, q_pus, q_small, 1, 0, c->ctus_y, shape_rule, d_shapes, nullptr, c->stream);
+  if (rc == FHEVC_OK) rc = fhevc_p_tree_select_device(c, d_shapes, 1, 0, c->ctus_y, tree_rule, c->d_p_maps + maps, c->d_p_maps + 2 * maps, nullptr, c->stream);
+  if (rc != FHEVC_OK) { (void)hipStreamSynchronize(c->stream); return rc; }   // the uploads read the caller's buffers: through before the call returns
+  HIP_TRY(c, hipMemcpyAsync(depth_min, c->d_p_maps + maps, maps, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(depth_max, c->d_p_maps + 2 * maps, maps, hipMemcpyDeviceToHost, c->stream));
+  if (shapes) HIP_TRY(c, hipMemcpyAsync(shapes, c->d_motion, node_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->stats.bytes_d2h += (uint64_t)(2 * maps + (shapes ? node_bytes : 0));
   return FHEVC_OK;
 }
 

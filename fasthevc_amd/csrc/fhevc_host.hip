@@ -316,6 +316,78 @@ int fhevc_pu_shape_select(const fhevc_motion_qpel_node* nodes, const fhevc_motio
   return FHEVC_OK;
 }
 
+// ---- P-picture depth ranges from the selection's records, bottom-up over the quad-tree (spec in include/fasthevc.h; the device form is k_p_tree.hip) ----
+
+void fhevc_p_tree_rule_default(fhevc_p_tree_rule* rule)
+{
+  if (!rule) return;
+  std::memset(rule, 0, sizeof *rule);   // the unfitted hard decision: no margins, no split cost
+}
+
+int fhevc_p_tree_select(const fhevc_pu_shape_node* shapes, int valid_w, int valid_h, const fhevc_p_tree_rule* rule, uint8_t* depth_min, uint8_t* depth_max,
+                        fhevc_p_tree_node* tree)
+{
+  if (!shapes || !rule || (!depth_min && !depth_max && !tree) || valid_w < 8 || valid_w > 64 || valid_h < 8 || valid_h > 64 || fhevc_p_tree_rule_error(*rule))
+    return FHEVC_E_INVALID;
+  const uint32_t mark = 0xFFFFFFFFu, sat = 0xFFFFFFFEu;
+  fhevc_p_tree_node t[FHEVC_NODES];
+  bool sure[21], maybe[21];
+  // bottom-up: the children of a node carry larger numbers, so node numbers descending
+  for (int k = FHEVC_NODES - 1; k >= 0; --k) {
+    const int lvl = k < 1 ? 0 : (k < 5 ? 1 : (k < 21 ? 2 : 3));
+    const int size = 64 >> lvl, idx = k - kLevel[lvl].first, nx = idx % kLevel[lvl].per_row, ny = idx / kLevel[lvl].per_row;
+    const bool inside = nx * size + size <= valid_w && ny * size + size <= valid_h, outside = nx * size >= valid_w || ny * size >= valid_h;
+    fhevc_p_tree_node& n = t[k];
+    n.cost_own = n.cost_kids = n.cost_tree = mark;
+    n.flags = 0; n.level = (uint8_t)lvl; n.pad[0] = n.pad[1] = 0;
+    if (lvl < 3) { sure[k] = false; maybe[k] = true; }
+    if (outside || (lvl == 3 && !inside)) { n.flags = 8; continue; }   // no CU is coded there
+    if (inside) n.cost_own = shapes[k].cost_best;
+    if (lvl == 3) { n.cost_tree = n.cost_own; n.flags = n.cost_own != mark ? 16 : 0; continue; }
+    uint64_t sum = inside ? (uint64_t)rule->split_cost[lvl] : 0;
+    bool marked = false;
+    for (int c = 0; c < 4; ++c) {
+      const fhevc_p_tree_node& ch = t[kLevel[lvl + 1].first + (2 * ny + (c >> 1)) * kLevel[lvl + 1].per_row + 2 * nx + (c & 1)];
+      if (ch.flags & 8) continue;
+      if (ch.cost_tree == mark) marked = true;
+      else sum += ch.cost_tree;
+    }
+    if (!marked) n.cost_kids = (uint32_t)std::min<uint64_t>(sum, sat);
+    const uint64_t own = n.cost_own, kids = n.cost_kids;
+    bool split = false, stop = false;
+    if (!inside) n.cost_tree = n.cost_kids;
+    else if (kids == mark) n.cost_tree = n.cost_own;
+    else if (own == mark) n.cost_tree = n.cost_kids;
+    else {
+      n.cost_tree = kids < own ? n.cost_kids : n.cost_own;   // strict "<": xCheckBestMode
+      split = kids + (uint64_t)rule->split_abs[lvl] + ((kids * (uint64_t)rule->split_q8[lvl]) >> 8) < own;
+      stop = own + (uint64_t)rule->stop_abs[lvl] + ((own * (uint64_t)rule->stop_q8[lvl]) >> 8) <= kids;
+    }
+    n.flags = (uint8_t)((split ? 1 : 0) | (stop ? 2 : 0) | (!inside ? 4 : 0) | (own != mark ? 16 : 0) | (kids != mark ? 32 : 0));
+    sure[k] = !inside || split;
+    maybe[k] = !inside || !stop;
+  }
+  if (tree) std::memcpy(tree, t, sizeof t);
+  if (depth_min) std::memset(depth_min, 0, 256);
+  if (depth_max) std::memset(depth_max, 0, 256);
+  // the per-unit walk of fhevc_p_depth_range, without its window
+  for (int uy = 0; uy * 4 < valid_h; ++uy)
+    for (int ux = 0; ux * 4 < valid_w; ++ux) {
+      int lo = 0, hi = 0;
+      bool lo_open = true, hi_open = true;
+      for (int lvl = 0; lvl < 3 && (lo_open || hi_open); ++lvl) {
+        const int id = kLevel[lvl].first + (uy >> (4 - lvl)) * kLevel[lvl].per_row + (ux >> (4 - lvl));
+        lo_open = lo_open && sure[id];
+        hi_open = hi_open && maybe[id];
+        if (lo_open) lo = lvl + 1;
+        if (hi_open) hi = lvl + 1;
+      }
+      if (depth_min) depth_min[uy * 16 + ux] = (uint8_t)lo;
+      if (depth_max) depth_max[uy * 16 + ux] = (uint8_t)hi;
+    }
+  return FHEVC_OK;
+}
+
 int fhevc_p_motion_compensated_depth(const fhevc_motion_node* nodes, const uint8_t* prev_map, int width, int height, int ctu, uint8_t* out)
 {
   if (!nodes || !prev_map || !out || width < 8 || height < 8 || ctu < 0) return FHEVC_E_INVALID;

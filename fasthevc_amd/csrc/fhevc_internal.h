@@ -292,6 +292,27 @@ struct FhevcPuShapeNode { uint32_t cost_2Nx2N, cost_best, cost_second; uint8_t b
 hipError_t fhevc_launch_pu_shape(const FhevcFrames& fr, const FhevcPuShapeRule& rule, const FhevcMotionQpelNode* d_nodes, const FhevcMotionQpelNode* d_pus,
                                  const FhevcMotionQpelNode* d_pus_small, FhevcPuShapeNode* d_shapes, uint32_t* d_costs, int num_cus, hipStream_t stream);
 
+// ---- P-picture depth ranges from the selection's records, bottom-up over the quad-tree (k_p_tree.hip; config 4) ------------------------------------
+// fhevc_p_tree_rule of fasthevc.h; travels by value as a kernel argument, so every launch has its own rule
+struct FhevcPTreeRule { int32_t split_q8[3], split_abs[3], stop_q8[3], stop_abs[3], split_cost[3]; };
+// what is wrong with a rule (host form and device form reject the same rules); null: nothing
+template <class R> inline const char* fhevc_p_tree_rule_error(const R& r)
+{
+  for (int l = 0; l < 3; ++l) {
+    if (r.split_q8[l] < 0 || r.split_q8[l] > 65535) return "split_q8 out of range (0..65535)";
+    if (r.stop_q8[l] < 0 || r.stop_q8[l] > 65535) return "stop_q8 out of range (0..65535)";
+    if (r.split_abs[l] < 0) return "split_abs out of range (>= 0)";
+    if (r.stop_abs[l] < 0) return "stop_abs out of range (>= 0)";
+    if (r.split_cost[l] < 0) return "split_cost out of range (>= 0)";
+  }
+  return nullptr;
+}
+struct FhevcPTreeNode { uint32_t cost_own, cost_kids, cost_tree; uint8_t flags, level, pad[2]; };
+// fr: geometry, band, num_frames = the P pictures of the batch (luma is not read).  d_shapes: num_frames * band CTUs * 85 records as fhevc_launch_pu_shape writes
+// them; d_depth_min / d_depth_max: ... * 256 bytes; d_tree: ... * 85 records; each output may be null (not all three); all compact over the band
+hipError_t fhevc_launch_p_tree(const FhevcFrames& fr, const FhevcPTreeRule& rule, const FhevcPuShapeNode* d_shapes, uint8_t* d_depth_min, uint8_t* d_depth_max,
+                               FhevcPTreeNode* d_tree, int num_cus, hipStream_t stream);
+
 // ---- adaptive-QP pre-analysis (k_preanalyze.hip) -----------------------------------------------------------
 // d_activity: per frame parts_per_frame doubles, layers concatenated (layer d: ceil(H/P) x ceil(W/P), P = 64 >> d)
 hipError_t fhevc_launch_preanalyze(const FhevcFrames& fr, int layers, long long parts_per_frame, double* d_activity,

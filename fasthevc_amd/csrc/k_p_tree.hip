@@ -1,0 +1,170 @@
+// k_p_tree.hip -- P-picture depth ranges from the selection's records, decided bottom-up over the quad-tree, on the device (config 4), gfx950 only.
+//
+// The device form of fhevc_p_tree_select (fhevc_host.hip; spec in include/fasthevc.h): per CTU the 85 records of fhevc_pu_shape_select_device, of which only
+// cost_best is read; the best tree of every node against its own cost, the two decisions per node of levels 0..2, and the depth_min / depth_max maps as
+// k_p_rule.hip writes them.  Integer arithmetic throughout, the same bits as the host code for any content of the records.
+//
+// A memory-bound pass: 1 360 B of records read per CTU (dword 1 of each is used), 512 B of maps and (optionally) 1 360 B of tree records written.  One wave per
+// CTU, four per workgroup, grid-stride; no LDS, no workgroup barriers: waves are independent.
+//   * lane i loads cost_best of node 21 + i, so a lane is an 8x8 node in raster position (x = i & 7, y = i >> 3); lanes 0..20 load nodes 0..20 in a second
+//     load (the other lanes re-read node 20, in bounds); both loads are issued before the first is waited for;
+//   * the three sums of four children are lane exchanges: xor 1 and xor 8, then xor 2 and xor 16, then xor 4 and xor 32.  What a node hands its parent
+//     travels as one 64-bit value: its tree cost, 2^40 where that is the marker, 0 where no CU is coded; four of them never carry into each other, so the
+//     high bits of a sum say whether a child was marked and the low 40 bits hold the 64-bit sum.  After each exchange all lanes of a node hold that node,
+//     and every lane decides its three ancestors redundantly;
+//   * a map leaves as one dword per lane (row lane >> 2, units 4 (lane & 3) .. + 3, all in ONE 16x16 node): the depths its three ancestors open come from
+//     the lane at that 16x16 node's corner in one shuffle;
+//   * the records of nodes 21 + lane are the lane's own; those of nodes 0..20 come to lanes 0..20 from one lane inside each node, chosen so that no lane
+//     serves two nodes (16x16: its corner, even x and y; 32x32: x % 4 == 1, y % 4 == 0; the CTU: lane 8).
+// Which lane and which address is read depends on lane and node numbers alone -- never on what the records hold.
+// The rule (60 bytes) and the geometry are kernel arguments: two launches with different rules never share state (no per-context table).
+#include "../../include/fasthevc.h"
+#include "fhevc_internal.h"
+
+namespace {
+
+constexpr uint32_t kMark = 0xFFFFFFFFu, kSat = 0xFFFFFFFEu;
+constexpr uint64_t kMarked = 1ull << 40;
+
+struct PTreeGeom {
+  int width, height, ctus_x;   // the whole picture
+  int row_begin, band_ctus;    // the band: first CTU row, CTUs per picture in it
+  int total;                   // num_pictures * band_ctus
+};
+
+// flags: bit 0 split_sure, 1 stop_sure, 2 CROSSING, 3 ABSENT, 4 own available, 5 kids available; sure / maybe: whether depth_min / depth_max descend through the node
+struct TreeNode { uint32_t own, kids, tree, flags; bool sure, maybe; };
+
+// what a node hands its parent
+__device__ __forceinline__ uint64_t share(uint32_t tree, bool absent) { return absent ? 0ull : (tree == kMark ? kMarked : (uint64_t)tree); }
+
+__device__ __forceinline__ uint64_t sum4(uint64_t v, int a, int b)
+{
+  v += __shfl_xor(v, a);
+  v += __shfl_xor(v, b);
+  return v;
+}
+
+// the node of level L (0..2) at sample (x, y) of the CTU: cost_best of its record, the sum of what its four children hand it
+template <int L>
+__device__ __forceinline__ TreeNode decide(const FhevcPTreeRule& R, uint32_t cost_best, uint64_t sum, int x, int y, int valid_w, int valid_h)
+{
+  constexpr int S = 64 >> L;
+  const bool inside = x + S <= valid_w && y + S <= valid_h, outside = x >= valid_w || y >= valid_h;
+  TreeNode n;
+  n.own = inside ? cost_best : kMark;
+  const uint64_t total = (sum & (kMarked - 1)) + (inside ? (uint64_t)R.split_cost[L] : 0ull);
+  n.kids = sum >= kMarked ? kMark : (total > kSat ? kSat : (uint32_t)total);
+  n.tree = !inside ? n.kids : (n.kids == kMark ? n.own : (n.own == kMark ? n.kids : (n.kids < n.own ? n.kids : n.own)));
+  bool split = false, stop = false;
+  if (inside && n.own != kMark && n.kids != kMark) {
+    split = (uint64_t)n.kids + (uint64_t)R.split_abs[L] + (((uint64_t)n.kids * (uint64_t)R.split_q8[L]) >> 8) < (uint64_t)n.own;
+    stop = (uint64_t)n.own + (uint64_t)R.stop_abs[L] + (((uint64_t)n.own * (uint64_t)R.stop_q8[L]) >> 8) <= (uint64_t)n.kids;
+  }
+  n.sure = !inside || split;
+  n.maybe = !inside || !stop;
+  n.flags = (split ? 1u : 0u) | (stop ? 2u : 0u) | (!inside ? 4u : 0u) | (n.own != kMark ? 16u : 0u) | (n.kids != kMark ? 32u : 0u);
+  if (outside) { n.own = n.kids = n.tree = kMark; n.flags = 8u; }
+  return n;
+}
+
+__device__ __forceinline__ void store_map(uint8_t* dst, uint32_t v, bool wide)
+{
+  if (wide) *reinterpret_cast<uint32_t*>(dst) = v;
+  else { dst[0] = (uint8_t)v; dst[1] = (uint8_t)(v >> 8); dst[2] = (uint8_t)(v >> 16); dst[3] = (uint8_t)(v >> 24); }
+}
+
+__device__ __forceinline__ void store_record(uint32_t* dst, uint32_t own, uint32_t kids, uint32_t tree, uint32_t flags_level, bool wide)
+{
+  if (wide) *reinterpret_cast<uint4*>(dst) = make_uint4(own, kids, tree, flags_level);
+  else { dst[0] = own; dst[1] = kids; dst[2] = tree; dst[3] = flags_level; }
+}
+
+// WIDE_MAPS: both map pointers are 4-byte aligned (dword stores; otherwise bytes); WIDE_TREE: tree is 16-byte aligned (16-byte stores; otherwise dwords)
+template <bool WIDE_MAPS, bool WIDE_TREE>
+__global__ __launch_bounds__(256) void fhevc_p_tree_kernel(PTreeGeom G, FhevcPTreeRule R, const uint32_t* __restrict__ shapes, uint8_t* __restrict__ depth_min,
+                                                           uint8_t* __restrict__ depth_max, uint32_t* __restrict__ tree)
+{
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int x = (lane & 7) * 8, y = (lane >> 3) * 8;   // this lane's 8x8 node
+  // where this lane's ancestors sit among lanes 0..20 of the second load
+  const int k16 = 5 + (y >> 4) * 4 + (x >> 4), k32 = 1 + (y >> 5) * 2 + (x >> 5);
+  // the map dword of this lane: its 16x16 node's corner lane
+  const int map_src = (lane >> 4) * 16 + (lane & 3) * 2;
+  // the record of node `lane` (lanes 0..20) comes from one lane inside that node
+  const int rec_level = lane < 1 ? 0 : (lane < 5 ? 1 : 2);
+  const int rec_src = lane < 1 ? 8 : (lane < 5 ? ((lane - 1) >> 1) * 32 + ((lane - 1) & 1) * 4 + 1 : (lane < 21 ? ((lane - 5) >> 2) * 16 + ((lane - 5) & 3) * 2 : 0));
+  // ... and which of its ancestors this lane serves
+  const int serves = (x & 8) == 0 && (y & 8) == 0 ? 2 : ((x & 24) == 8 && (y & 24) == 0 ? 1 : 0);
+
+  for (int g = blockIdx.x * 4 + wave; g < G.total; g += gridDim.x * 4) {
+    const int in_band = g % G.band_ctus;
+    const int ctu = G.row_begin * G.ctus_x + in_band;
+    const int x0 = (ctu % G.ctus_x) * 64, y0 = (ctu / G.ctus_x) * 64;
+    const int valid_w = min(64, G.width - x0), valid_h = min(64, G.height - y0);
+    const uint32_t* src = shapes + (size_t)g * (FHEVC_NODES * 4);
+    const uint32_t leaf = src[4 * (21 + lane) + 1], upper = src[4 * min(lane, 20) + 1];
+
+    // ---- level 3: a leaf is coded iff it lies wholly inside ----
+    const bool inside8 = x + 8 <= valid_w && y + 8 <= valid_h;
+    const uint32_t own8 = inside8 ? leaf : kMark;
+    // ---- levels 2, 1, 0: every lane decides the node around it ----
+    const TreeNode n16 = decide<2>(R, __shfl(upper, k16), sum4(share(own8, !inside8), 1, 8), x & 48, y & 48, valid_w, valid_h);
+    const TreeNode n32 = decide<1>(R, __shfl(upper, k32), sum4(share(n16.tree, n16.flags == 8u), 2, 16), x & 32, y & 32, valid_w, valid_h);
+    const TreeNode n64 = decide<0>(R, __shfl(upper, 0), sum4(share(n32.tree, n32.flags == 8u), 4, 32), 0, 0, valid_w, valid_h);
+
+    // ---- the maps: the depths the decisions open top-down, 0 outside the picture ----
+    if (depth_min || depth_max) {
+      const bool lo64 = n64.sure, lo32 = lo64 && n32.sure, lo16 = lo32 && n16.sure;
+      const bool hi64 = n64.maybe, hi32 = hi64 && n32.maybe, hi16 = hi32 && n16.maybe;
+      const uint32_t opened = __shfl(((uint32_t)lo64 + (uint32_t)lo32 + (uint32_t)lo16) | ((uint32_t)hi64 + (uint32_t)hi32 + (uint32_t)hi16) << 8, map_src);
+      const uint32_t lo = opened & 255u, hi = opened >> 8;
+      uint32_t out_lo = 0, out_hi = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const bool inside = ((lane & 3) * 4 + k) * 4 < valid_w && (lane >> 2) * 4 < valid_h;
+        out_lo |= (inside ? lo : 0u) << (8 * k);
+        out_hi |= (inside ? hi : 0u) << (8 * k);
+      }
+      if (depth_min) store_map(depth_min + (size_t)g * 256 + 4 * lane, out_lo, WIDE_MAPS);
+      if (depth_max) store_map(depth_max + (size_t)g * 256 + 4 * lane, out_hi, WIDE_MAPS);
+    }
+
+    // ---- the records: node 21 + lane from every lane, node `lane` from lanes 0..20 ----
+    if (tree) {
+      uint32_t* dst = tree + (size_t)g * (FHEVC_NODES * 4);
+      store_record(dst + 4 * (21 + lane), own8, kMark, own8, (inside8 ? (own8 != kMark ? 16u : 0u) : 8u) | 3u << 8, WIDE_TREE);
+      const TreeNode& mine = serves == 2 ? n16 : (serves == 1 ? n32 : n64);
+      const uint32_t own = __shfl(mine.own, rec_src), kids = __shfl(mine.kids, rec_src), best = __shfl(mine.tree, rec_src), flags = __shfl(mine.flags, rec_src);
+      if (lane < 21) store_record(dst + 4 * lane, own, kids, best, flags | (uint32_t)rec_level << 8, WIDE_TREE);
+    }
+  }
+}
+
+}  // namespace
+
+hipError_t fhevc_launch_p_tree(const FhevcFrames& fr, const FhevcPTreeRule& rule, const FhevcPuShapeNode* d_shapes, uint8_t* d_depth_min, uint8_t* d_depth_max,
+                               FhevcPTreeNode* d_tree, int num_cus, hipStream_t stream)
+{
+  static_assert(sizeof(FhevcPuShapeNode) == 16 && sizeof(FhevcPTreeNode) == 16 && sizeof(FhevcPTreeRule) == 60, "record layouts");
+  PTreeGeom G;
+  G.width = fr.width; G.height = fr.height; G.ctus_x = fr.ctus_x;
+  G.row_begin = fr.row_begin; G.band_ctus = (fr.row_end - fr.row_begin) * fr.ctus_x;
+  const long long total = (long long)G.band_ctus * fr.num_frames;
+  if (total <= 0) return hipSuccess;
+  if (total > 0x7FFFFFFF) return hipErrorInvalidValue;
+  G.total = (int)total;
+  long long grid = (total + 3) / 4;
+  const long long cap = (long long)num_cus * 8;
+  if (grid > cap) grid = cap;
+  // the records are read as dwords whatever their alignment (4 bytes by type)
+  const bool wide_maps = (((uintptr_t)d_depth_min | (uintptr_t)d_depth_max) & 3) == 0, wide_tree = ((uintptr_t)d_tree & 15) == 0;
+  const uint32_t* shapes = reinterpret_cast<const uint32_t*>(d_shapes);
+  uint32_t* tree = reinterpret_cast<uint32_t*>(d_tree);
+  const dim3 blocks((unsigned)grid), threads(256);
+  if (wide_maps && wide_tree) hipLaunchKernelGGL((fhevc_p_tree_kernel<true, true>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree);
+  else if (wide_maps) hipLaunchKernelGGL((fhevc_p_tree_kernel<true, false>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree);
+  else if (wide_tree) hipLaunchKernelGGL((fhevc_p_tree_kernel<false, true>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree);
+  else hipLaunchKernelGGL((fhevc_p_tree_kernel<false, false>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree);
+  return hipGetLastError();
+}

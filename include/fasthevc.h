@@ -536,7 +536,7 @@ int  fhevc_motion_centres(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t
  * written): what fhevc_motion_search_pu_wide_device rejects, a null d_centres, search_range outside 1..8.  Timed under slot 15 of fhevc_kernel_timing, each
  * launch counted.
  * NOT covered: search ranges above 8 around a centre; a centred fhevc_p_shape_frame; the encoder hook; the P rule.  (The refinement priced against 4 P is
- * fhevc_motion_refine_pu_centred, below.) */
+ * fhevc_motion_refine_pu_centred, below.)  (Since then: fhevc_p_tree_frame, further below, runs the centred chain end to end from host buffers.) */
 int  fhevc_motion_search_pu_centred_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
                                            int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range, const fhevc_motion_node* d_centres,
                                            fhevc_motion_node* d_nodes, fhevc_motion_node* d_pus, fhevc_motion_node* d_pus_small, void* stream);
@@ -562,7 +562,8 @@ int  fhevc_motion_search_pu_centred(fhevc_ctx* ctx, const int16_t* cur_luma, con
  * and centres may be in flight on two streams; centres, centred search, this refinement and fhevc_pu_shape_select_device may follow each other on one stream
  * without a host synchronisation.  FHEVC_E_INVALID with a fhevc_last_error text (nothing is launched or written): what fhevc_motion_refine_pu_wide_device
  * rejects, a null d_centres, max_range outside 1..8.  Timed under slot 15 of fhevc_kernel_timing, each launch counted.
- * NOT covered: max_range above 8 around a centre; a centred fhevc_p_shape_frame; the encoder hook; the P rule. */
+ * NOT covered: max_range above 8 around a centre; a centred fhevc_p_shape_frame; the encoder hook; the P rule.  (Since then: fhevc_p_tree_frame, further below, runs
+ * centres, centred search, this refinement, the selection and the tree decision as one call from host buffers.) */
 int  fhevc_motion_refine_pu_centred_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
                                            int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_node* d_centres,
                                            const fhevc_motion_node* d_nodes, fhevc_motion_qpel_node* d_out_nodes,
@@ -725,6 +726,84 @@ int  fhevc_pu_shape_select_device(fhevc_ctx* ctx, const fhevc_motion_qpel_node* 
 int  fhevc_p_shape_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
                          const fhevc_pu_shape_rule* rule, fhevc_pu_shape_node* shapes /* numCtus * 85 */);
 
+/* ---- config 4 (P slices): depth ranges from the refined inter costs, decided bottom-up over the quad-tree (k_p_tree.hip) -------------------------
+ * HM decides the quad-tree bottom-up: the best cost of a CU over its partition sizes against the sum of the best trees of its four children
+ * (TEncCu::xCompressCU, xCheckBestMode).  The records of fhevc_pu_shape_select[_device] hold "best cost over partition sizes" per node, on quarter-sample
+ * Hadamard costs; this entry point makes the comparison and writes its outcome in the form the encoder hook already takes: a depth_min / depth_max map per
+ * CTU, as fhevc_p_depth_range writes them.
+ * Input per CTU: the 85 fhevc_pu_shape_node records; only cost_best is read.  Node order, levels l = 0, 1, 2, 3 for k = 0, 1..4, 5..20, 21..84 and raster
+ * order inside a level as everywhere else.  MARK = 0xFFFFFFFF, SAT = 0xFFFFFFFE, s = 64 >> l, node (nx, ny) of level l, valid_w / valid_h the CTU's samples
+ * inside the picture.
+ * Geometry classes (the geometry alone decides them, no input byte does):
+ *   INSIDE    iff nx * s + s <= valid_w && ny * s + s <= valid_h
+ *   OUTSIDE   iff nx * s >= valid_w || ny * s >= valid_h
+ *   CROSSING  otherwise
+ *   ABSENT    iff OUTSIDE, or l == 3 and not INSIDE: no CU is coded there
+ * Bottom-up costs:
+ *   own[k]    cost_best of record k if INSIDE, else MARK
+ *   kids[k]   level 3: MARK.  Other levels, not ABSENT: MARK if any non-ABSENT child has tree == MARK; otherwise the 64-bit sum of tree[child] over the
+ *             non-ABSENT children, plus split_cost[l] only when k is INSIDE, saturated at SAT
+ *   tree[k]   level 3: own[k].  CROSSING: kids[k].  INSIDE: own if kids == MARK; kids if own == MARK (both MARK gives MARK); otherwise
+ *             kids < own ? kids : own -- strict "<": xCheckBestMode replaces only on a strictly smaller cost
+ * Margins never enter tree.
+ * Decisions exist for an INSIDE node of level 0..2 with own != MARK && kids != MARK, evaluated in 64 bits:
+ *   split_sure = kids + split_abs[l] + ((kids * split_q8[l]) >> 8) < own
+ *   stop_sure  = own + stop_abs[l] + ((own * stop_q8[l]) >> 8) <= kids
+ * otherwise neither holds.  With all margins 0 exactly one of the two holds; with non-negative margins never both.
+ * Maps: assembled exactly as fhevc_p_depth_range assembles its maps (the per-unit walk over levels 0..2) with
+ *   sure  = CROSSING || split_sure          (depth_min follows the sure splits top-down)
+ *   maybe = CROSSING || !stop_sure          (depth_max follows the maybe splits top-down)
+ * There is no window and no prev_depth.  Units with 4 * ux >= valid_w or 4 * uy >= valid_h get 0.  depth_min <= depth_max per unit follows from the
+ * definition. */
+typedef struct {
+  uint32_t cost_own;        /* own[k] */
+  uint32_t cost_kids;       /* kids[k] */
+  uint32_t cost_tree;       /* tree[k] */
+  uint8_t  flags;           /* bit 0 split_sure, bit 1 stop_sure, bit 2 CROSSING, bit 3 ABSENT, bit 4 own available (!= MARK), bit 5 kids available */
+  uint8_t  level;           /* l */
+  uint8_t  pad[2];          /* written 0 */
+} fhevc_p_tree_node;        /* 16 bytes; an ABSENT node gets three MARKs and bit 3 only */
+typedef struct {
+  int32_t split_q8[3];      /* per level 0..2, 0..65535: relative margin in 1/256 of kids */
+  int32_t split_abs[3];     /* per level, cost units, >= 0 */
+  int32_t stop_q8[3];       /* per level, 0..65535: relative margin in 1/256 of own */
+  int32_t stop_abs[3];      /* per level, cost units, >= 0 */
+  int32_t split_cost[3];    /* per level, cost units, >= 0: added to the children's sum of an INSIDE node (what signalling the split costs) */
+} fhevc_p_tree_rule;        /* 60 bytes */
+/* all zero: the UNFITTED hard decision (depth_min == depth_max wherever no MARK is involved) -- not a tuned default; margins have to be fitted on the
+ * reference's own depths first */
+void fhevc_p_tree_rule_default(fhevc_p_tree_rule* rule);
+/* One CTU, host-side integer logic, no context, no device work (the twin of the kernel).  shapes: the CTU's 85 records; valid_w / valid_h: 8..64.
+ * depth_min / depth_max: 256 bytes each, raster 16 x 16; tree: 85 records.  Each of the three outputs may be NULL, not all three.  FHEVC_E_INVALID (nothing
+ * is written): a null shapes or rule, all three outputs null, valid_w / valid_h outside 8..64, a q8 outside 0..65535, a negative abs or split_cost. */
+int  fhevc_p_tree_select(const fhevc_pu_shape_node* shapes /* 85 */, int valid_w, int valid_h, const fhevc_p_tree_rule* rule,
+                         uint8_t* depth_min /* 256 or NULL */, uint8_t* depth_max /* 256 or NULL */, fhevc_p_tree_node* tree /* 85 or NULL */);
+/* Device form (k_p_tree.hip): the same bits per CTU with the valid width / height the context's geometry gives it (any 1..64).  d_shapes: num_pictures *
+ * band CTUs * 85 records, compact over the band: exactly what fhevc_pu_shape_select_device writes for the same arguments.  d_depth_min / d_depth_max:
+ * compact over the band, entry ((p * band_rows + row - ctu_row_begin) * ctus_per_row + col) * 256; d_tree: num_pictures * band CTUs * 85 records.  Each of
+ * the three outputs may be NULL, not all three; each is written over exactly its extent, an empty band writes nothing.  rule: HOST memory, read during the
+ * call (it travels to the kernel by value); NULL = fhevc_p_tree_rule_default.  Asynchronous with respect to the host, allocates nothing, keeps no state:
+ * calls with different rules may be in flight on two streams.  Stream semantics as fhevc_pu_shape_select_device (NULL = the context's blocking stream), so
+ * the selection and the tree may follow each other on one stream without a host synchronisation.  d_shapes and d_tree may have any alignment their type
+ * allows (4 bytes), the maps any byte alignment: where the maps are 4-byte aligned they leave as dwords, as bytes otherwise; where d_tree is 16-byte aligned
+ * its records leave as 16-byte stores, as dwords otherwise; the bytes written are the same.  Timed under slot 17 of fhevc_kernel_timing.  FHEVC_E_INVALID
+ * with a fhevc_last_error text (nothing is launched or written): a null context or d_shapes, all three outputs null, num_pictures < 1, a bad band, a rule
+ * field outside its range, more than 2^31 - 1 CTUs.  The maps reach the encoder as fhevc_p_depth_range's do (TEncFastDepth::setExternalRange,
+ * INTEGRATION.md); the margins are unfitted. */
+int  fhevc_p_tree_select_device(fhevc_ctx* ctx, const fhevc_pu_shape_node* d_shapes, int num_pictures, int ctu_row_begin, int ctu_row_end,
+                                const fhevc_p_tree_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream);
+/* One picture pair, host buffers (both planes with the same stride), synchronous, on the context's stream: uploads the pair and runs
+ *   coarse_range == 0      the chain of fhevc_p_shape_frame (fhevc_motion_search_pu_wide_device for all three families, search_range 1..64;
+ *                          fhevc_motion_refine_pu_wide_device with max_range = search_range; the selection), then the tree;
+ *   coarse_range 1..14     fhevc_motion_centres_device, fhevc_motion_search_pu_centred_device (search_range 1..8, all three families),
+ *                          fhevc_motion_refine_pu_centred_device (max_range = search_range), the selection, the tree: the centred chain end to end.
+ * shape_rule / tree_rule: NULL = the defaults.  Downloads the two maps (numCtus * 256 bytes each, both required) and, where shapes is not NULL, the
+ * selection's records.  FHEVC_E_INVALID (nothing is launched or written): a null context, plane or map, stride_samples < width, qp outside 0..51,
+ * coarse_range outside 0..14, search_range outside 1..64 (coarse_range 0) or 1..8 (coarse_range > 0), a rule field outside its range. */
+int  fhevc_p_tree_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                        const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min /* numCtus * 256 */,
+                        uint8_t* depth_max /* numCtus * 256 */, fhevc_pu_shape_node* shapes /* numCtus * 85 or NULL */);
+
 /* CTU-row band of rank `rank` out of `world`: rows [begin, end) */
 int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
 
@@ -736,7 +815,8 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
  * (fhevc_motion_refine_pu*), 11 = the searches at HM's SearchRange (fhevc_motion_search_pu_wide*: one launch for nodes and PUs, one for the
  * small PUs, each counted), 12 = the refinements at HM's SearchRange (fhevc_motion_refine_pu_wide*: one launch for the nodes, one for the PUs,
  * each counted), 13 = the partition-size selection (fhevc_pu_shape_select_device), 15 = the coarse motion centres (fhevc_motion_centres*), the searches around them
- * (fhevc_motion_search_pu_centred*) and their refinements (fhevc_motion_refine_pu_centred*), each launch counted; 14 is not a slot and is rejected like any number above 15 */
+ * (fhevc_motion_search_pu_centred*) and their refinements (fhevc_motion_refine_pu_centred*), each launch counted; 14 is not a slot and is rejected like any number above 15
+ * -- except 17 = the P-picture tree decision (fhevc_p_tree_select_device), added later.  16 is not a slot either: it stays rejected, as does any number above 17 */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
 int  fhevc_enable_kernel_timing(fhevc_ctx* ctx, int on);
 
