@@ -41,6 +41,7 @@ SYMBOLS = [
     "fhevc_motion_centres", "fhevc_motion_centres_device", "fhevc_motion_search_pu_centred", "fhevc_motion_search_pu_centred_device",
     "fhevc_motion_refine_pu_centred", "fhevc_motion_refine_pu_centred_device",
     "fhevc_p_tree_rule_default", "fhevc_p_tree_select", "fhevc_p_tree_select_device", "fhevc_p_tree_frame",
+    "fhevc_motion_merge", "fhevc_motion_merge_device", "fhevc_p_tree_select_merge", "fhevc_p_tree_select_merge_device", "fhevc_p_tree_merge_frame",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -89,6 +90,10 @@ MOTION_QPEL_DTYPE = np.dtype([("satd_int", np.uint32), ("satd_best", np.uint32),
 SHAPE_DTYPE = np.dtype([("cost_2Nx2N", np.uint32), ("cost_best", np.uint32), ("cost_second", np.uint32), ("best", np.uint8), ("second", np.uint8),
                         ("mask", np.uint8), ("avail", np.uint8)])
 
+# fhevc_motion_merge_node: the cheapest merge candidate of a CU node (src: 0..4 = L, A, AR, BL, AL, 5 = the zero vector; idx / num: its place in / the length of the list)
+MOTION_MERGE_DTYPE = np.dtype([("satd_best", np.uint32), ("cost_best", np.uint32), ("mvx", np.int16), ("mvy", np.int16), ("idx", np.uint8), ("num", np.uint8),
+                               ("src", np.uint8), ("pad", np.uint8)])
+MERGE_L, MERGE_A, MERGE_AR, MERGE_BL, MERGE_AL, MERGE_ZERO = 0, 1, 2, 3, 4, 5
 # fhevc_p_tree_node: one record per CU node (flags: 1 split_sure, 2 stop_sure, 4 CROSSING, 8 ABSENT, 16 own available, 32 kids available)
 TREE_DTYPE = np.dtype([("cost_own", np.uint32), ("cost_kids", np.uint32), ("cost_tree", np.uint32), ("flags", np.uint8), ("level", np.uint8), ("pad", np.uint8, (2,))])
 
@@ -225,6 +230,11 @@ def load_library(path=None):
     lib.fhevc_p_tree_select.argtypes = [vp, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp]
     lib.fhevc_p_tree_select_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp, vp]
     lib.fhevc_p_tree_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), vp, vp, vp]
+    lib.fhevc_motion_merge.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.fhevc_motion_merge_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.fhevc_p_tree_select_merge.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp]
+    lib.fhevc_p_tree_select_merge_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp, vp]
+    lib.fhevc_p_tree_merge_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), vp, vp, vp, vp]
     lib.fhevc_predict_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, vp, vp]
     lib.fhevc_alloc_host.argtypes = [vp, C.c_size_t]
     lib.fhevc_alloc_host.restype = vp
@@ -316,6 +326,25 @@ def p_tree_select(shapes, width, height, rule=None, with_tree=False):
         rc = lib.fhevc_p_tree_select(shapes[c].ctypes.data, vw, vh, C.byref(rule), dmin[c].ctypes.data, dmax[c].ctypes.data, tree[c].ctypes.data if with_tree else None)
         if rc != OK:
             raise FastHevcError(rc, "fhevc_p_tree_select")
+    return (dmin, dmax, tree) if with_tree else (dmin, dmax)
+
+
+def p_tree_select_merge(shapes, merge, width, height, rule=None, with_tree=False):
+    """p_tree_select with the merge records [numCtus, 85] MOTION_MERGE_DTYPE beside the selection's: a node's own cost is the smaller of the two cost_best"""
+    lib = load_library()
+    rule = rule if rule is not None else p_tree_rule_default()
+    shapes, merge = np.ascontiguousarray(shapes), np.ascontiguousarray(merge)
+    assert shapes.dtype.itemsize == 16 and merge.dtype.itemsize == 16 and merge.shape == shapes.shape
+    cw = (width + 63) // 64
+    n = shapes.shape[0]
+    dmin, dmax = np.zeros((n, 256), np.uint8), np.zeros((n, 256), np.uint8)
+    tree = np.zeros((n, NODES_PER_CTU), TREE_DTYPE) if with_tree else None
+    for c in range(n):
+        vw, vh = min(64, width - (c % cw) * 64), min(64, height - (c // cw) * 64)
+        rc = lib.fhevc_p_tree_select_merge(shapes[c].ctypes.data, merge[c].ctypes.data, vw, vh, C.byref(rule), dmin[c].ctypes.data, dmax[c].ctypes.data,
+                                           tree[c].ctypes.data if with_tree else None)
+        if rc != OK:
+            raise FastHevcError(rc, "fhevc_p_tree_select_merge")
     return (dmin, dmax, tree) if with_tree else (dmin, dmax)
 
 
@@ -543,6 +572,27 @@ class Context:
         rb, re = rows if rows is not None else (0, self.ctus_y)
         self._check(self.lib.fhevc_motion_refine_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range,
                                                         d_nodes, d_out, stream))
+
+    def motion_merge(self, cur_plane, ref_plane, refined, origin=0, stride=None, qp=32, max_range=4):
+        """config 4: the cheapest merge candidate of every CU node from the refined nodes [numCtus, 85] (MOTION_QPEL_DTYPE, as motion_refine returns them
+        for the same planes; only cost_best, mvx, mvy are read) -> [numCtus, 85] MOTION_MERGE_DTYPE.  max_range: the refinement's."""
+        cur = np.ascontiguousarray(cur_plane).reshape(-1)
+        ref = np.ascontiguousarray(ref_plane).reshape(-1)
+        assert cur.dtype == np.int16 and ref.dtype == np.int16
+        refined = np.ascontiguousarray(refined).reshape(-1)
+        assert refined.dtype.itemsize == 16 and refined.size == self.num_ctus * NODES_PER_CTU
+        stride = stride if stride is not None else cur_plane.shape[-1]
+        out = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_MERGE_DTYPE)
+        self._check(self.lib.fhevc_motion_merge(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, max_range,
+                                                refined.ctypes.data, out.ctypes.data))
+        return out.reshape(self.num_ctus, NODES_PER_CTU)
+
+    def motion_merge_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_refined, d_out, rows=None, stream=None, qp=32, max_range=4):
+        """frames 1.. of the batch, each predicted from the frame before it, at the vectors of the neighbours' records in d_refined (what a refinement wrote
+        for the same rows: 85 per CTU); d_out: (num_frames - 1) * band CTUs * 85 merge records (16 B).  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_motion_merge_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range,
+                                                       d_refined, d_out, stream))
 
     def motion_search_pu(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=4, with_nodes=False):
         """config 4: the search of motion_search for the rectangular PUs -> [numCtus, 124] MOTION_DTYPE in the order of motion_pu_index; with_nodes:
@@ -788,6 +838,31 @@ class Context:
         rb, re = rows if rows is not None else (0, self.ctus_y)
         self._check(self.lib.fhevc_p_tree_select_device(self.h, d_shapes, num_pictures, rb, re, C.byref(rule) if rule is not None else None, d_depth_min,
                                                         d_depth_max, d_tree, stream))
+
+    def p_tree_select_merge_device(self, d_shapes, d_merge, num_pictures, d_depth_min=None, d_depth_max=None, d_tree=None, rows=None, stream=None, rule=None):
+        """p_tree_select_device with the merge records of motion_merge_device beside the selection's (85 per CTU, compact over the same rows).  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_p_tree_select_merge_device(self.h, d_shapes, d_merge, num_pictures, rb, re, C.byref(rule) if rule is not None else None,
+                                                              d_depth_min, d_depth_max, d_tree, stream))
+
+    def p_tree_merge_frame(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=8, coarse_range=0, shape_rule=None, tree_rule=None,
+                           with_shapes=False, with_merge=False):
+        """p_tree_frame with the merge stage between refinement and tree -> (depth_min, depth_max) [numCtus, 256], then the records [numCtus, 85] SHAPE_DTYPE
+        (with_shapes) and [numCtus, 85] MOTION_MERGE_DTYPE (with_merge)"""
+        cur = np.ascontiguousarray(cur_plane).reshape(-1)
+        ref = np.ascontiguousarray(ref_plane).reshape(-1)
+        assert cur.dtype == np.int16 and ref.dtype == np.int16
+        stride = stride if stride is not None else cur_plane.shape[-1]
+        dmin, dmax = np.zeros(self.num_ctus * 256, np.uint8), np.zeros(self.num_ctus * 256, np.uint8)
+        shapes = np.zeros(self.num_ctus * NODES_PER_CTU, SHAPE_DTYPE) if with_shapes else None
+        merge = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_MERGE_DTYPE) if with_merge else None
+        self._check(self.lib.fhevc_p_tree_merge_frame(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, search_range, coarse_range,
+                                                      C.byref(shape_rule) if shape_rule is not None else None, C.byref(tree_rule) if tree_rule is not None else None,
+                                                      dmin.ctypes.data, dmax.ctypes.data, shapes.ctypes.data if with_shapes else None,
+                                                      merge.ctypes.data if with_merge else None))
+        out = (dmin.reshape(self.num_ctus, 256), dmax.reshape(self.num_ctus, 256))
+        out += (shapes.reshape(self.num_ctus, NODES_PER_CTU),) if with_shapes else ()
+        return out + ((merge.reshape(self.num_ctus, NODES_PER_CTU),) if with_merge else ())
 
     def p_tree_frame(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=8, coarse_range=0, shape_rule=None, tree_rule=None, with_shapes=False):
         """config 4, one picture pair from host buffers: coarse_range 0: the wide SAD search of all three families, their quarter-sample refinement, the

@@ -292,8 +292,8 @@ int fhevc_enable_kernel_timing(fhevc_ctx* c, int on)
 
 int fhevc_kernel_timing(fhevc_ctx* c, int which, int reset, double* avg_ms, uint64_t* launches)
 {
-  // 14 and 16 stay rejected: callers probe them as the first numbers behind the slots of the partition-size selection and of the centred chain
-  if (!c || which < 0 || which > 17 || which == 14 || which == 16) return FHEVC_E_INVALID;
+  // 14, 16 and 18 stay rejected: callers probe them as the first numbers behind the slots of the partition-size selection, of the centred chain and of the tree
+  if (!c || which < 0 || which > 19 || which == 14 || which == 16 || which == 18) return FHEVC_E_INVALID;
   time_resolve(c);
   if (avg_ms) *avg_ms = c->launches[which] ? c->sum_ms[which] / (double)c->launches[which] : 0.0;
   if (launches) *launches = c->launches[which];
@@ -1104,6 +1104,47 @@ int fhevc_motion_refine(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* re
   return FHEVC_OK;
 }
 
+// ---- merge-candidate costs per CU node from the refined nodes (k_motion_merge.hip) ----
+
+int fhevc_motion_merge_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                              int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_qpel_node* d_refined,
+                              fhevc_motion_merge_node* d_out, void* stream)
+{
+  if (!c || !d_luma || !d_refined || !d_out) return c ? fail(c, FHEVC_E_INVALID, "bad merge-stage arguments") : FHEVC_E_INVALID;
+  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
+  if (max_range < 1 || max_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad merge-stage arguments (max_range 1..64)");
+  if ((long long)(num_frames - 1) * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "more than 2^31 - 1 CTUs");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
+  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
+  static_assert(sizeof(fhevc_motion_merge_node) == sizeof(FhevcMotionMergeNode) && sizeof(FhevcMotionMergeNode) == 16, "merge node layout");
+  return launch_on(c, stream, 19, "fhevc_launch_motion_merge", [&](hipStream_t s) {
+    return fhevc_launch_motion_merge(fr, max_range, mv_bit_cost_table(qp), reinterpret_cast<const FhevcMotionQpelNode*>(d_refined), reinterpret_cast<FhevcMotionMergeNode*>(d_out),
+                                     c->num_cus, s);
+  });
+}
+
+int fhevc_motion_merge(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                       const fhevc_motion_qpel_node* refined, fhevc_motion_merge_node* out)
+{
+  if (!c || !cur_luma || !ref_luma || !refined || !out || stride_samples < c->cfg.width)
+    return c ? fail(c, FHEVC_E_INVALID, "bad merge-stage arguments") : FHEVC_E_INVALID;
+  if (qp < 0 || qp > 51 || max_range < 1 || max_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad merge-stage arguments");
+  (void)hipSetDevice(c->device);
+  const size_t nbytes = motion_bytes(c);   // a merge record is as large as a node of the search: the refined nodes go through d_qpel, the records through d_motion
+  HIP_TRY(c, ensure(c->d_qpel, nbytes));
+  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
+  if (rc != FHEVC_OK) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->d_qpel, refined, nbytes, hipMemcpyHostToDevice, c->stream));
+  c->stats.bytes_h2d += nbytes;
+  rc = fhevc_motion_merge_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, max_range,
+                                 reinterpret_cast<const fhevc_motion_qpel_node*>(c->d_qpel), reinterpret_cast<fhevc_motion_merge_node*>(c->d_motion), c->stream);
+  if (rc != FHEVC_OK) { (void)hipStreamSynchronize(c->stream); return rc; }   // the uploads read the caller's buffers: through before the call returns
+  HIP_TRY(c, hipMemcpyAsync(out, c->d_motion, nbytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->stats.bytes_d2h += (uint64_t)nbytes;
+  return FHEVC_OK;
+}
+
 // ---- quarter-sample refinement of the PUs' vectors (k_motion_refine_pu.hip) ----
 
 int fhevc_motion_refine_pu_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
@@ -1413,11 +1454,12 @@ int fhevc_p_shape_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* re
 }
 
 // ---- P-picture depth ranges from the selection's records over a device-resident batch (k_p_tree.hip; the host form: fhevc_host.hip) ----
-int fhevc_p_tree_select_device(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, int num_pictures, int ctu_row_begin, int ctu_row_end, const fhevc_p_tree_rule* rule,
-                               uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream)
+// d_merge: null for fhevc_p_tree_select_device; with_merge says which of the two entry points is asking
+static int p_tree_select_on(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, const fhevc_motion_merge_node* d_merge, bool with_merge, int num_pictures, int ctu_row_begin,
+                            int ctu_row_end, const fhevc_p_tree_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream)
 {
   if (!c) return FHEVC_E_INVALID;
-  if (!d_shapes || (!d_depth_min && !d_depth_max && !d_tree)) return fail(c, FHEVC_E_INVALID, "bad tree-decision arguments");
+  if (!d_shapes || (with_merge && !d_merge) || (!d_depth_min && !d_depth_max && !d_tree)) return fail(c, FHEVC_E_INVALID, "bad tree-decision arguments");
   // (records have no sample layout: the checks of the pictures' number and the band)
   if (const char* bad = batch_error(c, 2, c->cfg.width, 0, num_pictures, 1, ctu_row_begin, ctu_row_end, 0, false)) return fail(c, FHEVC_E_INVALID, bad);
   static_assert(sizeof(fhevc_p_tree_rule) == sizeof(FhevcPTreeRule) && sizeof(fhevc_p_tree_node) == sizeof(FhevcPTreeNode), "tree-decision layouts");
@@ -1428,13 +1470,32 @@ int fhevc_p_tree_select_device(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes
   if ((long long)num_pictures * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "more than 2^31 - 1 CTUs");
   if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
   const FhevcFrames fr = frames_of(c, nullptr, 1, c->cfg.width, 0, num_pictures, ctu_row_begin, ctu_row_end);
+  if (with_merge)
+    return launch_on(c, stream, 17, "fhevc_launch_p_tree_merge", [&](hipStream_t s) {
+      return fhevc_launch_p_tree_merge(fr, r, reinterpret_cast<const FhevcPuShapeNode*>(d_shapes), reinterpret_cast<const FhevcMotionMergeNode*>(d_merge), d_depth_min, d_depth_max,
+                                       reinterpret_cast<FhevcPTreeNode*>(d_tree), c->num_cus, s);
+    });
   return launch_on(c, stream, 17, "fhevc_launch_p_tree", [&](hipStream_t s) {
     return fhevc_launch_p_tree(fr, r, reinterpret_cast<const FhevcPuShapeNode*>(d_shapes), d_depth_min, d_depth_max, reinterpret_cast<FhevcPTreeNode*>(d_tree), c->num_cus, s);
   });
 }
 
-int fhevc_p_tree_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
-                       const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes)
+int fhevc_p_tree_select_device(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, int num_pictures, int ctu_row_begin, int ctu_row_end, const fhevc_p_tree_rule* rule,
+                               uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream)
+{
+  return p_tree_select_on(c, d_shapes, nullptr, false, num_pictures, ctu_row_begin, ctu_row_end, rule, d_depth_min, d_depth_max, d_tree, stream);
+}
+
+int fhevc_p_tree_select_merge_device(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, const fhevc_motion_merge_node* d_merge, int num_pictures, int ctu_row_begin,
+                                     int ctu_row_end, const fhevc_p_tree_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream)
+{
+  return p_tree_select_on(c, d_shapes, d_merge, true, num_pictures, ctu_row_begin, ctu_row_end, rule, d_depth_min, d_depth_max, d_tree, stream);
+}
+
+// with_merge: fhevc_p_tree_merge_frame -- the merge stage between refinement and tree; its records go where the integer PUs were once the refinement has read them
+static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                           const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes,
+                           bool with_merge, fhevc_motion_merge_node* merge)
 {
   if (!c) return FHEVC_E_INVALID;
   if (!cur_luma || !ref_luma || !depth_min || !depth_max || stride_samples < c->cfg.width) return fail(c, FHEVC_E_INVALID, "bad tree-decision frame arguments");
@@ -1467,6 +1528,7 @@ int fhevc_p_tree_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref
   fhevc_motion_qpel_node* q_pus = reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu);
   fhevc_motion_qpel_node* q_small = reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu_small);
   fhevc_pu_shape_node* d_shapes = reinterpret_cast<fhevc_pu_shape_node*>(c->d_motion);
+  fhevc_motion_merge_node* d_merge = reinterpret_cast<fhevc_motion_merge_node*>(c->d_motion_pu);   // 85 of the 124 entries per CTU
   const long long plane = (long long)pair_plane(c);
   if (coarse_range) {
     rc = fhevc_motion_centres_device(c, c->d_pair, 2, c->dev_stride, plane, 2, 0, c->ctus_y, qp, coarse_range, centres, c->stream);
@@ -1481,15 +1543,35 @@ int fhevc_p_tree_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref
       rc = fhevc_motion_refine_pu_wide_device(c, c->d_pair, 2, c->dev_stride, plane, 2, 0, c->ctus_y, qp, search_range, nodes, q_nodes, pus, q_pus, small, q_small,
                                               c->stream);
   }
+  // absolute vectors of the centred chain reach +-64 and neighbouring CTUs have different centres: the merge stage looks around zero at the full range there
+  if (rc == FHEVC_OK && with_merge)
+    rc = fhevc_motion_merge_device(c, c->d_pair, 2, c->dev_stride, plane, 2, 0, c->ctus_y, qp, coarse_range ? FHEVC_MOTION_WIDE_MAX_RANGE : search_range, q_nodes, d_merge,
+                                   c->stream);
   if (rc == FHEVC_OK) rc = fhevc_pu_shape_select_device(c, q_nodes, q_pus, q_small, 1, 0, c->ctus_y, shape_rule, d_shapes, nullptr, c->stream);
-  if (rc == FHEVC_OK) rc = fhevc_p_tree_select_device(c, d_shapes, 1, 0, c->ctus_y, tree_rule, c->d_p_maps + maps, c->d_p_maps + 2 * maps, nullptr, c->stream);
+  if (rc == FHEVC_OK && with_merge)
+    rc = fhevc_p_tree_select_merge_device(c, d_shapes, d_merge, 1, 0, c->ctus_y, tree_rule, c->d_p_maps + maps, c->d_p_maps + 2 * maps, nullptr, c->stream);
+  else if (rc == FHEVC_OK) rc = fhevc_p_tree_select_device(c, d_shapes, 1, 0, c->ctus_y, tree_rule, c->d_p_maps + maps, c->d_p_maps + 2 * maps, nullptr, c->stream);
   if (rc != FHEVC_OK) { (void)hipStreamSynchronize(c->stream); return rc; }   // the uploads read the caller's buffers: through before the call returns
   HIP_TRY(c, hipMemcpyAsync(depth_min, c->d_p_maps + maps, maps, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(depth_max, c->d_p_maps + 2 * maps, maps, hipMemcpyDeviceToHost, c->stream));
   if (shapes) HIP_TRY(c, hipMemcpyAsync(shapes, c->d_motion, node_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (with_merge && merge) HIP_TRY(c, hipMemcpyAsync(merge, c->d_motion_pu, node_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->stats.bytes_d2h += (uint64_t)(2 * maps + (shapes ? node_bytes : 0));
+  c->stats.bytes_d2h += (uint64_t)(2 * maps + (shapes ? node_bytes : 0) + (with_merge && merge ? node_bytes : 0));
   return FHEVC_OK;
+}
+
+int fhevc_p_tree_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                       const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes)
+{
+  return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, false, nullptr);
+}
+
+int fhevc_p_tree_merge_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                             const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes,
+                             fhevc_motion_merge_node* merge)
+{
+  return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge);
 }
 
 // Diagnostic (not part of include/fasthevc.h): run the stamped instantiation of the depth kernel over a

@@ -49,8 +49,8 @@ struct fhevc_ctx {
   bool timing = false;
   std::vector<TimedLaunch> pending;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-  double sum_ms[18] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };     // slots 14 and 16 are not in use (fhevc_kernel_timing rejects them)
-  uint64_t launches[18] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+  double sum_ms[20] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };     // slots 14, 16 and 18 are not in use (fhevc_kernel_timing rejects them)
+  uint64_t launches[20] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
   double* d_act = nullptr;
   int16_t* d_pair = nullptr;          // two staging planes (reference, current) of fhevc_motion_search
   FhevcMotionNode* d_motion = nullptr;     // ... and, once the refinement has read them, the records of fhevc_p_shape_frame (an entry is as large)

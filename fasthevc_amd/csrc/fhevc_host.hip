@@ -324,8 +324,11 @@ void fhevc_p_tree_rule_default(fhevc_p_tree_rule* rule)
   std::memset(rule, 0, sizeof *rule);   // the unfitted hard decision: no margins, no split cost
 }
 
-int fhevc_p_tree_select(const fhevc_pu_shape_node* shapes, int valid_w, int valid_h, const fhevc_p_tree_rule* rule, uint8_t* depth_min, uint8_t* depth_max,
-                        fhevc_p_tree_node* tree)
+}  // extern "C"
+
+// merge: null for fhevc_p_tree_select; otherwise the CTU's 85 merge records, of which cost_best is read
+static int p_tree_select(const fhevc_pu_shape_node* shapes, const fhevc_motion_merge_node* merge, int valid_w, int valid_h, const fhevc_p_tree_rule* rule, uint8_t* depth_min,
+                         uint8_t* depth_max, fhevc_p_tree_node* tree)
 {
   if (!shapes || !rule || (!depth_min && !depth_max && !tree) || valid_w < 8 || valid_w > 64 || valid_h < 8 || valid_h > 64 || fhevc_p_tree_rule_error(*rule))
     return FHEVC_E_INVALID;
@@ -343,7 +346,10 @@ int fhevc_p_tree_select(const fhevc_pu_shape_node* shapes, int valid_w, int vali
     if (lvl < 3) { sure[k] = false; maybe[k] = true; }
     if (outside || (lvl == 3 && !inside)) { n.flags = 8; continue; }   // no CU is coded there
     if (inside) n.cost_own = shapes[k].cost_best;
-    if (lvl == 3) { n.cost_tree = n.cost_own; n.flags = n.cost_own != mark ? 16 : 0; continue; }
+    // the merge cost is taken where it is strictly smaller: the marker is the largest value, so an unavailable one never is, and any cost beats a marker
+    const bool merged = inside && merge && merge[k].cost_best < n.cost_own;
+    if (merged) n.cost_own = merge[k].cost_best;
+    if (lvl == 3) { n.cost_tree = n.cost_own; n.flags = (uint8_t)((n.cost_own != mark ? 16 : 0) | (merged ? 64 : 0)); continue; }
     uint64_t sum = inside ? (uint64_t)rule->split_cost[lvl] : 0;
     bool marked = false;
     for (int c = 0; c < 4; ++c) {
@@ -363,7 +369,7 @@ int fhevc_p_tree_select(const fhevc_pu_shape_node* shapes, int valid_w, int vali
       split = kids + (uint64_t)rule->split_abs[lvl] + ((kids * (uint64_t)rule->split_q8[lvl]) >> 8) < own;
       stop = own + (uint64_t)rule->stop_abs[lvl] + ((own * (uint64_t)rule->stop_q8[lvl]) >> 8) <= kids;
     }
-    n.flags = (uint8_t)((split ? 1 : 0) | (stop ? 2 : 0) | (!inside ? 4 : 0) | (own != mark ? 16 : 0) | (kids != mark ? 32 : 0));
+    n.flags = (uint8_t)((split ? 1 : 0) | (stop ? 2 : 0) | (!inside ? 4 : 0) | (own != mark ? 16 : 0) | (kids != mark ? 32 : 0) | (merged ? 64 : 0));
     sure[k] = !inside || split;
     maybe[k] = !inside || !stop;
   }
@@ -386,6 +392,21 @@ int fhevc_p_tree_select(const fhevc_pu_shape_node* shapes, int valid_w, int vali
       if (depth_max) depth_max[uy * 16 + ux] = (uint8_t)hi;
     }
   return FHEVC_OK;
+}
+
+extern "C" {
+
+int fhevc_p_tree_select(const fhevc_pu_shape_node* shapes, int valid_w, int valid_h, const fhevc_p_tree_rule* rule, uint8_t* depth_min, uint8_t* depth_max,
+                        fhevc_p_tree_node* tree)
+{
+  return p_tree_select(shapes, nullptr, valid_w, valid_h, rule, depth_min, depth_max, tree);
+}
+
+int fhevc_p_tree_select_merge(const fhevc_pu_shape_node* shapes, const fhevc_motion_merge_node* merge, int valid_w, int valid_h, const fhevc_p_tree_rule* rule,
+                              uint8_t* depth_min, uint8_t* depth_max, fhevc_p_tree_node* tree)
+{
+  if (!merge) return FHEVC_E_INVALID;
+  return p_tree_select(shapes, merge, valid_w, valid_h, rule, depth_min, depth_max, tree);
 }
 
 int fhevc_p_motion_compensated_depth(const fhevc_motion_node* nodes, const uint8_t* prev_map, int width, int height, int ctu, uint8_t* out)

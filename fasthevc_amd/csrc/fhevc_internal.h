@@ -230,6 +230,13 @@ struct FhevcMotionQpelNode { uint32_t satd_int, satd_best, cost_best; int16_t mv
 hipError_t fhevc_launch_motion_refine(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_nodes, FhevcMotionQpelNode* d_out,
                                       int num_cus, hipStream_t stream);
 
+// ---- merge-candidate costs per CU node from the refined nodes of the same level (k_motion_merge.hip; config 4) --------------------------
+struct FhevcMotionMergeNode { uint32_t satd_best, cost_best; int16_t mvx, mvy; uint8_t idx, num, src, pad; };
+// fr, max_range (1 .. FHEVC_MOTION_WIDE_MAX_RANGE), cost as fhevc_launch_motion_refine; d_refined: (num_frames - 1) * band CTUs * 85 refined nodes of which
+// cost_best, mvx and mvy are read; d_out: as many records
+hipError_t fhevc_launch_motion_merge(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionQpelNode* d_refined, FhevcMotionMergeNode* d_out,
+                                     int num_cus, hipStream_t stream);
+
 // ---- ... and of the PUs' vectors (k_motion_refine_pu.hip; config 4) --------------------------------------------------
 // fr, max_range (1 .. FHEVC_MOTION_WIDE_MAX_RANGE: up to FHEVC_MOTION_MAX_RANGE the MR = 8 layout, above it the MR = 64 layout with its window in dynamic LDS),
 // cost as fhevc_launch_motion_refine; d_pus / d_out_pus: (num_frames - 1) * band CTUs * 124 entries in the order of fhevc_motion_pu_index, d_pus_small /
@@ -312,6 +319,10 @@ struct FhevcPTreeNode { uint32_t cost_own, cost_kids, cost_tree; uint8_t flags, 
 // them; d_depth_min / d_depth_max: ... * 256 bytes; d_tree: ... * 85 records; each output may be null (not all three); all compact over the band
 hipError_t fhevc_launch_p_tree(const FhevcFrames& fr, const FhevcPTreeRule& rule, const FhevcPuShapeNode* d_shapes, uint8_t* d_depth_min, uint8_t* d_depth_max,
                                FhevcPTreeNode* d_tree, int num_cus, hipStream_t stream);
+// ... with the merge records of fhevc_launch_motion_merge beside the selection's (never null): a node's own cost is the smaller of the two, and bit 6 of the
+// record's flags says that the merge cost is the one taken
+hipError_t fhevc_launch_p_tree_merge(const FhevcFrames& fr, const FhevcPTreeRule& rule, const FhevcPuShapeNode* d_shapes, const FhevcMotionMergeNode* d_merge,
+                                     uint8_t* d_depth_min, uint8_t* d_depth_max, FhevcPTreeNode* d_tree, int num_cus, hipStream_t stream);
 
 // ---- adaptive-QP pre-analysis (k_preanalyze.hip) -----------------------------------------------------------
 // d_activity: per frame parts_per_frame doubles, layers concatenated (layer d: ceil(H/P) x ceil(W/P), P = 64 >> d)

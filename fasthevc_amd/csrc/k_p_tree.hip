@@ -46,8 +46,9 @@ __device__ __forceinline__ uint64_t sum4(uint64_t v, int a, int b)
 }
 
 // the node of level L (0..2) at sample (x, y) of the CTU: cost_best of its record, the sum of what its four children hand it
+// merged (the merge variant only): the record's merge cost is the smaller one -- bit 6 of an INSIDE node's flags
 template <int L>
-__device__ __forceinline__ TreeNode decide(const FhevcPTreeRule& R, uint32_t cost_best, uint64_t sum, int x, int y, int valid_w, int valid_h)
+__device__ __forceinline__ TreeNode decide(const FhevcPTreeRule& R, uint32_t cost_best, uint64_t sum, int x, int y, int valid_w, int valid_h, bool merged)
 {
   constexpr int S = 64 >> L;
   const bool inside = x + S <= valid_w && y + S <= valid_h, outside = x >= valid_w || y >= valid_h;
@@ -64,6 +65,7 @@ __device__ __forceinline__ TreeNode decide(const FhevcPTreeRule& R, uint32_t cos
   n.sure = !inside || split;
   n.maybe = !inside || !stop;
   n.flags = (split ? 1u : 0u) | (stop ? 2u : 0u) | (!inside ? 4u : 0u) | (n.own != kMark ? 16u : 0u) | (n.kids != kMark ? 32u : 0u);
+  if (merged && inside) n.flags |= 64u;
   if (outside) { n.own = n.kids = n.tree = kMark; n.flags = 8u; }
   return n;
 }
@@ -81,10 +83,17 @@ __device__ __forceinline__ void store_record(uint32_t* dst, uint32_t own, uint32
 }
 
 // WIDE_MAPS: both map pointers are 4-byte aligned (dword stores; otherwise bytes); WIDE_TREE: tree is 16-byte aligned (16-byte stores; otherwise dwords)
-template <bool WIDE_MAPS, bool WIDE_TREE>
+// M... (fhevc_p_tree_select_merge_device): empty, or ONE const uint32_t* -- the records of k_motion_merge.hip beside the selection's, of which cost_best
+// (dword 1) is read by the same lanes in the same two loads; a node's cost is the smaller of the two (the marker is the largest value, so it loses to any
+// cost), bit 6 of its flags says that the merge cost is strictly smaller.  A pack keeps the plain instantiation's argument list, and so its code, what it was
+__device__ __forceinline__ const uint32_t* merge_of() { return nullptr; }
+__device__ __forceinline__ const uint32_t* merge_of(const uint32_t* m) { return m; }
+template <bool WIDE_MAPS, bool WIDE_TREE, class... M>
 __global__ __launch_bounds__(256) void fhevc_p_tree_kernel(PTreeGeom G, FhevcPTreeRule R, const uint32_t* __restrict__ shapes, uint8_t* __restrict__ depth_min,
-                                                           uint8_t* __restrict__ depth_max, uint32_t* __restrict__ tree)
+                                                           uint8_t* __restrict__ depth_max, uint32_t* __restrict__ tree, M... merge_arg)
 {
+  constexpr bool MERGE = sizeof...(M) != 0;
+  const uint32_t* __restrict__ merge = merge_of(merge_arg...);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int x = (lane & 7) * 8, y = (lane >> 3) * 8;   // this lane's 8x8 node
   // where this lane's ancestors sit among lanes 0..20 of the second load
@@ -103,15 +112,24 @@ __global__ __launch_bounds__(256) void fhevc_p_tree_kernel(PTreeGeom G, FhevcPTr
     const int x0 = (ctu % G.ctus_x) * 64, y0 = (ctu / G.ctus_x) * 64;
     const int valid_w = min(64, G.width - x0), valid_h = min(64, G.height - y0);
     const uint32_t* src = shapes + (size_t)g * (FHEVC_NODES * 4);
-    const uint32_t leaf = src[4 * (21 + lane) + 1], upper = src[4 * min(lane, 20) + 1];
+    uint32_t leaf = src[4 * (21 + lane) + 1], upper = src[4 * min(lane, 20) + 1];
+    bool leaf_merged = false, upper_merged = false;
+    if constexpr (MERGE) {
+      const uint32_t* msrc = merge + (size_t)g * (FHEVC_NODES * 4);
+      const uint32_t mleaf = msrc[4 * (21 + lane) + 1], mupper = msrc[4 * min(lane, 20) + 1];
+      leaf_merged = mleaf < leaf; upper_merged = mupper < upper;
+      leaf = leaf_merged ? mleaf : leaf; upper = upper_merged ? mupper : upper;
+    }
 
     // ---- level 3: a leaf is coded iff it lies wholly inside ----
     const bool inside8 = x + 8 <= valid_w && y + 8 <= valid_h;
     const uint32_t own8 = inside8 ? leaf : kMark;
     // ---- levels 2, 1, 0: every lane decides the node around it ----
-    const TreeNode n16 = decide<2>(R, __shfl(upper, k16), sum4(share(own8, !inside8), 1, 8), x & 48, y & 48, valid_w, valid_h);
-    const TreeNode n32 = decide<1>(R, __shfl(upper, k32), sum4(share(n16.tree, n16.flags == 8u), 2, 16), x & 32, y & 32, valid_w, valid_h);
-    const TreeNode n64 = decide<0>(R, __shfl(upper, 0), sum4(share(n32.tree, n32.flags == 8u), 4, 32), 0, 0, valid_w, valid_h);
+    // (the merge variant hands the "merged" bit along in bit 0 of a second shuffle; the plain one passes a constant)
+    const uint32_t um = MERGE ? (uint32_t)upper_merged : 0u;
+    const TreeNode n16 = decide<2>(R, __shfl(upper, k16), sum4(share(own8, !inside8), 1, 8), x & 48, y & 48, valid_w, valid_h, MERGE && __shfl(um, k16) != 0u);
+    const TreeNode n32 = decide<1>(R, __shfl(upper, k32), sum4(share(n16.tree, n16.flags == 8u), 2, 16), x & 32, y & 32, valid_w, valid_h, MERGE && __shfl(um, k32) != 0u);
+    const TreeNode n64 = decide<0>(R, __shfl(upper, 0), sum4(share(n32.tree, n32.flags == 8u), 4, 32), 0, 0, valid_w, valid_h, MERGE && __shfl(um, 0) != 0u);
 
     // ---- the maps: the depths the decisions open top-down, 0 outside the picture ----
     if (depth_min || depth_max) {
@@ -133,7 +151,7 @@ __global__ __launch_bounds__(256) void fhevc_p_tree_kernel(PTreeGeom G, FhevcPTr
     // ---- the records: node 21 + lane from every lane, node `lane` from lanes 0..20 ----
     if (tree) {
       uint32_t* dst = tree + (size_t)g * (FHEVC_NODES * 4);
-      store_record(dst + 4 * (21 + lane), own8, kMark, own8, (inside8 ? (own8 != kMark ? 16u : 0u) : 8u) | 3u << 8, WIDE_TREE);
+      store_record(dst + 4 * (21 + lane), own8, kMark, own8, (inside8 ? (own8 != kMark ? 16u : 0u) | (MERGE && leaf_merged ? 64u : 0u) : 8u) | 3u << 8, WIDE_TREE);
       const TreeNode& mine = serves == 2 ? n16 : (serves == 1 ? n32 : n64);
       const uint32_t own = __shfl(mine.own, rec_src), kids = __shfl(mine.kids, rec_src), best = __shfl(mine.tree, rec_src), flags = __shfl(mine.flags, rec_src);
       if (lane < 21) store_record(dst + 4 * lane, own, kids, best, flags | (uint32_t)rec_level << 8, WIDE_TREE);
@@ -143,10 +161,10 @@ __global__ __launch_bounds__(256) void fhevc_p_tree_kernel(PTreeGeom G, FhevcPTr
 
 }  // namespace
 
-hipError_t fhevc_launch_p_tree(const FhevcFrames& fr, const FhevcPTreeRule& rule, const FhevcPuShapeNode* d_shapes, uint8_t* d_depth_min, uint8_t* d_depth_max,
-                               FhevcPTreeNode* d_tree, int num_cus, hipStream_t stream)
+static hipError_t launch_p_tree(const FhevcFrames& fr, const FhevcPTreeRule& rule, const FhevcPuShapeNode* d_shapes, const FhevcMotionMergeNode* d_merge, uint8_t* d_depth_min,
+                                uint8_t* d_depth_max, FhevcPTreeNode* d_tree, int num_cus, hipStream_t stream)
 {
-  static_assert(sizeof(FhevcPuShapeNode) == 16 && sizeof(FhevcPTreeNode) == 16 && sizeof(FhevcPTreeRule) == 60, "record layouts");
+  static_assert(sizeof(FhevcPuShapeNode) == 16 && sizeof(FhevcPTreeNode) == 16 && sizeof(FhevcPTreeRule) == 60 && sizeof(FhevcMotionMergeNode) == 16, "record layouts");
   PTreeGeom G;
   G.width = fr.width; G.height = fr.height; G.ctus_x = fr.ctus_x;
   G.row_begin = fr.row_begin; G.band_ctus = (fr.row_end - fr.row_begin) * fr.ctus_x;
@@ -160,11 +178,31 @@ hipError_t fhevc_launch_p_tree(const FhevcFrames& fr, const FhevcPTreeRule& rule
   // the records are read as dwords whatever their alignment (4 bytes by type)
   const bool wide_maps = (((uintptr_t)d_depth_min | (uintptr_t)d_depth_max) & 3) == 0, wide_tree = ((uintptr_t)d_tree & 15) == 0;
   const uint32_t* shapes = reinterpret_cast<const uint32_t*>(d_shapes);
+  const uint32_t* merge = reinterpret_cast<const uint32_t*>(d_merge);   // cost_best is dword 1 of a merge record too
   uint32_t* tree = reinterpret_cast<uint32_t*>(d_tree);
   const dim3 blocks((unsigned)grid), threads(256);
-  if (wide_maps && wide_tree) hipLaunchKernelGGL((fhevc_p_tree_kernel<true, true>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree);
+  if (merge) {
+    if (wide_maps && wide_tree) hipLaunchKernelGGL((fhevc_p_tree_kernel<true, true, const uint32_t*>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree, merge);
+    else if (wide_maps) hipLaunchKernelGGL((fhevc_p_tree_kernel<true, false, const uint32_t*>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree, merge);
+    else if (wide_tree) hipLaunchKernelGGL((fhevc_p_tree_kernel<false, true, const uint32_t*>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree, merge);
+    else hipLaunchKernelGGL((fhevc_p_tree_kernel<false, false, const uint32_t*>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree, merge);
+  }
+  else if (wide_maps && wide_tree) hipLaunchKernelGGL((fhevc_p_tree_kernel<true, true>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree);
   else if (wide_maps) hipLaunchKernelGGL((fhevc_p_tree_kernel<true, false>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree);
   else if (wide_tree) hipLaunchKernelGGL((fhevc_p_tree_kernel<false, true>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree);
   else hipLaunchKernelGGL((fhevc_p_tree_kernel<false, false>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree);
   return hipGetLastError();
+}
+
+hipError_t fhevc_launch_p_tree(const FhevcFrames& fr, const FhevcPTreeRule& rule, const FhevcPuShapeNode* d_shapes, uint8_t* d_depth_min, uint8_t* d_depth_max,
+                               FhevcPTreeNode* d_tree, int num_cus, hipStream_t stream)
+{
+  return launch_p_tree(fr, rule, d_shapes, nullptr, d_depth_min, d_depth_max, d_tree, num_cus, stream);
+}
+
+hipError_t fhevc_launch_p_tree_merge(const FhevcFrames& fr, const FhevcPTreeRule& rule, const FhevcPuShapeNode* d_shapes, const FhevcMotionMergeNode* d_merge,
+                                     uint8_t* d_depth_min, uint8_t* d_depth_max, FhevcPTreeNode* d_tree, int num_cus, hipStream_t stream)
+{
+  if (!d_merge) return hipErrorInvalidValue;
+  return launch_p_tree(fr, rule, d_shapes, d_merge, d_depth_min, d_depth_max, d_tree, num_cus, stream);
 }

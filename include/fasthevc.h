@@ -759,7 +759,8 @@ typedef struct {
   uint32_t cost_own;        /* own[k] */
   uint32_t cost_kids;       /* kids[k] */
   uint32_t cost_tree;       /* tree[k] */
-  uint8_t  flags;           /* bit 0 split_sure, bit 1 stop_sure, bit 2 CROSSING, bit 3 ABSENT, bit 4 own available (!= MARK), bit 5 kids available */
+  uint8_t  flags;           /* bit 0 split_sure, bit 1 stop_sure, bit 2 CROSSING, bit 3 ABSENT, bit 4 own available (!= MARK), bit 5 kids available;
+                             * bit 6 (fhevc_p_tree_select_merge* only): own is the merge cost */
   uint8_t  level;           /* l */
   uint8_t  pad[2];          /* written 0 */
 } fhevc_p_tree_node;        /* 16 bytes; an ABSENT node gets three MARKs and bit 3 only */
@@ -804,6 +805,90 @@ int  fhevc_p_tree_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* 
                         const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min /* numCtus * 256 */,
                         uint8_t* depth_max /* numCtus * 256 */, fhevc_pu_shape_node* shapes /* numCtus * 85 or NULL */);
 
+/* ---- config 4 (P slices): merge-candidate costs per CU node (k_motion_merge.hip) -------------------------------------------------------------
+ * Every inter cost above is the cost of an explicitly coded vector: a Hadamard distortion plus the exp-Golomb bits of the vector.  HM checks something else
+ * first at every CU of a P picture (TEncCu::xCheckRDCostMerge2Nx2N, a full RD check of every merge candidate of the 2Nx2N CU), and for every PU of the OTHER
+ * partition sizes predInterSearch runs TEncSearch::xMergeEstimation (TEncSearch.cpp:2831-2884, called at :3371 under `getPartitionSize != SIZE_2Nx2N`, :3336):
+ * the same Hadamard distortion at a vector INHERITED from a spatial neighbour, priced at one to four bits of merge index and no vector bits at all.  HM does
+ * not run xMergeEstimation for a 2Nx2N CU; this entry point APPLIES its pricing to the square CU node -- a source-only estimate of what the 2Nx2N merge check
+ * finds -- on what a source-only pass has: the vectors the neighbouring nodes of the SAME level were refined to.
+ * Input: the 85 refined square nodes per CTU, fhevc_motion_qpel_node records, (num_frames - 1) * band CTUs * 85, compact over the band -- what
+ * fhevc_motion_refine_device, the d_out_nodes of fhevc_motion_refine_pu_wide_device or of fhevc_motion_refine_pu_centred_device wrote for the same pictures
+ * and band.  Only cost_best (for the marker test), mvx and mvy (quarter samples) are read.  qp 0..51, max_range 1..64.
+ * Geometry: node k of level l (s = 64 >> l, N = 1 << l) at (bx, by) in CTU (cx, cy) has the grid position (gx, gy) = (cx N + bx, cy N + by) in the picture; it
+ * is valid iff it lies wholly inside the picture (INSIDE as for fhevc_p_tree_select); its coding-order key is (CTU raster index, z-index of (bx, by) at level
+ * l), the z-index being the bit interleave with x in the even bits.
+ * Candidate positions: HM's five spatial positions (TComDataCU::getInterMergeCandidates, TComDataCU.cpp:2142-2320) mapped to the same-level node that holds
+ * HM's sample:
+ *   j = 0  L   (A1)  node (gx - 1, gy)          j = 1  A   (B1)  node (gx, gy - 1)          j = 2  AR  (B0)  node (gx + 1, gy - 1)
+ *   j = 3  BL  (A0)  node (gx - 1, gy + 1)      j = 4  AL  (B2)  node (gx - 1, gy - 1)
+ * avail[j] iff ALL of: the neighbour lies on the level's grid and is INSIDE; its CTU row lies in [ctu_row_begin, ctu_row_end) -- a band behaves as a slice,
+ * candidates never cross it, as in HM --; its key is smaller than the node's own (always so for L, A and AL; for AR and BL this decides exactly what
+ * getPUAboveRight and getPUBelowLeft decide for CUs of equal size); its record's cost_best != 0xFFFFFFFF; |mvx| <= 4 max_range + 3 and |mvy| <= 4 max_range + 3,
+ * the reach of a refined vector, so that no input byte can send a read outside the staged window.
+ * List, in HM's order with HM's pruning pairs (vectors compared as (mvx, mvy)):
+ *   1. L   if avail[L]                                              2. A   if avail[A] and not (avail[L] and v_A = v_L)
+ *   3. AR  if avail[AR] and not (avail[A] and v_AR = v_A)           4. BL  if avail[BL] and not (avail[L] and v_BL = v_L)
+ *   5. AL  only if the list holds fewer than 4 entries, avail[AL], and its vector equals neither an available L's nor an available A's
+ *   6. the zero vector if the list holds fewer than 5 entries; it is not pruned
+ * so the list is never empty.  Two parts of HM's list are left out: HM fills the rest of its list with zero candidates (of which only the first can win
+ * under strict "<", so one is enough), and the temporal candidate needs a coded co-located picture.
+ * Cost of list entry i with vector q: sd(q) + c[bits], bits = i + 1 except bits = 4 for i = 4 (MaxNumMergeCand 5, TEncSearch.cpp:2869-2874).  sd(q) is
+ * TComRdCost::xGetHADs of the whole node -- the sum over its 8x8 tiles of (sum |H8 d H8| + 2) >> 2, the node's sum shifted ONCE by bit_depth - 8 -- on
+ * fhevc_motion_refine's prediction: HEVC's 8-tap interpolation of the PREVIOUS ORIGINAL picture in that entry point's one arithmetic form, coordinates
+ * clamped to the picture.  c[b] = getCost(b) at the lambda of slice QP qp, the table the refinements pass by value: predInterSearch calls
+ * m_pcRdCost->selectMotionLambda(true, 0, ..) at TEncSearch.cpp:3345, before the xMergeEstimation of :3371, and xMotionEstimation selects the same lambda
+ * again (:3717), so the getCost of :2874 runs under the motion estimation's lambda; getCost(bits) does not involve the cost scale.  The winner takes strict
+ * "<": the first entry of equal cost wins. */
+typedef struct {
+  uint32_t satd_best;       /* sd at the winner */
+  uint32_t cost_best;       /* its cost */
+  int16_t  mvx, mvy;        /* the winner's vector, quarter samples */
+  uint8_t  idx;             /* the winner's position in the list */
+  uint8_t  num;             /* the list's length, 1..5 */
+  uint8_t  src;             /* where the winner came from: 0..4 = L, A, AR, BL, AL; 5 = the zero vector */
+  uint8_t  pad;             /* written 0 */
+} fhevc_motion_merge_node;  /* 16 bytes; a node that is not INSIDE gets 0xFFFFFFFF twice, a zero vector, idx = src = 255, num = 0, pad = 0 */
+/* Device form: planes, band and stream arguments as fhevc_motion_refine_device; frame f = 1 .. num_frames-1 is predicted from frame f-1.  d_refined, d_out:
+ * (num_frames - 1) * band CTUs * 85 records, compact over the band; the output is written over exactly that extent, an empty band writes nothing.  The
+ * kernel has the square refinement's mapping (a workgroup of four waves per CTU over a persistent grid, wave = level, lane = 8x8 tile, the window of that
+ * kernel in LDS: the MR = 8 layout up to max_range 8, the MR = 64 layout above, of which the part max_range reaches is staged) and walks the node's list of
+ * at most five entries where that kernel walks 18 candidates.  Asynchronous with respect to the host, allocates nothing, keeps NO state in HBM between calls
+ * (the bit costs travel by value): calls with different QPs and ranges may be in flight on two streams, and a refinement and the merge stage may follow each
+ * other on one stream without a host synchronisation.  FHEVC_E_INVALID with a fhevc_last_error text (nothing is launched or written): a null context, d_luma,
+ * d_refined or d_out, num_frames < 2, qp outside 0..51, max_range outside 1..64, stride_samples < width, a bad band, overlapping frames, uint8 planes on a
+ * context above 8 bit -- whatever fhevc_motion_refine_device rejects.  Timed under slot 19 of fhevc_kernel_timing.
+ * NOT covered: merge for rectangular PUs, HM's second-PU and parallel-merge-level rules, the temporal candidate, candidates from neighbours of a finer level
+ * than the node's own, a window staged around per-CTU centres, skip detection.  The encoder hook does not consume this output. */
+int  fhevc_motion_merge_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                               int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_qpel_node* d_refined,
+                               fhevc_motion_merge_node* d_out, void* stream);
+/* one picture pair, host buffers (both planes with the same stride), synchronous, as fhevc_motion_refine; refined, out: numCtus * 85 */
+int  fhevc_motion_merge(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                        const fhevc_motion_qpel_node* refined, fhevc_motion_merge_node* out);
+
+/* The tree decision WITH the merge costs: fhevc_p_tree_select[_device] with one more input, the CTU's 85 fhevc_motion_merge_node records (never NULL; on the
+ * device compact over the band like d_shapes; only cost_best is read).  The one change to the definition above is the own cost: for an INSIDE node
+ *   own[k] = the smaller of shapes[k].cost_best and merge[k].cost_best, MARK counting as unavailable (both MARK: own[k] = MARK)
+ * and bit 6 of the record's flags is set iff the node is INSIDE and the merge cost is available and strictly smaller than shapes[k].cost_best, or that is
+ * MARK -- which, MARK being the largest value, is merge[k].cost_best < shapes[k].cost_best.  Everything else -- kids, tree, margins, maps, CROSSING / ABSENT,
+ * NULL outputs, alignments, the rule by value, the rejected calls -- is the existing definition; with all merge costs MARK the output is byte for byte
+ * fhevc_p_tree_select[_device]'s.  The device form is a further instantiation of k_p_tree.hip (one more dword load per lane and round), timed under slot 17;
+ * d_merge may have any alignment its type allows (4 bytes).  The host form needs no context. */
+int  fhevc_p_tree_select_merge(const fhevc_pu_shape_node* shapes /* 85 */, const fhevc_motion_merge_node* merge /* 85 */, int valid_w, int valid_h,
+                               const fhevc_p_tree_rule* rule, uint8_t* depth_min /* 256 or NULL */, uint8_t* depth_max /* 256 or NULL */,
+                               fhevc_p_tree_node* tree /* 85 or NULL */);
+int  fhevc_p_tree_select_merge_device(fhevc_ctx* ctx, const fhevc_pu_shape_node* d_shapes, const fhevc_motion_merge_node* d_merge, int num_pictures,
+                                      int ctu_row_begin, int ctu_row_end, const fhevc_p_tree_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max,
+                                      fhevc_p_tree_node* d_tree, void* stream);
+/* fhevc_p_tree_frame with the merge stage between refinement and tree: the same arguments, checks and chains, then fhevc_motion_merge_device on the refined
+ * nodes -- with max_range = search_range on the zero-centred chain (coarse_range 0), with max_range 64 on the centred chain, where absolute vectors reach
+ * +-64 and neighbouring CTUs have different centres --, the selection, and fhevc_p_tree_select_merge_device.  merge: numCtus * 85 records, or NULL. */
+int  fhevc_p_tree_merge_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                              const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min /* numCtus * 256 */,
+                              uint8_t* depth_max /* numCtus * 256 */, fhevc_pu_shape_node* shapes /* numCtus * 85 or NULL */,
+                              fhevc_motion_merge_node* merge /* numCtus * 85 or NULL */);
+
 /* CTU-row band of rank `rank` out of `world`: rows [begin, end) */
 int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
 
@@ -816,7 +901,8 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
  * small PUs, each counted), 12 = the refinements at HM's SearchRange (fhevc_motion_refine_pu_wide*: one launch for the nodes, one for the PUs,
  * each counted), 13 = the partition-size selection (fhevc_pu_shape_select_device), 15 = the coarse motion centres (fhevc_motion_centres*), the searches around them
  * (fhevc_motion_search_pu_centred*) and their refinements (fhevc_motion_refine_pu_centred*), each launch counted; 14 is not a slot and is rejected like any number above 15
- * -- except 17 = the P-picture tree decision (fhevc_p_tree_select_device), added later.  16 is not a slot either: it stays rejected, as does any number above 17 */
+ * -- except 17 = the P-picture tree decision (fhevc_p_tree_select_device, fhevc_p_tree_select_merge_device), added later.  16 is not a slot either: it stays rejected
+ * -- and 19 = the merge-candidate costs (fhevc_motion_merge*), added later still.  18 is not a slot: it stays rejected, as does any number above 19 */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
 int  fhevc_enable_kernel_timing(fhevc_ctx* ctx, int on);
 
