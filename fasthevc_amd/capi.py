@@ -533,14 +533,45 @@ class Context:
         self._check(self.lib.fhevc_intra_first_pass(self.h, flat.ctypes.data + 2 * origin, stride, qp, out.ctypes.data))
         return out.reshape(self.num_ctus, NODES_PER_CTU)
 
+    def _pair(self, cur_plane, ref_plane, origin, stride):
+        """the picture pair of a host form -> (pointer to sample (0, 0) of cur, of ref, stride in samples); each pointer keeps its (contiguous) array alive"""
+        out = []
+        for plane in (cur_plane, ref_plane):
+            flat = np.ascontiguousarray(plane).reshape(-1)
+            assert flat.dtype == np.int16
+            p = C.c_void_p(flat.ctypes.data + 2 * origin)
+            p._array = flat
+            out.append(p)
+        return out[0], out[1], stride if stride is not None else cur_plane.shape[-1]
+
+    _FAMILIES = (NODES_PER_CTU, PUS_PER_CTU, PUS_SMALL_PER_CTU)
+
+    def _search_families(self, *wanted):
+        """(nodes, pus, pus_small) flags -> (outputs of MOTION_DTYPE, None for a family not asked for; their pointers)"""
+        outs = [np.zeros(self.num_ctus * per_ctu, MOTION_DTYPE) if want else None for want, per_ctu in zip(wanted, self._FAMILIES)]
+        return outs, [None if o is None else o.ctypes.data for o in outs]
+
+    def _refine_families(self, *arrays, dtype=None):
+        """(nodes, pus, pus_small) arrays of 16-byte entries (of `dtype`, where given), None for a family left out -> (flat inputs, outputs of
+        MOTION_QPEL_DTYPE, the pointers in, out per family)"""
+        ins, outs, ptrs = [], [], []
+        for a, per_ctu in zip(arrays, self._FAMILIES):
+            if a is not None:
+                a = np.ascontiguousarray(a).reshape(-1)
+                assert (a.dtype.itemsize == 16 if dtype is None else a.dtype == dtype) and a.size == self.num_ctus * per_ctu
+            ins.append(a)
+            outs.append(None if a is None else np.zeros(a.size, MOTION_QPEL_DTYPE))
+            ptrs += [None if a is None else a.ctypes.data, None if a is None else outs[-1].ctypes.data]
+        return ins, outs, ptrs
+
+    def _per_ctu(self, outs):
+        return tuple(None if o is None else o.reshape(self.num_ctus, -1) for o in outs)
+
     def motion_search(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=4):
         """config 4: [numCtus, 85] MOTION_DTYPE nodes of cur searched in ref (two Pel planes of the same layout)."""
-        cur = np.ascontiguousarray(cur_plane).reshape(-1)
-        ref = np.ascontiguousarray(ref_plane).reshape(-1)
-        assert cur.dtype == np.int16 and ref.dtype == np.int16
-        stride = stride if stride is not None else cur_plane.shape[-1]
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
         out = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_DTYPE)
-        self._check(self.lib.fhevc_motion_search(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp,
+        self._check(self.lib.fhevc_motion_search(self.h, cur, ref, stride, qp,
                                                  search_range, out.ctypes.data))
         return out.reshape(self.num_ctus, NODES_PER_CTU)
 
@@ -554,14 +585,11 @@ class Context:
     def motion_refine(self, cur_plane, ref_plane, nodes, origin=0, stride=None, qp=32, max_range=4):
         """config 4: the quarter-sample refinement of nodes [numCtus, 85] (MOTION_DTYPE, as motion_search returns them for the same planes; only
         mvx / mvy are read) -> [numCtus, 85] MOTION_QPEL_DTYPE.  max_range: the search's range (a longer vector gets the marker)."""
-        cur = np.ascontiguousarray(cur_plane).reshape(-1)
-        ref = np.ascontiguousarray(ref_plane).reshape(-1)
-        assert cur.dtype == np.int16 and ref.dtype == np.int16
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
         nodes = np.ascontiguousarray(nodes).reshape(-1)
         assert nodes.dtype.itemsize == 16 and nodes.size == self.num_ctus * NODES_PER_CTU
-        stride = stride if stride is not None else cur_plane.shape[-1]
         out = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_QPEL_DTYPE)
-        self._check(self.lib.fhevc_motion_refine(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, max_range,
+        self._check(self.lib.fhevc_motion_refine(self.h, cur, ref, stride, qp, max_range,
                                                  nodes.ctypes.data, out.ctypes.data))
         return out.reshape(self.num_ctus, NODES_PER_CTU)
 
@@ -576,14 +604,11 @@ class Context:
     def motion_merge(self, cur_plane, ref_plane, refined, origin=0, stride=None, qp=32, max_range=4):
         """config 4: the cheapest merge candidate of every CU node from the refined nodes [numCtus, 85] (MOTION_QPEL_DTYPE, as motion_refine returns them
         for the same planes; only cost_best, mvx, mvy are read) -> [numCtus, 85] MOTION_MERGE_DTYPE.  max_range: the refinement's."""
-        cur = np.ascontiguousarray(cur_plane).reshape(-1)
-        ref = np.ascontiguousarray(ref_plane).reshape(-1)
-        assert cur.dtype == np.int16 and ref.dtype == np.int16
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
         refined = np.ascontiguousarray(refined).reshape(-1)
         assert refined.dtype.itemsize == 16 and refined.size == self.num_ctus * NODES_PER_CTU
-        stride = stride if stride is not None else cur_plane.shape[-1]
         out = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_MERGE_DTYPE)
-        self._check(self.lib.fhevc_motion_merge(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, max_range,
+        self._check(self.lib.fhevc_motion_merge(self.h, cur, ref, stride, qp, max_range,
                                                 refined.ctypes.data, out.ctypes.data))
         return out.reshape(self.num_ctus, NODES_PER_CTU)
 
@@ -597,13 +622,10 @@ class Context:
     def motion_search_pu(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=4, with_nodes=False):
         """config 4: the search of motion_search for the rectangular PUs -> [numCtus, 124] MOTION_DTYPE in the order of motion_pu_index; with_nodes:
         (nodes [numCtus, 85], pus), the nodes as motion_search returns them, from the same pass.  search_range 1..8."""
-        cur = np.ascontiguousarray(cur_plane).reshape(-1)
-        ref = np.ascontiguousarray(ref_plane).reshape(-1)
-        assert cur.dtype == np.int16 and ref.dtype == np.int16
-        stride = stride if stride is not None else cur_plane.shape[-1]
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
         pus = np.zeros(self.num_ctus * PUS_PER_CTU, MOTION_DTYPE)
         nodes = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_DTYPE) if with_nodes else None
-        self._check(self.lib.fhevc_motion_search_pu(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, search_range,
+        self._check(self.lib.fhevc_motion_search_pu(self.h, cur, ref, stride, qp, search_range,
                                                     nodes.ctypes.data if with_nodes else None, pus.ctypes.data))
         pus = pus.reshape(self.num_ctus, PUS_PER_CTU)
         return (nodes.reshape(self.num_ctus, NODES_PER_CTU), pus) if with_nodes else pus
@@ -619,12 +641,9 @@ class Context:
     def motion_search_pu_small(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=4):
         """config 4: the search of motion_search for the PUs with a 4-sample side (AMP of 16x16 CUs, 8x4 / 4x8) -> [numCtus, 384] MOTION_DTYPE in the order
         of motion_pu_small_index.  search_range 1..8."""
-        cur = np.ascontiguousarray(cur_plane).reshape(-1)
-        ref = np.ascontiguousarray(ref_plane).reshape(-1)
-        assert cur.dtype == np.int16 and ref.dtype == np.int16
-        stride = stride if stride is not None else cur_plane.shape[-1]
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
         pus = np.zeros(self.num_ctus * PUS_SMALL_PER_CTU, MOTION_DTYPE)
-        self._check(self.lib.fhevc_motion_search_pu_small(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, search_range,
+        self._check(self.lib.fhevc_motion_search_pu_small(self.h, cur, ref, stride, qp, search_range,
                                                           pus.ctypes.data))
         return pus.reshape(self.num_ctus, PUS_SMALL_PER_CTU)
 
@@ -637,16 +656,10 @@ class Context:
     def motion_search_pu_wide(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=64, nodes=True, pus=True, pus_small=True):
         """config 4: the SAD search of motion_search, motion_search_pu and motion_search_pu_small at search_range 1..64 from one call ->
         (nodes [numCtus, 85], pus [numCtus, 124], pus_small [numCtus, 384]) of MOTION_DTYPE, None for a family not asked for (at least one must be)."""
-        cur = np.ascontiguousarray(cur_plane).reshape(-1)
-        ref = np.ascontiguousarray(ref_plane).reshape(-1)
-        assert cur.dtype == np.int16 and ref.dtype == np.int16
-        stride = stride if stride is not None else cur_plane.shape[-1]
-        outs = [np.zeros(self.num_ctus * per_ctu, MOTION_DTYPE) if want else None
-                for want, per_ctu in ((nodes, NODES_PER_CTU), (pus, PUS_PER_CTU), (pus_small, PUS_SMALL_PER_CTU))]
-        ptr = lambda a: None if a is None else a.ctypes.data
-        self._check(self.lib.fhevc_motion_search_pu_wide(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, search_range,
-                                                         ptr(outs[0]), ptr(outs[1]), ptr(outs[2])))
-        return tuple(None if o is None else o.reshape(self.num_ctus, -1) for o in outs)
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
+        outs, p = self._search_families(nodes, pus, pus_small)
+        self._check(self.lib.fhevc_motion_search_pu_wide(self.h, cur, ref, stride, qp, search_range, *p))
+        return self._per_ctu(outs)
 
     def motion_search_pu_wide_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_nodes=None, d_pus=None, d_pus_small=None, rows=None,
                                      stream=None, qp=32, search_range=64):
@@ -659,12 +672,9 @@ class Context:
     def motion_centres(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, coarse_range=14):
         """config 4: one coarse motion centre per CTU from the 4:1 decimated pair (coarse_range 1..14 cells) -> [numCtus] of MOTION_DTYPE; mvx / mvy are
         multiples of 4 within +-56 whole samples.  This library's own definition (include/fasthevc.h), no HM counterpart."""
-        cur = np.ascontiguousarray(cur_plane).reshape(-1)
-        ref = np.ascontiguousarray(ref_plane).reshape(-1)
-        assert cur.dtype == np.int16 and ref.dtype == np.int16
-        stride = stride if stride is not None else cur_plane.shape[-1]
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
         out = np.zeros(self.num_ctus, MOTION_DTYPE)
-        self._check(self.lib.fhevc_motion_centres(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, coarse_range, out.ctypes.data))
+        self._check(self.lib.fhevc_motion_centres(self.h, cur, ref, stride, qp, coarse_range, out.ctypes.data))
         return out
 
     def motion_centres_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_centres, rows=None, stream=None, qp=32, coarse_range=14):
@@ -677,17 +687,12 @@ class Context:
     def motion_search_pu_centred(self, cur_plane, ref_plane, centres, origin=0, stride=None, qp=32, search_range=8, nodes=True, pus=True, pus_small=True):
         """config 4: the SAD searches of motion_search_pu_wide in a window of +-search_range (1..8) around one centre per CTU (centres: [numCtus] of
         MOTION_DTYPE, as motion_centres returns them; only mvx / mvy are read) -> (nodes, pus, pus_small) with ABSOLUTE vectors, None for a family not asked for."""
-        cur = np.ascontiguousarray(cur_plane).reshape(-1)
-        ref = np.ascontiguousarray(ref_plane).reshape(-1)
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
         cen = np.ascontiguousarray(centres).reshape(-1)
-        assert cur.dtype == np.int16 and ref.dtype == np.int16 and cen.dtype == MOTION_DTYPE and cen.size == self.num_ctus
-        stride = stride if stride is not None else cur_plane.shape[-1]
-        outs = [np.zeros(self.num_ctus * per_ctu, MOTION_DTYPE) if want else None
-                for want, per_ctu in ((nodes, NODES_PER_CTU), (pus, PUS_PER_CTU), (pus_small, PUS_SMALL_PER_CTU))]
-        ptr = lambda a: None if a is None else a.ctypes.data
-        self._check(self.lib.fhevc_motion_search_pu_centred(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, search_range,
-                                                            cen.ctypes.data, ptr(outs[0]), ptr(outs[1]), ptr(outs[2])))
-        return tuple(None if o is None else o.reshape(self.num_ctus, -1) for o in outs)
+        assert cen.dtype == MOTION_DTYPE and cen.size == self.num_ctus
+        outs, p = self._search_families(nodes, pus, pus_small)
+        self._check(self.lib.fhevc_motion_search_pu_centred(self.h, cur, ref, stride, qp, search_range, cen.ctypes.data, *p))
+        return self._per_ctu(outs)
 
     def motion_search_pu_centred_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_centres, d_nodes=None, d_pus=None, d_pus_small=None,
                                         rows=None, stream=None, qp=32, search_range=8):
@@ -701,25 +706,12 @@ class Context:
         """config 4: the quarter-sample refinement of motion_search_pu_centred's vectors, priced against the CTU's centre: nodes [numCtus, 85], pus
         [numCtus, 124], pus_small [numCtus, 384] (MOTION_DTYPE, absolute vectors; only mvx / mvy are read), centres [numCtus] -> (out_nodes, out_pus,
         out_pus_small) of MOTION_QPEL_DTYPE, None for a family not given.  max_range 1..8 around the centre."""
-        cur = np.ascontiguousarray(cur_plane).reshape(-1)
-        ref = np.ascontiguousarray(ref_plane).reshape(-1)
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
         cen = np.ascontiguousarray(centres).reshape(-1)
-        assert cur.dtype == np.int16 and ref.dtype == np.int16 and cen.dtype == MOTION_DTYPE and cen.size == self.num_ctus
-        stride = stride if stride is not None else cur_plane.shape[-1]
-        ins, outs = [], []
-        for a, per_ctu in ((nodes, NODES_PER_CTU), (pus, PUS_PER_CTU), (pus_small, PUS_SMALL_PER_CTU)):
-            if a is None:
-                ins.append(None)
-                outs.append(None)
-            else:
-                a = np.ascontiguousarray(a).reshape(-1)
-                assert a.dtype == MOTION_DTYPE and a.size == self.num_ctus * per_ctu
-                ins.append(a)
-                outs.append(np.zeros(a.size, MOTION_QPEL_DTYPE))
-        ptr = lambda a: None if a is None else a.ctypes.data
-        self._check(self.lib.fhevc_motion_refine_pu_centred(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, max_range, cen.ctypes.data,
-                                                            ptr(ins[0]), ptr(outs[0]), ptr(ins[1]), ptr(outs[1]), ptr(ins[2]), ptr(outs[2])))
-        return tuple(None if o is None else o.reshape(self.num_ctus, -1) for o in outs)
+        assert cen.dtype == MOTION_DTYPE and cen.size == self.num_ctus
+        ins, outs, p = self._refine_families(nodes, pus, pus_small, dtype=MOTION_DTYPE)
+        self._check(self.lib.fhevc_motion_refine_pu_centred(self.h, cur, ref, stride, qp, max_range, cen.ctypes.data, *p))
+        return self._per_ctu(outs)
 
     def motion_refine_pu_centred_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_centres, d_nodes=None, d_out_nodes=None, d_pus=None,
                                         d_out_pus=None, d_pus_small=None, d_out_pus_small=None, rows=None, stream=None, qp=32, max_range=8):
@@ -733,21 +725,10 @@ class Context:
         """config 4: the quarter-sample refinement of the PUs' vectors: pus [numCtus, 124] and / or pus_small [numCtus, 384] (MOTION_DTYPE, as
         motion_search_pu / motion_search_pu_small return them for the same planes; only mvx / mvy are read) -> (out_pus, out_pus_small) of
         MOTION_QPEL_DTYPE in the same layouts, None for a family not given.  max_range 1..8: the search's range (a longer vector gets the marker)."""
-        cur = np.ascontiguousarray(cur_plane).reshape(-1)
-        ref = np.ascontiguousarray(ref_plane).reshape(-1)
-        assert cur.dtype == np.int16 and ref.dtype == np.int16
-        stride = stride if stride is not None else cur_plane.shape[-1]
-        ins, outs = [], []
-        for a, per_ctu in ((pus, PUS_PER_CTU), (pus_small, PUS_SMALL_PER_CTU)):
-            if a is not None:
-                a = np.ascontiguousarray(a).reshape(-1)
-                assert a.dtype.itemsize == 16 and a.size == self.num_ctus * per_ctu
-            ins.append(a)
-            outs.append(None if a is None else np.zeros(self.num_ctus * per_ctu, MOTION_QPEL_DTYPE))
-        ptr = lambda a: None if a is None else a.ctypes.data
-        self._check(self.lib.fhevc_motion_refine_pu(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, max_range,
-                                                    ptr(ins[0]), ptr(outs[0]), ptr(ins[1]), ptr(outs[1])))
-        return tuple(None if o is None else o.reshape(self.num_ctus, -1) for o in outs)
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
+        ins, outs, p = self._refine_families(None, pus, pus_small)
+        self._check(self.lib.fhevc_motion_refine_pu(self.h, cur, ref, stride, qp, max_range, *p[2:]))
+        return self._per_ctu(outs[1:])
 
     def motion_refine_pu_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_pus, d_out_pus, d_pus_small, d_out_pus_small, rows=None,
                                 stream=None, qp=32, max_range=4):
@@ -762,21 +743,10 @@ class Context:
         """config 4: the quarter-sample refinements of motion_refine and motion_refine_pu at max_range 1..64 from one call: nodes [numCtus, 85], pus
         [numCtus, 124] and / or pus_small [numCtus, 384] (MOTION_DTYPE, as motion_search_pu_wide returns them for the same planes; only mvx / mvy are
         read) -> (out_nodes, out_pus, out_pus_small) of MOTION_QPEL_DTYPE in the same layouts, None for a family not given (at least one must be)."""
-        cur = np.ascontiguousarray(cur_plane).reshape(-1)
-        ref = np.ascontiguousarray(ref_plane).reshape(-1)
-        assert cur.dtype == np.int16 and ref.dtype == np.int16
-        stride = stride if stride is not None else cur_plane.shape[-1]
-        ins, outs = [], []
-        for a, per_ctu in ((nodes, NODES_PER_CTU), (pus, PUS_PER_CTU), (pus_small, PUS_SMALL_PER_CTU)):
-            if a is not None:
-                a = np.ascontiguousarray(a).reshape(-1)
-                assert a.dtype.itemsize == 16 and a.size == self.num_ctus * per_ctu
-            ins.append(a)
-            outs.append(None if a is None else np.zeros(self.num_ctus * per_ctu, MOTION_QPEL_DTYPE))
-        ptr = lambda a: None if a is None else a.ctypes.data
-        self._check(self.lib.fhevc_motion_refine_pu_wide(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, max_range,
-                                                         ptr(ins[0]), ptr(outs[0]), ptr(ins[1]), ptr(outs[1]), ptr(ins[2]), ptr(outs[2])))
-        return tuple(None if o is None else o.reshape(self.num_ctus, -1) for o in outs)
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
+        ins, outs, p = self._refine_families(nodes, pus, pus_small)
+        self._check(self.lib.fhevc_motion_refine_pu_wide(self.h, cur, ref, stride, qp, max_range, *p))
+        return self._per_ctu(outs)
 
     def motion_refine_pu_wide_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_nodes=None, d_out_nodes=None, d_pus=None, d_out_pus=None,
                                      d_pus_small=None, d_out_pus_small=None, rows=None, stream=None, qp=32, max_range=64):
@@ -799,14 +769,11 @@ class Context:
     def p_predict_frame(self, cur_plane, ref_plane, prev_map, origin=0, stride=None, qp=32, search_range=4, prev_mode="colocated", rule=None):
         """config 4, one picture pair from host buffers: motion search of cur in ref (as motion_search) and the depth ranges decided on the
         device against prev_map [numCtus, 256], the reference picture's depths -> (depth_min, depth_max), each [numCtus, 256]."""
-        cur = np.ascontiguousarray(cur_plane).reshape(-1)
-        ref = np.ascontiguousarray(ref_plane).reshape(-1)
-        assert cur.dtype == np.int16 and ref.dtype == np.int16
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
         prev = np.ascontiguousarray(prev_map, np.uint8).reshape(-1)
         assert prev.size == self.num_ctus * 256
-        stride = stride if stride is not None else cur_plane.shape[-1]
         dmin, dmax = np.zeros(self.num_ctus * 256, np.uint8), np.zeros(self.num_ctus * 256, np.uint8)
-        self._check(self.lib.fhevc_p_predict_frame(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, search_range,
+        self._check(self.lib.fhevc_p_predict_frame(self.h, cur, ref, stride, qp, search_range,
                                                    prev.ctypes.data, P_PREV.get(prev_mode, prev_mode), C.byref(rule) if rule is not None else None,
                                                    dmin.ctypes.data, dmax.ctypes.data))
         return dmin.reshape(self.num_ctus, 256), dmax.reshape(self.num_ctus, 256)
@@ -822,12 +789,9 @@ class Context:
     def p_shape_frame(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=64, rule=None):
         """config 4, one picture pair from host buffers: the wide SAD search of all three families, their quarter-sample refinement and the partition-size
         selection on the device -> [numCtus, 85] SHAPE_DTYPE; only the records come back."""
-        cur = np.ascontiguousarray(cur_plane).reshape(-1)
-        ref = np.ascontiguousarray(ref_plane).reshape(-1)
-        assert cur.dtype == np.int16 and ref.dtype == np.int16
-        stride = stride if stride is not None else cur_plane.shape[-1]
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
         out = np.zeros(self.num_ctus * NODES_PER_CTU, SHAPE_DTYPE)
-        self._check(self.lib.fhevc_p_shape_frame(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, search_range,
+        self._check(self.lib.fhevc_p_shape_frame(self.h, cur, ref, stride, qp, search_range,
                                                  C.byref(rule) if rule is not None else None, out.ctypes.data))
         return out.reshape(self.num_ctus, NODES_PER_CTU)
 
@@ -849,14 +813,11 @@ class Context:
                            with_shapes=False, with_merge=False):
         """p_tree_frame with the merge stage between refinement and tree -> (depth_min, depth_max) [numCtus, 256], then the records [numCtus, 85] SHAPE_DTYPE
         (with_shapes) and [numCtus, 85] MOTION_MERGE_DTYPE (with_merge)"""
-        cur = np.ascontiguousarray(cur_plane).reshape(-1)
-        ref = np.ascontiguousarray(ref_plane).reshape(-1)
-        assert cur.dtype == np.int16 and ref.dtype == np.int16
-        stride = stride if stride is not None else cur_plane.shape[-1]
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
         dmin, dmax = np.zeros(self.num_ctus * 256, np.uint8), np.zeros(self.num_ctus * 256, np.uint8)
         shapes = np.zeros(self.num_ctus * NODES_PER_CTU, SHAPE_DTYPE) if with_shapes else None
         merge = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_MERGE_DTYPE) if with_merge else None
-        self._check(self.lib.fhevc_p_tree_merge_frame(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, search_range, coarse_range,
+        self._check(self.lib.fhevc_p_tree_merge_frame(self.h, cur, ref, stride, qp, search_range, coarse_range,
                                                       C.byref(shape_rule) if shape_rule is not None else None, C.byref(tree_rule) if tree_rule is not None else None,
                                                       dmin.ctypes.data, dmax.ctypes.data, shapes.ctypes.data if with_shapes else None,
                                                       merge.ctypes.data if with_merge else None))
@@ -868,13 +829,10 @@ class Context:
         """config 4, one picture pair from host buffers: coarse_range 0: the wide SAD search of all three families, their quarter-sample refinement, the
         partition-size selection and the tree decision on the device; coarse_range 1..14: the same chain around one coarse centre per CTU (search_range
         1..8) -> (depth_min, depth_max) [numCtus, 256]; with_shapes: (depth_min, depth_max, records [numCtus, 85] SHAPE_DTYPE)"""
-        cur = np.ascontiguousarray(cur_plane).reshape(-1)
-        ref = np.ascontiguousarray(ref_plane).reshape(-1)
-        assert cur.dtype == np.int16 and ref.dtype == np.int16
-        stride = stride if stride is not None else cur_plane.shape[-1]
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
         dmin, dmax = np.zeros(self.num_ctus * 256, np.uint8), np.zeros(self.num_ctus * 256, np.uint8)
         shapes = np.zeros(self.num_ctus * NODES_PER_CTU, SHAPE_DTYPE) if with_shapes else None
-        self._check(self.lib.fhevc_p_tree_frame(self.h, cur.ctypes.data + 2 * origin, ref.ctypes.data + 2 * origin, stride, qp, search_range, coarse_range,
+        self._check(self.lib.fhevc_p_tree_frame(self.h, cur, ref, stride, qp, search_range, coarse_range,
                                                 C.byref(shape_rule) if shape_rule is not None else None, C.byref(tree_rule) if tree_rule is not None else None,
                                                 dmin.ctypes.data, dmax.ctypes.data, shapes.ctypes.data if with_shapes else None))
         out = (dmin.reshape(self.num_ctus, 256), dmax.reshape(self.num_ctus, 256))

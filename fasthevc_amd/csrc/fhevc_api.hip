@@ -1,4 +1,4 @@
-// fhevc_api.hip -- the C ABI of include/fasthevc.h: context, staging buffers, launches, multi-device sharding, the host-batch ring.
+// fhevc_api.hip -- the C ABI of include/fasthevc.h but for config 4 (fhevc_motion_api.hip): context, staging buffers, launches, multi-device sharding, the host-batch ring.
 // Host-side C++ only; all device work is in the k_*.hip files, the weight images in fhevc_weights.hip, the context-free functions in fhevc_host.hip.
 #include "fhevc_ctx.h"
 
@@ -13,21 +13,6 @@
 
 namespace {
 
-void time_begin(fhevc_ctx* c, hipStream_t s, int which)
-{
-  if (!c->timing) return;
-  TimedLaunch t;
-  if (!c->pool.empty()) { t.start = c->pool.back().first; t.stop = c->pool.back().second; c->pool.pop_back(); }
-  else { (void)hipEventCreate(&t.start); (void)hipEventCreate(&t.stop); }
-  t.which = which;
-  (void)hipEventRecord(t.start, s);
-  c->pending.push_back(t);
-}
-void time_end(fhevc_ctx* c, hipStream_t s)
-{
-  if (!c->timing) return;
-  (void)hipEventRecord(c->pending.back().stop, s);
-}
 void time_resolve(fhevc_ctx* c)
 {
   for (auto& t : c->pending) {
@@ -44,84 +29,8 @@ void time_resolve(fhevc_ctx* c)
   c->pending.clear();
 }
 
-// One launch of an entry point: on the context's device, on the caller's stream (null: the context's own), between the timing events of slot `which`, counted.
-// launch(stream) returns the launcher's hipError_t
-template <class F> int launch_on(fhevc_ctx* c, void* stream, int which, const char* what, F&& launch)
-{
-  (void)hipSetDevice(c->device);
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-  time_begin(c, s, which);
-  const hipError_t e = launch(s);
-  if (e != hipSuccess) return fail(c, FHEVC_E_HIP, what, e);
-  time_end(c, s);
-  c->stats.kernels_launched++;
-  return FHEVC_OK;
-}
-
-// a buffer of the context that is allocated by the first call that needs it
-template <class T> hipError_t ensure(T*& p, size_t bytes) { return p ? hipSuccess : hipMalloc(&p, bytes); }
-
-FhevcFrames frames_of(const fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride, long long frame_stride,
-                      int num_frames, int row_begin, int row_end, int qp = 32)
-{
-  FhevcFrames f;
-  f.luma = d_luma; f.sample_bytes = sample_bytes; f.stride = stride; f.frame_stride = frame_stride;
-  f.width = c->cfg.width; f.height = c->cfg.height; f.bit_depth = c->cfg.bit_depth;
-  f.ctus_x = c->ctus_x; f.ctus_y = c->ctus_y; f.num_frames = num_frames; f.row_begin = row_begin; f.row_end = row_end;
-  f.qp = qp < 0 ? 0 : (qp > 51 ? 51 : qp);
-  return f;
-}
 // the one picture in the context's staging plane (the host-buffer entry points)
 FhevcFrames staged_frame(const fhevc_ctx* c) { return frames_of(c, c->d_luma, 2, c->dev_stride, 0, 1, 0, c->ctus_y); }
-
-// What the entry points over a device-resident batch check of its layout, each condition in one spelling; null: nothing wrong.  min_frames: 2 where a picture
-// is searched in the one before it.  qp: 0..51 (an entry point that clamps it, or has none, passes 0).  overlap: the frames of a batch must not overlap (asked
-// by the entry points whose launch covers the whole batch at once and by the motion entry points)
-const char* batch_error(const fhevc_ctx* c, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames, int min_frames,
-                        int ctu_row_begin, int ctu_row_end, int qp, bool overlap)
-{
-  if ((sample_bytes != 1 && sample_bytes != 2) || stride_samples < c->cfg.width || num_frames < min_frames) return "bad frame layout";
-  if (ctu_row_begin < 0 || ctu_row_end > c->ctus_y || ctu_row_begin > ctu_row_end) return "bad CTU-row band";
-  if (qp < 0 || qp > 51) return "qp out of range (0..51)";
-  if (sample_bytes == 1 && c->cfg.bit_depth != 8) return "uint8 samples need bit_depth 8";
-  if (overlap && num_frames > 1 && frame_stride_samples < (long long)stride_samples * (c->cfg.height - 1) + c->cfg.width) return "frames overlap";
-  return nullptr;
-}
-
-// lambda = 0.57 * 2^((qp-12)/3): TEncSlice::calculateLambda, all-intra path (TEncSlice.cpp:433-527).  The first-pass cost is compared bit-for-bit with the
-// oracle's doubles: this expression stays as it is
-double sqrt_lambda_intra(int qp) { return std::sqrt(0.57 * std::pow(2.0, ((double)qp - 12.0) / 3.0)); }
-
-// the vector costs, with HM's own arithmetic (TComRdCost.h:166-174, TComRdCost.cpp:109-114, 177-190): getCost(bits) of the exp-Golomb lengths of both components
-double motion_lambda(int qp) { return 65536.0 * sqrt_lambda_intra(qp); }
-uint32_t mv_bits_cost(double motion_lambda, unsigned bits) { return (uint32_t)((motion_lambda * bits) / 65536.0); }
-unsigned exp_golomb_bits(int v)
-{
-  unsigned len = 1, u = (v <= 0) ? (((unsigned)(-v)) << 1) + 1 : ((unsigned)v) << 1;
-  while (u != 1) { u >>= 1; len += 2; }
-  return len;
-}
-// ... of the window of +-range whole samples in raster order, (2 range + 1)^2 entries
-void mv_window_costs(int qp, int range, uint32_t* out)
-{
-  const double ml = motion_lambda(qp);
-  const int side = 2 * range + 1;
-  for (int m = 0; m < side * side; ++m) out[m] = mv_bits_cost(ml, exp_golomb_bits(((m % side) - range) << 2) + exp_golomb_bits(((m / side) - range) << 2));
-}
-FhevcMvCost mv_cost_table(int qp, int range)
-{
-  FhevcMvCost t;
-  mv_window_costs(qp, range, t.c);
-  return t;
-}
-// ... of every number of bits a quarter-sample vector can take (k_motion_refine.hip)
-FhevcMvBitCost mv_bit_cost_table(int qp)
-{
-  FhevcMvBitCost t;
-  const double ml = motion_lambda(qp);
-  for (int b = 0; b < FHEVC_MV_BIT_COSTS; ++b) t.c[b] = mv_bits_cost(ml, (unsigned)b);
-  return t;
-}
 
 // upload rows [y0, y1) of one host picture (Pel plane with stride) into the context's staging plane, between the events that time the upload
 int upload_rows(fhevc_ctx* c, const int16_t* luma, int stride_samples, int y0, int y1)
@@ -134,22 +43,6 @@ int upload_rows(fhevc_ctx* c, const int16_t* luma, int stride_samples, int y0, i
   return FHEVC_OK;
 }
 int upload_frame(fhevc_ctx* c, const int16_t* luma, int stride_samples) { return upload_rows(c, luma, stride_samples, 0, c->cfg.height); }
-
-// the reference and the current picture of the host-buffer motion entry points, into the context's two staging planes (a batch of two frames for the
-// *_device entry points: frame stride = pair_plane); the search's nodes live beside them
-size_t pair_plane(const fhevc_ctx* c) { return (size_t)c->dev_stride * c->ctus_y * 64; }
-size_t motion_bytes(const fhevc_ctx* c) { return (size_t)c->num_ctus * FHEVC_NODES * sizeof(FhevcMotionNode); }
-int upload_pair(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples)
-{
-  HIP_TRY(c, ensure(c->d_pair, 2 * pair_plane(c) * sizeof(int16_t)));
-  HIP_TRY(c, ensure(c->d_motion, motion_bytes(c)));
-  const int16_t* src[2] = { ref_luma, cur_luma };
-  for (int i = 0; i < 2; ++i)
-    HIP_TRY(c, hipMemcpy2DAsync(c->d_pair + i * pair_plane(c), (size_t)c->dev_stride * 2, src[i], (size_t)stride_samples * 2, (size_t)c->cfg.width * 2,
-                                (size_t)c->cfg.height, hipMemcpyHostToDevice, c->stream));
-  c->stats.bytes_h2d += (uint64_t)c->cfg.width * c->cfg.height * 4;
-  return FHEVC_OK;
-}
 
 // The parity entry points that bring back the cost of every (unit, mode) pair: a table allocated per call, one picture up, launch(frame, sqrt_lambda, table),
 // the table (and, where asked, the 85-node best costs) back, the table freed
@@ -780,798 +673,6 @@ int fhevc_preanalyze(fhevc_ctx* c, const int16_t* luma, int stride_samples, int 
   }
   c->stats.bytes_d2h += (uint64_t)total * sizeof(double);
   return FHEVC_OK;
-}
-
-// ---- source-only motion search per CU node (k_motion.hip, k_motion_wide.hip) ----
-
-int fhevc_motion_search_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
-                               int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range, fhevc_motion_node* d_out, void* stream)
-{
-  if (!c || !d_luma || !d_out) return FHEVC_E_INVALID;
-  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
-  if (search_range < 1 || search_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad motion-search arguments");
-  const bool wide = search_range > FHEVC_MOTION_MAX_RANGE;
-  if (wide && !c->motion_sad) return fail(c, FHEVC_E_INVALID, "search ranges above 8 need the SAD distortion (fhevc_set_motion_distortion)");
-  if (wide && c->cfg.bit_depth > 8 && sample_bytes != 2) return fail(c, FHEVC_E_INVALID, "bad motion-search arguments");
-  const bool big = wide && c->cfg.bit_depth > 8;   // above 8 bit: the generic kernel laid out for the wide window (round 4); 8 bit: the byte-SAD kernel
-  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;
-  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
-  static_assert(sizeof(fhevc_motion_node) == sizeof(FhevcMotionNode), "motion node layout");
-  if (wide && (c->mvtab_qp != qp || c->mvtab_range != search_range)) {
-    // the wide kernels read the window's vector costs from HBM
-    (void)hipSetDevice(c->device);
-    HIP_TRY(c, ensure(c->d_mvtab, sizeof(uint32_t) * (2 * FHEVC_MOTION_WIDE_MAX_RANGE + 1) * (2 * FHEVC_MOTION_WIDE_MAX_RANGE + 1)));
-    // EVERY launch that reads the old table has to be through, on whatever streams the callers passed (an event behind the latest launch would
-    // cover that one stream only).  A rebuild happens only when (qp, range) changes: off the hot path
-    HIP_TRY(c, hipDeviceSynchronize());
-    c->mvtab_host.resize((size_t)(2 * search_range + 1) * (2 * search_range + 1));
-    mv_window_costs(qp, search_range, c->mvtab_host.data());
-    HIP_TRY(c, hipMemcpy(c->d_mvtab, c->mvtab_host.data(), c->mvtab_host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    c->mvtab_qp = qp; c->mvtab_range = search_range;
-  }
-  FhevcMotionNode* out = reinterpret_cast<FhevcMotionNode*>(d_out);
-  return launch_on(c, stream, 4, "motion search", [&](hipStream_t s) {
-    if (big) return fhevc_launch_motion_big(fr, search_range, c->d_mvtab, out, c->num_cus, s);
-    if (wide) return fhevc_launch_motion_wide(fr, search_range, c->d_mvtab, out, c->num_cus, s);
-    return fhevc_launch_motion(fr, search_range, mv_cost_table(qp, search_range), out, c->num_cus, c->motion_sad, s);
-  });
-}
-
-int fhevc_motion_search(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
-                        fhevc_motion_node* out)
-{
-  if (!c || !cur_luma || !ref_luma || !out || stride_samples < c->cfg.width) return FHEVC_E_INVALID;
-  (void)hipSetDevice(c->device);
-  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
-  if (rc != FHEVC_OK) return rc;
-  rc = fhevc_motion_search_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, search_range,
-                                  reinterpret_cast<fhevc_motion_node*>(c->d_motion), c->stream);
-  if (rc != FHEVC_OK) return rc;
-  HIP_TRY(c, hipMemcpyAsync(out, c->d_motion, motion_bytes(c), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->stats.bytes_d2h += (uint64_t)motion_bytes(c);
-  return FHEVC_OK;
-}
-
-// ---- the search of the rectangular PUs (k_motion_pu.hip) ----
-
-int fhevc_motion_search_pu_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
-                                  int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range,
-                                  fhevc_motion_node* d_nodes, fhevc_motion_node* d_pus, void* stream)
-{
-  if (!c || !d_luma || !d_pus) return c ? fail(c, FHEVC_E_INVALID, "bad PU motion-search arguments") : FHEVC_E_INVALID;
-  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
-  if (search_range < 1 || search_range > FHEVC_MOTION_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "the PU motion search covers search ranges 1..8");
-  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
-  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
-  static_assert(FHEVC_PUS_PER_CTU == FHEVC_PUS, "PU count");
-  return launch_on(c, stream, 8, "fhevc_launch_motion_pu", [&](hipStream_t s) {
-    return fhevc_launch_motion_pu(fr, search_range, mv_cost_table(qp, search_range), reinterpret_cast<FhevcMotionNode*>(d_nodes), reinterpret_cast<FhevcMotionNode*>(d_pus),
-                                  c->num_cus, c->motion_sad, s);
-  });
-}
-
-int fhevc_motion_search_pu(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
-                           fhevc_motion_node* nodes, fhevc_motion_node* pus)
-{
-  if (!c || !cur_luma || !ref_luma || !pus || stride_samples < c->cfg.width)
-    return c ? fail(c, FHEVC_E_INVALID, "bad PU motion-search arguments") : FHEVC_E_INVALID;
-  if (qp < 0 || qp > 51 || search_range < 1 || search_range > FHEVC_MOTION_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad PU motion-search arguments");
-  (void)hipSetDevice(c->device);
-  const size_t pu_bytes = (size_t)c->num_ctus * FHEVC_PUS * sizeof(FhevcMotionNode);
-  HIP_TRY(c, ensure(c->d_motion_pu, pu_bytes));
-  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
-  if (rc != FHEVC_OK) return rc;
-  rc = fhevc_motion_search_pu_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, search_range,
-                                     nodes ? reinterpret_cast<fhevc_motion_node*>(c->d_motion) : nullptr, reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu), c->stream);
-  if (rc != FHEVC_OK) return rc;
-  if (nodes) HIP_TRY(c, hipMemcpyAsync(nodes, c->d_motion, motion_bytes(c), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(pus, c->d_motion_pu, pu_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->stats.bytes_d2h += (uint64_t)pu_bytes + (nodes ? (uint64_t)motion_bytes(c) : 0);
-  return FHEVC_OK;
-}
-
-// ---- the search of the PUs with a 4-sample side (k_motion_pu_small.hip) ----
-
-int fhevc_motion_search_pu_small_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
-                                        int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range,
-                                        fhevc_motion_node* d_pus, void* stream)
-{
-  if (!c || !d_luma || !d_pus) return c ? fail(c, FHEVC_E_INVALID, "bad small-PU motion-search arguments") : FHEVC_E_INVALID;
-  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
-  if (search_range < 1 || search_range > FHEVC_MOTION_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "the small-PU motion search covers search ranges 1..8");
-  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
-  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
-  static_assert(FHEVC_PUS_SMALL_PER_CTU == FHEVC_PUS_SMALL, "small-PU count");
-  return launch_on(c, stream, 9, "fhevc_launch_motion_pu_small", [&](hipStream_t s) {
-    return fhevc_launch_motion_pu_small(fr, search_range, mv_cost_table(qp, search_range), reinterpret_cast<FhevcMotionNode*>(d_pus), c->num_cus, c->motion_sad, s);
-  });
-}
-
-int fhevc_motion_search_pu_small(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
-                                 fhevc_motion_node* pus)
-{
-  if (!c || !cur_luma || !ref_luma || !pus || stride_samples < c->cfg.width)
-    return c ? fail(c, FHEVC_E_INVALID, "bad small-PU motion-search arguments") : FHEVC_E_INVALID;
-  if (qp < 0 || qp > 51 || search_range < 1 || search_range > FHEVC_MOTION_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad small-PU motion-search arguments");
-  (void)hipSetDevice(c->device);
-  const size_t pu_bytes = (size_t)c->num_ctus * FHEVC_PUS_SMALL * sizeof(FhevcMotionNode);
-  HIP_TRY(c, ensure(c->d_motion_pu_small, pu_bytes));
-  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
-  if (rc != FHEVC_OK) return rc;
-  rc = fhevc_motion_search_pu_small_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, search_range,
-                                           reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu_small), c->stream);
-  if (rc != FHEVC_OK) return rc;
-  HIP_TRY(c, hipMemcpyAsync(pus, c->d_motion_pu_small, pu_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->stats.bytes_d2h += (uint64_t)pu_bytes;
-  return FHEVC_OK;
-}
-
-// ---- the three searches at HM's own SearchRange, SAD (the MR = 64 layouts of k_motion_pu.hip and k_motion_pu_small.hip) ----
-
-int fhevc_motion_search_pu_wide_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
-                                       int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range,
-                                       fhevc_motion_node* d_nodes, fhevc_motion_node* d_pus, fhevc_motion_node* d_pus_small, void* stream)
-{
-  if (!c || !d_luma || (!d_nodes && !d_pus && !d_pus_small)) return c ? fail(c, FHEVC_E_INVALID, "bad wide PU motion-search arguments") : FHEVC_E_INVALID;
-  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
-  if (search_range < 1 || search_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "the wide PU motion search covers search ranges 1..64");
-  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
-  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
-  FhevcMotionNode* nodes = reinterpret_cast<FhevcMotionNode*>(d_nodes);
-  FhevcMotionNode* pus = reinterpret_cast<FhevcMotionNode*>(d_pus);
-  FhevcMotionNode* small = reinterpret_cast<FhevcMotionNode*>(d_pus_small);
-  // Always SAD, and every vector cost travels with its launch: the window's table up to +-8 (the MR = 8 layouts, several workgroups per CU), the 40 bit
-  // costs above.  Nothing of the context is read or written by the launches: calls on different streams may be in flight together.  Above +-8: 8-bit
-  // contexts take the byte-SAD kernel (k_motion_pu_wide.hip: one launch for whatever is asked for), contexts above 8 bit -- and 8-bit int16 planes under
-  // FHEVC_PU_WIDE=generic -- the MR = 64 layouts of the generic kernels (one launch for nodes and PUs, one for the small PUs).  Timed under slot 11
-  const bool big = search_range > FHEVC_MOTION_MAX_RANGE;
-  if (big && c->cfg.bit_depth == 8 && !(c->knobs.pu_wide_generic && sample_bytes == 2))
-    return launch_on(c, stream, 11, "fhevc_launch_motion_pu_wide", [&](hipStream_t s) {
-      return fhevc_launch_motion_pu_wide(fr, search_range, mv_bit_cost_table(qp), nodes, pus, small, c->num_cus, s);
-    });
-  if (nodes || pus) {
-    const int rc = launch_on(c, stream, 11, "fhevc_motion_search_pu_wide (nodes, PUs)", [&](hipStream_t s) {
-      if (big) return fhevc_launch_motion_pu_big(fr, search_range, mv_bit_cost_table(qp), nodes, pus, c->num_cus, s);
-      if (!pus) return fhevc_launch_motion(fr, search_range, mv_cost_table(qp, search_range), nodes, c->num_cus, true, s);
-      return fhevc_launch_motion_pu(fr, search_range, mv_cost_table(qp, search_range), nodes, pus, c->num_cus, true, s);
-    });
-    if (rc != FHEVC_OK) return rc;
-  }
-  if (!small) return FHEVC_OK;
-  return launch_on(c, stream, 11, "fhevc_motion_search_pu_wide (small PUs)", [&](hipStream_t s) {
-    if (big) return fhevc_launch_motion_pu_small_big(fr, search_range, mv_bit_cost_table(qp), small, c->num_cus, s);
-    return fhevc_launch_motion_pu_small(fr, search_range, mv_cost_table(qp, search_range), small, c->num_cus, true, s);
-  });
-}
-
-int fhevc_motion_search_pu_wide(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
-                                fhevc_motion_node* nodes, fhevc_motion_node* pus, fhevc_motion_node* pus_small)
-{
-  if (!c || !cur_luma || !ref_luma || (!nodes && !pus && !pus_small) || stride_samples < c->cfg.width)
-    return c ? fail(c, FHEVC_E_INVALID, "bad wide PU motion-search arguments") : FHEVC_E_INVALID;
-  if (qp < 0 || qp > 51 || search_range < 1 || search_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad wide PU motion-search arguments");
-  (void)hipSetDevice(c->device);
-  const size_t pu_bytes = (size_t)c->num_ctus * FHEVC_PUS * sizeof(FhevcMotionNode), small_bytes = (size_t)c->num_ctus * FHEVC_PUS_SMALL * sizeof(FhevcMotionNode);
-  if (pus) HIP_TRY(c, ensure(c->d_motion_pu, pu_bytes));
-  if (pus_small) HIP_TRY(c, ensure(c->d_motion_pu_small, small_bytes));
-  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
-  if (rc != FHEVC_OK) return rc;
-  rc = fhevc_motion_search_pu_wide_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, search_range,
-                                          nodes ? reinterpret_cast<fhevc_motion_node*>(c->d_motion) : nullptr, pus ? reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu) : nullptr,
-                                          pus_small ? reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu_small) : nullptr, c->stream);
-  if (rc != FHEVC_OK) return rc;
-  if (nodes) HIP_TRY(c, hipMemcpyAsync(nodes, c->d_motion, motion_bytes(c), hipMemcpyDeviceToHost, c->stream));
-  if (pus) HIP_TRY(c, hipMemcpyAsync(pus, c->d_motion_pu, pu_bytes, hipMemcpyDeviceToHost, c->stream));
-  if (pus_small) HIP_TRY(c, hipMemcpyAsync(pus_small, c->d_motion_pu_small, small_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->stats.bytes_d2h += (nodes ? (uint64_t)motion_bytes(c) : 0) + (pus ? (uint64_t)pu_bytes : 0) + (pus_small ? (uint64_t)small_bytes : 0);
-  return FHEVC_OK;
-}
-
-// ---- one coarse motion centre per CTU from the 4:1 decimated picture pair (k_motion_coarse.hip) ----
-
-int fhevc_motion_centres_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
-                                int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int coarse_range, fhevc_motion_node* d_centres, void* stream)
-{
-  if (!c || !d_luma || !d_centres) return c ? fail(c, FHEVC_E_INVALID, "bad motion-centre arguments") : FHEVC_E_INVALID;
-  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
-  if (coarse_range < 1 || coarse_range > FHEVC_MOTION_COARSE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "the motion centres cover coarse ranges 1..14");
-  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
-  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
-  // the bit costs travel with the launch: nothing of the context is read or written by it.  Timed under slot 15
-  return launch_on(c, stream, 15, "fhevc_launch_motion_coarse", [&](hipStream_t s) {
-    return fhevc_launch_motion_coarse(fr, coarse_range, mv_bit_cost_table(qp), reinterpret_cast<FhevcMotionNode*>(d_centres), c->num_cus, s);
-  });
-}
-
-int fhevc_motion_centres(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int coarse_range, fhevc_motion_node* centres)
-{
-  if (!c || !cur_luma || !ref_luma || !centres || stride_samples < c->cfg.width)
-    return c ? fail(c, FHEVC_E_INVALID, "bad motion-centre arguments") : FHEVC_E_INVALID;
-  if (qp < 0 || qp > 51 || coarse_range < 1 || coarse_range > FHEVC_MOTION_COARSE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad motion-centre arguments");
-  (void)hipSetDevice(c->device);
-  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
-  if (rc != FHEVC_OK) return rc;
-  // one entry per CTU, through the head of the nodes' staging buffer (85 entries per CTU)
-  rc = fhevc_motion_centres_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, coarse_range,
-                                   reinterpret_cast<fhevc_motion_node*>(c->d_motion), c->stream);
-  if (rc != FHEVC_OK) return rc;
-  const size_t bytes = (size_t)c->num_ctus * sizeof(FhevcMotionNode);
-  HIP_TRY(c, hipMemcpyAsync(centres, c->d_motion, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->stats.bytes_d2h += (uint64_t)bytes;
-  return FHEVC_OK;
-}
-
-// ---- the three integer searches around one centre per CTU (the MR = 8 layouts of k_motion_pu.hip and k_motion_pu_small.hip, centred) ----
-
-int fhevc_motion_search_pu_centred_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
-                                          int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range, const fhevc_motion_node* d_centres,
-                                          fhevc_motion_node* d_nodes, fhevc_motion_node* d_pus, fhevc_motion_node* d_pus_small, void* stream)
-{
-  if (!c || !d_luma || !d_centres || (!d_nodes && !d_pus && !d_pus_small)) return c ? fail(c, FHEVC_E_INVALID, "bad centred PU motion-search arguments") : FHEVC_E_INVALID;
-  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
-  if (search_range < 1 || search_range > FHEVC_MOTION_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "the centred PU motion search covers search ranges 1..8");
-  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
-  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
-  const FhevcMotionNode* centres = reinterpret_cast<const FhevcMotionNode*>(d_centres);
-  FhevcMotionNode* nodes = reinterpret_cast<FhevcMotionNode*>(d_nodes);
-  FhevcMotionNode* pus = reinterpret_cast<FhevcMotionNode*>(d_pus);
-  FhevcMotionNode* small = reinterpret_cast<FhevcMotionNode*>(d_pus_small);
-  // Always SAD.  The window's table of vector costs travels with the launch and prices d = v - P, the vector relative to the centre: exactly
-  // getCostOfVectorWithPredictor with the predictor 4 P.  Whether a centre is in range is the kernel's to decide (the host cannot see device centres).  Nothing of the
-  // context is read or written by the launches.  One launch for nodes and PUs, one for the small PUs, each timed and counted under slot 15
-  if (nodes || pus) {
-    const int rc = launch_on(c, stream, 15, "fhevc_motion_search_pu_centred (nodes, PUs)", [&](hipStream_t s) {
-      return fhevc_launch_motion_pu_centred(fr, search_range, mv_cost_table(qp, search_range), centres, nodes, pus, c->num_cus, s);
-    });
-    if (rc != FHEVC_OK) return rc;
-  }
-  if (!small) return FHEVC_OK;
-  return launch_on(c, stream, 15, "fhevc_motion_search_pu_centred (small PUs)", [&](hipStream_t s) {
-    return fhevc_launch_motion_pu_small_centred(fr, search_range, mv_cost_table(qp, search_range), centres, small, c->num_cus, s);
-  });
-}
-
-int fhevc_motion_search_pu_centred(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
-                                   const fhevc_motion_node* centres, fhevc_motion_node* nodes, fhevc_motion_node* pus, fhevc_motion_node* pus_small)
-{
-  if (!c || !cur_luma || !ref_luma || !centres || (!nodes && !pus && !pus_small) || stride_samples < c->cfg.width)
-    return c ? fail(c, FHEVC_E_INVALID, "bad centred PU motion-search arguments") : FHEVC_E_INVALID;
-  if (qp < 0 || qp > 51 || search_range < 1 || search_range > FHEVC_MOTION_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad centred PU motion-search arguments");
-  (void)hipSetDevice(c->device);
-  const size_t pu_bytes = (size_t)c->num_ctus * FHEVC_PUS * sizeof(FhevcMotionNode), small_bytes = (size_t)c->num_ctus * FHEVC_PUS_SMALL * sizeof(FhevcMotionNode);
-  const size_t centre_bytes = (size_t)c->num_ctus * sizeof(FhevcMotionNode);
-  if (pus) HIP_TRY(c, ensure(c->d_motion_pu, pu_bytes));
-  if (pus_small) HIP_TRY(c, ensure(c->d_motion_pu_small, small_bytes));
-  HIP_TRY(c, ensure(c->d_centres, centre_bytes));
-  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
-  if (rc != FHEVC_OK) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->d_centres, centres, centre_bytes, hipMemcpyHostToDevice, c->stream));
-  c->stats.bytes_h2d += (uint64_t)centre_bytes;
-  rc = fhevc_motion_search_pu_centred_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, search_range,
-                                             reinterpret_cast<const fhevc_motion_node*>(c->d_centres), nodes ? reinterpret_cast<fhevc_motion_node*>(c->d_motion) : nullptr,
-                                             pus ? reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu) : nullptr,
-                                             pus_small ? reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu_small) : nullptr, c->stream);
-  if (rc != FHEVC_OK) return rc;
-  if (nodes) HIP_TRY(c, hipMemcpyAsync(nodes, c->d_motion, motion_bytes(c), hipMemcpyDeviceToHost, c->stream));
-  if (pus) HIP_TRY(c, hipMemcpyAsync(pus, c->d_motion_pu, pu_bytes, hipMemcpyDeviceToHost, c->stream));
-  if (pus_small) HIP_TRY(c, hipMemcpyAsync(pus_small, c->d_motion_pu_small, small_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->stats.bytes_d2h += (nodes ? (uint64_t)motion_bytes(c) : 0) + (pus ? (uint64_t)pu_bytes : 0) + (pus_small ? (uint64_t)small_bytes : 0);
-  return FHEVC_OK;
-}
-
-// ---- quarter-sample refinement of the search's vectors (k_motion_refine.hip) ----
-
-int fhevc_motion_refine_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
-                               int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_node* d_nodes,
-                               fhevc_motion_qpel_node* d_out, void* stream)
-{
-  if (!c || !d_luma || !d_nodes || !d_out) return c ? fail(c, FHEVC_E_INVALID, "bad motion-refinement arguments") : FHEVC_E_INVALID;
-  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
-  if (max_range < 1 || max_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad motion-refinement arguments");
-  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
-  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
-  static_assert(sizeof(fhevc_motion_qpel_node) == sizeof(FhevcMotionQpelNode) && sizeof(FhevcMotionQpelNode) == 16, "quarter-sample node layout");
-  return launch_on(c, stream, 7, "fhevc_launch_motion_refine", [&](hipStream_t s) {
-    return fhevc_launch_motion_refine(fr, max_range, mv_bit_cost_table(qp), reinterpret_cast<const FhevcMotionNode*>(d_nodes), reinterpret_cast<FhevcMotionQpelNode*>(d_out), c->num_cus, s);
-  });
-}
-
-int fhevc_motion_refine(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
-                        const fhevc_motion_node* nodes, fhevc_motion_qpel_node* out)
-{
-  if (!c || !cur_luma || !ref_luma || !nodes || !out || stride_samples < c->cfg.width)
-    return c ? fail(c, FHEVC_E_INVALID, "bad motion-refinement arguments") : FHEVC_E_INVALID;
-  if (qp < 0 || qp > 51 || max_range < 1 || max_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad motion-refinement arguments");
-  (void)hipSetDevice(c->device);
-  const size_t nbytes = motion_bytes(c);   // a quarter-sample node is as large as a node of the search
-  HIP_TRY(c, ensure(c->d_qpel, nbytes));
-  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
-  if (rc != FHEVC_OK) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->d_motion, nodes, nbytes, hipMemcpyHostToDevice, c->stream));
-  c->stats.bytes_h2d += nbytes;
-  rc = fhevc_motion_refine_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, max_range,
-                                  reinterpret_cast<const fhevc_motion_node*>(c->d_motion), reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel), c->stream);
-  if (rc != FHEVC_OK) return rc;
-  HIP_TRY(c, hipMemcpyAsync(out, c->d_qpel, nbytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->stats.bytes_d2h += (uint64_t)nbytes;
-  return FHEVC_OK;
-}
-
-// ---- merge-candidate costs per CU node from the refined nodes (k_motion_merge.hip) ----
-
-int fhevc_motion_merge_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
-                              int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_qpel_node* d_refined,
-                              fhevc_motion_merge_node* d_out, void* stream)
-{
-  if (!c || !d_luma || !d_refined || !d_out) return c ? fail(c, FHEVC_E_INVALID, "bad merge-stage arguments") : FHEVC_E_INVALID;
-  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
-  if (max_range < 1 || max_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad merge-stage arguments (max_range 1..64)");
-  if ((long long)(num_frames - 1) * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "more than 2^31 - 1 CTUs");
-  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
-  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
-  static_assert(sizeof(fhevc_motion_merge_node) == sizeof(FhevcMotionMergeNode) && sizeof(FhevcMotionMergeNode) == 16, "merge node layout");
-  return launch_on(c, stream, 19, "fhevc_launch_motion_merge", [&](hipStream_t s) {
-    return fhevc_launch_motion_merge(fr, max_range, mv_bit_cost_table(qp), reinterpret_cast<const FhevcMotionQpelNode*>(d_refined), reinterpret_cast<FhevcMotionMergeNode*>(d_out),
-                                     c->num_cus, s);
-  });
-}
-
-int fhevc_motion_merge(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
-                       const fhevc_motion_qpel_node* refined, fhevc_motion_merge_node* out)
-{
-  if (!c || !cur_luma || !ref_luma || !refined || !out || stride_samples < c->cfg.width)
-    return c ? fail(c, FHEVC_E_INVALID, "bad merge-stage arguments") : FHEVC_E_INVALID;
-  if (qp < 0 || qp > 51 || max_range < 1 || max_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad merge-stage arguments");
-  (void)hipSetDevice(c->device);
-  const size_t nbytes = motion_bytes(c);   // a merge record is as large as a node of the search: the refined nodes go through d_qpel, the records through d_motion
-  HIP_TRY(c, ensure(c->d_qpel, nbytes));
-  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
-  if (rc != FHEVC_OK) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->d_qpel, refined, nbytes, hipMemcpyHostToDevice, c->stream));
-  c->stats.bytes_h2d += nbytes;
-  rc = fhevc_motion_merge_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, max_range,
-                                 reinterpret_cast<const fhevc_motion_qpel_node*>(c->d_qpel), reinterpret_cast<fhevc_motion_merge_node*>(c->d_motion), c->stream);
-  if (rc != FHEVC_OK) { (void)hipStreamSynchronize(c->stream); return rc; }   // the uploads read the caller's buffers: through before the call returns
-  HIP_TRY(c, hipMemcpyAsync(out, c->d_motion, nbytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->stats.bytes_d2h += (uint64_t)nbytes;
-  return FHEVC_OK;
-}
-
-// ---- quarter-sample refinement of the PUs' vectors (k_motion_refine_pu.hip) ----
-
-int fhevc_motion_refine_pu_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
-                                  int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range,
-                                  const fhevc_motion_node* d_pus, fhevc_motion_qpel_node* d_out_pus,
-                                  const fhevc_motion_node* d_pus_small, fhevc_motion_qpel_node* d_out_pus_small, void* stream)
-{
-  if (!c) return FHEVC_E_INVALID;
-  // either family's pair may be null together, not both pairs and not half a pair
-  if (!d_luma || (!d_pus && !d_pus_small) || !d_pus != !d_out_pus || !d_pus_small != !d_out_pus_small) return fail(c, FHEVC_E_INVALID, "bad PU motion-refinement arguments");
-  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
-  if (max_range < 1 || max_range > FHEVC_MOTION_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "the PU motion refinement covers vectors of the search ranges 1..8");
-  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
-  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
-  return launch_on(c, stream, 10, "fhevc_launch_motion_refine_pu", [&](hipStream_t s) {
-    return fhevc_launch_motion_refine_pu(fr, max_range, mv_bit_cost_table(qp), reinterpret_cast<const FhevcMotionNode*>(d_pus), reinterpret_cast<FhevcMotionQpelNode*>(d_out_pus),
-                                         reinterpret_cast<const FhevcMotionNode*>(d_pus_small), reinterpret_cast<FhevcMotionQpelNode*>(d_out_pus_small), c->num_cus, false, s);
-  });
-}
-
-int fhevc_motion_refine_pu(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
-                           const fhevc_motion_node* pus, fhevc_motion_qpel_node* out_pus, const fhevc_motion_node* pus_small, fhevc_motion_qpel_node* out_pus_small)
-{
-  if (!c) return FHEVC_E_INVALID;
-  if (!cur_luma || !ref_luma || (!pus && !pus_small) || !pus != !out_pus || !pus_small != !out_pus_small || stride_samples < c->cfg.width)
-    return fail(c, FHEVC_E_INVALID, "bad PU motion-refinement arguments");
-  if (qp < 0 || qp > 51 || max_range < 1 || max_range > FHEVC_MOTION_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad PU motion-refinement arguments");
-  (void)hipSetDevice(c->device);
-  // a quarter-sample entry is as large as an entry of the search
-  const size_t pu_bytes = pus ? (size_t)c->num_ctus * FHEVC_PUS * sizeof(FhevcMotionNode) : 0;
-  const size_t small_bytes = pus_small ? (size_t)c->num_ctus * FHEVC_PUS_SMALL * sizeof(FhevcMotionNode) : 0;
-  if (pus) { HIP_TRY(c, ensure(c->d_motion_pu, pu_bytes)); HIP_TRY(c, ensure(c->d_qpel_pu, pu_bytes)); }
-  if (pus_small) { HIP_TRY(c, ensure(c->d_motion_pu_small, small_bytes)); HIP_TRY(c, ensure(c->d_qpel_pu_small, small_bytes)); }
-  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
-  if (rc != FHEVC_OK) return rc;
-  if (pus) HIP_TRY(c, hipMemcpyAsync(c->d_motion_pu, pus, pu_bytes, hipMemcpyHostToDevice, c->stream));
-  if (pus_small) HIP_TRY(c, hipMemcpyAsync(c->d_motion_pu_small, pus_small, small_bytes, hipMemcpyHostToDevice, c->stream));
-  c->stats.bytes_h2d += pu_bytes + small_bytes;
-  rc = fhevc_motion_refine_pu_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, max_range,
-                                     pus ? reinterpret_cast<const fhevc_motion_node*>(c->d_motion_pu) : nullptr, pus ? reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu) : nullptr,
-                                     pus_small ? reinterpret_cast<const fhevc_motion_node*>(c->d_motion_pu_small) : nullptr,
-                                     pus_small ? reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu_small) : nullptr, c->stream);
-  if (rc != FHEVC_OK) return rc;
-  if (pus) HIP_TRY(c, hipMemcpyAsync(out_pus, c->d_qpel_pu, pu_bytes, hipMemcpyDeviceToHost, c->stream));
-  if (pus_small) HIP_TRY(c, hipMemcpyAsync(out_pus_small, c->d_qpel_pu_small, small_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->stats.bytes_d2h += (uint64_t)(pu_bytes + small_bytes);
-  return FHEVC_OK;
-}
-
-// ---- the two refinements at HM's own SearchRange: what fhevc_motion_search_pu_wide writes feeds straight in (k_motion_refine.hip, k_motion_refine_pu.hip) ----
-
-int fhevc_motion_refine_pu_wide_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
-                                       int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range,
-                                       const fhevc_motion_node* d_nodes, fhevc_motion_qpel_node* d_out_nodes,
-                                       const fhevc_motion_node* d_pus, fhevc_motion_qpel_node* d_out_pus,
-                                       const fhevc_motion_node* d_pus_small, fhevc_motion_qpel_node* d_out_pus_small, void* stream)
-{
-  if (!c) return FHEVC_E_INVALID;
-  // each family's pair may be null together, not all three pairs and not half a pair
-  if (!d_luma || (!d_nodes && !d_pus && !d_pus_small) || !d_nodes != !d_out_nodes || !d_pus != !d_out_pus || !d_pus_small != !d_out_pus_small)
-    return fail(c, FHEVC_E_INVALID, "bad wide PU motion-refinement arguments");
-  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
-  if (max_range < 1 || max_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "the wide PU motion refinement covers vectors of the search ranges 1..64");
-  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
-  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
-  // Nothing of the context is read or written by the launches (the 40 bit costs travel by value): calls on different streams may be in flight together.
-  // The nodes: the square kernel, the launch of fhevc_motion_refine_device; the PUs: one launch for both families, the MR = 8 layout up to +-8 (the launch
-  // of fhevc_motion_refine_pu_device), the MR = 64 layout above.  Each launch is timed and counted under slot 12
-  if (d_nodes) {
-    const int rc = launch_on(c, stream, 12, "fhevc_motion_refine_pu_wide (nodes)", [&](hipStream_t s) {
-      return fhevc_launch_motion_refine(fr, max_range, mv_bit_cost_table(qp), reinterpret_cast<const FhevcMotionNode*>(d_nodes), reinterpret_cast<FhevcMotionQpelNode*>(d_out_nodes),
-                                        c->num_cus, s);
-    });
-    if (rc != FHEVC_OK) return rc;
-  }
-  if (!d_pus && !d_pus_small) return FHEVC_OK;
-  return launch_on(c, stream, 12, "fhevc_motion_refine_pu_wide (PUs)", [&](hipStream_t s) {
-    return fhevc_launch_motion_refine_pu(fr, max_range, mv_bit_cost_table(qp), reinterpret_cast<const FhevcMotionNode*>(d_pus), reinterpret_cast<FhevcMotionQpelNode*>(d_out_pus),
-                                         reinterpret_cast<const FhevcMotionNode*>(d_pus_small), reinterpret_cast<FhevcMotionQpelNode*>(d_out_pus_small), c->num_cus,
-                                         c->knobs.refine_pu_stage_full, s);
-  });
-}
-
-int fhevc_motion_refine_pu_wide(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
-                                const fhevc_motion_node* nodes, fhevc_motion_qpel_node* out_nodes,
-                                const fhevc_motion_node* pus, fhevc_motion_qpel_node* out_pus,
-                                const fhevc_motion_node* pus_small, fhevc_motion_qpel_node* out_pus_small)
-{
-  if (!c) return FHEVC_E_INVALID;
-  if (!cur_luma || !ref_luma || (!nodes && !pus && !pus_small) || !nodes != !out_nodes || !pus != !out_pus || !pus_small != !out_pus_small || stride_samples < c->cfg.width)
-    return fail(c, FHEVC_E_INVALID, "bad wide PU motion-refinement arguments");
-  if (qp < 0 || qp > 51 || max_range < 1 || max_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad wide PU motion-refinement arguments");
-  (void)hipSetDevice(c->device);
-  // a quarter-sample entry is as large as an entry of the search; the nodes go in through d_motion (upload_pair allocates it) and come out of d_qpel
-  const size_t node_bytes = nodes ? motion_bytes(c) : 0;
-  const size_t pu_bytes = pus ? (size_t)c->num_ctus * FHEVC_PUS * sizeof(FhevcMotionNode) : 0;
-  const size_t small_bytes = pus_small ? (size_t)c->num_ctus * FHEVC_PUS_SMALL * sizeof(FhevcMotionNode) : 0;
-  if (nodes) HIP_TRY(c, ensure(c->d_qpel, node_bytes));
-  if (pus) { HIP_TRY(c, ensure(c->d_motion_pu, pu_bytes)); HIP_TRY(c, ensure(c->d_qpel_pu, pu_bytes)); }
-  if (pus_small) { HIP_TRY(c, ensure(c->d_motion_pu_small, small_bytes)); HIP_TRY(c, ensure(c->d_qpel_pu_small, small_bytes)); }
-  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
-  if (rc != FHEVC_OK) return rc;
-  if (nodes) HIP_TRY(c, hipMemcpyAsync(c->d_motion, nodes, node_bytes, hipMemcpyHostToDevice, c->stream));
-  if (pus) HIP_TRY(c, hipMemcpyAsync(c->d_motion_pu, pus, pu_bytes, hipMemcpyHostToDevice, c->stream));
-  if (pus_small) HIP_TRY(c, hipMemcpyAsync(c->d_motion_pu_small, pus_small, small_bytes, hipMemcpyHostToDevice, c->stream));
-  c->stats.bytes_h2d += node_bytes + pu_bytes + small_bytes;
-  rc = fhevc_motion_refine_pu_wide_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, max_range,
-                                          nodes ? reinterpret_cast<const fhevc_motion_node*>(c->d_motion) : nullptr, nodes ? reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel) : nullptr,
-                                          pus ? reinterpret_cast<const fhevc_motion_node*>(c->d_motion_pu) : nullptr, pus ? reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu) : nullptr,
-                                          pus_small ? reinterpret_cast<const fhevc_motion_node*>(c->d_motion_pu_small) : nullptr,
-                                          pus_small ? reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu_small) : nullptr, c->stream);
-  if (rc != FHEVC_OK) return rc;
-  if (nodes) HIP_TRY(c, hipMemcpyAsync(out_nodes, c->d_qpel, node_bytes, hipMemcpyDeviceToHost, c->stream));
-  if (pus) HIP_TRY(c, hipMemcpyAsync(out_pus, c->d_qpel_pu, pu_bytes, hipMemcpyDeviceToHost, c->stream));
-  if (pus_small) HIP_TRY(c, hipMemcpyAsync(out_pus_small, c->d_qpel_pu_small, small_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->stats.bytes_d2h += (uint64_t)(node_bytes + pu_bytes + small_bytes);
-  return FHEVC_OK;
-}
-
-// ---- the two refinements around one centre per CTU: what fhevc_motion_search_pu_centred writes feeds straight in (k_motion_refine.hip, k_motion_refine_pu.hip, centred) ----
-
-int fhevc_motion_refine_pu_centred_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
-                                          int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_node* d_centres,
-                                          const fhevc_motion_node* d_nodes, fhevc_motion_qpel_node* d_out_nodes,
-                                          const fhevc_motion_node* d_pus, fhevc_motion_qpel_node* d_out_pus,
-                                          const fhevc_motion_node* d_pus_small, fhevc_motion_qpel_node* d_out_pus_small, void* stream)
-{
-  if (!c || !d_luma || !d_centres || (!d_nodes && !d_pus && !d_pus_small) || !d_nodes != !d_out_nodes || !d_pus != !d_out_pus || !d_pus_small != !d_out_pus_small)
-    return c ? fail(c, FHEVC_E_INVALID, "bad centred PU motion-refinement arguments") : FHEVC_E_INVALID;
-  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 2, ctu_row_begin, ctu_row_end, qp, true)) return fail(c, FHEVC_E_INVALID, bad);
-  if (max_range < 1 || max_range > FHEVC_MOTION_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "the centred PU motion refinement covers max_range 1..8");
-  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
-  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
-  const FhevcMotionNode* centres = reinterpret_cast<const FhevcMotionNode*>(d_centres);
-  // the MR = 8 layouts with the window staged around each CTU's centre; one launch for the nodes, one for both PU families, each timed and counted under slot 15
-  if (d_nodes) {
-    const int rc = launch_on(c, stream, 15, "fhevc_motion_refine_pu_centred (nodes)", [&](hipStream_t s) {
-      return fhevc_launch_motion_refine_centred(fr, max_range, mv_bit_cost_table(qp), centres, reinterpret_cast<const FhevcMotionNode*>(d_nodes),
-                                                reinterpret_cast<FhevcMotionQpelNode*>(d_out_nodes), c->num_cus, s);
-    });
-    if (rc != FHEVC_OK) return rc;
-  }
-  if (!d_pus && !d_pus_small) return FHEVC_OK;
-  return launch_on(c, stream, 15, "fhevc_motion_refine_pu_centred (PUs)", [&](hipStream_t s) {
-    return fhevc_launch_motion_refine_pu_centred(fr, max_range, mv_bit_cost_table(qp), centres, reinterpret_cast<const FhevcMotionNode*>(d_pus), reinterpret_cast<FhevcMotionQpelNode*>(d_out_pus),
-                                                 reinterpret_cast<const FhevcMotionNode*>(d_pus_small), reinterpret_cast<FhevcMotionQpelNode*>(d_out_pus_small), c->num_cus, s);
-  });
-}
-
-int fhevc_motion_refine_pu_centred(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
-                                   const fhevc_motion_node* centres, const fhevc_motion_node* nodes, fhevc_motion_qpel_node* out_nodes,
-                                   const fhevc_motion_node* pus, fhevc_motion_qpel_node* out_pus,
-                                   const fhevc_motion_node* pus_small, fhevc_motion_qpel_node* out_pus_small)
-{
-  if (!c || !cur_luma || !ref_luma || !centres || stride_samples < c->cfg.width || (!nodes && !pus && !pus_small) || !nodes != !out_nodes || !pus != !out_pus ||
-      !pus_small != !out_pus_small)
-    return c ? fail(c, FHEVC_E_INVALID, "bad centred PU motion-refinement arguments") : FHEVC_E_INVALID;
-  if (qp < 0 || qp > 51 || max_range < 1 || max_range > FHEVC_MOTION_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad centred PU motion-refinement arguments");
-  (void)hipSetDevice(c->device);
-  const size_t pu_bytes = (size_t)c->num_ctus * FHEVC_PUS * sizeof(FhevcMotionNode), small_bytes = (size_t)c->num_ctus * FHEVC_PUS_SMALL * sizeof(FhevcMotionNode);
-  const size_t centre_bytes = (size_t)c->num_ctus * sizeof(FhevcMotionNode);
-  if (nodes) HIP_TRY(c, ensure(c->d_qpel, motion_bytes(c)));
-  if (pus) { HIP_TRY(c, ensure(c->d_motion_pu, pu_bytes)); HIP_TRY(c, ensure(c->d_qpel_pu, pu_bytes)); }
-  if (pus_small) { HIP_TRY(c, ensure(c->d_motion_pu_small, small_bytes)); HIP_TRY(c, ensure(c->d_qpel_pu_small, small_bytes)); }
-  HIP_TRY(c, ensure(c->d_centres, centre_bytes));
-  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
-  if (rc != FHEVC_OK) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->d_centres, centres, centre_bytes, hipMemcpyHostToDevice, c->stream));
-  if (nodes) HIP_TRY(c, hipMemcpyAsync(c->d_motion, nodes, motion_bytes(c), hipMemcpyHostToDevice, c->stream));
-  if (pus) HIP_TRY(c, hipMemcpyAsync(c->d_motion_pu, pus, pu_bytes, hipMemcpyHostToDevice, c->stream));
-  if (pus_small) HIP_TRY(c, hipMemcpyAsync(c->d_motion_pu_small, pus_small, small_bytes, hipMemcpyHostToDevice, c->stream));
-  c->stats.bytes_h2d += (uint64_t)centre_bytes + (nodes ? (uint64_t)motion_bytes(c) : 0) + (pus ? (uint64_t)pu_bytes : 0) + (pus_small ? (uint64_t)small_bytes : 0);
-  rc = fhevc_motion_refine_pu_centred_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, max_range,
-                                             reinterpret_cast<const fhevc_motion_node*>(c->d_centres),
-                                             nodes ? reinterpret_cast<const fhevc_motion_node*>(c->d_motion) : nullptr, nodes ? reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel) : nullptr,
-                                             pus ? reinterpret_cast<const fhevc_motion_node*>(c->d_motion_pu) : nullptr, pus ? reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu) : nullptr,
-                                             pus_small ? reinterpret_cast<const fhevc_motion_node*>(c->d_motion_pu_small) : nullptr,
-                                             pus_small ? reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu_small) : nullptr, c->stream);
-  if (rc != FHEVC_OK) return rc;
-  if (nodes) HIP_TRY(c, hipMemcpyAsync(out_nodes, c->d_qpel, motion_bytes(c), hipMemcpyDeviceToHost, c->stream));
-  if (pus) HIP_TRY(c, hipMemcpyAsync(out_pus, c->d_qpel_pu, pu_bytes, hipMemcpyDeviceToHost, c->stream));
-  if (pus_small) HIP_TRY(c, hipMemcpyAsync(out_pus_small, c->d_qpel_pu_small, small_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->stats.bytes_d2h += (nodes ? (uint64_t)motion_bytes(c) : 0) + (pus ? (uint64_t)pu_bytes : 0) + (pus_small ? (uint64_t)small_bytes : 0);
-  return FHEVC_OK;
-}
-
-// measurement tools only (tools/motion_refine_pu_wide_bench.py; not in fasthevc.h): what hipOccupancyMaxActiveBlocksPerMultiprocessor answers for the MR = 64
-// instance of k_motion_refine_pu.hip that planes of sample_bytes take on this context, and the cap of its persistent grid
-int fhevc_debug_refine_pu_wide_residency(fhevc_ctx* c, int sample_bytes, int* blocks_per_cu, int* grid_cap)
-{
-  if (!c || !blocks_per_cu || !grid_cap || (sample_bytes != 1 && sample_bytes != 2)) return FHEVC_E_INVALID;
-  (void)hipSetDevice(c->device);
-  HIP_TRY(c, fhevc_motion_refine_pu_big_residency(sample_bytes, c->cfg.bit_depth, blocks_per_cu));
-  *grid_cap = (*blocks_per_cu < 2 ? *blocks_per_cu : 2) * c->num_cus;
-  return FHEVC_OK;
-}
-
-// ---- P-picture depth ranges over a device-resident batch (k_p_rule.hip; the host form of the rule: fhevc_host.hip) ----
-int fhevc_p_depth_range_device(fhevc_ctx* c, const fhevc_motion_node* d_nodes, const uint8_t* d_prev_maps, int num_pictures, int ctu_row_begin,
-                               int ctu_row_end, int qp, int prev_mode, const fhevc_p_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, void* stream)
-{
-  if (!c || !d_nodes || !d_prev_maps || !d_depth_min) return FHEVC_E_INVALID;
-  // (nodes and maps have no sample layout: the checks of the pictures' number, the band and the qp)
-  if (const char* bad = batch_error(c, 2, c->cfg.width, 0, num_pictures, 1, ctu_row_begin, ctu_row_end, qp, false)) return fail(c, FHEVC_E_INVALID, bad);
-  if (prev_mode != FHEVC_P_PREV_COLOCATED && prev_mode != FHEVC_P_PREV_UNIT && prev_mode != FHEVC_P_PREV_NODE)
-    return fail(c, FHEVC_E_INVALID, "prev_mode: FHEVC_P_PREV_COLOCATED, FHEVC_P_PREV_UNIT or FHEVC_P_PREV_NODE");
-  if ((long long)num_pictures * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "bad P-rule arguments");
-  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;
-  static_assert(sizeof(fhevc_p_rule) == sizeof(FhevcPRule), "P rule layout");
-  FhevcPRule r;   // read here, handed to the kernel by value: the caller's struct is free again when this call returns
-  if (rule) std::memcpy(&r, rule, sizeof r);
-  else { fhevc_p_rule d; fhevc_p_rule_default(&d); std::memcpy(&r, &d, sizeof r); }
-  const FhevcFrames fr = frames_of(c, nullptr, 1, c->cfg.width, 0, num_pictures, ctu_row_begin, ctu_row_end, qp);
-  return launch_on(c, stream, 5, "fhevc_launch_p_rule", [&](hipStream_t s) {
-    return fhevc_launch_p_rule(fr, prev_mode, r, reinterpret_cast<const FhevcMotionNode*>(d_nodes), d_prev_maps, d_depth_min, d_depth_max, c->num_cus, s);
-  });
-}
-
-int fhevc_p_predict_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
-                          const uint8_t* prev_map, int prev_mode, const fhevc_p_rule* rule, uint8_t* depth_min, uint8_t* depth_max)
-{
-  if (!c || !cur_luma || !ref_luma || !prev_map || !depth_min || !depth_max || stride_samples < c->cfg.width) return FHEVC_E_INVALID;
-  if (prev_mode != FHEVC_P_PREV_COLOCATED && prev_mode != FHEVC_P_PREV_UNIT && prev_mode != FHEVC_P_PREV_NODE)
-    return fail(c, FHEVC_E_INVALID, "prev_mode: FHEVC_P_PREV_COLOCATED, FHEVC_P_PREV_UNIT or FHEVC_P_PREV_NODE");
-  (void)hipSetDevice(c->device);
-  const size_t maps = (size_t)c->num_ctus * 256;
-  HIP_TRY(c, ensure(c->d_p_maps, 3 * maps));
-  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
-  if (rc != FHEVC_OK) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->d_p_maps, prev_map, maps, hipMemcpyHostToDevice, c->stream));
-  c->stats.bytes_h2d += maps;
-  rc = fhevc_motion_search_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, search_range,
-                                  reinterpret_cast<fhevc_motion_node*>(c->d_motion), c->stream);
-  if (rc == FHEVC_OK)
-    rc = fhevc_p_depth_range_device(c, reinterpret_cast<const fhevc_motion_node*>(c->d_motion), c->d_p_maps, 1, 0, c->ctus_y, qp, prev_mode, rule,
-                                    c->d_p_maps + maps, c->d_p_maps + 2 * maps, c->stream);
-  if (rc != FHEVC_OK) { (void)hipStreamSynchronize(c->stream); return rc; }   // the uploads read the caller's buffers: through before the call returns
-  HIP_TRY(c, hipMemcpyAsync(depth_min, c->d_p_maps + maps, maps, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(depth_max, c->d_p_maps + 2 * maps, maps, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->stats.bytes_d2h += 2 * maps;
-  return FHEVC_OK;
-}
-
-// ---- partition sizes per CU from the refined PU costs over a device-resident batch (k_pu_shape.hip; the host form: fhevc_host.hip) ----
-int fhevc_pu_shape_select_device(fhevc_ctx* c, const fhevc_motion_qpel_node* d_nodes, const fhevc_motion_qpel_node* d_pus, const fhevc_motion_qpel_node* d_pus_small,
-                                 int num_pictures, int ctu_row_begin, int ctu_row_end, const fhevc_pu_shape_rule* rule, fhevc_pu_shape_node* d_shapes,
-                                 uint32_t* d_costs, void* stream)
-{
-  if (!c) return FHEVC_E_INVALID;
-  if (!d_nodes || !d_pus || !d_shapes) return fail(c, FHEVC_E_INVALID, "bad partition-size selection arguments");
-  // (refined entries have no sample layout: the checks of the pictures' number and the band)
-  if (const char* bad = batch_error(c, 2, c->cfg.width, 0, num_pictures, 1, ctu_row_begin, ctu_row_end, 0, false)) return fail(c, FHEVC_E_INVALID, bad);
-  static_assert(sizeof(fhevc_pu_shape_rule) == sizeof(FhevcPuShapeRule) && sizeof(fhevc_pu_shape_node) == sizeof(FhevcPuShapeNode), "partition-size layouts");
-  FhevcPuShapeRule r;   // read here, handed to the kernel by value: the caller's struct is free again when this call returns
-  if (rule) std::memcpy(&r, rule, sizeof r);
-  else { fhevc_pu_shape_rule d; fhevc_pu_shape_rule_default(&d); std::memcpy(&r, &d, sizeof r); }
-  if (const char* bad = fhevc_pu_shape_rule_error(r)) return fail(c, FHEVC_E_INVALID, bad);
-  if ((long long)num_pictures * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "more than 2^31 - 1 CTUs");
-  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
-  const FhevcFrames fr = frames_of(c, nullptr, 1, c->cfg.width, 0, num_pictures, ctu_row_begin, ctu_row_end);
-  return launch_on(c, stream, 13, "fhevc_launch_pu_shape", [&](hipStream_t s) {
-    return fhevc_launch_pu_shape(fr, r, reinterpret_cast<const FhevcMotionQpelNode*>(d_nodes), reinterpret_cast<const FhevcMotionQpelNode*>(d_pus),
-                                 reinterpret_cast<const FhevcMotionQpelNode*>(d_pus_small), reinterpret_cast<FhevcPuShapeNode*>(d_shapes), d_costs, c->num_cus, s);
-  });
-}
-
-int fhevc_p_shape_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
-                        const fhevc_pu_shape_rule* rule, fhevc_pu_shape_node* shapes)
-{
-  if (!c) return FHEVC_E_INVALID;
-  if (!cur_luma || !ref_luma || !shapes || stride_samples < c->cfg.width) return fail(c, FHEVC_E_INVALID, "bad partition-size frame arguments");
-  if (qp < 0 || qp > 51 || search_range < 1 || search_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad partition-size frame arguments");
-  if (rule)
-    if (const char* bad = fhevc_pu_shape_rule_error(*rule)) return fail(c, FHEVC_E_INVALID, bad);
-  (void)hipSetDevice(c->device);
-  // the buffers of the host forms of the wide search and its refinement; the records go where the integer nodes were once the refinement has read them
-  const size_t node_bytes = motion_bytes(c), pu_bytes = (size_t)c->num_ctus * FHEVC_PUS * sizeof(FhevcMotionNode),
-               small_bytes = (size_t)c->num_ctus * FHEVC_PUS_SMALL * sizeof(FhevcMotionNode);
-  HIP_TRY(c, ensure(c->d_qpel, node_bytes));
-  HIP_TRY(c, ensure(c->d_motion_pu, pu_bytes));
-  HIP_TRY(c, ensure(c->d_qpel_pu, pu_bytes));
-  HIP_TRY(c, ensure(c->d_motion_pu_small, small_bytes));
-  HIP_TRY(c, ensure(c->d_qpel_pu_small, small_bytes));
-  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
-  if (rc != FHEVC_OK) return rc;
-  fhevc_motion_node* nodes = reinterpret_cast<fhevc_motion_node*>(c->d_motion);
-  fhevc_motion_node* pus = reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu);
-  fhevc_motion_node* small = reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu_small);
-  fhevc_motion_qpel_node* q_nodes = reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel);
-  fhevc_motion_qpel_node* q_pus = reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu);
-  fhevc_motion_qpel_node* q_small = reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu_small);
-  rc = fhevc_motion_search_pu_wide_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, search_range, nodes, pus, small, c->stream);
-  if (rc == FHEVC_OK)
-    rc = fhevc_motion_refine_pu_wide_device(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, search_range, nodes, q_nodes, pus, q_pus,
-                                            small, q_small, c->stream);
-  if (rc == FHEVC_OK)
-    rc = fhevc_pu_shape_select_device(c, q_nodes, q_pus, q_small, 1, 0, c->ctus_y, rule, reinterpret_cast<fhevc_pu_shape_node*>(c->d_motion), nullptr, c->stream);
-  if (rc != FHEVC_OK) { (void)hipStreamSynchronize(c->stream); return rc; }   // the uploads read the caller's buffers: through before the call returns
-  HIP_TRY(c, hipMemcpyAsync(shapes, c->d_motion, node_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->stats.bytes_d2h += (uint64_t)node_bytes;
-  return FHEVC_OK;
-}
-
-// ---- P-picture depth ranges from the selection's records over a device-resident batch (k_p_tree.hip; the host form: fhevc_host.hip) ----
-// d_merge: null for fhevc_p_tree_select_device; with_merge says which of the two entry points is asking
-static int p_tree_select_on(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, const fhevc_motion_merge_node* d_merge, bool with_merge, int num_pictures, int ctu_row_begin,
-                            int ctu_row_end, const fhevc_p_tree_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream)
-{
-  if (!c) return FHEVC_E_INVALID;
-  if (!d_shapes || (with_merge && !d_merge) || (!d_depth_min && !d_depth_max && !d_tree)) return fail(c, FHEVC_E_INVALID, "bad tree-decision arguments");
-  // (records have no sample layout: the checks of the pictures' number and the band)
-  if (const char* bad = batch_error(c, 2, c->cfg.width, 0, num_pictures, 1, ctu_row_begin, ctu_row_end, 0, false)) return fail(c, FHEVC_E_INVALID, bad);
-  static_assert(sizeof(fhevc_p_tree_rule) == sizeof(FhevcPTreeRule) && sizeof(fhevc_p_tree_node) == sizeof(FhevcPTreeNode), "tree-decision layouts");
-  FhevcPTreeRule r;   // read here, handed to the kernel by value: the caller's struct is free again when this call returns
-  if (rule) std::memcpy(&r, rule, sizeof r);
-  else std::memset(&r, 0, sizeof r);   // fhevc_p_tree_rule_default
-  if (const char* bad = fhevc_p_tree_rule_error(r)) return fail(c, FHEVC_E_INVALID, bad);
-  if ((long long)num_pictures * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "more than 2^31 - 1 CTUs");
-  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
-  const FhevcFrames fr = frames_of(c, nullptr, 1, c->cfg.width, 0, num_pictures, ctu_row_begin, ctu_row_end);
-  if (with_merge)
-    return launch_on(c, stream, 17, "fhevc_launch_p_tree_merge", [&](hipStream_t s) {
-      return fhevc_launch_p_tree_merge(fr, r, reinterpret_cast<const FhevcPuShapeNode*>(d_shapes), reinterpret_cast<const FhevcMotionMergeNode*>(d_merge), d_depth_min, d_depth_max,
-                                       reinterpret_cast<FhevcPTreeNode*>(d_tree), c->num_cus, s);
-    });
-  return launch_on(c, stream, 17, "fhevc_launch_p_tree", [&](hipStream_t s) {
-    return fhevc_launch_p_tree(fr, r, reinterpret_cast<const FhevcPuShapeNode*>(d_shapes), d_depth_min, d_depth_max, reinterpret_cast<FhevcPTreeNode*>(d_tree), c->num_cus, s);
-  });
-}
-
-int fhevc_p_tree_select_device(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, int num_pictures, int ctu_row_begin, int ctu_row_end, const fhevc_p_tree_rule* rule,
-                               uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream)
-{
-  return p_tree_select_on(c, d_shapes, nullptr, false, num_pictures, ctu_row_begin, ctu_row_end, rule, d_depth_min, d_depth_max, d_tree, stream);
-}
-
-int fhevc_p_tree_select_merge_device(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, const fhevc_motion_merge_node* d_merge, int num_pictures, int ctu_row_begin,
-                                     int ctu_row_end, const fhevc_p_tree_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream)
-{
-  return p_tree_select_on(c, d_shapes, d_merge, true, num_pictures, ctu_row_begin, ctu_row_end, rule, d_depth_min, d_depth_max, d_tree, stream);
-}
-
-// with_merge: fhevc_p_tree_merge_frame -- the merge stage between refinement and tree; its records go where the integer PUs were once the refinement has read them
-static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
-                           const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes,
-                           bool with_merge, fhevc_motion_merge_node* merge)
-{
-  if (!c) return FHEVC_E_INVALID;
-  if (!cur_luma || !ref_luma || !depth_min || !depth_max || stride_samples < c->cfg.width) return fail(c, FHEVC_E_INVALID, "bad tree-decision frame arguments");
-  if (qp < 0 || qp > 51 || coarse_range < 0 || coarse_range > FHEVC_MOTION_COARSE_MAX_RANGE || search_range < 1 ||
-      search_range > (coarse_range ? FHEVC_MOTION_MAX_RANGE : FHEVC_MOTION_WIDE_MAX_RANGE))
-    return fail(c, FHEVC_E_INVALID, "bad tree-decision frame arguments (around a centre the search covers ranges 1..8, coarse ranges 1..14)");
-  if (shape_rule)
-    if (const char* bad = fhevc_pu_shape_rule_error(*shape_rule)) return fail(c, FHEVC_E_INVALID, bad);
-  if (tree_rule)
-    if (const char* bad = fhevc_p_tree_rule_error(*tree_rule)) return fail(c, FHEVC_E_INVALID, bad);
-  (void)hipSetDevice(c->device);
-  // the buffers of the host forms of the searches and their refinements; the records go where the integer nodes were once the refinement has read them (as in
-  // fhevc_p_shape_frame), the maps where fhevc_p_predict_frame keeps its own
-  const size_t node_bytes = motion_bytes(c), pu_bytes = (size_t)c->num_ctus * FHEVC_PUS * sizeof(FhevcMotionNode),
-               small_bytes = (size_t)c->num_ctus * FHEVC_PUS_SMALL * sizeof(FhevcMotionNode), maps = (size_t)c->num_ctus * 256;
-  HIP_TRY(c, ensure(c->d_qpel, node_bytes));
-  HIP_TRY(c, ensure(c->d_motion_pu, pu_bytes));
-  HIP_TRY(c, ensure(c->d_qpel_pu, pu_bytes));
-  HIP_TRY(c, ensure(c->d_motion_pu_small, small_bytes));
-  HIP_TRY(c, ensure(c->d_qpel_pu_small, small_bytes));
-  HIP_TRY(c, ensure(c->d_p_maps, 3 * maps));
-  if (coarse_range) HIP_TRY(c, ensure(c->d_centres, (size_t)c->num_ctus * sizeof(FhevcMotionNode)));
-  int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
-  if (rc != FHEVC_OK) return rc;
-  fhevc_motion_node* nodes = reinterpret_cast<fhevc_motion_node*>(c->d_motion);
-  fhevc_motion_node* pus = reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu);
-  fhevc_motion_node* small = reinterpret_cast<fhevc_motion_node*>(c->d_motion_pu_small);
-  fhevc_motion_node* centres = reinterpret_cast<fhevc_motion_node*>(c->d_centres);
-  fhevc_motion_qpel_node* q_nodes = reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel);
-  fhevc_motion_qpel_node* q_pus = reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu);
-  fhevc_motion_qpel_node* q_small = reinterpret_cast<fhevc_motion_qpel_node*>(c->d_qpel_pu_small);
-  fhevc_pu_shape_node* d_shapes = reinterpret_cast<fhevc_pu_shape_node*>(c->d_motion);
-  fhevc_motion_merge_node* d_merge = reinterpret_cast<fhevc_motion_merge_node*>(c->d_motion_pu);   // 85 of the 124 entries per CTU
-  const long long plane = (long long)pair_plane(c);
-  if (coarse_range) {
-    rc = fhevc_motion_centres_device(c, c->d_pair, 2, c->dev_stride, plane, 2, 0, c->ctus_y, qp, coarse_range, centres, c->stream);
-    if (rc == FHEVC_OK)
-      rc = fhevc_motion_search_pu_centred_device(c, c->d_pair, 2, c->dev_stride, plane, 2, 0, c->ctus_y, qp, search_range, centres, nodes, pus, small, c->stream);
-    if (rc == FHEVC_OK)
-      rc = fhevc_motion_refine_pu_centred_device(c, c->d_pair, 2, c->dev_stride, plane, 2, 0, c->ctus_y, qp, search_range, centres, nodes, q_nodes, pus, q_pus, small,
-                                                 q_small, c->stream);
-  } else {
-    rc = fhevc_motion_search_pu_wide_device(c, c->d_pair, 2, c->dev_stride, plane, 2, 0, c->ctus_y, qp, search_range, nodes, pus, small, c->stream);
-    if (rc == FHEVC_OK)
-      rc = fhevc_motion_refine_pu_wide_device(c, c->d_pair, 2, c->dev_stride, plane, 2, 0, c->ctus_y, qp, search_range, nodes, q_nodes, pus, q_pus, small, q_small,
-                                              c->stream);
-  }
-  // absolute vectors of the centred chain reach +-64 and neighbouring CTUs have different centres: the merge stage looks around zero at the full range there
-  if (rc == FHEVC_OK && with_merge)
-    rc = fhevc_motion_merge_device(c, c->d_pair, 2, c->dev_stride, plane, 2, 0, c->ctus_y, qp, coarse_range ? FHEVC_MOTION_WIDE_MAX_RANGE : search_range, q_nodes, d_merge,
-                                   c->stream);
-  if (rc == FHEVC_OK) rc = fhevc_pu_shape_select_device(c, q_nodes, q_pus, q_small, 1, 0, c->ctus_y, shape_rule, d_shapes, nullptr, c->stream);
-  if (rc == FHEVC_OK && with_merge)
-    rc = fhevc_p_tree_select_merge_device(c, d_shapes, d_merge, 1, 0, c->ctus_y, tree_rule, c->d_p_maps + maps, c->d_p_maps + 2 * maps, nullptr, c->stream);
-  else if (rc == FHEVC_OK) rc = fhevc_p_tree_select_device(c, d_shapes, 1, 0, c->ctus_y, tree_rule, c->d_p_maps + maps, c->d_p_maps + 2 * maps, nullptr, c->stream);
-  if (rc != FHEVC_OK) { (void)hipStreamSynchronize(c->stream); return rc; }   // the uploads read the caller's buffers: through before the call returns
-  HIP_TRY(c, hipMemcpyAsync(depth_min, c->d_p_maps + maps, maps, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(depth_max, c->d_p_maps + 2 * maps, maps, hipMemcpyDeviceToHost, c->stream));
-  if (shapes) HIP_TRY(c, hipMemcpyAsync(shapes, c->d_motion, node_bytes, hipMemcpyDeviceToHost, c->stream));
-  if (with_merge && merge) HIP_TRY(c, hipMemcpyAsync(merge, c->d_motion_pu, node_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->stats.bytes_d2h += (uint64_t)(2 * maps + (shapes ? node_bytes : 0) + (with_merge && merge ? node_bytes : 0));
-  return FHEVC_OK;
-}
-
-int fhevc_p_tree_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
-                       const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes)
-{
-  return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, false, nullptr);
-}
-
-int fhevc_p_tree_merge_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
-                             const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes,
-                             fhevc_motion_merge_node* merge)
-{
-  return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge);
 }
 
 // Diagnostic (not part of include/fasthevc.h): run the stamped instantiation of the depth kernel over a

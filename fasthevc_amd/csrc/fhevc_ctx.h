@@ -1,9 +1,10 @@
-// fhevc_ctx.h -- private to the C-ABI layer (fhevc_api.hip, fhevc_weights.hip): the context behind the opaque fhevc_ctx of include/fasthevc.h,
-// its error helpers, and the few functions that cross those two files.
+// fhevc_ctx.h -- private to the C-ABI layer (fhevc_api.hip, fhevc_motion_api.hip, fhevc_weights.hip): the context behind the opaque fhevc_ctx of
+// include/fasthevc.h, its error helpers, and the few functions that cross those files.
 #pragma once
 #include "../../include/fasthevc.h"
 #include "fhevc_internal.h"
 
+#include <cmath>
 #include <string>
 #include <utility>
 #include <vector>
@@ -49,18 +50,14 @@ struct fhevc_ctx {
   bool timing = false;
   std::vector<TimedLaunch> pending;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-  double sum_ms[20] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };     // slots 14, 16 and 18 are not in use (fhevc_kernel_timing rejects them)
+  // per timing slot (14, 16 and 18 are not in use); config 4's slots and its staging buffers d_pair .. d_p_maps: the tables in fhevc_motion_api.hip
+  double sum_ms[20] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
   uint64_t launches[20] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
   double* d_act = nullptr;
-  int16_t* d_pair = nullptr;          // two staging planes (reference, current) of fhevc_motion_search
-  FhevcMotionNode* d_motion = nullptr;     // ... and, once the refinement has read them, the records of fhevc_p_shape_frame (an entry is as large)
-  FhevcMotionQpelNode* d_qpel = nullptr;   // the output of fhevc_motion_refine and the nodes' output of fhevc_motion_refine_pu_wide (host forms); the input nodes go through d_motion
-  FhevcMotionNode* d_motion_pu = nullptr;  // the output of fhevc_motion_search_pu (host form); its optional nodes go through d_motion
-  FhevcMotionNode* d_motion_pu_small = nullptr;  // the output of fhevc_motion_search_pu_small (host form)
-  FhevcMotionNode* d_centres = nullptr;    // the centres of fhevc_motion_search_pu_centred (host form): one entry per CTU
-  FhevcMotionQpelNode* d_qpel_pu = nullptr;        // the outputs of fhevc_motion_refine_pu (host form); its input PUs go through d_motion_pu /
-  FhevcMotionQpelNode* d_qpel_pu_small = nullptr;  // d_motion_pu_small
-  uint8_t* d_p_maps = nullptr;       // fhevc_p_predict_frame: the reference picture's map, depth_min, depth_max (numCtus * 256 each)
+  int16_t* d_pair = nullptr;
+  FhevcMotionNode *d_motion = nullptr, *d_motion_pu = nullptr, *d_motion_pu_small = nullptr, *d_centres = nullptr;
+  FhevcMotionQpelNode *d_qpel = nullptr, *d_qpel_pu = nullptr, *d_qpel_pu_small = nullptr;
+  uint8_t* d_p_maps = nullptr;
   FhevcNodeCost* d_cand_all = nullptr; uint8_t* d_cand = nullptr;   // fhevc_intra_first_pass_candidates: every (node, mode) cost, the lists
   FhevcNodeCost* d_best4 = nullptr; uint8_t* d_modes4 = nullptr;    // fhevc_intra_first_pass_4x4: the best mode and the list of every 4x4 PU
   uint32_t* d_mvtab = nullptr;        // vector costs of the wide search (k_motion_wide.hip), rebuilt when (qp, range) changes
@@ -99,6 +96,73 @@ static inline int fail(fhevc_ctx* c, int code, const char* what, hipError_t e = 
     hipError_t e_ = (call);                                                \
     if (e_ != hipSuccess) return fail((c), FHEVC_E_HIP, #call, e_);        \
   } while (0)
+
+// ---- what the entry points of fhevc_api.hip and fhevc_motion_api.hip share ----
+
+inline void time_begin(fhevc_ctx* c, hipStream_t s, int which)
+{
+  if (!c->timing) return;
+  TimedLaunch t;
+  if (!c->pool.empty()) { t.start = c->pool.back().first; t.stop = c->pool.back().second; c->pool.pop_back(); }
+  else { (void)hipEventCreate(&t.start); (void)hipEventCreate(&t.stop); }
+  t.which = which;
+  (void)hipEventRecord(t.start, s);
+  c->pending.push_back(t);
+}
+inline void time_end(fhevc_ctx* c, hipStream_t s)
+{
+  if (!c->timing) return;
+  (void)hipEventRecord(c->pending.back().stop, s);
+}
+
+// One launch of an entry point: on the context's device, on the caller's stream (null: the context's own), between the timing events of slot `which`, counted.
+// launch(stream) returns the launcher's hipError_t
+template <class F> int launch_on(fhevc_ctx* c, void* stream, int which, const char* what, F&& launch)
+{
+  (void)hipSetDevice(c->device);
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+  time_begin(c, s, which);
+  const hipError_t e = launch(s);
+  if (e != hipSuccess) return fail(c, FHEVC_E_HIP, what, e);
+  time_end(c, s);
+  c->stats.kernels_launched++;
+  return FHEVC_OK;
+}
+
+// a buffer of the context that is allocated by the first call that needs it
+template <class T> hipError_t ensure(T*& p, size_t bytes) { return p ? hipSuccess : hipMalloc(&p, bytes); }
+
+inline FhevcFrames frames_of(const fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride, long long frame_stride,
+                      int num_frames, int row_begin, int row_end, int qp = 32)
+{
+  FhevcFrames f;
+  f.luma = d_luma; f.sample_bytes = sample_bytes; f.stride = stride; f.frame_stride = frame_stride;
+  f.width = c->cfg.width; f.height = c->cfg.height; f.bit_depth = c->cfg.bit_depth;
+  f.ctus_x = c->ctus_x; f.ctus_y = c->ctus_y; f.num_frames = num_frames; f.row_begin = row_begin; f.row_end = row_end;
+  f.qp = qp < 0 ? 0 : (qp > 51 ? 51 : qp);
+  return f;
+}
+
+// What the entry points over a device-resident batch check of its layout, each condition in one spelling; null: nothing wrong.  min_frames: 2 where a picture
+// is searched in the one before it.  qp: 0..51 (an entry point that clamps it, or has none, passes 0).  overlap: the frames of a batch must not overlap (asked
+// by the entry points whose launch covers the whole batch at once and by the motion entry points)
+inline const char* batch_error(const fhevc_ctx* c, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames, int min_frames,
+                        int ctu_row_begin, int ctu_row_end, int qp, bool overlap)
+{
+  if ((sample_bytes != 1 && sample_bytes != 2) || stride_samples < c->cfg.width || num_frames < min_frames) return "bad frame layout";
+  if (ctu_row_begin < 0 || ctu_row_end > c->ctus_y || ctu_row_begin > ctu_row_end) return "bad CTU-row band";
+  if (qp < 0 || qp > 51) return "qp out of range (0..51)";
+  if (sample_bytes == 1 && c->cfg.bit_depth != 8) return "uint8 samples need bit_depth 8";
+  if (overlap && num_frames > 1 && frame_stride_samples < (long long)stride_samples * (c->cfg.height - 1) + c->cfg.width) return "frames overlap";
+  return nullptr;
+}
+
+// lambda = 0.57 * 2^((qp-12)/3): TEncSlice::calculateLambda, all-intra path (TEncSlice.cpp:433-527).  The first-pass cost is compared bit-for-bit with the
+// oracle's doubles: this expression stays as it is
+inline double sqrt_lambda_intra(int qp) { return std::sqrt(0.57 * std::pow(2.0, ((double)qp - 12.0) / 3.0)); }
+
+// one of the context's two staging planes of a picture pair, in samples (fhevc_motion_api.hip); the single staging plane d_luma is as large
+inline size_t pair_plane(const fhevc_ctx* c) { return (size_t)c->dev_stride * c->ctus_y * 64; }
 
 // the kernel-argument views of the weight image in use (fhevc_weights.hip)
 FhevcCnnWeights cnn_weights(const fhevc_ctx* c);

@@ -1,0 +1,752 @@
+// fhevc_motion_api.hip -- the C ABI of config 4 (P pictures): the device forms of the motion stages over a device-resident batch, and the host forms
+// that stage one picture pair, run device forms on the context's own stream and bring the results back.  Host-side C++ only, as fhevc_api.hip.
+#include "fhevc_ctx.h"
+
+#include <cstring>
+
+namespace {
+
+// ---- the vector costs, with HM's own arithmetic (TComRdCost.h:166-174, TComRdCost.cpp:109-114, 177-190): getCost(bits) of the exp-Golomb lengths ----
+
+double motion_lambda(int qp) { return 65536.0 * sqrt_lambda_intra(qp); }
+uint32_t mv_bits_cost(double motion_lambda, unsigned bits) { return (uint32_t)((motion_lambda * bits) / 65536.0); }
+unsigned exp_golomb_bits(int v)
+{
+  unsigned len = 1, u = (v <= 0) ? (((unsigned)(-v)) << 1) + 1 : ((unsigned)v) << 1;
+  while (u != 1) { u >>= 1; len += 2; }
+  return len;
+}
+// ... of the window of +-range whole samples in raster order, (2 range + 1)^2 entries
+void mv_window_costs(int qp, int range, uint32_t* out)
+{
+  const double ml = motion_lambda(qp);
+  const int side = 2 * range + 1;
+  for (int m = 0; m < side * side; ++m) out[m] = mv_bits_cost(ml, exp_golomb_bits(((m % side) - range) << 2) + exp_golomb_bits(((m / side) - range) << 2));
+}
+FhevcMvCost mv_cost_table(int qp, int range)
+{
+  FhevcMvCost t;
+  mv_window_costs(qp, range, t.c);
+  return t;
+}
+// ... of every number of bits a quarter-sample vector can take (k_motion_refine.hip)
+FhevcMvBitCost mv_bit_cost_table(int qp)
+{
+  FhevcMvBitCost t;
+  const double ml = motion_lambda(qp);
+  for (int b = 0; b < FHEVC_MV_BIT_COSTS; ++b) t.c[b] = mv_bits_cost(ml, (unsigned)b);
+  return t;
+}
+
+// ---- the records of fasthevc.h as the kernels' own types (the same 16 bytes) ----
+
+template <class P> struct Kernel;
+template <> struct Kernel<fhevc_motion_node> { using T = FhevcMotionNode; };
+template <> struct Kernel<fhevc_motion_qpel_node> { using T = FhevcMotionQpelNode; };
+template <> struct Kernel<fhevc_motion_merge_node> { using T = FhevcMotionMergeNode; };
+template <> struct Kernel<fhevc_pu_shape_node> { using T = FhevcPuShapeNode; };
+template <> struct Kernel<fhevc_p_tree_node> { using T = FhevcPTreeNode; };
+template <class P> typename Kernel<P>::T* kn(P* p) { return reinterpret_cast<typename Kernel<P>::T*>(p); }
+template <class P> const typename Kernel<P>::T* kn(const P* p) { return reinterpret_cast<const typename Kernel<P>::T*>(p); }
+static_assert(sizeof(fhevc_motion_node) == 16 && sizeof(FhevcMotionNode) == 16 && sizeof(fhevc_motion_qpel_node) == 16 && sizeof(FhevcMotionQpelNode) == 16, "node layouts");
+static_assert(sizeof(fhevc_motion_merge_node) == 16 && sizeof(FhevcMotionMergeNode) == 16 && sizeof(fhevc_pu_shape_node) == 16 && sizeof(FhevcPuShapeNode) == 16, "record layouts");
+static_assert(FHEVC_PUS_PER_CTU == FHEVC_PUS && FHEVC_PUS_SMALL_PER_CTU == FHEVC_PUS_SMALL, "PU counts");
+
+// ---- how every device form over a batch of picture pairs opens ----
+
+const int GO = 1;   // beside FHEVC_OK (nothing to do) and the error codes (rejected)
+struct Batch { const void* luma; int sample_bytes, stride; long long frame_stride; int num_frames, row_begin, row_end, qp; };
+inline const char* nothing_more() { return nullptr; }
+
+// args_ok: the entry point's pointers (bad_args: its message; null: none is set); then the batch's layout, the range against 1..limit (bad_range), whatever
+// more() finds (a message, or null) and the empty band, which launches nothing and writes nothing.  GO: *fr describes the batch
+template <class More = const char* (*)()>
+int open_device_form(fhevc_ctx* c, bool args_ok, const char* bad_args, const Batch& b, int range, int limit, const char* bad_range, FhevcFrames* fr, More&& more = nothing_more)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!args_ok) return bad_args ? fail(c, FHEVC_E_INVALID, bad_args) : FHEVC_E_INVALID;
+  if (const char* bad = batch_error(c, b.sample_bytes, b.stride, b.frame_stride, b.num_frames, 2, b.row_begin, b.row_end, b.qp, true)) return fail(c, FHEVC_E_INVALID, bad);
+  if (range < 1 || range > limit) return fail(c, FHEVC_E_INVALID, bad_range);
+  if (const char* bad = more()) return fail(c, FHEVC_E_INVALID, bad);
+  if (b.row_begin == b.row_end) return FHEVC_OK;
+  *fr = frames_of(c, b.luma, b.sample_bytes, b.stride, b.frame_stride, b.num_frames, b.row_begin, b.row_end, b.qp);
+  return GO;
+}
+
+// ... and the device forms of one launch: launch(frames, stream), timed and counted under `slot`
+template <class L, class More = const char* (*)()>
+int device_form(fhevc_ctx* c, bool args_ok, const char* bad_args, const Batch& b, int range, int limit, const char* bad_range, void* stream, int slot, const char* what,
+                L&& launch, More&& more = nothing_more)
+{
+  FhevcFrames fr;
+  const int rc = open_device_form(c, args_ok, bad_args, b, range, limit, bad_range, &fr, more);
+  return rc != GO ? rc : launch_on(c, stream, slot, what, [&](hipStream_t s) { return launch(fr, s); });
+}
+
+// ---- how every host form stages its picture pair and its arrays ----
+//
+// The context's staging buffers, each allocated by the first call that needs it.  An entry of every family is 16 bytes, whichever record it holds:
+//
+//   buffer                   entries per CTU   what the host forms keep in it
+//   d_pair                   --                the reference and the current picture, two planes of pair_plane() samples: a batch of two frames
+//   d_motion                 85  (nodes)       the integer nodes; once the refinement has read them, the partition-size records of the frame chains;
+//                                              the merge records of fhevc_motion_merge; in its head, the one centre per CTU of fhevc_motion_centres
+//   d_qpel                   85                the refined nodes (the input of fhevc_motion_merge)
+//   d_motion_pu, d_qpel_pu   124 (PUs)         the integer and the refined PUs; once the refinement has read the integer PUs, the merge records
+//                                              of fhevc_p_tree_merge_frame in the head of d_motion_pu (85 of the 124 entries per CTU)
+//   d_motion_pu_small,       384 (small PUs)   the integer and the refined small PUs
+//   d_qpel_pu_small
+//   d_centres                1                 the centres that the centred searches and refinements read
+//   d_p_maps                 3 x 256 bytes     the reference picture's depth map, depth_min, depth_max (fhevc_p_predict_frame; the tree chains use the last two)
+//
+// The timing slots (fhevc_kernel_timing) of the launches below: 4 fhevc_motion_search, 5 the P rule, 7 fhevc_motion_refine, 8 / 9 the searches of the PUs / the
+// small PUs, 10 fhevc_motion_refine_pu, 11 / 12 the wide search / refinement, 13 the partition sizes, 15 the centres and everything centred, 17 the tree, 19 the merge stage
+struct Family { int per_ctu; FhevcMotionNode* fhevc_ctx::*found; FhevcMotionQpelNode* fhevc_ctx::*refined; };
+constexpr Family kNodes = { FHEVC_NODES, &fhevc_ctx::d_motion, &fhevc_ctx::d_qpel }, kPus = { FHEVC_PUS, &fhevc_ctx::d_motion_pu, &fhevc_ctx::d_qpel_pu },
+                 kSmall = { FHEVC_PUS_SMALL, &fhevc_ctx::d_motion_pu_small, &fhevc_ctx::d_qpel_pu_small }, kCentres = { 1, &fhevc_ctx::d_centres, nullptr };
+
+// fn, a device form, over the staged pair: a batch of two frames, the whole picture
+template <class Fn, class... A> int on_pair(fhevc_ctx* c, Fn fn, int qp, A... rest)
+{
+  return fn(c, c->d_pair, 2, c->dev_stride, (long long)pair_plane(c), 2, 0, c->ctus_y, qp, rest...);
+}
+
+int upload_pair(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples)
+{
+  HIP_TRY(c, ensure(c->d_pair, 2 * pair_plane(c) * sizeof(int16_t)));
+  HIP_TRY(c, ensure(c->d_motion, (size_t)c->num_ctus * FHEVC_NODES * sizeof(FhevcMotionNode)));
+  const int16_t* src[2] = { ref_luma, cur_luma };
+  for (int i = 0; i < 2; ++i)
+    HIP_TRY(c, hipMemcpy2DAsync(c->d_pair + i * pair_plane(c), (size_t)c->dev_stride * 2, src[i], (size_t)stride_samples * 2, (size_t)c->cfg.width * 2,
+                                (size_t)c->cfg.height, hipMemcpyHostToDevice, c->stream));
+  c->stats.bytes_h2d += (uint64_t)c->cfg.width * c->cfg.height * 4;
+  return FHEVC_OK;
+}
+
+// One call of a host form.  First name what it moves: in() and out() take a staging buffer with its full size, the caller's array, the bytes to copy and
+// where in the buffer they lie, and answer the device address the device form gets -- null for an array the caller left out, which moves nothing; dev()
+// only claims the buffer.  Then run(): the pair and the inputs up, queue() -- the device form or chain, on the context's stream --, the outputs down,
+// one synchronisation, the counters
+class HostForm {
+ public:
+  explicit HostForm(fhevc_ctx* ctx) : c(ctx) { (void)hipSetDevice(c->device); }
+  size_t bytes(const Family& f) const { return (size_t)c->num_ctus * f.per_ctu * sizeof(FhevcMotionNode); }
+
+  template <class H, class D> H* dev(D*& buf, size_t size, size_t at = 0)
+  {
+    if (e == hipSuccess) e = ensure(buf, size);
+    return reinterpret_cast<H*>(reinterpret_cast<char*>(buf) + at);
+  }
+  template <class H, class D> const H* in(D*& buf, size_t size, const H* host, size_t n, size_t at = 0) { return host ? copy(ins[n_in++], dev<H>(buf, size, at), const_cast<H*>(host), n) : nullptr; }
+  template <class H, class D> H* out(D*& buf, size_t size, H* host, size_t n, size_t at = 0) { return host ? copy(outs[n_out++], dev<H>(buf, size, at), host, n) : nullptr; }
+  // ... a family's integer entries in, its integer or refined entries out, or on the device only
+  template <class H> const H* found_in(const Family& f, const H* host) { return in(c->*f.found, bytes(f), host, bytes(f)); }
+  template <class H> H* found_out(const Family& f, H* host) { return out(c->*f.found, bytes(f), host, bytes(f)); }
+  template <class H> H* refined_out(const Family& f, H* host) { return out(c->*f.refined, bytes(f), host, bytes(f)); }
+  fhevc_motion_node* found(const Family& f) { return dev<fhevc_motion_node>(c->*f.found, bytes(f)); }
+  fhevc_motion_qpel_node* refined(const Family& f) { return dev<fhevc_motion_qpel_node>(c->*f.refined, bytes(f)); }
+
+  template <class Q> int run(const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, Q&& queue)
+  {
+    const int rc = e != hipSuccess ? fail(c, FHEVC_E_HIP, "staging buffer", e) : staged(cur_luma, ref_luma, stride_samples, queue);
+    if (rc != FHEVC_OK) (void)hipStreamSynchronize(c->stream);   // the uploads read the caller's buffers, the downloads write them: through before a failed call returns
+    return rc;
+  }
+
+ private:
+  struct Copy { void* dev; void* host; size_t n; };
+  template <class H> static H* copy(Copy& slot, H* dev, H* host, size_t n) { slot = { dev, host, n }; return dev; }
+
+  template <class Q> int staged(const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, Q& queue)
+  {
+    int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
+    if (rc != FHEVC_OK) return rc;
+    for (int i = 0; i < n_in; ++i) {
+      HIP_TRY(c, hipMemcpyAsync(ins[i].dev, ins[i].host, ins[i].n, hipMemcpyHostToDevice, c->stream));
+      c->stats.bytes_h2d += ins[i].n;
+    }
+    rc = queue();
+    if (rc != FHEVC_OK) return rc;
+    uint64_t down = 0;
+    for (int i = 0; i < n_out; ++i) {
+      HIP_TRY(c, hipMemcpyAsync(outs[i].host, outs[i].dev, outs[i].n, hipMemcpyDeviceToHost, c->stream));
+      down += outs[i].n;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->stats.bytes_d2h += down;
+    return FHEVC_OK;
+  }
+
+  fhevc_ctx* c;
+  hipError_t e = hipSuccess;
+  Copy ins[4], outs[4];   // at most: the centres and three families in; two maps and two sets of records out
+  int n_in = 0, n_out = 0;
+};
+
+// what the host forms check before they touch the device: the context, the entry point's pointers, the stride, qp 0..51 and the range 1..limit -> GO or the error
+int open_host_form(fhevc_ctx* c, bool args_ok, int stride_samples, int qp, int range, int limit, const char* bad)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!args_ok || stride_samples < c->cfg.width || qp < 0 || qp > 51 || range < 1 || range > limit) return fail(c, FHEVC_E_INVALID, bad);
+  return GO;
+}
+
+// The frame chains: all three families through a search and its refinement on the context's stream -- coarse_range 0: the wide pair; otherwise the centres
+// and the centred pair around them -- into the refined staging buffers
+struct Chain { fhevc_motion_node *nodes, *pus, *small, *centres; fhevc_motion_qpel_node *q_nodes, *q_pus, *q_small; };
+Chain claim_chain(HostForm& h, bool centred)
+{
+  return { h.found(kNodes), h.found(kPus), h.found(kSmall), centred ? h.found(kCentres) : nullptr, h.refined(kNodes), h.refined(kPus), h.refined(kSmall) };
+}
+int queue_chain(fhevc_ctx* c, int qp, int search_range, int coarse_range, const Chain& k)
+{
+  int rc;
+  if (!coarse_range) {
+    rc = on_pair(c, fhevc_motion_search_pu_wide_device, qp, search_range, k.nodes, k.pus, k.small, c->stream);
+    return rc != FHEVC_OK ? rc : on_pair(c, fhevc_motion_refine_pu_wide_device, qp, search_range, k.nodes, k.q_nodes, k.pus, k.q_pus, k.small, k.q_small, c->stream);
+  }
+  rc = on_pair(c, fhevc_motion_centres_device, qp, coarse_range, k.centres, c->stream);
+  if (rc == FHEVC_OK) rc = on_pair(c, fhevc_motion_search_pu_centred_device, qp, search_range, k.centres, k.nodes, k.pus, k.small, c->stream);
+  return rc != FHEVC_OK ? rc : on_pair(c, fhevc_motion_refine_pu_centred_device, qp, search_range, k.centres, k.nodes, k.q_nodes, k.pus, k.q_pus, k.small, k.q_small, c->stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- source-only motion search per CU node (k_motion.hip, k_motion_wide.hip) ----
+
+int fhevc_motion_search_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                               int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range, fhevc_motion_node* d_out, void* stream)
+{
+  const bool wide = search_range > FHEVC_MOTION_MAX_RANGE;
+  const Batch b{ d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp };
+  FhevcFrames fr;
+  const int rc = open_device_form(c, d_luma && d_out, nullptr, b, search_range, FHEVC_MOTION_WIDE_MAX_RANGE, "bad motion-search arguments", &fr, [&]() -> const char* {
+    if (wide && !c->motion_sad) return "search ranges above 8 need the SAD distortion (fhevc_set_motion_distortion)";
+    return wide && c->cfg.bit_depth > 8 && sample_bytes != 2 ? "bad motion-search arguments" : nullptr;
+  });
+  if (rc != GO) return rc;
+  const bool big = wide && c->cfg.bit_depth > 8;   // above 8 bit: the generic kernel laid out for the wide window (round 4); 8 bit: the byte-SAD kernel
+  if (wide && (c->mvtab_qp != qp || c->mvtab_range != search_range)) {
+    // the wide kernels read the window's vector costs from HBM
+    (void)hipSetDevice(c->device);
+    HIP_TRY(c, ensure(c->d_mvtab, sizeof(uint32_t) * (2 * FHEVC_MOTION_WIDE_MAX_RANGE + 1) * (2 * FHEVC_MOTION_WIDE_MAX_RANGE + 1)));
+    // EVERY launch that reads the old table has to be through, on whatever streams the callers passed (an event behind the latest launch would
+    // cover that one stream only).  A rebuild happens only when (qp, range) changes: off the hot path
+    HIP_TRY(c, hipDeviceSynchronize());
+    c->mvtab_host.resize((size_t)(2 * search_range + 1) * (2 * search_range + 1));
+    mv_window_costs(qp, search_range, c->mvtab_host.data());
+    HIP_TRY(c, hipMemcpy(c->d_mvtab, c->mvtab_host.data(), c->mvtab_host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    c->mvtab_qp = qp; c->mvtab_range = search_range;
+  }
+  return launch_on(c, stream, 4, "motion search", [&](hipStream_t s) {
+    if (big) return fhevc_launch_motion_big(fr, search_range, c->d_mvtab, kn(d_out), c->num_cus, s);
+    if (wide) return fhevc_launch_motion_wide(fr, search_range, c->d_mvtab, kn(d_out), c->num_cus, s);
+    return fhevc_launch_motion(fr, search_range, mv_cost_table(qp, search_range), kn(d_out), c->num_cus, c->motion_sad, s);
+  });
+}
+
+int fhevc_motion_search(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                        fhevc_motion_node* out)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!cur_luma || !ref_luma || !out || stride_samples < c->cfg.width) return fail(c, FHEVC_E_INVALID, "bad motion-search arguments");
+  // what the device form says to these two, said before the pair is staged; which distortion a range needs stays the device form's to say
+  if (qp < 0 || qp > 51) return fail(c, FHEVC_E_INVALID, "qp out of range (0..51)");
+  if (search_range < 1 || search_range > FHEVC_MOTION_WIDE_MAX_RANGE) return fail(c, FHEVC_E_INVALID, "bad motion-search arguments");
+  HostForm h(c);
+  fhevc_motion_node* d_out = h.found_out(kNodes, out);
+  return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_search_device, qp, search_range, d_out, c->stream); });
+}
+
+// ---- the search of the rectangular PUs (k_motion_pu.hip) ----
+
+int fhevc_motion_search_pu_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                  int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range,
+                                  fhevc_motion_node* d_nodes, fhevc_motion_node* d_pus, void* stream)
+{
+  const Batch b{ d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp };
+  return device_form(c, d_luma && d_pus, "bad PU motion-search arguments", b, search_range, FHEVC_MOTION_MAX_RANGE, "the PU motion search covers search ranges 1..8",
+                     stream, 8, "fhevc_launch_motion_pu", [&](const FhevcFrames& fr, hipStream_t s) {
+    return fhevc_launch_motion_pu(fr, search_range, mv_cost_table(qp, search_range), kn(d_nodes), kn(d_pus), c->num_cus, c->motion_sad, s);
+  });
+}
+
+int fhevc_motion_search_pu(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                           fhevc_motion_node* nodes, fhevc_motion_node* pus)
+{
+  const int rc = open_host_form(c, cur_luma && ref_luma && pus, stride_samples, qp, search_range, FHEVC_MOTION_MAX_RANGE, "bad PU motion-search arguments");
+  if (rc != GO) return rc;
+  HostForm h(c);
+  fhevc_motion_node *d_nodes = h.found_out(kNodes, nodes), *d_pus = h.found_out(kPus, pus);
+  return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_search_pu_device, qp, search_range, d_nodes, d_pus, c->stream); });
+}
+
+// ---- the search of the PUs with a 4-sample side (k_motion_pu_small.hip) ----
+
+int fhevc_motion_search_pu_small_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                        int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range,
+                                        fhevc_motion_node* d_pus, void* stream)
+{
+  const Batch b{ d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp };
+  return device_form(c, d_luma && d_pus, "bad small-PU motion-search arguments", b, search_range, FHEVC_MOTION_MAX_RANGE, "the small-PU motion search covers search ranges 1..8",
+                     stream, 9, "fhevc_launch_motion_pu_small", [&](const FhevcFrames& fr, hipStream_t s) {
+    return fhevc_launch_motion_pu_small(fr, search_range, mv_cost_table(qp, search_range), kn(d_pus), c->num_cus, c->motion_sad, s);
+  });
+}
+
+int fhevc_motion_search_pu_small(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                                 fhevc_motion_node* pus)
+{
+  const int rc = open_host_form(c, cur_luma && ref_luma && pus, stride_samples, qp, search_range, FHEVC_MOTION_MAX_RANGE, "bad small-PU motion-search arguments");
+  if (rc != GO) return rc;
+  HostForm h(c);
+  fhevc_motion_node* d_pus = h.found_out(kSmall, pus);
+  return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_search_pu_small_device, qp, search_range, d_pus, c->stream); });
+}
+
+// ---- the three searches at HM's own SearchRange, SAD (the MR = 64 layouts of k_motion_pu.hip and k_motion_pu_small.hip) ----
+
+int fhevc_motion_search_pu_wide_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                       int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range,
+                                       fhevc_motion_node* d_nodes, fhevc_motion_node* d_pus, fhevc_motion_node* d_pus_small, void* stream)
+{
+  FhevcFrames fr;
+  const Batch b{ d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp };
+  const int open = open_device_form(c, d_luma && (d_nodes || d_pus || d_pus_small), "bad wide PU motion-search arguments", b, search_range, FHEVC_MOTION_WIDE_MAX_RANGE,
+                                    "the wide PU motion search covers search ranges 1..64", &fr);
+  if (open != GO) return open;
+  FhevcMotionNode *nodes = kn(d_nodes), *pus = kn(d_pus), *small = kn(d_pus_small);
+  // Always SAD, and every vector cost travels with its launch: the window's table up to +-8 (the MR = 8 layouts, several workgroups per CU), the 40 bit
+  // costs above.  Nothing of the context is read or written by the launches: calls on different streams may be in flight together.  Above +-8: 8-bit
+  // contexts take the byte-SAD kernel (k_motion_pu_wide.hip: one launch for whatever is asked for), contexts above 8 bit -- and 8-bit int16 planes under
+  // FHEVC_PU_WIDE=generic -- the MR = 64 layouts of the generic kernels (one launch for nodes and PUs, one for the small PUs).  Timed under slot 11
+  const bool big = search_range > FHEVC_MOTION_MAX_RANGE;
+  if (big && c->cfg.bit_depth == 8 && !(c->knobs.pu_wide_generic && sample_bytes == 2))
+    return launch_on(c, stream, 11, "fhevc_launch_motion_pu_wide", [&](hipStream_t s) {
+      return fhevc_launch_motion_pu_wide(fr, search_range, mv_bit_cost_table(qp), nodes, pus, small, c->num_cus, s);
+    });
+  if (nodes || pus) {
+    const int rc = launch_on(c, stream, 11, "fhevc_motion_search_pu_wide (nodes, PUs)", [&](hipStream_t s) {
+      if (big) return fhevc_launch_motion_pu_big(fr, search_range, mv_bit_cost_table(qp), nodes, pus, c->num_cus, s);
+      if (!pus) return fhevc_launch_motion(fr, search_range, mv_cost_table(qp, search_range), nodes, c->num_cus, true, s);
+      return fhevc_launch_motion_pu(fr, search_range, mv_cost_table(qp, search_range), nodes, pus, c->num_cus, true, s);
+    });
+    if (rc != FHEVC_OK) return rc;
+  }
+  if (!small) return FHEVC_OK;
+  return launch_on(c, stream, 11, "fhevc_motion_search_pu_wide (small PUs)", [&](hipStream_t s) {
+    if (big) return fhevc_launch_motion_pu_small_big(fr, search_range, mv_bit_cost_table(qp), small, c->num_cus, s);
+    return fhevc_launch_motion_pu_small(fr, search_range, mv_cost_table(qp, search_range), small, c->num_cus, true, s);
+  });
+}
+
+int fhevc_motion_search_pu_wide(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                                fhevc_motion_node* nodes, fhevc_motion_node* pus, fhevc_motion_node* pus_small)
+{
+  const int rc = open_host_form(c, cur_luma && ref_luma && (nodes || pus || pus_small), stride_samples, qp, search_range, FHEVC_MOTION_WIDE_MAX_RANGE,
+                                "bad wide PU motion-search arguments");
+  if (rc != GO) return rc;
+  HostForm h(c);
+  fhevc_motion_node *d_nodes = h.found_out(kNodes, nodes), *d_pus = h.found_out(kPus, pus), *d_small = h.found_out(kSmall, pus_small);
+  return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_search_pu_wide_device, qp, search_range, d_nodes, d_pus, d_small, c->stream); });
+}
+
+// ---- one coarse motion centre per CTU from the 4:1 decimated picture pair (k_motion_coarse.hip) ----
+
+int fhevc_motion_centres_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int coarse_range, fhevc_motion_node* d_centres, void* stream)
+{
+  const Batch b{ d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp };
+  // the bit costs travel with the launch: nothing of the context is read or written by it.  Timed under slot 15
+  return device_form(c, d_luma && d_centres, "bad motion-centre arguments", b, coarse_range, FHEVC_MOTION_COARSE_MAX_RANGE, "the motion centres cover coarse ranges 1..14",
+                     stream, 15, "fhevc_launch_motion_coarse", [&](const FhevcFrames& fr, hipStream_t s) {
+    return fhevc_launch_motion_coarse(fr, coarse_range, mv_bit_cost_table(qp), kn(d_centres), c->num_cus, s);
+  });
+}
+
+int fhevc_motion_centres(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int coarse_range, fhevc_motion_node* centres)
+{
+  const int rc = open_host_form(c, cur_luma && ref_luma && centres, stride_samples, qp, coarse_range, FHEVC_MOTION_COARSE_MAX_RANGE, "bad motion-centre arguments");
+  if (rc != GO) return rc;
+  HostForm h(c);
+  fhevc_motion_node* d_centres = h.out(c->d_motion, h.bytes(kNodes), centres, h.bytes(kCentres));
+  return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_centres_device, qp, coarse_range, d_centres, c->stream); });
+}
+
+// ---- the three integer searches around one centre per CTU (the MR = 8 layouts of k_motion_pu.hip and k_motion_pu_small.hip, centred) ----
+
+int fhevc_motion_search_pu_centred_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                          int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int search_range, const fhevc_motion_node* d_centres,
+                                          fhevc_motion_node* d_nodes, fhevc_motion_node* d_pus, fhevc_motion_node* d_pus_small, void* stream)
+{
+  FhevcFrames fr;
+  const Batch b{ d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp };
+  const int open = open_device_form(c, d_luma && d_centres && (d_nodes || d_pus || d_pus_small), "bad centred PU motion-search arguments", b, search_range,
+                                    FHEVC_MOTION_MAX_RANGE, "the centred PU motion search covers search ranges 1..8", &fr);
+  if (open != GO) return open;
+  // Always SAD.  The window's table of vector costs travels with the launch and prices d = v - P, the vector relative to the centre: exactly
+  // getCostOfVectorWithPredictor with the predictor 4 P.  Whether a centre is in range is the kernel's to decide (the host cannot see device centres).  Nothing of the
+  // context is read or written by the launches.  One launch for nodes and PUs, one for the small PUs, each timed and counted under slot 15
+  if (d_nodes || d_pus) {
+    const int rc = launch_on(c, stream, 15, "fhevc_motion_search_pu_centred (nodes, PUs)", [&](hipStream_t s) {
+      return fhevc_launch_motion_pu_centred(fr, search_range, mv_cost_table(qp, search_range), kn(d_centres), kn(d_nodes), kn(d_pus), c->num_cus, s);
+    });
+    if (rc != FHEVC_OK) return rc;
+  }
+  if (!d_pus_small) return FHEVC_OK;
+  return launch_on(c, stream, 15, "fhevc_motion_search_pu_centred (small PUs)", [&](hipStream_t s) {
+    return fhevc_launch_motion_pu_small_centred(fr, search_range, mv_cost_table(qp, search_range), kn(d_centres), kn(d_pus_small), c->num_cus, s);
+  });
+}
+
+int fhevc_motion_search_pu_centred(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                                   const fhevc_motion_node* centres, fhevc_motion_node* nodes, fhevc_motion_node* pus, fhevc_motion_node* pus_small)
+{
+  const int rc = open_host_form(c, cur_luma && ref_luma && centres && (nodes || pus || pus_small), stride_samples, qp, search_range, FHEVC_MOTION_MAX_RANGE,
+                                "bad centred PU motion-search arguments");
+  if (rc != GO) return rc;
+  HostForm h(c);
+  const fhevc_motion_node* d_centres = h.found_in(kCentres, centres);
+  fhevc_motion_node *d_nodes = h.found_out(kNodes, nodes), *d_pus = h.found_out(kPus, pus), *d_small = h.found_out(kSmall, pus_small);
+  return h.run(cur_luma, ref_luma, stride_samples,
+               [&] { return on_pair(c, fhevc_motion_search_pu_centred_device, qp, search_range, d_centres, d_nodes, d_pus, d_small, c->stream); });
+}
+
+// ---- quarter-sample refinement of the search's vectors (k_motion_refine.hip) ----
+
+int fhevc_motion_refine_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                               int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_node* d_nodes,
+                               fhevc_motion_qpel_node* d_out, void* stream)
+{
+  const Batch b{ d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp };
+  return device_form(c, d_luma && d_nodes && d_out, "bad motion-refinement arguments", b, max_range, FHEVC_MOTION_WIDE_MAX_RANGE, "bad motion-refinement arguments",
+                     stream, 7, "fhevc_launch_motion_refine", [&](const FhevcFrames& fr, hipStream_t s) {
+    return fhevc_launch_motion_refine(fr, max_range, mv_bit_cost_table(qp), kn(d_nodes), kn(d_out), c->num_cus, s);
+  });
+}
+
+int fhevc_motion_refine(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                        const fhevc_motion_node* nodes, fhevc_motion_qpel_node* out)
+{
+  const int rc = open_host_form(c, cur_luma && ref_luma && nodes && out, stride_samples, qp, max_range, FHEVC_MOTION_WIDE_MAX_RANGE, "bad motion-refinement arguments");
+  if (rc != GO) return rc;
+  HostForm h(c);
+  const fhevc_motion_node* d_nodes = h.found_in(kNodes, nodes);
+  fhevc_motion_qpel_node* d_out = h.refined_out(kNodes, out);
+  return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_refine_device, qp, max_range, d_nodes, d_out, c->stream); });
+}
+
+// ---- merge-candidate costs per CU node from the refined nodes (k_motion_merge.hip) ----
+
+int fhevc_motion_merge_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                              int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_qpel_node* d_refined,
+                              fhevc_motion_merge_node* d_out, void* stream)
+{
+  const Batch b{ d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp };
+  return device_form(c, d_luma && d_refined && d_out, "bad merge-stage arguments", b, max_range, FHEVC_MOTION_WIDE_MAX_RANGE, "bad merge-stage arguments (max_range 1..64)",
+                     stream, 19, "fhevc_launch_motion_merge", [&](const FhevcFrames& fr, hipStream_t s) {
+    return fhevc_launch_motion_merge(fr, max_range, mv_bit_cost_table(qp), kn(d_refined), kn(d_out), c->num_cus, s);
+  }, [&]() -> const char* {
+    return (long long)(num_frames - 1) * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL ? "more than 2^31 - 1 CTUs" : nullptr;
+  });
+}
+
+int fhevc_motion_merge(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                       const fhevc_motion_qpel_node* refined, fhevc_motion_merge_node* out)
+{
+  const int rc = open_host_form(c, cur_luma && ref_luma && refined && out, stride_samples, qp, max_range, FHEVC_MOTION_WIDE_MAX_RANGE, "bad merge-stage arguments");
+  if (rc != GO) return rc;
+  HostForm h(c);
+  const fhevc_motion_qpel_node* d_refined = h.in(c->d_qpel, h.bytes(kNodes), refined, h.bytes(kNodes));
+  fhevc_motion_merge_node* d_out = h.out(c->d_motion, h.bytes(kNodes), out, h.bytes(kNodes));
+  return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_merge_device, qp, max_range, d_refined, d_out, c->stream); });
+}
+
+// ---- quarter-sample refinement of the PUs' vectors (k_motion_refine_pu.hip) ----
+
+int fhevc_motion_refine_pu_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                  int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range,
+                                  const fhevc_motion_node* d_pus, fhevc_motion_qpel_node* d_out_pus,
+                                  const fhevc_motion_node* d_pus_small, fhevc_motion_qpel_node* d_out_pus_small, void* stream)
+{
+  const Batch b{ d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp };
+  // either family's pair may be null together, not both pairs and not half a pair
+  return device_form(c, d_luma && (d_pus || d_pus_small) && !d_pus == !d_out_pus && !d_pus_small == !d_out_pus_small, "bad PU motion-refinement arguments", b, max_range,
+                     FHEVC_MOTION_MAX_RANGE, "the PU motion refinement covers vectors of the search ranges 1..8", stream, 10, "fhevc_launch_motion_refine_pu",
+                     [&](const FhevcFrames& fr, hipStream_t s) {
+    return fhevc_launch_motion_refine_pu(fr, max_range, mv_bit_cost_table(qp), kn(d_pus), kn(d_out_pus), kn(d_pus_small), kn(d_out_pus_small), c->num_cus, false, s);
+  });
+}
+
+int fhevc_motion_refine_pu(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                           const fhevc_motion_node* pus, fhevc_motion_qpel_node* out_pus, const fhevc_motion_node* pus_small, fhevc_motion_qpel_node* out_pus_small)
+{
+  const int rc = open_host_form(c, cur_luma && ref_luma && (pus || pus_small) && !pus == !out_pus && !pus_small == !out_pus_small, stride_samples, qp, max_range,
+                                FHEVC_MOTION_MAX_RANGE, "bad PU motion-refinement arguments");
+  if (rc != GO) return rc;
+  HostForm h(c);
+  const fhevc_motion_node *d_pus = h.found_in(kPus, pus), *d_small = h.found_in(kSmall, pus_small);
+  fhevc_motion_qpel_node *q_pus = h.refined_out(kPus, out_pus), *q_small = h.refined_out(kSmall, out_pus_small);
+  return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_refine_pu_device, qp, max_range, d_pus, q_pus, d_small, q_small, c->stream); });
+}
+
+// ---- the two refinements at HM's own SearchRange: what fhevc_motion_search_pu_wide writes feeds straight in (k_motion_refine.hip, k_motion_refine_pu.hip) ----
+
+int fhevc_motion_refine_pu_wide_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                       int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range,
+                                       const fhevc_motion_node* d_nodes, fhevc_motion_qpel_node* d_out_nodes,
+                                       const fhevc_motion_node* d_pus, fhevc_motion_qpel_node* d_out_pus,
+                                       const fhevc_motion_node* d_pus_small, fhevc_motion_qpel_node* d_out_pus_small, void* stream)
+{
+  FhevcFrames fr;
+  const Batch b{ d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp };
+  // each family's pair may be null together, not all three pairs and not half a pair
+  const bool args_ok = d_luma && (d_nodes || d_pus || d_pus_small) && !d_nodes == !d_out_nodes && !d_pus == !d_out_pus && !d_pus_small == !d_out_pus_small;
+  const int open = open_device_form(c, args_ok, "bad wide PU motion-refinement arguments", b, max_range, FHEVC_MOTION_WIDE_MAX_RANGE,
+                                    "the wide PU motion refinement covers vectors of the search ranges 1..64", &fr);
+  if (open != GO) return open;
+  // Nothing of the context is read or written by the launches (the 40 bit costs travel by value): calls on different streams may be in flight together.
+  // The nodes: the square kernel, the launch of fhevc_motion_refine_device; the PUs: one launch for both families, the MR = 8 layout up to +-8 (the launch
+  // of fhevc_motion_refine_pu_device), the MR = 64 layout above.  Each launch is timed and counted under slot 12
+  if (d_nodes) {
+    const int rc = launch_on(c, stream, 12, "fhevc_motion_refine_pu_wide (nodes)", [&](hipStream_t s) {
+      return fhevc_launch_motion_refine(fr, max_range, mv_bit_cost_table(qp), kn(d_nodes), kn(d_out_nodes), c->num_cus, s);
+    });
+    if (rc != FHEVC_OK) return rc;
+  }
+  if (!d_pus && !d_pus_small) return FHEVC_OK;
+  return launch_on(c, stream, 12, "fhevc_motion_refine_pu_wide (PUs)", [&](hipStream_t s) {
+    return fhevc_launch_motion_refine_pu(fr, max_range, mv_bit_cost_table(qp), kn(d_pus), kn(d_out_pus), kn(d_pus_small), kn(d_out_pus_small), c->num_cus,
+                                         c->knobs.refine_pu_stage_full, s);
+  });
+}
+
+int fhevc_motion_refine_pu_wide(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                                const fhevc_motion_node* nodes, fhevc_motion_qpel_node* out_nodes,
+                                const fhevc_motion_node* pus, fhevc_motion_qpel_node* out_pus,
+                                const fhevc_motion_node* pus_small, fhevc_motion_qpel_node* out_pus_small)
+{
+  const bool args_ok = cur_luma && ref_luma && (nodes || pus || pus_small) && !nodes == !out_nodes && !pus == !out_pus && !pus_small == !out_pus_small;
+  const int rc = open_host_form(c, args_ok, stride_samples, qp, max_range, FHEVC_MOTION_WIDE_MAX_RANGE, "bad wide PU motion-refinement arguments");
+  if (rc != GO) return rc;
+  HostForm h(c);
+  const fhevc_motion_node *d_nodes = h.found_in(kNodes, nodes), *d_pus = h.found_in(kPus, pus), *d_small = h.found_in(kSmall, pus_small);
+  fhevc_motion_qpel_node *q_nodes = h.refined_out(kNodes, out_nodes), *q_pus = h.refined_out(kPus, out_pus), *q_small = h.refined_out(kSmall, out_pus_small);
+  return h.run(cur_luma, ref_luma, stride_samples,
+               [&] { return on_pair(c, fhevc_motion_refine_pu_wide_device, qp, max_range, d_nodes, q_nodes, d_pus, q_pus, d_small, q_small, c->stream); });
+}
+
+// ---- the two refinements around one centre per CTU: what fhevc_motion_search_pu_centred writes feeds straight in (k_motion_refine.hip, k_motion_refine_pu.hip, centred) ----
+
+int fhevc_motion_refine_pu_centred_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                          int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_node* d_centres,
+                                          const fhevc_motion_node* d_nodes, fhevc_motion_qpel_node* d_out_nodes,
+                                          const fhevc_motion_node* d_pus, fhevc_motion_qpel_node* d_out_pus,
+                                          const fhevc_motion_node* d_pus_small, fhevc_motion_qpel_node* d_out_pus_small, void* stream)
+{
+  FhevcFrames fr;
+  const Batch b{ d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp };
+  const bool args_ok = d_luma && d_centres && (d_nodes || d_pus || d_pus_small) && !d_nodes == !d_out_nodes && !d_pus == !d_out_pus && !d_pus_small == !d_out_pus_small;
+  const int open = open_device_form(c, args_ok, "bad centred PU motion-refinement arguments", b, max_range, FHEVC_MOTION_MAX_RANGE,
+                                    "the centred PU motion refinement covers max_range 1..8", &fr);
+  if (open != GO) return open;
+  // the MR = 8 layouts with the window staged around each CTU's centre; one launch for the nodes, one for both PU families, each timed and counted under slot 15
+  if (d_nodes) {
+    const int rc = launch_on(c, stream, 15, "fhevc_motion_refine_pu_centred (nodes)", [&](hipStream_t s) {
+      return fhevc_launch_motion_refine_centred(fr, max_range, mv_bit_cost_table(qp), kn(d_centres), kn(d_nodes), kn(d_out_nodes), c->num_cus, s);
+    });
+    if (rc != FHEVC_OK) return rc;
+  }
+  if (!d_pus && !d_pus_small) return FHEVC_OK;
+  return launch_on(c, stream, 15, "fhevc_motion_refine_pu_centred (PUs)", [&](hipStream_t s) {
+    return fhevc_launch_motion_refine_pu_centred(fr, max_range, mv_bit_cost_table(qp), kn(d_centres), kn(d_pus), kn(d_out_pus), kn(d_pus_small), kn(d_out_pus_small), c->num_cus, s);
+  });
+}
+
+int fhevc_motion_refine_pu_centred(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                                   const fhevc_motion_node* centres, const fhevc_motion_node* nodes, fhevc_motion_qpel_node* out_nodes,
+                                   const fhevc_motion_node* pus, fhevc_motion_qpel_node* out_pus,
+                                   const fhevc_motion_node* pus_small, fhevc_motion_qpel_node* out_pus_small)
+{
+  const bool args_ok = cur_luma && ref_luma && centres && (nodes || pus || pus_small) && !nodes == !out_nodes && !pus == !out_pus && !pus_small == !out_pus_small;
+  const int rc = open_host_form(c, args_ok, stride_samples, qp, max_range, FHEVC_MOTION_MAX_RANGE, "bad centred PU motion-refinement arguments");
+  if (rc != GO) return rc;
+  HostForm h(c);
+  const fhevc_motion_node *d_centres = h.found_in(kCentres, centres), *d_nodes = h.found_in(kNodes, nodes), *d_pus = h.found_in(kPus, pus), *d_small = h.found_in(kSmall, pus_small);
+  fhevc_motion_qpel_node *q_nodes = h.refined_out(kNodes, out_nodes), *q_pus = h.refined_out(kPus, out_pus), *q_small = h.refined_out(kSmall, out_pus_small);
+  return h.run(cur_luma, ref_luma, stride_samples,
+               [&] { return on_pair(c, fhevc_motion_refine_pu_centred_device, qp, max_range, d_centres, d_nodes, q_nodes, d_pus, q_pus, d_small, q_small, c->stream); });
+}
+
+// measurement tools only (tools/motion_refine_pu_wide_bench.py; not in fasthevc.h): what hipOccupancyMaxActiveBlocksPerMultiprocessor answers for the MR = 64
+// instance of k_motion_refine_pu.hip that planes of sample_bytes take on this context, and the cap of its persistent grid
+int fhevc_debug_refine_pu_wide_residency(fhevc_ctx* c, int sample_bytes, int* blocks_per_cu, int* grid_cap)
+{
+  if (!c || !blocks_per_cu || !grid_cap || (sample_bytes != 1 && sample_bytes != 2)) return FHEVC_E_INVALID;
+  (void)hipSetDevice(c->device);
+  HIP_TRY(c, fhevc_motion_refine_pu_big_residency(sample_bytes, c->cfg.bit_depth, blocks_per_cu));
+  *grid_cap = (*blocks_per_cu < 2 ? *blocks_per_cu : 2) * c->num_cus;
+  return FHEVC_OK;
+}
+
+// ---- P-picture depth ranges over a device-resident batch (k_p_rule.hip; the host form of the rule: fhevc_host.hip) ----
+int fhevc_p_depth_range_device(fhevc_ctx* c, const fhevc_motion_node* d_nodes, const uint8_t* d_prev_maps, int num_pictures, int ctu_row_begin,
+                               int ctu_row_end, int qp, int prev_mode, const fhevc_p_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, void* stream)
+{
+  if (!c || !d_nodes || !d_prev_maps || !d_depth_min) return FHEVC_E_INVALID;
+  // (nodes and maps have no sample layout: the checks of the pictures' number, the band and the qp)
+  if (const char* bad = batch_error(c, 2, c->cfg.width, 0, num_pictures, 1, ctu_row_begin, ctu_row_end, qp, false)) return fail(c, FHEVC_E_INVALID, bad);
+  if (prev_mode != FHEVC_P_PREV_COLOCATED && prev_mode != FHEVC_P_PREV_UNIT && prev_mode != FHEVC_P_PREV_NODE)
+    return fail(c, FHEVC_E_INVALID, "prev_mode: FHEVC_P_PREV_COLOCATED, FHEVC_P_PREV_UNIT or FHEVC_P_PREV_NODE");
+  if ((long long)num_pictures * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "bad P-rule arguments");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;
+  static_assert(sizeof(fhevc_p_rule) == sizeof(FhevcPRule), "P rule layout");
+  FhevcPRule r;   // read here, handed to the kernel by value: the caller's struct is free again when this call returns
+  if (rule) std::memcpy(&r, rule, sizeof r);
+  else { fhevc_p_rule d; fhevc_p_rule_default(&d); std::memcpy(&r, &d, sizeof r); }
+  const FhevcFrames fr = frames_of(c, nullptr, 1, c->cfg.width, 0, num_pictures, ctu_row_begin, ctu_row_end, qp);
+  return launch_on(c, stream, 5, "fhevc_launch_p_rule", [&](hipStream_t s) {
+    return fhevc_launch_p_rule(fr, prev_mode, r, kn(d_nodes), d_prev_maps, d_depth_min, d_depth_max, c->num_cus, s);
+  });
+}
+
+int fhevc_p_predict_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                          const uint8_t* prev_map, int prev_mode, const fhevc_p_rule* rule, uint8_t* depth_min, uint8_t* depth_max)
+{
+  if (!c || !cur_luma || !ref_luma || !prev_map || !depth_min || !depth_max || stride_samples < c->cfg.width) return FHEVC_E_INVALID;
+  if (prev_mode != FHEVC_P_PREV_COLOCATED && prev_mode != FHEVC_P_PREV_UNIT && prev_mode != FHEVC_P_PREV_NODE)
+    return fail(c, FHEVC_E_INVALID, "prev_mode: FHEVC_P_PREV_COLOCATED, FHEVC_P_PREV_UNIT or FHEVC_P_PREV_NODE");
+  HostForm h(c);
+  const size_t map = (size_t)c->num_ctus * 256;
+  const uint8_t* d_prev = h.in(c->d_p_maps, 3 * map, prev_map, map);
+  uint8_t *d_min = h.out(c->d_p_maps, 3 * map, depth_min, map, map), *d_max = h.out(c->d_p_maps, 3 * map, depth_max, map, 2 * map);
+  fhevc_motion_node* d_nodes = h.found(kNodes);
+  return h.run(cur_luma, ref_luma, stride_samples, [&] {
+    const int rc = on_pair(c, fhevc_motion_search_device, qp, search_range, d_nodes, c->stream);
+    return rc != FHEVC_OK ? rc : fhevc_p_depth_range_device(c, d_nodes, d_prev, 1, 0, c->ctus_y, qp, prev_mode, rule, d_min, d_max, c->stream);
+  });
+}
+
+// ---- partition sizes per CU from the refined PU costs over a device-resident batch (k_pu_shape.hip; the host form: fhevc_host.hip) ----
+int fhevc_pu_shape_select_device(fhevc_ctx* c, const fhevc_motion_qpel_node* d_nodes, const fhevc_motion_qpel_node* d_pus, const fhevc_motion_qpel_node* d_pus_small,
+                                 int num_pictures, int ctu_row_begin, int ctu_row_end, const fhevc_pu_shape_rule* rule, fhevc_pu_shape_node* d_shapes,
+                                 uint32_t* d_costs, void* stream)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!d_nodes || !d_pus || !d_shapes) return fail(c, FHEVC_E_INVALID, "bad partition-size selection arguments");
+  // (refined entries have no sample layout: the checks of the pictures' number and the band)
+  if (const char* bad = batch_error(c, 2, c->cfg.width, 0, num_pictures, 1, ctu_row_begin, ctu_row_end, 0, false)) return fail(c, FHEVC_E_INVALID, bad);
+  static_assert(sizeof(fhevc_pu_shape_rule) == sizeof(FhevcPuShapeRule), "partition-size rule layout");
+  FhevcPuShapeRule r;   // read here, handed to the kernel by value: the caller's struct is free again when this call returns
+  if (rule) std::memcpy(&r, rule, sizeof r);
+  else { fhevc_pu_shape_rule d; fhevc_pu_shape_rule_default(&d); std::memcpy(&r, &d, sizeof r); }
+  if (const char* bad = fhevc_pu_shape_rule_error(r)) return fail(c, FHEVC_E_INVALID, bad);
+  if ((long long)num_pictures * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "more than 2^31 - 1 CTUs");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
+  const FhevcFrames fr = frames_of(c, nullptr, 1, c->cfg.width, 0, num_pictures, ctu_row_begin, ctu_row_end);
+  return launch_on(c, stream, 13, "fhevc_launch_pu_shape", [&](hipStream_t s) {
+    return fhevc_launch_pu_shape(fr, r, kn(d_nodes), kn(d_pus), kn(d_pus_small), kn(d_shapes), d_costs, c->num_cus, s);
+  });
+}
+
+int fhevc_p_shape_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                        const fhevc_pu_shape_rule* rule, fhevc_pu_shape_node* shapes)
+{
+  const int open = open_host_form(c, cur_luma && ref_luma && shapes, stride_samples, qp, search_range, FHEVC_MOTION_WIDE_MAX_RANGE, "bad partition-size frame arguments");
+  if (open != GO) return open;
+  if (rule)
+    if (const char* bad = fhevc_pu_shape_rule_error(*rule)) return fail(c, FHEVC_E_INVALID, bad);
+  HostForm h(c);
+  const Chain k = claim_chain(h, false);
+  fhevc_pu_shape_node* d_shapes = h.out(c->d_motion, h.bytes(kNodes), shapes, h.bytes(kNodes));
+  return h.run(cur_luma, ref_luma, stride_samples, [&] {
+    const int rc = queue_chain(c, qp, search_range, 0, k);
+    return rc != FHEVC_OK ? rc : fhevc_pu_shape_select_device(c, k.q_nodes, k.q_pus, k.q_small, 1, 0, c->ctus_y, rule, d_shapes, nullptr, c->stream);
+  });
+}
+
+// ---- P-picture depth ranges from the selection's records over a device-resident batch (k_p_tree.hip; the host form: fhevc_host.hip) ----
+// d_merge: null for fhevc_p_tree_select_device; with_merge says which of the two entry points is asking
+static int p_tree_select_on(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, const fhevc_motion_merge_node* d_merge, bool with_merge, int num_pictures, int ctu_row_begin,
+                            int ctu_row_end, const fhevc_p_tree_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!d_shapes || (with_merge && !d_merge) || (!d_depth_min && !d_depth_max && !d_tree)) return fail(c, FHEVC_E_INVALID, "bad tree-decision arguments");
+  // (records have no sample layout: the checks of the pictures' number and the band)
+  if (const char* bad = batch_error(c, 2, c->cfg.width, 0, num_pictures, 1, ctu_row_begin, ctu_row_end, 0, false)) return fail(c, FHEVC_E_INVALID, bad);
+  static_assert(sizeof(fhevc_p_tree_rule) == sizeof(FhevcPTreeRule) && sizeof(fhevc_p_tree_node) == sizeof(FhevcPTreeNode), "tree-decision layouts");
+  FhevcPTreeRule r;   // read here, handed to the kernel by value: the caller's struct is free again when this call returns
+  if (rule) std::memcpy(&r, rule, sizeof r);
+  else std::memset(&r, 0, sizeof r);   // fhevc_p_tree_rule_default
+  if (const char* bad = fhevc_p_tree_rule_error(r)) return fail(c, FHEVC_E_INVALID, bad);
+  if ((long long)num_pictures * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "more than 2^31 - 1 CTUs");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
+  const FhevcFrames fr = frames_of(c, nullptr, 1, c->cfg.width, 0, num_pictures, ctu_row_begin, ctu_row_end);
+  if (with_merge)
+    return launch_on(c, stream, 17, "fhevc_launch_p_tree_merge", [&](hipStream_t s) {
+      return fhevc_launch_p_tree_merge(fr, r, kn(d_shapes), kn(d_merge), d_depth_min, d_depth_max, kn(d_tree), c->num_cus, s);
+    });
+  return launch_on(c, stream, 17, "fhevc_launch_p_tree", [&](hipStream_t s) {
+    return fhevc_launch_p_tree(fr, r, kn(d_shapes), d_depth_min, d_depth_max, kn(d_tree), c->num_cus, s);
+  });
+}
+
+int fhevc_p_tree_select_device(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, int num_pictures, int ctu_row_begin, int ctu_row_end, const fhevc_p_tree_rule* rule,
+                               uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream)
+{
+  return p_tree_select_on(c, d_shapes, nullptr, false, num_pictures, ctu_row_begin, ctu_row_end, rule, d_depth_min, d_depth_max, d_tree, stream);
+}
+
+int fhevc_p_tree_select_merge_device(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, const fhevc_motion_merge_node* d_merge, int num_pictures, int ctu_row_begin,
+                                     int ctu_row_end, const fhevc_p_tree_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream)
+{
+  return p_tree_select_on(c, d_shapes, d_merge, true, num_pictures, ctu_row_begin, ctu_row_end, rule, d_depth_min, d_depth_max, d_tree, stream);
+}
+
+// with_merge: fhevc_p_tree_merge_frame -- the merge stage between refinement and tree
+static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                           const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes,
+                           bool with_merge, fhevc_motion_merge_node* merge)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!cur_luma || !ref_luma || !depth_min || !depth_max || stride_samples < c->cfg.width) return fail(c, FHEVC_E_INVALID, "bad tree-decision frame arguments");
+  if (qp < 0 || qp > 51 || coarse_range < 0 || coarse_range > FHEVC_MOTION_COARSE_MAX_RANGE || search_range < 1 ||
+      search_range > (coarse_range ? FHEVC_MOTION_MAX_RANGE : FHEVC_MOTION_WIDE_MAX_RANGE))
+    return fail(c, FHEVC_E_INVALID, "bad tree-decision frame arguments (around a centre the search covers ranges 1..8, coarse ranges 1..14)");
+  if (shape_rule)
+    if (const char* bad = fhevc_pu_shape_rule_error(*shape_rule)) return fail(c, FHEVC_E_INVALID, bad);
+  if (tree_rule)
+    if (const char* bad = fhevc_p_tree_rule_error(*tree_rule)) return fail(c, FHEVC_E_INVALID, bad);
+  HostForm h(c);
+  const size_t map = (size_t)c->num_ctus * 256, records = h.bytes(kNodes);
+  const Chain k = claim_chain(h, coarse_range != 0);
+  uint8_t *d_min = h.out(c->d_p_maps, 3 * map, depth_min, map, map), *d_max = h.out(c->d_p_maps, 3 * map, depth_max, map, 2 * map);
+  fhevc_pu_shape_node* d_shapes = h.dev<fhevc_pu_shape_node>(c->d_motion, records);
+  fhevc_motion_merge_node* d_merge = h.dev<fhevc_motion_merge_node>(c->d_motion_pu, h.bytes(kPus));
+  h.out(c->d_motion, records, shapes, records);
+  if (with_merge) h.out(c->d_motion_pu, h.bytes(kPus), merge, records);
+  return h.run(cur_luma, ref_luma, stride_samples, [&] {
+    int rc = queue_chain(c, qp, search_range, coarse_range, k);
+    // absolute vectors of the centred chain reach +-64 and neighbouring CTUs have different centres: the merge stage looks around zero at the full range there
+    if (rc == FHEVC_OK && with_merge) rc = on_pair(c, fhevc_motion_merge_device, qp, coarse_range ? FHEVC_MOTION_WIDE_MAX_RANGE : search_range, k.q_nodes, d_merge, c->stream);
+    if (rc == FHEVC_OK) rc = fhevc_pu_shape_select_device(c, k.q_nodes, k.q_pus, k.q_small, 1, 0, c->ctus_y, shape_rule, d_shapes, nullptr, c->stream);
+    return rc != FHEVC_OK ? rc : p_tree_select_on(c, d_shapes, d_merge, with_merge, 1, 0, c->ctus_y, tree_rule, d_min, d_max, nullptr, c->stream);
+  });
+}
+
+int fhevc_p_tree_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                       const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes)
+{
+  return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, false, nullptr);
+}
+
+int fhevc_p_tree_merge_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                             const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes,
+                             fhevc_motion_merge_node* merge)
+{
+  return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge);
+}
+
+}  // extern "C"
