@@ -42,6 +42,7 @@ SYMBOLS = [
     "fhevc_motion_refine_pu_centred", "fhevc_motion_refine_pu_centred_device",
     "fhevc_p_tree_rule_default", "fhevc_p_tree_select", "fhevc_p_tree_select_device", "fhevc_p_tree_frame",
     "fhevc_motion_merge", "fhevc_motion_merge_device", "fhevc_p_tree_select_merge", "fhevc_p_tree_select_merge_device", "fhevc_p_tree_merge_frame",
+    "fhevc_motion_merge_pu", "fhevc_motion_merge_pu_device", "fhevc_pu_shape_select_merge", "fhevc_pu_shape_select_merge_device", "fhevc_p_tree_merge_pu_frame",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -235,6 +236,11 @@ def load_library(path=None):
     lib.fhevc_p_tree_select_merge.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp]
     lib.fhevc_p_tree_select_merge_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp, vp]
     lib.fhevc_p_tree_merge_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), vp, vp, vp, vp]
+    lib.fhevc_motion_merge_pu.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.fhevc_motion_merge_pu_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.fhevc_pu_shape_select_merge.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(PuShapeRule), vp, vp, vp]
+    lib.fhevc_pu_shape_select_merge_device.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), vp, vp, vp, vp]
+    lib.fhevc_p_tree_merge_pu_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), vp, vp, vp, vp]
     lib.fhevc_predict_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, vp, vp]
     lib.fhevc_alloc_host.argtypes = [vp, C.c_size_t]
     lib.fhevc_alloc_host.restype = vp
@@ -367,6 +373,29 @@ def pu_shape_select(nodes, pus, pus_small, width, height, rule=None, with_costs=
         if rc != OK:
             raise FastHevcError(rc, "fhevc_pu_shape_select")
     return (out, costs) if with_costs else out
+
+
+def pu_shape_select_merge(nodes, pus, pus_small, merge_pus, merge_pus_small, width, height, rule=None, with_costs=False):
+    """pu_shape_select with the PUs' merge records [numCtus, 124] and [numCtus, 384] or None (MOTION_MERGE_DTYPE; only cost_best is read) beside the refined
+    entries: a part costs the smaller of the two -> (records, merged [numCtus, 85] uint16), with_costs: (records, costs, merged)"""
+    lib = load_library()
+    rule = rule if rule is not None else pu_shape_rule_default()
+    cont = lambda a: None if a is None else np.ascontiguousarray(a)
+    nodes, pus, small, mpus, msmall = cont(nodes), cont(pus), cont(pus_small), cont(merge_pus), cont(merge_pus_small)
+    assert all(a is None or a.dtype.itemsize == 16 for a in (nodes, pus, small, mpus, msmall))
+    at = lambda a, c: None if a is None else a[c].ctypes.data
+    cw = (width + 63) // 64
+    n = nodes.shape[0]
+    out = np.zeros((n, NODES_PER_CTU), SHAPE_DTYPE)
+    costs = np.zeros((n, NODES_PER_CTU, 8), np.uint32) if with_costs else None
+    merged = np.zeros((n, NODES_PER_CTU), np.uint16)
+    for c in range(n):
+        vw, vh = min(64, width - (c % cw) * 64), min(64, height - (c // cw) * 64)
+        rc = lib.fhevc_pu_shape_select_merge(nodes[c].ctypes.data, pus[c].ctypes.data, at(small, c), at(mpus, c), at(msmall, c), vw, vh, C.byref(rule),
+                                             out[c].ctypes.data, at(costs, c), merged[c].ctypes.data)
+        if rc != OK:
+            raise FastHevcError(rc, "fhevc_pu_shape_select_merge")
+    return (out, costs, merged) if with_costs else (out, merged)
 
 
 def p_depth_range(nodes, prev_depth, width, height, qp, rule=None):
@@ -619,6 +648,26 @@ class Context:
         self._check(self.lib.fhevc_motion_merge_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range,
                                                        d_refined, d_out, stream))
 
+    def motion_merge_pu(self, cur_plane, ref_plane, refined, origin=0, stride=None, qp=32, max_range=4, with_pus=True, with_small=True):
+        """config 4: the cheapest merge candidate of every PU from the refined square nodes [numCtus, 85] (MOTION_QPEL_DTYPE; only cost_best, mvx, mvy are
+        read) -> ([numCtus, 124], [numCtus, 384]) MOTION_MERGE_DTYPE in the orders of motion_pu_index / motion_pu_small_index; None for a family not asked for"""
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
+        refined = np.ascontiguousarray(refined).reshape(-1)
+        assert refined.dtype.itemsize == 16 and refined.size == self.num_ctus * NODES_PER_CTU
+        pus = np.zeros((self.num_ctus, PUS_PER_CTU), MOTION_MERGE_DTYPE) if with_pus else None
+        small = np.zeros((self.num_ctus, PUS_SMALL_PER_CTU), MOTION_MERGE_DTYPE) if with_small else None
+        self._check(self.lib.fhevc_motion_merge_pu(self.h, cur, ref, stride, qp, max_range, refined.ctypes.data, pus.ctypes.data if with_pus else None,
+                                                   small.ctypes.data if with_small else None))
+        return pus, small
+
+    def motion_merge_pu_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_refined, d_out_pus, d_out_pus_small, rows=None, stream=None, qp=32,
+                               max_range=4):
+        """motion_merge_device per PU: d_refined as there (85 refined nodes per CTU); d_out_pus: (num_frames - 1) * band CTUs * 124 merge records,
+        d_out_pus_small: ... * 384; either may be None, not both.  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_motion_merge_pu_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range,
+                                                          d_refined, d_out_pus, d_out_pus_small, stream))
+
     def motion_search_pu(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=4, with_nodes=False):
         """config 4: the search of motion_search for the rectangular PUs -> [numCtus, 124] MOTION_DTYPE in the order of motion_pu_index; with_nodes:
         (nodes [numCtus, 85], pus), the nodes as motion_search returns them, from the same pass.  search_range 1..8."""
@@ -786,6 +835,14 @@ class Context:
         self._check(self.lib.fhevc_pu_shape_select_device(self.h, d_nodes, d_pus, d_pus_small, num_pictures, rb, re, C.byref(rule) if rule is not None else None,
                                                           d_shapes, d_costs, stream))
 
+    def pu_shape_select_merge_device(self, d_nodes, d_pus, d_pus_small, d_merge_pus, d_merge_pus_small, num_pictures, d_shapes, d_costs=None, d_merged=None, rows=None,
+                                     stream=None, rule=None):
+        """pu_shape_select_device with the merge records of motion_merge_pu_device beside the refined PUs (124 / 384 per CTU, compact over the same rows;
+        d_merge_pus_small may be None); d_merged (optional): num_pictures * band CTUs * 85 uint16.  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_pu_shape_select_merge_device(self.h, d_nodes, d_pus, d_pus_small, d_merge_pus, d_merge_pus_small, num_pictures, rb, re,
+                                                                C.byref(rule) if rule is not None else None, d_shapes, d_costs, d_merged, stream))
+
     def p_shape_frame(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=64, rule=None):
         """config 4, one picture pair from host buffers: the wide SAD search of all three families, their quarter-sample refinement and the partition-size
         selection on the device -> [numCtus, 85] SHAPE_DTYPE; only the records come back."""
@@ -809,18 +866,27 @@ class Context:
         self._check(self.lib.fhevc_p_tree_select_merge_device(self.h, d_shapes, d_merge, num_pictures, rb, re, C.byref(rule) if rule is not None else None,
                                                               d_depth_min, d_depth_max, d_tree, stream))
 
+    def p_tree_merge_pu_frame(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=8, coarse_range=0, shape_rule=None, tree_rule=None,
+                              with_shapes=False, with_merge=False):
+        """p_tree_merge_frame with the merge stage per PU behind the one per node, and the selection on merge-aware costs; the same results"""
+        return self._p_tree_merge_frame(self.lib.fhevc_p_tree_merge_pu_frame, cur_plane, ref_plane, origin, stride, qp, search_range, coarse_range, shape_rule,
+                                        tree_rule, with_shapes, with_merge)
+
     def p_tree_merge_frame(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=8, coarse_range=0, shape_rule=None, tree_rule=None,
                            with_shapes=False, with_merge=False):
         """p_tree_frame with the merge stage between refinement and tree -> (depth_min, depth_max) [numCtus, 256], then the records [numCtus, 85] SHAPE_DTYPE
         (with_shapes) and [numCtus, 85] MOTION_MERGE_DTYPE (with_merge)"""
+        return self._p_tree_merge_frame(self.lib.fhevc_p_tree_merge_frame, cur_plane, ref_plane, origin, stride, qp, search_range, coarse_range, shape_rule, tree_rule,
+                                        with_shapes, with_merge)
+
+    def _p_tree_merge_frame(self, entry, cur_plane, ref_plane, origin, stride, qp, search_range, coarse_range, shape_rule, tree_rule, with_shapes, with_merge):
         cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
         dmin, dmax = np.zeros(self.num_ctus * 256, np.uint8), np.zeros(self.num_ctus * 256, np.uint8)
         shapes = np.zeros(self.num_ctus * NODES_PER_CTU, SHAPE_DTYPE) if with_shapes else None
         merge = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_MERGE_DTYPE) if with_merge else None
-        self._check(self.lib.fhevc_p_tree_merge_frame(self.h, cur, ref, stride, qp, search_range, coarse_range,
-                                                      C.byref(shape_rule) if shape_rule is not None else None, C.byref(tree_rule) if tree_rule is not None else None,
-                                                      dmin.ctypes.data, dmax.ctypes.data, shapes.ctypes.data if with_shapes else None,
-                                                      merge.ctypes.data if with_merge else None))
+        self._check(entry(self.h, cur, ref, stride, qp, search_range, coarse_range, C.byref(shape_rule) if shape_rule is not None else None,
+                          C.byref(tree_rule) if tree_rule is not None else None, dmin.ctypes.data, dmax.ctypes.data, shapes.ctypes.data if with_shapes else None,
+                          merge.ctypes.data if with_merge else None))
         out = (dmin.reshape(self.num_ctus, 256), dmax.reshape(self.num_ctus, 256))
         out += (shapes.reshape(self.num_ctus, NODES_PER_CTU),) if with_shapes else ()
         return out + ((merge.reshape(self.num_ctus, NODES_PER_CTU),) if with_merge else ())

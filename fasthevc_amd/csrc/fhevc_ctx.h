@@ -50,13 +50,14 @@ struct fhevc_ctx {
   bool timing = false;
   std::vector<TimedLaunch> pending;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-  // per timing slot (14, 16 and 18 are not in use); config 4's slots and its staging buffers d_pair .. d_p_maps: the tables in fhevc_motion_api.hip
-  double sum_ms[20] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-  uint64_t launches[20] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+  // per timing slot (14, 16, 18 and 20 are not in use); config 4's slots and its staging buffers d_pair .. d_p_maps: the tables in fhevc_motion_api.hip
+  double sum_ms[22] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+  uint64_t launches[22] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
   double* d_act = nullptr;
   int16_t* d_pair = nullptr;
   FhevcMotionNode *d_motion = nullptr, *d_motion_pu = nullptr, *d_motion_pu_small = nullptr, *d_centres = nullptr;
   FhevcMotionQpelNode *d_qpel = nullptr, *d_qpel_pu = nullptr, *d_qpel_pu_small = nullptr;
+  FhevcMotionMergeNode* d_merge_pu = nullptr;
   uint8_t* d_p_maps = nullptr;
   FhevcNodeCost* d_cand_all = nullptr; uint8_t* d_cand = nullptr;   // fhevc_intra_first_pass_candidates: every (node, mode) cost, the lists
   FhevcNodeCost* d_best4 = nullptr; uint8_t* d_modes4 = nullptr;    // fhevc_intra_first_pass_4x4: the best mode and the list of every 4x4 PU

@@ -253,8 +253,11 @@ void fhevc_pu_shape_rule_default(fhevc_pu_shape_rule* rule)
   rule->amp_mode = 1;
 }
 
-int fhevc_pu_shape_select(const fhevc_motion_qpel_node* nodes, const fhevc_motion_qpel_node* pus, const fhevc_motion_qpel_node* pus_small, int valid_w,
-                          int valid_h, const fhevc_pu_shape_rule* rule, fhevc_pu_shape_node* out, uint32_t* costs)
+// merge_pus: null for fhevc_pu_shape_select; otherwise the merge records of the 124 PUs and (or null: all markers) of the 384, of which cost_best is read: a part
+// costs the smaller of its refined and its merge cost (a null pus_small: all markers too), and merged (or null) says per node for which parts that is the merge cost
+static int pu_shape_select(const fhevc_motion_qpel_node* nodes, const fhevc_motion_qpel_node* pus, const fhevc_motion_qpel_node* pus_small,
+                           const fhevc_motion_merge_node* merge_pus, const fhevc_motion_merge_node* merge_small, int valid_w, int valid_h, const fhevc_pu_shape_rule* rule,
+                           fhevc_pu_shape_node* out, uint32_t* costs, uint16_t* merged)
 {
   if (!nodes || !pus || !rule || !out || valid_w < 8 || valid_w > 64 || valid_h < 8 || valid_h > 64 || fhevc_pu_shape_rule_error(*rule)) return FHEVC_E_INVALID;
   const uint32_t none = 0xFFFFFFFFu;
@@ -265,6 +268,7 @@ int fhevc_pu_shape_select(const fhevc_motion_qpel_node* nodes, const fhevc_motio
     const bool valid = nx * size + size <= valid_w && ny * size + size <= valid_h;
     uint32_t cost[8];
     for (int p = 0; p < 8; ++p) cost[p] = none;
+    unsigned bits = 0;
     if (valid) {
       cost[0] = nodes[k].cost_best;
       for (int p = 1; p < 8; ++p) {
@@ -272,15 +276,21 @@ int fhevc_pu_shape_select(const fhevc_motion_qpel_node* nodes, const fhevc_motio
         const int shape = p < 3 ? p - 1 : p - 2;
         // the two parts: in pus where fhevc_motion_pu_index covers the combination, otherwise in pus_small where fhevc_motion_pu_small_index does
         const fhevc_motion_qpel_node* src = pus;
+        const fhevc_motion_merge_node* msrc = merge_pus;
         int e0 = fhevc_motion_pu_index(k, shape, 0);
-        if (e0 < 0) { src = pus_small; e0 = fhevc_motion_pu_small_index(k, shape, 0); }
-        if (e0 < 0 || !src) continue;
-        const uint32_t a = src[e0].cost_best, b = src[e0 + 1].cost_best;   // part 1 follows part 0 in both orders
+        if (e0 < 0) { src = pus_small; msrc = merge_small; e0 = fhevc_motion_pu_small_index(k, shape, 0); }
+        if (e0 < 0 || (!src && !msrc)) continue;
+        uint32_t a = src ? src[e0].cost_best : none, b = src ? src[e0 + 1].cost_best : none;   // part 1 follows part 0 in both orders
+        if (msrc) {   // uiMRGCost < uiMECost (TEncSearch.cpp:3373): the marker is the largest value, so it never wins
+          if (msrc[e0].cost_best < a) { a = msrc[e0].cost_best; bits |= 1u << (2 * p); }
+          if (msrc[e0 + 1].cost_best < b) { b = msrc[e0 + 1].cost_best; bits |= 2u << (2 * p); }
+        }
         if (a == none || b == none) continue;
         cost[p] = (uint32_t)std::min<uint64_t>((uint64_t)a + b, 0xFFFFFFFEu);
       }
     }
     if (costs) std::memcpy(costs + k * 8, cost, sizeof cost);
+    if (merged) merged[k] = (uint16_t)bits;
     fhevc_pu_shape_node& o = out[k];
     o.cost_2Nx2N = cost[0]; o.cost_best = o.cost_second = none;
     o.best = o.second = 255; o.mask = o.avail = 0;
@@ -314,6 +324,20 @@ int fhevc_pu_shape_select(const fhevc_motion_qpel_node* nodes, const fhevc_motio
     o.mask = (uint8_t)mask;
   }
   return FHEVC_OK;
+}
+
+int fhevc_pu_shape_select(const fhevc_motion_qpel_node* nodes, const fhevc_motion_qpel_node* pus, const fhevc_motion_qpel_node* pus_small, int valid_w,
+                          int valid_h, const fhevc_pu_shape_rule* rule, fhevc_pu_shape_node* out, uint32_t* costs)
+{
+  return pu_shape_select(nodes, pus, pus_small, nullptr, nullptr, valid_w, valid_h, rule, out, costs, nullptr);
+}
+
+int fhevc_pu_shape_select_merge(const fhevc_motion_qpel_node* nodes, const fhevc_motion_qpel_node* pus, const fhevc_motion_qpel_node* pus_small,
+                                const fhevc_motion_merge_node* merge_pus, const fhevc_motion_merge_node* merge_pus_small, int valid_w, int valid_h,
+                                const fhevc_pu_shape_rule* rule, fhevc_pu_shape_node* out, uint32_t* costs, uint16_t* merged)
+{
+  if (!merge_pus) return FHEVC_E_INVALID;
+  return pu_shape_select(nodes, pus, pus_small, merge_pus, merge_pus_small, valid_w, valid_h, rule, out, costs, merged);
 }
 
 // ---- P-picture depth ranges from the selection's records, bottom-up over the quad-tree (spec in include/fasthevc.h; the device form is k_p_tree.hip) ----

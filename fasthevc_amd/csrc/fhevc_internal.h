@@ -237,6 +237,11 @@ struct FhevcMotionMergeNode { uint32_t satd_best, cost_best; int16_t mvx, mvy; u
 hipError_t fhevc_launch_motion_merge(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionQpelNode* d_refined, FhevcMotionMergeNode* d_out,
                                      int num_cus, hipStream_t stream);
 
+// ... per PU (k_motion_merge_pu.hip): the same input; d_out_pus: ... * 124 records in the order of fhevc_motion_pu_index, d_out_small: ... * 384 in the order of
+// fhevc_motion_pu_small_index; either may be null, not both
+hipError_t fhevc_launch_motion_merge_pu(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionQpelNode* d_refined,
+                                        FhevcMotionMergeNode* d_out_pus, FhevcMotionMergeNode* d_out_small, int num_cus, hipStream_t stream);
+
 // ---- ... and of the PUs' vectors (k_motion_refine_pu.hip; config 4) --------------------------------------------------
 // fr, max_range (1 .. FHEVC_MOTION_WIDE_MAX_RANGE: up to FHEVC_MOTION_MAX_RANGE the MR = 8 layout, above it the MR = 64 layout with its window in dynamic LDS),
 // cost as fhevc_launch_motion_refine; d_pus / d_out_pus: (num_frames - 1) * band CTUs * 124 entries in the order of fhevc_motion_pu_index, d_pus_small /
@@ -298,6 +303,11 @@ struct FhevcPuShapeNode { uint32_t cost_2Nx2N, cost_best, cost_second; uint8_t b
 // 384 refined entries; d_shapes: num_frames * band CTUs * 85; d_costs (may be null): ... * 85 * 8 dwords; all compact over the band
 hipError_t fhevc_launch_pu_shape(const FhevcFrames& fr, const FhevcPuShapeRule& rule, const FhevcMotionQpelNode* d_nodes, const FhevcMotionQpelNode* d_pus,
                                  const FhevcMotionQpelNode* d_pus_small, FhevcPuShapeNode* d_shapes, uint32_t* d_costs, int num_cus, hipStream_t stream);
+// ... with the merge records of fhevc_launch_motion_merge_pu beside the refined PUs (d_merge_pus never null; d_merge_small may be null: all markers): a part
+// costs the smaller of the two; d_merged (may be null): ... * 85 uint16_t, bit 2p + part set iff that part's merge cost is strictly the smaller one
+hipError_t fhevc_launch_pu_shape_merge(const FhevcFrames& fr, const FhevcPuShapeRule& rule, const FhevcMotionQpelNode* d_nodes, const FhevcMotionQpelNode* d_pus,
+                                       const FhevcMotionQpelNode* d_pus_small, const FhevcMotionMergeNode* d_merge_pus, const FhevcMotionMergeNode* d_merge_small,
+                                       FhevcPuShapeNode* d_shapes, uint32_t* d_costs, uint16_t* d_merged, int num_cus, hipStream_t stream);
 
 // ---- P-picture depth ranges from the selection's records, bottom-up over the quad-tree (k_p_tree.hip; config 4) ------------------------------------
 // fhevc_p_tree_rule of fasthevc.h; travels by value as a kernel argument, so every launch has its own rule

@@ -97,10 +97,13 @@ int device_form(fhevc_ctx* c, bool args_ok, const char* bad_args, const Batch& b
 //   d_motion_pu_small,       384 (small PUs)   the integer and the refined small PUs
 //   d_qpel_pu_small
 //   d_centres                1                 the centres that the centred searches and refinements read
+//   d_merge_pu               508 (all PUs)     the PUs' merge records: the 124 in fhevc_motion_pu_index order, behind them the 384 (fhevc_motion_merge_pu,
+//                                              fhevc_p_tree_merge_pu_frame) -- 8 128 B per CTU; no dead buffer of the chain holds that much
 //   d_p_maps                 3 x 256 bytes     the reference picture's depth map, depth_min, depth_max (fhevc_p_predict_frame; the tree chains use the last two)
 //
 // The timing slots (fhevc_kernel_timing) of the launches below: 4 fhevc_motion_search, 5 the P rule, 7 fhevc_motion_refine, 8 / 9 the searches of the PUs / the
-// small PUs, 10 fhevc_motion_refine_pu, 11 / 12 the wide search / refinement, 13 the partition sizes, 15 the centres and everything centred, 17 the tree, 19 the merge stage
+// small PUs, 10 fhevc_motion_refine_pu, 11 / 12 the wide search / refinement, 13 the partition sizes, 15 the centres and everything centred, 17 the tree, 19 the merge stage,
+// 21 the merge stage per PU
 struct Family { int per_ctu; FhevcMotionNode* fhevc_ctx::*found; FhevcMotionQpelNode* fhevc_ctx::*refined; };
 constexpr Family kNodes = { FHEVC_NODES, &fhevc_ctx::d_motion, &fhevc_ctx::d_qpel }, kPus = { FHEVC_PUS, &fhevc_ctx::d_motion_pu, &fhevc_ctx::d_qpel_pu },
                  kSmall = { FHEVC_PUS_SMALL, &fhevc_ctx::d_motion_pu_small, &fhevc_ctx::d_qpel_pu_small }, kCentres = { 1, &fhevc_ctx::d_centres, nullptr };
@@ -464,6 +467,35 @@ int fhevc_motion_merge(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref
   return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_merge_device, qp, max_range, d_refined, d_out, c->stream); });
 }
 
+// ---- merge-candidate costs per PU from the refined nodes (k_motion_merge_pu.hip) ----
+
+int fhevc_motion_merge_pu_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                 int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_qpel_node* d_refined,
+                                 fhevc_motion_merge_node* d_out_pus, fhevc_motion_merge_node* d_out_pus_small, void* stream)
+{
+  const Batch b{ d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp };
+  // either family may be null, not both
+  return device_form(c, d_luma && d_refined && (d_out_pus || d_out_pus_small), "bad PU merge-stage arguments", b, max_range, FHEVC_MOTION_WIDE_MAX_RANGE,
+                     "bad PU merge-stage arguments (max_range 1..64)", stream, 21, "fhevc_launch_motion_merge_pu", [&](const FhevcFrames& fr, hipStream_t s) {
+    return fhevc_launch_motion_merge_pu(fr, max_range, mv_bit_cost_table(qp), kn(d_refined), kn(d_out_pus), kn(d_out_pus_small), c->num_cus, s);
+  }, [&]() -> const char* {
+    return (long long)(num_frames - 1) * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL ? "more than 2^31 - 1 CTUs" : nullptr;
+  });
+}
+
+int fhevc_motion_merge_pu(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                          const fhevc_motion_qpel_node* refined, fhevc_motion_merge_node* out_pus, fhevc_motion_merge_node* out_pus_small)
+{
+  const int rc = open_host_form(c, cur_luma && ref_luma && refined && (out_pus || out_pus_small), stride_samples, qp, max_range, FHEVC_MOTION_WIDE_MAX_RANGE,
+                                "bad PU merge-stage arguments");
+  if (rc != GO) return rc;
+  HostForm h(c);
+  const size_t all = h.bytes(kPus) + h.bytes(kSmall);
+  const fhevc_motion_qpel_node* d_refined = h.in(c->d_qpel, h.bytes(kNodes), refined, h.bytes(kNodes));
+  fhevc_motion_merge_node *d_pus = h.out(c->d_merge_pu, all, out_pus, h.bytes(kPus)), *d_small = h.out(c->d_merge_pu, all, out_pus_small, h.bytes(kSmall), h.bytes(kPus));
+  return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_merge_pu_device, qp, max_range, d_refined, d_pus, d_small, c->stream); });
+}
+
 // ---- quarter-sample refinement of the PUs' vectors (k_motion_refine_pu.hip) ----
 
 int fhevc_motion_refine_pu_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
@@ -630,12 +662,14 @@ int fhevc_p_predict_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* 
 }
 
 // ---- partition sizes per CU from the refined PU costs over a device-resident batch (k_pu_shape.hip; the host form: fhevc_host.hip) ----
-int fhevc_pu_shape_select_device(fhevc_ctx* c, const fhevc_motion_qpel_node* d_nodes, const fhevc_motion_qpel_node* d_pus, const fhevc_motion_qpel_node* d_pus_small,
-                                 int num_pictures, int ctu_row_begin, int ctu_row_end, const fhevc_pu_shape_rule* rule, fhevc_pu_shape_node* d_shapes,
-                                 uint32_t* d_costs, void* stream)
+// d_merge_pus: null for fhevc_pu_shape_select_device; with_merge says which of the two entry points is asking
+static int pu_shape_select_on(fhevc_ctx* c, const fhevc_motion_qpel_node* d_nodes, const fhevc_motion_qpel_node* d_pus, const fhevc_motion_qpel_node* d_pus_small,
+                              const fhevc_motion_merge_node* d_merge_pus, const fhevc_motion_merge_node* d_merge_pus_small, bool with_merge, int num_pictures,
+                              int ctu_row_begin, int ctu_row_end, const fhevc_pu_shape_rule* rule, fhevc_pu_shape_node* d_shapes, uint32_t* d_costs, uint16_t* d_merged,
+                              void* stream)
 {
   if (!c) return FHEVC_E_INVALID;
-  if (!d_nodes || !d_pus || !d_shapes) return fail(c, FHEVC_E_INVALID, "bad partition-size selection arguments");
+  if (!d_nodes || !d_pus || !d_shapes || (with_merge && !d_merge_pus)) return fail(c, FHEVC_E_INVALID, "bad partition-size selection arguments");
   // (refined entries have no sample layout: the checks of the pictures' number and the band)
   if (const char* bad = batch_error(c, 2, c->cfg.width, 0, num_pictures, 1, ctu_row_begin, ctu_row_end, 0, false)) return fail(c, FHEVC_E_INVALID, bad);
   static_assert(sizeof(fhevc_pu_shape_rule) == sizeof(FhevcPuShapeRule), "partition-size rule layout");
@@ -646,9 +680,28 @@ int fhevc_pu_shape_select_device(fhevc_ctx* c, const fhevc_motion_qpel_node* d_n
   if ((long long)num_pictures * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "more than 2^31 - 1 CTUs");
   if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
   const FhevcFrames fr = frames_of(c, nullptr, 1, c->cfg.width, 0, num_pictures, ctu_row_begin, ctu_row_end);
+  if (with_merge)
+    return launch_on(c, stream, 13, "fhevc_launch_pu_shape_merge", [&](hipStream_t s) {
+      return fhevc_launch_pu_shape_merge(fr, r, kn(d_nodes), kn(d_pus), kn(d_pus_small), kn(d_merge_pus), kn(d_merge_pus_small), kn(d_shapes), d_costs, d_merged, c->num_cus, s);
+    });
   return launch_on(c, stream, 13, "fhevc_launch_pu_shape", [&](hipStream_t s) {
     return fhevc_launch_pu_shape(fr, r, kn(d_nodes), kn(d_pus), kn(d_pus_small), kn(d_shapes), d_costs, c->num_cus, s);
   });
+}
+
+int fhevc_pu_shape_select_device(fhevc_ctx* c, const fhevc_motion_qpel_node* d_nodes, const fhevc_motion_qpel_node* d_pus, const fhevc_motion_qpel_node* d_pus_small,
+                                 int num_pictures, int ctu_row_begin, int ctu_row_end, const fhevc_pu_shape_rule* rule, fhevc_pu_shape_node* d_shapes,
+                                 uint32_t* d_costs, void* stream)
+{
+  return pu_shape_select_on(c, d_nodes, d_pus, d_pus_small, nullptr, nullptr, false, num_pictures, ctu_row_begin, ctu_row_end, rule, d_shapes, d_costs, nullptr, stream);
+}
+
+int fhevc_pu_shape_select_merge_device(fhevc_ctx* c, const fhevc_motion_qpel_node* d_nodes, const fhevc_motion_qpel_node* d_pus, const fhevc_motion_qpel_node* d_pus_small,
+                                       const fhevc_motion_merge_node* d_merge_pus, const fhevc_motion_merge_node* d_merge_pus_small, int num_pictures, int ctu_row_begin,
+                                       int ctu_row_end, const fhevc_pu_shape_rule* rule, fhevc_pu_shape_node* d_shapes, uint32_t* d_costs, uint16_t* d_merged, void* stream)
+{
+  return pu_shape_select_on(c, d_nodes, d_pus, d_pus_small, d_merge_pus, d_merge_pus_small, true, num_pictures, ctu_row_begin, ctu_row_end, rule, d_shapes, d_costs, d_merged,
+                            stream);
 }
 
 int fhevc_p_shape_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
@@ -705,10 +758,11 @@ int fhevc_p_tree_select_merge_device(fhevc_ctx* c, const fhevc_pu_shape_node* d_
   return p_tree_select_on(c, d_shapes, d_merge, true, num_pictures, ctu_row_begin, ctu_row_end, rule, d_depth_min, d_depth_max, d_tree, stream);
 }
 
-// with_merge: fhevc_p_tree_merge_frame -- the merge stage between refinement and tree
+// with_merge: fhevc_p_tree_merge_frame -- the merge stage between refinement and tree; with_merge_pu: fhevc_p_tree_merge_pu_frame -- behind it the merge stage
+// per PU, and the selection that takes its costs
 static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
                            const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes,
-                           bool with_merge, fhevc_motion_merge_node* merge)
+                           bool with_merge, fhevc_motion_merge_node* merge, bool with_merge_pu = false)
 {
   if (!c) return FHEVC_E_INVALID;
   if (!cur_luma || !ref_luma || !depth_min || !depth_max || stride_samples < c->cfg.width) return fail(c, FHEVC_E_INVALID, "bad tree-decision frame arguments");
@@ -727,11 +781,20 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
   fhevc_motion_merge_node* d_merge = h.dev<fhevc_motion_merge_node>(c->d_motion_pu, h.bytes(kPus));
   h.out(c->d_motion, records, shapes, records);
   if (with_merge) h.out(c->d_motion_pu, h.bytes(kPus), merge, records);
+  fhevc_motion_merge_node *d_merge_pus = nullptr, *d_merge_small = nullptr;
+  if (with_merge_pu) {
+    d_merge_pus = h.dev<fhevc_motion_merge_node>(c->d_merge_pu, h.bytes(kPus) + h.bytes(kSmall));
+    d_merge_small = h.dev<fhevc_motion_merge_node>(c->d_merge_pu, h.bytes(kPus) + h.bytes(kSmall), h.bytes(kPus));
+  }
   return h.run(cur_luma, ref_luma, stride_samples, [&] {
     int rc = queue_chain(c, qp, search_range, coarse_range, k);
-    // absolute vectors of the centred chain reach +-64 and neighbouring CTUs have different centres: the merge stage looks around zero at the full range there
-    if (rc == FHEVC_OK && with_merge) rc = on_pair(c, fhevc_motion_merge_device, qp, coarse_range ? FHEVC_MOTION_WIDE_MAX_RANGE : search_range, k.q_nodes, d_merge, c->stream);
-    if (rc == FHEVC_OK) rc = fhevc_pu_shape_select_device(c, k.q_nodes, k.q_pus, k.q_small, 1, 0, c->ctus_y, shape_rule, d_shapes, nullptr, c->stream);
+    // absolute vectors of the centred chain reach +-64 and neighbouring CTUs have different centres: the merge stages look around zero at the full range there
+    const int merge_range = coarse_range ? FHEVC_MOTION_WIDE_MAX_RANGE : search_range;
+    if (rc == FHEVC_OK && with_merge) rc = on_pair(c, fhevc_motion_merge_device, qp, merge_range, k.q_nodes, d_merge, c->stream);
+    if (rc == FHEVC_OK && with_merge_pu) rc = on_pair(c, fhevc_motion_merge_pu_device, qp, merge_range, k.q_nodes, d_merge_pus, d_merge_small, c->stream);
+    if (rc == FHEVC_OK && with_merge_pu)
+      rc = fhevc_pu_shape_select_merge_device(c, k.q_nodes, k.q_pus, k.q_small, d_merge_pus, d_merge_small, 1, 0, c->ctus_y, shape_rule, d_shapes, nullptr, nullptr, c->stream);
+    else if (rc == FHEVC_OK) rc = fhevc_pu_shape_select_device(c, k.q_nodes, k.q_pus, k.q_small, 1, 0, c->ctus_y, shape_rule, d_shapes, nullptr, c->stream);
     return rc != FHEVC_OK ? rc : p_tree_select_on(c, d_shapes, d_merge, with_merge, 1, 0, c->ctus_y, tree_rule, d_min, d_max, nullptr, c->stream);
   });
 }
@@ -747,6 +810,13 @@ int fhevc_p_tree_merge_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_
                              fhevc_motion_merge_node* merge)
 {
   return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge);
+}
+
+int fhevc_p_tree_merge_pu_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                                const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes,
+                                fhevc_motion_merge_node* merge)
+{
+  return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge, true);
 }
 
 }  // extern "C"

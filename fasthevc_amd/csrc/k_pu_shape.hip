@@ -13,6 +13,10 @@
 //     depends on the node number alone -- never on what the entries hold --, so every LDS read stays inside the image for any input;
 //   * a record leaves as one 16-byte store, the eight costs as two, where both output pointers are 16-byte aligned; as dwords otherwise.
 // The rule (36 bytes) and the geometry are kernel arguments: two launches with different rules never share state (no per-context table).
+//
+// The merge form (fhevc_pu_shape_select_merge_device): two further instantiations that also get the PUs' merge records (k_motion_merge_pu.hip) and park, per
+// PU entry, the SMALLER of the refined cost_best and the merge cost_best (dword 1 of a merge record) -- HM's uiMRGCost < uiMECost -- and one flag byte that says
+// which it was: 8 128 B more read per CTU, 2 048 B more LDS, and optionally 170 B of "merged" bits written.  Everything behind the image is the same code.
 #include "../../include/fasthevc.h"   // FHEVC_PART_*
 #include "fhevc_internal.h"
 
@@ -42,6 +46,24 @@ __device__ __forceinline__ void park_costs(uint32_t* dst, const uint32_t* __rest
     if (lane + 64 * r < COUNT) dst[lane + 64 * r] = v[r];
 }
 
+// the merge variant's: per entry the smaller of the refined entry's cost_best (dword 2; src null: the marker) and of its merge record's (dword 1; merge null:
+// the marker) into dst, and into flg whether the merge cost is strictly the smaller one
+template <int COUNT>
+__device__ __forceinline__ void park_min_costs(uint32_t* dst, uint8_t* flg, const uint32_t* __restrict__ src, const uint32_t* __restrict__ merge, int lane)
+{
+  constexpr int ROUNDS = (COUNT + 63) / 64;
+  uint32_t a[ROUNDS], m[ROUNDS];
+#pragma unroll
+  for (int r = 0; r < ROUNDS; ++r) {
+    const int e = min(lane + 64 * r, COUNT - 1);
+    a[r] = src ? src[4 * e + 2] : kNone;
+    m[r] = merge ? merge[4 * e + 1] : kNone;
+  }
+#pragma unroll
+  for (int r = 0; r < ROUNDS; ++r)
+    if (lane + 64 * r < COUNT) { dst[lane + 64 * r] = min(a[r], m[r]); flg[lane + 64 * r] = m[r] < a[r] ? 1 : 0; }
+}
+
 // the sum of a shape's two parts: unavailable if either is, otherwise saturated below the marker
 __device__ __forceinline__ uint32_t pair_cost(const uint32_t* img, int e0)
 {
@@ -50,14 +72,27 @@ __device__ __forceinline__ uint32_t pair_cost(const uint32_t* img, int e0)
   return a == kNone || b == kNone ? kNone : (s > 0xFFFFFFFEull ? 0xFFFFFFFEu : (uint32_t)s);
 }
 
+// what the merge variant gets beside the plain form's arguments: the merge records of the 124 and of the 384 PUs (small may be null), and where the
+// "merged" bits go (may be null)
+struct PuShapeMerge { const uint32_t *pus, *small; uint16_t* merged; };
+
 // WIDE: both output pointers are 16-byte aligned (16-byte stores; otherwise dwords)
-template <bool WIDE>
+// M... (fhevc_pu_shape_select_merge_device): empty, or ONE PuShapeMerge -- a part then costs the smaller of its refined cost and its merge cost (HM's uiMRGCost <
+// uiMECost, TEncSearch.cpp:3373).  A pack keeps the plain instantiations' argument list, and so their code, what it was
+template <bool WIDE, class... M>
 __global__ __launch_bounds__(256) void fhevc_pu_shape_kernel(PuShapeGeom G, FhevcPuShapeRule R, const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ pus,
-                                                             const uint32_t* __restrict__ pus_small, uint32_t* __restrict__ shapes, uint32_t* __restrict__ costs)
+                                                             const uint32_t* __restrict__ pus_small, uint32_t* __restrict__ shapes, uint32_t* __restrict__ costs,
+                                                             M... merge_arg)
 {
+  constexpr bool MERGE = sizeof...(M) != 0;
   __shared__ uint32_t cost_image[4][kImage + 3];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   uint32_t* img = cost_image[wave];
+  uint8_t* flg = nullptr;   // the merge variant: per PU entry of the image, whether its merge cost was the smaller one
+  if constexpr (MERGE) {
+    __shared__ uint8_t merged_image[4][FHEVC_PUS + FHEVC_PUS_SMALL + 4];
+    flg = merged_image[wave];
+  }
 
   for (int g = blockIdx.x * 4 + wave; g < G.total; g += gridDim.x * 4) {
     const int in_band = g % G.band_ctus;
@@ -65,10 +100,17 @@ __global__ __launch_bounds__(256) void fhevc_pu_shape_kernel(PuShapeGeom G, Fhev
     const int x0 = (ctu % G.ctus_x) * 64, y0 = (ctu / G.ctus_x) * 64;
     const int valid_w = min(64, G.width - x0), valid_h = min(64, G.height - y0);
     park_costs<FHEVC_NODES>(img, nodes + (size_t)g * (FHEVC_NODES * 4), lane);
-    park_costs<FHEVC_PUS>(img + FHEVC_NODES, pus + (size_t)g * (FHEVC_PUS * 4), lane);
-    if (pus_small) park_costs<FHEVC_PUS_SMALL>(img + FHEVC_NODES + FHEVC_PUS, pus_small + (size_t)g * (FHEVC_PUS_SMALL * 4), lane);
-    else
-      for (int e = lane; e < FHEVC_PUS_SMALL; e += 64) img[FHEVC_NODES + FHEVC_PUS + e] = kNone;
+    if constexpr (MERGE) {
+      const PuShapeMerge mg = (merge_arg, ...);
+      park_min_costs<FHEVC_PUS>(img + FHEVC_NODES, flg, pus + (size_t)g * (FHEVC_PUS * 4), mg.pus + (size_t)g * (FHEVC_PUS * 4), lane);
+      park_min_costs<FHEVC_PUS_SMALL>(img + FHEVC_NODES + FHEVC_PUS, flg + FHEVC_PUS, pus_small ? pus_small + (size_t)g * (FHEVC_PUS_SMALL * 4) : nullptr,
+                                      mg.small ? mg.small + (size_t)g * (FHEVC_PUS_SMALL * 4) : nullptr, lane);
+    } else {
+      park_costs<FHEVC_PUS>(img + FHEVC_NODES, pus + (size_t)g * (FHEVC_PUS * 4), lane);
+      if (pus_small) park_costs<FHEVC_PUS_SMALL>(img + FHEVC_NODES + FHEVC_PUS, pus_small + (size_t)g * (FHEVC_PUS_SMALL * 4), lane);
+      else
+        for (int e = lane; e < FHEVC_PUS_SMALL; e += 64) img[FHEVC_NODES + FHEVC_PUS + e] = kNone;
+    }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -144,6 +186,23 @@ __global__ __launch_bounds__(256) void fhevc_pu_shape_kernel(PuShapeGeom G, Fhev
           for (int p = 0; p < 8; ++p) cd[p] = c[p];
         }
       }
+      if constexpr (MERGE) {
+        const PuShapeMerge mg = (merge_arg, ...);
+        if (mg.merged) {
+          // bit 2 p + part: that part's merge cost is strictly smaller than its refined cost; p = 0 stays the explicit cost, an invalid node has none
+          uint32_t bits = 0;
+          if (valid) {
+            const uint8_t* fs = flg + (sym - FHEVC_NODES);
+            bits = (uint32_t)fs[0] << 2 | (uint32_t)fs[1] << 3 | (uint32_t)fs[2] << 4 | (uint32_t)fs[3] << 5;
+            if (amp >= 0) {
+              const uint8_t* fa = flg + (amp - FHEVC_NODES);
+#pragma unroll
+              for (int e = 0; e < 8; ++e) bits |= (uint32_t)fa[e] << (8 + e);
+            }
+          }
+          mg.merged[(size_t)g * FHEVC_NODES + k] = (uint16_t)bits;
+        }
+      }
     }
     __builtin_amdgcn_wave_barrier();  // the next CTU of this wave overwrites the image
   }
@@ -151,10 +210,12 @@ __global__ __launch_bounds__(256) void fhevc_pu_shape_kernel(PuShapeGeom G, Fhev
 
 }  // namespace
 
-hipError_t fhevc_launch_pu_shape(const FhevcFrames& fr, const FhevcPuShapeRule& rule, const FhevcMotionQpelNode* d_nodes, const FhevcMotionQpelNode* d_pus,
-                                 const FhevcMotionQpelNode* d_pus_small, FhevcPuShapeNode* d_shapes, uint32_t* d_costs, int num_cus, hipStream_t stream)
+// d_merge_pus: null for the plain form
+static hipError_t launch_pu_shape(const FhevcFrames& fr, const FhevcPuShapeRule& rule, const FhevcMotionQpelNode* d_nodes, const FhevcMotionQpelNode* d_pus,
+                                  const FhevcMotionQpelNode* d_pus_small, const FhevcMotionMergeNode* d_merge_pus, const FhevcMotionMergeNode* d_merge_small,
+                                  FhevcPuShapeNode* d_shapes, uint32_t* d_costs, uint16_t* d_merged, int num_cus, hipStream_t stream)
 {
-  static_assert(sizeof(FhevcMotionQpelNode) == 16 && sizeof(FhevcPuShapeNode) == 16, "entry layout");
+  static_assert(sizeof(FhevcMotionQpelNode) == 16 && sizeof(FhevcPuShapeNode) == 16 && sizeof(FhevcMotionMergeNode) == 16, "entry layout");
   PuShapeGeom G;
   G.width = fr.width; G.height = fr.height; G.ctus_x = fr.ctus_x;
   G.row_begin = fr.row_begin; G.band_ctus = (fr.row_end - fr.row_begin) * fr.ctus_x;
@@ -171,7 +232,28 @@ hipError_t fhevc_launch_pu_shape(const FhevcFrames& fr, const FhevcPuShapeRule& 
   const uint32_t* pus = reinterpret_cast<const uint32_t*>(d_pus);
   const uint32_t* small = reinterpret_cast<const uint32_t*>(d_pus_small);
   uint32_t* shapes = reinterpret_cast<uint32_t*>(d_shapes);
+  if (d_merge_pus) {
+    // cost_best is dword 1 of a merge record; the records are read as dwords whatever their alignment, the "merged" bits leave as 2-byte stores
+    const PuShapeMerge mg = { reinterpret_cast<const uint32_t*>(d_merge_pus), reinterpret_cast<const uint32_t*>(d_merge_small), d_merged };
+    if ((all & 15) == 0) hipLaunchKernelGGL((fhevc_pu_shape_kernel<true, PuShapeMerge>), dim3((unsigned)grid), dim3(256), 0, stream, G, rule, nodes, pus, small, shapes, d_costs, mg);
+    else hipLaunchKernelGGL((fhevc_pu_shape_kernel<false, PuShapeMerge>), dim3((unsigned)grid), dim3(256), 0, stream, G, rule, nodes, pus, small, shapes, d_costs, mg);
+    return hipGetLastError();
+  }
   if ((all & 15) == 0) hipLaunchKernelGGL((fhevc_pu_shape_kernel<true>), dim3((unsigned)grid), dim3(256), 0, stream, G, rule, nodes, pus, small, shapes, d_costs);
   else hipLaunchKernelGGL((fhevc_pu_shape_kernel<false>), dim3((unsigned)grid), dim3(256), 0, stream, G, rule, nodes, pus, small, shapes, d_costs);
   return hipGetLastError();
+}
+
+hipError_t fhevc_launch_pu_shape(const FhevcFrames& fr, const FhevcPuShapeRule& rule, const FhevcMotionQpelNode* d_nodes, const FhevcMotionQpelNode* d_pus,
+                                 const FhevcMotionQpelNode* d_pus_small, FhevcPuShapeNode* d_shapes, uint32_t* d_costs, int num_cus, hipStream_t stream)
+{
+  return launch_pu_shape(fr, rule, d_nodes, d_pus, d_pus_small, nullptr, nullptr, d_shapes, d_costs, nullptr, num_cus, stream);
+}
+
+hipError_t fhevc_launch_pu_shape_merge(const FhevcFrames& fr, const FhevcPuShapeRule& rule, const FhevcMotionQpelNode* d_nodes, const FhevcMotionQpelNode* d_pus,
+                                       const FhevcMotionQpelNode* d_pus_small, const FhevcMotionMergeNode* d_merge_pus, const FhevcMotionMergeNode* d_merge_small,
+                                       FhevcPuShapeNode* d_shapes, uint32_t* d_costs, uint16_t* d_merged, int num_cus, hipStream_t stream)
+{
+  if (!d_merge_pus) return hipErrorInvalidValue;
+  return launch_pu_shape(fr, rule, d_nodes, d_pus, d_pus_small, d_merge_pus, d_merge_small, d_shapes, d_costs, d_merged, num_cus, stream);
 }

@@ -858,8 +858,8 @@ typedef struct {
  * other on one stream without a host synchronisation.  FHEVC_E_INVALID with a fhevc_last_error text (nothing is launched or written): a null context, d_luma,
  * d_refined or d_out, num_frames < 2, qp outside 0..51, max_range outside 1..64, stride_samples < width, a bad band, overlapping frames, uint8 planes on a
  * context above 8 bit -- whatever fhevc_motion_refine_device rejects.  Timed under slot 19 of fhevc_kernel_timing.
- * NOT covered: merge for rectangular PUs, HM's second-PU and parallel-merge-level rules, the temporal candidate, candidates from neighbours of a finer level
- * than the node's own, a window staged around per-CTU centres, skip detection.  The encoder hook does not consume this output. */
+ * NOT covered: the temporal candidate, candidates from neighbours of a finer level than the node's own, a window staged around per-CTU centres, skip
+ * detection.  (The rectangular PUs, with HM's second-PU rules: fhevc_motion_merge_pu*, further below.)  The encoder hook does not consume this output. */
 int  fhevc_motion_merge_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
                                int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_qpel_node* d_refined,
                                fhevc_motion_merge_node* d_out, void* stream);
@@ -889,6 +889,69 @@ int  fhevc_p_tree_merge_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int
                               uint8_t* depth_max /* numCtus * 256 */, fhevc_pu_shape_node* shapes /* numCtus * 85 or NULL */,
                               fhevc_motion_merge_node* merge /* numCtus * 85 or NULL */);
 
+/* ---- config 4 (P slices): merge-candidate costs per PU (k_motion_merge_pu.hip) -----------------------------------------------------------------
+ * TEncSearch::xMergeEstimation (TEncSearch.cpp:2831-2884) where HM itself runs it: for every PU of a CU whose partition size is not 2Nx2N (:3336, :3371);
+ * predInterSearch then keeps the merge cost instead of the motion-estimation cost when uiMRGCost < uiMECost (:3373).  The 124 + 384 PUs are those of
+ * fhevc_motion_refine_pu*.
+ *   Input: the refined square nodes (85 per CTU; cost_best, mvx, mvy are read) -- exactly what fhevc_motion_merge_device takes.  No PU entry is read.
+ *   Output: one fhevc_motion_merge_node per PU: d_out_pus 124 per CTU in fhevc_motion_pu_index order, d_out_pus_small 384 per CTU in
+ * fhevc_motion_pu_small_index order; either may be NULL, not both.
+ *   Geometry: a PU belongs to CU node k of level l (s = 64 >> l); its rectangle (xP, yP, w, h) in picture samples is getPartIndexAndSize's, the one the PU
+ * searches use.  It is valid iff its CU node is INSIDE; an invalid PU gets the record of an invalid node (0xFFFFFFFF twice, a zero vector, idx = src = 255,
+ * num = 0, pad = 0).
+ *   Candidate positions (TComDataCU.cpp:2142-2320): L (xP - 1, yP + h - 1), A (xP + w - 1, yP - 1), AR (xP + w, yP - 1), BL (xP - 1, yP + h),
+ * AL (xP - 1, yP - 1).  Each maps to the node of the CU's OWN level l that holds the sample: grid position (sx >> log2 s, sy >> log2 s), a negative
+ * coordinate is off the grid; its vector is that node's refined square vector.
+ *   A candidate is available iff it is on the grid and INSIDE, its CTU row lies in the band, its coding-order key (CTU raster index, z-index of the node
+ * in its CTU) is strictly smaller than the key of the PU's own CU, its record is no marker, and |mvx| and |mvy| are both <= 4 max_range + 3.  The key
+ * rule reproduces HM's two second-PU exclusions (:2170, :2202): part 1 of Nx2N / nLx2N / nRx2N has its L sample, part 1 of 2NxN / 2NxnU / 2NxnD its A sample
+ * inside part 0 of its own CU, whose key is equal, not smaller; no other candidate of any of the 508 PUs falls inside its own CU.
+ *   Parallel merge level: modelled at HM's default Log2ParMrgLevel 2, where isDiffMER is true for every position outside the PU and the shared list of
+ * 8x8 CUs (TEncSearch.cpp:2841) does not apply.
+ *   List, cost and choice as fhevc_motion_merge*: HM's order and pruning pairs on vectors (two positions in one node prune each other), AL only below four
+ * entries, one zero vector below five; entry i costs sd(q) + c[bits], bits = i + 1, 4 for i = 4, c at the slice QP's motion lambda; sd(q) = xGetHADs of the
+ * whole w x h PU through the branch xGetHADs takes -- 8x8 Hadamards (sum + 2) >> 2 for the 124, 4x4 Hadamards (sum + 1) >> 1 over all (w/4)(h/4) tiles for the
+ * 384 --, the PU's sum shifted once by bit_depth - 8, on fhevc_motion_refine's prediction; strict "<", the first entry of equal cost wins.
+ *   Device form: planes, band, qp 0..51, max_range 1..64 and stream as fhevc_motion_merge_device, and whatever that rejects is rejected here with
+ * FHEVC_E_INVALID and a fhevc_last_error text, nothing launched, nothing written.  Outputs compact over the band, written over exactly their extent; an
+ * empty band writes nothing.  Asynchronous, allocates nothing, keeps no state in HBM (the bit costs travel by value).  The kernel has
+ * fhevc_motion_refine_pu's mapping (workgroup = CTU over a persistent grid, 26 passes dealt to four waves, lane = 8x8 tile) and the merge stage's list in
+ * registers; the 123 nodes that can be a neighbour are parked in LDS once per CTU.  Timed under slot 21 of fhevc_kernel_timing.
+ * NOT covered: the temporal candidate, candidates from finer-level neighbours, Log2ParMrgLevel above 2, skip detection, a window around per-CTU centres.
+ * The encoder hook does not consume this output. */
+int  fhevc_motion_merge_pu_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                                  int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_qpel_node* d_refined,
+                                  fhevc_motion_merge_node* d_out_pus, fhevc_motion_merge_node* d_out_pus_small, void* stream);
+/* one picture pair, host buffers (both planes with the same stride), synchronous, as fhevc_motion_merge; refined: numCtus * 85; out_pus: numCtus * 124 or
+ * NULL; out_pus_small: numCtus * 384 or NULL (not both NULL) */
+int  fhevc_motion_merge_pu(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                           const fhevc_motion_qpel_node* refined, fhevc_motion_merge_node* out_pus, fhevc_motion_merge_node* out_pus_small);
+
+/* The partition-size selection WITH the PUs' merge costs: fhevc_pu_shape_select[_device] with two more inputs, the merge records of the 124 and of the 384
+ * PUs (merge_pus never NULL; merge_pus_small may be NULL, which means all markers -- as a NULL pus_small means for the refined small PUs), and ONE changed
+ * rule, HM's :3373: the cost of a part is min(refined cost_best, merge cost_best).  The marker is the largest value, so it loses to any cost and two markers
+ * stay one; a pair's sum, saturation and unavailability are as before.  p = 0 stays the explicit 2Nx2N cost: the node's own merge cost enters at the tree
+ * (fhevc_p_tree_select_merge*).  One more optional output, merged: a uint16_t per node, bit 2 p + part set iff that part's merge cost is strictly smaller
+ * than its refined cost; 0 for an invalid node, and never set for a part whose two costs are both markers or for a size the node does not have.  With every
+ * merge cost MARK, records and cost table are byte for byte fhevc_pu_shape_select[_device]'s.  The host form needs no context; the device form is a
+ * further instantiation of k_pu_shape.hip (of a merge record cost_best is dword 1), timed under slot 13; d_merged is written as 2-byte stores over
+ * num_pictures * band CTUs * 85 values.  Everything else -- rule, bands, alignments, rejected calls -- is the existing definition. */
+int  fhevc_pu_shape_select_merge(const fhevc_motion_qpel_node* nodes /* 85 */, const fhevc_motion_qpel_node* pus /* 124 */,
+                                 const fhevc_motion_qpel_node* pus_small /* 384 or NULL */, const fhevc_motion_merge_node* merge_pus /* 124 */,
+                                 const fhevc_motion_merge_node* merge_pus_small /* 384 or NULL */, int valid_w, int valid_h, const fhevc_pu_shape_rule* rule,
+                                 fhevc_pu_shape_node* out /* 85 */, uint32_t* costs /* 85 * 8 or NULL */, uint16_t* merged /* 85 or NULL */);
+int  fhevc_pu_shape_select_merge_device(fhevc_ctx* ctx, const fhevc_motion_qpel_node* d_nodes, const fhevc_motion_qpel_node* d_pus,
+                                        const fhevc_motion_qpel_node* d_pus_small, const fhevc_motion_merge_node* d_merge_pus,
+                                        const fhevc_motion_merge_node* d_merge_pus_small, int num_pictures, int ctu_row_begin, int ctu_row_end,
+                                        const fhevc_pu_shape_rule* rule, fhevc_pu_shape_node* d_shapes, uint32_t* d_costs, uint16_t* d_merged, void* stream);
+/* fhevc_p_tree_merge_frame on merge-aware selection costs: the same arguments, checks and chains; behind fhevc_motion_merge_device comes
+ * fhevc_motion_merge_pu_device for all 508 PUs with the same max_range (search_range, or 64 on the centred chain), and the selection is
+ * fhevc_pu_shape_select_merge_device.  Downloads what fhevc_p_tree_merge_frame downloads. */
+int  fhevc_p_tree_merge_pu_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                                 const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min /* numCtus * 256 */,
+                                 uint8_t* depth_max /* numCtus * 256 */, fhevc_pu_shape_node* shapes /* numCtus * 85 or NULL */,
+                                 fhevc_motion_merge_node* merge /* numCtus * 85 or NULL */);
+
 /* CTU-row band of rank `rank` out of `world`: rows [begin, end) */
 int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
 
@@ -902,7 +965,8 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
  * each counted), 13 = the partition-size selection (fhevc_pu_shape_select_device), 15 = the coarse motion centres (fhevc_motion_centres*), the searches around them
  * (fhevc_motion_search_pu_centred*) and their refinements (fhevc_motion_refine_pu_centred*), each launch counted; 14 is not a slot and is rejected like any number above 15
  * -- except 17 = the P-picture tree decision (fhevc_p_tree_select_device, fhevc_p_tree_select_merge_device), added later.  16 is not a slot either: it stays rejected
- * -- and 19 = the merge-candidate costs (fhevc_motion_merge*), added later still.  18 is not a slot: it stays rejected, as does any number above 19 */
+ * -- and 19 = the merge-candidate costs (fhevc_motion_merge*), added later still.  18 is not a slot: it stays rejected -- and 21 = the merge-candidate
+ * costs per PU (fhevc_motion_merge_pu*).  20 is not a slot: it stays rejected, as does any number above 21 */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
 int  fhevc_enable_kernel_timing(fhevc_ctx* ctx, int on);
 
