@@ -36,6 +36,7 @@ struct FhevcKnobs {
   int wg_per_cu = 0;            // FHEVC_CNN_WG_PER_CU=1..4: workgroups per CU of the depth kernel's persistent grid (0: the form's own)
   int debug_wg_per_cu = 0;      // FHEVC_DEBUG_WG_PER_CU=1..4: the same for the stamped diagnostic build only
   bool requant_general = false; // FHEVC_CNN_REQUANT=general: the i8 form's general requant instead of the short forms
+  bool requant_short = false;   // FHEVC_CNN_REQUANT=short: the short forms 1 / 2 also where the blob qualifies for the high-byte forms (tests, A/B)
   bool family_layers = false;   // FHEVC_FAMILY_LAYERS: a member with a fused kernel runs layer by layer all the same (tests)
   bool trio = false;            // FHEVC_CNN_TRIO=1: the i8 depth kernel as ONE 768-thread workgroup per CU, three groups one barrier interval apart (k_cnn.hip, TRIO)
   bool d2_requant_general = false; // FHEVC_D2_REQUANT=general: the fused two-convolution kernel's general requant instantiation whatever the blob allows (tests, A/B)
@@ -72,7 +73,8 @@ struct FhevcCnnWeights {
   const uint4* frag_i8;
   const int32_t* bias_i8;
   int shift[3];
-  int requant_mode[3];       // per layer: 0 general, 1 shift <= 7 (packed 16-bit shift), 2 shift == 8 and |accumulator| < 2^23 (byte gather)
+  int requant_mode[3];       // per layer: 0 general, 1 shift <= 7 (packed 16-bit shift), 2 shift == 8 and |accumulator| < 2^23 (byte gather),
+                             // 3 high byte of the saturated 16-bit value (conv2 at shift 7, conv3 at shift 8; bias_i8 then carries - (128 << shift) as well)
   int i8;                    // 1: run that variant
   int had_valu;              // 1: the fused source Hadamard on packed 16-bit VALU also for 8-bit content (default; FHEVC_HADAMARD_FORM=mfma: 0)
 };

@@ -251,6 +251,15 @@ int build_weight_image(fhevc_ctx* c, const BlobView& b)
   // the requant's form per layer (k_cnn.hip: requant4_i8); FHEVC_CNN_REQUANT=general keeps the general one (A/B, tests)
   for (int l = 1; l < 3; ++l)
     new_mode[l] = c->knobs.requant_general ? 0 : (new_shift[l] == 8 && bound[l] < (1LL << 23)) ? 2 : (new_shift[l] <= 7 ? 1 : 0);
+  // the high-byte forms (k_cnn.hip: requant4_i8_hi; mode 3): conv2 at shift 7 (one saturating doubling), conv3 at shift 8, their biases with - (128 << shift) folded
+  // in -- valid while the folded accumulator cannot wrap int32.  The depth kernel has ONE instantiation for them, so both layers take mode 3 or neither does;
+  // FHEVC_CNN_REQUANT=short and the TRIO form (built on the short forms) keep modes 1 / 2 and their biases
+  auto high_byte_ok = [&](int l, int want_shift) { return new_shift[l] == want_shift && bound[l] + (128LL << new_shift[l]) < (1LL << 31); };
+  if (!c->knobs.requant_general && !c->knobs.requant_short && !c->knobs.trio && high_byte_ok(1, 7) && high_byte_ok(2, 8)) {
+    new_mode[1] = new_mode[2] = 3;
+    for (int oc = 0; oc < 32; ++oc) bias8[16 + oc] -= 128 << new_shift[1];
+    for (int oc = 0; oc < 64; ++oc) bias8[48 + oc] -= 128 << new_shift[2];
+  }
   std::vector<float> bias(112);
   for (int i = 0; i < 16; ++i) {
     int32_t b1;

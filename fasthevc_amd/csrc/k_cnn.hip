@@ -11,9 +11,10 @@
 //   ARITH = 0, the 16-bit form (round 1): conv1 v_mfma_f32_32x32x16_bf16, conv2 v_mfma_f32_32x32x16_f16, conv3 v_mfma_f32_16x16x32_f16;
 //     activations between the convs as f16 in 8-channel LDS planes; weights carry 2^-shift, biases are the C operand, fp32 rounding toward
 //     -inf turns v_cvt_pk_u8_f32 into floor + ReLU + clamp + pack; FC heads on v_dot4_i32_i8; two workgroups per CU (79.8 KB of LDS, 254 VGPRs);
-//   ARITH = 1 | 2, the i8 form (round 2, the library's default): conv2 and conv3 on v_mfma_i32_32x32x32_i8 with the activations as signed
+//   ARITH = 1 | 2 | 3, the i8 form (round 2, the library's default): conv2 and conv3 on v_mfma_i32_32x32x32_i8 with the activations as signed
 //     bytes a - 128 in 16-channel planes (half the LDS), int32 accumulators, requant by shifts (2: the short forms where the blob's shifts
-//     and accumulator bounds allow), the 16- / 32-level heads as one v_mfma_i32_16x16x64_i8 GEMM, conv2's fragments re-fetched per CTU;
+//     and accumulator bounds allow; 3: the high-byte forms for shifts 7 / 8, with the - 128 folded into the biases by the host: requant4_i8_hi),
+//     the 16- / 32-level heads as one v_mfma_i32_16x16x64_i8 GEMM, conv2's fragments re-fetched per CTU;
 //     three workgroups per CU (51 KB of LDS, 168 VGPRs), s_setprio per phase.
 // Common to both: persistent workgroups of 256 threads, grid-stride over CTUs in an XCD-aware order; A = weights (resident in VGPRs), B =
 // im2col fragments read from LDS with one ds_read_b128 per K step through a register ring; the 2x2 max-pools in-lane (conv1 folds the pool
@@ -319,6 +320,18 @@ __device__ __forceinline__ unsigned requant4_i8(int a, int b, int c, int d, int 
   asm("v_sat_pk_u8_i16_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD" : "+v"(r) : "v"(p1));
   return r ^ 0x80808080u;
 }
+// The high-byte form (mode 3; shift 8 - DBL, DBL = 0 | 1): the host has folded - (128 << shift) into the layer's biases (build_weight_image), so the accumulator is
+// y = x - (128 << shift) and the wanted signed byte clamp(x >> shift, 0, 255) - 128 = clamp(floor(y / 2^shift), -128, 127).  At shift 8 that is the HIGH BYTE of
+// sat16(y): 2 v_cvt_pk_i16_i32 (saturating) + 1 v_perm_b32 gathering the four high bytes = 3 instructions; at shift 7 one saturating doubling per pair
+// (v_pk_add_i16 p, p clamp: sat16(2 sat16(y)) has the high byte of sat16(2 y)) in between = 5.  No xor, no bound on the accumulator short of int32 itself
+template <int DBL>
+__device__ __forceinline__ unsigned requant4_i8_hi(int a, int b, int c, int d)
+{
+  s16x2_t p0 = __builtin_amdgcn_cvt_pk_i16(a, b), p1 = __builtin_amdgcn_cvt_pk_i16(c, d);
+#pragma unroll
+  for (int k = 0; k < DBL; ++k) { p0 = __builtin_elementwise_add_sat(p0, p0); p1 = __builtin_elementwise_add_sat(p1, p1); }
+  return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, p1), __builtin_bit_cast(unsigned, p0), 0x07050301u);
+}
 // conv1 (still on the bf16 MFMA: K = 16 gains nothing from the i8 shape): pool, floor + clamp, a - 128; the lane's 8 channels
 // (8h .. 8h+7) are 8 bytes of the position's 16
 __device__ __forceinline__ void conv1_store_i8(const f32x16& acc0, const f32x16& acc1, unsigned char* dst)
@@ -354,7 +367,8 @@ __device__ __forceinline__ void conv2_requant_store_i8m(const i32x16& m, unsigne
 {
 #pragma unroll
   for (int g = 0; g < 4; ++g)
-    *reinterpret_cast<unsigned*>(dst + (g >> 1) * A2_PLANE + 8 * (g & 1)) = requant4_i8(m[4 * g], m[4 * g + 1], m[4 * g + 2], m[4 * g + 3], shift, MODE);
+    *reinterpret_cast<unsigned*>(dst + (g >> 1) * A2_PLANE + 8 * (g & 1)) =
+        MODE == 3 ? requant4_i8_hi<1>(m[4 * g], m[4 * g + 1], m[4 * g + 2], m[4 * g + 3]) : requant4_i8(m[4 * g], m[4 * g + 1], m[4 * g + 2], m[4 * g + 3], shift, MODE);
 }
 // conv3: channel 32 tile + 8 g + 4 h + (i & 3) of a position lives in logical 16-B chunk 2 tile + (g >> 1), bytes 8 (g & 1) + 4 h ..;
 // dst = the position's 64-byte row + 4 h; psw = chunk swizzle of the position
@@ -364,7 +378,7 @@ __device__ __forceinline__ void conv3_store_i8m(const i32x16& acc, unsigned char
 #pragma unroll
   for (int g = 0; g < 4; ++g)
     *reinterpret_cast<unsigned*>(dst + (((2 * tile + (g >> 1)) ^ psw) << 4) + 8 * (g & 1)) =
-        requant4_i8(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3], shift, MODE);
+        MODE == 3 ? requant4_i8_hi<0>(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]) : requant4_i8(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3], shift, MODE);
 }
 
 // ---- MFMA chains with a register ring of B fragments ---------------------------------------------------------
@@ -865,7 +879,9 @@ __device__ __forceinline__ unsigned long long stamp()
 //      1 = on packed 16-bit VALU from the prefetched samples (up to 10 bit: wave_src_hadamard), 2 = on the bf16 MFMA from the staged
 //      tile (8-bit content only: the tile holds the samples rounded to 8 bits; src_hadamard_mfma)
 // I8: conv2 and conv3 on v_mfma_i32_32x32x32_i8 with the activations as signed bytes (see Lds); the same integers come out.
-// I8 = 2: the same with the short requant forms (requant4_i8: conv2 mode 1, conv3 mode 2), where the host found them valid
+// ARITH = 2: the same with the short requant forms (requant4_i8: conv2 mode 1, conv3 mode 2), where the host found them valid
+// ARITH = 3: the same with the high-byte forms (requant4_i8_hi: conv2 at shift 7, conv3 at shift 8), whose biases the host built with - (128 << shift) folded in;
+//            the TRIO form stays on ARITH = 2 (the host keeps modes 1 / 2 and their biases for a context created under FHEVC_CNN_TRIO)
 // TRIO = 1 (round 4): the CU's three workgroups as ONE workgroup of 768 threads = three groups of four waves, each group a "workgroup" of the form above with its own
 // third of the LDS and its own CTUs, but behind COMMON barriers and one barrier interval apart: at any time the three groups are in three different
 // intervals of the four (conv1 | conv2 | conv3 | heads + staging), so the intervals that load the matrix pipe never coincide -- three independent workgroups fall
@@ -890,7 +906,8 @@ __global__ __launch_bounds__(TRIO ? 768 : 256, TRIO ? 1 : (ARITH ? FHEVC_I8_WG_P
   __builtin_amdgcn_s_setreg((1 << 11) | 1, 2);
   const int tid = TRIO ? (int)(threadIdx.x & 255) : (int)threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
-  constexpr bool I8 = ARITH != 0, FASTRQ = ARITH == 2;
+  constexpr bool I8 = ARITH != 0;
+  constexpr int RQ2 = ARITH == 3 ? 3 : (ARITH == 2 ? 1 : 0), RQ3 = ARITH == 3 ? 3 : (ARITH == 2 ? 2 : 0);  // requant forms of conv2 / conv3 (requant4_i8, requant4_i8_hi)
   int prio_slot = 0;   // which of the CU's workgroups this is, from where its LDS allocation starts (see FHEVC_PRIO_ON)
   if (I8) {
     const unsigned la = __builtin_amdgcn_s_getreg((31 << 11) | 6);   // HW_REG_LDS_ALLOC: base [11:0], size [20:12], both in 256-byte granules
@@ -900,13 +917,15 @@ __global__ __launch_bounds__(TRIO ? 768 : 256, TRIO ? 1 : (ARITH ? FHEVC_I8_WG_P
   }
   (void)prio_slot;
   constexpr bool MFMA_HEADS = I8;  // the two smaller FC heads as an i8 MFMA GEMM (P4)
-  (void)FASTRQ;
+  (void)RQ2; (void)RQ3;
   using L = Lds<I8>;
   const HaloCells hc = halo_cells<I8>(tid);  // three registers for the life of the kernel
   // head bias + QP prior on "split" (class 1): uniform, lives in scalar registers
   const int hb64a = W.bhead[0], hb64b = W.bhead[1] + W.bhead[6 + 0 * 52 + F.qp];
-  const int hb32a = W.bhead[2], hb32b = W.bhead[3] + W.bhead[6 + 1 * 52 + F.qp];
-  const int hb16a = W.bhead[4], hb16b = W.bhead[5] + W.bhead[6 + 2 * 52 + F.qp];
+  // (hipcc fetches them with vector loads; the 32- and 16-level pairs are only read by conv2's logit reset, and pinning them to scalar registers hands
+  // their four kernel-long VGPRs back: the i8 instantiations with the high-byte requant forms otherwise spill one or two registers at 168)
+  const int hb32a = __builtin_amdgcn_readfirstlane(W.bhead[2]), hb32b = __builtin_amdgcn_readfirstlane(W.bhead[3] + W.bhead[6 + 1 * 52 + F.qp]);
+  const int hb16a = __builtin_amdgcn_readfirstlane(W.bhead[4]), hb16b = __builtin_amdgcn_readfirstlane(W.bhead[5] + W.bhead[6 + 2 * 52 + F.qp]);
   // ---- resident weight fragments (A operands) ----
   // conv1's two fragments are only live from the end of a CTU's heads to its conv1: they are re-fetched (L2-hot) under
   // the heads of the previous CTU, which frees 8 registers in the conv2 phase, the tightest one
@@ -1188,14 +1207,14 @@ __global__ __launch_bounds__(TRIO ? 768 : 256, TRIO ? 1 : (ARITH ? FHEVC_I8_WG_P
       pool_v_i8(t0, a0, a1);
       if (FHEVC_I8_C2_FENCE) __builtin_amdgcn_sched_barrier(0);
       conv2_half_i8<false, false, (2 * C2F) % RINGI>(h10, h10 + A1_ROW, c2l, wA2, ring, b2t, h, t1, a0);
-      conv2_requant_store_i8m<FASTRQ ? 1 : 0>(t0, a2dst + (2 * u0) * A2_PITCH * 16, shift2);
+      conv2_requant_store_i8m<RQ2>(t0, a2dst + (2 * u0) * A2_PITCH * 16, shift2);
       if (FHEVC_I8_C2_SCHED) sched_chain12_i8<FHEVC_I8_C2_FILL_REQUANT>();
       conv2_half_i8<false, true, (3 * C2F) % RINGI>(h10 + A1_ROW, h10 + A1_ROW, c2l, wA2, ring, b2t, h, a1, t0);
       pool_h_i8(t1, a0);
       if (FHEVC_I8_C2_SCHED) sched_chain12_i8<FHEVC_I8_C2_FILL_POOL>();
       if (FHEVC_I8_C2_FENCE) __builtin_amdgcn_sched_barrier(0);
       pool_v_i8(t1, a1, t0);
-      conv2_requant_store_i8m<FASTRQ ? 1 : 0>(t1, a2dst + (2 * u1) * A2_PITCH * 16, shift2);
+      conv2_requant_store_i8m<RQ2>(t1, a2dst + (2 * u1) * A2_PITCH * 16, shift2);
       FHEVC_PRIO_OFF(1)
     } else {
       FHEVC_PHASE_IDS
@@ -1260,11 +1279,11 @@ __global__ __launch_bounds__(TRIO ? 768 : 256, TRIO ? 1 : (ARITH ? FHEVC_I8_WG_P
       if (FHEVC_I8_C3_SCHED) sched_pairs18_i8<0>();
       conv3_pairs_i8<1>(a2, wA3, ring, b3p, h, q0, q1);
       if (FHEVC_I8_C3_SCHED) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-      conv3_store_i8m<FASTRQ ? 2 : 0>(p0, a3dst + conv3_pair_row_i8(0) * 1024, tile3, psw, shift3);
-      conv3_store_i8m<FASTRQ ? 2 : 0>(p1, a3dst + conv3_pair_row_i8(1) * 1024, tile3, psw, shift3);
+      conv3_store_i8m<RQ3>(p0, a3dst + conv3_pair_row_i8(0) * 1024, tile3, psw, shift3);
+      conv3_store_i8m<RQ3>(p1, a3dst + conv3_pair_row_i8(1) * 1024, tile3, psw, shift3);
       if (FHEVC_I8_C3_SCHED) sched_pairs18_i8<FHEVC_I8_C3_FILL>();
-      conv3_store_i8m<FASTRQ ? 2 : 0>(q0, a3dst + conv3_pair_row_i8(2) * 1024, tile3, psw, shift3);
-      conv3_store_i8m<FASTRQ ? 2 : 0>(q1, a3dst + conv3_pair_row_i8(3) * 1024, tile3, psw, shift3);
+      conv3_store_i8m<RQ3>(q0, a3dst + conv3_pair_row_i8(2) * 1024, tile3, psw, shift3);
+      conv3_store_i8m<RQ3>(q1, a3dst + conv3_pair_row_i8(3) * 1024, tile3, psw, shift3);
       FHEVC_PRIO_OFF(2)
     } else if constexpr (FHEVC_F16_CONV3_32 != 0) {
       FHEVC_PHASE_IDS
@@ -1690,8 +1709,13 @@ void launch_depth_kernel(int grid, hipStream_t stream, const FhevcFrames& fr, co
   hipLaunchKernelGGL((fhevc_cnn_depth_kernel<STAMPS, HAD, ARITH>), dim3(grid), dim3(256), Lds<ARITH != 0>::LDS_BYTES, stream, fr, w, d_depth, d_had, d_logits,
                      d_flags, d_stamps, d_depth_max, margin_split, margin_stop);
 }
-// 0: 16-bit MFMAs; 1: i8, general requant; 2: i8 with the short requant forms
-int cnn_arith(const FhevcCnnWeights& w) { return !w.i8 ? 0 : (w.requant_mode[1] == 1 && w.requant_mode[2] == 2) ? 2 : 1; }
+// 0: 16-bit MFMAs; 1: i8, general requant; 2: i8 with the short requant forms; 3: i8 with the high-byte forms (the host sets mode 3 on both layers or on neither)
+int cnn_arith(const FhevcCnnWeights& w)
+{
+  if (!w.i8) return 0;
+  if (w.requant_mode[1] == 3 && w.requant_mode[2] == 3) return 3;
+  return (w.requant_mode[1] == 1 && w.requant_mode[2] == 2) ? 2 : 1;
+}
 }  // namespace
 
 // the switches of FhevcKnobs, read once per context (fhevc_create)
@@ -1701,7 +1725,7 @@ FhevcKnobs fhevc_read_knobs()
   auto digit = [](const char* e) { return (e && e[0] >= '1' && e[0] <= '4') ? e[0] - '0' : 0; };
   k.wg_per_cu = digit(std::getenv("FHEVC_CNN_WG_PER_CU"));
   k.debug_wg_per_cu = digit(std::getenv("FHEVC_DEBUG_WG_PER_CU"));
-  if (const char* rq = std::getenv("FHEVC_CNN_REQUANT")) k.requant_general = std::strcmp(rq, "general") == 0;
+  if (const char* rq = std::getenv("FHEVC_CNN_REQUANT")) { k.requant_general = std::strcmp(rq, "general") == 0; k.requant_short = std::strcmp(rq, "short") == 0; }
   k.family_layers = std::getenv("FHEVC_FAMILY_LAYERS") != nullptr;
   if (const char* fd = std::getenv("FHEVC_FUSED_D2")) k.fused_d2 = fd[0] != '0';
   k.layers_no_fuse = std::getenv("FHEVC_LAYERS_NO_FUSE") != nullptr;
@@ -1743,6 +1767,7 @@ hipError_t fhevc_launch_cnn(const FhevcFrames& fr, const FhevcCnnWeights& w, uin
   }
 #define FHEVC_LAUNCH_HAD(ARITH) do { if (had == 2) FHEVC_LAUNCH(2, ARITH); else if (had == 1) FHEVC_LAUNCH(1, ARITH); else FHEVC_LAUNCH(0, ARITH); } while (0)
   switch (cnn_arith(w)) {
+    case 3: FHEVC_LAUNCH_HAD(3); break;
     case 2: FHEVC_LAUNCH_HAD(2); break;
     case 1: FHEVC_LAUNCH_HAD(1); break;
     default: FHEVC_LAUNCH_HAD(0); break;
@@ -1768,11 +1793,14 @@ hipError_t fhevc_launch_cnn_stamped(const FhevcFrames& fr, const FhevcCnnWeights
     if (e != hipSuccess) return e;
     launch_depth_kernel<true, 0, 0>(grid, stream, fr, w, d_depth, nullptr, nullptr, nullptr, d_stamps, nullptr, 0, 0);
   } else if (arith == 1) launch_depth_kernel<true, 0, 1>(grid, stream, fr, w, d_depth, nullptr, nullptr, nullptr, d_stamps, nullptr, 0, 0);
-  else if (d_had && knobs.trio && !knobs.debug_wg_per_cu && !knobs.wg_per_cu) {
+  else if (arith == 2 && d_had && knobs.trio && !knobs.debug_wg_per_cu && !knobs.wg_per_cu) {
     const int tgrid = (int)std::min<long long>(num_cus, (total + 2) / 3);
     *grid_out = 3 * tgrid;
     hipLaunchKernelGGL((fhevc_cnn_depth_kernel<true, 1, 2, 1>), dim3(tgrid), dim3(768), 3 * Lds<true>::LDS_BYTES, stream, fr, w, d_depth, d_had, nullptr, nullptr, d_stamps, nullptr, 0, 0);
-  } else if (d_had) launch_depth_kernel<true, 1, 2>(grid, stream, fr, w, d_depth, d_had, nullptr, nullptr, d_stamps, nullptr, 0, 0);  // as bench.py times it: with the fused source Hadamard
+  } else if (arith == 3) {  // (the image's biases belong to the high-byte forms)
+    if (d_had) launch_depth_kernel<true, 1, 3>(grid, stream, fr, w, d_depth, d_had, nullptr, nullptr, d_stamps, nullptr, 0, 0);  // as bench.py times it: with the fused source Hadamard
+    else launch_depth_kernel<true, 0, 3>(grid, stream, fr, w, d_depth, nullptr, nullptr, nullptr, d_stamps, nullptr, 0, 0);
+  } else if (d_had) launch_depth_kernel<true, 1, 2>(grid, stream, fr, w, d_depth, d_had, nullptr, nullptr, d_stamps, nullptr, 0, 0);
   else launch_depth_kernel<true, 0, 2>(grid, stream, fr, w, d_depth, nullptr, nullptr, nullptr, d_stamps, nullptr, 0, 0);
   return hipGetLastError();
 }

@@ -226,7 +226,9 @@ def requant_limit_weights(layer, over=False, seed=0):
     """The 16 / 32 / 64 network with conv2 (layer 2) or conv3 (layer 3) at the requant limit; layer "high": conv3 at 127 on every tap
     with bias 2^22 (accumulators near 13.5 M: the general form, and the f16 form's 2^24 exactness bound).
     The depth kernel runs its short forms only as a pair, conv2 in form 1 (shift <= 7) and conv3 in form 2 (k_cnn.hip: cnn_arith): the
-    conv3 blobs keep conv2 at shift 7, so that the conv3 bound alone decides; a shift-8 conv2 runs the general forms on either side of 2^23."""
+    conv3 blobs keep conv2 at shift 7, so that the conv3 bound alone decides; a shift-8 conv2 runs the general forms on either side of 2^23.
+    By default the conv3 blobs (shifts 7 / 8) now take the high-byte forms on BOTH sides of 2^23 (requant_modes: no bound short of int32);
+    FHEVC_CNN_REQUANT=short and the TRIO form run them as described above."""
     w = random_weights(seed)
     w["w1"][:], w["b1"][:] = 0, 255 << 4
     if layer == 2:
@@ -240,6 +242,25 @@ def requant_limit_weights(layer, over=False, seed=0):
         w["w3"][:], w["b3"][:] = v, b
     validate(w)
     return w
+
+
+def requant_bound(wl, b):
+    """the library's bound on |accumulator| of conv2 / conv3 (fhevc_weights.hip: folded_bias): max over outputs of |b + 128 sum w| + 128 sum |w|"""
+    wl = np.asarray(wl, np.int64).reshape(len(b), -1)
+    return int((np.abs(np.asarray(b, np.int64) + 128 * wl.sum(1)) + 128 * np.abs(wl).sum(1)).max())
+
+
+def requant_modes(shift2, shift3, bound2, bound3, requant=None, trio=False):
+    """Restatement of build_weight_image's choice of the i8 form's requant per layer (tests) -> (mode of conv2, mode of conv3, bias offsets).
+    0 general, 1 shift <= 7, 2 shift 8 and bound < 2^23, 3 the high-byte forms (conv2 at shift 7 AND conv3 at shift 8, both with
+    bound + (128 << shift) < 2^31: - (128 << shift) is then folded into the layer's biases); requant = FHEVC_CNN_REQUANT's value."""
+    if requant == "general":
+        return 0, 0, (0, 0)
+    short = tuple(2 if s == 8 and b < REQUANT_LIMIT else (1 if s <= 7 else 0) for s, b in ((shift2, bound2), (shift3, bound3)))
+    fits = lambda s, b, want: s == want and b + (128 << s) < 1 << 31
+    if requant != "short" and not trio and fits(shift2, bound2, 7) and fits(shift3, bound3, 8):
+        return 3, 3, (-(128 << shift2), -(128 << shift3))
+    return short[0], short[1], (0, 0)
 
 
 def requant_limit_family(widths=(23, 46, 92), depth=2, over=False, seed=0):
