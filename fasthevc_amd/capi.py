@@ -43,6 +43,7 @@ SYMBOLS = [
     "fhevc_p_tree_rule_default", "fhevc_p_tree_select", "fhevc_p_tree_select_device", "fhevc_p_tree_frame",
     "fhevc_motion_merge", "fhevc_motion_merge_device", "fhevc_p_tree_select_merge", "fhevc_p_tree_select_merge_device", "fhevc_p_tree_merge_frame",
     "fhevc_motion_merge_pu", "fhevc_motion_merge_pu_device", "fhevc_pu_shape_select_merge", "fhevc_pu_shape_select_merge_device", "fhevc_p_tree_merge_pu_frame",
+    "fhevc_motion_skip", "fhevc_motion_skip_device", "fhevc_p_tree_select_skip", "fhevc_p_tree_select_skip_device",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -94,6 +95,11 @@ SHAPE_DTYPE = np.dtype([("cost_2Nx2N", np.uint32), ("cost_best", np.uint32), ("c
 # fhevc_motion_merge_node: the cheapest merge candidate of a CU node (src: 0..4 = L, A, AR, BL, AL, 5 = the zero vector; idx / num: its place in / the length of the list)
 MOTION_MERGE_DTYPE = np.dtype([("satd_best", np.uint32), ("cost_best", np.uint32), ("mvx", np.int16), ("mvy", np.int16), ("idx", np.uint8), ("num", np.uint8),
                                ("src", np.uint8), ("pad", np.uint8)])
+# fhevc_motion_skip_node: the transformed and quantised residual of a CU node at its merge vector (flags: SKIP_ZERO_PLAIN under the P-slice dead zone,
+# SKIP_ZERO_HALF under the rounding RDOQ starts from)
+MOTION_SKIP_DTYPE = np.dtype([("coef_max", np.uint32), ("level_sum", np.uint32), ("nonzero", np.uint16), ("flags", np.uint8), ("pad", np.uint8),
+                              ("mvx", np.int16), ("mvy", np.int16)])
+SKIP_ZERO_PLAIN, SKIP_ZERO_HALF = 1, 2
 MERGE_L, MERGE_A, MERGE_AR, MERGE_BL, MERGE_AL, MERGE_ZERO = 0, 1, 2, 3, 4, 5
 # fhevc_p_tree_node: one record per CU node (flags: 1 split_sure, 2 stop_sure, 4 CROSSING, 8 ABSENT, 16 own available, 32 kids available)
 TREE_DTYPE = np.dtype([("cost_own", np.uint32), ("cost_kids", np.uint32), ("cost_tree", np.uint32), ("flags", np.uint8), ("level", np.uint8), ("pad", np.uint8, (2,))])
@@ -240,6 +246,10 @@ def load_library(path=None):
     lib.fhevc_motion_merge_pu_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.fhevc_pu_shape_select_merge.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(PuShapeRule), vp, vp, vp]
     lib.fhevc_pu_shape_select_merge_device.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), vp, vp, vp, vp]
+    lib.fhevc_motion_skip.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.fhevc_motion_skip_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.fhevc_p_tree_select_skip.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp]
+    lib.fhevc_p_tree_select_skip_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp, vp]
     lib.fhevc_p_tree_merge_pu_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), vp, vp, vp, vp]
     lib.fhevc_predict_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, vp, vp]
     lib.fhevc_alloc_host.argtypes = [vp, C.c_size_t]
@@ -351,6 +361,26 @@ def p_tree_select_merge(shapes, merge, width, height, rule=None, with_tree=False
                                            tree[c].ctypes.data if with_tree else None)
         if rc != OK:
             raise FastHevcError(rc, "fhevc_p_tree_select_merge")
+    return (dmin, dmax, tree) if with_tree else (dmin, dmax)
+
+
+def p_tree_select_skip(shapes, merge, skip, skip_mask, width, height, rule=None, with_tree=False):
+    """p_tree_select_merge with the skip records [numCtus, 85] MOTION_SKIP_DTYPE: a node whose own cost is the merge cost and whose flags carry a bit of
+    skip_mask (0..3) is not descended"""
+    lib = load_library()
+    rule = rule if rule is not None else p_tree_rule_default()
+    shapes, merge, skip = np.ascontiguousarray(shapes), np.ascontiguousarray(merge), np.ascontiguousarray(skip)
+    assert shapes.dtype.itemsize == 16 and merge.dtype.itemsize == 16 and skip.dtype.itemsize == 16 and merge.shape == shapes.shape == skip.shape
+    cw = (width + 63) // 64
+    n = shapes.shape[0]
+    dmin, dmax = np.zeros((n, 256), np.uint8), np.zeros((n, 256), np.uint8)
+    tree = np.zeros((n, NODES_PER_CTU), TREE_DTYPE) if with_tree else None
+    for c in range(n):
+        vw, vh = min(64, width - (c % cw) * 64), min(64, height - (c // cw) * 64)
+        rc = lib.fhevc_p_tree_select_skip(shapes[c].ctypes.data, merge[c].ctypes.data, skip[c].ctypes.data, skip_mask, vw, vh, C.byref(rule), dmin[c].ctypes.data,
+                                          dmax[c].ctypes.data, tree[c].ctypes.data if with_tree else None)
+        if rc != OK:
+            raise FastHevcError(rc, "fhevc_p_tree_select_skip")
     return (dmin, dmax, tree) if with_tree else (dmin, dmax)
 
 
@@ -648,6 +678,23 @@ class Context:
         self._check(self.lib.fhevc_motion_merge_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range,
                                                        d_refined, d_out, stream))
 
+    def motion_skip(self, cur_plane, ref_plane, merge, origin=0, stride=None, qp=32, max_range=4):
+        """config 4: the zero-residual test of every CU node at the vector of its merge record [numCtus, 85] (MOTION_MERGE_DTYPE, as motion_merge returns
+        them for the same planes; only cost_best, mvx, mvy are read) -> [numCtus, 85] MOTION_SKIP_DTYPE.  max_range: the merge stage's."""
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
+        merge = np.ascontiguousarray(merge).reshape(-1)
+        assert merge.dtype.itemsize == 16 and merge.size == self.num_ctus * NODES_PER_CTU
+        out = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_SKIP_DTYPE)
+        self._check(self.lib.fhevc_motion_skip(self.h, cur, ref, stride, qp, max_range, merge.ctypes.data, out.ctypes.data))
+        return out.reshape(self.num_ctus, NODES_PER_CTU)
+
+    def motion_skip_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_merge, d_out, rows=None, stream=None, qp=32, max_range=4):
+        """frames 1.. of the batch, each predicted from the frame before it at the vectors of d_merge (what motion_merge_device wrote for the same rows:
+        85 per CTU), transformed and quantised at qp; d_out: (num_frames - 1) * band CTUs * 85 skip records (16 B).  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_motion_skip_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range,
+                                                      d_merge, d_out, stream))
+
     def motion_merge_pu(self, cur_plane, ref_plane, refined, origin=0, stride=None, qp=32, max_range=4, with_pus=True, with_small=True):
         """config 4: the cheapest merge candidate of every PU from the refined square nodes [numCtus, 85] (MOTION_QPEL_DTYPE; only cost_best, mvx, mvy are
         read) -> ([numCtus, 124], [numCtus, 384]) MOTION_MERGE_DTYPE in the orders of motion_pu_index / motion_pu_small_index; None for a family not asked for"""
@@ -865,6 +912,13 @@ class Context:
         rb, re = rows if rows is not None else (0, self.ctus_y)
         self._check(self.lib.fhevc_p_tree_select_merge_device(self.h, d_shapes, d_merge, num_pictures, rb, re, C.byref(rule) if rule is not None else None,
                                                               d_depth_min, d_depth_max, d_tree, stream))
+
+    def p_tree_select_skip_device(self, d_shapes, d_merge, d_skip, skip_mask, num_pictures, d_depth_min=None, d_depth_max=None, d_tree=None, rows=None, stream=None,
+                                  rule=None):
+        """p_tree_select_merge_device with the skip records of motion_skip_device (85 per CTU, compact over the same rows) and skip_mask 0..3.  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_p_tree_select_skip_device(self.h, d_shapes, d_merge, d_skip, skip_mask, num_pictures, rb, re,
+                                                             C.byref(rule) if rule is not None else None, d_depth_min, d_depth_max, d_tree, stream))
 
     def p_tree_merge_pu_frame(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=8, coarse_range=0, shape_rule=None, tree_rule=None,
                               with_shapes=False, with_merge=False):

@@ -185,9 +185,9 @@ int fhevc_enable_kernel_timing(fhevc_ctx* c, int on)
 
 int fhevc_kernel_timing(fhevc_ctx* c, int which, int reset, double* avg_ms, uint64_t* launches)
 {
-  // 14, 16, 18 and 20 stay rejected: callers probe them as the first numbers behind the slots of the partition-size selection, of the centred chain, of the tree
-  // and of the merge stage
-  if (!c || which < 0 || which > 21 || which == 14 || which == 16 || which == 18 || which == 20) return FHEVC_E_INVALID;
+  // 14, 16, 18, 20 and 22 stay rejected: callers probe them as the first numbers behind the slots of the partition-size selection, of the centred chain, of the
+  // tree and of the two merge stages
+  if (!c || which < 0 || which > 23 || which == 14 || which == 16 || which == 18 || which == 20 || which == 22) return FHEVC_E_INVALID;
   time_resolve(c);
   if (avg_ms) *avg_ms = c->launches[which] ? c->sum_ms[which] / (double)c->launches[which] : 0.0;
   if (launches) *launches = c->launches[which];

@@ -50,9 +50,9 @@ struct fhevc_ctx {
   bool timing = false;
   std::vector<TimedLaunch> pending;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-  // per timing slot (14, 16, 18 and 20 are not in use); config 4's slots and its staging buffers d_pair .. d_p_maps: the tables in fhevc_motion_api.hip
-  double sum_ms[22] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-  uint64_t launches[22] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+  // per timing slot (14, 16, 18, 20 and 22 are not in use); config 4's slots and its staging buffers d_pair .. d_p_maps: the tables in fhevc_motion_api.hip
+  double sum_ms[24] = {};
+  uint64_t launches[24] = {};
   double* d_act = nullptr;
   int16_t* d_pair = nullptr;
   FhevcMotionNode *d_motion = nullptr, *d_motion_pu = nullptr, *d_motion_pu_small = nullptr, *d_centres = nullptr;

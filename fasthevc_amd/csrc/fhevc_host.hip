@@ -351,8 +351,9 @@ void fhevc_p_tree_rule_default(fhevc_p_tree_rule* rule)
 }  // extern "C"
 
 // merge: null for fhevc_p_tree_select; otherwise the CTU's 85 merge records, of which cost_best is read
+// skip: null but for fhevc_p_tree_select_skip; otherwise the CTU's 85 skip records, of which flags is read under skip_mask (HM's EarlyCU, TEncCu.cpp:892)
 static int p_tree_select(const fhevc_pu_shape_node* shapes, const fhevc_motion_merge_node* merge, int valid_w, int valid_h, const fhevc_p_tree_rule* rule, uint8_t* depth_min,
-                         uint8_t* depth_max, fhevc_p_tree_node* tree)
+                         uint8_t* depth_max, fhevc_p_tree_node* tree, const fhevc_motion_skip_node* skip = nullptr, int skip_mask = 0)
 {
   if (!shapes || !rule || (!depth_min && !depth_max && !tree) || valid_w < 8 || valid_w > 64 || valid_h < 8 || valid_h > 64 || fhevc_p_tree_rule_error(*rule))
     return FHEVC_E_INVALID;
@@ -393,7 +394,10 @@ static int p_tree_select(const fhevc_pu_shape_node* shapes, const fhevc_motion_m
       split = kids + (uint64_t)rule->split_abs[lvl] + ((kids * (uint64_t)rule->split_q8[lvl]) >> 8) < own;
       stop = own + (uint64_t)rule->stop_abs[lvl] + ((own * (uint64_t)rule->stop_q8[lvl]) >> 8) <= kids;
     }
-    n.flags = (uint8_t)((split ? 1 : 0) | (stop ? 2 : 0) | (!inside ? 4 : 0) | (own != mark ? 16 : 0) | (kids != mark ? 32 : 0) | (merged ? 64 : 0));
+    // a merged node with an all-zero residual is a skip: its children are never visited, whatever they would cost
+    const bool early = merged && skip && (skip[k].flags & skip_mask) != 0;
+    if (early) { n.cost_tree = n.cost_own; split = false; stop = true; }
+    n.flags = (uint8_t)((split ? 1 : 0) | (stop ? 2 : 0) | (!inside ? 4 : 0) | (own != mark ? 16 : 0) | (kids != mark ? 32 : 0) | (merged ? 64 : 0) | (early ? 128 : 0));
     sure[k] = !inside || split;
     maybe[k] = !inside || !stop;
   }
@@ -431,6 +435,13 @@ int fhevc_p_tree_select_merge(const fhevc_pu_shape_node* shapes, const fhevc_mot
 {
   if (!merge) return FHEVC_E_INVALID;
   return p_tree_select(shapes, merge, valid_w, valid_h, rule, depth_min, depth_max, tree);
+}
+
+int fhevc_p_tree_select_skip(const fhevc_pu_shape_node* shapes, const fhevc_motion_merge_node* merge, const fhevc_motion_skip_node* skip, int skip_mask, int valid_w,
+                             int valid_h, const fhevc_p_tree_rule* rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_p_tree_node* tree)
+{
+  if (!merge || !skip || skip_mask < 0 || skip_mask > 3) return FHEVC_E_INVALID;
+  return p_tree_select(shapes, merge, valid_w, valid_h, rule, depth_min, depth_max, tree, skip, skip_mask);
 }
 
 int fhevc_p_motion_compensated_depth(const fhevc_motion_node* nodes, const uint8_t* prev_map, int width, int height, int ctu, uint8_t* out)

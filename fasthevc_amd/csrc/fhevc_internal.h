@@ -244,6 +244,28 @@ hipError_t fhevc_launch_motion_merge(const FhevcFrames& fr, int max_range, const
 hipError_t fhevc_launch_motion_merge_pu(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionQpelNode* d_refined,
                                         FhevcMotionMergeNode* d_out_pus, FhevcMotionMergeNode* d_out_small, int num_cus, hipStream_t stream);
 
+// ---- the zero-residual (skip) test per CU node at its merge vector (k_motion_skip.hip; config 4) --------------------------
+struct FhevcMotionSkipNode { uint32_t coef_max, level_sum; uint16_t nonzero; uint8_t flags, pad; int16_t mvx, mvy; };
+static_assert(sizeof(FhevcMotionSkipNode) == 16, "skip record: 16 bytes without padding");
+// HM's scalar quantiser per TU size 8, 16, 32 (index log2 N - 3), computed on the host: level = (|c| * scale + add) >> qbits
+struct FhevcSkipQuant { uint32_t scale, qbits[3], add_plain[3], add_half[3]; };
+inline FhevcSkipQuant fhevc_skip_quant(int qp, int bit_depth)
+{
+  static const uint32_t scales[6] = { 26214, 23302, 20560, 18396, 16384, 14564 };   // g_quantScales
+  const int qpp = qp + 6 * (bit_depth - 8);
+  FhevcSkipQuant q;
+  q.scale = scales[qpp % 6];
+  for (int i = 0; i < 3; ++i) {
+    q.qbits[i] = (uint32_t)(14 + qpp / 6 + (15 - bit_depth - (i + 3)));   // 16 .. 26
+    q.add_plain[i] = 85u << (q.qbits[i] - 9);                              // the P-slice dead zone
+    q.add_half[i] = 1u << (q.qbits[i] - 1);                                // the rounding RDOQ starts from
+  }
+  return q;
+}
+// fr, max_range as fhevc_launch_motion_merge; d_merge: (num_frames - 1) * band CTUs * 85 merge records of which cost_best, mvx and mvy are read; d_out: as many
+hipError_t fhevc_launch_motion_skip(const FhevcFrames& fr, int max_range, const FhevcSkipQuant& q, const FhevcMotionMergeNode* d_merge, FhevcMotionSkipNode* d_out,
+                                    int num_cus, hipStream_t stream);
+
 // ---- ... and of the PUs' vectors (k_motion_refine_pu.hip; config 4) --------------------------------------------------
 // fr, max_range (1 .. FHEVC_MOTION_WIDE_MAX_RANGE: up to FHEVC_MOTION_MAX_RANGE the MR = 8 layout, above it the MR = 64 layout with its window in dynamic LDS),
 // cost as fhevc_launch_motion_refine; d_pus / d_out_pus: (num_frames - 1) * band CTUs * 124 entries in the order of fhevc_motion_pu_index, d_pus_small /
@@ -335,6 +357,11 @@ hipError_t fhevc_launch_p_tree(const FhevcFrames& fr, const FhevcPTreeRule& rule
 // record's flags says that the merge cost is the one taken
 hipError_t fhevc_launch_p_tree_merge(const FhevcFrames& fr, const FhevcPTreeRule& rule, const FhevcPuShapeNode* d_shapes, const FhevcMotionMergeNode* d_merge,
                                      uint8_t* d_depth_min, uint8_t* d_depth_max, FhevcPTreeNode* d_tree, int num_cus, hipStream_t stream);
+// ... and with the skip records of fhevc_launch_motion_skip (never null; only flags, byte 10, is read): an INSIDE node of level 0..2 whose own cost is the
+// merge cost and whose flags carry a bit of skip_mask (0..3) is not descended -- tree = own, stop_sure, bit 7
+hipError_t fhevc_launch_p_tree_skip(const FhevcFrames& fr, const FhevcPTreeRule& rule, const FhevcPuShapeNode* d_shapes, const FhevcMotionMergeNode* d_merge,
+                                    const FhevcMotionSkipNode* d_skip, int skip_mask, uint8_t* d_depth_min, uint8_t* d_depth_max, FhevcPTreeNode* d_tree, int num_cus,
+                                    hipStream_t stream);
 
 // ---- adaptive-QP pre-analysis (k_preanalyze.hip) -----------------------------------------------------------
 // d_activity: per frame parts_per_frame doubles, layers concatenated (layer d: ceil(H/P) x ceil(W/P), P = 64 >> d)

@@ -2,6 +2,7 @@
 // that stage one picture pair, run device forms on the context's own stream and bring the results back.  Host-side C++ only, as fhevc_api.hip.
 #include "fhevc_ctx.h"
 
+#include <cstddef>
 #include <cstring>
 
 namespace {
@@ -44,12 +45,15 @@ template <class P> struct Kernel;
 template <> struct Kernel<fhevc_motion_node> { using T = FhevcMotionNode; };
 template <> struct Kernel<fhevc_motion_qpel_node> { using T = FhevcMotionQpelNode; };
 template <> struct Kernel<fhevc_motion_merge_node> { using T = FhevcMotionMergeNode; };
+template <> struct Kernel<fhevc_motion_skip_node> { using T = FhevcMotionSkipNode; };
 template <> struct Kernel<fhevc_pu_shape_node> { using T = FhevcPuShapeNode; };
 template <> struct Kernel<fhevc_p_tree_node> { using T = FhevcPTreeNode; };
 template <class P> typename Kernel<P>::T* kn(P* p) { return reinterpret_cast<typename Kernel<P>::T*>(p); }
 template <class P> const typename Kernel<P>::T* kn(const P* p) { return reinterpret_cast<const typename Kernel<P>::T*>(p); }
 static_assert(sizeof(fhevc_motion_node) == 16 && sizeof(FhevcMotionNode) == 16 && sizeof(fhevc_motion_qpel_node) == 16 && sizeof(FhevcMotionQpelNode) == 16, "node layouts");
 static_assert(sizeof(fhevc_motion_merge_node) == 16 && sizeof(FhevcMotionMergeNode) == 16 && sizeof(fhevc_pu_shape_node) == 16 && sizeof(FhevcPuShapeNode) == 16, "record layouts");
+static_assert(sizeof(fhevc_motion_skip_node) == 16 && offsetof(fhevc_motion_skip_node, nonzero) == 8 && offsetof(fhevc_motion_skip_node, flags) == 10 &&
+              offsetof(fhevc_motion_skip_node, mvx) == 12 && offsetof(FhevcMotionSkipNode, flags) == 10 && offsetof(FhevcMotionSkipNode, mvx) == 12, "skip record layout");
 static_assert(FHEVC_PUS_PER_CTU == FHEVC_PUS && FHEVC_PUS_SMALL_PER_CTU == FHEVC_PUS_SMALL, "PU counts");
 
 // ---- how every device form over a batch of picture pairs opens ----
@@ -90,8 +94,10 @@ int device_form(fhevc_ctx* c, bool args_ok, const char* bad_args, const Batch& b
 //   buffer                   entries per CTU   what the host forms keep in it
 //   d_pair                   --                the reference and the current picture, two planes of pair_plane() samples: a batch of two frames
 //   d_motion                 85  (nodes)       the integer nodes; once the refinement has read them, the partition-size records of the frame chains;
-//                                              the merge records of fhevc_motion_merge; in its head, the one centre per CTU of fhevc_motion_centres
-//   d_qpel                   85                the refined nodes (the input of fhevc_motion_merge)
+//                                              the merge records of fhevc_motion_merge, and those fhevc_motion_skip reads; in its head, the one centre per
+//                                              CTU of fhevc_motion_centres
+//   d_qpel                   85                the refined nodes (the input of fhevc_motion_merge); the skip records of fhevc_motion_skip, which has no
+//                                              refined nodes: the buffer is dead there
 //   d_motion_pu, d_qpel_pu   124 (PUs)         the integer and the refined PUs; once the refinement has read the integer PUs, the merge records
 //                                              of fhevc_p_tree_merge_frame in the head of d_motion_pu (85 of the 124 entries per CTU)
 //   d_motion_pu_small,       384 (small PUs)   the integer and the refined small PUs
@@ -103,7 +109,7 @@ int device_form(fhevc_ctx* c, bool args_ok, const char* bad_args, const Batch& b
 //
 // The timing slots (fhevc_kernel_timing) of the launches below: 4 fhevc_motion_search, 5 the P rule, 7 fhevc_motion_refine, 8 / 9 the searches of the PUs / the
 // small PUs, 10 fhevc_motion_refine_pu, 11 / 12 the wide search / refinement, 13 the partition sizes, 15 the centres and everything centred, 17 the tree, 19 the merge stage,
-// 21 the merge stage per PU
+// 21 the merge stage per PU, 23 the zero-residual test
 struct Family { int per_ctu; FhevcMotionNode* fhevc_ctx::*found; FhevcMotionQpelNode* fhevc_ctx::*refined; };
 constexpr Family kNodes = { FHEVC_NODES, &fhevc_ctx::d_motion, &fhevc_ctx::d_qpel }, kPus = { FHEVC_PUS, &fhevc_ctx::d_motion_pu, &fhevc_ctx::d_qpel_pu },
                  kSmall = { FHEVC_PUS_SMALL, &fhevc_ctx::d_motion_pu_small, &fhevc_ctx::d_qpel_pu_small }, kCentres = { 1, &fhevc_ctx::d_centres, nullptr };
@@ -467,6 +473,33 @@ int fhevc_motion_merge(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref
   return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_merge_device, qp, max_range, d_refined, d_out, c->stream); });
 }
 
+// ---- the zero-residual (skip) test per CU node at its merge vector (k_motion_skip.hip) ----
+
+int fhevc_motion_skip_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                             int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_merge_node* d_merge,
+                             fhevc_motion_skip_node* d_out, void* stream)
+{
+  const Batch b{ d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp };
+  // the quantiser's numbers per TU size travel with the launch: nothing of the context is read or written by it
+  return device_form(c, d_luma && d_merge && d_out, "bad skip-stage arguments", b, max_range, FHEVC_MOTION_WIDE_MAX_RANGE, "bad skip-stage arguments (max_range 1..64)",
+                     stream, 23, "fhevc_launch_motion_skip", [&](const FhevcFrames& fr, hipStream_t s) {
+    return fhevc_launch_motion_skip(fr, max_range, fhevc_skip_quant(qp, c->cfg.bit_depth), kn(d_merge), kn(d_out), c->num_cus, s);
+  }, [&]() -> const char* {
+    return (long long)(num_frames - 1) * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL ? "more than 2^31 - 1 CTUs" : nullptr;
+  });
+}
+
+int fhevc_motion_skip(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                      const fhevc_motion_merge_node* merge, fhevc_motion_skip_node* out)
+{
+  const int rc = open_host_form(c, cur_luma && ref_luma && merge && out, stride_samples, qp, max_range, FHEVC_MOTION_WIDE_MAX_RANGE, "bad skip-stage arguments");
+  if (rc != GO) return rc;
+  HostForm h(c);
+  const fhevc_motion_merge_node* d_merge = h.in(c->d_motion, h.bytes(kNodes), merge, h.bytes(kNodes));
+  fhevc_motion_skip_node* d_out = h.out(c->d_qpel, h.bytes(kNodes), out, h.bytes(kNodes));   // no refined nodes in this call: their buffer is dead
+  return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_skip_device, qp, max_range, d_merge, d_out, c->stream); });
+}
+
 // ---- merge-candidate costs per PU from the refined nodes (k_motion_merge_pu.hip) ----
 
 int fhevc_motion_merge_pu_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
@@ -721,12 +754,14 @@ int fhevc_p_shape_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* re
 }
 
 // ---- P-picture depth ranges from the selection's records over a device-resident batch (k_p_tree.hip; the host form: fhevc_host.hip) ----
-// d_merge: null for fhevc_p_tree_select_device; with_merge says which of the two entry points is asking
+// d_merge: null for fhevc_p_tree_select_device; with_merge / with_skip say which of the three entry points is asking (the skip variant takes the merge records too)
 static int p_tree_select_on(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, const fhevc_motion_merge_node* d_merge, bool with_merge, int num_pictures, int ctu_row_begin,
-                            int ctu_row_end, const fhevc_p_tree_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream)
+                            int ctu_row_end, const fhevc_p_tree_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream,
+                            bool with_skip = false, const fhevc_motion_skip_node* d_skip = nullptr, int skip_mask = 0)
 {
   if (!c) return FHEVC_E_INVALID;
   if (!d_shapes || (with_merge && !d_merge) || (!d_depth_min && !d_depth_max && !d_tree)) return fail(c, FHEVC_E_INVALID, "bad tree-decision arguments");
+  if (with_skip && (!d_skip || skip_mask < 0 || skip_mask > 3)) return fail(c, FHEVC_E_INVALID, "bad tree-decision arguments (skip records, skip_mask 0..3)");
   // (records have no sample layout: the checks of the pictures' number and the band)
   if (const char* bad = batch_error(c, 2, c->cfg.width, 0, num_pictures, 1, ctu_row_begin, ctu_row_end, 0, false)) return fail(c, FHEVC_E_INVALID, bad);
   static_assert(sizeof(fhevc_p_tree_rule) == sizeof(FhevcPTreeRule) && sizeof(fhevc_p_tree_node) == sizeof(FhevcPTreeNode), "tree-decision layouts");
@@ -737,6 +772,10 @@ static int p_tree_select_on(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, c
   if ((long long)num_pictures * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "more than 2^31 - 1 CTUs");
   if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
   const FhevcFrames fr = frames_of(c, nullptr, 1, c->cfg.width, 0, num_pictures, ctu_row_begin, ctu_row_end);
+  if (with_skip)
+    return launch_on(c, stream, 17, "fhevc_launch_p_tree_skip", [&](hipStream_t s) {
+      return fhevc_launch_p_tree_skip(fr, r, kn(d_shapes), kn(d_merge), kn(d_skip), skip_mask, d_depth_min, d_depth_max, kn(d_tree), c->num_cus, s);
+    });
   if (with_merge)
     return launch_on(c, stream, 17, "fhevc_launch_p_tree_merge", [&](hipStream_t s) {
       return fhevc_launch_p_tree_merge(fr, r, kn(d_shapes), kn(d_merge), d_depth_min, d_depth_max, kn(d_tree), c->num_cus, s);
@@ -756,6 +795,13 @@ int fhevc_p_tree_select_merge_device(fhevc_ctx* c, const fhevc_pu_shape_node* d_
                                      int ctu_row_end, const fhevc_p_tree_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream)
 {
   return p_tree_select_on(c, d_shapes, d_merge, true, num_pictures, ctu_row_begin, ctu_row_end, rule, d_depth_min, d_depth_max, d_tree, stream);
+}
+
+int fhevc_p_tree_select_skip_device(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, const fhevc_motion_merge_node* d_merge, const fhevc_motion_skip_node* d_skip,
+                                    int skip_mask, int num_pictures, int ctu_row_begin, int ctu_row_end, const fhevc_p_tree_rule* rule, uint8_t* d_depth_min,
+                                    uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream)
+{
+  return p_tree_select_on(c, d_shapes, d_merge, true, num_pictures, ctu_row_begin, ctu_row_end, rule, d_depth_min, d_depth_max, d_tree, stream, true, d_skip, skip_mask);
 }
 
 // with_merge: fhevc_p_tree_merge_frame -- the merge stage between refinement and tree; with_merge_pu: fhevc_p_tree_merge_pu_frame -- behind it the merge stage

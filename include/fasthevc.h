@@ -760,7 +760,8 @@ typedef struct {
   uint32_t cost_kids;       /* kids[k] */
   uint32_t cost_tree;       /* tree[k] */
   uint8_t  flags;           /* bit 0 split_sure, bit 1 stop_sure, bit 2 CROSSING, bit 3 ABSENT, bit 4 own available (!= MARK), bit 5 kids available;
-                             * bit 6 (fhevc_p_tree_select_merge* only): own is the merge cost */
+                             * bit 6 (fhevc_p_tree_select_merge* and fhevc_p_tree_select_skip* only): own is the merge cost;
+                             * bit 7 (fhevc_p_tree_select_skip* only): a skip, not descended */
   uint8_t  level;           /* l */
   uint8_t  pad[2];          /* written 0 */
 } fhevc_p_tree_node;        /* 16 bytes; an ABSENT node gets three MARKs and bit 3 only */
@@ -858,8 +859,8 @@ typedef struct {
  * other on one stream without a host synchronisation.  FHEVC_E_INVALID with a fhevc_last_error text (nothing is launched or written): a null context, d_luma,
  * d_refined or d_out, num_frames < 2, qp outside 0..51, max_range outside 1..64, stride_samples < width, a bad band, overlapping frames, uint8 planes on a
  * context above 8 bit -- whatever fhevc_motion_refine_device rejects.  Timed under slot 19 of fhevc_kernel_timing.
- * NOT covered: the temporal candidate, candidates from neighbours of a finer level than the node's own, a window staged around per-CTU centres, skip
- * detection.  (The rectangular PUs, with HM's second-PU rules: fhevc_motion_merge_pu*, further below.)  The encoder hook does not consume this output. */
+ * NOT covered: the temporal candidate, candidates from neighbours of a finer level than the node's own, a window staged around per-CTU centres.  (Skip
+ * detection: fhevc_motion_skip*, further below.)  (The rectangular PUs, with HM's second-PU rules: fhevc_motion_merge_pu*, further below.)  The encoder hook does not consume this output. */
 int  fhevc_motion_merge_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
                                int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_qpel_node* d_refined,
                                fhevc_motion_merge_node* d_out, void* stream);
@@ -917,7 +918,8 @@ int  fhevc_p_tree_merge_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int
  * empty band writes nothing.  Asynchronous, allocates nothing, keeps no state in HBM (the bit costs travel by value).  The kernel has
  * fhevc_motion_refine_pu's mapping (workgroup = CTU over a persistent grid, 26 passes dealt to four waves, lane = 8x8 tile) and the merge stage's list in
  * registers; the 123 nodes that can be a neighbour are parked in LDS once per CTU.  Timed under slot 21 of fhevc_kernel_timing.
- * NOT covered: the temporal candidate, candidates from finer-level neighbours, Log2ParMrgLevel above 2, skip detection, a window around per-CTU centres.
+ * NOT covered: the temporal candidate, candidates from finer-level neighbours, Log2ParMrgLevel above 2, per-PU skip tests (the CU nodes' own:
+ * fhevc_motion_skip*, further below), a window around per-CTU centres.
  * The encoder hook does not consume this output. */
 int  fhevc_motion_merge_pu_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
                                   int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_qpel_node* d_refined,
@@ -952,6 +954,67 @@ int  fhevc_p_tree_merge_pu_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const 
                                  uint8_t* depth_max /* numCtus * 256 */, fhevc_pu_shape_node* shapes /* numCtus * 85 or NULL */,
                                  fhevc_motion_merge_node* merge /* numCtus * 85 or NULL */);
 
+/* ---- config 4 (P slices): the zero-residual (skip) test per CU node (k_motion_skip.hip) -----------------------------------------------------------
+ * In HM a CU whose best mode is merge with an all-zero residual is a skip: TEncCu.cpp:892 (EarlyCU) does not descend below it, and :610-637 with
+ * :1444-1468 (EarlySkipDetection) do not try its other partition sizes.  Whether a residual quantises to zero is an exact integer question: HM's forward
+ * transform and its dead-zone quantiser are closed-form integer arithmetic.  This entry point answers it for the vector a node's merge record holds.
+ *   Input per CTU: the 85 fhevc_motion_merge_node records that fhevc_motion_merge_device wrote for the same pictures and band; only cost_best (the marker
+ * test), mvx and mvy are read.  qp 0..51, max_range 1..64.  Planes, band, stream, frame pairing (frame f is predicted from frame f - 1), the
+ * compact-over-the-band record layout and the rejected calls are exactly fhevc_motion_merge_device's.
+ *   A node k of level l (s = 64 >> l) is valid iff it is INSIDE, its merge record is no marker (cost_best != 0xFFFFFFFF), and |mvx| and |mvy| are both
+ * <= 4 max_range + 3, so that no input byte can send a read outside the staged window.
+ *   Step 1, the residual: r = original - fhevc_motion_refine's prediction at (mvx, mvy): the previous ORIGINAL picture through HEVC's 8-tap interpolation
+ * in the one arithmetic form, coordinates clamped to the picture.
+ *   Step 2, the transform: HM's forward transform xTrMxN (TComTrQuant.cpp:860-915).  TU size N = min(s, 32): a 64x64 node is four 32x32 TUs
+ * (QuadtreeTULog2MaxSize 5, cfg/encoder_lowdelay_P_main.cfg:12), every other node is one TU; the TU tree is not searched.  The DCT, never the DST;
+ * maxLog2TrDynamicRange 15, so shift_1st = log2 N + bit_depth - 9 over the rows and shift_2nd = log2 N + 6 over the columns; the matrices are the
+ * reference's g_aiT8 / g_aiT16 / g_aiT32; rounding as partialButterfly8 / 16 / 32: add 1 << (shift - 1), then an arithmetic shift right.
+ *   Step 3, the quantiser: HM's scalar quantiser without scaling lists (TComTrQuant.cpp:1186-1232).  QP' = qp + 6 (bit_depth - 8), per = QP' / 6,
+ * rem = QP' % 6, scale = g_quantScales[rem] = {26214, 23302, 20560, 18396, 16384, 14564}, qbits = 14 + per + (15 - bit_depth - log2 N),
+ * level(c) = (|c| * scale + add) >> qbits evaluated in 64 bits, under two offsets: add_plain = 85 << (qbits - 9), the P-slice dead zone (:1215), and
+ * add_half = 1 << (qbits - 1), the rounding from which RDOQ takes its starting levels (uiMaxAbsLevel, :2257).  If every starting level is 0, RDOQ never
+ * finds a last position (:2264) and the block is zero: the second test is a SUFFICIENT condition for cbf = 0 under the reference's RDOQ : 1.
+ *   Field order (pinned: 16 bytes without padding): */
+typedef struct {
+  uint32_t coef_max;        /* max |c| over the node's TU or TUs; depends on no QP */
+  uint32_t level_sum;       /* sum of level(c) under add_plain: uiAbsSum of xQuant */
+  uint16_t nonzero;         /* number of coefficients with level != 0 under add_plain, 0..4096 */
+  uint8_t  flags;           /* bit 0: zero under add_plain (nonzero == 0); bit 1: zero under add_half.  Bit 1 implies bit 0 */
+  uint8_t  pad;             /* written 0 */
+  int16_t  mvx, mvy;        /* the vector tested, copied from the merge record */
+} fhevc_motion_skip_node;   /* 16 bytes; an invalid node gets coef_max = level_sum = 0xFFFFFFFF, nonzero = 0xFFFF, flags = 0, pad = 0 and a zero vector */
+/* Device form: d_merge, d_out: (num_frames - 1) * band CTUs * 85 records, compact over the band; the output is written over exactly that extent, an empty
+ * band writes nothing.  The kernel keeps the merge kernel's outer mapping (a workgroup of four waves per CTU over a persistent grid sized by the
+ * device's own occupancy answer, the window of the refinement in LDS in both layouts, lane = one 8x8 tile, one prediction per node) and runs both passes of
+ * the transform through LDS buffers laid over the dead window, as 16-bit dot products -- exact: no intermediate exceeds 32 760.  The quantiser's numbers
+ * are computed on the host and travel by value.  Asynchronous with respect to the host, allocates nothing, keeps NO state in HBM between calls: calls with
+ * different QPs and ranges may be in flight on two streams, and the merge stage and this one may follow each other on one stream without a host
+ * synchronisation.  FHEVC_E_INVALID with a fhevc_last_error text (nothing is launched or written): a null context, d_luma, d_merge or d_out, and whatever
+ * fhevc_motion_merge_device rejects.  Timed under slot 23 of fhevc_kernel_timing.
+ * NOT covered: per-PU skip tests, the TU quad-tree, transform skip, sign hiding, chroma.  The encoder hook does not consume this output. */
+int  fhevc_motion_skip_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                              int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, const fhevc_motion_merge_node* d_merge,
+                              fhevc_motion_skip_node* d_out, void* stream);
+/* one picture pair, host buffers (both planes with the same stride), synchronous, as fhevc_motion_merge; merge, out: numCtus * 85 */
+int  fhevc_motion_skip(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range,
+                       const fhevc_motion_merge_node* merge, fhevc_motion_skip_node* out);
+
+/* The tree decision that STOPS at a skip: fhevc_p_tree_select_merge[_device] with two more arguments, the CTU's 85 fhevc_motion_skip_node records (never
+ * NULL; on the device compact over the band like d_shapes; any 4-byte alignment; only flags is read) and skip_mask (0..3: which of the two zero tests
+ * count).  ONE changed rule, HM's EarlyCU (TEncCu.cpp:892): for an INSIDE node of level 0..2 whose own cost is the merge cost (bit 6 of the tree flags as
+ * defined above) and whose skip.flags & skip_mask != 0
+ *   tree[k] = own[k] whatever kids is -- HM never visits the children --, stop_sure = 1, split_sure = 0, and bit 7 of the record's flags is set;
+ * kids[k] is still recorded.  Everything else is the existing definition; with skip_mask 0, or with no record carrying a masked bit, the output is byte for
+ * byte fhevc_p_tree_select_merge[_device]'s.  The device form is a further instantiation of k_p_tree.hip (one more byte load per lane and round), timed
+ * under slot 17.  The host form needs no context.  FHEVC_E_INVALID: what fhevc_p_tree_select_merge[_device] rejects, a null skip pointer, skip_mask
+ * outside 0..3. */
+int  fhevc_p_tree_select_skip(const fhevc_pu_shape_node* shapes /* 85 */, const fhevc_motion_merge_node* merge /* 85 */,
+                              const fhevc_motion_skip_node* skip /* 85 */, int skip_mask, int valid_w, int valid_h, const fhevc_p_tree_rule* rule,
+                              uint8_t* depth_min /* 256 or NULL */, uint8_t* depth_max /* 256 or NULL */, fhevc_p_tree_node* tree /* 85 or NULL */);
+int  fhevc_p_tree_select_skip_device(fhevc_ctx* ctx, const fhevc_pu_shape_node* d_shapes, const fhevc_motion_merge_node* d_merge,
+                                     const fhevc_motion_skip_node* d_skip, int skip_mask, int num_pictures, int ctu_row_begin, int ctu_row_end,
+                                     const fhevc_p_tree_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream);
+
 /* CTU-row band of rank `rank` out of `world`: rows [begin, end) */
 int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
 
@@ -966,7 +1029,8 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
  * (fhevc_motion_search_pu_centred*) and their refinements (fhevc_motion_refine_pu_centred*), each launch counted; 14 is not a slot and is rejected like any number above 15
  * -- except 17 = the P-picture tree decision (fhevc_p_tree_select_device, fhevc_p_tree_select_merge_device), added later.  16 is not a slot either: it stays rejected
  * -- and 19 = the merge-candidate costs (fhevc_motion_merge*), added later still.  18 is not a slot: it stays rejected -- and 21 = the merge-candidate
- * costs per PU (fhevc_motion_merge_pu*).  20 is not a slot: it stays rejected, as does any number above 21 */
+ * costs per PU (fhevc_motion_merge_pu*).  20 is not a slot: it stays rejected -- and 23 = the zero-residual test (fhevc_motion_skip*).  22 is not a slot: it stays
+ * rejected, as does any number above 23.  The tree that stops at a skip (fhevc_p_tree_select_skip_device) is timed under 17 */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
 int  fhevc_enable_kernel_timing(fhevc_ctx* ctx, int on);
 
