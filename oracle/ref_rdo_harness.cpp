@@ -797,6 +797,87 @@ int href_frac_search(const int16_t* cur, const int16_t* ref, int stride, int wid
   return done == nblocks ? nblocks : -1;
 }
 
+// ---- config 4: the reference's OWN quantiser on one luma TU of n = 8, 16 or 32 -- TComTrQuant::xQuant (TComTrQuant.cpp:1126-1250), which is either the
+// plain dead-zone quantiser or, with m_useRDOQ, xRateDistOptQuant (:2119-2700) -- on a live CU of the picture encoded last in this geometry (the CU at
+// the origin of CTU 0, as href_intra_lines: width, height and depth set for the call and restored after, so that TComTURecurse's rectangle is n x n).
+//   block: n x n TCoeff.  from_residual != 0: residuals, which first go through the reference's xT (:1942-1966, as transformNxN :1510 calls it) into
+// m_plTempCoeff, handed back in coef; from_residual == 0: coefficients, straight to xQuant (coef may be NULL).
+//   rdoq == 0: m_useRDOQ = false.  rdoq != 0: m_useRDOQ = true, m_useSelectiveRDOQ = false; the bit estimates are the reference's own estimateBit on the
+// slice-initial CABAC state of a P slice at this QP (TEncSearch.cpp:4712-4717 does the same on the state it has reached), lambda = 0.57 * 2^((qp-12)/3)
+// as href_rdo_encode_next_p.  RDOQ's answer depends on both; callers read it only for which levels are zero.
+//   For the call, and restored after it: slice type P_SLICE (xQuant takes 171 or 85 by it, :1215) and slice QP qp; the CU inter with transform index 0,
+// no transform skip, no transquant bypass; PPS sign data hiding off (:1241, :2530); scaling lists off.  QpParam comes from the reference's own
+// constructor on the slice QP and the SPS's getQpBDOffset: per and rem are the reference's.
+//   levels: n x n quantised levels; abs_sum: uiAbsSum.  Returns n * n, -3 when nothing was encoded in this geometry, -1 on a bad argument.
+int href_quant_tu(int width, int height, int bit_depth, int qp, int n, int from_residual, int rdoq, const int32_t* block, int32_t* levels,
+                  int32_t* abs_sum, int32_t* coef)
+{
+  static_assert(sizeof(TCoeff) == sizeof(int32_t), "TCoeff is Int in this build");
+  Encoder* e = get_encoder(width, height, bit_depth);
+  if (!e->last) return -3;
+  if ((n != 8 && n != 16 && n != 32) || qp < 0 || qp > 51 || !block || !levels || !abs_sum || (from_residual && !coef)) return -1;
+  const int depth = n == 32 ? 1 : n == 16 ? 2 : 3;
+  TComPic* pic = e->last;
+  TComDataCU* cu = pic->getCtu(0);
+  TComSlice* slice = cu->getSlice();
+  if (slice->getPPS() != &e->pps || slice->getSPS() != &e->sps) return -1;
+  const UInt z = 0;
+  // what the call changes
+  const UChar w0 = cu->getWidth()[z], h0 = cu->getHeight()[z], d0 = cu->getDepth()[z], tr0 = cu->m_puhTrIdx[z], ts0 = cu->m_puhTransformSkip[COMPONENT_Y][z];
+  const SChar pm0 = cu->m_pePredMode[z];
+  const Bool bypass0 = cu->m_CUTransquantBypass[z];
+  const SliceType type0 = slice->getSliceType();
+  const Int qp0 = slice->getSliceQp();
+  const Bool sdh0 = e->pps.getSignDataHidingEnabledFlag();
+  const Bool rdoq0 = e->trq.m_useRDOQ, selective0 = e->trq.m_useSelectiveRDOQ, lists0 = e->trq.m_scalingListEnabledFlag;
+  const Double lambda0 = e->trq.m_dLambda;
+  cu->getWidth()[z] = (UChar)n; cu->getHeight()[z] = (UChar)n; cu->getDepth()[z] = (UChar)depth;
+  cu->m_puhTrIdx[z] = 0; cu->m_puhTransformSkip[COMPONENT_Y][z] = 0; cu->m_pePredMode[z] = MODE_INTER; cu->m_CUTransquantBypass[z] = false;
+  slice->setSliceType(P_SLICE); slice->setSliceQp(qp);
+  e->pps.setSignDataHidingEnabledFlag(false);
+  e->trq.m_useRDOQ = rdoq != 0; e->trq.m_useSelectiveRDOQ = false; e->trq.setUseScalingList(false);
+  int rc = n * n;
+  {
+    TComTURecurse tu(cu, z, (UInt)depth);
+    const TComRectangle& rect = tu.getRect(COMPONENT_Y);
+    if ((int)rect.width != n || (int)rect.height != n) rc = -1;
+    else {
+      const QpParam cQP(slice->getSliceQp(), CHANNEL_TYPE_LUMA, e->sps.getQpBDOffset(CHANNEL_TYPE_LUMA), 0, e->sps.getChromaFormatIdc());
+      if (rdoq) {
+        e->entropy.setEntropyCoder(e->rdSbac[0][CI_CURR_BEST]);
+        e->entropy.resetEntropy(slice);
+        const COEFF_SCAN_TYPE scan = COEFF_SCAN_TYPE(cu->getCoefScanIdx(z, n, n, COMPONENT_Y));
+        e->entropy.estimateBit(e->trq.m_pcEstBitsSbac, n, n, CHANNEL_TYPE_LUMA, scan);
+        e->trq.m_dLambda = 0.57 * std::pow(2.0, (qp - 12) / 3.0);
+      }
+      std::vector<TCoeff> src(block, block + (size_t)n * n), arl((size_t)n * n, 0);
+      TCoeff* in = src.data();
+      if (from_residual) {
+        std::vector<Pel> resi((size_t)n * n);
+        for (int i = 0; i < n * n; i++) resi[i] = (Pel)block[i];
+        e->trq.xT(bit_depth, tu.useDST(COMPONENT_Y), resi.data(), (UInt)n, e->trq.m_plTempCoeff, n, n, e->sps.getMaxLog2TrDynamicRange(CHANNEL_TYPE_LUMA));
+        in = e->trq.m_plTempCoeff;
+        std::memcpy(coef, in, (size_t)n * n * sizeof(TCoeff));
+      }
+      std::vector<TCoeff> dst((size_t)n * n, 0);
+      TCoeff sum = 0;
+      e->trq.xQuant(tu, in, dst.data(),
+#if ADAPTIVE_QP_SELECTION
+                    arl.data(),
+#endif
+                    sum, COMPONENT_Y, cQP);
+      std::memcpy(levels, dst.data(), (size_t)n * n * sizeof(TCoeff));
+      *abs_sum = sum;
+    }
+  }
+  e->trq.m_useRDOQ = rdoq0; e->trq.m_useSelectiveRDOQ = selective0; e->trq.setUseScalingList(lists0); e->trq.m_dLambda = lambda0;
+  e->pps.setSignDataHidingEnabledFlag(sdh0);
+  slice->setSliceType(type0); slice->setSliceQp(qp0);
+  cu->m_puhTrIdx[z] = tr0; cu->m_puhTransformSkip[COMPONENT_Y][z] = ts0; cu->m_pePredMode[z] = pm0; cu->m_CUTransquantBypass[z] = bypass0;
+  cu->getWidth()[z] = w0; cu->getHeight()[z] = h0; cu->getDepth()[z] = d0;
+  return rc;
+}
+
 // md5 (16 bytes) of the slice-data bytes written by the reference's encodeSlice in the last href_rdo_encode_frame* call of that geometry
 // (FHREF_ENCODE_SLICE=1); -1 when there is none
 int href_slice_md5(int width, int height, int bit_depth, unsigned char* digest16)

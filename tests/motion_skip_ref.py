@@ -2,8 +2,10 @@
 in Python from the definitions in include/fasthevc.h -- not from the C code: HM's forward DCT (xTrMxN) as two integer matrix products with its shifts and
 rounding on int64 intermediates, the scalar quantiser without scaling lists in Python integers, expected() over a picture and a band on
 motion_refine_ref's prediction, and the tree rule on p_tree_ref's geometry.  tests/test_motion_skip_ref.py pins this module to the reference's own
-transform (tests/golden/ref_transform.npz) without a GPU, tests/test_motion_skip_abi.py compares the host functions with it,
-tests/test_gpu_motion_skip.py the kernels.  A plain module, not a conftest and not a test."""
+transform (tests/golden/ref_transform.npz) without a GPU, tests/test_motion_skip_quant_pin.py pins quant(), first_nonzero() and node_record() to the
+reference's own quantiser, plain and RDOQ (tests/golden/ref_quant.npz), tests/test_motion_skip_abi.py compares the host functions with it,
+tests/test_gpu_motion_skip.py the kernels.  All three readings of HM a record rests on are thereby pinned: the prediction (ref_frac_search*.npz through
+motion_refine_ref.Planes), the transform, and the quantiser with its two zero bits.  A plain module, not a conftest and not a test."""
 import numpy as np
 
 import motion_merge_ref as mg

@@ -1,6 +1,7 @@
 """Config 4 (P slices): the zero-residual stage (k_motion_skip.hip) and the tree decision that stops at a skip (the skip instantiation of k_p_tree.hip)
 on the MI355X, field by field against the Python restatement tests/motion_skip_ref.py, which tests/test_motion_skip_ref.py pins to the reference's own
-transform without a GPU.  Nothing is compared with a kernel's own output except where two launches must give the same bytes.
+transform without a GPU (and tests/test_motion_skip_quant_pin.py to its quantiser; tests/test_gpu_motion_skip_quant_pin.py compares the kernel with the
+reference's recorded numbers directly).  Nothing is compared with a kernel's own output except where two launches must give the same bytes.
 
 Pictures are 200 x 136 = 4 x 3 CTUs, ragged by 8 samples on both sides (the merge tests' picture), so the last column and row hold nodes that are not
 INSIDE; the constructed cases bring their own sizes."""

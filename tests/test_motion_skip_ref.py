@@ -1,6 +1,8 @@
 """The restatement of the zero-residual stage (tests/motion_skip_ref.py) held to the reference's own forward transform (tests/golden/ref_transform.npz,
 written by tests/quality/gen_transform_golden.py from calls into xTrMxN), to closed-form cases and to its own definition -- without a GPU.  The GPU test
-(tests/test_gpu_motion_skip.py) compares the kernels with this restatement, so what is pinned here is what the kernels are held to."""
+(tests/test_gpu_motion_skip.py) compares the kernels with this restatement, so what is pinned here is what the kernels are held to.  Pinned HERE: the
+transform, its matrices and g_quantScales.  The formula around the scales -- qbits, per / rem, the two offsets -- is compared below only with itself
+(a loop, a search); tests/test_motion_skip_quant_pin.py pins it to the reference's own quantiser (tests/golden/ref_quant.npz)."""
 import os
 
 import numpy as np
