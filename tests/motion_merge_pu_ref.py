@@ -132,13 +132,13 @@ def same(got, exp, what=""):
 DRAW_W, DRAW_H, DRAW_QP, DRAW_RANGE = 200, 136, 4, 8      # 4 x 3 CTUs, ragged by 8 both ways; bits are cheap at qp 4: any list position can win
 
 
-def random_refined(rng, shape, max_range):
+def random_refined(rng, shape, max_range, pool=None):
     """refined records of random bytes; vectors drawn from four near ones (so that every pruning pair fires), one record in ten out of reach (one quarter
-    sample beyond it, or anywhere), one in seven marked"""
+    sample beyond it, or anywhere), one in seven marked; pool: other vectors to draw from, in their place (tests/motion_merge_sweep_cases.py)"""
     a = np.frombuffer(rng.bytes(int(np.prod(shape)) * 16), QDT).reshape(shape).copy()
     reach = 4 * max_range + 3
-    pool = np.array([(-5, 2), (3, 3), (reach, -reach), (0, -7)], np.int16)
-    pick = pool[rng.integers(0, 4, size=shape)]
+    pool = np.array([(-5, 2), (3, 3), (reach, -reach), (0, -7)] if pool is None else pool, np.int16)
+    pick = pool[rng.integers(0, len(pool), size=shape)]
     far = rng.random(shape) < 0.1
     beyond = np.where(rng.random(shape) < 0.5, reach + 1, rng.integers(reach + 1, 32768, size=shape)) * rng.choice([-1, 1], size=shape)
     a["mvx"] = np.where(far & (rng.random(shape) < 0.5), beyond, pick[..., 0])
