@@ -43,51 +43,41 @@ __global__ __launch_bounds__(256) void fhevc_motion_refine_kernel(FhevcFrames F,
   __shared__ unsigned s_cost[FHEVC_MV_BIT_COSTS], s_taps[16];
   const int tid = threadIdx.x, lane = tid & 63, lvl = tid >> 6;
   const int tx = lane & 7, ty = lane >> 3;
-  const int band_rows = F.row_end - F.row_begin;
-  const int per_frame = band_rows * F.ctus_x;
-  const int total = per_frame * (F.num_frames - 1);  // frame f >= 1 is refined in frame f - 1
-  const int bd = F.bit_depth;
-  const int shift = bd - 8;
-  const RefineArith arith(bd);
+  const int total = SearchWork::total(F);  // frame f >= 1 is refined in frame f - 1
+  const int shift = F.bit_depth - 8;
+  const RefineArith arith(F.bit_depth);
   const T* plane = reinterpret_cast<const T*>(F.luma);
   if (tid < FHEVC_MV_BIT_COSTS) s_cost[tid] = cost.c[tid];
   if (tid < 16) s_taps[tid] = kLumaTaps[tid];
-  // this lane's node: level lvl, (nbx, nby) in the CTU
-  const int nsize = 64 >> lvl, ncnt = 1 << lvl;
-  const int nbx = tx >> (3 - lvl), nby = ty >> (3 - lvl);
-  const int nidx = ((1 << (2 * lvl)) - 1) / 3 + nby * ncnt + nbx;
-  const bool writer = (tx & ((8 >> lvl) - 1)) == 0 && (ty & ((8 >> lvl) - 1)) == 0;
+  const RefineNode N(lvl, tx, ty);  // this lane's node: level lvl, (nbx, nby) in the CTU
 
   for (int work = blockIdx.x; work < total; work += gridDim.x) {
-    const int f = 1 + work / per_frame;
-    const int rem = work % per_frame;
-    const int cy = F.row_begin + rem / F.ctus_x, cx = rem % F.ctus_x;
-    const long long cur_base = (long long)f * F.frame_stride, ref_base = (long long)(f - 1) * F.frame_stride;
-    const long long oc = (long long)((f - 1) * band_rows + (cy - F.row_begin)) * F.ctus_x + cx;
+    const SearchWork W(F, work);
+    const int cy = W.cy, cx = W.cx;
+    const long long oc = W.oc(F);
     SearchCentre P;
     if constexpr (CENTRED) {
       P = SearchCentre(centres, oc);
       if (!P.in_range()) {  // uniform: every node of this CTU gets the marker, nothing is read for it
-        if (writer) { FhevcMotionQpelNode o; o.satd_int = o.satd_best = o.cost_best = 0xFFFFFFFFu; o.mvx = 0; o.mvy = 0; out[oc * FHEVC_NODES + nidx] = o; }
+        if (N.writer) out[oc * FHEVC_NODES + N.nidx] = refine_record(false, 0, 0, 0, 0, 0);
         continue;
       }
     }
     // ---- stage the reference window: rows cy*64 - MR - 4 .., columns cx*64 - MR - 4 .., coordinates clamped to the picture ----
     __syncthreads();  // the previous CTU's readers are done
-    if constexpr (CENTRED) refine_stage_window<T, MR>(s_ref, plane, ref_base, F, cx, cy, tid, P.x, P.y);
-    else refine_stage_window<T, MR>(s_ref, plane, ref_base, F, cx, cy, tid);
+    if constexpr (CENTRED) refine_stage_window<T, MR>(s_ref, plane, W.ref_base, F, cx, cy, tid, P.x, P.y);
+    else refine_stage_window<T, MR>(s_ref, plane, W.ref_base, F, cx, cy, tid);
     // ---- this lane's original 8x8 tile (all four waves hold the same 64 tiles) ----
     const int px = cx * 64 + tx * 8, py = cy * 64 + ty * 8;
     const bool inside = (px + 8 <= F.width) && (py + 8 <= F.height);
     unsigned O[32];
-    load_tile8x8(plane, cur_base, F, px, py, inside, O);
+    load_tile8x8(plane, W.cur_base, F, px, py, inside, O);
     // ---- its node's integer vector: only mvx / mvy of the input are read, validity comes from the geometry and from max_range ----
-    const bool node_in = cx * 64 + nbx * nsize + nsize <= F.width && cy * 64 + nby * nsize + nsize <= F.height;
     int mx = 0, my = 0;
     bool valid = false;
-    if (node_in) {
-      const unsigned w = reinterpret_cast<const unsigned*>(nodes)[(oc * FHEVC_NODES + nidx) * 4 + 3];
-      mx = (int)(short)(w & 0xFFFFu); my = (int)(short)(w >> 16);
+    if (search_node_inside(F, cx, cy, N.nbx, N.nby, 64 >> lvl)) {
+      const unsigned w = reinterpret_cast<const unsigned*>(nodes)[(oc * FHEVC_NODES + N.nidx) * 4 + 3];
+      mx = vec_x(w); my = vec_y(w);
       if constexpr (CENTRED) { mx -= P.x; my -= P.y; }
       valid = abs(mx) <= max_range && abs(my) <= max_range;
       if (!valid) { mx = 0; my = 0; }  // the arithmetic below stays inside the window; its result is dropped
@@ -102,64 +92,24 @@ __global__ __launch_bounds__(256) void fhevc_motion_refine_kernel(FhevcFrames F,
       if (i == 9) { base_x = best_x; base_y = best_y; best_c = 0xFFFFFFFFu; }  // the quarter stage starts from the half stage's winner
       const int step = i < 9 ? 2 : 1;
       const int qx = base_x + step * (int)kRefineX[i], qy = base_y + step * (int)kRefineY[i];
-      const int fx = qx & 3, fy = qy & 3;
-      const int col = tx * 8 + MR + 4 + (qx >> 2) - 3, row0 = ty * 8 + MR + 4 + (qy >> 2) - 3;  // first tap of sample (0, 0)
-      // ---- the tile's prediction at the candidate, its difference to the original (k_refine_tile.h), Hadamard ----
+      // ---- the tile's prediction at the candidate, its difference to the original, Hadamard (k_refine_tile.h); the node's sum ----
       unsigned t8;
       {
         unsigned D[32];
         int v[64];
-        refine_tile_diff<PACKED, RP>(s_ref, s_taps, arith, col, row0, fx, fy, O, D, v);
-        if constexpr (PACKED) t8 = had8x8_packed(D);
-        else t8 = had8x8_wide(v);
+        refine_tile_at<PACKED, RP>(s_ref, s_taps, arith, tx, ty, qx, qy, O, D, v);
+        t8 = refine_had8x8<PACKED>(D, v, inside);
       }
-      t8 = inside ? ((t8 + 2) >> 2) : 0u;  // xCalcHADs8x8: (sum + 2) >> 2 (TComRdCost.cpp:1747)
-      // the node's sum: 16x16 = tiles (tx ^ 1, ty ^ 1), 32x32 = + bits 1, 64x64 = + bits 2 (wave-uniform depth)
-      unsigned s = t8;
-      for (int k = 0; k < 3 - lvl; ++k) {
-        s += __shfl_xor(s, 1 << k);
-        s += __shfl_xor(s, 8 << k);
-      }
-      const unsigned sd = s >> shift;  // DISTORTION_PRECISION_ADJUSTMENT on the block's sum (TComRdCost.cpp:1823)
+      const unsigned sd = refine_node_sum(t8, lvl) >> shift;  // DISTORTION_PRECISION_ADJUSTMENT on the block's sum (TComRdCost.cpp:1823)
       const unsigned c = sd + s_cost[eg_bits(qx) + eg_bits(qy)];
       if (i == 0) satd_int = sd;
       if (c < best_c) { best_c = c; best_s = sd; best_x = qx; best_y = qy; }
     }
-    if (writer) {
-      FhevcMotionQpelNode o;
+    if (N.writer) {
       if constexpr (CENTRED) { best_x += 4 * P.x; best_y += 4 * P.y; }
-      if (valid) { o.satd_int = satd_int; o.satd_best = best_s; o.cost_best = best_c; o.mvx = (short)best_x; o.mvy = (short)best_y; }
-      else { o.satd_int = o.satd_best = o.cost_best = 0xFFFFFFFFu; o.mvx = 0; o.mvy = 0; }
-      out[oc * FHEVC_NODES + nidx] = o;
+      out[oc * FHEVC_NODES + N.nidx] = refine_record(valid, satd_int, best_s, best_c, best_x, best_y);
     }
   }
-}
-
-template <typename T, bool PACKED>
-hipError_t launch_refine(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_nodes, FhevcMotionQpelNode* d_out, int num_cus,
-                         long long total, hipStream_t stream)
-{
-  if (max_range <= FHEVC_MOTION_MAX_RANGE) {
-    const int grid = (int)(total < 4LL * num_cus ? total : 4LL * num_cus);
-    hipLaunchKernelGGL((fhevc_motion_refine_kernel<T, PACKED, FHEVC_MOTION_MAX_RANGE>), dim3(grid), dim3(256), 0, stream, fr, max_range, cost, d_nodes, d_out, SearchNoCentres{});
-  } else {
-    constexpr int MRB = FHEVC_MOTION_WIDE_MAX_RANGE;
-    const size_t lds = (size_t)RefineGeom<MRB>::SAMPLES * sizeof(short);  // 80 016 B: one workgroup per CU beside another kernel's, two alone
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fhevc_motion_refine_kernel<T, PACKED, MRB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    const int grid = (int)(total < 2LL * num_cus ? total : 2LL * num_cus);
-    hipLaunchKernelGGL((fhevc_motion_refine_kernel<T, PACKED, MRB>), dim3(grid), dim3(256), lds, stream, fr, max_range, cost, d_nodes, d_out, SearchNoCentres{});
-  }
-  return hipGetLastError();
-}
-
-template <typename T, bool PACKED>
-hipError_t launch_refine_centred(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_centres, const FhevcMotionNode* d_nodes,
-                                 FhevcMotionQpelNode* d_out, int num_cus, long long total, hipStream_t stream)
-{
-  const int grid = (int)(total < 4LL * num_cus ? total : 4LL * num_cus);
-  hipLaunchKernelGGL((fhevc_motion_refine_kernel<T, PACKED, FHEVC_MOTION_MAX_RANGE, true>), dim3(grid), dim3(256), 0, stream, fr, max_range, cost, d_nodes, d_out, d_centres);
-  return hipGetLastError();
 }
 
 }  // namespace
@@ -168,21 +118,16 @@ hipError_t launch_refine_centred(const FhevcFrames& fr, int max_range, const Fhe
 hipError_t fhevc_launch_motion_refine_centred(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_centres, const FhevcMotionNode* d_nodes,
                                               FhevcMotionQpelNode* d_out, int num_cus, hipStream_t stream)
 {
-  const long long total = (long long)(fr.row_end - fr.row_begin) * fr.ctus_x * (fr.num_frames - 1);
-  if (total <= 0) return hipSuccess;
-  if (max_range < 1 || max_range > FHEVC_MOTION_MAX_RANGE || !d_centres) return hipErrorInvalidValue;
-  if (fr.sample_bytes == 2 && fr.bit_depth <= 10) return launch_refine_centred<int16_t, true>(fr, max_range, cost, d_centres, d_nodes, d_out, num_cus, total, stream);
-  if (fr.sample_bytes == 2) return launch_refine_centred<int16_t, false>(fr, max_range, cost, d_centres, d_nodes, d_out, num_cus, total, stream);
-  return launch_refine_centred<uint8_t, true>(fr, max_range, cost, d_centres, d_nodes, d_out, num_cus, total, stream);
+  return refine_launch<FHEVC_MOTION_MAX_RANGE>(fr, d_centres != nullptr, max_range, num_cus, {4, false}, {}, stream, [&](auto t, auto packed, auto mr, const RefineLaunch& L) {
+    return refine_launch_kernel<&fhevc_motion_refine_kernel<decltype(t), decltype(packed)::value, decltype(mr)::value, true>>(L, fr, max_range, cost, d_nodes, d_out, d_centres);
+  });
 }
 
+// four workgroups per CU at MR = 8; at MR = 64 the window of 80 016 B leaves one workgroup per CU beside another kernel's, two alone
 hipError_t fhevc_launch_motion_refine(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionNode* d_nodes, FhevcMotionQpelNode* d_out,
                                       int num_cus, hipStream_t stream)
 {
-  const long long total = (long long)(fr.row_end - fr.row_begin) * fr.ctus_x * (fr.num_frames - 1);
-  if (total <= 0) return hipSuccess;
-  if (max_range < 1 || max_range > FHEVC_MOTION_WIDE_MAX_RANGE) return hipErrorInvalidValue;
-  if (fr.sample_bytes == 2 && fr.bit_depth <= 10) return launch_refine<int16_t, true>(fr, max_range, cost, d_nodes, d_out, num_cus, total, stream);
-  if (fr.sample_bytes == 2) return launch_refine<int16_t, false>(fr, max_range, cost, d_nodes, d_out, num_cus, total, stream);
-  return launch_refine<uint8_t, true>(fr, max_range, cost, d_nodes, d_out, num_cus, total, stream);
+  return refine_launch<FHEVC_MOTION_WIDE_MAX_RANGE>(fr, true, max_range, num_cus, {4, false}, {2, false}, stream, [&](auto t, auto packed, auto mr, const RefineLaunch& L) {
+    return refine_launch_kernel<&fhevc_motion_refine_kernel<decltype(t), decltype(packed)::value, decltype(mr)::value>>(L, fr, max_range, cost, d_nodes, d_out, SearchNoCentres{});
+  });
 }

@@ -5,9 +5,9 @@
 // (xTrMxN, TComTrQuant.cpp:860-915: TUs of min(node, 32) samples, shifts log2 N + bit depth - 9 and log2 N + 6 with partialButterfly's rounding) and HM's
 // scalar quantiser without scaling lists (TComTrQuant.cpp:1186-1232) under the two offsets: the P-slice dead zone and RDOQ's starting levels.
 //
-// Mapping: k_motion_merge.hip's outer one -- workgroup (4 waves) = one CTU at a time over a persistent grid; the reference window of k_refine_tile.h in LDS
-// (MR = 8 layout: static; MR = 64 layout: dynamic), of which only the part max_range reaches is staged; wave = level and lane = one 8x8 tile for the
-// prediction: ONE refine_tile_diff per lane, at its node's vector.  The residual fits 16 bits at every bit depth (|r| <= 4095), so the packed form of
+// Mapping: k_refine_tile.h's -- workgroup (4 waves) = one CTU at a time over a persistent grid; the reference window in LDS (MR = 8 layout: static;
+// MR = 64 layout: dynamic), of which only the part max_range reaches is staged; wave = level and lane = one 8x8 tile (RefineNode) for the prediction: ONE
+// refine_tile_diff per lane, at its node's vector.  The residual fits 16 bits at every bit depth (|r| <= 4095), so the packed form of
 // refine_tile_diff serves 12 bit too: there is no PACKED parameter.
 // The transform goes through LDS.  Once all four waves hold their residual tiles the window is dead: behind a barrier four buffers of 64 rows x 72 shorts
 // (one per level; 9 216 B each, a pitch of 36 dwords so that a wave's 64 rows start in different banks) lie OVER it.  Both passes are the same loop: a
@@ -23,7 +23,6 @@
 #include "fhevc_internal.h"
 #include "k_had8x8.h"
 #include "k_refine_tile.h"
-#include <atomic>
 
 namespace {
 
@@ -152,50 +151,42 @@ __global__ __launch_bounds__(256) void fhevc_motion_skip_kernel(FhevcFrames F, i
   const int tid = threadIdx.x, lane = tid & 63, lvl = tid >> 6;
   const int wave = __builtin_amdgcn_readfirstlane(lvl);   // the transform's matrix rows are read at wave-uniform addresses
   const int tx = lane & 7, ty = lane >> 3;
-  const int band_rows = F.row_end - F.row_begin;
-  const int per_frame = band_rows * F.ctus_x;
-  const int total = per_frame * (F.num_frames - 1);  // frame f >= 1 is predicted from frame f - 1
+  const int total = SearchWork::total(F);  // frame f >= 1 is predicted from frame f - 1
   const RefineArith arith(F.bit_depth);
   const T* plane = reinterpret_cast<const T*>(F.luma);
   if (tid < 16) s_taps[tid] = kLumaTaps[tid];
-  // this lane's node: level lvl, (nbx, nby) in the CTU
-  const int ncnt = 1 << lvl;
-  const int nbx = tx >> (3 - lvl), nby = ty >> (3 - lvl);
-  const int nidx = ((1 << (2 * lvl)) - 1) / 3 + nby * ncnt + nbx;
-  const bool writer = (tx & ((8 >> lvl) - 1)) == 0 && (ty & ((8 >> lvl) - 1)) == 0;
+  const RefineNode N(lvl, tx, ty);  // this lane's node: level lvl, (nbx, nby) in the CTU
+  const int nidx = N.nidx;
   const int gw = F.width >> (6 - lvl), gh = F.height >> (6 - lvl);   // the level's nodes that lie wholly inside the picture
-  const int reach = 4 * max_range + 3;
+  const int reach = vec_reach(max_range);
   const int s1_8 = F.bit_depth - 6, s1_16 = F.bit_depth - 5, s1_32 = F.bit_depth - 4;   // shift_1st = log2 N + bit depth - 9
   // the transform's work of this thread: its row is its lane
   const int seg32 = wave & 1, k32 = (wave >> 1) * 16;
 
   for (int work = blockIdx.x; work < total; work += gridDim.x) {
-    const int f = 1 + work / per_frame;
-    const int rem = work % per_frame;
-    const int cy = F.row_begin + rem / F.ctus_x, cx = rem % F.ctus_x;
-    const long long cur_base = (long long)f * F.frame_stride, ref_base = (long long)(f - 1) * F.frame_stride;
-    const long long oc = (long long)((f - 1) * band_rows + (cy - F.row_begin)) * F.ctus_x + cx;
+    const SearchWork W(F, work);
+    const int cy = W.cy, cx = W.cx;
+    const long long oc = W.oc(F);
     // ---- the node's merge record: cost_best (the marker test) and the vector dword; the address depends on geometry alone ----
-    const bool node_in = cx * ncnt + nbx < gw && cy * ncnt + nby < gh;
+    const bool node_in = cx * N.ncnt + N.nbx < gw && cy * N.ncnt + N.nby < gh;
     const unsigned mcost = merge[(oc * FHEVC_NODES + nidx) * 4 + 1], mvec = merge[(oc * FHEVC_NODES + nidx) * 4 + 2];
     // ---- stage the part of the reference window that max_range reaches ----
     __syncthreads();  // the previous CTU's readers of the buffers and of the sums are done
-    refine_stage_window_reach<T, MR>(s_ref, plane, ref_base, F, cx, cy, tid, max_range);
+    refine_stage_window_reach<T, MR>(s_ref, plane, W.ref_base, F, cx, cy, tid, max_range);
     for (int i = tid; i < 3 * FHEVC_NODES; i += 256) s_acc[i] = 0;
     const int px = cx * 64 + tx * 8, py = cy * 64 + ty * 8;
     const bool inside = (px + 8 <= F.width) && (py + 8 <= F.height);
     unsigned O[32];
-    load_tile8x8(plane, cur_base, F, px, py, inside, O);
-    const int vx = (int)(short)(mvec & 0xFFFFu), vy = (int)(short)(mvec >> 16);
-    const bool valid = node_in && mcost != kSkipMark && abs(vx) <= reach && abs(vy) <= reach;
+    load_tile8x8(plane, W.cur_base, F, px, py, inside, O);
+    const int vx = vec_x(mvec), vy = vec_y(mvec);
+    const bool valid = node_in && mcost != kSkipMark && vec_in_reach(mvec, reach);
     const int qx = valid ? vx : 0, qy = valid ? vy : 0;   // an invalid node predicts at the zero vector and drops the result: no read outside the window
     __syncthreads();
     // ---- the residual of this lane's tile at its node's vector ----
     unsigned D[32];
     {
       int v[64];
-      const int col = tx * 8 + MR + 4 + (qx >> 2) - 3, row0 = ty * 8 + MR + 4 + (qy >> 2) - 3;  // first tap of sample (0, 0)
-      refine_tile_diff<true, RP>(s_ref, s_taps, arith, col, row0, qx & 3, qy & 3, O, D, v);
+      refine_tile_at<true, RP>(s_ref, s_taps, arith, tx, ty, qx, qy, O, D, v);
     }
     __syncthreads();  // the window is dead: the transform buffers lie over it
     {
@@ -244,7 +235,7 @@ __global__ __launch_bounds__(256) void fhevc_motion_skip_kernel(FhevcFrames F, i
       skip_commit(s_acc, 21 + (lane >> 3) * 8 + wave + 4, lane, s);
     }
     __syncthreads();
-    if (writer) {
+    if (N.writer) {
       FhevcMotionSkipNode o;
       o.coef_max = o.level_sum = kSkipMark; o.nonzero = 0xFFFFu; o.flags = 0; o.pad = 0; o.mvx = o.mvy = 0;
       if (valid) {
@@ -260,74 +251,16 @@ __global__ __launch_bounds__(256) void fhevc_motion_skip_kernel(FhevcFrames F, i
   }
 }
 
-// the MR = 64 instance of one plane type: its dynamic LDS, and how many of its workgroups the device keeps on one CU (asked once per instance)
-template <typename T> struct SkipBig {
-  static constexpr int MRB = FHEVC_MOTION_WIDE_MAX_RANGE;
-  static constexpr size_t LDS = (size_t)RefineGeom<MRB>::SAMPLES * sizeof(short);  // 80 016 B
-  static hipError_t resident(int* per_cu)
-  {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fhevc_motion_skip_kernel<T, MRB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-    if (e != hipSuccess) return e;
-    static std::atomic<int> asked{0};   // every device of a context is a gfx950: one answer per instance
-    int n = asked.load(std::memory_order_relaxed);
-    if (n == 0) {
-      const hipError_t q = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fhevc_motion_skip_kernel<T, MRB>, 256, LDS);
-      if (q != hipSuccess) return q;
-      asked.store(n, std::memory_order_relaxed);
-    }
-    *per_cu = n;
-    return hipSuccess;
-  }
-};
-
-// the MR = 8 instance: 38 912 B of static LDS for the transform buffers and the matrix -- how many workgroups share a CU is the device's to say here too
-template <typename T> hipError_t skip_small_resident(int* per_cu)
-{
-  static std::atomic<int> asked{0};
-  int n = asked.load(std::memory_order_relaxed);
-  if (n == 0) {
-    const hipError_t q = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fhevc_motion_skip_kernel<T, FHEVC_MOTION_MAX_RANGE>, 256, 0);
-    if (q != hipSuccess) return q;
-    asked.store(n, std::memory_order_relaxed);
-  }
-  *per_cu = n;
-  return hipSuccess;
-}
-
-template <typename T>
-hipError_t launch_skip(const FhevcFrames& fr, int max_range, const FhevcSkipQuant& q, const unsigned* merge, FhevcMotionSkipNode* d_out, int num_cus, long long total,
-                       hipStream_t stream)
-{
-  int per_cu = 0;
-  if (max_range <= FHEVC_MOTION_MAX_RANGE) {
-    const hipError_t e = skip_small_resident<T>(&per_cu);
-    if (e != hipSuccess) return e;
-    if (per_cu < 1) return hipErrorLaunchOutOfResources;
-    const long long resident = (long long)(per_cu < 4 ? per_cu : 4) * num_cus;
-    const int grid = (int)(total < resident ? total : resident);
-    hipLaunchKernelGGL((fhevc_motion_skip_kernel<T, FHEVC_MOTION_MAX_RANGE>), dim3(grid), dim3(256), 0, stream, fr, max_range, q, merge, d_out);
-  } else {
-    using Big = SkipBig<T>;
-    const hipError_t e = Big::resident(&per_cu);
-    if (e != hipSuccess) return e;
-    if (per_cu < 1) return hipErrorLaunchOutOfResources;
-    const long long resident = (long long)(per_cu < 2 ? per_cu : 2) * num_cus;   // the LDS holds two windows per CU at most
-    const int grid = (int)(total < resident ? total : resident);
-    hipLaunchKernelGGL((fhevc_motion_skip_kernel<T, Big::MRB>), dim3(grid), dim3(256), Big::LDS, stream, fr, max_range, q, merge, d_out);
-  }
-  return hipGetLastError();
-}
-
 }  // namespace
 
+// what the device keeps resident, at most four workgroups per CU at MR = 8 (38 912 B of static LDS for the transform buffers and the matrix) and two at
+// MR = 64: the LDS holds two windows per CU at most
 hipError_t fhevc_launch_motion_skip(const FhevcFrames& fr, int max_range, const FhevcSkipQuant& q, const FhevcMotionMergeNode* d_merge, FhevcMotionSkipNode* d_out,
                                     int num_cus, hipStream_t stream)
 {
   static_assert(sizeof(FhevcMotionMergeNode) == 16 && sizeof(FhevcMotionSkipNode) == 16, "record layouts");
-  const long long total = (long long)(fr.row_end - fr.row_begin) * fr.ctus_x * (fr.num_frames - 1);
-  if (total <= 0) return hipSuccess;
-  if (max_range < 1 || max_range > FHEVC_MOTION_WIDE_MAX_RANGE || total > 0x7FFFFFFF) return hipErrorInvalidValue;
   const unsigned* merge = reinterpret_cast<const unsigned*>(d_merge);
-  if (fr.sample_bytes == 2) return launch_skip<int16_t>(fr, max_range, q, merge, d_out, num_cus, total, stream);
-  return launch_skip<uint8_t>(fr, max_range, q, merge, d_out, num_cus, total, stream);
+  return refine_launch<FHEVC_MOTION_WIDE_MAX_RANGE>(fr, true, max_range, num_cus, {4, true}, {2, true}, stream, [&](auto t, auto, auto mr, const RefineLaunch& L) {
+    return refine_launch_kernel<&fhevc_motion_skip_kernel<decltype(t), decltype(mr)::value>>(L, fr, max_range, q, merge, d_out);
+  });
 }

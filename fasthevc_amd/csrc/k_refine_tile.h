@@ -1,8 +1,12 @@
-// k_refine_tile.h -- what the two quarter-sample refinement kernels share (k_motion_refine.hip: the 85 square CU nodes; k_motion_refine_pu.hip: the
-// 508 PUs): the reference window in LDS, the candidate tables, and the prediction of one 8x8 tile at one quarter-sample
-// candidate as a block of differences to the original.  The interpolation form is the one k_motion_refine.hip's header comment derives: the
-// fractions are DATA (two packed coefficient vectors per lane), so the lanes of a wave need not agree on a phase.
+// k_refine_tile.h -- what the five quarter-sample window kernels share (k_motion_refine.hip: the 85 square CU nodes refined; k_motion_refine_pu.hip: the
+// 508 PUs refined; k_motion_merge.hip and k_motion_merge_pu.hip: the merge candidates of the nodes and of the PUs; k_motion_skip.hip: the zero-residual test
+// per node).  All five run one mapping: workgroup (4 waves) = one CTU at a time, grid-stride (k_search_tile.h's SearchWork); the reference window in LDS
+// (MR = 8 layout: static, MR = 64 layout: dynamic); lane = one 8x8 tile, predicted at a quarter-sample candidate as a block of differences to the
+// original.  Here, once: the window and its staging, the candidate tables, the tile prediction, a lane's square node and its sum, the PU passes and a PU's
+// sum, the merge list, the output records, and the launch.  Each kernel keeps its body.  The interpolation form is the one k_motion_refine.hip's header
+// comment derives: the fractions are DATA (two packed coefficient vectors per lane), so the lanes of a wave need not agree on a phase.
 #pragma once
+#include <atomic>
 #include "fhevc_internal.h"
 #include "k_had8x8.h"
 #include "k_search_tile.h"  // sample_of, load_tile8x8: one definition for the searches and the refinements
@@ -195,6 +199,285 @@ __device__ __forceinline__ void refine_tile_diff(const short* s_ref, const unsig
       else { v[8 * y + 2 * k] = (int)(o & 0xFFFFu) - p[2 * k]; v[8 * y + 2 * k + 1] = (int)(o >> 16) - p[2 * k + 1]; }
     }
   }
+}
+
+// ... of the lane's tile (tx, ty) of the CTU at the quarter-sample vector (qx, qy); the CTU begins (RP - 64) / 2 = MR + 4 samples into the window
+template <bool PACKED, int RP>
+__device__ __forceinline__ void refine_tile_at(const short* s_ref, const unsigned* s_taps, const RefineArith& A, int tx, int ty, int qx, int qy,
+                                               const unsigned (&O)[32], unsigned (&D)[32], int (&v)[64])
+{
+  constexpr int ORG = (RP - 64) / 2;
+  const int col = tx * 8 + ORG + (qx >> 2) - 3, row0 = ty * 8 + ORG + (qy >> 2) - 3;  // first tap of sample (0, 0)
+  refine_tile_diff<PACKED, RP>(s_ref, s_taps, A, col, row0, qx & 3, qy & 3, O, D, v);
+}
+// the tile's Hadamard of that difference; 0 where the tile is not inside the picture.  The caller declares D and v inside its candidate loop: with the two
+// arrays in a helper of their own the compiler allocated the registers of that loop differently from how it does for the loop written out
+template <bool PACKED>
+__device__ __forceinline__ unsigned refine_had8x8(unsigned (&D)[32], int (&v)[64], bool inside)
+{
+  unsigned t8;
+  if constexpr (PACKED) t8 = had8x8_packed(D);
+  else t8 = had8x8_wide(v);
+  return inside ? ((t8 + 2) >> 2) : 0u;  // xCalcHADs8x8: (sum + 2) >> 2 (TComRdCost.cpp:1747)
+}
+
+// ---- a vector dword of a record: mvx in the low half, mvy in the high one.  A vector is used only if both components lie within the reach of a refined
+// vector, 4 max_range + 3 quarter samples, so no input byte can send a read outside the staged window ----
+__device__ __forceinline__ int vec_x(unsigned w) { return (int)(short)(w & 0xFFFFu); }
+__device__ __forceinline__ int vec_y(unsigned w) { return (int)(short)(w >> 16); }
+__device__ __forceinline__ int vec_reach(int max_range) { return 4 * max_range + 3; }
+__device__ __forceinline__ bool vec_in_reach(unsigned w, int reach) { return abs(vec_x(w)) <= reach && abs(vec_y(w)) <= reach; }
+
+// ---- the square node of tile (tx, ty) where wave = level (0: 64x64 .. 3: 8x8): ncnt x ncnt nodes in the CTU, this one at (nbx, nby); first: the level's
+// first node among the CTU's 85, nidx: this one; writer: the lane of the node's first tile ----
+struct RefineNode {
+  int ncnt, nbx, nby, first, nidx;
+  bool writer;
+  __device__ __forceinline__ RefineNode(int lvl, int tx, int ty)
+    : ncnt(1 << lvl), nbx(tx >> (3 - lvl)), nby(ty >> (3 - lvl)), first(((1 << (2 * lvl)) - 1) / 3), nidx(first + nby * ncnt + nbx),
+      writer((tx & ((8 >> lvl) - 1)) == 0 && (ty & ((8 >> lvl) - 1)) == 0) {}
+};
+// the node's sum: 16x16 = tiles (tx ^ 1, ty ^ 1), 32x32 = + bits 1, 64x64 = + bits 2 (wave-uniform depth)
+__device__ __forceinline__ unsigned refine_node_sum(unsigned t8, int lvl)
+{
+  unsigned s = t8;
+  for (int k = 0; k < 3 - lvl; ++k) {
+    s += __shfl_xor(s, 1 << k);
+    s += __shfl_xor(s, 8 << k);
+  }
+  return s;
+}
+
+// ---- the 26 PU passes (k_motion_refine_pu.hip's header comment), each a covering of the CTU by one (CU size, shape) pair: what pass `pass` (wave-uniform)
+// makes of tile (tx, ty) ----
+constexpr int PASSES_PU = 14, PASSES = 26;
+struct RefinePuPass {
+  bool small, horiz, rep;   // one of the 12 passes of the 384; the CU is cut by a horizontal line: part 0 on top; this lane writes the PU
+  int n, s;                 // CU of 2^n x 2^n tiles (small: n = 1: 16x16, 0: 8x8), shape (0 2NxN, 1 Nx2N, 2 2NxnU, 3 2NxnD, 4 nLx2N, 5 nRx2N)
+  int nbx, nby, lx, ly;     // the CU on its level's grid inside the CTU, the tile inside the CU
+  int part, entry;          // the part that holds the tile (small: the part the pass sums), its index in the family's layout
+  unsigned qmask;           // small: the quadrants q00 q01 / q10 q11 of the tile that lie in the pass's part
+  __device__ __forceinline__ RefinePuPass(int pass, int tx, int ty)
+  {
+    small = pass >= PASSES_PU;
+    int want = 0;
+    if (!small) { n = pass < 6 ? 3 : pass < 12 ? 2 : 1; s = pass - (pass < 6 ? 0 : pass < 12 ? 6 : 12); }
+    else { const int c = (pass - PASSES_PU) >> 1; want = (pass - PASSES_PU) & 1; n = c < 4 ? 1 : 0; s = c < 4 ? 2 + c : c - 4; }
+    const int tn = 1 << n;
+    lx = tx & (tn - 1); ly = ty & (tn - 1);
+    horiz = s == 0 || s == 2 || s == 3;
+    nbx = tx >> n; nby = ty >> n;
+    const int ni = nby * (8 >> n) + nbx;                             // the CU among those of its size, raster
+    qmask = 0;
+    if (!small) {
+      const int sp = s < 2 ? tn / 2 : (s & 1) ? 3 * tn / 4 : tn / 4;   // where the CU is cut, in tiles
+      const int other = horiz ? lx : ly;
+      part = along() >= sp ? 1 : 0;
+      rep = other == 0 && along() == part * sp;
+      entry = (n == 3 ? 0 : n == 2 ? (1 + ni) * 12 : 60 + ni * 4) + s * 2 + part;
+    } else {
+      part = want;
+      const int cut = n == 0 ? 1 : (s & 1) ? 3 : 1;                // in 4-sample units from the CU's top (left) edge
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int pos = horiz ? ly * 2 + (k >> 1) : lx * 2 + (k & 1);
+        if ((pos >= cut ? 1 : 0) == want) qmask |= 1u << k;
+      }
+      rep = lx == 0 && ly == 0;
+      entry = n == 1 ? ni * 8 + (s - 2) * 2 + part : 128 + ni * 4 + s * 2 + part;
+    }
+  }
+  __device__ __forceinline__ int along() const { return horiz ? ly : lx; }   // the tile's row (column) inside the CU
+  __device__ __forceinline__ int nsize() const { return 8 << n; }            // the CU's side in samples
+  // the PU's record among those of its family (pus / pus_small) of the CTU with output index oc
+  __device__ __forceinline__ long long record(long long oc) const { return small ? oc * FHEVC_PUS_SMALL + entry : oc * FHEVC_PUS + entry; }
+};
+
+// the sum over the tiles of this lane's PU of a tile-aligned pass: n and s are wave-uniform
+__device__ __forceinline__ unsigned pu_sum(unsigned t8, int lane, const RefinePuPass& U)
+{
+  const int n = U.n, s = U.s, along = U.along();
+  const int ob = U.horiz ? 1 : 8, ab = U.horiz ? 8 : 1;   // lane bits across the cut's direction / along it
+  unsigned strip = t8;
+  for (int k = 0; k < n; ++k) strip += __shfl_xor(strip, ob << k);       // the CU's whole width (height) at this tile row (column)
+  const int own = s < 2 ? n - 1 : n - 2;                                 // ... summed over the lane's own half, or its own quarter
+  for (int k = 0; k < own; ++k) strip += __shfl_xor(strip, ab << k);
+  if (s < 2) return strip;
+  unsigned cu = strip;
+  for (int k = own; k < n; ++k) cu += __shfl_xor(cu, ab << k);
+  const int qpart = s & 1;                                               // 2NxnU, nLx2N: the quarter comes first; 2NxnD, nRx2N: last
+  const unsigned quarter = __shfl(strip, lane + ((qpart ? (1 << n) - 1 : 0) - along) * ab);
+  return U.part == qpart ? quarter : cu - quarter;
+}
+
+// xGetHADs of this lane's PU of pass U at the quarter-sample vector (qx, qy), before the shift by bit depth - 8: every lane predicts its tile there
+template <bool PACKED, int RP>
+__device__ __forceinline__ unsigned refine_pu_had(const short* s_ref, const unsigned* s_taps, const RefineArith& A, int lane, int tx, int ty, const RefinePuPass& U,
+                                                  int qx, int qy, const unsigned (&O)[32], bool inside)
+{
+  unsigned D[32];
+  int v[64];
+  refine_tile_at<PACKED, RP>(s_ref, s_taps, A, tx, ty, qx, qy, O, D, v);
+  if (U.small) {  // xCalcHADs4x4 per quadrant, (sum + 1) >> 1 each (TComRdCost.cpp:1771-1803); only the quadrants of this pass's part
+    unsigned sum = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      unsigned q;
+      if constexpr (PACKED) q = had4x4_packed(D, (k >> 1) * 4, (k & 1) * 2);
+      else q = had4x4_wide(v, (k >> 1) * 4, (k & 1) * 4);
+      sum += ((U.qmask >> k) & 1u) ? q : 0u;
+    }
+    sum = inside ? sum : 0u;
+    if (U.n == 1) { sum += __shfl_xor(sum, 1); sum += __shfl_xor(sum, 8); }  // the four tiles of the 16x16 CU
+    return sum;
+  }
+  return pu_sum(refine_had8x8<PACKED>(D, v, inside), lane, U);
+}
+
+// ---- the refinements' output record; the marker where nothing was refined ----
+__device__ __forceinline__ FhevcMotionQpelNode refine_record(bool valid, unsigned satd_int, unsigned satd_best, unsigned cost_best, int mvx, int mvy)
+{
+  FhevcMotionQpelNode o;
+  if (valid) { o.satd_int = satd_int; o.satd_best = satd_best; o.cost_best = cost_best; o.mvx = (short)mvx; o.mvy = (short)mvy; }
+  else { o.satd_int = o.satd_best = o.cost_best = 0xFFFFFFFFu; o.mvx = 0; o.mvy = 0; }
+  return o;
+}
+
+// ---- the merge list of TComDataCU::getInterMergeCandidates (TComDataCU.cpp:2142-2320) from the vectors nvec of the five neighbours L, A, AR, BL, AL of
+// which av says whether they can be used: HM's order with HM's four pruning pairs, AL only below four entries, then one zero vector.  Five "taken" flags in
+// registers; a lane whose list is shorter than its wave's longest picks the zero vector there and drops the result ----
+constexpr unsigned kMergeMark = 0xFFFFFFFFu;
+struct MergeList {
+  bool take[5];
+  unsigned nvec[5];
+  int num;
+  __device__ __forceinline__ MergeList(const bool (&av)[5], const unsigned (&vec)[5], bool node_in)
+  {
+#pragma unroll
+    for (int j = 0; j < 5; ++j) nvec[j] = vec[j];
+    take[0] = av[0];
+    take[1] = av[1] && !(av[0] && nvec[1] == nvec[0]);
+    take[2] = av[2] && !(av[1] && nvec[2] == nvec[1]);
+    take[3] = av[3] && !(av[0] && nvec[3] == nvec[0]);
+    const int n4 = (int)take[0] + (int)take[1] + (int)take[2] + (int)take[3];
+    take[4] = n4 < 4 && av[4] && !(av[0] && nvec[4] == nvec[0]) && !(av[1] && nvec[4] == nvec[1]);
+    const int n5 = n4 + (int)take[4];
+    num = node_in ? n5 + (n5 < 5 ? 1 : 0) : 0;   // the zero vector closes a list of fewer than five
+  }
+  // the longest list of the wave: the candidate loop's wave-uniform length
+  __device__ __forceinline__ int longest() const
+  {
+    int l = 1;
+#pragma unroll
+    for (int n = 2; n <= 5; ++n)
+      if (__builtin_amdgcn_ballot_w64(num >= n) != 0) l = n;
+    return l;
+  }
+  // entry i: its vector dword and which neighbour it came from (5: the zero vector, or the list has ended); unrolled, no dynamic indexing
+  __device__ __forceinline__ void pick(int i, unsigned& qv, int& src) const
+  {
+    qv = 0; src = 5;
+    int pos = 0;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      if (take[j] && pos == i) { qv = nvec[j]; src = j; }
+      pos += (int)take[j];
+    }
+  }
+};
+// z-scan index of (x, y) in a level's grid of up to 8 x 8 nodes: the bit interleave, x in the even bits
+__device__ __forceinline__ unsigned merge_z(unsigned x, unsigned y)
+{
+  const unsigned sx = (x & 1u) | ((x & 2u) << 1) | ((x & 4u) << 2), sy = (y & 1u) | ((y & 2u) << 1) | ((y & 4u) << 2);
+  return sx | (sy << 1);
+}
+// getCost(bits of merge index i) from the launch's table by number of bits: 1, 2, 3, 4, 4 -- MaxNumMergeCand 5: the last index saves its terminating bit
+__device__ __forceinline__ unsigned merge_index_cost(const unsigned* s_cost, int i) { return s_cost[i == 4 ? 4 : i + 1]; }
+// the best entry so far (strict "<": the first entry of equal cost wins) and the record it ends as
+struct MergeBest {
+  unsigned c = kMergeMark, s = kMergeMark, v = 0;
+  int i = 255, src = 255;
+  __device__ __forceinline__ void offer(int idx, int num, unsigned cost, unsigned satd, unsigned qv, int from)
+  {
+    if (idx < num && cost < c) { c = cost; s = satd; v = qv; i = idx; src = from; }
+  }
+  __device__ __forceinline__ FhevcMotionMergeNode record(int num) const
+  {
+    FhevcMotionMergeNode o;
+    o.satd_best = s; o.cost_best = c;
+    o.mvx = (short)(v & 0xFFFFu); o.mvy = (short)(v >> 16);
+    o.idx = (uint8_t)i; o.num = (uint8_t)num; o.src = (uint8_t)src; o.pad = 0;
+    return o;
+  }
+};
+
+// ---- launch.  Per layout the persistent grid has at most `cap` workgroups per CU (0: no cap) and, where `ask` is set, no more than the device says it
+// keeps resident (hipErrorLaunchOutOfResources where that is none); no more workgroups than there are CTUs ----
+struct RefineResidency { int cap; bool ask; };
+struct RefineLaunch {
+  size_t lds;   // dynamic LDS: the MR = 64 window (80 016 B), 0 at MR = 8
+  RefineResidency res;
+  int num_cus;
+  long long total;
+  hipStream_t stream;
+};
+
+// one kernel instance: its dynamic LDS allowed, and how many of its workgroups the device keeps on one CU (asked once per instance)
+template <auto Kernel>
+hipError_t refine_resident(size_t lds, int* per_cu)
+{
+  if (lds) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  if (!per_cu) return hipSuccess;
+  static std::atomic<int> asked{0};   // every device of a context is a gfx950: one answer per instance
+  int n = asked.load(std::memory_order_relaxed);
+  if (n == 0) {
+    const hipError_t q = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, Kernel, 256, lds);
+    if (q != hipSuccess) return q;
+    asked.store(n, std::memory_order_relaxed);
+  }
+  *per_cu = n;
+  return hipSuccess;
+}
+
+template <auto Kernel, typename... Args>
+hipError_t refine_launch_kernel(const RefineLaunch& L, Args... args)
+{
+  int asked = 0, per_cu = L.res.cap;
+  const hipError_t e = refine_resident<Kernel>(L.lds, L.res.ask ? &asked : nullptr);
+  if (e != hipSuccess) return e;
+  if (L.res.ask) {
+    if (asked < 1) return hipErrorLaunchOutOfResources;
+    if (per_cu == 0 || asked < per_cu) per_cu = asked;
+  }
+  const long long resident = (long long)per_cu * L.num_cus;
+  const int grid = (int)(L.total < resident ? L.total : resident);
+  hipLaunchKernelGGL(Kernel, dim3(grid), dim3(256), L.lds, L.stream, args...);
+  return hipGetLastError();
+}
+
+// what the launch functions of the five kernels share: nothing to do for an empty band; max_range 1 .. RANGE_MAX and a CTU count the kernels' int holds;
+// the layout from max_range (the MR = 64 one only where RANGE_MAX reaches it); launch(T(), packed, mr, L) with T = int16_t (HM Pel planes) or uint8_t,
+// packed (bit depth <= 10) as std::true_type / std::false_type, mr as std::integral_constant, and L for refine_launch_kernel
+template <int RANGE_MAX, typename Launch>
+hipError_t refine_launch(const FhevcFrames& fr, bool args_ok, int max_range, int num_cus, RefineResidency small, RefineResidency big, hipStream_t stream, Launch&& launch)
+{
+  const long long total = (long long)(fr.row_end - fr.row_begin) * fr.ctus_x * (fr.num_frames - 1);
+  if (total <= 0) return hipSuccess;
+  if (!args_ok || max_range < 1 || max_range > RANGE_MAX || total > 0x7FFFFFFF) return hipErrorInvalidValue;
+  const auto dispatch = [&](auto mr, RefineResidency res) -> hipError_t {
+    constexpr int MR = decltype(mr)::value;
+    const RefineLaunch L = { MR > FHEVC_MOTION_MAX_RANGE ? (size_t)RefineGeom<MR>::SAMPLES * sizeof(short) : 0, res, num_cus, total, stream };
+    const std::true_type yes; const std::false_type no;
+    if (fr.sample_bytes == 2 && fr.bit_depth <= 10) return launch(int16_t(), yes, mr, L);
+    if (fr.sample_bytes == 2) return launch(int16_t(), no, mr, L);
+    return launch(uint8_t(), yes, mr, L);
+  };
+  if constexpr (RANGE_MAX > FHEVC_MOTION_MAX_RANGE)
+    if (max_range > FHEVC_MOTION_MAX_RANGE) return dispatch(std::integral_constant<int, FHEVC_MOTION_WIDE_MAX_RANGE>(), big);
+  return dispatch(std::integral_constant<int, FHEVC_MOTION_MAX_RANGE>(), small);
 }
 
 }  // namespace

@@ -15,10 +15,12 @@ explicit stream, ending in a synchronise; every figure is the median of --repeat
 Recorded, not asserted: a / b, c / d, e / f with the run-to-run spread (the smallest and largest ratio of windows of the same round); by candidate count
 a / b and c / d would be near 5 / 18 plus the staging, and lists are often shorter than five.  Also recorded (g): per partition size how often a part's
 "merged" bit is set, how often `best` changes, and the mean cost_best with and without the merge costs.  Before anything is timed the device's selection
-of picture 0 is compared with the host function.  --lib times another build of the library (A/B of a kernel variant) under the same protocol.
+of picture 0 is compared with the host function.  Every leg's figures carry the SHA-256 of the buffers it wrote: the inputs are seeded, so two builds that
+behave alike give equal digests.  --lib times another build of the library (A/B of a kernel variant) under the same protocol.
 
 Needs an MI355X; without one it fails.  Writes profiles/motion_merge_pu.json (--out)."""
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -95,6 +97,8 @@ def main():
         "e_select_with_merge": lambda: select(True, d_shapes),
         "f_select_without_merge": lambda: select(False, d_shapes_plain),
     }
+    written = {name: [scratch_pu, scratch_small] for name in runs}   # the buffers a leg writes
+    written.update(c_merge_pu_64=[mpu64, msmall64], e_select_with_merge=[d_shapes, d_costs, d_merged], f_select_without_merge=[d_shapes_plain, d_costs])
 
     # the result first: picture 0 against the host function, and what the merge costs change (g)
     host = lambda t, dt, k: t.cpu().numpy().view(dt).reshape(total, k)
@@ -145,6 +149,11 @@ def main():
     for _ in range(args.repeats):     # interleaved: one window of each per round
         for name, fn in runs.items():
             ms[name].append(window(fn, launches[name]))
+    sha = {}
+    for name, fn in runs.items():     # one more launch of each, alone, and what it left behind
+        fn()
+        torch.cuda.synchronize()
+        sha[name] = hashlib.sha256(b"".join(t.cpu().numpy().tobytes() for t in written[name])).hexdigest()
 
     out = {"tool": "tools/motion_merge_pu_bench.py", "device": torch.cuda.get_device_name(0), "library": capi.load_library(args.lib).fhevc_version().decode(),
            "geometry": {"width": W, "height": H, "frames": NF, "pairs": P, "ctus_per_picture": n, "ctus": total, "qp": qp, "planes": "uint8"},
@@ -153,8 +162,8 @@ def main():
     for name in runs:
         v = ms[name]
         out["runs"][name] = {"ms": statistics.median(v), "ms_min": min(v), "ms_max": max(v), "spread_ms": max(v) - min(v), "windows": len(v),
-                             "launches_per_window": launches[name]}
-        print(f"{name:24s}: {statistics.median(v):10.3f} ms  ({min(v):.3f} .. {max(v):.3f})", flush=True)
+                             "launches_per_window": launches[name], "sha256": sha[name]}
+        print(f"{name:24s}: {statistics.median(v):10.3f} ms  ({min(v):.3f} .. {max(v):.3f})  sha256 {sha[name][:16]}", flush=True)
 
     def ratio(x, y):
         per_round = [a / b for a, b in zip(ms[x], ms[y])]

@@ -6,13 +6,18 @@ Per launch: HIP events on the caller's stream around a window of warmed launches
 --repeats windows with the smallest and largest next to it.  Measured in ONE process on one device:
   * the refinement alone (fhevc_motion_refine_device) on the nodes of the +-8 SATD search, and on those of the +-4 search;
   * the +-4 and the +-8 SATD searches alone (fhevc_motion_search_device);
-  * search plus refinement queued on one stream, for both ranges.
+  * search plus refinement queued on one stream, for both ranges;
+  * the refinement at max_range 64 (the MR = 64 layout) on the nodes of the +-64 SAD search (fhevc_motion_search_pu_wide_device).
 One statement is recorded (it does not make the tool fail): the refinement takes less time than the +-8 search.  A count from the code gives
 4 levels x 64 tiles x 18 candidates = 4 608 tile Hadamards per CTU against 5 184 (+-4) and 18 496 (+-8) of the search, plus about 1 500 filter
 multiply-adds per tile candidate.
 
+Every leg's figures carry the SHA-256 of the buffers it wrote: the inputs are seeded, so two builds that behave alike give equal digests.  --lib times
+another build of the library (A/B of a kernel variant) under the same protocol.
+
 Needs an MI355X; without one it fails.  Writes profiles/motion_refine.json (--out)."""
 import argparse
+import hashlib
 import json
 import os
 import socket
@@ -44,6 +49,7 @@ def main():
     ap.add_argument("--qp", type=int, default=32)
     ap.add_argument("--repeats", type=int, default=5, help="timed windows per figure (median, smallest, largest)")
     ap.add_argument("--launches", type=int, default=3, help="launches per window")
+    ap.add_argument("--lib", default=None, help="another build of the library to measure (default: the tree's own)")
     ap.add_argument("--commit", default=None, help="recorded in the output (default: git rev-parse HEAD)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "motion_refine.json"))
     args = ap.parse_args()
@@ -60,7 +66,7 @@ def main():
     st = ts.cuda_stream
     layout = (planes.data_ptr() + 2 * org, 2, stride, fs, NF)
 
-    def measure(fn):
+    def measure(fn, written):
         for _ in range(2):
             fn()
         torch.cuda.synchronize()
@@ -73,14 +79,19 @@ def main():
             e1.record()
             torch.cuda.synchronize()
             ev.append(e0.elapsed_time(e1) / args.launches)
-        return {"ms": statistics.median(ev), "ms_min": min(ev), "ms_max": max(ev), "windows": args.repeats, "launches_per_window": args.launches}
+        sha = hashlib.sha256()
+        for t in written:
+            sha.update(t.cpu().numpy().tobytes())
+        return {"ms": statistics.median(ev), "ms_min": min(ev), "ms_max": max(ev), "windows": args.repeats, "launches_per_window": args.launches,
+                "sha256": sha.hexdigest()}
 
-    ctx = capi.Context(W, H, 8, max_frames=NF)
+    ctx = capi.Context(W, H, 8, max_frames=NF, lib_path=args.lib)
     n = (NF - 1) * ctx.num_ctus
-    d_nodes = {r: torch.zeros(n * 85 * 16, dtype=torch.uint8, device="cuda") for r in (4, 8)}
+    d_nodes = {r: torch.zeros(n * 85 * 16, dtype=torch.uint8, device="cuda") for r in (4, 8, 64)}
     d_out = torch.zeros(n * 85 * 16, dtype=torch.uint8, device="cuda")
     for r in (4, 8):   # the nodes the refinement alone starts from
         ctx.motion_search_device(*layout, d_nodes[r].data_ptr(), stream=st, qp=qp, search_range=r)
+    ctx.motion_search_pu_wide_device(*layout, d_nodes[64].data_ptr(), None, None, stream=st, qp=qp, search_range=64)
     torch.cuda.synchronize()
 
     def search(r):
@@ -90,24 +101,27 @@ def main():
         ctx.motion_refine_device(*layout, d_nodes[r].data_ptr(), d_out.data_ptr(), stream=st, qp=qp, max_range=r)
 
     out = {"tool": "tools/motion_refine_bench.py", "commit": _commit(args.commit), "box": socket.gethostname(), "device": torch.cuda.get_device_name(0),
-           "library": capi.load_library().fhevc_version().decode(),
+           "library": capi.load_library(args.lib).fhevc_version().decode(),
            "geometry": {"width": W, "height": H, "frames": NF, "picture_pairs": NF - 1, "ctus_per_launch": n, "qp": qp, "planes": "int16", "clip": "frames.pan_clip"},
            "timing": "per launch; HIP events on the caller's stream around a window of launches ending in a synchronise; ms = median of the windows, "
                      "warmed by two launches; all figures from one process",
            "expectation": "the refinement takes less time than the +-8 SATD search (4 608 tile Hadamards per CTU against 18 496, plus ~1 500 filter "
                           "multiply-adds per tile candidate)"}
-    runs = {
-        "refine_after_range8": lambda: refine(8),
-        "refine_after_range4": lambda: refine(4),
-        "search_range4_satd": lambda: search(4),
-        "search_range8_satd": lambda: search(8),
-        "search_range4_plus_refine": lambda: (search(4), refine(4)),
-        "search_range8_plus_refine": lambda: (search(8), refine(8)),
+    runs = {   # what is launched, and the buffers it writes
+        "refine_after_range8": (lambda: refine(8), [d_out]),
+        "refine_after_range4": (lambda: refine(4), [d_out]),
+        "search_range4_satd": (lambda: search(4), [d_nodes[4]]),
+        "search_range8_satd": (lambda: search(8), [d_nodes[8]]),
+        "search_range4_plus_refine": (lambda: (search(4), refine(4)), [d_nodes[4], d_out]),
+        "search_range8_plus_refine": (lambda: (search(8), refine(8)), [d_nodes[8], d_out]),
+        "refine_after_range64": (lambda: refine(64), [d_out]),
     }
-    for name, fn in runs.items():
-        out[name] = measure(fn)
+    for name, (fn, written) in runs.items():
+        out[name] = measure(fn, written)
         r = out[name]
-        print(f"{name:28s}: {r['ms']:.3f} ms per launch ({r['ms_min']:.3f} .. {r['ms_max']:.3f})", flush=True)
+        print(f"{name:28s}: {r['ms']:.3f} ms per launch ({r['ms_min']:.3f} .. {r['ms_max']:.3f})  sha256 {r['sha256'][:16]}", flush=True)
+    refine(8)   # the content figures are those of the +-8 nodes
+    torch.cuda.synchronize()
     q = np.frombuffer(d_out.cpu().numpy().tobytes(), capi.MOTION_QPEL_DTYPE)
     live = q["cost_best"] != 0xFFFFFFFF
     out["content"] = {"nodes": int(live.sum()), "off_the_integer_grid": float((((q["mvx"] | q["mvy"]) & 3) != 0)[live].mean())}

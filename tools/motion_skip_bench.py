@@ -15,10 +15,12 @@ windows with the smallest and largest next to it:
   f  fhevc_p_tree_select_merge_device on the same records
 Recorded, not asserted: a / b, c / d, e / f with the run-to-run spread; the share of coded nodes with each bit set, per level, at QP 22 / 27 / 32 / 37;
 how often the skip rule changes depth_max.  Before anything is timed the device's skip records of picture pair 0 are compared with the host form, and the
-device's skip-tree records and maps of picture 0 with the host function.
+device's skip-tree records and maps of picture 0 with the host function.  Every leg's figures carry the SHA-256 of the buffers it wrote: the inputs are
+seeded, so two builds that behave alike give equal digests.  --lib times another build of the library (A/B of a kernel variant) under the same protocol.
 
 Needs an MI355X; without one it fails.  Writes profiles/motion_skip.json (--out)."""
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -43,6 +45,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=7, help="rounds: timed windows per figure (median, smallest, largest); at least 7")
     ap.add_argument("--launches", type=int, default=5, help="launches per window of the four motion legs (milliseconds each)")
     ap.add_argument("--tree-launches", type=int, default=50, help="launches per window of the two tree legs (tens of microseconds each)")
+    ap.add_argument("--lib", default=None, help="another build of the library to measure (default: the tree's own)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "motion_skip.json"))
     args = ap.parse_args()
     if args.repeats < 7:
@@ -53,7 +56,7 @@ def main():
         sys.exit("motion_skip_bench.py needs an MI355X: no GPU is visible")
     W, H, NF, qp = args.width, args.height, args.frames, args.qp
     P = NF - 1
-    ctx = capi.Context(W, H, 8, max_frames=NF)
+    ctx = capi.Context(W, H, 8, max_frames=NF, lib_path=args.lib)
     n = ctx.num_ctus
     total = P * n
     pics = frames.pan_clip(W, H, NF)
@@ -96,6 +99,7 @@ def main():
         "e_tree_with_skip": lambda: tree(True),
         "f_tree_with_merge": lambda: tree(False),
     }
+    written = {name: [d_min, d_max, d_tree] if "tree" in name else [scratch] for name in runs}   # the buffers a leg writes
 
     # the result first: picture pair 0 against the host form, picture 0's tree against the host function
     host = lambda t, dt: t.cpu().numpy().view(dt).reshape(total, 85)
@@ -150,8 +154,13 @@ def main():
     for _ in range(args.repeats):     # interleaved: one window of each per round
         for name, fn in runs.items():
             ms[name].append(window(fn, launches[name]))
+    sha = {}
+    for name, fn in runs.items():     # one more launch of each, alone, and what it left behind
+        fn()
+        torch.cuda.synchronize()
+        sha[name] = hashlib.sha256(b"".join(t.cpu().numpy().tobytes() for t in written[name])).hexdigest()
 
-    out = {"tool": "tools/motion_skip_bench.py", "device": torch.cuda.get_device_name(0), "library": capi.load_library().fhevc_version().decode(),
+    out = {"tool": "tools/motion_skip_bench.py", "device": torch.cuda.get_device_name(0), "library": capi.load_library(args.lib).fhevc_version().decode(),
            "geometry": {"width": W, "height": H, "frames": NF, "pairs": P, "ctus_per_picture": n, "ctus": total, "qp": qp, "planes": "uint8"},
            "timing": "HIP events on one stream around warmed, repeated launches ending in a synchronise; rounds interleave the six runs; ms = median of the windows",
            "device_equals_host_path_on_picture_0": bool(equal), "effect_of_the_skip_rule_at_range_8": effect,
@@ -159,8 +168,8 @@ def main():
     for name in runs:
         v = ms[name]
         out["runs"][name] = {"ms": statistics.median(v), "ms_min": min(v), "ms_max": max(v), "spread_ms": max(v) - min(v), "windows": len(v),
-                             "launches_per_window": launches[name]}
-        print(f"{name:22s}: {statistics.median(v):10.3f} ms  ({min(v):.3f} .. {max(v):.3f})", flush=True)
+                             "launches_per_window": launches[name], "sha256": sha[name]}
+        print(f"{name:22s}: {statistics.median(v):10.3f} ms  ({min(v):.3f} .. {max(v):.3f})  sha256 {sha[name][:16]}", flush=True)
 
     def ratio(x, y):
         per_round = [a / b for a, b in zip(ms[x], ms[y])]
