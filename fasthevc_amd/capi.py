@@ -44,6 +44,7 @@ SYMBOLS = [
     "fhevc_motion_merge", "fhevc_motion_merge_device", "fhevc_p_tree_select_merge", "fhevc_p_tree_select_merge_device", "fhevc_p_tree_merge_frame",
     "fhevc_motion_merge_pu", "fhevc_motion_merge_pu_device", "fhevc_pu_shape_select_merge", "fhevc_pu_shape_select_merge_device", "fhevc_p_tree_merge_pu_frame",
     "fhevc_motion_skip", "fhevc_motion_skip_device", "fhevc_p_tree_select_skip", "fhevc_p_tree_select_skip_device",
+    "fhevc_motion_amvp", "fhevc_motion_amvp_device", "fhevc_motion_amvp_picture", "fhevc_p_tree_amvp_frame",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -100,6 +101,9 @@ MOTION_MERGE_DTYPE = np.dtype([("satd_best", np.uint32), ("cost_best", np.uint32
 MOTION_SKIP_DTYPE = np.dtype([("coef_max", np.uint32), ("level_sum", np.uint32), ("nonzero", np.uint16), ("flags", np.uint8), ("pad", np.uint8),
                               ("mvx", np.int16), ("mvy", np.int16)])
 SKIP_ZERO_PLAIN, SKIP_ZERO_HALF = 1, 2
+# fhevc_motion_mvp: the predictor fhevc_motion_amvp* priced an entry against (src: 0..4 = L, A, AR, BL, AL, 5 = a filled zero; idx = src = 255: no price)
+MOTION_MVP_DTYPE = np.dtype([("px", np.int16), ("py", np.int16), ("idx", np.uint8), ("num_spatial", np.uint8), ("src", np.uint8), ("bits", np.uint8)])
+MVP_BIT_COSTS = 67
 MERGE_L, MERGE_A, MERGE_AR, MERGE_BL, MERGE_AL, MERGE_ZERO = 0, 1, 2, 3, 4, 5
 # fhevc_p_tree_node: one record per CU node (flags: 1 split_sure, 2 stop_sure, 4 CROSSING, 8 ABSENT, 16 own available, 32 kids available)
 TREE_DTYPE = np.dtype([("cost_own", np.uint32), ("cost_kids", np.uint32), ("cost_tree", np.uint32), ("flags", np.uint8), ("level", np.uint8), ("pad", np.uint8, (2,))])
@@ -251,6 +255,10 @@ def load_library(path=None):
     lib.fhevc_p_tree_select_skip.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp]
     lib.fhevc_p_tree_select_skip_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp, vp]
     lib.fhevc_p_tree_merge_pu_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), vp, vp, vp, vp]
+    lib.fhevc_motion_amvp.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.fhevc_motion_amvp_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.fhevc_motion_amvp_picture.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.fhevc_p_tree_amvp_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), vp, vp, vp, vp]
     lib.fhevc_predict_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, vp, vp]
     lib.fhevc_alloc_host.argtypes = [vp, C.c_size_t]
     lib.fhevc_alloc_host.restype = vp
@@ -426,6 +434,34 @@ def pu_shape_select_merge(nodes, pus, pus_small, merge_pus, merge_pus_small, wid
         if rc != OK:
             raise FastHevcError(rc, "fhevc_pu_shape_select_merge")
     return (out, costs, merged) if with_costs else (out, merged)
+
+
+def _amvp_arrays(n_ctus, nodes, pus, pus_small, with_records, with_mvp):
+    """the inputs of the re-pricing as contiguous [n_ctus, per] arrays (None stays None) and, per family that has an input, its zeroed outputs"""
+    ins, outs, mvps = [], [], []
+    for a, per in ((nodes, NODES_PER_CTU), (pus, PUS_PER_CTU), (pus_small, PUS_SMALL_PER_CTU)):
+        if a is not None:
+            a = np.ascontiguousarray(a).reshape(n_ctus, per)
+            assert a.dtype.itemsize == 16
+        ins.append(a)
+        outs.append(np.zeros((n_ctus, per), MOTION_QPEL_DTYPE) if a is not None and with_records else None)
+        mvps.append(np.zeros((n_ctus, per), MOTION_MVP_DTYPE) if a is not None and with_mvp else None)
+    return ins, outs, mvps
+
+
+def motion_amvp_picture(nodes, pus, pus_small, width, height, bit_depth=8, qp=32, rows=None, with_records=True, with_mvp=False):
+    """config 4, host side (fhevc_motion_amvp_picture; no context, no device): the refined records [band CTUs, 85] / [.., 124] / [.., 384]
+    (MOTION_QPEL_DTYPE; pus / pus_small may be None) re-priced against neighbour predictors -> (nodes, pus, pus_small) re-priced records, None for a
+    family without input; with_mvp: behind them the three MOTION_MVP_DTYPE arrays; with_records=False: only those"""
+    lib = load_library()
+    cw, ch = (width + 63) // 64, (height + 63) // 64
+    rb, re = rows if rows is not None else (0, ch)
+    ins, outs, mvps = _amvp_arrays((re - rb) * cw, nodes, pus, pus_small, with_records, with_mvp)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    rc = lib.fhevc_motion_amvp_picture(width, height, bit_depth, rb, re, qp, *[ptr(a) for a in ins + outs + mvps])
+    if rc != OK:
+        raise FastHevcError(rc, "fhevc_motion_amvp_picture")
+    return tuple(outs if with_records else []) + tuple(mvps if with_mvp else [])
 
 
 def p_depth_range(nodes, prev_depth, width, height, qp, rule=None):
@@ -715,6 +751,22 @@ class Context:
         self._check(self.lib.fhevc_motion_merge_pu_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range,
                                                           d_refined, d_out_pus, d_out_pus_small, stream))
 
+    def motion_amvp(self, nodes, pus=None, pus_small=None, qp=32, with_records=True, with_mvp=False):
+        """config 4: the refined records of one picture [numCtus, 85] / [numCtus, 124] / [numCtus, 384] (MOTION_QPEL_DTYPE; pus / pus_small may be None)
+        re-priced against neighbour predictors on the device -> as motion_amvp_picture"""
+        ins, outs, mvps = _amvp_arrays(self.num_ctus, nodes, pus, pus_small, with_records, with_mvp)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._check(self.lib.fhevc_motion_amvp(self.h, qp, *[ptr(a) for a in ins + outs + mvps]))
+        return tuple(outs if with_records else []) + tuple(mvps if with_mvp else [])
+
+    def motion_amvp_device(self, num_frames, d_nodes, d_pus=None, d_pus_small=None, d_out_nodes=None, d_out_pus=None, d_out_pus_small=None, d_mvp_nodes=None,
+                           d_mvp_pus=None, d_mvp_pus_small=None, rows=None, stream=None, qp=32):
+        """the refined records of num_frames - 1 picture pairs (85 / 124 / 384 per CTU, compact over the rows) re-priced against neighbour predictors;
+        d_out_*: as many records (16 B), d_mvp_*: as many predictor records (8 B); each output may be None, not all six.  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_motion_amvp_device(self.h, num_frames, rb, re, qp, d_nodes, d_pus, d_pus_small, d_out_nodes, d_out_pus, d_out_pus_small,
+                                                      d_mvp_nodes, d_mvp_pus, d_mvp_pus_small, stream))
+
     def motion_search_pu(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=4, with_nodes=False):
         """config 4: the search of motion_search for the rectangular PUs -> [numCtus, 124] MOTION_DTYPE in the order of motion_pu_index; with_nodes:
         (nodes [numCtus, 85], pus), the nodes as motion_search returns them, from the same pass.  search_range 1..8."""
@@ -924,6 +976,12 @@ class Context:
                               with_shapes=False, with_merge=False):
         """p_tree_merge_frame with the merge stage per PU behind the one per node, and the selection on merge-aware costs; the same results"""
         return self._p_tree_merge_frame(self.lib.fhevc_p_tree_merge_pu_frame, cur_plane, ref_plane, origin, stride, qp, search_range, coarse_range, shape_rule,
+                                        tree_rule, with_shapes, with_merge)
+
+    def p_tree_amvp_frame(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=8, coarse_range=0, shape_rule=None, tree_rule=None,
+                          with_shapes=False, with_merge=False):
+        """p_tree_merge_pu_frame with the re-pricing against neighbour predictors between the refinements and the merge stages; the same results"""
+        return self._p_tree_merge_frame(self.lib.fhevc_p_tree_amvp_frame, cur_plane, ref_plane, origin, stride, qp, search_range, coarse_range, shape_rule,
                                         tree_rule, with_shapes, with_merge)
 
     def p_tree_merge_frame(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=8, coarse_range=0, shape_rule=None, tree_rule=None,

@@ -1,5 +1,6 @@
 // fhevc_ctx.h -- private to the C-ABI layer (fhevc_api.hip, fhevc_motion_api.hip, fhevc_weights.hip): the context behind the opaque fhevc_ctx of
-// include/fasthevc.h, its error helpers, and the few functions that cross those files.
+// include/fasthevc.h, its error helpers, and the few functions that cross those files.  (fhevc_host.hip, which never touches a context, takes
+// sqrt_lambda_intra from here: the host twin of the re-pricing builds the table of bit costs the device form builds.)
 #pragma once
 #include "../../include/fasthevc.h"
 #include "fhevc_internal.h"
@@ -50,14 +51,16 @@ struct fhevc_ctx {
   bool timing = false;
   std::vector<TimedLaunch> pending;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-  // per timing slot (14, 16, 18, 20 and 22 are not in use); config 4's slots and its staging buffers d_pair .. d_p_maps: the tables in fhevc_motion_api.hip
-  double sum_ms[24] = {};
-  uint64_t launches[24] = {};
+  // per timing slot (14, 16, 18, 20, 22 and 24 are not in use); config 4's slots and its staging buffers d_pair .. d_p_maps: the tables in fhevc_motion_api.hip
+  double sum_ms[26] = {};
+  uint64_t launches[26] = {};
   double* d_act = nullptr;
   int16_t* d_pair = nullptr;
   FhevcMotionNode *d_motion = nullptr, *d_motion_pu = nullptr, *d_motion_pu_small = nullptr, *d_centres = nullptr;
   FhevcMotionQpelNode *d_qpel = nullptr, *d_qpel_pu = nullptr, *d_qpel_pu_small = nullptr;
   FhevcMotionMergeNode* d_merge_pu = nullptr;
+  FhevcMotionQpelNode* d_amvp = nullptr;     // the 593 re-priced entries per CTU of fhevc_motion_amvp and of fhevc_p_tree_amvp_frame
+  FhevcMotionMvp* d_amvp_mvp = nullptr;      // ... and their predictor records
   uint8_t* d_p_maps = nullptr;
   FhevcNodeCost* d_cand_all = nullptr; uint8_t* d_cand = nullptr;   // fhevc_intra_first_pass_candidates: every (node, mode) cost, the lists
   FhevcNodeCost* d_best4 = nullptr; uint8_t* d_modes4 = nullptr;    // fhevc_intra_first_pass_4x4: the best mode and the list of every 4x4 PU

@@ -1,7 +1,8 @@
 // fhevc_host.hip -- the functions of include/fasthevc.h that take no context and never touch the device: the band split, the YUV reader, the AQ
 // partition / QP arithmetic, the host form of the P-picture rule, the two motion-compensated depth maps and the host form of the
-// partition-size selection.  Plain C++.
+// partition-size selection, of the tree decision and of the re-pricing against neighbour predictors.  Plain C++.
 #include "../../include/fasthevc.h"
+#include "fhevc_ctx.h"   // sqrt_lambda_intra
 #include "fhevc_internal.h"
 
 #include <algorithm>
@@ -442,6 +443,107 @@ int fhevc_p_tree_select_skip(const fhevc_pu_shape_node* shapes, const fhevc_moti
 {
   if (!merge || !skip || skip_mask < 0 || skip_mask > 3) return FHEVC_E_INVALID;
   return p_tree_select(shapes, merge, valid_w, valid_h, rule, depth_min, depth_max, tree, skip, skip_mask);
+}
+
+}  // extern "C"
+
+// ---- refined costs re-priced against neighbour predictors (spec in include/fasthevc.h; the device form is k_motion_amvp.hip) ----
+// One family of one picture: entries[band CTUs][per] in the order `index` gives for (node, shape, part) -- shape -1: the square node itself.  The candidates are
+// looked up in `nodes` by picture position, the own-CU candidate in `entries`; list and choice are fhevc_mvp_choose
+namespace {
+struct AmvpPicture { int width, height, cw, row_begin, row_end; };
+
+inline unsigned amvp_z(int x, int y)
+{
+  unsigned z = 0;
+  for (int b = 0; b < 3; ++b) z |= (unsigned)((x >> b) & 1) << (2 * b) | (unsigned)((y >> b) & 1) << (2 * b + 1);
+  return z;
+}
+
+void amvp_entry(const AmvpPicture& P, const FhevcMvpBitCost& cost, const fhevc_motion_qpel_node* nodes, const fhevc_motion_qpel_node* entries, int per, int i, int k, int shape,
+                int part, int e, fhevc_motion_qpel_node* out, fhevc_motion_mvp* mvp)
+{
+  const uint32_t mark = 0xFFFFFFFFu;
+  const int ctu = P.row_begin * P.cw + i, cx = ctu % P.cw, cy = ctu / P.cw;
+  const int lvl = k < 1 ? 0 : (k < 5 ? 1 : (k < 21 ? 2 : 3)), n = 1 << lvl, s = 64 >> lvl;
+  const int bx = (k - kLevel[lvl].first) % n, by = (k - kLevel[lvl].first) / n;
+  const int cu_x = cx * 64 + bx * s, cu_y = cy * 64 + by * s;          // the CU in picture samples
+  int x = cu_x, y = cu_y, w = s, h = s;
+  if (shape >= 0) {                                                    // getPartIndexAndSize
+    const int cut = shape < 2 ? s / 2 : ((shape & 1) ? 3 * s / 4 : s / 4);
+    if (shape == 0 || shape == 2 || shape == 3) { y += part ? cut : 0; h = part ? s - cut : cut; }
+    else { x += part ? cut : 0; w = part ? s - cut : cut; }
+  }
+  const fhevc_motion_qpel_node& in = entries[(size_t)i * per + e];
+  const bool inside = cu_x + s <= P.width && cu_y + s <= P.height;
+  auto packed = [](const fhevc_motion_qpel_node& r) { return (uint32_t)(uint16_t)r.mvx | (uint32_t)(uint16_t)r.mvy << 16; };
+  bool av[5];
+  uint32_t vec[5];
+  const int sxs[5] = { x - 1, x + w - 1, x + w, x - 1, x - 1 }, sys[5] = { y + h - 1, y - 1, y - 1, y + h, y - 1 };   // L, A, AR, BL, AL
+  for (int j = 0; j < 5; ++j) {
+    const int sx = sxs[j], sy = sys[j];
+    av[j] = false; vec[j] = 0;
+    if (sx >= cu_x && sx < cu_x + s && sy >= cu_y && sy < cu_y + s) {
+      // inside the entry's own CU: part 0 of the same partition size, the entry before this one
+      if (part == 1) {
+        const fhevc_motion_qpel_node& p0 = entries[(size_t)i * per + e - 1];
+        av[j] = p0.cost_best != mark; vec[j] = packed(p0);
+      }
+      continue;
+    }
+    if (sx < 0 || sy < 0) continue;
+    const int gx = sx / s, gy = sy / s;                                // the same-level node that holds the sample
+    if ((gx + 1) * s > P.width || (gy + 1) * s > P.height) continue;   // not on the grid or not INSIDE
+    const int ncx = gx >> lvl, ncy = gy >> lvl, nctu = ncy * P.cw + ncx;
+    if (ncy < P.row_begin || ncy >= P.row_end) continue;
+    const unsigned zn = amvp_z(gx & (n - 1), gy & (n - 1)), zme = amvp_z(bx, by);
+    if (!(nctu < ctu || (nctu == ctu && zn < zme))) continue;          // the coding-order key, strictly smaller
+    const fhevc_motion_qpel_node& r = nodes[(size_t)(nctu - P.row_begin * P.cw) * FHEVC_NODES + kLevel[lvl].first + (gy & (n - 1)) * n + (gx & (n - 1))];
+    av[j] = r.cost_best != mark; vec[j] = packed(r);
+  }
+  const FhevcMvpChoice c = fhevc_mvp_choose(av[0], av[1], av[2], av[3], av[4], vec[0], vec[1], vec[2], vec[3], vec[4], packed(in));
+  const bool priced = inside && in.cost_best != mark;
+  if (out) {
+    fhevc_motion_qpel_node o = in;                                     // an input marker record is copied as it is
+    if (priced) o.cost_best = (uint32_t)std::min<uint64_t>((uint64_t)in.satd_best + cost.c[c.bits], 0xFFFFFFFEu);
+    if (!inside) { o.satd_int = o.satd_best = o.cost_best = mark; o.mvx = o.mvy = 0; }
+    out[(size_t)i * per + e] = o;
+  }
+  if (mvp) {
+    fhevc_motion_mvp m = { 0, 0, 255, 0, 255, 0 };
+    if (priced) m = { (int16_t)(c.pred & 0xFFFFu), (int16_t)(c.pred >> 16), (uint8_t)c.idx, (uint8_t)c.num_spatial, (uint8_t)c.src, (uint8_t)c.bits };
+    mvp[(size_t)i * per + e] = m;
+  }
+}
+}  // namespace
+
+extern "C" {
+
+int fhevc_motion_amvp_picture(int width, int height, int bit_depth, int ctu_row_begin, int ctu_row_end, int qp, const fhevc_motion_qpel_node* nodes,
+                              const fhevc_motion_qpel_node* pus, const fhevc_motion_qpel_node* pus_small, fhevc_motion_qpel_node* out_nodes,
+                              fhevc_motion_qpel_node* out_pus, fhevc_motion_qpel_node* out_pus_small, fhevc_motion_mvp* mvp_nodes, fhevc_motion_mvp* mvp_pus,
+                              fhevc_motion_mvp* mvp_pus_small)
+{
+  if (width < 8 || height < 8 || bit_depth < 8 || bit_depth > 12 || qp < 0 || qp > 51) return FHEVC_E_INVALID;
+  const int cw = (width + 63) / 64, ch = (height + 63) / 64;
+  if (ctu_row_begin < 0 || ctu_row_end > ch || ctu_row_begin > ctu_row_end) return FHEVC_E_INVALID;
+  if (!nodes || (!out_nodes && !out_pus && !out_pus_small && !mvp_nodes && !mvp_pus && !mvp_pus_small)) return FHEVC_E_INVALID;
+  if ((!pus && (out_pus || mvp_pus)) || (!pus_small && (out_pus_small || mvp_pus_small))) return FHEVC_E_INVALID;
+  // getCost(b) at the slice QP's motion lambda (the lambda does not depend on the bit depth), as the device form's launch gets it
+  const FhevcMvpBitCost cost = fhevc_mvp_bit_cost_table(65536.0 * sqrt_lambda_intra(qp));
+  const AmvpPicture P = { width, height, cw, ctu_row_begin, ctu_row_end };
+  for (int i = 0; i < (ctu_row_end - ctu_row_begin) * cw; ++i) {
+    if (out_nodes || mvp_nodes)
+      for (int k = 0; k < FHEVC_NODES; ++k) amvp_entry(P, cost, nodes, nodes, FHEVC_NODES, i, k, -1, 0, k, out_nodes, mvp_nodes);
+    for (int k = 0; k < FHEVC_NODES; ++k)
+      for (int shape = 0; shape < 6; ++shape)
+        for (int part = 0; part < 2; ++part) {
+          const int e = fhevc_motion_pu_index(k, shape, part), es = fhevc_motion_pu_small_index(k, shape, part);
+          if (e >= 0 && (out_pus || mvp_pus)) amvp_entry(P, cost, nodes, pus, FHEVC_PUS, i, k, shape, part, e, out_pus, mvp_pus);
+          if (es >= 0 && (out_pus_small || mvp_pus_small)) amvp_entry(P, cost, nodes, pus_small, FHEVC_PUS_SMALL, i, k, shape, part, es, out_pus_small, mvp_pus_small);
+        }
+  }
+  return FHEVC_OK;
 }
 
 int fhevc_p_motion_compensated_depth(const fhevc_motion_node* nodes, const uint8_t* prev_map, int width, int height, int ctu, uint8_t* out)

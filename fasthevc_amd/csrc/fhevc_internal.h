@@ -244,6 +244,56 @@ hipError_t fhevc_launch_motion_merge(const FhevcFrames& fr, int max_range, const
 hipError_t fhevc_launch_motion_merge_pu(const FhevcFrames& fr, int max_range, const FhevcMvBitCost& cost, const FhevcMotionQpelNode* d_refined,
                                         FhevcMotionMergeNode* d_out_pus, FhevcMotionMergeNode* d_out_small, int num_cus, hipStream_t stream);
 
+// ---- refined costs re-priced against neighbour predictors (k_motion_amvp.hip; config 4) --------------------------
+// getCost(bits) for every number of bits two exp-Golomb components of a DIFFERENCE of two int16 vectors can take: at most 2 * 33; travels by value
+#define FHEVC_MVP_BIT_COSTS 67
+struct FhevcMvpBitCost { uint32_t c[FHEVC_MVP_BIT_COSTS]; };
+// motion_lambda: 65536 * sqrt(lambda) of the slice QP, the number mv_bit_cost_table (fhevc_motion_api.hip) builds FhevcMvBitCost from
+inline FhevcMvpBitCost fhevc_mvp_bit_cost_table(double motion_lambda)
+{
+  FhevcMvpBitCost t;
+  for (int b = 0; b < FHEVC_MVP_BIT_COSTS; ++b) t.c[b] = (uint32_t)((motion_lambda * (unsigned)b) / 65536.0);
+  return t;
+}
+struct FhevcMotionMvp { int16_t px, py; uint8_t idx, num_spatial, src, bits; };
+static_assert(sizeof(FhevcMotionMvp) == 8, "predictor record: 8 bytes without padding");
+// xGetExpGolombNumberOfBits at cost scale 0 of a vector difference v (|v| <= 65535): 2 floor(log2 t) + 1, t = v <= 0 ? (-v << 1) + 1 : v << 1; at most 33
+__host__ __device__ inline int fhevc_mvd_bits(int v)
+{
+  const unsigned t = v <= 0 ? ((unsigned)(-v) << 1) + 1u : (unsigned)v << 1;
+  return 2 * (31 - __builtin_clz(t)) + 1;
+}
+// List and choice of fhevc_motion_amvp* (include/fasthevc.h), shared by the kernel and the host twin.  The candidates at L, A, AR, BL, AL: whether each is
+// available, and its vector (as dword 3 of a record: mvx in the low half); q: the entry's own vector, packed alike.  a = the first available of (BL, L),
+// b = of (AR, A, AL); b is dropped if it equals a; (0, 0) fills the list up to two; the first index of least bits wins.  Ten scalars, no arrays: a select
+// between two elements of an array handed over by address becomes an indexed load, and the array then leaves the registers
+struct FhevcMvpChoice { uint32_t pred; int idx, num_spatial, src, bits; };
+__host__ __device__ inline FhevcMvpChoice fhevc_mvp_choose(bool av_l, bool av_a, bool av_ar, bool av_bl, bool av_al, uint32_t v_l, uint32_t v_a, uint32_t v_ar, uint32_t v_bl,
+                                                           uint32_t v_al, uint32_t q)
+{
+  const bool has_a = av_bl || av_l;
+  bool has_b = av_ar || av_a || av_al;
+  const uint32_t va = av_bl ? v_bl : v_l, vb = av_ar ? v_ar : (av_a ? v_a : v_al);
+  const int sa = av_bl ? 3 : 0, sb = av_ar ? 2 : (av_a ? 1 : 4);
+  if (has_a && has_b && va == vb) has_b = false;
+  const uint32_t p0 = has_a ? va : (has_b ? vb : 0u), p1 = has_a && has_b ? vb : 0u;
+  const int s0 = has_a ? sa : (has_b ? sb : 5), s1 = has_a && has_b ? sb : 5;
+  const int qx = (int16_t)(q & 0xFFFFu), qy = (int16_t)(q >> 16);
+  const int b0 = fhevc_mvd_bits(qx - (int16_t)(p0 & 0xFFFFu)) + fhevc_mvd_bits(qy - (int16_t)(p0 >> 16));
+  const int b1 = fhevc_mvd_bits(qx - (int16_t)(p1 & 0xFFFFu)) + fhevc_mvd_bits(qy - (int16_t)(p1 >> 16));
+  FhevcMvpChoice c;
+  c.idx = b1 < b0 ? 1 : 0;
+  c.pred = c.idx ? p1 : p0; c.src = c.idx ? s1 : s0; c.bits = c.idx ? b1 : b0;
+  c.num_spatial = (has_a ? 1 : 0) + (has_b ? 1 : 0);
+  return c;
+}
+// fr: geometry, band, num_frames = the picture pairs of the batch (luma is not read).  d_nodes (never null) / d_pus / d_pus_small: num_frames * band CTUs * 85 /
+// 124 / 384 refined entries; d_out_*: as many records, d_mvp_*: as many predictor records; each output may be null (not all six), all compact over the band
+hipError_t fhevc_launch_motion_amvp(const FhevcFrames& fr, const FhevcMvpBitCost& cost, const FhevcMotionQpelNode* d_nodes, const FhevcMotionQpelNode* d_pus,
+                                    const FhevcMotionQpelNode* d_pus_small, FhevcMotionQpelNode* d_out_nodes, FhevcMotionQpelNode* d_out_pus,
+                                    FhevcMotionQpelNode* d_out_small, FhevcMotionMvp* d_mvp_nodes, FhevcMotionMvp* d_mvp_pus, FhevcMotionMvp* d_mvp_small, int num_cus,
+                                    hipStream_t stream);
+
 // ---- the zero-residual (skip) test per CU node at its merge vector (k_motion_skip.hip; config 4) --------------------------
 struct FhevcMotionSkipNode { uint32_t coef_max, level_sum; uint16_t nonzero; uint8_t flags, pad; int16_t mvx, mvy; };
 static_assert(sizeof(FhevcMotionSkipNode) == 16, "skip record: 16 bytes without padding");

@@ -48,6 +48,7 @@ template <> struct Kernel<fhevc_motion_merge_node> { using T = FhevcMotionMergeN
 template <> struct Kernel<fhevc_motion_skip_node> { using T = FhevcMotionSkipNode; };
 template <> struct Kernel<fhevc_pu_shape_node> { using T = FhevcPuShapeNode; };
 template <> struct Kernel<fhevc_p_tree_node> { using T = FhevcPTreeNode; };
+template <> struct Kernel<fhevc_motion_mvp> { using T = FhevcMotionMvp; };
 template <class P> typename Kernel<P>::T* kn(P* p) { return reinterpret_cast<typename Kernel<P>::T*>(p); }
 template <class P> const typename Kernel<P>::T* kn(const P* p) { return reinterpret_cast<const typename Kernel<P>::T*>(p); }
 static_assert(sizeof(fhevc_motion_node) == 16 && sizeof(FhevcMotionNode) == 16 && sizeof(fhevc_motion_qpel_node) == 16 && sizeof(FhevcMotionQpelNode) == 16, "node layouts");
@@ -55,6 +56,8 @@ static_assert(sizeof(fhevc_motion_merge_node) == 16 && sizeof(FhevcMotionMergeNo
 static_assert(sizeof(fhevc_motion_skip_node) == 16 && offsetof(fhevc_motion_skip_node, nonzero) == 8 && offsetof(fhevc_motion_skip_node, flags) == 10 &&
               offsetof(fhevc_motion_skip_node, mvx) == 12 && offsetof(FhevcMotionSkipNode, flags) == 10 && offsetof(FhevcMotionSkipNode, mvx) == 12, "skip record layout");
 static_assert(FHEVC_PUS_PER_CTU == FHEVC_PUS && FHEVC_PUS_SMALL_PER_CTU == FHEVC_PUS_SMALL, "PU counts");
+static_assert(sizeof(fhevc_motion_mvp) == 8 && offsetof(fhevc_motion_mvp, idx) == 4 && offsetof(fhevc_motion_mvp, bits) == 7 && offsetof(FhevcMotionMvp, bits) == 7,
+              "predictor record layout");
 
 // ---- how every device form over a batch of picture pairs opens ----
 
@@ -105,11 +108,13 @@ int device_form(fhevc_ctx* c, bool args_ok, const char* bad_args, const Batch& b
 //   d_centres                1                 the centres that the centred searches and refinements read
 //   d_merge_pu               508 (all PUs)     the PUs' merge records: the 124 in fhevc_motion_pu_index order, behind them the 384 (fhevc_motion_merge_pu,
 //                                              fhevc_p_tree_merge_pu_frame) -- 8 128 B per CTU; no dead buffer of the chain holds that much
+//   d_amvp, d_amvp_mvp       593 (everything)  the re-priced entries and their predictor records (8 bytes each): the 85, behind them the 124, behind them the
+//                                              384 (fhevc_motion_amvp, fhevc_p_tree_amvp_frame)
 //   d_p_maps                 3 x 256 bytes     the reference picture's depth map, depth_min, depth_max (fhevc_p_predict_frame; the tree chains use the last two)
 //
 // The timing slots (fhevc_kernel_timing) of the launches below: 4 fhevc_motion_search, 5 the P rule, 7 fhevc_motion_refine, 8 / 9 the searches of the PUs / the
 // small PUs, 10 fhevc_motion_refine_pu, 11 / 12 the wide search / refinement, 13 the partition sizes, 15 the centres and everything centred, 17 the tree, 19 the merge stage,
-// 21 the merge stage per PU, 23 the zero-residual test
+// 21 the merge stage per PU, 23 the zero-residual test, 25 the re-pricing against neighbour predictors
 struct Family { int per_ctu; FhevcMotionNode* fhevc_ctx::*found; FhevcMotionQpelNode* fhevc_ctx::*refined; };
 constexpr Family kNodes = { FHEVC_NODES, &fhevc_ctx::d_motion, &fhevc_ctx::d_qpel }, kPus = { FHEVC_PUS, &fhevc_ctx::d_motion_pu, &fhevc_ctx::d_qpel_pu },
                  kSmall = { FHEVC_PUS_SMALL, &fhevc_ctx::d_motion_pu_small, &fhevc_ctx::d_qpel_pu_small }, kCentres = { 1, &fhevc_ctx::d_centres, nullptr };
@@ -161,6 +166,8 @@ class HostForm {
     if (rc != FHEVC_OK) (void)hipStreamSynchronize(c->stream);   // the uploads read the caller's buffers, the downloads write them: through before a failed call returns
     return rc;
   }
+  // ... of a form that reads no samples: only its arrays move
+  template <class Q> int run(Q&& queue) { return run(nullptr, nullptr, 0, queue); }
 
  private:
   struct Copy { void* dev; void* host; size_t n; };
@@ -168,7 +175,7 @@ class HostForm {
 
   template <class Q> int staged(const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, Q& queue)
   {
-    int rc = upload_pair(c, cur_luma, ref_luma, stride_samples);
+    int rc = cur_luma ? upload_pair(c, cur_luma, ref_luma, stride_samples) : FHEVC_OK;
     if (rc != FHEVC_OK) return rc;
     for (int i = 0; i < n_in; ++i) {
       HIP_TRY(c, hipMemcpyAsync(ins[i].dev, ins[i].host, ins[i].n, hipMemcpyHostToDevice, c->stream));
@@ -188,7 +195,7 @@ class HostForm {
 
   fhevc_ctx* c;
   hipError_t e = hipSuccess;
-  Copy ins[4], outs[4];   // at most: the centres and three families in; two maps and two sets of records out
+  Copy ins[4], outs[6];   // at most: the centres and three families in; three families of records and of predictor records out
   int n_in = 0, n_out = 0;
 };
 
@@ -202,7 +209,11 @@ int open_host_form(fhevc_ctx* c, bool args_ok, int stride_samples, int qp, int r
 
 // The frame chains: all three families through a search and its refinement on the context's stream -- coarse_range 0: the wide pair; otherwise the centres
 // and the centred pair around them -- into the refined staging buffers
-struct Chain { fhevc_motion_node *nodes, *pus, *small, *centres; fhevc_motion_qpel_node *q_nodes, *q_pus, *q_small; };
+struct Chain {
+  fhevc_motion_node *nodes, *pus, *small, *centres;
+  fhevc_motion_qpel_node *q_nodes, *q_pus, *q_small;
+  fhevc_motion_qpel_node *q_nodes_out = nullptr, *q_pus_out = nullptr, *q_small_out = nullptr;   // fhevc_p_tree_amvp_frame: where the re-priced records go
+};
 Chain claim_chain(HostForm& h, bool centred)
 {
   return { h.found(kNodes), h.found(kPus), h.found(kSmall), centred ? h.found(kCentres) : nullptr, h.refined(kNodes), h.refined(kPus), h.refined(kSmall) };
@@ -529,6 +540,51 @@ int fhevc_motion_merge_pu(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* 
   return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_merge_pu_device, qp, max_range, d_refined, d_pus, d_small, c->stream); });
 }
 
+// ---- refined costs re-priced against neighbour predictors (k_motion_amvp.hip) ----
+
+int fhevc_motion_amvp_device(fhevc_ctx* c, int num_frames, int ctu_row_begin, int ctu_row_end, int qp, const fhevc_motion_qpel_node* d_nodes,
+                             const fhevc_motion_qpel_node* d_pus, const fhevc_motion_qpel_node* d_pus_small, fhevc_motion_qpel_node* d_out_nodes,
+                             fhevc_motion_qpel_node* d_out_pus, fhevc_motion_qpel_node* d_out_pus_small, fhevc_motion_mvp* d_mvp_nodes, fhevc_motion_mvp* d_mvp_pus,
+                             fhevc_motion_mvp* d_mvp_pus_small, void* stream)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!d_nodes || (!d_out_nodes && !d_out_pus && !d_out_pus_small && !d_mvp_nodes && !d_mvp_pus && !d_mvp_pus_small))
+    return fail(c, FHEVC_E_INVALID, "bad re-pricing arguments (the refined nodes and at least one output)");
+  if ((!d_pus && (d_out_pus || d_mvp_pus)) || (!d_pus_small && (d_out_pus_small || d_mvp_pus_small)))
+    return fail(c, FHEVC_E_INVALID, "bad re-pricing arguments (a family's outputs need that family's input)");
+  const uintptr_t all = (uintptr_t)d_nodes | (uintptr_t)d_pus | (uintptr_t)d_pus_small | (uintptr_t)d_out_nodes | (uintptr_t)d_out_pus | (uintptr_t)d_out_pus_small |
+                        (uintptr_t)d_mvp_nodes | (uintptr_t)d_mvp_pus | (uintptr_t)d_mvp_pus_small;
+  if (all & 3) return fail(c, FHEVC_E_INVALID, "bad re-pricing arguments (records are 4-byte aligned)");
+  // (records have no sample layout: the checks of the frames' number, the band and the qp)
+  if (const char* bad = batch_error(c, 2, c->cfg.width, 0, num_frames, 2, ctu_row_begin, ctu_row_end, qp, false)) return fail(c, FHEVC_E_INVALID, bad);
+  if ((long long)(num_frames - 1) * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "more than 2^31 - 1 CTUs");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
+  // the 67 bit costs travel with the launch: nothing of the context is read or written by it
+  const FhevcFrames fr = frames_of(c, nullptr, 2, c->cfg.width, 0, num_frames - 1, ctu_row_begin, ctu_row_end, qp);
+  return launch_on(c, stream, 25, "fhevc_launch_motion_amvp", [&](hipStream_t s) {
+    return fhevc_launch_motion_amvp(fr, fhevc_mvp_bit_cost_table(motion_lambda(qp)), kn(d_nodes), kn(d_pus), kn(d_pus_small), kn(d_out_nodes), kn(d_out_pus),
+                                    kn(d_out_pus_small), kn(d_mvp_nodes), kn(d_mvp_pus), kn(d_mvp_pus_small), c->num_cus, s);
+  });
+}
+
+int fhevc_motion_amvp(fhevc_ctx* c, int qp, const fhevc_motion_qpel_node* nodes, const fhevc_motion_qpel_node* pus, const fhevc_motion_qpel_node* pus_small,
+                      fhevc_motion_qpel_node* out_nodes, fhevc_motion_qpel_node* out_pus, fhevc_motion_qpel_node* out_pus_small, fhevc_motion_mvp* mvp_nodes,
+                      fhevc_motion_mvp* mvp_pus, fhevc_motion_mvp* mvp_pus_small)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!nodes || (!out_nodes && !out_pus && !out_pus_small && !mvp_nodes && !mvp_pus && !mvp_pus_small) || qp < 0 || qp > 51)
+    return fail(c, FHEVC_E_INVALID, "bad re-pricing arguments (the refined nodes, at least one output, qp 0..51)");
+  if ((!pus && (out_pus || mvp_pus)) || (!pus_small && (out_pus_small || mvp_pus_small)))
+    return fail(c, FHEVC_E_INVALID, "bad re-pricing arguments (a family's outputs need that family's input)");
+  HostForm h(c);
+  const size_t bn = h.bytes(kNodes), bp = h.bytes(kPus), bs = h.bytes(kSmall), all = bn + bp + bs;
+  const fhevc_motion_qpel_node *d_nodes = h.in(c->d_qpel, bn, nodes, bn), *d_pus = h.in(c->d_qpel_pu, bp, pus, bp), *d_small = h.in(c->d_qpel_pu_small, bs, pus_small, bs);
+  fhevc_motion_qpel_node *o_nodes = h.out(c->d_amvp, all, out_nodes, bn), *o_pus = h.out(c->d_amvp, all, out_pus, bp, bn), *o_small = h.out(c->d_amvp, all, out_pus_small, bs, bn + bp);
+  fhevc_motion_mvp *m_nodes = h.out(c->d_amvp_mvp, all / 2, mvp_nodes, bn / 2), *m_pus = h.out(c->d_amvp_mvp, all / 2, mvp_pus, bp / 2, bn / 2),
+                   *m_small = h.out(c->d_amvp_mvp, all / 2, mvp_pus_small, bs / 2, (bn + bp) / 2);
+  return h.run([&] { return fhevc_motion_amvp_device(c, 2, 0, c->ctus_y, qp, d_nodes, d_pus, d_small, o_nodes, o_pus, o_small, m_nodes, m_pus, m_small, c->stream); });
+}
+
 // ---- quarter-sample refinement of the PUs' vectors (k_motion_refine_pu.hip) ----
 
 int fhevc_motion_refine_pu_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
@@ -805,10 +861,10 @@ int fhevc_p_tree_select_skip_device(fhevc_ctx* c, const fhevc_pu_shape_node* d_s
 }
 
 // with_merge: fhevc_p_tree_merge_frame -- the merge stage between refinement and tree; with_merge_pu: fhevc_p_tree_merge_pu_frame -- behind it the merge stage
-// per PU, and the selection that takes its costs
+// per PU, and the selection that takes its costs; with_amvp: fhevc_p_tree_amvp_frame -- the re-pricing behind the refinements, and every later stage on its records
 static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
                            const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes,
-                           bool with_merge, fhevc_motion_merge_node* merge, bool with_merge_pu = false)
+                           bool with_merge, fhevc_motion_merge_node* merge, bool with_merge_pu = false, bool with_amvp = false)
 {
   if (!c) return FHEVC_E_INVALID;
   if (!cur_luma || !ref_luma || !depth_min || !depth_max || stride_samples < c->cfg.width) return fail(c, FHEVC_E_INVALID, "bad tree-decision frame arguments");
@@ -821,7 +877,7 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
     if (const char* bad = fhevc_p_tree_rule_error(*tree_rule)) return fail(c, FHEVC_E_INVALID, bad);
   HostForm h(c);
   const size_t map = (size_t)c->num_ctus * 256, records = h.bytes(kNodes);
-  const Chain k = claim_chain(h, coarse_range != 0);
+  Chain k = claim_chain(h, coarse_range != 0);
   uint8_t *d_min = h.out(c->d_p_maps, 3 * map, depth_min, map, map), *d_max = h.out(c->d_p_maps, 3 * map, depth_max, map, 2 * map);
   fhevc_pu_shape_node* d_shapes = h.dev<fhevc_pu_shape_node>(c->d_motion, records);
   fhevc_motion_merge_node* d_merge = h.dev<fhevc_motion_merge_node>(c->d_motion_pu, h.bytes(kPus));
@@ -832,8 +888,17 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
     d_merge_pus = h.dev<fhevc_motion_merge_node>(c->d_merge_pu, h.bytes(kPus) + h.bytes(kSmall));
     d_merge_small = h.dev<fhevc_motion_merge_node>(c->d_merge_pu, h.bytes(kPus) + h.bytes(kSmall), h.bytes(kPus));
   }
+  if (with_amvp) {
+    const size_t all = h.bytes(kNodes) + h.bytes(kPus) + h.bytes(kSmall);
+    fhevc_motion_qpel_node* const d_priced = h.dev<fhevc_motion_qpel_node>(c->d_amvp, all);
+    k.q_nodes_out = d_priced; k.q_pus_out = d_priced + (size_t)c->num_ctus * FHEVC_NODES; k.q_small_out = k.q_pus_out + (size_t)c->num_ctus * FHEVC_PUS;
+  }
   return h.run(cur_luma, ref_luma, stride_samples, [&] {
     int rc = queue_chain(c, qp, search_range, coarse_range, k);
+    if (rc == FHEVC_OK && with_amvp) {
+      rc = fhevc_motion_amvp_device(c, 2, 0, c->ctus_y, qp, k.q_nodes, k.q_pus, k.q_small, k.q_nodes_out, k.q_pus_out, k.q_small_out, nullptr, nullptr, nullptr, c->stream);
+      k.q_nodes = k.q_nodes_out; k.q_pus = k.q_pus_out; k.q_small = k.q_small_out;   // what every later stage reads
+    }
     // absolute vectors of the centred chain reach +-64 and neighbouring CTUs have different centres: the merge stages look around zero at the full range there
     const int merge_range = coarse_range ? FHEVC_MOTION_WIDE_MAX_RANGE : search_range;
     if (rc == FHEVC_OK && with_merge) rc = on_pair(c, fhevc_motion_merge_device, qp, merge_range, k.q_nodes, d_merge, c->stream);
@@ -863,6 +928,13 @@ int fhevc_p_tree_merge_pu_frame(fhevc_ctx* c, const int16_t* cur_luma, const int
                                 fhevc_motion_merge_node* merge)
 {
   return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge, true);
+}
+
+int fhevc_p_tree_amvp_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                            const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes,
+                            fhevc_motion_merge_node* merge)
+{
+  return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge, true, true);
 }
 
 }  // extern "C"

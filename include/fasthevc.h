@@ -334,7 +334,8 @@ int  fhevc_motion_refine_device(fhevc_ctx* ctx, const void* d_luma, int sample_b
  * NOT covered by this entry point: AMP of 16x16 CUs (16x4 PUs need 4x4 Hadamards) and the 8x4 and 4x8 PUs of 8x8 CUs -- those are
  * fhevc_motion_search_pu_small's, below.  NOT covered by either: search ranges above 8 -- those are fhevc_motion_search_pu_wide's, further below
  * (SAD only, up to HM's own SearchRange 64); a
- * predictor other than zero (HM's second PU sees the first PU's vector as a candidate, this source-only twin does not).
+ * predictor other than zero (HM's second PU sees the first PU's vector as a candidate, this source-only twin does not).  The SEARCH stays so; its
+ * refined costs are priced against such predictors afterwards by fhevc_motion_amvp*, further below.
  * An entry is a fhevc_motion_node.  A PU is valid iff its CU NODE lies wholly inside the picture (HM never codes a partitioned CU that crosses the
  * edge); otherwise the three distortion fields hold 0xFFFFFFFF and the vector is zero, as for nodes.  The encoder hook does not consume this
  * output yet: a rule that turns it into a shape mask has to be fitted on the reference's own decisions first. */
@@ -954,6 +955,79 @@ int  fhevc_p_tree_merge_pu_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const 
                                  uint8_t* depth_max /* numCtus * 256 */, fhevc_pu_shape_node* shapes /* numCtus * 85 or NULL */,
                                  fhevc_motion_merge_node* merge /* numCtus * 85 or NULL */);
 
+/* ---- config 4 (P slices): refined costs re-priced against neighbour predictors (k_motion_amvp.hip) ---------------------------------------------
+ * Every explicit cost above is satd + getCost(bits(q - p)) with p the zero vector (the centred chain: one coarse centre per CTU).  HM does not price an
+ * explicit vector against zero: predInterSearch calls xEstimateMvPredAMVP (TEncSearch.cpp:3028), xMotionEstimation and xPatternSearchFracDIF run under
+ * setPredictor(mvp) (:3065), and xCheckBestMVP then keeps the predictor of fewest bits (:3566-3615).  The list is TComDataCU::fillMvpCand
+ * (TComDataCU.cpp:2578-2716).  This stage re-prices the refined records on what a source-only pass has -- the refined vectors of the same-level neighbours
+ * -- and reads NO samples: the vector stays the one the chain found, only its price changes.  It writes the record type it reads, so the selection, the
+ * merge stages, the skip stage and the tree consume its output unchanged.
+ *   Inputs per CTU: the 85 refined nodes (always: neighbour vectors come from them), optionally the 124 refined PUs and the 384 refined small PUs; all
+ * fhevc_motion_qpel_node, compact over the band, as fhevc_motion_refine_pu_wide_device (or _centred_device) writes them.  Of a record satd_int, satd_best,
+ * cost_best (for the marker test only: 0xFFFFFFFF), mvx and mvy are read.  Any int16 vector is legal: there is no reach condition, nothing is read from a plane.
+ *   Entry E: a node, or a PU with getPartIndexAndSize's rectangle: (xP, yP, w, h) in picture samples, in CU node k of level l (s = 64 >> l).
+ *   Positions, the five of fillMvpCand, which are the merge stage's: L (xP - 1, yP + h - 1), A (xP + w - 1, yP - 1), AR (xP + w, yP - 1), BL (xP - 1, yP + h),
+ * AL (xP - 1, yP - 1).
+ *   Candidate at a position.  (1) The sample lies inside E's own CU -- only for part 1: L of Nx2N / nLx2N / nRx2N, A of 2NxN / 2NxnU / 2NxnD --: the
+ * candidate is part 0 of the same partition size in the same input family, its vector that PU's refined vector, available iff that record is no marker.
+ * This is where AMVP departs from merge: fillMvpCand has no second-PU exclusion, and HM has set PU 0's motion by the time it searches PU 1.  (2) Any other
+ * sample maps to the same-level node that holds it, exactly as for fhevc_motion_merge_pu*: available iff the node is on the grid and INSIDE, its CTU row lies
+ * in the band, its coding-order key is strictly smaller than that of E's own CU, and its record is no marker; its vector is that node's refined square vector.
+ *   List (single reference picture, TMVP off, as oracle/ref_rdo_harness.cpp runs the reference): a = the first available of (BL, L) (:2603-2619),
+ * b = the first available of (AR, A, AL) (:2621-2632); the list is [a] then [b]; if both exist and are equal the second is dropped (the iN == 2 pruning,
+ * :2647-2653); (0, 0) is appended until the list holds two entries (:2710-2714).  With one reference picture every inter neighbour refers to the target picture,
+ * so xAddMVPCandUnscaled finds whatever xAddMVPCandWithScaling would: the scaled left passes (:2612-2615) never run, and the scaled above passes (:2634-2645),
+ * which run only when neither BL nor L is inter, can only add the vector the unscaled above pass has added already -- which the iN == 2 pruning removes.
+ *   Choice: bits_i = eg(mvx - p_i.x) + eg(mvy - p_i.y), eg = xGetExpGolombNumberOfBits at cost scale 0 (TComRdCost.h:166-174): 2 floor(log2 t) + 1 with
+ * t = v <= 0 ? (-v << 1) + 1 : v << 1.  The index costs one bit for either index (xGetMvpIdxBits(., 2)), so it cancels and is left out, like the reference-index
+ * and mode bits of every other stage.  idx = the first i of least bits.  DEPARTURE: where the bits tie, HM keeps the index its template match
+ * (xEstimateMvPredAMVP) chose; this library takes the lower index.
+ *   Output: per entry one fhevc_motion_qpel_node: satd_int, satd_best, mvx, mvy copied; cost_best = min(satd_best + c[bits_idx], 0xFFFFFFFE), the sum in 64
+ * bits; c[b] = getCost(b) at the slice QP's motion lambda, the arithmetic of every other stage's table, in a table of its own with 67 entries (two int16
+ * differences take at most 2 * 33 bits) that travels by value.  An input marker record is copied as it is.  An entry whose CU node is not INSIDE gets the
+ * refinement's marker record (0xFFFFFFFF three times, a zero vector), whatever the input holds.
+ *   Optional second output per family, one 8-byte record per entry: */
+typedef struct {
+  int16_t  px, py;          /* the chosen predictor, quarter samples */
+  uint8_t  idx;             /* its index in the list, 0 or 1 */
+  uint8_t  num_spatial;     /* entries of the list before the zero fill (after the pruning), 0..2 */
+  uint8_t  src;             /* where it came from: 0..4 = L, A, AR, BL, AL; 5 = a filled zero */
+  uint8_t  bits;            /* bits_idx, 2..66 */
+} fhevc_motion_mvp;         /* 8 bytes; a marker entry and an entry that is not INSIDE get zeros with idx = src = 255 */
+/* Device form: num_frames - 1 picture pairs (as the motion entry points count them: num_frames >= 2), the band, qp 0..51; d_nodes never NULL; d_pus /
+ * d_pus_small may be NULL; a family's outputs (d_out_*, d_mvp_*) need that family's input; at least one of the six outputs must be non-NULL.  All arrays
+ * compact over the band: (num_frames - 1) * band CTUs * 85 / 124 / 384 entries, outputs written over exactly that extent; an empty band writes nothing.
+ * Every array may sit on any 4-byte alignment (16-byte accesses where all are 16-byte -- the predictor records 8-byte -- aligned, dwords otherwise); input
+ * and output arrays must not overlap.  One launch for all 593 entries of every CTU: a workgroup per CTU, the 123 nodes that can be a neighbour parked in LDS
+ * once per CTU, part 0 of a PU read from the lane before.  Asynchronous, allocates nothing, keeps NO state in HBM (the bit costs travel by value): calls with
+ * different QPs may be in flight on two streams, and refinement, this stage and the merge stages may follow each other on one stream without a host
+ * synchronisation.  FHEVC_E_INVALID with a fhevc_last_error text (nothing launched, nothing written): a null context (no text), a null d_nodes, no output, an
+ * output without its input, a pointer that is not 4-byte aligned, num_frames < 2, a bad band, qp outside 0..51.  Timed under slot 25 of fhevc_kernel_timing.
+ * NOT covered: a search or refinement that moves its window to the predictor or picks its winner under it, the temporal candidate, predictors from
+ * finer-level neighbours.  Table entries 39..66 rest on the formula alone: the reference's recorded costs reach 38 bits.  The encoder hook does not
+ * consume this output. */
+int  fhevc_motion_amvp_device(fhevc_ctx* ctx, int num_frames, int ctu_row_begin, int ctu_row_end, int qp, const fhevc_motion_qpel_node* d_nodes,
+                              const fhevc_motion_qpel_node* d_pus, const fhevc_motion_qpel_node* d_pus_small, fhevc_motion_qpel_node* d_out_nodes,
+                              fhevc_motion_qpel_node* d_out_pus, fhevc_motion_qpel_node* d_out_pus_small, fhevc_motion_mvp* d_mvp_nodes,
+                              fhevc_motion_mvp* d_mvp_pus, fhevc_motion_mvp* d_mvp_pus_small, void* stream);
+/* one picture, host arrays over the whole picture (numCtus * 85 / 124 / 384), synchronous; NULL rules as the device form */
+int  fhevc_motion_amvp(fhevc_ctx* ctx, int qp, const fhevc_motion_qpel_node* nodes, const fhevc_motion_qpel_node* pus, const fhevc_motion_qpel_node* pus_small,
+                       fhevc_motion_qpel_node* out_nodes, fhevc_motion_qpel_node* out_pus, fhevc_motion_qpel_node* out_pus_small, fhevc_motion_mvp* mvp_nodes,
+                       fhevc_motion_mvp* mvp_pus, fhevc_motion_mvp* mvp_pus_small);
+/* The host twin: the same definition in plain C++ for one picture of width x height and the band [ctu_row_begin, ctu_row_end); arrays compact over the
+ * band.  Needs no context and no device.  bit_depth 8..12 (the motion lambda does not depend on it).  FHEVC_E_INVALID (nothing written): what the device
+ * form rejects, width or height below 8. */
+int  fhevc_motion_amvp_picture(int width, int height, int bit_depth, int ctu_row_begin, int ctu_row_end, int qp, const fhevc_motion_qpel_node* nodes,
+                               const fhevc_motion_qpel_node* pus, const fhevc_motion_qpel_node* pus_small, fhevc_motion_qpel_node* out_nodes,
+                               fhevc_motion_qpel_node* out_pus, fhevc_motion_qpel_node* out_pus_small, fhevc_motion_mvp* mvp_nodes, fhevc_motion_mvp* mvp_pus,
+                               fhevc_motion_mvp* mvp_pus_small);
+/* fhevc_p_tree_merge_pu_frame with this stage between the refinements and the merge stages: the same arguments, checks and both chains; the merge stages,
+ * the selection and the tree then read the re-priced records.  On the centred chain the stage replaces the per-CTU-centre pricing. */
+int  fhevc_p_tree_amvp_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                             const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min /* numCtus * 256 */,
+                             uint8_t* depth_max /* numCtus * 256 */, fhevc_pu_shape_node* shapes /* numCtus * 85 or NULL */,
+                             fhevc_motion_merge_node* merge /* numCtus * 85 or NULL */);
+
 /* ---- config 4 (P slices): the zero-residual (skip) test per CU node (k_motion_skip.hip) -----------------------------------------------------------
  * In HM a CU whose best mode is merge with an all-zero residual is a skip: TEncCu.cpp:892 (EarlyCU) does not descend below it, and :610-637 with
  * :1444-1468 (EarlySkipDetection) do not try its other partition sizes.  Whether a residual quantises to zero is an exact integer question: HM's forward
@@ -1030,7 +1104,8 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
  * -- except 17 = the P-picture tree decision (fhevc_p_tree_select_device, fhevc_p_tree_select_merge_device), added later.  16 is not a slot either: it stays rejected
  * -- and 19 = the merge-candidate costs (fhevc_motion_merge*), added later still.  18 is not a slot: it stays rejected -- and 21 = the merge-candidate
  * costs per PU (fhevc_motion_merge_pu*).  20 is not a slot: it stays rejected -- and 23 = the zero-residual test (fhevc_motion_skip*).  22 is not a slot: it stays
- * rejected, as does any number above 23.  The tree that stops at a skip (fhevc_p_tree_select_skip_device) is timed under 17 */
+ * rejected -- and 25 = the re-pricing against neighbour predictors (fhevc_motion_amvp*).  24 is not a slot: it stays rejected, as does any number above 25.
+ * The tree that stops at a skip (fhevc_p_tree_select_skip_device) is timed under 17 */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
 int  fhevc_enable_kernel_timing(fhevc_ctx* ctx, int on);
 
