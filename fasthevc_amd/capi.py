@@ -45,6 +45,7 @@ SYMBOLS = [
     "fhevc_motion_merge_pu", "fhevc_motion_merge_pu_device", "fhevc_pu_shape_select_merge", "fhevc_pu_shape_select_merge_device", "fhevc_p_tree_merge_pu_frame",
     "fhevc_motion_skip", "fhevc_motion_skip_device", "fhevc_p_tree_select_skip", "fhevc_p_tree_select_skip_device",
     "fhevc_motion_amvp", "fhevc_motion_amvp_device", "fhevc_motion_amvp_picture", "fhevc_p_tree_amvp_frame",
+    "fhevc_intra_p", "fhevc_intra_p_device", "fhevc_intra_p_picture", "fhevc_p_tree_select_intra", "fhevc_p_tree_select_intra_device", "fhevc_p_tree_intra_frame",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -107,6 +108,9 @@ MVP_BIT_COSTS = 67
 MERGE_L, MERGE_A, MERGE_AR, MERGE_BL, MERGE_AL, MERGE_ZERO = 0, 1, 2, 3, 4, 5
 # fhevc_p_tree_node: one record per CU node (flags: 1 split_sure, 2 stop_sure, 4 CROSSING, 8 ABSENT, 16 own available, 32 kids available)
 TREE_DTYPE = np.dtype([("cost_own", np.uint32), ("cost_kids", np.uint32), ("cost_tree", np.uint32), ("flags", np.uint8), ("level", np.uint8), ("pad", np.uint8, (2,))])
+# fhevc_intra_p_node: the intra candidate of a CU node of a P picture (part 0: 2Nx2N, modes = the mode four times; part 1: NxN, the modes of the four PUs)
+INTRA_P_DTYPE = np.dtype([("satd_best", np.uint32), ("cost_best", np.uint32), ("modes", np.uint8, (4,)), ("part", np.uint8), ("pad", np.uint8, (3,))])
+TREE_INTRA = 1  # bit 0 of pad[0] (byte 14) of a tree record of fhevc_p_tree_select_intra*: own is the intra cost
 
 
 def motion_pu_index(node, shape, part):
@@ -259,6 +263,12 @@ def load_library(path=None):
     lib.fhevc_motion_amvp_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.fhevc_motion_amvp_picture.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.fhevc_p_tree_amvp_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), vp, vp, vp, vp]
+    lib.fhevc_intra_p.argtypes = [vp, C.c_int, vp, vp, vp]
+    lib.fhevc_intra_p_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.fhevc_intra_p_picture.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.fhevc_p_tree_select_intra.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp]
+    lib.fhevc_p_tree_select_intra_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp, vp]
+    lib.fhevc_p_tree_intra_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), C.c_int, vp, vp, vp, vp, vp]
     lib.fhevc_predict_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, vp, vp]
     lib.fhevc_alloc_host.argtypes = [vp, C.c_size_t]
     lib.fhevc_alloc_host.restype = vp
@@ -390,6 +400,42 @@ def p_tree_select_skip(shapes, merge, skip, skip_mask, width, height, rule=None,
         if rc != OK:
             raise FastHevcError(rc, "fhevc_p_tree_select_skip")
     return (dmin, dmax, tree) if with_tree else (dmin, dmax)
+
+
+def p_tree_select_intra(shapes, merge, skip, skip_mask, intra, width, height, rule=None, with_tree=False):
+    """p_tree_select_skip with the intra records [numCtus, 85] INTRA_P_DTYPE: a node that is not calm (merged with a masked zero bit) takes its intra cost
+    where that is strictly smaller; bit TREE_INTRA of pad[0] of its tree record says so"""
+    lib = load_library()
+    rule = rule if rule is not None else p_tree_rule_default()
+    shapes, merge, skip, intra = (np.ascontiguousarray(a) for a in (shapes, merge, skip, intra))
+    assert all(a.dtype.itemsize == 16 and a.shape == shapes.shape for a in (shapes, merge, skip, intra))
+    cw = (width + 63) // 64
+    n = shapes.shape[0]
+    dmin, dmax = np.zeros((n, 256), np.uint8), np.zeros((n, 256), np.uint8)
+    tree = np.zeros((n, NODES_PER_CTU), TREE_DTYPE) if with_tree else None
+    for c in range(n):
+        vw, vh = min(64, width - (c % cw) * 64), min(64, height - (c // cw) * 64)
+        rc = lib.fhevc_p_tree_select_intra(shapes[c].ctypes.data, merge[c].ctypes.data, skip[c].ctypes.data, skip_mask, intra[c].ctypes.data, vw, vh, C.byref(rule),
+                                           dmin[c].ctypes.data, dmax[c].ctypes.data, tree[c].ctypes.data if with_tree else None)
+        if rc != OK:
+            raise FastHevcError(rc, "fhevc_p_tree_select_intra")
+    return (dmin, dmax, tree) if with_tree else (dmin, dmax)
+
+
+def intra_p_picture(first, first4, width, height, qp=32, rows=None):
+    """config 4, host side (no context, no device): the intra candidate costs of one picture's band from its first-pass records: first [band CTUs, 85],
+    first4 [band CTUs, 256] or None (NODE_DTYPE; only satd and mode are read) -> [band CTUs, 85] INTRA_P_DTYPE"""
+    lib = load_library()
+    first = np.ascontiguousarray(first)
+    first4 = None if first4 is None else np.ascontiguousarray(first4)
+    rb, re = rows if rows is not None else (0, (height + 63) // 64)
+    n = (re - rb) * ((width + 63) // 64)
+    assert first.size == n * NODES_PER_CTU and first.dtype.itemsize == 16 and (first4 is None or (first4.size == n * PUS4_PER_CTU and first4.dtype.itemsize == 16))
+    out = np.zeros((n, NODES_PER_CTU), INTRA_P_DTYPE)
+    rc = lib.fhevc_intra_p_picture(width, height, rb, re, qp, first.ctypes.data, first4.ctypes.data if first4 is not None else None, out.ctypes.data)
+    if rc != OK:
+        raise FastHevcError(rc, "fhevc_intra_p_picture")
+    return out
 
 
 def pu_shape_select(nodes, pus, pus_small, width, height, rule=None, with_costs=False):
@@ -971,6 +1017,48 @@ class Context:
         rb, re = rows if rows is not None else (0, self.ctus_y)
         self._check(self.lib.fhevc_p_tree_select_skip_device(self.h, d_shapes, d_merge, d_skip, skip_mask, num_pictures, rb, re,
                                                              C.byref(rule) if rule is not None else None, d_depth_min, d_depth_max, d_tree, stream))
+
+    def p_tree_select_intra_device(self, d_shapes, d_merge, d_skip, skip_mask, d_intra, num_pictures, d_depth_min=None, d_depth_max=None, d_tree=None, rows=None,
+                                   stream=None, rule=None):
+        """p_tree_select_skip_device with the intra records of intra_p_device (85 per CTU, compact over the same rows): a node that is not calm takes its
+        intra cost where that is strictly smaller.  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_p_tree_select_intra_device(self.h, d_shapes, d_merge, d_skip, skip_mask, d_intra, num_pictures, rb, re,
+                                                              C.byref(rule) if rule is not None else None, d_depth_min, d_depth_max, d_tree, stream))
+
+    def intra_p_device(self, num_pictures, d_first, d_first4, d_out, rows=None, stream=None, qp=32):
+        """config 4 on the device: the intra candidate costs of num_pictures P pictures from the records of intra_first_pass_device (85 per CTU) and, unless
+        None, of intra_first_pass_4x4_device (256 per CTU); d_out: num_pictures * band CTUs * 85 records (16 B).  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_intra_p_device(self.h, num_pictures, rb, re, qp, d_first, d_first4, d_out, stream))
+
+    def intra_p(self, first, first4=None, qp=32):
+        """one picture, host arrays: first [numCtus, 85], first4 [numCtus, 256] or None (NODE_DTYPE) -> [numCtus, 85] INTRA_P_DTYPE"""
+        first = np.ascontiguousarray(first)
+        first4 = None if first4 is None else np.ascontiguousarray(first4)
+        assert first.size == self.num_ctus * NODES_PER_CTU and first.dtype.itemsize == 16
+        assert first4 is None or (first4.size == self.num_ctus * PUS4_PER_CTU and first4.dtype.itemsize == 16)
+        out = np.zeros(self.num_ctus * NODES_PER_CTU, INTRA_P_DTYPE)
+        self._check(self.lib.fhevc_intra_p(self.h, qp, first.ctypes.data, first4.ctypes.data if first4 is not None else None, out.ctypes.data))
+        return out.reshape(self.num_ctus, NODES_PER_CTU)
+
+    def p_tree_intra_frame(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=8, coarse_range=0, shape_rule=None, tree_rule=None, skip_mask=3,
+                           with_shapes=False, with_merge=False, with_intra=False):
+        """p_tree_amvp_frame with the zero-residual stage, the two intra first passes of the current picture and the intra stage behind the selection, and the
+        tree that takes them -> (depth_min, depth_max) [numCtus, 256], then the records asked for: SHAPE_DTYPE, MOTION_MERGE_DTYPE, INTRA_P_DTYPE [numCtus, 85]"""
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
+        dmin, dmax = np.zeros(self.num_ctus * 256, np.uint8), np.zeros(self.num_ctus * 256, np.uint8)
+        shapes = np.zeros(self.num_ctus * NODES_PER_CTU, SHAPE_DTYPE) if with_shapes else None
+        merge = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_MERGE_DTYPE) if with_merge else None
+        intra = np.zeros(self.num_ctus * NODES_PER_CTU, INTRA_P_DTYPE) if with_intra else None
+        self._check(self.lib.fhevc_p_tree_intra_frame(self.h, cur, ref, stride, qp, search_range, coarse_range, C.byref(shape_rule) if shape_rule is not None else None,
+                                                      C.byref(tree_rule) if tree_rule is not None else None, skip_mask, dmin.ctypes.data, dmax.ctypes.data,
+                                                      shapes.ctypes.data if with_shapes else None, merge.ctypes.data if with_merge else None,
+                                                      intra.ctypes.data if with_intra else None))
+        out = (dmin.reshape(self.num_ctus, 256), dmax.reshape(self.num_ctus, 256))
+        for a in (shapes, merge, intra):
+            out += (a.reshape(self.num_ctus, NODES_PER_CTU),) if a is not None else ()
+        return out
 
     def p_tree_merge_pu_frame(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=8, coarse_range=0, shape_rule=None, tree_rule=None,
                               with_shapes=False, with_merge=False):

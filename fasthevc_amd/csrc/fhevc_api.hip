@@ -161,7 +161,7 @@ void fhevc_destroy(fhevc_ctx* c)
   void* const bufs[] = { c->d_frag, c->d_bias, c->d_whead, c->d_bhead, c->d_frag_i8, c->d_bias_i8,                                  // the base image
                          c->f_frag1, c->f_bias1, c->f_frag2, c->f_frag3, c->f_bias_i8, c->f_whead, c->f_headm, c->f_bhead,          // a fused family member's
                          c->d_luma, c->d_depth, c->d_had, c->d_nodes, c->d_satd, c->d_satd_out, c->d_act, c->d_depth_max, c->d_pair, c->d_motion, c->d_qpel, c->d_motion_pu, c->d_motion_pu_small, c->d_centres, c->d_qpel_pu, c->d_qpel_pu_small, c->d_merge_pu, c->d_amvp, c->d_amvp_mvp,
-                         c->d_p_maps, c->d_mvtab, c->d_cand_all, c->d_cand, c->d_best4, c->d_modes4 };
+                         c->d_p_maps, c->d_first_p, c->d_intra_p, c->d_mvtab, c->d_cand_all, c->d_cand, c->d_best4, c->d_modes4 };
   for (void* q : bufs) (void)hipFree(q);
   for (void* q : c->lw_bufs) (void)hipFree(q);
   for (auto& sl : c->slot) {  // the host-batch ring of fhevc_predict_frames: stream, device buffers, pinned staging
@@ -185,9 +185,9 @@ int fhevc_enable_kernel_timing(fhevc_ctx* c, int on)
 
 int fhevc_kernel_timing(fhevc_ctx* c, int which, int reset, double* avg_ms, uint64_t* launches)
 {
-  // 14, 16, 18, 20, 22 and 24 stay rejected: callers probe them as the first numbers behind the slots of the partition-size selection, of the centred chain, of
-  // the tree, of the two merge stages and of the zero-residual test
-  if (!c || which < 0 || which > 25 || which == 14 || which == 16 || which == 18 || which == 20 || which == 22 || which == 24) return FHEVC_E_INVALID;
+  // 14, 16, 18, 20, 22, 24 and 26 stay rejected: callers probe them as the first numbers behind the slots of the partition-size selection, of the centred chain,
+  // of the tree, of the two merge stages, of the zero-residual test and of the re-pricing
+  if (!c || which < 0 || which > 27 || which == 14 || which == 16 || which == 18 || which == 20 || which == 22 || which == 24 || which == 26) return FHEVC_E_INVALID;
   time_resolve(c);
   if (avg_ms) *avg_ms = c->launches[which] ? c->sum_ms[which] / (double)c->launches[which] : 0.0;
   if (launches) *launches = c->launches[which];

@@ -51,9 +51,9 @@ struct fhevc_ctx {
   bool timing = false;
   std::vector<TimedLaunch> pending;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-  // per timing slot (14, 16, 18, 20, 22 and 24 are not in use); config 4's slots and its staging buffers d_pair .. d_p_maps: the tables in fhevc_motion_api.hip
-  double sum_ms[26] = {};
-  uint64_t launches[26] = {};
+  // per timing slot (14, 16, 18, 20, 22, 24 and 26 are not in use); config 4's slots and its staging buffers d_pair .. d_intra_p: the tables in fhevc_motion_api.hip
+  double sum_ms[28] = {};
+  uint64_t launches[28] = {};
   double* d_act = nullptr;
   int16_t* d_pair = nullptr;
   FhevcMotionNode *d_motion = nullptr, *d_motion_pu = nullptr, *d_motion_pu_small = nullptr, *d_centres = nullptr;
@@ -62,6 +62,8 @@ struct fhevc_ctx {
   FhevcMotionQpelNode* d_amvp = nullptr;     // the 593 re-priced entries per CTU of fhevc_motion_amvp and of fhevc_p_tree_amvp_frame
   FhevcMotionMvp* d_amvp_mvp = nullptr;      // ... and their predictor records
   uint8_t* d_p_maps = nullptr;
+  FhevcNodeCost* d_first_p = nullptr;        // the 85 + 256 first-pass records per CTU of fhevc_intra_p and of fhevc_p_tree_intra_frame
+  FhevcIntraPNode* d_intra_p = nullptr;      // ... and their 85 intra records
   FhevcNodeCost* d_cand_all = nullptr; uint8_t* d_cand = nullptr;   // fhevc_intra_first_pass_candidates: every (node, mode) cost, the lists
   FhevcNodeCost* d_best4 = nullptr; uint8_t* d_modes4 = nullptr;    // fhevc_intra_first_pass_4x4: the best mode and the list of every 4x4 PU
   uint32_t* d_mvtab = nullptr;        // vector costs of the wide search (k_motion_wide.hip), rebuilt when (qp, range) changes

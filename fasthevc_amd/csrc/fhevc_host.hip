@@ -352,9 +352,11 @@ void fhevc_p_tree_rule_default(fhevc_p_tree_rule* rule)
 }  // extern "C"
 
 // merge: null for fhevc_p_tree_select; otherwise the CTU's 85 merge records, of which cost_best is read
-// skip: null but for fhevc_p_tree_select_skip; otherwise the CTU's 85 skip records, of which flags is read under skip_mask (HM's EarlyCU, TEncCu.cpp:892)
+// skip: null but for fhevc_p_tree_select_skip and _intra; otherwise the CTU's 85 skip records, of which flags is read under skip_mask (HM's EarlyCU, TEncCu.cpp:892)
+// intra: null but for fhevc_p_tree_select_intra; otherwise the CTU's 85 intra records, of which cost_best is read (HM's intra check, TEncCu.cpp:797-816)
 static int p_tree_select(const fhevc_pu_shape_node* shapes, const fhevc_motion_merge_node* merge, int valid_w, int valid_h, const fhevc_p_tree_rule* rule, uint8_t* depth_min,
-                         uint8_t* depth_max, fhevc_p_tree_node* tree, const fhevc_motion_skip_node* skip = nullptr, int skip_mask = 0)
+                         uint8_t* depth_max, fhevc_p_tree_node* tree, const fhevc_motion_skip_node* skip = nullptr, int skip_mask = 0,
+                         const fhevc_intra_p_node* intra = nullptr)
 {
   if (!shapes || !rule || (!depth_min && !depth_max && !tree) || valid_w < 8 || valid_w > 64 || valid_h < 8 || valid_h > 64 || fhevc_p_tree_rule_error(*rule))
     return FHEVC_E_INVALID;
@@ -375,6 +377,9 @@ static int p_tree_select(const fhevc_pu_shape_node* shapes, const fhevc_motion_m
     // the merge cost is taken where it is strictly smaller: the marker is the largest value, so an unavailable one never is, and any cost beats a marker
     const bool merged = inside && merge && merge[k].cost_best < n.cost_own;
     if (merged) n.cost_own = merge[k].cost_best;
+    // a calm node (merged, with a masked zero bit) is HM's "best mode has no coded residual": intra is not tried there; elsewhere it wins where strictly cheaper
+    const bool calm = merged && skip && (skip[k].flags & skip_mask) != 0;
+    if (inside && intra && !calm && intra[k].cost_best < n.cost_own) { n.cost_own = intra[k].cost_best; n.pad[0] = 1; }
     if (lvl == 3) { n.cost_tree = n.cost_own; n.flags = (uint8_t)((n.cost_own != mark ? 16 : 0) | (merged ? 64 : 0)); continue; }
     uint64_t sum = inside ? (uint64_t)rule->split_cost[lvl] : 0;
     bool marked = false;
@@ -396,7 +401,7 @@ static int p_tree_select(const fhevc_pu_shape_node* shapes, const fhevc_motion_m
       stop = own + (uint64_t)rule->stop_abs[lvl] + ((own * (uint64_t)rule->stop_q8[lvl]) >> 8) <= kids;
     }
     // a merged node with an all-zero residual is a skip: its children are never visited, whatever they would cost
-    const bool early = merged && skip && (skip[k].flags & skip_mask) != 0;
+    const bool early = calm;
     if (early) { n.cost_tree = n.cost_own; split = false; stop = true; }
     n.flags = (uint8_t)((split ? 1 : 0) | (stop ? 2 : 0) | (!inside ? 4 : 0) | (own != mark ? 16 : 0) | (kids != mark ? 32 : 0) | (merged ? 64 : 0) | (early ? 128 : 0));
     sure[k] = !inside || split;
@@ -443,6 +448,74 @@ int fhevc_p_tree_select_skip(const fhevc_pu_shape_node* shapes, const fhevc_moti
 {
   if (!merge || !skip || skip_mask < 0 || skip_mask > 3) return FHEVC_E_INVALID;
   return p_tree_select(shapes, merge, valid_w, valid_h, rule, depth_min, depth_max, tree, skip, skip_mask);
+}
+
+int fhevc_p_tree_select_intra(const fhevc_pu_shape_node* shapes, const fhevc_motion_merge_node* merge, const fhevc_motion_skip_node* skip, int skip_mask,
+                              const fhevc_intra_p_node* intra, int valid_w, int valid_h, const fhevc_p_tree_rule* rule, uint8_t* depth_min, uint8_t* depth_max,
+                              fhevc_p_tree_node* tree)
+{
+  if (!merge || !skip || !intra || skip_mask < 0 || skip_mask > 3) return FHEVC_E_INVALID;
+  return p_tree_select(shapes, merge, valid_w, valid_h, rule, depth_min, depth_max, tree, skip, skip_mask, intra);
+}
+
+// ---- intra candidate costs per CU node for P pictures (spec in include/fasthevc.h; the device form is k_intra_p.hip) ----
+
+int fhevc_intra_p_picture(int width, int height, int ctu_row_begin, int ctu_row_end, int qp, const fhevc_node_cost* first, const fhevc_node_cost* first4,
+                          fhevc_intra_p_node* out)
+{
+  if (width < 8 || height < 8 || qp < 0 || qp > 51 || !first || !out) return FHEVC_E_INVALID;
+  const int cw = (width + 63) / 64, ch = (height + 63) / 64;
+  if (ctu_row_begin < 0 || ctu_row_end > ch || ctu_row_begin > ctu_row_end) return FHEVC_E_INVALID;
+  if ((((uintptr_t)first | (uintptr_t)first4 | (uintptr_t)out) & 3) != 0) return FHEVC_E_INVALID;
+  const uint32_t mark = 0xFFFFFFFFu, sat = 0xFFFFFFFEu;
+  const FhevcIntraBitCost cost = fhevc_intra_bit_cost(65536.0 * sqrt_lambda_intra(qp));
+  // satd and mode of record `index` as two dwords, addressed in bytes: the arrays may sit on any 4-byte alignment (a fhevc_node_cost wants 8), and the double
+  // is never read
+  auto dwords = [](const fhevc_node_cost* records, size_t index, uint32_t* satd, uint32_t* mode) {
+    uint32_t v[2];
+    std::memcpy(v, reinterpret_cast<const unsigned char*>(records) + 16 * index, sizeof v);
+    *satd = v[0]; *mode = v[1] & 255u;
+  };
+  auto put = [](fhevc_intra_p_node* dst, uint32_t satd, uint32_t price, const uint32_t* modes, int part) {
+    const uint8_t rec[16] = { (uint8_t)satd, (uint8_t)(satd >> 8), (uint8_t)(satd >> 16), (uint8_t)(satd >> 24), (uint8_t)price, (uint8_t)(price >> 8), (uint8_t)(price >> 16),
+                              (uint8_t)(price >> 24), (uint8_t)modes[0], (uint8_t)modes[1], (uint8_t)modes[2], (uint8_t)modes[3], (uint8_t)part, 0, 0, 0 };
+    std::memcpy(dst, rec, sizeof rec);
+  };
+  const uint32_t no_modes[4] = { 255, 255, 255, 255 };
+  for (int i = 0; i < (ctu_row_end - ctu_row_begin) * cw; ++i) {
+    const int ctu = ctu_row_begin * cw + i;
+    const int valid_w = std::min(64, width - (ctu % cw) * 64), valid_h = std::min(64, height - (ctu / cw) * 64);
+    for (int k = 0; k < FHEVC_NODES; ++k) {
+      const int lvl = k < 1 ? 0 : (k < 5 ? 1 : (k < 21 ? 2 : 3));
+      const int size = 64 >> lvl, idx = k - kLevel[lvl].first, nx = idx % kLevel[lvl].per_row, ny = idx / kLevel[lvl].per_row;
+      const bool inside = nx * size + size <= valid_w && ny * size + size <= valid_h;
+      fhevc_intra_p_node* dst = out + (size_t)i * FHEVC_NODES + k;
+      uint32_t satd, mode;
+      dwords(first, (size_t)i * FHEVC_NODES + k, &satd, &mode);
+      bool have = inside && satd != mark;
+      uint32_t price = fhevc_intra_p_price(satd, mode, cost), modes[4] = { mode, mode, mode, mode };
+      int part = 0;
+      if (lvl == 3 && first4 && inside) {
+        uint64_t sum_price = 0, sum_satd = 0;
+        uint32_t m4[4];
+        bool have4 = true;
+        for (int j = 0; j < 4; ++j) {
+          uint32_t s4;
+          dwords(first4, (size_t)i * FHEVC_PUS4_PER_CTU + (2 * ny + (j >> 1)) * 16 + 2 * nx + (j & 1), &s4, &m4[j]);
+          have4 = have4 && s4 != mark;
+          sum_price += fhevc_intra_p_price(s4, m4[j], cost); sum_satd += s4;
+        }
+        const uint32_t price4 = (uint32_t)std::min<uint64_t>(sum_price, sat);
+        if (have4 && (!have || price4 < price)) {   // strict "<": HM tries 2Nx2N first, and xCheckBestMode keeps the earlier mode on a tie
+          have = true; part = 1; price = price4; satd = (uint32_t)std::min<uint64_t>(sum_satd, sat);
+          std::memcpy(modes, m4, sizeof modes);
+        }
+      }
+      if (have) put(dst, satd, price, modes, part);
+      else put(dst, mark, mark, no_modes, 0);
+    }
+  }
+  return FHEVC_OK;
 }
 
 }  // extern "C"

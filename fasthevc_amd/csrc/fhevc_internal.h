@@ -413,6 +413,33 @@ hipError_t fhevc_launch_p_tree_skip(const FhevcFrames& fr, const FhevcPTreeRule&
                                     const FhevcMotionSkipNode* d_skip, int skip_mask, uint8_t* d_depth_min, uint8_t* d_depth_max, FhevcPTreeNode* d_tree, int num_cus,
                                     hipStream_t stream);
 
+// ---- intra candidate costs per CU node for P pictures, from the first passes' records (k_intra_p.hip; config 4) ------------------------------------
+struct FhevcIntraPNode { uint32_t satd_best, cost_best; uint8_t modes[4]; uint8_t part; uint8_t pad[3]; };
+static_assert(sizeof(FhevcIntraPNode) == 16, "intra record: 16 bytes without padding");
+// getCost(b) of the first pass's three mode-bit counts (k_firstpass.hip: 2 for planar, 3 for DC and vertical, 6 otherwise) at the slice QP's motion lambda,
+// computed on the host with the arithmetic of mv_bits_cost; travels by value
+struct FhevcIntraBitCost { uint32_t c2, c3, c6; };
+inline FhevcIntraBitCost fhevc_intra_bit_cost(double motion_lambda)
+{
+  return { (uint32_t)((motion_lambda * 2u) / 65536.0), (uint32_t)((motion_lambda * 3u) / 65536.0), (uint32_t)((motion_lambda * 6u) / 65536.0) };
+}
+// The price of a first-pass record, shared by the kernel and the host twin: mode = the low byte of the record's mode dword; the caller has tested
+// satd != 0xFFFFFFFF.  64-bit sum, saturated at 0xFFFFFFFE
+__host__ __device__ inline uint32_t fhevc_intra_p_price(uint32_t satd, uint32_t mode, const FhevcIntraBitCost& c)
+{
+  const uint64_t p = (uint64_t)satd + (mode == 0u ? c.c2 : (mode == 1u || mode == 26u ? c.c3 : c.c6));
+  return p > 0xFFFFFFFEull ? 0xFFFFFFFEu : (uint32_t)p;
+}
+// fr: geometry, band, num_frames = the P pictures of the batch (luma is not read).  d_first: num_frames * band CTUs * 85 first-pass records as dwords (4 per
+// record; dwords 0 and 1 are read); d_first4 (may be null: no NxN candidate): ... * 256 records alike; d_out: ... * 85 records; all compact over the band
+hipError_t fhevc_launch_intra_p(const FhevcFrames& fr, const FhevcIntraBitCost& cost, const uint32_t* d_first, const uint32_t* d_first4, FhevcIntraPNode* d_out,
+                                int num_cus, hipStream_t stream);
+// ... and the tree that takes them (k_p_tree.hip): fhevc_launch_p_tree_skip with the intra records (never null; only cost_best, dword 1, is read).  A node that
+// is not calm (merged with a masked zero bit) and whose intra cost is strictly below its inter cost takes the intra cost as its own: bit 0 of byte 14
+hipError_t fhevc_launch_p_tree_intra(const FhevcFrames& fr, const FhevcPTreeRule& rule, const FhevcPuShapeNode* d_shapes, const FhevcMotionMergeNode* d_merge,
+                                     const FhevcMotionSkipNode* d_skip, int skip_mask, const FhevcIntraPNode* d_intra, uint8_t* d_depth_min, uint8_t* d_depth_max,
+                                     FhevcPTreeNode* d_tree, int num_cus, hipStream_t stream);
+
 // ---- adaptive-QP pre-analysis (k_preanalyze.hip) -----------------------------------------------------------
 // d_activity: per frame parts_per_frame doubles, layers concatenated (layer d: ceil(H/P) x ceil(W/P), P = 64 >> d)
 hipError_t fhevc_launch_preanalyze(const FhevcFrames& fr, int layers, long long parts_per_frame, double* d_activity,

@@ -49,12 +49,17 @@ template <> struct Kernel<fhevc_motion_skip_node> { using T = FhevcMotionSkipNod
 template <> struct Kernel<fhevc_pu_shape_node> { using T = FhevcPuShapeNode; };
 template <> struct Kernel<fhevc_p_tree_node> { using T = FhevcPTreeNode; };
 template <> struct Kernel<fhevc_motion_mvp> { using T = FhevcMotionMvp; };
+template <> struct Kernel<fhevc_intra_p_node> { using T = FhevcIntraPNode; };
 template <class P> typename Kernel<P>::T* kn(P* p) { return reinterpret_cast<typename Kernel<P>::T*>(p); }
 template <class P> const typename Kernel<P>::T* kn(const P* p) { return reinterpret_cast<const typename Kernel<P>::T*>(p); }
 static_assert(sizeof(fhevc_motion_node) == 16 && sizeof(FhevcMotionNode) == 16 && sizeof(fhevc_motion_qpel_node) == 16 && sizeof(FhevcMotionQpelNode) == 16, "node layouts");
 static_assert(sizeof(fhevc_motion_merge_node) == 16 && sizeof(FhevcMotionMergeNode) == 16 && sizeof(fhevc_pu_shape_node) == 16 && sizeof(FhevcPuShapeNode) == 16, "record layouts");
 static_assert(sizeof(fhevc_motion_skip_node) == 16 && offsetof(fhevc_motion_skip_node, nonzero) == 8 && offsetof(fhevc_motion_skip_node, flags) == 10 &&
               offsetof(fhevc_motion_skip_node, mvx) == 12 && offsetof(FhevcMotionSkipNode, flags) == 10 && offsetof(FhevcMotionSkipNode, mvx) == 12, "skip record layout");
+static_assert(sizeof(fhevc_intra_p_node) == 16 && offsetof(fhevc_intra_p_node, satd_best) == 0 && offsetof(fhevc_intra_p_node, cost_best) == 4 &&
+              offsetof(fhevc_intra_p_node, modes) == 8 && offsetof(fhevc_intra_p_node, part) == 12 && offsetof(fhevc_intra_p_node, pad) == 13 &&
+              sizeof(FhevcIntraPNode) == 16 && offsetof(FhevcIntraPNode, cost_best) == 4 && offsetof(FhevcIntraPNode, part) == 12, "intra record layout");
+static_assert(sizeof(fhevc_node_cost) == 16 && offsetof(fhevc_node_cost, satd) == 0 && offsetof(fhevc_node_cost, mode) == 4, "first-pass record layout");
 static_assert(FHEVC_PUS_PER_CTU == FHEVC_PUS && FHEVC_PUS_SMALL_PER_CTU == FHEVC_PUS_SMALL, "PU counts");
 static_assert(sizeof(fhevc_motion_mvp) == 8 && offsetof(fhevc_motion_mvp, idx) == 4 && offsetof(fhevc_motion_mvp, bits) == 7 && offsetof(FhevcMotionMvp, bits) == 7,
               "predictor record layout");
@@ -111,10 +116,13 @@ int device_form(fhevc_ctx* c, bool args_ok, const char* bad_args, const Batch& b
 //   d_amvp, d_amvp_mvp       593 (everything)  the re-priced entries and their predictor records (8 bytes each): the 85, behind them the 124, behind them the
 //                                              384 (fhevc_motion_amvp, fhevc_p_tree_amvp_frame)
 //   d_p_maps                 3 x 256 bytes     the reference picture's depth map, depth_min, depth_max (fhevc_p_predict_frame; the tree chains use the last two)
+//   d_first_p                341 (85 + 256)    the first-pass records of the nodes, behind them those of the 4x4 PUs (fhevc_intra_p, fhevc_p_tree_intra_frame)
+//   d_intra_p                85                the intra records made from them
+// fhevc_p_tree_intra_frame keeps its skip records in d_qpel: the re-pricing has read the refined nodes by then, and every later stage reads d_amvp
 //
 // The timing slots (fhevc_kernel_timing) of the launches below: 4 fhevc_motion_search, 5 the P rule, 7 fhevc_motion_refine, 8 / 9 the searches of the PUs / the
 // small PUs, 10 fhevc_motion_refine_pu, 11 / 12 the wide search / refinement, 13 the partition sizes, 15 the centres and everything centred, 17 the tree, 19 the merge stage,
-// 21 the merge stage per PU, 23 the zero-residual test, 25 the re-pricing against neighbour predictors
+// 21 the merge stage per PU, 23 the zero-residual test, 25 the re-pricing against neighbour predictors, 27 the intra stage
 struct Family { int per_ctu; FhevcMotionNode* fhevc_ctx::*found; FhevcMotionQpelNode* fhevc_ctx::*refined; };
 constexpr Family kNodes = { FHEVC_NODES, &fhevc_ctx::d_motion, &fhevc_ctx::d_qpel }, kPus = { FHEVC_PUS, &fhevc_ctx::d_motion_pu, &fhevc_ctx::d_qpel_pu },
                  kSmall = { FHEVC_PUS_SMALL, &fhevc_ctx::d_motion_pu_small, &fhevc_ctx::d_qpel_pu_small }, kCentres = { 1, &fhevc_ctx::d_centres, nullptr };
@@ -195,7 +203,7 @@ class HostForm {
 
   fhevc_ctx* c;
   hipError_t e = hipSuccess;
-  Copy ins[4], outs[6];   // at most: the centres and three families in; three families of records and of predictor records out
+  Copy ins[4], outs[6];   // at most: the centres and three families in; three families of records and of predictor records out (the intra chain: five)
   int n_in = 0, n_out = 0;
 };
 
@@ -813,11 +821,16 @@ int fhevc_p_shape_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* re
 // d_merge: null for fhevc_p_tree_select_device; with_merge / with_skip say which of the three entry points is asking (the skip variant takes the merge records too)
 static int p_tree_select_on(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, const fhevc_motion_merge_node* d_merge, bool with_merge, int num_pictures, int ctu_row_begin,
                             int ctu_row_end, const fhevc_p_tree_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream,
-                            bool with_skip = false, const fhevc_motion_skip_node* d_skip = nullptr, int skip_mask = 0)
+                            bool with_skip = false, const fhevc_motion_skip_node* d_skip = nullptr, int skip_mask = 0, bool with_intra = false,
+                            const fhevc_intra_p_node* d_intra = nullptr)
 {
   if (!c) return FHEVC_E_INVALID;
   if (!d_shapes || (with_merge && !d_merge) || (!d_depth_min && !d_depth_max && !d_tree)) return fail(c, FHEVC_E_INVALID, "bad tree-decision arguments");
   if (with_skip && (!d_skip || skip_mask < 0 || skip_mask > 3)) return fail(c, FHEVC_E_INVALID, "bad tree-decision arguments (skip records, skip_mask 0..3)");
+  if (with_intra && !d_intra) return fail(c, FHEVC_E_INVALID, "bad tree-decision arguments (intra records)");
+  // (the older entry points read their records as dwords without asking; this one says what it wants)
+  if (with_intra && (((uintptr_t)d_shapes | (uintptr_t)d_merge | (uintptr_t)d_skip | (uintptr_t)d_intra | (uintptr_t)d_tree) & 3))
+    return fail(c, FHEVC_E_INVALID, "bad tree-decision arguments (records are 4-byte aligned)");
   // (records have no sample layout: the checks of the pictures' number and the band)
   if (const char* bad = batch_error(c, 2, c->cfg.width, 0, num_pictures, 1, ctu_row_begin, ctu_row_end, 0, false)) return fail(c, FHEVC_E_INVALID, bad);
   static_assert(sizeof(fhevc_p_tree_rule) == sizeof(FhevcPTreeRule) && sizeof(fhevc_p_tree_node) == sizeof(FhevcPTreeNode), "tree-decision layouts");
@@ -828,6 +841,10 @@ static int p_tree_select_on(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, c
   if ((long long)num_pictures * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "more than 2^31 - 1 CTUs");
   if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
   const FhevcFrames fr = frames_of(c, nullptr, 1, c->cfg.width, 0, num_pictures, ctu_row_begin, ctu_row_end);
+  if (with_intra)
+    return launch_on(c, stream, 17, "fhevc_launch_p_tree_intra", [&](hipStream_t s) {
+      return fhevc_launch_p_tree_intra(fr, r, kn(d_shapes), kn(d_merge), kn(d_skip), skip_mask, kn(d_intra), d_depth_min, d_depth_max, kn(d_tree), c->num_cus, s);
+    });
   if (with_skip)
     return launch_on(c, stream, 17, "fhevc_launch_p_tree_skip", [&](hipStream_t s) {
       return fhevc_launch_p_tree_skip(fr, r, kn(d_shapes), kn(d_merge), kn(d_skip), skip_mask, d_depth_min, d_depth_max, kn(d_tree), c->num_cus, s);
@@ -860,11 +877,53 @@ int fhevc_p_tree_select_skip_device(fhevc_ctx* c, const fhevc_pu_shape_node* d_s
   return p_tree_select_on(c, d_shapes, d_merge, true, num_pictures, ctu_row_begin, ctu_row_end, rule, d_depth_min, d_depth_max, d_tree, stream, true, d_skip, skip_mask);
 }
 
+int fhevc_p_tree_select_intra_device(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, const fhevc_motion_merge_node* d_merge, const fhevc_motion_skip_node* d_skip,
+                                     int skip_mask, const fhevc_intra_p_node* d_intra, int num_pictures, int ctu_row_begin, int ctu_row_end, const fhevc_p_tree_rule* rule,
+                                     uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream)
+{
+  return p_tree_select_on(c, d_shapes, d_merge, true, num_pictures, ctu_row_begin, ctu_row_end, rule, d_depth_min, d_depth_max, d_tree, stream, true, d_skip, skip_mask, true,
+                          d_intra);
+}
+
+// ---- intra candidate costs per CU node for P pictures, from the first passes' records (k_intra_p.hip; the host twin: fhevc_host.hip) ----
+
+int fhevc_intra_p_device(fhevc_ctx* c, int num_pictures, int ctu_row_begin, int ctu_row_end, int qp, const fhevc_node_cost* d_first, const fhevc_node_cost* d_first4,
+                         fhevc_intra_p_node* d_out, void* stream)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!d_first || !d_out) return fail(c, FHEVC_E_INVALID, "bad intra-stage arguments (the first-pass records and the output)");
+  if (((uintptr_t)d_first | (uintptr_t)d_first4 | (uintptr_t)d_out) & 3) return fail(c, FHEVC_E_INVALID, "bad intra-stage arguments (records are 4-byte aligned)");
+  // (records have no sample layout: the checks of the pictures' number, the band and the qp)
+  if (const char* bad = batch_error(c, 2, c->cfg.width, 0, num_pictures, 1, ctu_row_begin, ctu_row_end, qp, false)) return fail(c, FHEVC_E_INVALID, bad);
+  if ((long long)num_pictures * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "more than 2^31 - 1 CTUs");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;  // an empty band: nothing to launch, nothing written
+  // the three bit costs travel with the launch: nothing of the context is read or written by it
+  const FhevcFrames fr = frames_of(c, nullptr, 2, c->cfg.width, 0, num_pictures, ctu_row_begin, ctu_row_end, qp);
+  return launch_on(c, stream, 27, "fhevc_launch_intra_p", [&](hipStream_t s) {
+    return fhevc_launch_intra_p(fr, fhevc_intra_bit_cost(motion_lambda(qp)), reinterpret_cast<const uint32_t*>(d_first), reinterpret_cast<const uint32_t*>(d_first4),
+                                kn(d_out), c->num_cus, s);
+  });
+}
+
+int fhevc_intra_p(fhevc_ctx* c, int qp, const fhevc_node_cost* first, const fhevc_node_cost* first4, fhevc_intra_p_node* out)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!first || !out || qp < 0 || qp > 51) return fail(c, FHEVC_E_INVALID, "bad intra-stage arguments (the first-pass records, the output, qp 0..51)");
+  HostForm h(c);
+  const size_t bn = h.bytes(kNodes), b4 = (size_t)c->num_ctus * FHEVC_PUS4_PER_CTU * sizeof(fhevc_node_cost);
+  const fhevc_node_cost *d_first = h.in(c->d_first_p, bn + b4, first, bn), *d_first4 = h.in(c->d_first_p, bn + b4, first4, b4, bn);
+  fhevc_intra_p_node* d_out = h.out(c->d_intra_p, bn, out, bn);
+  return h.run([&] { return fhevc_intra_p_device(c, 1, 0, c->ctus_y, qp, d_first, d_first4, d_out, c->stream); });
+}
+
 // with_merge: fhevc_p_tree_merge_frame -- the merge stage between refinement and tree; with_merge_pu: fhevc_p_tree_merge_pu_frame -- behind it the merge stage
-// per PU, and the selection that takes its costs; with_amvp: fhevc_p_tree_amvp_frame -- the re-pricing behind the refinements, and every later stage on its records
+// per PU, and the selection that takes its costs; with_amvp: fhevc_p_tree_amvp_frame -- the re-pricing behind the refinements, and every later stage on its records;
+// with_intra: fhevc_p_tree_intra_frame -- behind the selection the zero-residual stage, the two first passes of the current picture and the intra stage, and the
+// tree that takes all of it
 static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
                            const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes,
-                           bool with_merge, fhevc_motion_merge_node* merge, bool with_merge_pu = false, bool with_amvp = false)
+                           bool with_merge, fhevc_motion_merge_node* merge, bool with_merge_pu = false, bool with_amvp = false, bool with_intra = false, int skip_mask = 0,
+                           fhevc_intra_p_node* intra = nullptr)
 {
   if (!c) return FHEVC_E_INVALID;
   if (!cur_luma || !ref_luma || !depth_min || !depth_max || stride_samples < c->cfg.width) return fail(c, FHEVC_E_INVALID, "bad tree-decision frame arguments");
@@ -875,6 +934,7 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
     if (const char* bad = fhevc_pu_shape_rule_error(*shape_rule)) return fail(c, FHEVC_E_INVALID, bad);
   if (tree_rule)
     if (const char* bad = fhevc_p_tree_rule_error(*tree_rule)) return fail(c, FHEVC_E_INVALID, bad);
+  if (with_intra && (skip_mask < 0 || skip_mask > 3)) return fail(c, FHEVC_E_INVALID, "bad tree-decision frame arguments (skip_mask 0..3)");
   HostForm h(c);
   const size_t map = (size_t)c->num_ctus * 256, records = h.bytes(kNodes);
   Chain k = claim_chain(h, coarse_range != 0);
@@ -893,6 +953,17 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
     fhevc_motion_qpel_node* const d_priced = h.dev<fhevc_motion_qpel_node>(c->d_amvp, all);
     k.q_nodes_out = d_priced; k.q_pus_out = d_priced + (size_t)c->num_ctus * FHEVC_NODES; k.q_small_out = k.q_pus_out + (size_t)c->num_ctus * FHEVC_PUS;
   }
+  fhevc_motion_skip_node* d_skip = nullptr;
+  fhevc_node_cost *d_first = nullptr, *d_first4 = nullptr;
+  fhevc_intra_p_node* d_intra = nullptr;
+  if (with_intra) {
+    const size_t b4 = (size_t)c->num_ctus * FHEVC_PUS4_PER_CTU * sizeof(fhevc_node_cost);
+    d_skip = h.dev<fhevc_motion_skip_node>(c->d_qpel, records);   // the refined nodes are dead once the re-pricing has read them
+    d_first = h.dev<fhevc_node_cost>(c->d_first_p, records + b4);
+    d_first4 = h.dev<fhevc_node_cost>(c->d_first_p, records + b4, records);
+    d_intra = h.dev<fhevc_intra_p_node>(c->d_intra_p, records);
+    h.out(c->d_intra_p, records, intra, records);
+  }
   return h.run(cur_luma, ref_luma, stride_samples, [&] {
     int rc = queue_chain(c, qp, search_range, coarse_range, k);
     if (rc == FHEVC_OK && with_amvp) {
@@ -906,6 +977,14 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
     if (rc == FHEVC_OK && with_merge_pu)
       rc = fhevc_pu_shape_select_merge_device(c, k.q_nodes, k.q_pus, k.q_small, d_merge_pus, d_merge_small, 1, 0, c->ctus_y, shape_rule, d_shapes, nullptr, nullptr, c->stream);
     else if (rc == FHEVC_OK) rc = fhevc_pu_shape_select_device(c, k.q_nodes, k.q_pus, k.q_small, 1, 0, c->ctus_y, shape_rule, d_shapes, nullptr, c->stream);
+    if (rc == FHEVC_OK && with_intra) {
+      const int16_t* d_cur = c->d_pair + pair_plane(c);   // the current picture of the staged pair, as a batch of one frame
+      rc = on_pair(c, fhevc_motion_skip_device, qp, merge_range, d_merge, d_skip, c->stream);
+      if (rc == FHEVC_OK) rc = fhevc_intra_first_pass_device(c, d_cur, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, d_first, c->stream);
+      if (rc == FHEVC_OK) rc = fhevc_intra_first_pass_4x4_device(c, d_cur, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, 0, d_first4, nullptr, c->stream);
+      if (rc == FHEVC_OK) rc = fhevc_intra_p_device(c, 1, 0, c->ctus_y, qp, d_first, d_first4, d_intra, c->stream);
+      return rc != FHEVC_OK ? rc : p_tree_select_on(c, d_shapes, d_merge, true, 1, 0, c->ctus_y, tree_rule, d_min, d_max, nullptr, c->stream, true, d_skip, skip_mask, true, d_intra);
+    }
     return rc != FHEVC_OK ? rc : p_tree_select_on(c, d_shapes, d_merge, with_merge, 1, 0, c->ctus_y, tree_rule, d_min, d_max, nullptr, c->stream);
   });
 }
@@ -935,6 +1014,14 @@ int fhevc_p_tree_amvp_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t
                             fhevc_motion_merge_node* merge)
 {
   return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge, true, true);
+}
+
+int fhevc_p_tree_intra_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                             const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, int skip_mask, uint8_t* depth_min, uint8_t* depth_max,
+                             fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge, fhevc_intra_p_node* intra)
+{
+  return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge, true, true,
+                         true, skip_mask, intra);
 }
 
 }  // extern "C"

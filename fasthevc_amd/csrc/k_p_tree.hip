@@ -19,6 +19,8 @@
 // Which lane and which address is read depends on lane and node numbers alone -- never on what the records hold.
 // Two further families of instantiations take more records beside the selection's (the parameter pack of the kernel): the merge stage's (own = the smaller
 // cost, bit 6) and, behind those, the skip stage's (fhevc_p_tree_select_skip_device: a merged node of level 0..2 with a masked zero bit is not descended).
+// A fourth family takes the intra stage's records behind all of these (fhevc_p_tree_select_intra_device: a node of any level that is not such a calm one
+// takes its intra cost where that is strictly smaller, bit 16 of the record's last dword).
 // The rule (60 bytes) and the geometry are kernel arguments: two launches with different rules never share state (no per-context table).
 #include "../../include/fasthevc.h"
 #include "fhevc_internal.h"
@@ -51,8 +53,10 @@ __device__ __forceinline__ uint64_t sum4(uint64_t v, int a, int b)
 // the node of level L (0..2) at sample (x, y) of the CTU: cost_best of its record, the sum of what its four children hand it
 // merged (the merge variants only): the record's merge cost is the smaller one -- bit 6 of an INSIDE node's flags
 // skipped (the skip variant only): the node's skip record carries a masked bit; with merged, on an INSIDE node: HM's EarlyCU -- not descended, bit 7
+// intra (the intra variant only): cost_best is the node's intra cost, taken by the lane that loaded it -- bit 16 of an INSIDE node's flags (byte 14 of the record)
 template <int L>
-__device__ __forceinline__ TreeNode decide(const FhevcPTreeRule& R, uint32_t cost_best, uint64_t sum, int x, int y, int valid_w, int valid_h, bool merged, bool skipped)
+__device__ __forceinline__ TreeNode decide(const FhevcPTreeRule& R, uint32_t cost_best, uint64_t sum, int x, int y, int valid_w, int valid_h, bool merged, bool skipped,
+                                           bool intra = false)
 {
   constexpr int S = 64 >> L;
   const bool inside = x + S <= valid_w && y + S <= valid_h, outside = x >= valid_w || y >= valid_h;
@@ -73,6 +77,7 @@ __device__ __forceinline__ TreeNode decide(const FhevcPTreeRule& R, uint32_t cos
   n.flags = (split ? 1u : 0u) | (stop ? 2u : 0u) | (!inside ? 4u : 0u) | (n.own != kMark ? 16u : 0u) | (n.kids != kMark ? 32u : 0u);
   if (merged && inside) n.flags |= 64u;
   if (early) n.flags |= 128u;
+  if (intra && inside) n.flags |= 1u << 16;
   if (outside) { n.own = n.kids = n.tree = kMark; n.flags = 8u; }
   return n;
 }
@@ -95,6 +100,8 @@ __device__ __forceinline__ void store_record(uint32_t* dst, uint32_t own, uint32
 // cost), bit 6 of its flags says that the merge cost is strictly smaller.  A pack keeps the plain instantiation's argument list, and so its code, what it was
 // ... or THREE (fhevc_p_tree_select_skip_device): behind the merge records the records of k_motion_skip.hip as bytes and the mask on their flags (byte 10),
 // read by lanes 0..20 in one byte load; the answer travels to the node's lanes in a shuffle of its own
+// ... or FOUR (fhevc_p_tree_select_intra_device): behind those the records of k_intra_p.hip, of which cost_best (dword 1) is read by the same lanes in the
+// same two loads, and one more byte load for the leaves' skip flags; whether the intra cost was taken travels like the merged bit
 __device__ __forceinline__ const uint32_t* merge_of() { return nullptr; }
 __device__ __forceinline__ const uint32_t* merge_of(const uint32_t* m) { return m; }
 __device__ __forceinline__ const uint32_t* merge_of(const uint32_t* m, const uint8_t*, int) { return m; }
@@ -104,14 +111,20 @@ __device__ __forceinline__ const uint8_t* skip_of(const uint32_t*, const uint8_t
 __device__ __forceinline__ int mask_of() { return 0; }
 __device__ __forceinline__ int mask_of(const uint32_t*) { return 0; }
 __device__ __forceinline__ int mask_of(const uint32_t*, const uint8_t*, int mask) { return mask; }
+__device__ __forceinline__ const uint32_t* merge_of(const uint32_t* m, const uint8_t*, int, const uint32_t*) { return m; }
+__device__ __forceinline__ const uint8_t* skip_of(const uint32_t*, const uint8_t* s, int, const uint32_t*) { return s; }
+__device__ __forceinline__ int mask_of(const uint32_t*, const uint8_t*, int mask, const uint32_t*) { return mask; }
+template <class... M> __device__ __forceinline__ const uint32_t* intra_of(M...) { return nullptr; }
+__device__ __forceinline__ const uint32_t* intra_of(const uint32_t*, const uint8_t*, int, const uint32_t* i) { return i; }
 template <bool WIDE_MAPS, bool WIDE_TREE, class... M>
 __global__ __launch_bounds__(256) void fhevc_p_tree_kernel(PTreeGeom G, FhevcPTreeRule R, const uint32_t* __restrict__ shapes, uint8_t* __restrict__ depth_min,
                                                            uint8_t* __restrict__ depth_max, uint32_t* __restrict__ tree, M... merge_arg)
 {
-  constexpr bool MERGE = sizeof...(M) != 0, SKIP = sizeof...(M) == 3;
+  constexpr bool MERGE = sizeof...(M) != 0, SKIP = sizeof...(M) >= 3, INTRA = sizeof...(M) == 4;
   const uint32_t* __restrict__ merge = merge_of(merge_arg...);
   const uint8_t* __restrict__ skip = skip_of(merge_arg...);
   const int skip_mask = mask_of(merge_arg...);
+  const uint32_t* __restrict__ intra = intra_of(merge_arg...);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int x = (lane & 7) * 8, y = (lane >> 3) * 8;   // this lane's 8x8 node
   // where this lane's ancestors sit among lanes 0..20 of the second load
@@ -140,6 +153,18 @@ __global__ __launch_bounds__(256) void fhevc_p_tree_kernel(PTreeGeom G, FhevcPTr
     }
     uint32_t us = 0u;
     if constexpr (SKIP) us = ((uint32_t)skip[(size_t)g * (FHEVC_NODES * 16) + 16 * min(lane, 20) + 10] & (uint32_t)skip_mask) != 0u ? 1u : 0u;
+    // the intra cost where the node is not calm (merged, with a masked zero bit) and it is strictly smaller: a marker, the largest value, never is
+    bool leaf_intra = false;
+    uint32_t ui = 0u;
+    if constexpr (INTRA) {
+      const uint32_t* isrc = intra + (size_t)g * (FHEVC_NODES * 4);
+      const uint32_t ileaf = isrc[4 * (21 + lane) + 1], iupper = isrc[4 * min(lane, 20) + 1];
+      const bool leaf_zero = ((uint32_t)skip[(size_t)g * (FHEVC_NODES * 16) + 16 * (21 + lane) + 10] & (uint32_t)skip_mask) != 0u;
+      leaf_intra = !(leaf_merged && leaf_zero) && ileaf < leaf;
+      const bool upper_intra = !(upper_merged && us != 0u) && iupper < upper;
+      leaf = leaf_intra ? ileaf : leaf; upper = upper_intra ? iupper : upper;
+      ui = (uint32_t)upper_intra;
+    }
 
     // ---- level 3: a leaf is coded iff it lies wholly inside ----
     const bool inside8 = x + 8 <= valid_w && y + 8 <= valid_h;
@@ -148,11 +173,11 @@ __global__ __launch_bounds__(256) void fhevc_p_tree_kernel(PTreeGeom G, FhevcPTr
     // (the merge variant hands the "merged" bit along in bit 0 of a second shuffle; the plain one passes a constant)
     const uint32_t um = MERGE ? (uint32_t)upper_merged : 0u;
     const TreeNode n16 = decide<2>(R, __shfl(upper, k16), sum4(share(own8, !inside8), 1, 8), x & 48, y & 48, valid_w, valid_h, MERGE && __shfl(um, k16) != 0u,
-                                    SKIP && __shfl(us, k16) != 0u);
+                                    SKIP && __shfl(us, k16) != 0u, INTRA && __shfl(ui, k16) != 0u);
     const TreeNode n32 = decide<1>(R, __shfl(upper, k32), sum4(share(n16.tree, n16.flags == 8u), 2, 16), x & 32, y & 32, valid_w, valid_h, MERGE && __shfl(um, k32) != 0u,
-                                    SKIP && __shfl(us, k32) != 0u);
+                                    SKIP && __shfl(us, k32) != 0u, INTRA && __shfl(ui, k32) != 0u);
     const TreeNode n64 = decide<0>(R, __shfl(upper, 0), sum4(share(n32.tree, n32.flags == 8u), 4, 32), 0, 0, valid_w, valid_h, MERGE && __shfl(um, 0) != 0u,
-                                    SKIP && __shfl(us, 0) != 0u);
+                                    SKIP && __shfl(us, 0) != 0u, INTRA && __shfl(ui, 0) != 0u);
 
     // ---- the maps: the depths the decisions open top-down, 0 outside the picture ----
     if (depth_min || depth_max) {
@@ -174,7 +199,7 @@ __global__ __launch_bounds__(256) void fhevc_p_tree_kernel(PTreeGeom G, FhevcPTr
     // ---- the records: node 21 + lane from every lane, node `lane` from lanes 0..20 ----
     if (tree) {
       uint32_t* dst = tree + (size_t)g * (FHEVC_NODES * 4);
-      store_record(dst + 4 * (21 + lane), own8, kMark, own8, (inside8 ? (own8 != kMark ? 16u : 0u) | (MERGE && leaf_merged ? 64u : 0u) : 8u) | 3u << 8, WIDE_TREE);
+      store_record(dst + 4 * (21 + lane), own8, kMark, own8, (inside8 ? (own8 != kMark ? 16u : 0u) | (MERGE && leaf_merged ? 64u : 0u) | (INTRA && leaf_intra ? 1u << 16 : 0u) : 8u) | 3u << 8, WIDE_TREE);
       const TreeNode& mine = serves == 2 ? n16 : (serves == 1 ? n32 : n64);
       const uint32_t own = __shfl(mine.own, rec_src), kids = __shfl(mine.kids, rec_src), best = __shfl(mine.tree, rec_src), flags = __shfl(mine.flags, rec_src);
       if (lane < 21) store_record(dst + 4 * lane, own, kids, best, flags | (uint32_t)rec_level << 8, WIDE_TREE);
@@ -185,8 +210,10 @@ __global__ __launch_bounds__(256) void fhevc_p_tree_kernel(PTreeGeom G, FhevcPTr
 }  // namespace
 
 static hipError_t launch_p_tree(const FhevcFrames& fr, const FhevcPTreeRule& rule, const FhevcPuShapeNode* d_shapes, const FhevcMotionMergeNode* d_merge, uint8_t* d_depth_min,
-                                uint8_t* d_depth_max, FhevcPTreeNode* d_tree, int num_cus, hipStream_t stream, const FhevcMotionSkipNode* d_skip = nullptr, int skip_mask = 0)
+                                uint8_t* d_depth_max, FhevcPTreeNode* d_tree, int num_cus, hipStream_t stream, const FhevcMotionSkipNode* d_skip = nullptr, int skip_mask = 0,
+                                const FhevcIntraPNode* d_intra = nullptr)
 {
+  static_assert(offsetof(FhevcIntraPNode, cost_best) == 4 && offsetof(FhevcPTreeNode, pad) == 14, "intra record layout, the tree record's byte 14");
   static_assert(sizeof(FhevcMotionSkipNode) == 16 && offsetof(FhevcMotionSkipNode, flags) == 10, "skip record layout");
   static_assert(sizeof(FhevcPuShapeNode) == 16 && sizeof(FhevcPTreeNode) == 16 && sizeof(FhevcPTreeRule) == 60 && sizeof(FhevcMotionMergeNode) == 16, "record layouts");
   PTreeGeom G;
@@ -205,7 +232,15 @@ static hipError_t launch_p_tree(const FhevcFrames& fr, const FhevcPTreeRule& rul
   const uint32_t* merge = reinterpret_cast<const uint32_t*>(d_merge);   // cost_best is dword 1 of a merge record too
   uint32_t* tree = reinterpret_cast<uint32_t*>(d_tree);
   const dim3 blocks((unsigned)grid), threads(256);
-  if (d_skip) {
+  if (d_intra) {
+    const uint8_t* skip = reinterpret_cast<const uint8_t*>(d_skip);
+    const uint32_t* intra = reinterpret_cast<const uint32_t*>(d_intra);   // cost_best is dword 1 of an intra record too
+    if (wide_maps && wide_tree) hipLaunchKernelGGL((fhevc_p_tree_kernel<true, true, const uint32_t*, const uint8_t*, int, const uint32_t*>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree, merge, skip, skip_mask, intra);
+    else if (wide_maps) hipLaunchKernelGGL((fhevc_p_tree_kernel<true, false, const uint32_t*, const uint8_t*, int, const uint32_t*>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree, merge, skip, skip_mask, intra);
+    else if (wide_tree) hipLaunchKernelGGL((fhevc_p_tree_kernel<false, true, const uint32_t*, const uint8_t*, int, const uint32_t*>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree, merge, skip, skip_mask, intra);
+    else hipLaunchKernelGGL((fhevc_p_tree_kernel<false, false, const uint32_t*, const uint8_t*, int, const uint32_t*>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree, merge, skip, skip_mask, intra);
+  }
+  else if (d_skip) {
     const uint8_t* skip = reinterpret_cast<const uint8_t*>(d_skip);
     if (wide_maps && wide_tree) hipLaunchKernelGGL((fhevc_p_tree_kernel<true, true, const uint32_t*, const uint8_t*, int>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree, merge, skip, skip_mask);
     else if (wide_maps) hipLaunchKernelGGL((fhevc_p_tree_kernel<true, false, const uint32_t*, const uint8_t*, int>), blocks, threads, 0, stream, G, rule, shapes, d_depth_min, d_depth_max, tree, merge, skip, skip_mask);
@@ -244,4 +279,12 @@ hipError_t fhevc_launch_p_tree_skip(const FhevcFrames& fr, const FhevcPTreeRule&
 {
   if (!d_merge || !d_skip || skip_mask < 0 || skip_mask > 3) return hipErrorInvalidValue;
   return launch_p_tree(fr, rule, d_shapes, d_merge, d_depth_min, d_depth_max, d_tree, num_cus, stream, d_skip, skip_mask);
+}
+
+hipError_t fhevc_launch_p_tree_intra(const FhevcFrames& fr, const FhevcPTreeRule& rule, const FhevcPuShapeNode* d_shapes, const FhevcMotionMergeNode* d_merge,
+                                     const FhevcMotionSkipNode* d_skip, int skip_mask, const FhevcIntraPNode* d_intra, uint8_t* d_depth_min, uint8_t* d_depth_max,
+                                     FhevcPTreeNode* d_tree, int num_cus, hipStream_t stream)
+{
+  if (!d_merge || !d_skip || !d_intra || skip_mask < 0 || skip_mask > 3) return hipErrorInvalidValue;
+  return launch_p_tree(fr, rule, d_shapes, d_merge, d_depth_min, d_depth_max, d_tree, num_cus, stream, d_skip, skip_mask, d_intra);
 }

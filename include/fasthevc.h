@@ -1089,6 +1089,86 @@ int  fhevc_p_tree_select_skip_device(fhevc_ctx* ctx, const fhevc_pu_shape_node* 
                                      const fhevc_motion_skip_node* d_skip, int skip_mask, int num_pictures, int ctu_row_begin, int ctu_row_end,
                                      const fhevc_p_tree_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream);
 
+/* ---- config 4 (P slices): intra candidate costs per CU node (k_intra_p.hip) -----------------------------------------------------------------------
+ * HM checks intra at every CU of a P slice (TEncCu.cpp:797-816): xCheckRDCostIntra(SIZE_2Nx2N) at every depth, SIZE_NxN at the 8x8 level, both only while
+ * the best mode so far has a non-zero CBF.  Without that candidate a node whose content is not in the reference picture -- uncovered background, the second
+ * of two transparent motions, a new object -- has only a huge inter cost, and the tree can only split.  The expensive half exists: the two first passes
+ * deliver the best of the 35 modes per node and per 4x4 PU under sqrt(lambda), the square-root lambda every motion stage prices its bits with, so intra
+ * first-pass cost and refined inter cost stand on one footing, SATD + sqrt(lambda) * bits.  This stage turns those records into the integer record form the
+ * tree reads.
+ *   Input per CTU: the 85 fhevc_node_cost records of fhevc_intra_first_pass_device and, optionally, the 256 of fhevc_intra_first_pass_4x4_device (NULL: no
+ * NxN candidate), for the pictures that are P pictures, compact over the band; num_pictures counts as in fhevc_pu_shape_select_device.  Of a record only
+ * satd and the low byte of mode are read -- the double `cost` never --, and any content of the input bytes is legal.
+ *   MARK = 0xFFFFFFFF, SAT = 0xFFFFFFFE.  bits(m) = 2 for mode 0, 3 for modes 1 and 26, 6 for every other byte value: the first pass's own model.
+ * c[b] = (uint32_t)((motion_lambda * b) / 65536.0) for b in {2, 3, 6} with motion_lambda = 65536 sqrt(lambda(qp)): getCost(b) in the arithmetic of the
+ * motion stages, computed on the host, by value with the launch.  A first-pass record is PRICED iff satd != MARK; its price is min(satd + c[bits(mode)], SAT),
+ * the sum in 64 bits.
+ *   Node k of level 0..2: a marker record unless the node is INSIDE (the tree's geometry class) and its record is priced; otherwise satd_best = satd,
+ * cost_best = the price, part = 0, modes[0..3] = mode.
+ *   Node of level 3 (a marker unless INSIDE): the 2Nx2N candidate as above.  The NxN candidate exists iff the 4x4 array is given and all four PUs of the
+ * 8x8 CU at (x, y) are priced: (2x, 2y), (2x + 1, 2y), (2x, 2y + 1), (2x + 1, 2y + 1) of the 16x16 unit raster.  Its cost is the 64-bit sum of the four
+ * prices saturated at SAT, its satd the saturated sum of the four satds.  NxN replaces 2Nx2N iff its cost is STRICTLY smaller (HM tries 2Nx2N first and
+ * xCheckBestMode keeps the earlier mode on a tie) or 2Nx2N is unavailable; then part = 1 and modes[i] = the four PU modes in that order.
+ *   Stated departures: the bits of the skip flag, the pred-mode flag and the part mode are left out, as every other stage leaves out its mode bits.  The
+ * price is the INTEGER price of the first pass's winner; the first pass chose that winner under its double cost, so a mode whose integer price is smaller by
+ * the truncation of c[] can exist and is not looked for.
+ *   Field order (pinned: 16 bytes without padding; cost_best is dword 1, as in every record the tree reads): */
+typedef struct {
+  uint32_t satd_best;       /* the SATD of the candidate taken (NxN: the saturated sum of four) */
+  uint32_t cost_best;       /* its price */
+  uint8_t  modes[4];        /* part 0: the node's mode four times; part 1: the modes of the four PUs */
+  uint8_t  part;            /* 0 = 2Nx2N, 1 = NxN */
+  uint8_t  pad[3];          /* written 0 */
+} fhevc_intra_p_node;       /* 16 bytes; a marker record: satd_best = cost_best = 0xFFFFFFFF, modes = 255 four times, part = 0, pad = 0 */
+/* Device form: d_first: num_pictures * band CTUs * 85 records, d_first4: ... * 256 or NULL, d_out: ... * 85 records, all compact over the band.  The output
+ * is written over exactly its extent, an empty band writes nothing.  One wave per CTU, four per workgroup, grid-stride, no LDS: lane i is 8x8 node 21 + i
+ * and loads its record and its four PU records, lanes 0..20 load the upper nodes; which address a lane reads depends on lane and node numbers only.  All
+ * arrays may sit on any 4-byte alignment: inputs are read as 8-byte pairs where both are 8-byte aligned, records leave as 16-byte stores where d_out is
+ * 16-byte aligned, as dwords otherwise; the bytes are the same.  Asynchronous with respect to the host, allocates nothing, keeps NO state in HBM between
+ * calls: calls with different QPs may be in flight on two streams, and the first passes and this stage may follow each other on one stream without a host
+ * synchronisation.  FHEVC_E_INVALID with a fhevc_last_error text (nothing is launched or written): a null context, d_first or d_out, a pointer that is not
+ * 4-byte aligned, num_pictures < 1, a bad band, qp outside 0..51.  Timed under slot 27 of fhevc_kernel_timing.
+ * NOT covered: reconstructed neighbours (the first passes predict from the source picture), the RD search behind HM's candidate list (one winner per
+ * block, no residual coding), chroma, PCM.  The encoder hook does not consume this output. */
+int  fhevc_intra_p_device(fhevc_ctx* ctx, int num_pictures, int ctu_row_begin, int ctu_row_end, int qp, const fhevc_node_cost* d_first,
+                          const fhevc_node_cost* d_first4 /* or NULL */, fhevc_intra_p_node* d_out, void* stream);
+/* one picture, host arrays over the whole picture (numCtus * 85 / 256 / 85), synchronous */
+int  fhevc_intra_p(fhevc_ctx* ctx, int qp, const fhevc_node_cost* first, const fhevc_node_cost* first4 /* or NULL */, fhevc_intra_p_node* out);
+/* The host twin: the same definition in plain C++ for one picture of width x height and the band [ctu_row_begin, ctu_row_end); arrays compact over the band.
+ * Needs no context and no device.  FHEVC_E_INVALID (nothing written): what the device form rejects, width or height below 8. */
+int  fhevc_intra_p_picture(int width, int height, int ctu_row_begin, int ctu_row_end, int qp, const fhevc_node_cost* first,
+                           const fhevc_node_cost* first4 /* or NULL */, fhevc_intra_p_node* out);
+
+/* The tree decision that takes the intra candidate: fhevc_p_tree_select_skip[_device] with one more argument, the CTU's 85 fhevc_intra_p_node records (never
+ * NULL; on the device compact over the band like d_shapes; any 4-byte alignment; only cost_best is read).  TWO changed rules.
+ *   Rule 1, the calm gate: for an INSIDE node of ANY level 0..3 let inter = the smaller of selection and merge cost, as before.  The node is CALM iff the
+ * merge cost is strictly smaller (bit 6) and skip.flags & skip_mask != 0: HM's "best mode has no coded residual", under which intra is not tried
+ * (TEncCu.cpp:799-804).  On levels 0..2 calm is exactly the EarlyCU condition above and behaves as there.
+ *   Rule 2, intra as own cost: if the node is not calm and intra.cost_best < inter (strict; a marker never wins), own[k] = intra.cost_best and bit 0 of
+ * byte 14 of the tree record (pad[0], a zero byte in every other tree) is set; byte 15 stays 0.  Bit 6 keeps its meaning.
+ *   Everything else is the existing definition: kids, tree, the margins, the maps, CROSSING and ABSENT.  With every intra cost 0xFFFFFFFF the output is byte
+ * for byte fhevc_p_tree_select_skip[_device]'s.  The device form is a further instantiation of k_p_tree.hip (one more dword load per lane and round for the
+ * intra cost, one more byte load for the leaves' skip flags), timed under slot 17.  The host form needs no context.  FHEVC_E_INVALID: what
+ * fhevc_p_tree_select_skip[_device] rejects, a null intra pointer; the device form also rejects a record pointer (d_shapes, d_merge, d_skip, d_intra, d_tree)
+ * that is not 4-byte aligned. */
+int  fhevc_p_tree_select_intra(const fhevc_pu_shape_node* shapes /* 85 */, const fhevc_motion_merge_node* merge /* 85 */,
+                               const fhevc_motion_skip_node* skip /* 85 */, int skip_mask, const fhevc_intra_p_node* intra /* 85 */, int valid_w, int valid_h,
+                               const fhevc_p_tree_rule* rule, uint8_t* depth_min /* 256 or NULL */, uint8_t* depth_max /* 256 or NULL */,
+                               fhevc_p_tree_node* tree /* 85 or NULL */);
+int  fhevc_p_tree_select_intra_device(fhevc_ctx* ctx, const fhevc_pu_shape_node* d_shapes, const fhevc_motion_merge_node* d_merge,
+                                      const fhevc_motion_skip_node* d_skip, int skip_mask, const fhevc_intra_p_node* d_intra, int num_pictures,
+                                      int ctu_row_begin, int ctu_row_end, const fhevc_p_tree_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max,
+                                      fhevc_p_tree_node* d_tree, void* stream);
+/* The frame chain with everything: fhevc_p_tree_amvp_frame's arguments, checks and both chains (zero-centred; coarse_range 1..14), plus skip_mask (0..3) and
+ * an optional download of the intra records.  One pair from host buffers on the context's stream: search, refinement, re-pricing, merge per node and per PU,
+ * merge-aware selection, the zero-residual stage on the node merge records, the two intra first passes of the CURRENT picture, the intra stage, and
+ * fhevc_p_tree_select_intra_device.  Every buffer is one of the context's staging buffers, allocated by the first call that needs it.  A rejected call
+ * moves nothing. */
+int  fhevc_p_tree_intra_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                              const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, int skip_mask, uint8_t* depth_min /* numCtus * 256 */,
+                              uint8_t* depth_max /* numCtus * 256 */, fhevc_pu_shape_node* shapes /* numCtus * 85 or NULL */,
+                              fhevc_motion_merge_node* merge /* numCtus * 85 or NULL */, fhevc_intra_p_node* intra /* numCtus * 85 or NULL */);
+
 /* CTU-row band of rank `rank` out of `world`: rows [begin, end) */
 int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
 
@@ -1104,8 +1184,10 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
  * -- except 17 = the P-picture tree decision (fhevc_p_tree_select_device, fhevc_p_tree_select_merge_device), added later.  16 is not a slot either: it stays rejected
  * -- and 19 = the merge-candidate costs (fhevc_motion_merge*), added later still.  18 is not a slot: it stays rejected -- and 21 = the merge-candidate
  * costs per PU (fhevc_motion_merge_pu*).  20 is not a slot: it stays rejected -- and 23 = the zero-residual test (fhevc_motion_skip*).  22 is not a slot: it stays
- * rejected -- and 25 = the re-pricing against neighbour predictors (fhevc_motion_amvp*).  24 is not a slot: it stays rejected, as does any number above 25.
- * The tree that stops at a skip (fhevc_p_tree_select_skip_device) is timed under 17 */
+ * rejected -- and 25 = the re-pricing against neighbour predictors (fhevc_motion_amvp*).  24 is not a slot: it stays rejected, as does any number above 25
+ * -- except 27 = the intra candidate costs of P pictures (fhevc_intra_p*).  26 is not a slot: it stays rejected, as does any number above 27.
+ * The tree that stops at a skip (fhevc_p_tree_select_skip_device) and the tree that takes the intra candidate (fhevc_p_tree_select_intra_device) are timed
+ * under 17 */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
 int  fhevc_enable_kernel_timing(fhevc_ctx* ctx, int on);
 
