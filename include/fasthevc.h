@@ -1004,8 +1004,9 @@ typedef struct {
  * synchronisation.  FHEVC_E_INVALID with a fhevc_last_error text (nothing launched, nothing written): a null context (no text), a null d_nodes, no output, an
  * output without its input, a pointer that is not 4-byte aligned, num_frames < 2, a bad band, qp outside 0..51.  Timed under slot 25 of fhevc_kernel_timing.
  * NOT covered: a search or refinement that moves its window to the predictor or picks its winner under it, the temporal candidate, predictors from
- * finer-level neighbours.  Table entries 39..66 rest on the formula alone: the reference's recorded costs reach 38 bits.  The encoder hook does not
- * consume this output. */
+ * finer-level neighbours.  Table entries 39..66 rest on the formula, and the formula on the reference's own getCost(0..66) at every QP: recorded, with
+ * fillMvpCand's lists on hand-set motion fields, in tests/golden/ref_motion_candidates.npz.  Not held to the reference: the band rule, INSIDE, the tie
+ * departure above.  The encoder hook does not consume this output. */
 int  fhevc_motion_amvp_device(fhevc_ctx* ctx, int num_frames, int ctu_row_begin, int ctu_row_end, int qp, const fhevc_motion_qpel_node* d_nodes,
                               const fhevc_motion_qpel_node* d_pus, const fhevc_motion_qpel_node* d_pus_small, fhevc_motion_qpel_node* d_out_nodes,
                               fhevc_motion_qpel_node* d_out_pus, fhevc_motion_qpel_node* d_out_pus_small, fhevc_motion_mvp* d_mvp_nodes,

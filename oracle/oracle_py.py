@@ -250,6 +250,27 @@ def bind_rdo(lib):
     return lib
 
 
+def have_candidates():
+    """oracle/_ref/libhmref.so is there AND was built from this tree's harness: it names the candidate-list entry points.  A library left behind by an
+    older tree, which `make -C oracle ref` could not replace (no reference sources), counts as not built"""
+    if not have_ref():
+        return False
+    with open(REF_SO, "rb") as f:
+        return b"href_mc_set_field\0" in f.read()
+
+
+def bind_candidates(lib):
+    """the candidate-list entry points of oracle/ref_rdo_harness.cpp: href_mc_set_field (a hand-set motion field of one CU level), href_mc_query (the
+    reference's own fillMvpCand and getInterMergeCandidates per CU / partition size / part) and href_mv_bit_tables (getCost and the vector bits)"""
+    lib.href_mc_set_field.argtypes = [C.c_int, C.c_int, C.c_int, _i16p, _u8p]
+    lib.href_mc_set_field.restype = C.c_int
+    lib.href_mc_query.argtypes = [C.c_int, C.c_int, C.c_int, _i32p, _i16p]
+    lib.href_mc_query.restype = C.c_int
+    lib.href_mv_bit_tables.argtypes = [C.c_int, C.c_int, _u32p, C.c_int, _i32p, _u32p]
+    lib.href_mv_bit_tables.restype = C.c_int
+    return lib
+
+
 def split_costs(lib, num_ctus):
     """`make -C oracle costs` build (load_ref(hook="costs")): RD costs of the last rdo_encode's xCompressCU nodes -> [numCtus, 21, 2] float64
     ([..., 0] best non-split mode, [..., 1] four-way split; node 0 the CTU, 1 + q quadrant q, 5 + b 16x16 block b, q / b in z-order;

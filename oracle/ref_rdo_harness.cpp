@@ -878,6 +878,176 @@ int href_quant_tu(int width, int height, int bit_depth, int qp, int n, int from_
   return rc;
 }
 
+// ---- config 4: the reference's OWN candidate lists -- TComDataCU::fillMvpCand (TComDataCU.cpp:2578-2716) and TComDataCU::getInterMergeCandidates
+// (:2142-2484) -- on a motion field the caller sets by hand.  No samples are read and nothing is encoded.
+//   href_mc_set_field: a P slice (POC 1) over the whole picture with ONE reference picture (a real picture object at POC 0: xAddMVPCandUnscaled reads its
+// POC through getRefPic, :2838), TMVP off, MaxNumMergeCand 5, parallel merge level 2.  Every CTU is tiled with 2Nx2N CUs of depth `level`; CU (bx, by) of CTU
+// c, at index by * (1 << level) + bx in raster order, is inter (refIdx 0, inter direction 1, the given vector in quarter samples) where inter[] is non-zero and
+// the CU lies wholly inside the picture, intra otherwise.
+//   href_mc_query: per query (ctu, cu index as above, HM PartSize, part index, part 0 set, part 0's vector) the CU is set to that partition size for the call,
+// its motion cleared; when part 1 is queried and part 0 is set, part 0's rectangle (the reference's own getPartPosition) gets that vector, as the encoder has
+// done by the time it searches part 1; the queried part stays unset.  The functions run on a sub-CU view of the picture's CTU (copySubCU: the view's arrays
+// ARE the CTU's, which is why motion is written at absolute partition addresses); the CU is restored afterwards.
+//   out per query, 40 int16: [0..3] the two AMVP candidates (x0, y0, x1, y1); [4 + 4 i ..] merge candidate i: mvx, mvy, inter direction, refIdx (list 0);
+// [24] numValidMergeCand + 16 * the number of spatial candidates in front of the zero fill; [25 + 3 j ..] position j of L, A, AR, BL, AL through the
+// reference's own getPULeft / Above / AboveRight / BelowLeft / AboveLeft at the part indices deriveLeftRightTopIdx / deriveLeftBottomIdx give: flags (bit 0: a CU came back, is inter and holds a vector, refIdx >= 0; bit 1: it is the
+// queried CU itself), mvx, mvy (zero without bit 0).
+static int g_mc_level = -1;
+static Encoder* g_mc_encoder = nullptr;
+
+static void mc_fill(TComDataCU* ctu, UInt z0, UInt count, int depth, PartSize ps, PredMode pm, UChar dir, const TComMv& mv, SChar refIdx)
+{
+  const UChar size = (UChar)(64 >> depth);
+  for (UInt z = z0; z < z0 + count; z++) {
+    ctu->m_puhDepth[z] = (UChar)depth; ctu->m_puhWidth[z] = size; ctu->m_puhHeight[z] = size;
+    ctu->m_pePartSize[z] = (SChar)ps; ctu->m_pePredMode[z] = (SChar)pm; ctu->m_puhInterDir[z] = dir;
+    ctu->m_acCUMvField[REF_PIC_LIST_0].m_pcMv[z] = mv; ctu->m_acCUMvField[REF_PIC_LIST_0].m_piRefIdx[z] = refIdx;
+    ctu->m_acCUMvField[REF_PIC_LIST_1].m_pcMv[z] = TComMv(0, 0); ctu->m_acCUMvField[REF_PIC_LIST_1].m_piRefIdx[z] = NOT_VALID;
+  }
+}
+
+int href_mc_set_field(int width, int height, int level, const int16_t* mv /* numCtus * 4^level * 2 */, const uint8_t* inter /* numCtus * 4^level */)
+{
+  if ((width % 8) || (height % 8) || width < 64 || height < 64 || level < 0 || level > 3 || !mv || !inter) return -1;
+  Encoder* e = get_encoder(width, height, 8);
+  if (!e->pic1) { e->pic1 = new TComPic(); e->pic1->create(e->sps, e->pps, true, true); }
+  e->pps.setLog2ParallelMergeLevelMinus2(0);
+  e->pic = e->pic1;              // the reference picture: a slice of its own at POC 0
+  init_slice(*e, 32);
+  e->pic = e->pic0;
+  init_slice(*e, 32);
+  TComSlice* s = e->pic->getSlice(0);
+  s->setPOC(1); s->setSliceType(P_SLICE); s->setNalUnitType(NAL_UNIT_CODED_SLICE_TRAIL_R);
+  s->setNumRefIdx(REF_PIC_LIST_0, 1); s->setNumRefIdx(REF_PIC_LIST_1, 0);
+  s->setRefPic(e->pic1, REF_PIC_LIST_0, 0);
+  s->setRefPOCList(); s->setList1IdxToList0Idx();
+  s->setEnableTMVPFlag(false); s->setColFromL0Flag(true); s->setColRefIdx(0);
+  s->setMaxNumMergeCand(5);
+  const int n = 1 << level, size = 64 >> level, cw = (width + 63) / 64;
+  const UInt count = 256u >> (2 * level);
+  for (int c = 0; c < (int)e->pic->getNumberOfCtusInFrame(); c++) {
+    TComDataCU* ctu = e->pic->getCtu(c);
+    ctu->initCtu(e->pic, c);
+    for (int by = 0; by < n; by++)
+      for (int bx = 0; bx < n; bx++) {
+        const int i = (c * n + by) * n + bx;
+        const int x = (c % cw) * 64 + bx * size, y = (c / cw) * 64 + by * size;
+        const bool is_inter = inter[i] && x + size <= width && y + size <= height;
+        const UInt z0 = g_auiRasterToZscan[(by * size / 4) * 16 + bx * size / 4];
+        if (is_inter) mc_fill(ctu, z0, count, level, SIZE_2Nx2N, MODE_INTER, 1, TComMv(mv[2 * i], mv[2 * i + 1]), 0);
+        else mc_fill(ctu, z0, count, level, SIZE_2Nx2N, MODE_INTRA, 0, TComMv(0, 0), NOT_VALID);
+      }
+  }
+  g_mc_level = level; g_mc_encoder = e;
+  return 0;
+}
+
+int href_mc_query(int width, int height, int nq, const int32_t* queries /* ctu, cu, PartSize, part, part 0 set, p0x, p0y, 0 per query */, int16_t* out /* 40 per query */)
+{
+  Encoder* e = get_encoder(width, height, 8);
+  if (e != g_mc_encoder || g_mc_level < 0 || !queries || !out) return -3;
+  const int level = g_mc_level, n = 1 << level, size = 64 >> level, cw = (width + 63) / 64;
+  const UInt count = 256u >> (2 * level);
+  for (int q = 0; q < nq; q++) {
+    const int32_t* k = queries + 8 * q;
+    int16_t* o = out + 40 * q;
+    std::memset(o, 0, 40 * sizeof(int16_t));
+    const int c = k[0], cu = k[1], ps = k[2], part = k[3];
+    const bool two = ps == SIZE_2NxN || ps == SIZE_Nx2N || (ps >= SIZE_2NxnU && ps <= SIZE_nRx2N);
+    if (c < 0 || c >= (int)e->pic->getNumberOfCtusInFrame() || cu < 0 || cu >= n * n || !(ps == SIZE_2Nx2N || two) || part < 0 || part > (two ? 1 : 0)) return -1;
+    if (ps >= SIZE_2NxnU && size < 16) return -1;
+    const int bx = cu % n, by = cu / n;
+    if ((c % cw) * 64 + (bx + 1) * size > width || (c / cw) * 64 + (by + 1) * size > height) return -1;
+    TComDataCU* ctu = e->pic->getCtu(c);
+    const UInt z0 = g_auiRasterToZscan[(by * size / 4) * 16 + bx * size / 4];
+    // what the call changes: the CU is uniform (2Nx2N), so its first partition says it all
+    const SChar pm0 = ctu->m_pePredMode[z0];
+    const UChar dir0 = ctu->m_puhInterDir[z0];
+    const TComMv mv0 = ctu->m_acCUMvField[REF_PIC_LIST_0].m_pcMv[z0];
+    const SChar ref0 = ctu->m_acCUMvField[REF_PIC_LIST_0].m_piRefIdx[z0];
+    mc_fill(ctu, z0, count, level, PartSize(ps), MODE_INTER, 0, TComMv(0, 0), NOT_VALID);
+    {
+      TComDataCU sub;
+      sub.copySubCU(ctu, z0);
+      sub.m_uiNumPartition = count;
+      if (part == 1 && k[4]) {
+        Int xP, yP, w, h;
+        sub.getPartPosition(0, xP, yP, w, h);
+        const int x0 = xP - (int)ctu->getCUPelX(), y0 = yP - (int)ctu->getCUPelY();
+        for (int y = y0; y < y0 + h; y += 4)
+          for (int x = x0; x < x0 + w; x += 4) {
+            const UInt z = g_auiRasterToZscan[(y / 4) * 16 + x / 4];
+            ctu->m_acCUMvField[REF_PIC_LIST_0].m_pcMv[z] = TComMv((Short)k[5], (Short)k[6]);
+            ctu->m_acCUMvField[REF_PIC_LIST_0].m_piRefIdx[z] = 0;
+            ctu->m_puhInterDir[z] = 1;
+          }
+      }
+      UInt partAddr = 0;
+      Int w = 0, h = 0;
+      sub.getPartIndexAndSize((UInt)part, partAddr, w, h);
+      AMVPInfo info;
+      sub.fillMvpCand((UInt)part, partAddr, REF_PIC_LIST_0, 0, &info);
+      if (info.iN != 2) return -4;
+      o[0] = info.m_acMvCand[0].getHor(); o[1] = info.m_acMvCand[0].getVer(); o[2] = info.m_acMvCand[1].getHor(); o[3] = info.m_acMvCand[1].getVer();
+      TComMvField fields[2 * MRG_MAX_NUM_CANDS];
+      UChar dirs[MRG_MAX_NUM_CANDS] = { 0 };
+      Int num = -1;
+      sub.getInterMergeCandidates(partAddr, (UInt)part, fields, dirs, num);
+      for (int i = 0; i < 5; i++) {
+        o[4 + 4 * i] = fields[2 * i].getHor(); o[5 + 4 * i] = fields[2 * i].getVer(); o[6 + 4 * i] = dirs[i]; o[7 + 4 * i] = (int16_t)fields[2 * i].getRefIdx();
+      }
+      // the number of spatial candidates, from the function's own early return: asked for candidate i alone (mrgCandIdx = i) it returns as soon as spatial
+      // candidate i is written and leaves the entries behind it at refIdx NOT_VALID; where fewer than i + 1 spatial candidates exist it runs on to the fill
+      int spatial = 0;
+      for (int i = 0; i < 4; i++) {
+        TComMvField f2[2 * MRG_MAX_NUM_CANDS];
+        UChar d2[MRG_MAX_NUM_CANDS] = { 0 };
+        Int n2 = -1;
+        sub.getInterMergeCandidates(partAddr, (UInt)part, f2, d2, n2, i);
+        if (f2[2 * 4].getRefIdx() < 0) spatial = i + 1;
+      }
+      o[24] = (int16_t)(num + 16 * spatial);
+      UInt lt, rt, lb;
+      sub.deriveLeftRightTopIdx((UInt)part, lt, rt);
+      sub.deriveLeftBottomIdx((UInt)part, lb);
+      for (int j = 0; j < 5; j++) {
+        UInt idx = 0;
+        const TComDataCU* nb = j == 0 ? sub.getPULeft(idx, lb) : j == 1 ? sub.getPUAbove(idx, rt) : j == 2 ? sub.getPUAboveRight(idx, rt)
+                             : j == 3 ? sub.getPUBelowLeft(idx, lb) : sub.getPUAboveLeft(idx, lt);
+        if (nb && nb->isInter(idx) && nb->getCUMvField(REF_PIC_LIST_0)->getRefIdx(idx) >= 0) {
+          const TComMv& m = nb->getCUMvField(REF_PIC_LIST_0)->getMv(idx);
+          o[25 + 3 * j] = 1; o[26 + 3 * j] = m.getHor(); o[27 + 3 * j] = m.getVer();
+        }
+        if (nb == &sub) o[25 + 3 * j] |= 2;
+      }
+    }
+    mc_fill(ctu, z0, count, level, SIZE_2Nx2N, PredMode(pm0), dir0, mv0, ref0);
+  }
+  return nq;
+}
+
+// ---- the bit side of the re-pricing: TComRdCost::getCost(b) (TComRdCost.h:165) for b = 0..66 at the motion lambda a P slice of the harness selects --
+// init_slice's setUpLambda, then selectMotionLambda(true, 0, false) as xCheckBestMVP (TEncSearch.cpp:3566-3615) -- for every QP 0..51; and
+// getBitsOfVectorWithPredictor (TComRdCost.h:170-174) at cost scale 0 for nv (vector, predictor) pairs.
+int href_mv_bit_tables(int width, int height, uint32_t* cost /* 52 * 67 */, int nv, const int32_t* pairs /* vx, vy, px, py */, uint32_t* bits /* nv */)
+{
+  Encoder* e = get_encoder(width, height, 8);
+  for (int qp = 0; qp < 52; qp++) {
+    init_slice(*e, qp);
+    e->pic->getSlice(0)->setSliceType(P_SLICE);
+    e->rd.selectMotionLambda(true, 0, false);
+    for (int b = 0; b < 67; b++) cost[qp * 67 + b] = (uint32_t)e->rd.getCost((UInt)b);
+  }
+  e->rd.setCostScale(0);
+  for (int i = 0; i < nv; i++) {
+    TComMv p((Short)pairs[4 * i + 2], (Short)pairs[4 * i + 3]);
+    e->rd.setPredictor(p);
+    bits[i] = e->rd.getBitsOfVectorWithPredictor(pairs[4 * i], pairs[4 * i + 1]);
+  }
+  g_mc_level = -1;               // init_slice replaced the slice the field was set on
+  return 0;
+}
+
 // md5 (16 bytes) of the slice-data bytes written by the reference's encodeSlice in the last href_rdo_encode_frame* call of that geometry
 // (FHREF_ENCODE_SLICE=1); -1 when there is none
 int href_slice_md5(int width, int height, int bit_depth, unsigned char* digest16)
