@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libfasthevc_hip.so")
-SOURCES = ["fhevc_api.hip", "fhevc_motion_api.hip", "fhevc_weights.hip", "fhevc_host.hip", "k_cnn.hip", "k_hadamard.hip", "k_firstpass.hip", "k_firstpass4.hip", "k_preanalyze.hip", "k_motion.hip", "k_motion_wide.hip", "k_motion_refine.hip", "k_motion_merge.hip", "k_motion_merge_pu.hip", "k_motion_amvp.hip", "k_motion_skip.hip", "k_motion_refine_pu.hip", "k_motion_pu.hip", "k_motion_pu_small.hip", "k_motion_pu_wide.hip", "k_motion_coarse.hip", "k_p_rule.hip", "k_pu_shape.hip", "k_p_tree.hip", "k_intra_p.hip"]
+SOURCES = ["fhevc_api.hip", "fhevc_motion_api.hip", "fhevc_weights.hip", "fhevc_host.hip", "k_cnn.hip", "k_hadamard.hip", "k_firstpass.hip", "k_firstpass4.hip", "k_preanalyze.hip", "k_motion.hip", "k_motion_wide.hip", "k_motion_refine.hip", "k_motion_merge.hip", "k_motion_merge_pu.hip", "k_motion_amvp.hip", "k_motion_skip.hip", "k_motion_rd.hip", "k_motion_refine_pu.hip", "k_motion_pu.hip", "k_motion_pu_small.hip", "k_motion_pu_wide.hip", "k_motion_coarse.hip", "k_p_rule.hip", "k_pu_shape.hip", "k_p_tree.hip", "k_intra_p.hip"]
 # per-source extra flags: the CNN kernel holds only finite integers in fp32, so the NaN-canonicalising v_max can go
 EXTRA = {"k_cnn.hip": ["-ffinite-math-only", "-fno-signed-zeros"]}
 # -ffp-contract=off: the first-pass cost is compared bit-for-bit with the CPU oracle's double arithmetic

@@ -46,6 +46,7 @@ SYMBOLS = [
     "fhevc_motion_skip", "fhevc_motion_skip_device", "fhevc_p_tree_select_skip", "fhevc_p_tree_select_skip_device",
     "fhevc_motion_amvp", "fhevc_motion_amvp_device", "fhevc_motion_amvp_picture", "fhevc_p_tree_amvp_frame",
     "fhevc_intra_p", "fhevc_intra_p_device", "fhevc_intra_p_picture", "fhevc_p_tree_select_intra", "fhevc_p_tree_select_intra_device", "fhevc_p_tree_intra_frame",
+    "fhevc_motion_rd", "fhevc_motion_rd_device", "fhevc_motion_rd_lambda_q8", "fhevc_p_tree_select_rd", "fhevc_p_tree_select_rd_device",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -102,6 +103,12 @@ MOTION_MERGE_DTYPE = np.dtype([("satd_best", np.uint32), ("cost_best", np.uint32
 MOTION_SKIP_DTYPE = np.dtype([("coef_max", np.uint32), ("level_sum", np.uint32), ("nonzero", np.uint16), ("flags", np.uint8), ("pad", np.uint8),
                               ("mvx", np.int16), ("mvy", np.int16)])
 SKIP_ZERO_PLAIN, SKIP_ZERO_HALF = 1, 2
+# fhevc_motion_rd_node: the RD estimate of a CU node at a vector (flags: the skip record's two bits, RD_TU_SPLIT: some depth-0 TU is split).  cost_rd lies
+# where the merge and the selection records keep cost_best, flags where the skip record keeps flags
+MOTION_RD_DTYPE = np.dtype([("dist", np.uint32), ("cost_rd", np.uint32), ("bits", np.uint16), ("flags", np.uint8), ("tu_split", np.uint8),
+                            ("mvx", np.int16), ("mvy", np.int16)])
+RD_SOURCE_MERGE, RD_SOURCE_EXPLICIT = 0, 1
+RD_TU_SPLIT = 4
 # fhevc_motion_mvp: the predictor fhevc_motion_amvp* priced an entry against (src: 0..4 = L, A, AR, BL, AL, 5 = a filled zero; idx = src = 255: no price)
 MOTION_MVP_DTYPE = np.dtype([("px", np.int16), ("py", np.int16), ("idx", np.uint8), ("num_spatial", np.uint8), ("src", np.uint8), ("bits", np.uint8)])
 MVP_BIT_COSTS = 67
@@ -258,6 +265,12 @@ def load_library(path=None):
     lib.fhevc_motion_skip_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     lib.fhevc_p_tree_select_skip.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp]
     lib.fhevc_p_tree_select_skip_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp, vp]
+    lib.fhevc_motion_rd.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.fhevc_motion_rd_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.fhevc_motion_rd_lambda_q8.argtypes = [C.c_int]
+    lib.fhevc_motion_rd_lambda_q8.restype = C.c_uint32
+    lib.fhevc_p_tree_select_rd.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp]
+    lib.fhevc_p_tree_select_rd_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp, vp]
     lib.fhevc_p_tree_merge_pu_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), vp, vp, vp, vp]
     lib.fhevc_motion_amvp.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.fhevc_motion_amvp_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -399,6 +412,26 @@ def p_tree_select_skip(shapes, merge, skip, skip_mask, width, height, rule=None,
                                           dmax[c].ctypes.data, tree[c].ctypes.data if with_tree else None)
         if rc != OK:
             raise FastHevcError(rc, "fhevc_p_tree_select_skip")
+    return (dmin, dmax, tree) if with_tree else (dmin, dmax)
+
+
+def p_tree_select_rd(rd_explicit, rd_merge, skip_mask, width, height, rule=None, with_tree=False):
+    """p_tree_select_skip on RD records [numCtus, 85] MOTION_RD_DTYPE: rd_explicit's cost_rd stands for the selection's cost_best, rd_merge's cost_rd for the
+    merge cost and rd_merge's flags for the skip flags"""
+    lib = load_library()
+    rule = rule if rule is not None else p_tree_rule_default()
+    rd_explicit, rd_merge = np.ascontiguousarray(rd_explicit), np.ascontiguousarray(rd_merge)
+    assert rd_explicit.dtype.itemsize == 16 and rd_merge.dtype.itemsize == 16 and rd_explicit.shape == rd_merge.shape
+    cw = (width + 63) // 64
+    n = rd_explicit.shape[0]
+    dmin, dmax = np.zeros((n, 256), np.uint8), np.zeros((n, 256), np.uint8)
+    tree = np.zeros((n, NODES_PER_CTU), TREE_DTYPE) if with_tree else None
+    for c in range(n):
+        vw, vh = min(64, width - (c % cw) * 64), min(64, height - (c // cw) * 64)
+        rc = lib.fhevc_p_tree_select_rd(rd_explicit[c].ctypes.data, rd_merge[c].ctypes.data, skip_mask, vw, vh, C.byref(rule), dmin[c].ctypes.data,
+                                        dmax[c].ctypes.data, tree[c].ctypes.data if with_tree else None)
+        if rc != OK:
+            raise FastHevcError(rc, "fhevc_p_tree_select_rd")
     return (dmin, dmax, tree) if with_tree else (dmin, dmax)
 
 
@@ -777,6 +810,28 @@ class Context:
         self._check(self.lib.fhevc_motion_skip_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range,
                                                       d_merge, d_out, stream))
 
+    def motion_rd(self, cur_plane, ref_plane, records, source, mvp=None, origin=0, stride=None, qp=32, max_range=4):
+        """config 4: the RD estimate of every CU node at the vector of its record [numCtus, 85] -- source RD_SOURCE_MERGE: MOTION_MERGE_DTYPE, RD_SOURCE_EXPLICIT:
+        MOTION_QPEL_DTYPE, with the re-pricing's predictor records mvp [numCtus, 85] MOTION_MVP_DTYPE or None -> [numCtus, 85] MOTION_RD_DTYPE"""
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
+        records = np.ascontiguousarray(records).reshape(-1)
+        assert records.dtype.itemsize == 16 and records.size == self.num_ctus * NODES_PER_CTU
+        if mvp is not None:
+            mvp = np.ascontiguousarray(mvp).reshape(-1)
+            assert mvp.dtype.itemsize == 8 and mvp.size == records.size
+        out = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_RD_DTYPE)
+        self._check(self.lib.fhevc_motion_rd(self.h, cur, ref, stride, qp, max_range, source, records.ctypes.data, mvp.ctypes.data if mvp is not None else None,
+                                             out.ctypes.data))
+        return out.reshape(self.num_ctus, NODES_PER_CTU)
+
+    def motion_rd_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, source, d_in, d_out, d_mvp=None, rows=None, stream=None, qp=32, max_range=4):
+        """frames 1.. of the batch, each predicted from the frame before it at the vectors of d_in (85 records of `source`'s kind per CTU, compact over the
+        rows; d_mvp: their predictor records or None), transformed, quantised and rebuilt at qp; d_out: (num_frames - 1) * band CTUs * 85 RD records (16 B).
+        Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_motion_rd_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range, source,
+                                                    d_in, d_mvp, d_out, stream))
+
     def motion_merge_pu(self, cur_plane, ref_plane, refined, origin=0, stride=None, qp=32, max_range=4, with_pus=True, with_small=True):
         """config 4: the cheapest merge candidate of every PU from the refined square nodes [numCtus, 85] (MOTION_QPEL_DTYPE; only cost_best, mvx, mvy are
         read) -> ([numCtus, 124], [numCtus, 384]) MOTION_MERGE_DTYPE in the orders of motion_pu_index / motion_pu_small_index; None for a family not asked for"""
@@ -1017,6 +1072,13 @@ class Context:
         rb, re = rows if rows is not None else (0, self.ctus_y)
         self._check(self.lib.fhevc_p_tree_select_skip_device(self.h, d_shapes, d_merge, d_skip, skip_mask, num_pictures, rb, re,
                                                              C.byref(rule) if rule is not None else None, d_depth_min, d_depth_max, d_tree, stream))
+
+    def p_tree_select_rd_device(self, d_rd_explicit, d_rd_merge, skip_mask, num_pictures, d_depth_min=None, d_depth_max=None, d_tree=None, rows=None, stream=None,
+                                rule=None):
+        """p_tree_select_skip_device on the RD records of two motion_rd_device launches (85 per CTU, compact over the same rows).  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_p_tree_select_rd_device(self.h, d_rd_explicit, d_rd_merge, skip_mask, num_pictures, rb, re,
+                                                           C.byref(rule) if rule is not None else None, d_depth_min, d_depth_max, d_tree, stream))
 
     def p_tree_select_intra_device(self, d_shapes, d_merge, d_skip, skip_mask, d_intra, num_pictures, d_depth_min=None, d_depth_max=None, d_tree=None, rows=None,
                                    stream=None, rule=None):

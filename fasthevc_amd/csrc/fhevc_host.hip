@@ -450,6 +450,17 @@ int fhevc_p_tree_select_skip(const fhevc_pu_shape_node* shapes, const fhevc_moti
   return p_tree_select(shapes, merge, valid_w, valid_h, rule, depth_min, depth_max, tree, skip, skip_mask);
 }
 
+// ... on RD records, which carry cost_rd where the selection and the merge records keep cost_best and flags where the skip record keeps flags
+int fhevc_p_tree_select_rd(const fhevc_motion_rd_node* rd_explicit, const fhevc_motion_rd_node* rd_merge, int skip_mask, int valid_w, int valid_h,
+                           const fhevc_p_tree_rule* rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_p_tree_node* tree)
+{
+  static_assert(sizeof(fhevc_motion_rd_node) == 16 && offsetof(fhevc_motion_rd_node, cost_rd) == offsetof(fhevc_pu_shape_node, cost_best) &&
+                offsetof(fhevc_motion_rd_node, cost_rd) == offsetof(fhevc_motion_merge_node, cost_best) &&
+                offsetof(fhevc_motion_rd_node, flags) == offsetof(fhevc_motion_skip_node, flags), "RD record layout");
+  return fhevc_p_tree_select_skip(reinterpret_cast<const fhevc_pu_shape_node*>(rd_explicit), reinterpret_cast<const fhevc_motion_merge_node*>(rd_merge),
+                                  reinterpret_cast<const fhevc_motion_skip_node*>(rd_merge), skip_mask, valid_w, valid_h, rule, depth_min, depth_max, tree);
+}
+
 int fhevc_p_tree_select_intra(const fhevc_pu_shape_node* shapes, const fhevc_motion_merge_node* merge, const fhevc_motion_skip_node* skip, int skip_mask,
                               const fhevc_intra_p_node* intra, int valid_w, int valid_h, const fhevc_p_tree_rule* rule, uint8_t* depth_min, uint8_t* depth_max,
                               fhevc_p_tree_node* tree)

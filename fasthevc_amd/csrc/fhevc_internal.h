@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 
 #define FHEVC_CTU 64
 
@@ -315,6 +316,39 @@ inline FhevcSkipQuant fhevc_skip_quant(int qp, int bit_depth)
 // fr, max_range as fhevc_launch_motion_merge; d_merge: (num_frames - 1) * band CTUs * 85 merge records of which cost_best, mvx and mvy are read; d_out: as many
 hipError_t fhevc_launch_motion_skip(const FhevcFrames& fr, int max_range, const FhevcSkipQuant& q, const FhevcMotionMergeNode* d_merge, FhevcMotionSkipNode* d_out,
                                     int num_cus, hipStream_t stream);
+
+// ---- the RD estimate per CU node at a vector: transform, quantiser, rebuilt block, one TU split (k_motion_rd.hip; config 4) --------------------------
+// dist / cost_rd / flags lie where the merge and selection records keep cost_best (dword 1) and the skip record keeps flags (byte 10)
+struct FhevcMotionRdNode { uint32_t dist, cost_rd; uint16_t bits; uint8_t flags, tu_split; int16_t mvx, mvy; };
+static_assert(sizeof(FhevcMotionRdNode) == 16, "RD record: 16 bytes without padding");
+// lam_q8 = floor(lambda * 256 + 0.5), lambda = 0.57 * 2^((qp - 12) / 3)
+inline uint32_t fhevc_rd_lambda_q8(int qp) { return (uint32_t)std::floor(0.57 * std::pow(2.0, (qp - 12) / 3.0) * 256.0 + 0.5); }
+// HM's quantiser and dequantiser without scaling lists per TU size 4, 8, 16, 32 (index log2 N - 2), computed on the host:
+// level = (|c| * scale + add) >> qbits; c^ = (level * inv_scale + inv_add) >> inv_shift, where inv_scale holds the left shift of a negative rightShift
+struct FhevcRdQuant { uint32_t scale, lam_q8, qbits[4], add_plain[4], add_half[4], inv_scale[4], inv_add[4], inv_shift[4]; };
+inline FhevcRdQuant fhevc_rd_quant(int qp, int bit_depth)
+{
+  static const uint32_t scales[6] = { 26214, 23302, 20560, 18396, 16384, 14564 };   // g_quantScales
+  static const uint32_t inv_scales[6] = { 40, 45, 51, 57, 64, 72 };                 // g_invQuantScales
+  const int qpp = qp + 6 * (bit_depth - 8);
+  FhevcRdQuant q;
+  q.scale = scales[qpp % 6];
+  q.lam_q8 = fhevc_rd_lambda_q8(qp);
+  for (int i = 0; i < 4; ++i) {
+    q.qbits[i] = (uint32_t)(14 + qpp / 6 + (15 - bit_depth - (i + 2)));     // 16 .. 27
+    q.add_plain[i] = 85u << (q.qbits[i] - 9);
+    q.add_half[i] = 1u << (q.qbits[i] - 1);
+    const int right = 6 - (15 - bit_depth - (i + 2) + qpp / 6);              // xDeQuant's rightShift = log2 N - 1 - qp / 6: -7 .. 4
+    q.inv_scale[i] = inv_scales[qpp % 6] << (right < 0 ? -right : 0);
+    q.inv_add[i] = right > 0 ? 1u << (right - 1) : 0u;
+    q.inv_shift[i] = (uint32_t)(right > 0 ? right : 0);
+  }
+  return q;
+}
+// fr, max_range as fhevc_launch_motion_skip; source 0: d_in are merge records, 1: refined (or re-priced) nodes, d_mvp (may be null) their predictor records;
+// d_in, d_out: (num_frames - 1) * band CTUs * 85 records
+hipError_t fhevc_launch_motion_rd(const FhevcFrames& fr, int max_range, const FhevcRdQuant& q, int source, const void* d_in, const FhevcMotionMvp* d_mvp,
+                                  FhevcMotionRdNode* d_out, int num_cus, hipStream_t stream);
 
 // ---- ... and of the PUs' vectors (k_motion_refine_pu.hip; config 4) --------------------------------------------------
 // fr, max_range (1 .. FHEVC_MOTION_WIDE_MAX_RANGE: up to FHEVC_MOTION_MAX_RANGE the MR = 8 layout, above it the MR = 64 layout with its window in dynamic LDS),

@@ -50,6 +50,7 @@ template <> struct Kernel<fhevc_pu_shape_node> { using T = FhevcPuShapeNode; };
 template <> struct Kernel<fhevc_p_tree_node> { using T = FhevcPTreeNode; };
 template <> struct Kernel<fhevc_motion_mvp> { using T = FhevcMotionMvp; };
 template <> struct Kernel<fhevc_intra_p_node> { using T = FhevcIntraPNode; };
+template <> struct Kernel<fhevc_motion_rd_node> { using T = FhevcMotionRdNode; };
 template <class P> typename Kernel<P>::T* kn(P* p) { return reinterpret_cast<typename Kernel<P>::T*>(p); }
 template <class P> const typename Kernel<P>::T* kn(const P* p) { return reinterpret_cast<const typename Kernel<P>::T*>(p); }
 static_assert(sizeof(fhevc_motion_node) == 16 && sizeof(FhevcMotionNode) == 16 && sizeof(fhevc_motion_qpel_node) == 16 && sizeof(FhevcMotionQpelNode) == 16, "node layouts");
@@ -59,6 +60,10 @@ static_assert(sizeof(fhevc_motion_skip_node) == 16 && offsetof(fhevc_motion_skip
 static_assert(sizeof(fhevc_intra_p_node) == 16 && offsetof(fhevc_intra_p_node, satd_best) == 0 && offsetof(fhevc_intra_p_node, cost_best) == 4 &&
               offsetof(fhevc_intra_p_node, modes) == 8 && offsetof(fhevc_intra_p_node, part) == 12 && offsetof(fhevc_intra_p_node, pad) == 13 &&
               sizeof(FhevcIntraPNode) == 16 && offsetof(FhevcIntraPNode, cost_best) == 4 && offsetof(FhevcIntraPNode, part) == 12, "intra record layout");
+// the RD record is read by the tree kernels as a selection record, a merge record and a skip record: cost_rd where they keep cost_best, flags where flags is
+static_assert(sizeof(fhevc_motion_rd_node) == 16 && offsetof(fhevc_motion_rd_node, cost_rd) == 4 && offsetof(fhevc_motion_rd_node, flags) == 10 &&
+              offsetof(fhevc_motion_rd_node, mvx) == 12 && offsetof(FhevcMotionRdNode, cost_rd) == 4 && offsetof(FhevcMotionRdNode, flags) == 10 &&
+              offsetof(fhevc_pu_shape_node, cost_best) == 4 && offsetof(fhevc_motion_merge_node, cost_best) == 4, "RD record layout");
 static_assert(sizeof(fhevc_node_cost) == 16 && offsetof(fhevc_node_cost, satd) == 0 && offsetof(fhevc_node_cost, mode) == 4, "first-pass record layout");
 static_assert(FHEVC_PUS_PER_CTU == FHEVC_PUS && FHEVC_PUS_SMALL_PER_CTU == FHEVC_PUS_SMALL, "PU counts");
 static_assert(sizeof(fhevc_motion_mvp) == 8 && offsetof(fhevc_motion_mvp, idx) == 4 && offsetof(fhevc_motion_mvp, bits) == 7 && offsetof(FhevcMotionMvp, bits) == 7,
@@ -122,7 +127,7 @@ int device_form(fhevc_ctx* c, bool args_ok, const char* bad_args, const Batch& b
 //
 // The timing slots (fhevc_kernel_timing) of the launches below: 4 fhevc_motion_search, 5 the P rule, 7 fhevc_motion_refine, 8 / 9 the searches of the PUs / the
 // small PUs, 10 fhevc_motion_refine_pu, 11 / 12 the wide search / refinement, 13 the partition sizes, 15 the centres and everything centred, 17 the tree, 19 the merge stage,
-// 21 the merge stage per PU, 23 the zero-residual test, 25 the re-pricing against neighbour predictors, 27 the intra stage
+// 21 the merge stage per PU, 23 the zero-residual test, 25 the re-pricing against neighbour predictors, 27 the intra stage, 29 the RD estimate
 struct Family { int per_ctu; FhevcMotionNode* fhevc_ctx::*found; FhevcMotionQpelNode* fhevc_ctx::*refined; };
 constexpr Family kNodes = { FHEVC_NODES, &fhevc_ctx::d_motion, &fhevc_ctx::d_qpel }, kPus = { FHEVC_PUS, &fhevc_ctx::d_motion_pu, &fhevc_ctx::d_qpel_pu },
                  kSmall = { FHEVC_PUS_SMALL, &fhevc_ctx::d_motion_pu_small, &fhevc_ctx::d_qpel_pu_small }, kCentres = { 1, &fhevc_ctx::d_centres, nullptr };
@@ -519,6 +524,41 @@ int fhevc_motion_skip(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_
   return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_skip_device, qp, max_range, d_merge, d_out, c->stream); });
 }
 
+// ---- the RD estimate per CU node at its merge or its explicit vector (k_motion_rd.hip) ----
+
+int fhevc_motion_rd_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                           int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, int source, const void* d_in,
+                           const fhevc_motion_mvp* d_mvp, fhevc_motion_rd_node* d_out, void* stream)
+{
+  const Batch b{ d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp };
+  // the quantiser's, the dequantiser's and lambda's numbers travel with the launch: nothing of the context is read or written by it
+  return device_form(c, d_luma && d_in && d_out, "bad RD-stage arguments", b, max_range, FHEVC_MOTION_WIDE_MAX_RANGE, "bad RD-stage arguments (max_range 1..64)",
+                     stream, 29, "fhevc_launch_motion_rd", [&](const FhevcFrames& fr, hipStream_t s) {
+    return fhevc_launch_motion_rd(fr, max_range, fhevc_rd_quant(qp, c->cfg.bit_depth), source, d_in, kn(d_mvp), kn(d_out), c->num_cus, s);
+  }, [&]() -> const char* {
+    if (source != FHEVC_RD_SOURCE_MERGE && source != FHEVC_RD_SOURCE_EXPLICIT) return "bad RD-stage arguments (source 0..1)";
+    if (d_mvp && source == FHEVC_RD_SOURCE_MERGE) return "bad RD-stage arguments (predictor records go with the explicit source)";
+    if (((uintptr_t)d_in | (uintptr_t)d_mvp | (uintptr_t)d_out) & 3) return "bad RD-stage arguments (records are 4-byte aligned)";
+    return (long long)(num_frames - 1) * (ctu_row_end - ctu_row_begin) * c->ctus_x > 0x7FFFFFFFLL ? "more than 2^31 - 1 CTUs" : nullptr;
+  });
+}
+
+int fhevc_motion_rd(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range, int source, const void* in,
+                    const fhevc_motion_mvp* mvp, fhevc_motion_rd_node* out)
+{
+  const bool source_ok = source == FHEVC_RD_SOURCE_EXPLICIT || (source == FHEVC_RD_SOURCE_MERGE && !mvp);
+  const int rc = open_host_form(c, cur_luma && ref_luma && in && out && source_ok, stride_samples, qp, max_range, FHEVC_MOTION_WIDE_MAX_RANGE, "bad RD-stage arguments");
+  if (rc != GO) return rc;
+  HostForm h(c);
+  const size_t bn = h.bytes(kNodes), all = bn + h.bytes(kPus) + h.bytes(kSmall);
+  const void* d_in = h.in(c->d_motion, bn, static_cast<const fhevc_motion_node*>(in), bn);   // 16-byte records of either kind
+  const fhevc_motion_mvp* d_mvp = h.in(c->d_amvp_mvp, all / 2, mvp, bn / 2);                  // the head of the re-pricing's predictor records
+  fhevc_motion_rd_node* d_out = h.out(c->d_qpel, bn, out, bn);                                // no refined nodes in this call: their buffer is dead
+  return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_rd_device, qp, max_range, source, d_in, d_mvp, d_out, c->stream); });
+}
+
+uint32_t fhevc_motion_rd_lambda_q8(int qp) { return fhevc_rd_lambda_q8(qp < 0 ? 0 : (qp > 51 ? 51 : qp)); }
+
 // ---- merge-candidate costs per PU from the refined nodes (k_motion_merge_pu.hip) ----
 
 int fhevc_motion_merge_pu_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
@@ -875,6 +915,16 @@ int fhevc_p_tree_select_skip_device(fhevc_ctx* c, const fhevc_pu_shape_node* d_s
                                     uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream)
 {
   return p_tree_select_on(c, d_shapes, d_merge, true, num_pictures, ctu_row_begin, ctu_row_end, rule, d_depth_min, d_depth_max, d_tree, stream, true, d_skip, skip_mask);
+}
+
+// the skip tree on RD records: cost_rd lies where the selection and the merge records keep cost_best, flags where the skip record keeps flags
+int fhevc_p_tree_select_rd_device(fhevc_ctx* c, const fhevc_motion_rd_node* d_rd_explicit, const fhevc_motion_rd_node* d_rd_merge, int skip_mask, int num_pictures,
+                                  int ctu_row_begin, int ctu_row_end, const fhevc_p_tree_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree,
+                                  void* stream)
+{
+  return fhevc_p_tree_select_skip_device(c, reinterpret_cast<const fhevc_pu_shape_node*>(d_rd_explicit), reinterpret_cast<const fhevc_motion_merge_node*>(d_rd_merge),
+                                         reinterpret_cast<const fhevc_motion_skip_node*>(d_rd_merge), skip_mask, num_pictures, ctu_row_begin, ctu_row_end, rule,
+                                         d_depth_min, d_depth_max, d_tree, stream);
 }
 
 int fhevc_p_tree_select_intra_device(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, const fhevc_motion_merge_node* d_merge, const fhevc_motion_skip_node* d_skip,

@@ -1,0 +1,367 @@
+// k_motion_rd.hip -- the RD estimate per CU node at a vector (config 4: P slices), gfx950 only.
+//
+// Spec in include/fasthevc.h: k_motion_skip.hip's pass carried through to the end.  The residual of fhevc_motion_refine's prediction at the vector a merge
+// record or a refined node holds goes through HM's forward DCT (xTrMxN), its plain quantiser, its dequantiser (xDeQuant) and its inverse DCT (xITrMxN); the
+// rebuilt block gives xGetSSE's distortion, the levels the library's own bit estimate; all of it at two TU sizes, N0 = min(node, 32) and N0 / 2, and per
+// depth-0 TU the cheaper of the two under J = 256 D + lam_q8 bits (TEncSearch.cpp:5117).
+//
+// Mapping: k_motion_skip.hip's.  Workgroup (4 waves) = one CTU at a time over a persistent grid, the window of the refinement in LDS in both layouts, wave =
+// level and lane = one 8x8 tile for the prediction; the lane keeps its tile's residual packed in registers to the end and loads the original again for the squared error (the prediction is their
+// difference).  Once the window is dead, four buffers of 64 rows x 72 shorts (one per level) lie over it, behind them the 32-point matrix (2 048 B: the
+// forward passes read its rows 32 / N k, first N columns) and the four TRANSPOSED matrices (32-, 16-, 8-, 4-point: 2 720 B; a smaller transpose is no
+// sub-block of a larger one), all read at wave-uniform addresses.  One depth = four passes, each "every thread reads its row segment, makes dot products
+// with matrix rows, a barrier, every thread writes": forward rows (written transposed inside the TU, as partialButterfly does), forward columns (quantised,
+// priced, dequantised in registers and written back IN PLACE: the thread of row k then holds horizontal frequency k over the vertical frequencies, which is
+// what partialButterflyInverse's first stage reads), inverse first stage on the transposed matrix (shift 7, clipped, written transposed), inverse second
+// stage (shift 20 - bit depth, clipped, in place).  Then the lane that holds the tile reads its 8x8 of the rebuilt residual and takes the squared error.
+// The residual is rewritten from registers and the same four passes run at N / 2.  Thread mapping per buffer: lane = row; N = 32: wave = (segment, half of
+// the outputs); N = 16: wave = segment; N = 8: segments w and w + 4; N = 4: segments w, w + 4, w + 8, w + 12 -- 16 outputs per thread, buffer and pass.
+// Sums per depth-0 TU (88 per CTU): bits and max |c| through eight-lane exchanges and LDS atomics, the distortion through lane exchanges over the TU's
+// tiles and ONE plain store.  The writer lane of each node makes the choice.  16-bit intermediates are exact: forward as in k_motion_skip.hip, now also at
+// N = 4; the inverse clips to 16 bits by definition, and its accumulations stay below 32 * 32 768 * 90 < 2^31.  The quantiser's and dequantiser's numbers
+// per TU size travel by value.  No scratch, no HBM state between calls.
+#include "fhevc_internal.h"
+#include "k_had8x8.h"
+#include "k_refine_tile.h"
+
+namespace {
+
+constexpr unsigned kRdMark = 0xFFFFFFFFu;
+constexpr int kPitch = 72;                       // shorts per row of a transform buffer
+constexpr int kLevelBuf = 64 * kPitch;           // shorts per level
+constexpr int kTransformShorts = 4 * kLevelBuf;  // 36 864 B
+constexpr int kFwdShorts = 32 * 32;              // the 32-point matrix behind them
+constexpr int kInvShorts = 32 * 32 + 16 * 16 + 8 * 8 + 4 * 4;   // ... and the four transposes behind it
+constexpr int kRowsInFlight = 2;                 // matrix rows the scheduler may fetch ahead of their products
+constexpr int kTus = 88, kAccWords = 5;          // per depth-0 TU: D0, bits0 - 1, sum D1, sum bits1 - 4, max |c| at depth 0
+enum { ROWS = 0, COLS = 1, INV1 = 2, INV2 = 3 };
+
+constexpr int ilog2(int n) { return n <= 1 ? 0 : 1 + ilog2(n >> 1); }
+constexpr int inv_at(int n) { return n == 32 ? 0 : n == 16 ? 1024 : n == 8 ? 1280 : 1344; }   // where the N-point transpose begins, in shorts
+
+// the 32-point matrix of the standard (H.265 8.6.4.2) as packed pairs [k][x / 2], low half = the even column, and the transposes [x][k / 2] of the N-point
+// matrices (its rows 32 / N k, first N columns) at a pitch of N.  Entry m of kCos is the scaled cos(m pi / 64), entry 0 the DC row's 64
+struct RdTables { unsigned fwd[kFwdShorts / 2], inv[kInvShorts / 2]; };
+constexpr int kCos[32] = { 64, 90, 90, 90, 89, 88, 87, 85, 83, 82, 80, 78, 75, 73, 70, 67, 64, 61, 57, 54, 50, 46, 43, 38, 36, 31, 25, 22, 18, 13, 9, 4 };
+constexpr int dct_entry(int k, int x)
+{
+  int a = ((2 * x + 1) * k) % 128;   // the angle in units of pi / 64
+  if (a > 64) a = 128 - a;
+  return a > 32 ? -kCos[64 - a] : kCos[a];
+}
+constexpr unsigned pack2(int lo, int hi) { return ((unsigned)lo & 0xFFFFu) | ((unsigned)hi << 16); }
+constexpr RdTables make_tables()
+{
+  RdTables t{};
+  for (int k = 0; k < 32; ++k)
+    for (int j = 0; j < 16; ++j) t.fwd[k * 16 + j] = pack2(dct_entry(k, 2 * j), dct_entry(k, 2 * j + 1));
+  for (int n = 4; n <= 32; n *= 2)
+    for (int x = 0; x < n; ++x)
+      for (int j = 0; j < n / 2; ++j) t.inv[(inv_at(n) + x * n) / 2 + j] = pack2(dct_entry(2 * j * (32 / n), x), dct_entry((2 * j + 1) * (32 / n), x));
+  return t;
+}
+__constant__ RdTables kRdTables = make_tables();
+
+// which units of an N-point pass over one buffer a thread has: UNITS segments of its row, NK outputs of each from k0 on -- 16 outputs in all
+template <int N> struct TuMap {
+  static constexpr int NK = N < 16 ? N : 16, UNITS = 16 / NK;
+  __device__ __forceinline__ static int seg(int wave, int u) { return N == 32 ? (wave & 1) : wave + 4 * u; }
+  __device__ __forceinline__ static int k0(int wave) { return N == 32 ? (wave >> 1) * 16 : 0; }
+};
+
+// the row segment of N shorts at buf[row][x0 ..] as N / 2 packed pairs: 16-byte reads (N = 4: one of 8 bytes); x0 is a multiple of N, the pitch of 8
+template <int N>
+__device__ __forceinline__ void load_segment(const short* buf, int row, int x0, unsigned (&x)[N / 2])
+{
+  if constexpr (N == 4) {
+    const uint2 q = *reinterpret_cast<const uint2*>(buf + row * kPitch + x0);
+    x[0] = q.x; x[1] = q.y;
+  } else {
+    const uint4* p = reinterpret_cast<const uint4*>(buf + row * kPitch + x0);
+#pragma unroll
+    for (int i = 0; i < N / 8; ++i) {
+      const uint4 q = p[i];
+      x[4 * i] = q.x; x[4 * i + 1] = q.y; x[4 * i + 2] = q.z; x[4 * i + 3] = q.w;
+    }
+  }
+}
+
+// a + the product of a segment with the matrix row at m (wave-uniform; LDS)
+template <int N>
+__device__ __forceinline__ int dot_row(const short* m, const unsigned (&x)[N / 2], int a)
+{
+  if constexpr (N == 4) {
+    const uint2 q = *reinterpret_cast<const uint2*>(m);
+    a = dot2(x[0], q.x, a); a = dot2(x[1], q.y, a);
+  } else {
+    const uint4* p = reinterpret_cast<const uint4*>(m);
+#pragma unroll
+    for (int i = 0; i < N / 8; ++i) {
+      const uint4 q = p[i];
+      a = dot2(x[4 * i], q.x, a); a = dot2(x[4 * i + 1], q.y, a); a = dot2(x[4 * i + 2], q.z, a); a = dot2(x[4 * i + 3], q.w, a);
+    }
+  }
+  return a;
+}
+
+__device__ __forceinline__ int clip16(int v) { return min(max(v, -32768), 32767); }
+
+// eight neighbouring lanes (rows that share every depth-0 TU) into one, then that lane into the TU's sums
+template <int DEPTH>
+__device__ __forceinline__ void rd_commit(unsigned* acc, int tu, int lane, unsigned bits, unsigned top)
+{
+#pragma unroll
+  for (int d = 1; d < 8; d <<= 1) {
+    bits += (unsigned)__shfl_xor((int)bits, d);
+    if (DEPTH == 0) top = max(top, (unsigned)__shfl_xor((int)top, d));
+  }
+  if ((lane & 7) == 0) {
+    atomicAdd(&acc[kAccWords * tu + 1 + 2 * DEPTH], bits);
+    if (DEPTH == 0) atomicMax(&acc[kAccWords * tu + 4], top);
+  }
+}
+
+// one pass over one buffer at TU size N: the thread's 16 outputs, packed two to a register until the barrier.  COLS quantises, prices and dequantises them
+// and commits the sums of every unit to its depth-0 TU: tu0 = the buffer's first, l0 = log2 of the buffer's depth-0 TU size
+template <int N, int STAGE, int DEPTH>
+__device__ __forceinline__ void tu_pass(const short* tables, const short* buf, int lane, int wave, int bd, const FhevcRdQuant& Q, unsigned* acc, int tu0, int l0,
+                                        unsigned (&t)[8])
+{
+  using M = TuMap<N>;
+  constexpr int LN = ilog2(N), QI = LN - 2;
+  const short* mat = STAGE <= COLS ? tables : tables + kFwdShorts + inv_at(N);
+  constexpr int pitch = STAGE <= COLS ? (32 / N) * 32 : N;
+  const int shift = STAGE == ROWS ? LN + bd - 9 : STAGE == COLS ? LN + 6 : STAGE == INV1 ? 7 : 20 - bd;
+  const int k0 = M::k0(wave);
+#pragma unroll
+  for (int u = 0; u < M::UNITS; ++u) {
+    const int seg = M::seg(wave, u);
+    unsigned x[N / 2];
+    load_segment<N>(buf, lane, seg * N, x);
+    unsigned bits = 0, top = 0;
+#pragma unroll
+    for (int i = 0; i < M::NK; ++i) {
+      int a = dot_row<N>(mat + (k0 + i) * pitch, x, 1 << (shift - 1)) >> shift;
+      if (STAGE == COLS) {
+        const unsigned mag = (unsigned)abs(a);
+        const unsigned lv = min((mag * Q.scale + Q.add_plain[QI]) >> Q.qbits[QI], 32767u);
+        bits += lv != 0u ? 3u + 2u * (31u - (unsigned)__builtin_clz(lv)) : 0u;
+        top = max(top, mag);
+        const int sl = a < 0 ? -(int)lv : (int)lv;
+        a = clip16((sl * (int)Q.inv_scale[QI] + (int)Q.inv_add[QI]) >> Q.inv_shift[QI]);
+      }
+      if (STAGE >= INV1) a = clip16(a);
+      const int o = u * M::NK + i;
+      if (o & 1) t[o >> 1] |= (unsigned)a << 16;
+      else t[o >> 1] = (unsigned)a & 0xFFFFu;
+      if ((i & (kRowsInFlight - 1)) == kRowsInFlight - 1) __builtin_amdgcn_sched_barrier(0);   // or every matrix row of the pass is fetched ahead, into registers
+    }
+    if (STAGE == COLS) rd_commit<DEPTH>(acc, tu0 + ((lane >> l0) << (6 - l0)) + ((seg * N) >> l0), lane, bits, top);
+  }
+}
+
+// ... written behind the barrier: ROWS and INV1 transposed inside the TU (output k of input row j at [k][j]), COLS and INV2 into the row they were read from
+template <int N, int STAGE>
+__device__ __forceinline__ void tu_store(short* buf, int lane, int wave, const unsigned (&t)[8])
+{
+  using M = TuMap<N>;
+  const int k0 = M::k0(wave);
+#pragma unroll
+  for (int u = 0; u < M::UNITS; ++u) {
+    const int seg = M::seg(wave, u);
+    if (STAGE == ROWS || STAGE == INV1) {
+      short* dst = buf + ((lane & ~(N - 1)) + k0) * kPitch + seg * N + (lane & (N - 1));
+#pragma unroll
+      for (int i = 0; i < M::NK; ++i) {
+        const int o = u * M::NK + i;
+        dst[i * kPitch] = (short)(o & 1 ? t[o >> 1] >> 16 : t[o >> 1] & 0xFFFFu);
+      }
+    } else {
+      short* dst = buf + lane * kPitch + seg * N + k0;   // a multiple of NK shorts
+      constexpr int R = M::NK / 2;                       // registers of this unit
+      if constexpr (M::NK == 4) *reinterpret_cast<uint2*>(dst) = make_uint2(t[u * R], t[u * R + 1]);
+      else {
+#pragma unroll
+        for (int i = 0; i < R / 4; ++i) reinterpret_cast<uint4*>(dst)[i] = make_uint4(t[u * R + 4 * i], t[u * R + 4 * i + 1], t[u * R + 4 * i + 2], t[u * R + 4 * i + 3]);
+      }
+    }
+  }
+}
+
+// one pass over the four buffers: levels 0 and 1 at 32 >> DEPTH, level 2 at 16 >> DEPTH, level 3 at 8 >> DEPTH
+template <int STAGE, int DEPTH>
+__device__ __forceinline__ void rd_stage(short* s, int lane, int wave, int bd, const FhevcRdQuant& Q, unsigned* acc)
+{
+  constexpr int NA = 32 >> DEPTH, NB = 16 >> DEPTH, NC = 8 >> DEPTH;
+  const short* tables = s + kTransformShorts;
+  short *const b0 = s, *const b1 = s + kLevelBuf, *const b2 = s + 2 * kLevelBuf, *const b3 = s + 3 * kLevelBuf;
+  unsigned t0[8], t1[8], t2[8], t3[8];
+  tu_pass<NA, STAGE, DEPTH>(tables, b0, lane, wave, bd, Q, acc, 0, 5, t0);
+  tu_pass<NA, STAGE, DEPTH>(tables, b1, lane, wave, bd, Q, acc, 4, 5, t1);
+  tu_pass<NB, STAGE, DEPTH>(tables, b2, lane, wave, bd, Q, acc, 8, 4, t2);
+  tu_pass<NC, STAGE, DEPTH>(tables, b3, lane, wave, bd, Q, acc, 24, 3, t3);
+  __syncthreads();   // every thread has read
+  tu_store<NA, STAGE>(b0, lane, wave, t0);
+  tu_store<NA, STAGE>(b1, lane, wave, t1);
+  tu_store<NB, STAGE>(b2, lane, wave, t2);
+  tu_store<NC, STAGE>(b3, lane, wave, t3);
+  __syncthreads();
+}
+
+// one depth of the TU tree: the residual tiles into the buffers, the four passes, xGetSSE of this lane's tile of the rebuilt block (the per-sample shift
+// of TComRdCost.cpp:1190-1199) summed over the tiles of its depth-0 TU
+// The original tile is loaded a second time here (from the cache): kept in registers across the passes it cost the kernel its second wave per SIMD
+template <int DEPTH, typename T>
+__device__ __forceinline__ void rd_depth(short* s, int lane, int lvl, int wave, int tx, int ty, const FhevcRdQuant& Q, unsigned* acc, const T* plane, long long cur_base,
+                                         const FhevcFrames& F, int px, int py, bool inside, const unsigned (&D)[32])
+{
+  const int bd = F.bit_depth;
+  short* const tile = s + lvl * kLevelBuf + (ty * 8) * kPitch + tx * 8;
+#pragma unroll
+  for (int y = 0; y < 8; ++y) *reinterpret_cast<uint4*>(tile + y * kPitch) = make_uint4(D[4 * y], D[4 * y + 1], D[4 * y + 2], D[4 * y + 3]);
+  __syncthreads();
+  rd_stage<ROWS, DEPTH>(s, lane, wave, bd, Q, acc);
+  rd_stage<COLS, DEPTH>(s, lane, wave, bd, Q, acc);
+  rd_stage<INV1, DEPTH>(s, lane, wave, bd, Q, acc);
+  rd_stage<INV2, DEPTH>(s, lane, wave, bd, Q, acc);
+  const int top = (1 << bd) - 1, sh = 2 * (bd - 8);
+  unsigned O[32];
+  load_tile8x8(plane, cur_base, F, px, py, inside, O);
+  unsigned sum = 0;
+#pragma unroll
+  for (int y = 0; y < 8; ++y) {
+    const uint4 q = *reinterpret_cast<const uint4*>(tile + y * kPitch);
+    const unsigned r[4] = { q.x, q.y, q.z, q.w };
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const unsigned o = O[4 * y + k], p = pk_sub(o, D[4 * y + k]);   // the prediction: original minus residual
+      const int e0 = (int)(o & 0xFFFFu) - min(max((int)(p & 0xFFFFu) + (int)(short)(r[k] & 0xFFFFu), 0), top);
+      const int e1 = (int)(o >> 16) - min(max((int)(p >> 16) + (int)(short)(r[k] >> 16), 0), top);
+      sum += ((unsigned)(e0 * e0) >> sh) + ((unsigned)(e1 * e1) >> sh);
+    }
+  }
+  const int lt = wave <= 1 ? 2 : 3 - wave;   // log2 of the depth-0 TU's side in tiles
+  for (int k = 0; k < lt; ++k) {
+    sum += __shfl_xor(sum, 1 << k);
+    sum += __shfl_xor(sum, 8 << k);
+  }
+  const int m = (1 << lt) - 1, tu0 = wave == 0 ? 0 : wave == 1 ? 4 : wave == 2 ? 8 : 24;
+  if ((tx & m) == 0 && (ty & m) == 0) acc[kAccWords * (tu0 + (ty >> lt) * (8 >> lt) + (tx >> lt)) + 2 * DEPTH] = sum;
+  __syncthreads();   // the tiles are read: the next depth rewrites them; the sums are in
+}
+
+// T = int16_t or uint8_t planes; MR = 8 or 64: the largest max_range the window is laid out for
+template <typename T, int MR>
+__global__ __launch_bounds__(256) void fhevc_motion_rd_kernel(FhevcFrames F, int max_range, FhevcRdQuant Q, int source, const unsigned* __restrict__ in,
+                                                              const unsigned* __restrict__ mvp, FhevcMotionRdNode* __restrict__ out)
+{
+  constexpr int RP = RefineGeom<MR>::RP;
+  constexpr bool BIG = MR > FHEVC_MOTION_MAX_RANGE;
+  constexpr int OVER = kTransformShorts + kFwdShorts + kInvShorts;                          // what lies over the dead window: 41 632 B
+  constexpr int SMALL = RefineGeom<MR>::SAMPLES > OVER ? RefineGeom<MR>::SAMPLES : OVER;   // the larger of the two uses
+  static_assert(!BIG || RefineGeom<MR>::SAMPLES >= OVER, "the dynamic window holds the transform buffers and the matrices");
+  static_assert(sizeof(RdTables) == (kFwdShorts + kInvShorts) * 2 && sizeof(RdTables) / 4 <= 5 * 256, "the tables: five dwords per thread at most");
+  extern __shared__ __attribute__((aligned(16))) short s_dyn[];
+  __shared__ __attribute__((aligned(16))) short s_small[BIG ? 8 : SMALL];
+  short* const s_ref = BIG ? s_dyn : s_small;
+  __shared__ unsigned s_taps[16], s_acc[kAccWords * kTus];
+  const int tid = threadIdx.x, lane = tid & 63, lvl = tid >> 6;
+  const int wave = __builtin_amdgcn_readfirstlane(lvl);   // the transform's matrix rows are read at wave-uniform addresses
+  const int tx = lane & 7, ty = lane >> 3;
+  const int total = SearchWork::total(F);  // frame f >= 1 is predicted from frame f - 1
+  const RefineArith arith(F.bit_depth);
+  const T* plane = reinterpret_cast<const T*>(F.luma);
+  if (tid < 16) s_taps[tid] = kLumaTaps[tid];
+  const RefineNode N(lvl, tx, ty);  // this lane's node: level lvl, (nbx, nby) in the CTU
+  const int nidx = N.nidx;
+  const int gw = F.width >> (6 - lvl), gh = F.height >> (6 - lvl);   // the level's nodes that lie wholly inside the picture
+  const int reach = vec_reach(max_range);
+  const int cost_at = source ? 2 : 1;   // the marker test's dword; the vector is the next one
+
+  for (int work = blockIdx.x; work < total; work += gridDim.x) {
+    const SearchWork W(F, work);
+    const int cy = W.cy, cx = W.cx;
+    const long long oc = W.oc(F);
+    // ---- the node's input record: the marker test, the vector, the side bits; the addresses depend on geometry alone ----
+    const bool node_in = cx * N.ncnt + N.nbx < gw && cy * N.ncnt + N.nby < gh;
+    const long long rec = oc * FHEVC_NODES + nidx;
+    const unsigned rcost = in[rec * 4 + cost_at], rvec = in[rec * 4 + cost_at + 1];
+    const int vx = vec_x(rvec), vy = vec_y(rvec);
+    unsigned side;
+    bool marked = rcost == kRdMark;
+    if (source == 0) {
+      const unsigned idx = in[rec * 4 + 3] & 0xFFu;   // the merge stage's own pricing of the index
+      side = idx == 4u ? 4u : idx + 1u;
+    } else if (mvp) {
+      const unsigned w = mvp[rec * 2 + 1];            // idx in the low byte (255: a marker), bits in the high one
+      marked = marked || (w & 0xFFu) == 255u;
+      side = w >> 24;
+    } else side = (unsigned)(eg_bits(vx) + eg_bits(vy));
+    // ---- stage the part of the reference window that max_range reaches ----
+    __syncthreads();  // the previous CTU's readers of the buffers and of the sums are done
+    refine_stage_window_reach<T, MR>(s_ref, plane, W.ref_base, F, cx, cy, tid, max_range);
+    for (int i = tid; i < kAccWords * kTus; i += 256) s_acc[i] = 0;
+    const int px = cx * 64 + tx * 8, py = cy * 64 + ty * 8;
+    const bool inside = (px + 8 <= F.width) && (py + 8 <= F.height);
+    unsigned O[32];
+    load_tile8x8(plane, W.cur_base, F, px, py, inside, O);
+    const bool valid = node_in && !marked && vec_in_reach(rvec, reach);
+    const int qx = valid ? vx : 0, qy = valid ? vy : 0;   // an invalid node predicts at the zero vector and drops the result: no read outside the window
+    __syncthreads();
+    // ---- the residual of this lane's tile at its node's vector ----
+    unsigned D[32];
+    {
+      int v[64];
+      refine_tile_at<true, RP>(s_ref, s_taps, arith, tx, ty, qx, qy, O, D, v);
+    }
+    __syncthreads();  // the window is dead: the transform buffers and the matrices lie over it
+    {
+      unsigned* mdst = reinterpret_cast<unsigned*>(s_ref + kTransformShorts);
+      const unsigned* msrc = reinterpret_cast<const unsigned*>(&kRdTables);
+      for (int i = tid; i < (kFwdShorts + kInvShorts) / 2; i += 256) mdst[i] = msrc[i];
+    }
+    rd_depth<0>(s_ref, lane, lvl, wave, tx, ty, Q, s_acc, plane, W.cur_base, F, px, py, inside, D);
+    rd_depth<1>(s_ref, lane, lvl, wave, tx, ty, Q, s_acc, plane, W.cur_base, F, px, py, inside, D);
+    if (N.writer) {
+      FhevcMotionRdNode o;
+      o.dist = o.cost_rd = kRdMark; o.bits = 0xFFFFu; o.flags = 0; o.tu_split = 0; o.mvx = o.mvy = 0;
+      if (valid) {
+        const int qi = lvl == 3 ? 1 : (lvl == 2 ? 2 : 3);                // the depth-0 TU size's numbers
+        const int tu0 = lvl == 0 ? 0 : (lvl == 1 ? 4 : lvl == 2 ? 8 : 24) + (nidx - N.first), ntu = lvl == 0 ? 4 : 1;   // a 64x64 node: four TUs
+        unsigned long long j = (unsigned long long)Q.lam_q8 * side, bits = side;
+        unsigned dist = 0, top = 0, any0 = 0, split = 0;
+        for (int i = 0; i < ntu; ++i) {
+          const unsigned* a = &s_acc[kAccWords * (tu0 + i)];
+          const unsigned d0 = a[0], r0 = 1u + a[1], d1 = a[2], r1 = 4u + a[3];
+          const unsigned long long j0 = 256ull * d0 + (unsigned long long)Q.lam_q8 * (1u + r0), j1 = 256ull * d1 + (unsigned long long)Q.lam_q8 * (1u + r1);
+          const bool take = a[3] != 0u && j1 < j0;                        // uiCbfAny && dSubdivCost < dSingleCost
+          j += take ? j1 : j0; dist += take ? d1 : d0; bits += 1u + (take ? r1 : r0);
+          split |= take ? 1u << i : 0u; any0 |= a[1]; top = max(top, a[4]);
+        }
+        // both levels grow with |c|: the node is zero under an offset iff its largest coefficient is
+        const bool zero_half = ((top * Q.scale + Q.add_half[qi]) >> Q.qbits[qi]) == 0u;
+        j >>= 8;
+        o.dist = dist; o.cost_rd = j < 0xFFFFFFFEull ? (unsigned)j : 0xFFFFFFFEu;
+        o.bits = (uint16_t)(bits < 65535ull ? bits : 65535ull);
+        o.flags = (uint8_t)((any0 == 0u ? 1 : 0) | (zero_half ? 2 : 0) | (split ? 4 : 0)); o.tu_split = (uint8_t)split;
+        o.mvx = (short)vx; o.mvy = (short)vy;
+      }
+      out[rec] = o;
+    }
+  }
+}
+
+}  // namespace
+
+// what the device keeps resident is the occupancy query's answer in both layouts: two workgroups per CU by the registers (256 VGPRs), which is also what the
+// LDS allows at MR = 64 (1 824 B static + 80 016 B dynamic); the caps are the skip stage's
+hipError_t fhevc_launch_motion_rd(const FhevcFrames& fr, int max_range, const FhevcRdQuant& q, int source, const void* d_in, const FhevcMotionMvp* d_mvp,
+                                  FhevcMotionRdNode* d_out, int num_cus, hipStream_t stream)
+{
+  static_assert(sizeof(FhevcMotionMergeNode) == 16 && sizeof(FhevcMotionQpelNode) == 16 && sizeof(FhevcMotionMvp) == 8 && sizeof(FhevcMotionRdNode) == 16, "record layouts");
+  const unsigned* in = reinterpret_cast<const unsigned*>(d_in);
+  const unsigned* mvp = reinterpret_cast<const unsigned*>(d_mvp);
+  return refine_launch<FHEVC_MOTION_WIDE_MAX_RANGE>(fr, source == 0 || source == 1, max_range, num_cus, {4, true}, {2, true}, stream, [&](auto t, auto, auto mr, const RefineLaunch& L) {
+    return refine_launch_kernel<&fhevc_motion_rd_kernel<decltype(t), decltype(mr)::value>>(L, fr, max_range, q, source, in, mvp, d_out);
+  });
+}

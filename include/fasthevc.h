@@ -1090,6 +1090,87 @@ int  fhevc_p_tree_select_skip_device(fhevc_ctx* ctx, const fhevc_pu_shape_node* 
                                      const fhevc_motion_skip_node* d_skip, int skip_mask, int num_pictures, int ctu_row_begin, int ctu_row_end,
                                      const fhevc_p_tree_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream);
 
+/* ---- config 4 (P slices): the RD estimate per CU node: transform, quantise, rebuild, one TU split (k_motion_rd.hip) -----------------------------------
+ * Every decision above compares Hadamard distortion + sqrt(lambda) * bits.  HM compares something else at every CU: xCheckRDCostMerge2Nx2N and
+ * xCheckRDCostInter end in encodeResAndCalcRdInterCU (TEncSearch.cpp), where the residual goes through the forward transform, the quantiser, the
+ * dequantiser and the inverse transform, and what xCheckBestMode compares is the SSE of the rebuilt block + lambda * bits over a residual quad-tree
+ * (xEstimateInterResidualQT).  This entry point carries the skip stage's pass through to that quantity, for the vector a record holds.
+ *   Input per CTU: 85 records that carry a vector, of the kind `source` names.
+ *   FHEVC_RD_SOURCE_MERGE (0): fhevc_motion_merge_node records; the marker test is cost_best (dword 1), the vector dword 2, and
+ * side_bits = idx + 1, but 4 for idx == 4: the merge stage's own pricing of the index.  d_mvp must be NULL.
+ *   FHEVC_RD_SOURCE_EXPLICIT (1): fhevc_motion_qpel_node records (refined or re-priced); the marker test is cost_best (dword 2), the vector dword 3.  With
+ * the re-pricing's fhevc_motion_mvp records in d_mvp, side_bits = bits of that record, and a marker predictor record (idx == 255) makes the node invalid;
+ * with d_mvp NULL, side_bits = eg(mvx) + eg(mvy) against the zero predictor at cost scale 0, eg exactly as fhevc_motion_amvp* defines it.
+ *   Planes (int16 or uint8), band, stream, frame pairing (frame f is predicted from frame f - 1), the compact-over-the-band record layout, qp 0..51,
+ * max_range 1..64 and the rejected calls are exactly fhevc_motion_skip_device's.  A node is valid iff it is INSIDE, its record is no marker, and |mvx| and
+ * |mvy| are both <= 4 max_range + 3.
+ *   Step 1, the residual: r = original - fhevc_motion_refine's prediction at the vector, as in the skip stage.
+ *   Step 2, the TUs: the depth-0 TU size is N0 = min(s, 32) (a 64x64 node is four 32x32 TUs), the depth-1 size N1 = N0 / 2: 64 -> 32 and 16, 32 -> 32 and
+ * 16, 16 -> 16 and 8, 8 -> 8 and 4.  Under HM's limits (QuadtreeTUMaxDepthInter 3, getQuadtreeTULog2MinSizeInCU = log2 CU - 2 clipped to 2..5 for 2Nx2N)
+ * these two sizes are HM's COMPLETE TU tree for 64x64 and 8x8 CUs; for 32x32 and 16x16 CUs HM has a third depth, which is left out.
+ *   Step 3, per TU of either size, all in integers:
+ *   forward transform: xTrMxN (TComTrQuant.cpp:860-915) as in the skip stage, now also at N = 4 -- the DCT: inter 4x4 never takes the DST --,
+ * shift_1st = log2 N + bit_depth - 9, shift_2nd = log2 N + 6;
+ *   quantiser: level = sign(c) * ((|c| * scale + add_plain) >> qbits), qbits = 21 + QP' / 6 - (bit_depth - 8) - log2 N: the skip stage's formula, with
+ * log2 N = 2 added (TComTrQuant.cpp:1186-1232).  add_half serves flag bit 1 only.  RDOQ is NOT modelled;
+ *   dequantiser: xDeQuant without scaling lists (TComTrQuant.cpp:1387-1422): rightShift = 6 - (15 - bit_depth - log2 N + per) = log2 N - 1 - qp / 6, which
+ * does not depend on the bit depth; the level clipped to int16 (targetInputBitDepth is 16 for every legal argument; no level exceeds 13 108);
+ * rightShift > 0: c^ = (level * g_invQuantScales[rem] + (1 << (rightShift - 1))) >> rightShift, otherwise c^ = (level * scale) << -rightShift; c^ clipped
+ * to [-32768, 32767]; g_invQuantScales = {40, 45, 51, 57, 64, 72};
+ *   inverse transform: xITrMxN (TComTrQuant.cpp:927-990): the first stage over the vertical frequencies, shift 7, clipped to [-32768, 32767]; the second
+ * stage, shift 20 - bit_depth, clipped to the Pel range (the same interval): r^.  Every accumulation stays below 32 * 32768 * 90 < 2^31;
+ *   distortion: xGetSSE with its PER-SAMPLE shift (TComRdCost.cpp:1190-1199): D = sum ((org - Clip(pred + r^, 0, 2^bit_depth - 1))^2 >> 2 (bit_depth - 8));
+ * D < 2^32 at every bit depth;
+ *   bits: the library's OWN estimate, unfitted: r(TU) = 1 + sum over the non-zero levels of (3 + 2 floor(log2 |level|)) -- 1 for the cbf; a level of 1
+ * costs 3 (significance, greater-1, sign), larger levels grow like an exp-Golomb code.  Not counted: the significance flags of zero levels, the last
+ * position, any context effect.
+ *   Step 4, the choice per depth-0 TU, in 64 bits: lam_q8 = floor(lambda * 256 + 0.5) with lambda = 0.57 * 2^((qp - 12) / 3), computed on the host
+ * (fhevc_motion_rd_lambda_q8) and handed to the kernel by value; J0 = 256 D0 + lam_q8 (1 + r0); J1 = 256 sum D1 + lam_q8 (1 + sum r1) over the four
+ * children; the split is taken iff some child holds a non-zero level AND J1 < J0, strictly (TEncSearch.cpp:5117: uiCbfAny && dSubdivCost < dSingleCost).
+ * Node: cost_rd = min((sum of the chosen J + lam_q8 * side_bits) >> 8, 0xFFFFFFFE).
+ *   Field order (pinned: 16 bytes without padding; dword 1 and byte 10 are where the existing tree kernels read): */
+#define FHEVC_RD_SOURCE_MERGE    0
+#define FHEVC_RD_SOURCE_EXPLICIT 1
+typedef struct {
+  uint32_t dist;            /* D summed over the chosen TUs */
+  uint32_t cost_rd;         /* dword 1: where merge and selection records keep cost_best */
+  uint16_t bits;            /* everything lam_q8 multiplies: sum over the depth-0 TUs of 1 + the chosen r, + side_bits; saturated at 65535 */
+  uint8_t  flags;           /* byte 10: where fhevc_motion_skip_node keeps flags.  bit 0: every depth-0 level zero under add_plain; bit 1: zero under
+                               add_half -- the skip stage's two bits, by the same arithmetic; bit 2: some TU split */
+  uint8_t  tu_split;        /* bit i: depth-0 TU i (raster in the node) is split; only the 64x64 node uses bits 1..3 */
+  int16_t  mvx, mvy;        /* the vector, copied from the input record */
+} fhevc_motion_rd_node;     /* 16 bytes; an invalid node gets dist = cost_rd = 0xFFFFFFFF, bits = 0xFFFF, flags = tu_split = 0 and a zero vector */
+/* Device form: d_in, d_out: (num_frames - 1) * band CTUs * 85 records of 16 bytes, d_mvp as many of 8, compact over the band; the output is written over
+ * exactly that extent, an empty band writes nothing.  The kernel keeps the skip kernel's mapping and buffers and runs four passes per TU depth through
+ * them -- forward rows, forward columns with quantiser, pricing and dequantiser in registers, and the two inverse stages on transposed matrices --, then
+ * takes the squared error of the rebuilt tile; by a count of its code about three times the skip stage's dot products (an expectation, not a
+ * measurement).  Asynchronous with respect to the host, allocates nothing, keeps NO state in HBM between calls: calls with different QPs, ranges and
+ * sources may be in flight on two streams.  FHEVC_E_INVALID with a fhevc_last_error text (nothing is launched or written): what
+ * fhevc_motion_skip_device rejects, source outside 0..1, d_mvp together with source 0, a pointer that is not 4-byte aligned.  Timed under slot 29 of
+ * fhevc_kernel_timing (28 stays rejected).
+ * NOT covered: RDOQ, the third TU depth of 32x32 and 16x16 CUs, the partition sizes other than 2Nx2N (their prediction is composed from two vectors),
+ * transform skip, sign hiding, chroma, CABAC's contexts.  The encoder hook does not consume this output. */
+int  fhevc_motion_rd_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames,
+                            int ctu_row_begin, int ctu_row_end, int qp, int max_range, int source, const void* d_in, const fhevc_motion_mvp* d_mvp /* or NULL */,
+                            fhevc_motion_rd_node* d_out, void* stream);
+/* one picture pair, host buffers (both planes with the same stride), synchronous, as fhevc_motion_skip; in, out: numCtus * 85; mvp: numCtus * 85 or NULL */
+int  fhevc_motion_rd(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range, int source, const void* in,
+                     const fhevc_motion_mvp* mvp /* or NULL */, fhevc_motion_rd_node* out);
+/* lam_q8 of a QP (clamped to 0..51); needs no context */
+uint32_t fhevc_motion_rd_lambda_q8(int qp);
+
+/* The tree on RD costs: fhevc_p_tree_select_skip[_device], byte for byte, with three substitutions: rd_explicit[k].cost_rd stands where
+ * shapes[k].cost_best is read, rd_merge[k].cost_rd where merge[k].cost_best is read, rd_merge[k].flags where skip[k].flags is read.  The record layout
+ * makes these the same byte offsets, so both forms forward to the existing implementation; the device form is timed under slot 17.  This is HM with 2Nx2N
+ * and merge as its ONLY inter candidates, decided on RD costs: a statement about two of the seven partition sizes.  FHEVC_E_INVALID: what the skip tree
+ * rejects. */
+int  fhevc_p_tree_select_rd(const fhevc_motion_rd_node* rd_explicit /* 85 */, const fhevc_motion_rd_node* rd_merge /* 85 */, int skip_mask, int valid_w,
+                            int valid_h, const fhevc_p_tree_rule* rule, uint8_t* depth_min /* 256 or NULL */, uint8_t* depth_max /* 256 or NULL */,
+                            fhevc_p_tree_node* tree /* 85 or NULL */);
+int  fhevc_p_tree_select_rd_device(fhevc_ctx* ctx, const fhevc_motion_rd_node* d_rd_explicit, const fhevc_motion_rd_node* d_rd_merge, int skip_mask,
+                                   int num_pictures, int ctu_row_begin, int ctu_row_end, const fhevc_p_tree_rule* rule, uint8_t* d_depth_min,
+                                   uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream);
+
 /* ---- config 4 (P slices): intra candidate costs per CU node (k_intra_p.hip) -----------------------------------------------------------------------
  * HM checks intra at every CU of a P slice (TEncCu.cpp:797-816): xCheckRDCostIntra(SIZE_2Nx2N) at every depth, SIZE_NxN at the 8x8 level, both only while
  * the best mode so far has a non-zero CBF.  Without that candidate a node whose content is not in the reference picture -- uncovered background, the second
@@ -1186,9 +1267,10 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
  * -- and 19 = the merge-candidate costs (fhevc_motion_merge*), added later still.  18 is not a slot: it stays rejected -- and 21 = the merge-candidate
  * costs per PU (fhevc_motion_merge_pu*).  20 is not a slot: it stays rejected -- and 23 = the zero-residual test (fhevc_motion_skip*).  22 is not a slot: it stays
  * rejected -- and 25 = the re-pricing against neighbour predictors (fhevc_motion_amvp*).  24 is not a slot: it stays rejected, as does any number above 25
- * -- except 27 = the intra candidate costs of P pictures (fhevc_intra_p*).  26 is not a slot: it stays rejected, as does any number above 27.
- * The tree that stops at a skip (fhevc_p_tree_select_skip_device) and the tree that takes the intra candidate (fhevc_p_tree_select_intra_device) are timed
- * under 17 */
+ * -- except 27 = the intra candidate costs of P pictures (fhevc_intra_p*).  26 is not a slot: it stays rejected, as does any number above 27
+ * -- except 29 = the RD estimate (fhevc_motion_rd*).  28 is not a slot: it stays rejected, as does any number above 29.
+ * The tree that stops at a skip (fhevc_p_tree_select_skip_device), the tree that takes the intra candidate (fhevc_p_tree_select_intra_device) and the tree
+ * on RD costs (fhevc_p_tree_select_rd_device) are timed under 17 */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
 int  fhevc_enable_kernel_timing(fhevc_ctx* ctx, int on);
 
