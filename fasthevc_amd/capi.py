@@ -47,6 +47,7 @@ SYMBOLS = [
     "fhevc_motion_amvp", "fhevc_motion_amvp_device", "fhevc_motion_amvp_picture", "fhevc_p_tree_amvp_frame",
     "fhevc_intra_p", "fhevc_intra_p_device", "fhevc_intra_p_picture", "fhevc_p_tree_select_intra", "fhevc_p_tree_select_intra_device", "fhevc_p_tree_intra_frame",
     "fhevc_motion_rd", "fhevc_motion_rd_device", "fhevc_motion_rd_lambda_q8", "fhevc_p_tree_select_rd", "fhevc_p_tree_select_rd_device",
+    "fhevc_motion_rd_pu", "fhevc_motion_rd_pu_device", "fhevc_p_tree_select_rd_pu", "fhevc_p_tree_select_rd_pu_device", "fhevc_p_tree_rd_frame",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -74,6 +75,11 @@ class PuShapeRule(C.Structure):
 class PTreeRule(C.Structure):
     """fhevc_p_tree_rule: the margins of the two decisions and the split cost per level (64, 32, 16)"""
     _fields_ = [("split_q8", C.c_int32 * 3), ("split_abs", C.c_int32 * 3), ("stop_q8", C.c_int32 * 3), ("stop_abs", C.c_int32 * 3), ("split_cost", C.c_int32 * 3)]
+
+
+class MotionRdPuInputs(C.Structure):
+    """fhevc_motion_rd_pu_inputs: ten pointers (device or host), None for an array left out"""
+    _fields_ = [(n, C.c_void_p) for n in ("nodes", "pus", "pus_small", "merge_pus", "merge_pus_small", "mvp_nodes", "mvp_pus", "mvp_pus_small", "shapes", "fold")]
 
 
 class NodeCost(C.Structure):
@@ -108,6 +114,12 @@ SKIP_ZERO_PLAIN, SKIP_ZERO_HALF = 1, 2
 MOTION_RD_DTYPE = np.dtype([("dist", np.uint32), ("cost_rd", np.uint32), ("bits", np.uint16), ("flags", np.uint8), ("tu_split", np.uint8),
                             ("mvx", np.int16), ("mvy", np.int16)])
 RD_SOURCE_MERGE, RD_SOURCE_EXPLICIT = 0, 1
+# fhevc_motion_rd_pu_node: the RD estimate of a CU node under one of HM's partition sizes; bytes 0..11 are MOTION_RD_DTYPE's (part: the PartSize priced, 255 in a
+# marker; merged bit i: part i took its merge vector)
+MOTION_RD_PU_DTYPE = np.dtype([("dist", np.uint32), ("cost_rd", np.uint32), ("bits", np.uint16), ("flags", np.uint8), ("tu_split", np.uint8),
+                               ("part", np.uint8), ("merged", np.uint8), ("pad", np.uint8, (2,))])
+# part_mode of fhevc_motion_rd_pu*: a PART_* number for every node, or the selection's best / second size per node
+RD_PART_BEST, RD_PART_SECOND = 8, 9
 RD_TU_SPLIT = 4
 # fhevc_motion_mvp: the predictor fhevc_motion_amvp* priced an entry against (src: 0..4 = L, A, AR, BL, AL, 5 = a filled zero; idx = src = 255: no price)
 MOTION_MVP_DTYPE = np.dtype([("px", np.int16), ("py", np.int16), ("idx", np.uint8), ("num_spatial", np.uint8), ("src", np.uint8), ("bits", np.uint8)])
@@ -281,6 +293,11 @@ def load_library(path=None):
     lib.fhevc_intra_p_picture.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     lib.fhevc_p_tree_select_intra.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp]
     lib.fhevc_p_tree_select_intra_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp, vp]
+    lib.fhevc_motion_rd_pu.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MotionRdPuInputs), vp]
+    lib.fhevc_motion_rd_pu_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MotionRdPuInputs), vp, vp]
+    lib.fhevc_p_tree_select_rd_pu.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp]
+    lib.fhevc_p_tree_select_rd_pu_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp, vp]
+    lib.fhevc_p_tree_rd_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), C.c_int, vp, vp, vp, vp, vp, vp]
     lib.fhevc_p_tree_intra_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), C.c_int, vp, vp, vp, vp, vp]
     lib.fhevc_predict_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, vp, vp]
     lib.fhevc_alloc_host.argtypes = [vp, C.c_size_t]
@@ -432,6 +449,25 @@ def p_tree_select_rd(rd_explicit, rd_merge, skip_mask, width, height, rule=None,
                                         dmax[c].ctypes.data, tree[c].ctypes.data if with_tree else None)
         if rc != OK:
             raise FastHevcError(rc, "fhevc_p_tree_select_rd")
+    return (dmin, dmax, tree) if with_tree else (dmin, dmax)
+
+
+def p_tree_select_rd_pu(rd_pu, rd_merge, skip_mask, width, height, rule=None, with_tree=False):
+    """p_tree_select_rd with the folded records of motion_rd_pu [numCtus, 85] MOTION_RD_PU_DTYPE where rd_explicit stands; the same results"""
+    rd_pu = np.ascontiguousarray(rd_pu)
+    assert rd_pu.dtype == MOTION_RD_PU_DTYPE
+    lib = load_library()
+    rd_merge = np.ascontiguousarray(rd_merge)
+    rule = rule if rule is not None else p_tree_rule_default()
+    n, ctus_x = rd_pu.shape[0], (width + 63) // 64
+    dmin, dmax = np.zeros((n, 256), np.uint8), np.zeros((n, 256), np.uint8)
+    tree = np.zeros((n, NODES_PER_CTU), TREE_DTYPE)
+    for c in range(n):
+        vw, vh = min(64, width - (c % ctus_x) * 64), min(64, height - (c // ctus_x) * 64)
+        rc = lib.fhevc_p_tree_select_rd_pu(rd_pu[c].ctypes.data, rd_merge[c].ctypes.data, skip_mask, vw, vh, C.byref(rule), dmin[c].ctypes.data,
+                                           dmax[c].ctypes.data, tree[c].ctypes.data if with_tree else None)
+        if rc != OK:
+            raise FastHevcError(rc, "fhevc_p_tree_select_rd_pu")
     return (dmin, dmax, tree) if with_tree else (dmin, dmax)
 
 
@@ -832,6 +868,41 @@ class Context:
         self._check(self.lib.fhevc_motion_rd_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range, source,
                                                     d_in, d_mvp, d_out, stream))
 
+    @staticmethod
+    def rd_pu_inputs(nodes, pus=None, pus_small=None, merge_pus=None, merge_pus_small=None, mvp_nodes=None, mvp_pus=None, mvp_pus_small=None, shapes=None, fold=None):
+        """fhevc_motion_rd_pu_inputs from device addresses (integers), None for an array left out"""
+        return MotionRdPuInputs(nodes, pus, pus_small, merge_pus, merge_pus_small, mvp_nodes, mvp_pus, mvp_pus_small, shapes, fold)
+
+    def motion_rd_pu(self, cur_plane, ref_plane, part_mode, nodes, pus=None, pus_small=None, merge_pus=None, merge_pus_small=None, mvp_nodes=None, mvp_pus=None,
+                     mvp_pus_small=None, shapes=None, fold=None, origin=0, stride=None, qp=32, max_range=4):
+        """config 4: the RD estimate of every CU node under a partition size -- part_mode a PART_* number, RD_PART_BEST or RD_PART_SECOND (of shapes) -- with the
+        prediction composed from the two parts' vectors: nodes / pus / pus_small [numCtus, 85 / 124 / 384] MOTION_QPEL_DTYPE, their merge records
+        (MOTION_MERGE_DTYPE) and predictor records (MOTION_MVP_DTYPE) or None, shapes [numCtus, 85] SHAPE_DTYPE, fold: an earlier call's result to fold into
+        -> [numCtus, 85] MOTION_RD_PU_DTYPE"""
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
+        keep, ptrs = [], []
+        for a, per_ctu, size in ((nodes, 85, 16), (pus, 124, 16), (pus_small, 384, 16), (merge_pus, 124, 16), (merge_pus_small, 384, 16), (mvp_nodes, 85, 8),
+                                 (mvp_pus, 124, 8), (mvp_pus_small, 384, 8), (shapes, 85, 16), (fold, 85, 16)):
+            if a is None:
+                ptrs.append(None)
+                continue
+            a = np.ascontiguousarray(a).reshape(-1)
+            assert a.dtype.itemsize == size and a.size == self.num_ctus * per_ctu
+            keep.append(a)
+            ptrs.append(a.ctypes.data)
+        inputs = MotionRdPuInputs(*ptrs)
+        out = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_RD_PU_DTYPE)
+        self._check(self.lib.fhevc_motion_rd_pu(self.h, cur, ref, stride, qp, max_range, part_mode, C.byref(inputs), out.ctypes.data))
+        return out.reshape(self.num_ctus, NODES_PER_CTU)
+
+    def motion_rd_pu_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, part_mode, inputs, d_out, rows=None, stream=None, qp=32, max_range=4):
+        """frames 1.. of the batch, each predicted from the frame before it with every node's prediction composed from the two parts of its partition size
+        (inputs: rd_pu_inputs(...) of device addresses, compact over the rows); d_out: (num_frames - 1) * band CTUs * 85 records (16 B), folded into
+        inputs.fold where that is given (d_out itself is allowed).  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_motion_rd_pu_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range, part_mode,
+                                                       C.byref(inputs) if inputs is not None else None, d_out, stream))
+
     def motion_merge_pu(self, cur_plane, ref_plane, refined, origin=0, stride=None, qp=32, max_range=4, with_pus=True, with_small=True):
         """config 4: the cheapest merge candidate of every PU from the refined square nodes [numCtus, 85] (MOTION_QPEL_DTYPE; only cost_best, mvx, mvy are
         read) -> ([numCtus, 124], [numCtus, 384]) MOTION_MERGE_DTYPE in the orders of motion_pu_index / motion_pu_small_index; None for a family not asked for"""
@@ -1080,6 +1151,13 @@ class Context:
         self._check(self.lib.fhevc_p_tree_select_rd_device(self.h, d_rd_explicit, d_rd_merge, skip_mask, num_pictures, rb, re,
                                                            C.byref(rule) if rule is not None else None, d_depth_min, d_depth_max, d_tree, stream))
 
+    def p_tree_select_rd_pu_device(self, d_rd_pu, d_rd_merge, skip_mask, num_pictures, d_depth_min=None, d_depth_max=None, d_tree=None, rows=None, stream=None,
+                                   rule=None):
+        """p_tree_select_rd_device with the folded records of motion_rd_pu_device where d_rd_explicit stands.  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_p_tree_select_rd_pu_device(self.h, d_rd_pu, d_rd_merge, skip_mask, num_pictures, rb, re,
+                                                              C.byref(rule) if rule is not None else None, d_depth_min, d_depth_max, d_tree, stream))
+
     def p_tree_select_intra_device(self, d_shapes, d_merge, d_skip, skip_mask, d_intra, num_pictures, d_depth_min=None, d_depth_max=None, d_tree=None, rows=None,
                                    stream=None, rule=None):
         """p_tree_select_skip_device with the intra records of intra_p_device (85 per CTU, compact over the same rows): a node that is not calm takes its
@@ -1119,6 +1197,23 @@ class Context:
                                                       intra.ctypes.data if with_intra else None))
         out = (dmin.reshape(self.num_ctus, 256), dmax.reshape(self.num_ctus, 256))
         for a in (shapes, merge, intra):
+            out += (a.reshape(self.num_ctus, NODES_PER_CTU),) if a is not None else ()
+        return out
+
+    def p_tree_rd_frame(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=8, coarse_range=0, shape_rule=None, tree_rule=None, skip_mask=3,
+                        with_shapes=False, with_merge=False, with_rd_merge=False, with_rd_pu=False):
+        """p_tree_amvp_frame carried to the RD stage: behind the selection the RD estimate of the nodes' merge records, the RD estimates of 2Nx2N and of the
+        selection's best and second size folded per node, and the RD tree -> (depth_min, depth_max) [numCtus, 256], then the records asked for [numCtus, 85]:
+        SHAPE_DTYPE, MOTION_MERGE_DTYPE, MOTION_RD_DTYPE (of the merge records), MOTION_RD_PU_DTYPE (folded)"""
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
+        dmin, dmax = np.zeros(self.num_ctus * 256, np.uint8), np.zeros(self.num_ctus * 256, np.uint8)
+        wanted = ((with_shapes, SHAPE_DTYPE), (with_merge, MOTION_MERGE_DTYPE), (with_rd_merge, MOTION_RD_DTYPE), (with_rd_pu, MOTION_RD_PU_DTYPE))
+        arrays = [np.zeros(self.num_ctus * NODES_PER_CTU, dt) if want else None for want, dt in wanted]
+        self._check(self.lib.fhevc_p_tree_rd_frame(self.h, cur, ref, stride, qp, search_range, coarse_range, C.byref(shape_rule) if shape_rule is not None else None,
+                                                   C.byref(tree_rule) if tree_rule is not None else None, skip_mask, dmin.ctypes.data, dmax.ctypes.data,
+                                                   *[a.ctypes.data if a is not None else None for a in arrays]))
+        out = (dmin.reshape(self.num_ctus, 256), dmax.reshape(self.num_ctus, 256))
+        for a in arrays:
             out += (a.reshape(self.num_ctus, NODES_PER_CTU),) if a is not None else ()
         return out
 

@@ -461,6 +461,16 @@ int fhevc_p_tree_select_rd(const fhevc_motion_rd_node* rd_explicit, const fhevc_
                                   reinterpret_cast<const fhevc_motion_skip_node*>(rd_merge), skip_mask, valid_w, valid_h, rule, depth_min, depth_max, tree);
 }
 
+// ... and on the folded records of fhevc_motion_rd_pu*: the same twelve bytes in front
+int fhevc_p_tree_select_rd_pu(const fhevc_motion_rd_pu_node* rd_pu, const fhevc_motion_rd_node* rd_merge, int skip_mask, int valid_w, int valid_h,
+                              const fhevc_p_tree_rule* rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_p_tree_node* tree)
+{
+  static_assert(sizeof(fhevc_motion_rd_pu_node) == 16 && offsetof(fhevc_motion_rd_pu_node, cost_rd) == offsetof(fhevc_motion_rd_node, cost_rd) &&
+                offsetof(fhevc_motion_rd_pu_node, flags) == offsetof(fhevc_motion_rd_node, flags) && offsetof(fhevc_motion_rd_pu_node, part) == 12,
+                "RD record layout of a partition size");
+  return fhevc_p_tree_select_rd(reinterpret_cast<const fhevc_motion_rd_node*>(rd_pu), rd_merge, skip_mask, valid_w, valid_h, rule, depth_min, depth_max, tree);
+}
+
 int fhevc_p_tree_select_intra(const fhevc_pu_shape_node* shapes, const fhevc_motion_merge_node* merge, const fhevc_motion_skip_node* skip, int skip_mask,
                               const fhevc_intra_p_node* intra, int valid_w, int valid_h, const fhevc_p_tree_rule* rule, uint8_t* depth_min, uint8_t* depth_max,
                               fhevc_p_tree_node* tree)

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cmath>
+#include <cstddef>
 
 #define FHEVC_CTU 64
 
@@ -349,6 +350,24 @@ inline FhevcRdQuant fhevc_rd_quant(int qp, int bit_depth)
 // d_in, d_out: (num_frames - 1) * band CTUs * 85 records
 hipError_t fhevc_launch_motion_rd(const FhevcFrames& fr, int max_range, const FhevcRdQuant& q, int source, const void* d_in, const FhevcMotionMvp* d_mvp,
                                   FhevcMotionRdNode* d_out, int num_cus, hipStream_t stream);
+
+// ... of a node under any of HM's seven inter partition sizes, the prediction composed from its two parts' vectors (the PU instances of k_motion_rd.hip):
+// bytes 0..11 as FhevcMotionRdNode, so the tree kernels read cost_rd and flags where they always do
+struct FhevcMotionRdPuNode { uint32_t dist, cost_rd; uint16_t bits; uint8_t flags, tu_split; uint8_t part, merged, pad[2]; };
+static_assert(sizeof(FhevcMotionRdPuNode) == 16 && offsetof(FhevcMotionRdPuNode, cost_rd) == 4 && offsetof(FhevcMotionRdPuNode, flags) == 10 &&
+              offsetof(FhevcMotionRdPuNode, part) == 12, "RD record of a partition size: 16 bytes, dword 1 and byte 10 where the tree kernels read");
+// the kernels' view of fhevc_motion_rd_pu_inputs (the same ten pointers)
+struct FhevcPuShapeNode;
+struct FhevcMotionRdPuInputs {
+  const FhevcMotionQpelNode *nodes, *pus, *pus_small;
+  const FhevcMotionMergeNode *merge_pus, *merge_pus_small;
+  const FhevcMotionMvp *mvp_nodes, *mvp_pus, *mvp_pus_small;
+  const FhevcPuShapeNode* shapes;
+  const FhevcMotionRdPuNode* fold;
+};
+// part_mode 0, 1, 2, 4..7: that PartSize for every node; 8 / 9: the selection's best / second; I.fold == d_out is allowed
+hipError_t fhevc_launch_motion_rd_pu(const FhevcFrames& fr, int max_range, const FhevcRdQuant& q, int part_mode, const FhevcMotionRdPuInputs& I, FhevcMotionRdPuNode* d_out,
+                                     int num_cus, hipStream_t stream);
 
 // ---- ... and of the PUs' vectors (k_motion_refine_pu.hip; config 4) --------------------------------------------------
 // fr, max_range (1 .. FHEVC_MOTION_WIDE_MAX_RANGE: up to FHEVC_MOTION_MAX_RANGE the MR = 8 layout, above it the MR = 64 layout with its window in dynamic LDS),

@@ -51,6 +51,7 @@ template <> struct Kernel<fhevc_p_tree_node> { using T = FhevcPTreeNode; };
 template <> struct Kernel<fhevc_motion_mvp> { using T = FhevcMotionMvp; };
 template <> struct Kernel<fhevc_intra_p_node> { using T = FhevcIntraPNode; };
 template <> struct Kernel<fhevc_motion_rd_node> { using T = FhevcMotionRdNode; };
+template <> struct Kernel<fhevc_motion_rd_pu_node> { using T = FhevcMotionRdPuNode; };
 template <class P> typename Kernel<P>::T* kn(P* p) { return reinterpret_cast<typename Kernel<P>::T*>(p); }
 template <class P> const typename Kernel<P>::T* kn(const P* p) { return reinterpret_cast<const typename Kernel<P>::T*>(p); }
 static_assert(sizeof(fhevc_motion_node) == 16 && sizeof(FhevcMotionNode) == 16 && sizeof(fhevc_motion_qpel_node) == 16 && sizeof(FhevcMotionQpelNode) == 16, "node layouts");
@@ -64,6 +65,11 @@ static_assert(sizeof(fhevc_intra_p_node) == 16 && offsetof(fhevc_intra_p_node, s
 static_assert(sizeof(fhevc_motion_rd_node) == 16 && offsetof(fhevc_motion_rd_node, cost_rd) == 4 && offsetof(fhevc_motion_rd_node, flags) == 10 &&
               offsetof(fhevc_motion_rd_node, mvx) == 12 && offsetof(FhevcMotionRdNode, cost_rd) == 4 && offsetof(FhevcMotionRdNode, flags) == 10 &&
               offsetof(fhevc_pu_shape_node, cost_best) == 4 && offsetof(fhevc_motion_merge_node, cost_best) == 4, "RD record layout");
+// ... and so is the RD record of a partition size; byte 12 is where the size priced lies
+static_assert(sizeof(fhevc_motion_rd_pu_node) == 16 && offsetof(fhevc_motion_rd_pu_node, cost_rd) == 4 && offsetof(fhevc_motion_rd_pu_node, flags) == 10 &&
+              offsetof(fhevc_motion_rd_pu_node, part) == 12 && offsetof(fhevc_motion_rd_pu_node, merged) == 13 && offsetof(fhevc_motion_rd_pu_node, bits) == 8 &&
+              offsetof(fhevc_motion_rd_pu_node, tu_split) == offsetof(fhevc_motion_rd_node, tu_split) && sizeof(FhevcMotionRdPuNode) == 16 &&
+              offsetof(fhevc_pu_shape_node, best) == 12 && offsetof(fhevc_pu_shape_node, second) == 13, "RD record of a partition size");
 static_assert(sizeof(fhevc_node_cost) == 16 && offsetof(fhevc_node_cost, satd) == 0 && offsetof(fhevc_node_cost, mode) == 4, "first-pass record layout");
 static_assert(FHEVC_PUS_PER_CTU == FHEVC_PUS && FHEVC_PUS_SMALL_PER_CTU == FHEVC_PUS_SMALL, "PU counts");
 static_assert(sizeof(fhevc_motion_mvp) == 8 && offsetof(fhevc_motion_mvp, idx) == 4 && offsetof(fhevc_motion_mvp, bits) == 7 && offsetof(FhevcMotionMvp, bits) == 7,
@@ -121,13 +127,17 @@ int device_form(fhevc_ctx* c, bool args_ok, const char* bad_args, const Batch& b
 //   d_amvp, d_amvp_mvp       593 (everything)  the re-priced entries and their predictor records (8 bytes each): the 85, behind them the 124, behind them the
 //                                              384 (fhevc_motion_amvp, fhevc_p_tree_amvp_frame)
 //   d_p_maps                 3 x 256 bytes     the reference picture's depth map, depth_min, depth_max (fhevc_p_predict_frame; the tree chains use the last two)
+//   (fhevc_motion_rd_pu)                       its inputs: the three families of entries in d_amvp, their predictor records in d_amvp_mvp, the PUs' merge
+//                                              records in d_merge_pu, the selection's records in d_motion; the folded records in d_qpel, in and out
+//   (fhevc_p_tree_rd_frame)                    fhevc_p_tree_amvp_frame's buffers, with d_amvp_mvp; the merge records' RD records in d_qpel and the folded RD
+//                                              records in the head of d_qpel_pu: the re-pricing has read the refined nodes and PUs by then
 //   d_first_p                341 (85 + 256)    the first-pass records of the nodes, behind them those of the 4x4 PUs (fhevc_intra_p, fhevc_p_tree_intra_frame)
 //   d_intra_p                85                the intra records made from them
 // fhevc_p_tree_intra_frame keeps its skip records in d_qpel: the re-pricing has read the refined nodes by then, and every later stage reads d_amvp
 //
 // The timing slots (fhevc_kernel_timing) of the launches below: 4 fhevc_motion_search, 5 the P rule, 7 fhevc_motion_refine, 8 / 9 the searches of the PUs / the
 // small PUs, 10 fhevc_motion_refine_pu, 11 / 12 the wide search / refinement, 13 the partition sizes, 15 the centres and everything centred, 17 the tree, 19 the merge stage,
-// 21 the merge stage per PU, 23 the zero-residual test, 25 the re-pricing against neighbour predictors, 27 the intra stage, 29 the RD estimate
+// 21 the merge stage per PU, 23 the zero-residual test, 25 the re-pricing against neighbour predictors, 27 the intra stage, 29 the RD estimate, 31 the RD estimate under a partition size
 struct Family { int per_ctu; FhevcMotionNode* fhevc_ctx::*found; FhevcMotionQpelNode* fhevc_ctx::*refined; };
 constexpr Family kNodes = { FHEVC_NODES, &fhevc_ctx::d_motion, &fhevc_ctx::d_qpel }, kPus = { FHEVC_PUS, &fhevc_ctx::d_motion_pu, &fhevc_ctx::d_qpel_pu },
                  kSmall = { FHEVC_PUS_SMALL, &fhevc_ctx::d_motion_pu_small, &fhevc_ctx::d_qpel_pu_small }, kCentres = { 1, &fhevc_ctx::d_centres, nullptr };
@@ -208,7 +218,7 @@ class HostForm {
 
   fhevc_ctx* c;
   hipError_t e = hipSuccess;
-  Copy ins[4], outs[6];   // at most: the centres and three families in; three families of records and of predictor records out (the intra chain: five)
+  Copy ins[10], outs[6];   // at most: the ten arrays of fhevc_motion_rd_pu in; three families of records and of predictor records out (the RD chain: six too)
   int n_in = 0, n_out = 0;
 };
 
@@ -241,6 +251,17 @@ int queue_chain(fhevc_ctx* c, int qp, int search_range, int coarse_range, const 
   rc = on_pair(c, fhevc_motion_centres_device, qp, coarse_range, k.centres, c->stream);
   if (rc == FHEVC_OK) rc = on_pair(c, fhevc_motion_search_pu_centred_device, qp, search_range, k.centres, k.nodes, k.pus, k.small, c->stream);
   return rc != FHEVC_OK ? rc : on_pair(c, fhevc_motion_refine_pu_centred_device, qp, search_range, k.centres, k.nodes, k.q_nodes, k.pus, k.q_pus, k.small, k.q_small, c->stream);
+}
+
+// what a part mode asks of the inputs of fhevc_motion_rd_pu*, the same for pointers of either kind -> a message, or null
+const char* rd_pu_mode_error(int part_mode, const fhevc_motion_rd_pu_inputs& in)
+{
+  if (part_mode < 0 || part_mode > 9 || part_mode == 3) return "bad partition-size RD-stage arguments (part_mode 0, 1, 2, 4..9)";
+  if (part_mode != 0 && !in.pus) return "bad partition-size RD-stage arguments (a two-part size needs the PUs' entries)";
+  if (part_mode >= 8 && !in.shapes) return "bad partition-size RD-stage arguments (part_mode 8 and 9 need the selection's records)";
+  if ((!in.pus && (in.merge_pus || in.mvp_pus)) || (!in.pus_small && (in.merge_pus_small || in.mvp_pus_small)))
+    return "bad partition-size RD-stage arguments (a family's merge and predictor records need that family's entries)";
+  return nullptr;
 }
 
 }  // namespace
@@ -558,6 +579,56 @@ int fhevc_motion_rd(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_lu
 }
 
 uint32_t fhevc_motion_rd_lambda_q8(int qp) { return fhevc_rd_lambda_q8(qp < 0 ? 0 : (qp > 51 ? 51 : qp)); }
+
+// ---- the RD estimate of a CU node under a partition size, folded over several launches (the PU instances of k_motion_rd.hip) ----
+
+int fhevc_motion_rd_pu_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames,
+                              int ctu_row_begin, int ctu_row_end, int qp, int max_range, int part_mode, const fhevc_motion_rd_pu_inputs* inputs,
+                              fhevc_motion_rd_pu_node* d_out, void* stream)
+{
+  const Batch b{ d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp };
+  fhevc_motion_rd_pu_inputs in{};   // read here, handed to the kernel by value: the caller's struct is free again when this call returns
+  if (inputs) in = *inputs;
+  // as for the RD stage, everything the kernel needs travels with the launch: nothing of the context is read or written by it
+  return device_form(c, d_luma && inputs && in.nodes && d_out, "bad partition-size RD-stage arguments", b, max_range, FHEVC_MOTION_WIDE_MAX_RANGE,
+                     "bad partition-size RD-stage arguments (max_range 1..64)", stream, 31, "fhevc_launch_motion_rd_pu", [&](const FhevcFrames& fr, hipStream_t s) {
+    const FhevcMotionRdPuInputs k = { kn(in.nodes), kn(in.pus), kn(in.pus_small), kn(in.merge_pus), kn(in.merge_pus_small), kn(in.mvp_nodes), kn(in.mvp_pus),
+                                      kn(in.mvp_pus_small), kn(in.shapes), kn(in.fold) };
+    return fhevc_launch_motion_rd_pu(fr, max_range, fhevc_rd_quant(qp, c->cfg.bit_depth), part_mode, k, kn(d_out), c->num_cus, s);
+  }, [&]() -> const char* {
+    if (const char* bad = rd_pu_mode_error(part_mode, in)) return bad;
+    const uintptr_t all = (uintptr_t)in.nodes | (uintptr_t)in.pus | (uintptr_t)in.pus_small | (uintptr_t)in.merge_pus | (uintptr_t)in.merge_pus_small |
+                          (uintptr_t)in.mvp_nodes | (uintptr_t)in.mvp_pus | (uintptr_t)in.mvp_pus_small | (uintptr_t)in.shapes | (uintptr_t)in.fold | (uintptr_t)d_out;
+    if (all & 3) return "bad partition-size RD-stage arguments (records are 4-byte aligned)";
+    const long long ctus = (long long)(num_frames - 1) * (ctu_row_end - ctu_row_begin) * c->ctus_x;
+    if (ctus > 0x7FFFFFFFLL) return "more than 2^31 - 1 CTUs";
+    // folding in place is one lane reading and writing one record; any other overlap of the two extents is a race between lanes
+    const uintptr_t extent = (uintptr_t)ctus * FHEVC_NODES * sizeof(fhevc_motion_rd_pu_node), f = (uintptr_t)in.fold, o = (uintptr_t)d_out;
+    if (in.fold && f != o && f < o + extent && o < f + extent) return "bad partition-size RD-stage arguments (fold overlaps the output without being it)";
+    return nullptr;
+  });
+}
+
+int fhevc_motion_rd_pu(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range, int part_mode,
+                       const fhevc_motion_rd_pu_inputs* inputs, fhevc_motion_rd_pu_node* out)
+{
+  const int rc = open_host_form(c, cur_luma && ref_luma && inputs && inputs->nodes && out, stride_samples, qp, max_range, FHEVC_MOTION_WIDE_MAX_RANGE,
+                                "bad partition-size RD-stage arguments");
+  if (rc != GO) return rc;
+  const fhevc_motion_rd_pu_inputs& in = *inputs;
+  if (const char* bad = rd_pu_mode_error(part_mode, in)) return fail(c, FHEVC_E_INVALID, bad);   // said before anything is staged
+  HostForm h(c);
+  const size_t bn = h.bytes(kNodes), bp = h.bytes(kPus), bs = h.bytes(kSmall), all = bn + bp + bs;
+  fhevc_motion_rd_pu_inputs d{};
+  d.nodes = h.in(c->d_amvp, all, in.nodes, bn); d.pus = h.in(c->d_amvp, all, in.pus, bp, bn); d.pus_small = h.in(c->d_amvp, all, in.pus_small, bs, bn + bp);
+  d.mvp_nodes = h.in(c->d_amvp_mvp, all / 2, in.mvp_nodes, bn / 2); d.mvp_pus = h.in(c->d_amvp_mvp, all / 2, in.mvp_pus, bp / 2, bn / 2);
+  d.mvp_pus_small = h.in(c->d_amvp_mvp, all / 2, in.mvp_pus_small, bs / 2, (bn + bp) / 2);
+  d.merge_pus = h.in(c->d_merge_pu, bp + bs, in.merge_pus, bp); d.merge_pus_small = h.in(c->d_merge_pu, bp + bs, in.merge_pus_small, bs, bp);
+  d.shapes = h.in(c->d_motion, bn, in.shapes, bn);
+  d.fold = h.in(c->d_qpel, bn, in.fold, bn);                       // folded in place on the device: the earlier records go up to where the new ones come from
+  fhevc_motion_rd_pu_node* d_out = h.out(c->d_qpel, bn, out, bn);
+  return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_rd_pu_device, qp, max_range, part_mode, &d, d_out, c->stream); });
+}
 
 // ---- merge-candidate costs per PU from the refined nodes (k_motion_merge_pu.hip) ----
 
@@ -927,6 +998,15 @@ int fhevc_p_tree_select_rd_device(fhevc_ctx* c, const fhevc_motion_rd_node* d_rd
                                          d_depth_min, d_depth_max, d_tree, stream);
 }
 
+// ... and on folded records of fhevc_motion_rd_pu*: bytes 0..11 are the RD record's
+int fhevc_p_tree_select_rd_pu_device(fhevc_ctx* c, const fhevc_motion_rd_pu_node* d_rd_pu, const fhevc_motion_rd_node* d_rd_merge, int skip_mask, int num_pictures,
+                                     int ctu_row_begin, int ctu_row_end, const fhevc_p_tree_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree,
+                                     void* stream)
+{
+  return fhevc_p_tree_select_rd_device(c, reinterpret_cast<const fhevc_motion_rd_node*>(d_rd_pu), d_rd_merge, skip_mask, num_pictures, ctu_row_begin, ctu_row_end, rule,
+                                       d_depth_min, d_depth_max, d_tree, stream);
+}
+
 int fhevc_p_tree_select_intra_device(fhevc_ctx* c, const fhevc_pu_shape_node* d_shapes, const fhevc_motion_merge_node* d_merge, const fhevc_motion_skip_node* d_skip,
                                      int skip_mask, const fhevc_intra_p_node* d_intra, int num_pictures, int ctu_row_begin, int ctu_row_end, const fhevc_p_tree_rule* rule,
                                      uint8_t* d_depth_min, uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream)
@@ -969,11 +1049,13 @@ int fhevc_intra_p(fhevc_ctx* c, int qp, const fhevc_node_cost* first, const fhev
 // with_merge: fhevc_p_tree_merge_frame -- the merge stage between refinement and tree; with_merge_pu: fhevc_p_tree_merge_pu_frame -- behind it the merge stage
 // per PU, and the selection that takes its costs; with_amvp: fhevc_p_tree_amvp_frame -- the re-pricing behind the refinements, and every later stage on its records;
 // with_intra: fhevc_p_tree_intra_frame -- behind the selection the zero-residual stage, the two first passes of the current picture and the intra stage, and the
-// tree that takes all of it
+// tree that takes all of it; with_rd: fhevc_p_tree_rd_frame -- the re-pricing keeps its predictor records, and behind the selection come the RD estimate of the
+// nodes' merge records, the RD estimates of 2Nx2N and of the selection's best and second size folded into one record per node, and the RD tree
+struct RdFrameOut { fhevc_motion_rd_node* rd_merge; fhevc_motion_rd_pu_node* rd_pu; };
 static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
                            const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes,
                            bool with_merge, fhevc_motion_merge_node* merge, bool with_merge_pu = false, bool with_amvp = false, bool with_intra = false, int skip_mask = 0,
-                           fhevc_intra_p_node* intra = nullptr)
+                           fhevc_intra_p_node* intra = nullptr, const RdFrameOut* with_rd = nullptr)
 {
   if (!c) return FHEVC_E_INVALID;
   if (!cur_luma || !ref_luma || !depth_min || !depth_max || stride_samples < c->cfg.width) return fail(c, FHEVC_E_INVALID, "bad tree-decision frame arguments");
@@ -984,7 +1066,7 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
     if (const char* bad = fhevc_pu_shape_rule_error(*shape_rule)) return fail(c, FHEVC_E_INVALID, bad);
   if (tree_rule)
     if (const char* bad = fhevc_p_tree_rule_error(*tree_rule)) return fail(c, FHEVC_E_INVALID, bad);
-  if (with_intra && (skip_mask < 0 || skip_mask > 3)) return fail(c, FHEVC_E_INVALID, "bad tree-decision frame arguments (skip_mask 0..3)");
+  if ((with_intra || with_rd) && (skip_mask < 0 || skip_mask > 3)) return fail(c, FHEVC_E_INVALID, "bad tree-decision frame arguments (skip_mask 0..3)");
   HostForm h(c);
   const size_t map = (size_t)c->num_ctus * 256, records = h.bytes(kNodes);
   Chain k = claim_chain(h, coarse_range != 0);
@@ -1003,6 +1085,18 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
     fhevc_motion_qpel_node* const d_priced = h.dev<fhevc_motion_qpel_node>(c->d_amvp, all);
     k.q_nodes_out = d_priced; k.q_pus_out = d_priced + (size_t)c->num_ctus * FHEVC_NODES; k.q_small_out = k.q_pus_out + (size_t)c->num_ctus * FHEVC_PUS;
   }
+  fhevc_motion_mvp *d_mvp_nodes = nullptr, *d_mvp_pus = nullptr, *d_mvp_small = nullptr;
+  fhevc_motion_rd_node* d_rd_merge = nullptr;
+  fhevc_motion_rd_pu_node* d_rd_pu = nullptr;
+  if (with_rd) {
+    const size_t all = h.bytes(kNodes) + h.bytes(kPus) + h.bytes(kSmall);
+    d_mvp_nodes = h.dev<fhevc_motion_mvp>(c->d_amvp_mvp, all / 2);
+    d_mvp_pus = d_mvp_nodes + (size_t)c->num_ctus * FHEVC_NODES; d_mvp_small = d_mvp_pus + (size_t)c->num_ctus * FHEVC_PUS;
+    d_rd_merge = h.dev<fhevc_motion_rd_node>(c->d_qpel, records);              // the refined nodes and PUs are dead once the re-pricing has read them
+    d_rd_pu = h.dev<fhevc_motion_rd_pu_node>(c->d_qpel_pu, h.bytes(kPus));
+    h.out(c->d_qpel, records, with_rd->rd_merge, records);
+    h.out(c->d_qpel_pu, h.bytes(kPus), with_rd->rd_pu, records);
+  }
   fhevc_motion_skip_node* d_skip = nullptr;
   fhevc_node_cost *d_first = nullptr, *d_first4 = nullptr;
   fhevc_intra_p_node* d_intra = nullptr;
@@ -1017,7 +1111,7 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
   return h.run(cur_luma, ref_luma, stride_samples, [&] {
     int rc = queue_chain(c, qp, search_range, coarse_range, k);
     if (rc == FHEVC_OK && with_amvp) {
-      rc = fhevc_motion_amvp_device(c, 2, 0, c->ctus_y, qp, k.q_nodes, k.q_pus, k.q_small, k.q_nodes_out, k.q_pus_out, k.q_small_out, nullptr, nullptr, nullptr, c->stream);
+      rc = fhevc_motion_amvp_device(c, 2, 0, c->ctus_y, qp, k.q_nodes, k.q_pus, k.q_small, k.q_nodes_out, k.q_pus_out, k.q_small_out, d_mvp_nodes, d_mvp_pus, d_mvp_small, c->stream);
       k.q_nodes = k.q_nodes_out; k.q_pus = k.q_pus_out; k.q_small = k.q_small_out;   // what every later stage reads
     }
     // absolute vectors of the centred chain reach +-64 and neighbouring CTUs have different centres: the merge stages look around zero at the full range there
@@ -1027,6 +1121,17 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
     if (rc == FHEVC_OK && with_merge_pu)
       rc = fhevc_pu_shape_select_merge_device(c, k.q_nodes, k.q_pus, k.q_small, d_merge_pus, d_merge_small, 1, 0, c->ctus_y, shape_rule, d_shapes, nullptr, nullptr, c->stream);
     else if (rc == FHEVC_OK) rc = fhevc_pu_shape_select_device(c, k.q_nodes, k.q_pus, k.q_small, 1, 0, c->ctus_y, shape_rule, d_shapes, nullptr, c->stream);
+    if (rc == FHEVC_OK && with_rd) {
+      rc = on_pair(c, fhevc_motion_rd_device, qp, merge_range, FHEVC_RD_SOURCE_MERGE, static_cast<const void*>(d_merge), static_cast<const fhevc_motion_mvp*>(nullptr), d_rd_merge,
+                   c->stream);
+      // 2Nx2N first, then the selection's best and its second size: the earlier record stays on a tie, as xCheckBestMode keeps the earlier mode
+      fhevc_motion_rd_pu_inputs in = { k.q_nodes, k.q_pus, k.q_small, d_merge_pus, d_merge_small, d_mvp_nodes, d_mvp_pus, d_mvp_small, d_shapes, nullptr };
+      if (rc == FHEVC_OK) rc = on_pair(c, fhevc_motion_rd_pu_device, qp, merge_range, 0, &in, d_rd_pu, c->stream);
+      in.fold = d_rd_pu;
+      if (rc == FHEVC_OK) rc = on_pair(c, fhevc_motion_rd_pu_device, qp, merge_range, 8, &in, d_rd_pu, c->stream);
+      if (rc == FHEVC_OK) rc = on_pair(c, fhevc_motion_rd_pu_device, qp, merge_range, 9, &in, d_rd_pu, c->stream);
+      return rc != FHEVC_OK ? rc : fhevc_p_tree_select_rd_pu_device(c, d_rd_pu, d_rd_merge, skip_mask, 1, 0, c->ctus_y, tree_rule, d_min, d_max, nullptr, c->stream);
+    }
     if (rc == FHEVC_OK && with_intra) {
       const int16_t* d_cur = c->d_pair + pair_plane(c);   // the current picture of the staged pair, as a batch of one frame
       rc = on_pair(c, fhevc_motion_skip_device, qp, merge_range, d_merge, d_skip, c->stream);
@@ -1072,6 +1177,15 @@ int fhevc_p_tree_intra_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_
 {
   return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge, true, true,
                          true, skip_mask, intra);
+}
+
+int fhevc_p_tree_rd_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                          const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, int skip_mask, uint8_t* depth_min, uint8_t* depth_max,
+                          fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge, fhevc_motion_rd_node* rd_merge, fhevc_motion_rd_pu_node* rd_pu)
+{
+  const RdFrameOut rd = { rd_merge, rd_pu };
+  return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge, true, true,
+                         false, skip_mask, nullptr, &rd);
 }
 
 }  // extern "C"

@@ -20,6 +20,15 @@
 // tiles and ONE plain store.  The writer lane of each node makes the choice.  16-bit intermediates are exact: forward as in k_motion_skip.hip, now also at
 // N = 4; the inverse clips to 16 bits by definition, and its accumulations stay below 32 * 32 768 * 90 < 2^31.  The quantiser's and dequantiser's numbers
 // per TU size travel by value.  No scratch, no HBM state between calls.
+//
+// The PU instances (fhevc_motion_rd_pu_device; PU = true): the same kernel with the prediction COMPOSED from the vectors of the two parts of one of HM's
+// partition sizes.  Per lane the node's size p (forced, or one dword of its selection record), the two parts' records at addresses that depend on lane,
+// node and p alone, the merged decision and the side bits -- computed by every lane of the node, as the node's record is --, and per 4x4 quadrant of the
+// lane's tile the part that holds it (RefinePuPass::qmask's arithmetic).  One prediction at the vector of the part that holds quadrant 0; only in a wave
+// where some tile straddles the cut (AMP of the 16x16 nodes, everything of the 8x8 nodes) a second one at the other part's vector, and the residual
+// registers are taken per quadrant: D[4 y + k] holds columns 2 k, 2 k + 1 of row y, so a quadrant is whole registers.  Everything behind the residual is
+// the code above, untouched; the writer lane folds its record into an earlier launch's where one is given.  The PU = false instances keep their argument
+// list (the PU arguments are a pack that is empty there) and their code.
 #include "fhevc_internal.h"
 #include "k_had8x8.h"
 #include "k_refine_tile.h"
@@ -250,11 +259,86 @@ __device__ __forceinline__ void rd_depth(short* s, int lane, int lvl, int wave, 
   __syncthreads();   // the tiles are read: the next depth rewrites them; the sums are in
 }
 
-// T = int16_t or uint8_t planes; MR = 8 or 64: the largest max_range the window is laid out for
-template <typename T, int MR>
-__global__ __launch_bounds__(256) void fhevc_motion_rd_kernel(FhevcFrames F, int max_range, FhevcRdQuant Q, int source, const unsigned* __restrict__ in,
-                                                              const unsigned* __restrict__ mvp, FhevcMotionRdNode* __restrict__ out)
+// ---- the PU instances: what one lane knows of its node's partition size ----
+struct RdPuArgs {
+  const unsigned *pus, *small;               // the refined (or re-priced) entries of the 124 and of the 384 PUs; small may be null
+  const unsigned *merge_pus, *merge_small;   // their merge records, or null
+  const unsigned *mvp_pus, *mvp_small;       // their predictor records, or null
+  const unsigned *shapes, *fold;             // the selection's records (part_mode 8, 9), an earlier launch's output; or null
+  int part_mode;
+};
+struct RdPuLane {
+  unsigned first = 0, other = 0;   // the vector dwords of the part that holds quadrant 0 of the lane's tile, and of the other part
+  unsigned info = 255u << 18;      // everything else in one register, which is all that lives through the transform: bits 0..11 the parts' side bits (at most
+                                   // 2 x 256), 12..13 merged, 14..17 bit k: quadrant k of the tile lies in the other part, 18..25 p, 26 both parts usable
+                                   // (before the INSIDE test), 27 this lane's tile needs the second prediction
+  __device__ __forceinline__ unsigned side() const { return info & 0xFFFu; }
+  __device__ __forceinline__ unsigned merged() const { return (info >> 12) & 3u; }
+  __device__ __forceinline__ unsigned flips() const { return (info >> 14) & 15u; }
+  __device__ __forceinline__ unsigned p() const { return (info >> 18) & 0xFFu; }
+  __device__ __forceinline__ bool ok() const { return (info >> 26) & 1u; }
+  __device__ __forceinline__ bool two() const { return (info >> 27) & 1u; }
+};
+// one part: the refined entry e of its family against its merge record (HM's uiMRGCost < uiMECost, strictly), the vector taken and its side bits.  Without
+// branches: an array that is not there is read in the refined entries instead (in bounds: the same entry, or half-way to it) and what was read is dropped
+__device__ __forceinline__ bool rd_pu_part(const unsigned* ref, const unsigned* mrg, const unsigned* mvp, long long e, int reach, unsigned& vec, unsigned& side, bool& merged)
 {
+  const unsigned* const m = mrg ? mrg : ref;
+  const unsigned* const pv = mvp ? mvp : ref;
+  const unsigned rc = ref[e * 4 + 2], rv = ref[e * 4 + 3], mc = mrg ? m[e * 4 + 1] : kRdMark, mv = m[e * 4 + 2], mi = m[e * 4 + 3] & 0xFFu;
+  const unsigned w = pv[e * 2 + 1];         // idx in the low byte (255: a marker), bits in the high one
+  merged = mc < rc;                         // a marker loses to anything
+  vec = merged ? mv : rv;
+  const bool ok = merged || (rc != kRdMark && !(mvp && (w & 0xFFu) == 255u));   // both markers: nothing to take
+  side = merged ? (mi == 4u ? 4u : mi + 1u) : mvp ? w >> 24 : (unsigned)(eg_bits(vec_x(rv)) + eg_bits(vec_y(rv)));
+  return ok && vec_in_reach(vec, reach);
+}
+// the lane's node k of level lvl in the CTU with output index oc; own_ok / own_vec / own_side: what the node's own record gives (p = 0).  No input byte
+// reaches an address: p is used only once it is one of the six two-part sizes that level has, and then selects among entries of this node
+__device__ __forceinline__ RdPuLane rd_pu_lane(const RdPuArgs& A, long long oc, int k, int lvl, int tx, int ty, int reach, bool own_ok, unsigned own_vec, unsigned own_side)
+{
+  RdPuLane L;
+  int p = A.part_mode;
+  if (p >= 8) p = (int)((A.shapes[(oc * FHEVC_NODES + k) * 4 + 3] >> (p == 8 ? 0 : 8)) & 0xFFu);   // best: byte 12, second: byte 13
+  L.info = (unsigned)p << 18;
+  if (p == 0) { L.first = L.other = own_vec; L.info = own_side | (own_ok ? 1u << 26 : 0u); return L; }
+  const bool two_part = p == 1 || p == 2 || (p >= 4 && p <= 7);
+  const bool amp = p >= 4;
+  const bool in_small = lvl == 3 || (lvl == 2 && amp);
+  const unsigned* ref = in_small ? A.small : A.pus;
+  if (!two_part || (lvl == 3 && amp) || !ref) return L;   // AMP of the 8x8 nodes, a family that is not there, 3 and 255: the marker
+  const int shape = amp ? p - 2 : p - 1;
+  const int e0 = lvl < 2 ? k * 12 + shape * 2 : lvl == 2 ? (amp ? (k - 5) * 8 + (shape - 2) * 2 : 60 + (k - 5) * 4 + shape * 2) : 128 + (k - 21) * 4 + shape * 2;
+  const long long e = oc * (in_small ? FHEVC_PUS_SMALL : FHEVC_PUS) + e0;
+  const unsigned* mrg = in_small ? A.merge_small : A.merge_pus;
+  const unsigned* mvp = in_small ? A.mvp_small : A.mvp_pus;
+  unsigned v0, v1, s0, s1;
+  bool m0, m1;
+  const bool ok0 = rd_pu_part(ref, mrg, mvp, e, reach, v0, s0, m0), ok1 = rd_pu_part(ref, mrg, mvp, e + 1, reach, v1, s1, m1);
+  L.info |= (s0 + s1) | (m0 ? 1u << 12 : 0u) | (m1 ? 2u << 12 : 0u) | (ok0 && ok1 ? 1u << 26 : 0u);
+  // which part holds each quadrant: positions in 4-sample units from the node's top (left) edge against the cut (getPartIndexAndSize)
+  const int tn = 8 >> lvl, s4 = 16 >> lvl;
+  const bool horiz = p == 1 || p == 4 || p == 5;
+  const int cut = !amp ? s4 / 2 : (p & 1) ? 3 * s4 / 4 : s4 / 4;
+  const int at = horiz ? (ty & (tn - 1)) * 2 : (tx & (tn - 1)) * 2;
+  unsigned parts = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) parts |= (at + (horiz ? q >> 1 : q & 1) >= cut ? 1u : 0u) << q;
+  const bool swap = (parts & 1u) != 0u;
+  L.first = swap ? v1 : v0; L.other = swap ? v0 : v1;
+  const unsigned flips = swap ? parts ^ 15u : parts;
+  L.info |= flips << 14 | (flips != 0u && v0 != v1 ? 1u << 27 : 0u);
+  return L;
+}
+
+// T = int16_t or uint8_t planes; MR = 8 or 64: the largest max_range the window is laid out for
+// PU (fhevc_motion_rd_pu_device): the prediction is composed from the two parts of a partition size; A...: ONE RdPuArgs then, empty otherwise -- a pack keeps
+// the plain instances' argument list, and so their code, what it was.  in / mvp are the nodes' own records there (source 1)
+template <typename T, int MR, bool PU, class... A>
+__global__ __launch_bounds__(256) void fhevc_motion_rd_kernel(FhevcFrames F, int max_range, FhevcRdQuant Q, int source, const unsigned* __restrict__ in,
+                                                              const unsigned* __restrict__ mvp, FhevcMotionRdNode* __restrict__ out, A... pu_args)
+{
+  static_assert(sizeof...(A) == (PU ? 1 : 0), "the PU arguments go with the PU instances");
   constexpr int RP = RefineGeom<MR>::RP;
   constexpr bool BIG = MR > FHEVC_MOTION_MAX_RANGE;
   constexpr int OVER = kTransformShorts + kFwdShorts + kInvShorts;                          // what lies over the dead window: 41 632 B
@@ -297,6 +381,17 @@ __global__ __launch_bounds__(256) void fhevc_motion_rd_kernel(FhevcFrames F, int
       marked = marked || (w & 0xFFu) == 255u;
       side = w >> 24;
     } else side = (unsigned)(eg_bits(vx) + eg_bits(vy));
+    RdPuLane L;
+    if constexpr (PU) {
+      const RdPuArgs pa = (pu_args, ...);
+      // the lane number and the level made opaque once per CTU: what the part addresses derive from it is then computed here, inside the loop.  Hoisted out of it, those
+      // values lived through the whole loop in nine registers more than the 256 there are.  (One is still missing: DESIGN 4.12)
+      int ln = lane, wv = wave;   // the level as the scalar it is
+      asm volatile("" : "+v"(ln), "+s"(wv));
+      const RefineNode M(wv, ln & 7, ln >> 3);
+      L = rd_pu_lane(pa, oc, M.nidx, wv, ln & 7, ln >> 3, reach, !marked && vec_in_reach(rvec, reach), rvec, side);
+      side = L.side();
+    }
     // ---- stage the part of the reference window that max_range reaches ----
     __syncthreads();  // the previous CTU's readers of the buffers and of the sums are done
     refine_stage_window_reach<T, MR>(s_ref, plane, W.ref_base, F, cx, cy, tid, max_range);
@@ -304,15 +399,42 @@ __global__ __launch_bounds__(256) void fhevc_motion_rd_kernel(FhevcFrames F, int
     const int px = cx * 64 + tx * 8, py = cy * 64 + ty * 8;
     const bool inside = (px + 8 <= F.width) && (py + 8 <= F.height);
     unsigned O[32];
-    load_tile8x8(plane, W.cur_base, F, px, py, inside, O);
-    const bool valid = node_in && !marked && vec_in_reach(rvec, reach);
-    const int qx = valid ? vx : 0, qy = valid ? vy : 0;   // an invalid node predicts at the zero vector and drops the result: no read outside the window
+    if constexpr (!PU) load_tile8x8(plane, W.cur_base, F, px, py, inside, O);
+    const bool valid = PU ? node_in && L.ok() : node_in && !marked && vec_in_reach(rvec, reach);
+    const int qx = valid ? (PU ? vec_x(L.first) : vx) : 0, qy = valid ? (PU ? vec_y(L.first) : vy) : 0;   // an invalid node predicts at the zero vector and drops the result: no read outside the window
     __syncthreads();
     // ---- the residual of this lane's tile at its node's vector ----
     unsigned D[32];
     {
       int v[64];
-      refine_tile_at<true, RP>(s_ref, s_taps, arith, tx, ty, qx, qy, O, D, v);
+      if constexpr (!PU) refine_tile_at<true, RP>(s_ref, s_taps, arith, tx, ty, qx, qy, O, D, v);
+      else {
+        // the predictions are taken against a zero tile and the original is added behind them: the original live across a second prediction cost
+        // 26 registers more (packed 16-bit arithmetic wraps, so o + (0 - p) is o - p)
+        unsigned Z[32];
+#pragma unroll
+        for (int i = 0; i < 32; ++i) Z[i] = 0u;
+        refine_tile_at<true, RP>(s_ref, s_taps, arith, tx, ty, qx, qy, Z, D, v);
+        // ---- ... and, where some tile of the wave straddles the cut, at the other part's vector: the quadrants of that part come from there ----
+        const bool two = valid && L.two();
+        if (__builtin_amdgcn_ballot_w64(two) != 0) {
+          unsigned E[32];
+          refine_tile_at<true, RP>(s_ref, s_taps, arith, tx, ty, two ? vec_x(L.other) : qx, two ? vec_y(L.other) : qy, Z, E, v);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const bool flip = two && ((L.flips() >> q) & 1u) != 0u;
+#pragma unroll
+            for (int y = 0; y < 4; ++y) {
+              const int r = 4 * ((q >> 1) * 4 + y) + (q & 1) * 2;
+              D[r] = flip ? E[r] : D[r]; D[r + 1] = flip ? E[r + 1] : D[r + 1];
+            }
+          }
+        }
+        unsigned P[32];
+        load_tile8x8(plane, W.cur_base, F, px, py, inside, P);
+#pragma unroll
+        for (int i = 0; i < 32; ++i) D[i] = pk_add(P[i], D[i]);
+      }
     }
     __syncthreads();  // the window is dead: the transform buffers and the matrices lie over it
     {
@@ -346,7 +468,21 @@ __global__ __launch_bounds__(256) void fhevc_motion_rd_kernel(FhevcFrames F, int
         o.flags = (uint8_t)((any0 == 0u ? 1 : 0) | (zero_half ? 2 : 0) | (split ? 4 : 0)); o.tu_split = (uint8_t)split;
         o.mvx = (short)vx; o.mvy = (short)vy;
       }
-      out[rec] = o;
+      if constexpr (PU) {
+        const RdPuArgs pa = (pu_args, ...);
+        FhevcMotionRdPuNode u;
+        u.dist = o.dist; u.cost_rd = o.cost_rd; u.bits = o.bits; u.flags = o.flags; u.tu_split = o.tu_split;
+        u.part = (uint8_t)(valid ? L.p() : 255u); u.merged = (uint8_t)(valid ? L.merged() : 0u); u.pad[0] = u.pad[1] = 0;
+        FhevcMotionRdPuNode* const dst = reinterpret_cast<FhevcMotionRdPuNode*>(out);
+        if (pa.fold) {
+          // the earlier record stays unless this one is valid and strictly cheaper (a marker's cost_rd is the largest number).  In place the earlier
+          // record is read through the output pointer: this lane reads it, then writes it
+          const FhevcMotionRdPuNode* const src = reinterpret_cast<const void*>(pa.fold) == reinterpret_cast<const void*>(out) ? dst : reinterpret_cast<const FhevcMotionRdPuNode*>(pa.fold);
+          const FhevcMotionRdPuNode f = src[rec];
+          if (!(valid && u.cost_rd < f.cost_rd)) u = f;
+        }
+        dst[rec] = u;
+      } else out[rec] = o;
     }
   }
 }
@@ -362,6 +498,21 @@ hipError_t fhevc_launch_motion_rd(const FhevcFrames& fr, int max_range, const Fh
   const unsigned* in = reinterpret_cast<const unsigned*>(d_in);
   const unsigned* mvp = reinterpret_cast<const unsigned*>(d_mvp);
   return refine_launch<FHEVC_MOTION_WIDE_MAX_RANGE>(fr, source == 0 || source == 1, max_range, num_cus, {4, true}, {2, true}, stream, [&](auto t, auto, auto mr, const RefineLaunch& L) {
-    return refine_launch_kernel<&fhevc_motion_rd_kernel<decltype(t), decltype(mr)::value>>(L, fr, max_range, q, source, in, mvp, d_out);
+    return refine_launch_kernel<&fhevc_motion_rd_kernel<decltype(t), decltype(mr)::value, false>>(L, fr, max_range, q, source, in, mvp, d_out);
+  });
+}
+
+// the PU instances: ONE workgroup per CU by their registers (256 VGPRs + 1 AGPR: the resource table in DESIGN 4.12), which the occupancy query
+// answers; the caps stay.  Every record array as dwords
+hipError_t fhevc_launch_motion_rd_pu(const FhevcFrames& fr, int max_range, const FhevcRdQuant& q, int part_mode, const FhevcMotionRdPuInputs& I, FhevcMotionRdPuNode* d_out,
+                                     int num_cus, hipStream_t stream)
+{
+  static_assert(sizeof(FhevcMotionRdPuNode) == 16 && sizeof(FhevcPuShapeNode) == 16, "record layouts");
+  const auto dw = [](const void* p) { return reinterpret_cast<const unsigned*>(p); };
+  const RdPuArgs pa = { dw(I.pus), dw(I.pus_small), dw(I.merge_pus), dw(I.merge_pus_small), dw(I.mvp_pus), dw(I.mvp_pus_small), dw(I.shapes), dw(I.fold), part_mode };
+  const bool mode_ok = part_mode >= 0 && part_mode <= 9 && part_mode != 3 && (part_mode == 0 || I.pus) && (part_mode < 8 || I.shapes);
+  return refine_launch<FHEVC_MOTION_WIDE_MAX_RANGE>(fr, I.nodes && d_out && mode_ok, max_range, num_cus, {4, true}, {2, true}, stream, [&](auto t, auto, auto mr, const RefineLaunch& L) {
+    return refine_launch_kernel<&fhevc_motion_rd_kernel<decltype(t), decltype(mr)::value, true, RdPuArgs>>(L, fr, max_range, q, 1, dw(I.nodes), dw(I.mvp_nodes),
+                                                                                                         reinterpret_cast<FhevcMotionRdNode*>(d_out), pa);
   });
 }

@@ -1171,6 +1171,87 @@ int  fhevc_p_tree_select_rd_device(fhevc_ctx* ctx, const fhevc_motion_rd_node* d
                                    int num_pictures, int ctu_row_begin, int ctu_row_end, const fhevc_p_tree_rule* rule, uint8_t* d_depth_min,
                                    uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream);
 
+/* ---- config 4 (P slices): the RD estimate of a CU node under any of HM's seven inter partition sizes (the PU instances of k_motion_rd.hip) ---------
+ * fhevc_motion_rd prices one vector per node, so the RD tree above speaks of 2Nx2N and merge alone, while the selection (fhevc_pu_shape_select*) picks a
+ * partition size on Hadamard costs.  This entry point closes that gap: the CU's prediction is composed from its two PUs' vectors -- what
+ * TComPrediction::motionCompensation does per PU -- before the residual goes through transform, quantiser and rebuild; several launches fold into one record
+ * per node, and the RD tree reads the folded records.
+ *   The record (pinned: 16 bytes without padding; cost_rd stays in dword 1 and flags in byte 10, where the tree kernels read): */
+typedef struct {
+  uint32_t dist;  uint32_t cost_rd;  uint16_t bits;  uint8_t flags;  uint8_t tu_split;   /* bytes 0..11: fhevc_motion_rd_node's, same meaning */
+  uint8_t  part;            /* the PartSize priced, 255 in a marker record */
+  uint8_t  merged;          /* bit i: part i took its merge vector */
+  uint8_t  pad[2];          /* written 0 */
+} fhevc_motion_rd_pu_node;  /* 16 bytes; marker: dist = cost_rd = 0xFFFFFFFF, bits = 0xFFFF, flags = tu_split = merged = 0, part = 255 */
+/*   Inputs travel in one struct: device pointers for the device form, host pointers for the host form.  Counts per CTU: 85 / 124 / 384. */
+typedef struct {
+  const fhevc_motion_qpel_node  *nodes, *pus, *pus_small;       /* refined or re-priced; 85 / 124 / 384 per CTU */
+  const fhevc_motion_merge_node *merge_pus, *merge_pus_small;   /* fhevc_motion_merge_pu*'s records, or NULL */
+  const fhevc_motion_mvp        *mvp_nodes, *mvp_pus, *mvp_pus_small;   /* the re-pricing's predictor records, or NULL */
+  const fhevc_pu_shape_node     *shapes;                        /* needed by part_mode 8 and 9 only */
+  const fhevc_motion_rd_pu_node *fold;                          /* an earlier launch's output, or NULL */
+} fhevc_motion_rd_pu_inputs;
+/*   part_mode 0, 1, 2, 4, 5, 6, 7: that HM PartSize (FHEVC_PART_*) for every node; 8: the node's shapes[k].best; 9: the node's shapes[k].second.
+ *   Per node k of level l (s = 64 >> l), with p the size chosen for it; the node is INSIDE as everywhere else.
+ *   p = 0: one vector, the node's own record in nodes.  Validity and side bits are exactly fhevc_motion_rd_device's with FHEVC_RD_SOURCE_EXPLICIT, with
+ * mvp_nodes given or not.  The node's own merge candidate keeps entering at the tree, as before.
+ *   p in {1, 2, 4..7}: the two parts are the entries the cost table of fhevc_pu_shape_select names (the formulas there: pus / pus_small by k and shape).
+ * The size is unavailable for that node, and the record is a marker, in three cases: AMP at level 3, a NULL family, and p = 3 / 255 (or any other number a
+ * selection record may hold that is no PartSize).
+ *   Per part the selection's own rule applies (fhevc_pu_shape_select_merge, HM's uiMRGCost < uiMECost): if the family's merge array is given and the merge
+ * record's cost_best is strictly smaller than the refined record's, the part takes the merge record's vector; its side bits are then idx + 1, or 4 for
+ * idx == 4.  Otherwise it takes the refined vector; its side bits are then bits of its predictor record where that family's mvp_* is given (idx == 255
+ * makes the part invalid), else eg(mvx) + eg(mvy).  A marker loses to anything; both markers make the part invalid; a part whose chosen vector is beyond
+ * 4 max_range + 3 in either component is invalid.
+ *   The node is valid iff it is INSIDE and both parts are valid.
+ *   The prediction is fhevc_motion_refine's prediction per sample at the vector of the part whose getPartIndexAndSize rectangle holds the sample.
+ *   Residual, TU sizes, transform, quantiser, dequantiser, inverse transform, SSE, bit estimate, TU choice and cost_rd are word for word those of
+ * fhevc_motion_rd; side_bits is the sum over the parts.
+ *   The TU tree does not depend on the partition size: under this configuration the interSplitFlag of TComDataCU::getQuadtreeTULog2MinSizeInCU
+ * (TComDataCU.cpp:1478-1503) needs QuadtreeTUMaxDepthInter == 1, and the cfg has 3, so a two-part CU gets the TU sizes of a 2Nx2N CU.
+ *   The bits of the part mode and of the merge flags are left out, as every other stage leaves them out.
+ *   Fold: with fold given, the record written is the new one iff it is valid and (the fold record is a marker, i.e. its cost_rd is 0xFFFFFFFF, or the new
+ * cost_rd < the fold record's cost_rd), strictly; otherwise the fold record's 16 bytes are written unchanged.  HM's xCheckBestMode keeps the earlier mode
+ * on a tie, so a caller gets HM's order by launching in HM's order.  fold == d_out is allowed: each record is read and written by the same lane.  An
+ * overlap of the two extents that is not equality is rejected.
+ *   Device form: planes, band, frame pairing, the compact-over-the-band layout, qp 0..51, max_range 1..64, the stream contract and asynchrony are
+ * fhevc_motion_rd_device's.  The output is written over exactly its extent ((num_frames - 1) * band CTUs * 85 records); an empty band writes nothing.  No
+ * per-context or HBM state: launches with different QPs, ranges and part modes may be in flight on two streams.  FHEVC_E_INVALID with a fhevc_last_error
+ * text (nothing is launched or written): what fhevc_motion_rd_device rejects; a null struct, nodes or d_out; part_mode outside {0, 1, 2, 4..9}; a non-zero
+ * part_mode without pus; 8 / 9 without shapes; a merge or predictor array whose family's records are NULL; any pointer that is not 4-byte aligned; the
+ * partial overlap above.  Timed under slot 31 of fhevc_kernel_timing (30 stays rejected).
+ *   The kernel is a further instantiation of the RD kernel: the same mapping and buffers; per lane the node's p, its two parts' records, the merged decision
+ * and the side bits; one prediction at the vector of the part that holds the first 4x4 quadrant of the lane's tile, and only where a tile straddles the cut
+ * (AMP of the 16x16 nodes, both sizes of the 8x8 nodes) a second one at the other part's vector.
+ * NOT covered: what fhevc_motion_rd does not cover (RDOQ, the third TU depth of 32x32 and 16x16 CUs, chroma, CABAC's contexts), the bits of the part mode and
+ * of the merge flag, a skip test per PU, the temporal merge candidate, several sizes in one launch.  The encoder hook does not consume this output. */
+int  fhevc_motion_rd_pu_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames,
+                               int ctu_row_begin, int ctu_row_end, int qp, int max_range, int part_mode, const fhevc_motion_rd_pu_inputs* inputs,
+                               fhevc_motion_rd_pu_node* d_out, void* stream);
+/* one picture pair, host buffers (both planes with the same stride), synchronous, as fhevc_motion_rd; every array of inputs is a host array of numCtus * 85 /
+ * 124 / 384 entries or NULL; out: numCtus * 85 (out == inputs->fold is allowed) */
+int  fhevc_motion_rd_pu(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range, int part_mode,
+                        const fhevc_motion_rd_pu_inputs* inputs, fhevc_motion_rd_pu_node* out);
+
+/* The RD tree on folded records: typed forwarders to fhevc_p_tree_select_rd[_device] -- folded fhevc_motion_rd_pu_node records stand where rd_explicit
+ * stands (bytes 0..11 are the same fields); no new tree kernel, the device form is timed under slot 17.  With the records of part_mode 0, 8 and 9 folded
+ * this is HM with 2Nx2N, the selection's two sizes and merge as its inter candidates.  FHEVC_E_INVALID: what fhevc_p_tree_select_rd rejects. */
+int  fhevc_p_tree_select_rd_pu(const fhevc_motion_rd_pu_node* rd_pu /* 85 */, const fhevc_motion_rd_node* rd_merge /* 85 */, int skip_mask, int valid_w,
+                               int valid_h, const fhevc_p_tree_rule* rule, uint8_t* depth_min /* 256 or NULL */, uint8_t* depth_max /* 256 or NULL */,
+                               fhevc_p_tree_node* tree /* 85 or NULL */);
+int  fhevc_p_tree_select_rd_pu_device(fhevc_ctx* ctx, const fhevc_motion_rd_pu_node* d_rd_pu, const fhevc_motion_rd_node* d_rd_merge, int skip_mask,
+                                      int num_pictures, int ctu_row_begin, int ctu_row_end, const fhevc_p_tree_rule* rule, uint8_t* d_depth_min,
+                                      uint8_t* d_depth_max, fhevc_p_tree_node* d_tree, void* stream);
+/* One picture pair, host buffers, synchronous -- the first frame call that reaches the RD stage.  On the context's stream, in order: the chain of
+ * fhevc_p_tree_amvp_frame up to and including fhevc_pu_shape_select_merge_device, this time keeping the re-pricing's predictor records;
+ * fhevc_motion_rd_device on the nodes' merge records; fhevc_motion_rd_pu_device with part_mode 0, then 8 and then 9 folded in place;
+ * fhevc_p_tree_select_rd_pu_device with skip_mask.  The RD launches run at the range of the chain's merge stages (search_range, or 64 around centres).
+ * Downloads the two maps and, where asked (non-NULL), the shapes, the nodes' merge records, their RD records and the folded RD records, numCtus * 85 each.
+ * coarse_range 0 and 1..14 as for the other frame calls. */
+int  fhevc_p_tree_rd_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                           const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, int skip_mask, uint8_t* depth_min, uint8_t* depth_max,
+                           fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge, fhevc_motion_rd_node* rd_merge, fhevc_motion_rd_pu_node* rd_pu);
+
 /* ---- config 4 (P slices): intra candidate costs per CU node (k_intra_p.hip) -----------------------------------------------------------------------
  * HM checks intra at every CU of a P slice (TEncCu.cpp:797-816): xCheckRDCostIntra(SIZE_2Nx2N) at every depth, SIZE_NxN at the 8x8 level, both only while
  * the best mode so far has a non-zero CBF.  Without that candidate a node whose content is not in the reference picture -- uncovered background, the second
@@ -1269,6 +1350,7 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
  * rejected -- and 25 = the re-pricing against neighbour predictors (fhevc_motion_amvp*).  24 is not a slot: it stays rejected, as does any number above 25
  * -- except 27 = the intra candidate costs of P pictures (fhevc_intra_p*).  26 is not a slot: it stays rejected, as does any number above 27
  * -- except 29 = the RD estimate (fhevc_motion_rd*).  28 is not a slot: it stays rejected, as does any number above 29.
+ * -- except 31 = the RD estimate under a partition size (fhevc_motion_rd_pu*).  30 is not a slot: it stays rejected, as does any number above 31.
  * The tree that stops at a skip (fhevc_p_tree_select_skip_device), the tree that takes the intra candidate (fhevc_p_tree_select_intra_device) and the tree
  * on RD costs (fhevc_p_tree_select_rd_device) are timed under 17 */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
