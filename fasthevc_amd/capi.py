@@ -48,6 +48,7 @@ SYMBOLS = [
     "fhevc_intra_p", "fhevc_intra_p_device", "fhevc_intra_p_picture", "fhevc_p_tree_select_intra", "fhevc_p_tree_select_intra_device", "fhevc_p_tree_intra_frame",
     "fhevc_motion_rd", "fhevc_motion_rd_device", "fhevc_motion_rd_lambda_q8", "fhevc_p_tree_select_rd", "fhevc_p_tree_select_rd_device",
     "fhevc_motion_rd_pu", "fhevc_motion_rd_pu_device", "fhevc_p_tree_select_rd_pu", "fhevc_p_tree_select_rd_pu_device", "fhevc_p_tree_rd_frame",
+    "fhevc_intra_rd", "fhevc_intra_rd_device", "fhevc_p_tree_rd_intra_frame",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -120,6 +121,8 @@ MOTION_RD_PU_DTYPE = np.dtype([("dist", np.uint32), ("cost_rd", np.uint32), ("bi
                                ("part", np.uint8), ("merged", np.uint8), ("pad", np.uint8, (2,))])
 # part_mode of fhevc_motion_rd_pu*: a PART_* number for every node, or the selection's best / second size per node
 RD_PART_BEST, RD_PART_SECOND = 8, 9
+# part of a record of fhevc_intra_rd*: the intra candidate (FHEVC_RD_PART_INTRA); its mode lies in pad[0]
+RD_PART_INTRA = 16
 RD_TU_SPLIT = 4
 # fhevc_motion_mvp: the predictor fhevc_motion_amvp* priced an entry against (src: 0..4 = L, A, AR, BL, AL, 5 = a filled zero; idx = src = 255: no price)
 MOTION_MVP_DTYPE = np.dtype([("px", np.int16), ("py", np.int16), ("idx", np.uint8), ("num_spatial", np.uint8), ("src", np.uint8), ("bits", np.uint8)])
@@ -298,6 +301,9 @@ def load_library(path=None):
     lib.fhevc_p_tree_select_rd_pu.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp]
     lib.fhevc_p_tree_select_rd_pu_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp, vp]
     lib.fhevc_p_tree_rd_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.fhevc_intra_rd.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]
+    lib.fhevc_intra_rd_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp]
+    lib.fhevc_p_tree_rd_intra_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), C.c_int, vp, vp, vp, vp, vp, vp, vp]
     lib.fhevc_p_tree_intra_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), C.c_int, vp, vp, vp, vp, vp]
     lib.fhevc_predict_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, vp, vp]
     lib.fhevc_alloc_host.argtypes = [vp, C.c_size_t]
@@ -903,6 +909,32 @@ class Context:
         self._check(self.lib.fhevc_motion_rd_pu_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range, part_mode,
                                                        C.byref(inputs) if inputs is not None else None, d_out, stream))
 
+    def intra_rd(self, plane, first, fold=None, rd_merge=None, skip_mask=0, origin=0, stride=None, qp=32):
+        """config 4: the RD estimate of the intra candidate of every CU node of one picture -- first [numCtus, 85] NODE_DTYPE (the first pass's records: the
+        mode priced), fold: MOTION_RD_PU_DTYPE records to fold into or None, rd_merge: MOTION_RD_DTYPE records for the calm gate under skip_mask or None
+        -> [numCtus, 85] MOTION_RD_PU_DTYPE (part RD_PART_INTRA, the mode in pad[0], where the intra candidate was written)"""
+        flat = np.ascontiguousarray(plane).reshape(-1)
+        assert flat.dtype == np.int16
+        stride = stride if stride is not None else plane.shape[-1]
+        arrays = []
+        for a in (first, fold, rd_merge):
+            if a is not None:
+                a = np.ascontiguousarray(a).reshape(-1)
+                assert a.dtype.itemsize == 16 and a.size == self.num_ctus * NODES_PER_CTU
+            arrays.append(a)
+        out = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_RD_PU_DTYPE)
+        self._check(self.lib.fhevc_intra_rd(self.h, flat.ctypes.data + 2 * origin, stride, qp, *[a.ctypes.data if a is not None else None for a in arrays], skip_mask,
+                                            out.ctypes.data))
+        return out.reshape(self.num_ctus, NODES_PER_CTU)
+
+    def intra_rd_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_first, d_out, d_fold=None, d_rd_merge=None, skip_mask=0, rows=None, stream=None,
+                        qp=32):
+        """every picture of the batch (no pairing): d_first num_frames * band CTUs * 85 first-pass records, d_out as many RD records (16 B), gated by d_rd_merge
+        under skip_mask and folded into d_fold where those are given (d_fold may be d_out).  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_intra_rd_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, d_first, d_fold, d_rd_merge, skip_mask,
+                                                   d_out, stream))
+
     def motion_merge_pu(self, cur_plane, ref_plane, refined, origin=0, stride=None, qp=32, max_range=4, with_pus=True, with_small=True):
         """config 4: the cheapest merge candidate of every PU from the refined square nodes [numCtus, 85] (MOTION_QPEL_DTYPE; only cost_best, mvx, mvy are
         read) -> ([numCtus, 124], [numCtus, 384]) MOTION_MERGE_DTYPE in the orders of motion_pu_index / motion_pu_small_index; None for a family not asked for"""
@@ -1212,6 +1244,22 @@ class Context:
         self._check(self.lib.fhevc_p_tree_rd_frame(self.h, cur, ref, stride, qp, search_range, coarse_range, C.byref(shape_rule) if shape_rule is not None else None,
                                                    C.byref(tree_rule) if tree_rule is not None else None, skip_mask, dmin.ctypes.data, dmax.ctypes.data,
                                                    *[a.ctypes.data if a is not None else None for a in arrays]))
+        out = (dmin.reshape(self.num_ctus, 256), dmax.reshape(self.num_ctus, 256))
+        for a in arrays:
+            out += (a.reshape(self.num_ctus, NODES_PER_CTU),) if a is not None else ()
+        return out
+
+    def p_tree_rd_intra_frame(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=8, coarse_range=0, shape_rule=None, tree_rule=None, skip_mask=3,
+                              with_shapes=False, with_merge=False, with_rd_merge=False, with_rd_pu=False, with_first=False):
+        """p_tree_rd_frame with the intra candidate: behind the folded inter records the first pass of the current picture and intra_rd gated and folded in
+        place, then the RD tree -> (depth_min, depth_max) [numCtus, 256], then the records asked for [numCtus, 85]: p_tree_rd_frame's four and NODE_DTYPE"""
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
+        dmin, dmax = np.zeros(self.num_ctus * 256, np.uint8), np.zeros(self.num_ctus * 256, np.uint8)
+        wanted = ((with_shapes, SHAPE_DTYPE), (with_merge, MOTION_MERGE_DTYPE), (with_rd_merge, MOTION_RD_DTYPE), (with_rd_pu, MOTION_RD_PU_DTYPE), (with_first, NODE_DTYPE))
+        arrays = [np.zeros(self.num_ctus * NODES_PER_CTU, dt) if want else None for want, dt in wanted]
+        self._check(self.lib.fhevc_p_tree_rd_intra_frame(self.h, cur, ref, stride, qp, search_range, coarse_range, C.byref(shape_rule) if shape_rule is not None else None,
+                                                         C.byref(tree_rule) if tree_rule is not None else None, skip_mask, dmin.ctypes.data, dmax.ctypes.data,
+                                                         *[a.ctypes.data if a is not None else None for a in arrays]))
         out = (dmin.reshape(self.num_ctus, 256), dmax.reshape(self.num_ctus, 256))
         for a in arrays:
             out += (a.reshape(self.num_ctus, NODES_PER_CTU),) if a is not None else ()

@@ -51,9 +51,9 @@ struct fhevc_ctx {
   bool timing = false;
   std::vector<TimedLaunch> pending;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-  // per timing slot (14, 16, 18, 20, 22, 24, 26, 28 and 30 are not in use); config 4's slots and its staging buffers d_pair .. d_intra_p: the tables in fhevc_motion_api.hip
-  double sum_ms[32] = {};
-  uint64_t launches[32] = {};
+  // per timing slot (14, 16, 18, 20, 22, 24, 26, 28, 30 and 32 are not in use); config 4's slots and its staging buffers d_pair .. d_intra_p: the tables in fhevc_motion_api.hip
+  double sum_ms[34] = {};
+  uint64_t launches[34] = {};
   double* d_act = nullptr;
   int16_t* d_pair = nullptr;
   FhevcMotionNode *d_motion = nullptr, *d_motion_pu = nullptr, *d_motion_pu_small = nullptr, *d_centres = nullptr;

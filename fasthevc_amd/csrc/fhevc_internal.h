@@ -369,6 +369,14 @@ struct FhevcMotionRdPuInputs {
 hipError_t fhevc_launch_motion_rd_pu(const FhevcFrames& fr, int max_range, const FhevcRdQuant& q, int part_mode, const FhevcMotionRdPuInputs& I, FhevcMotionRdPuNode* d_out,
                                      int num_cus, hipStream_t stream);
 
+// ... and of the intra candidate (the intra instances of k_motion_rd.hip): ONE mode per node, the first pass's, predicted per TU from the first pass's own
+// lines; the record is a FhevcMotionRdPuNode with part kRdPartIntra and the mode in pad[0].  fr: num_frames pictures, no pairing; d_first: num_frames * band
+// CTUs * 85 first-pass records of which satd and the low byte of mode are read; d_fold (an earlier launch's records; d_fold == d_out is allowed) and
+// d_rd_merge (the merge records' RD records, for the calm gate under skip_mask 0..3) may be null
+constexpr int kRdPartIntra = 16;   // FHEVC_RD_PART_INTRA
+hipError_t fhevc_launch_intra_rd(const FhevcFrames& fr, const FhevcRdQuant& q, const FhevcNodeCost* d_first, const FhevcMotionRdPuNode* d_fold,
+                                 const FhevcMotionRdNode* d_rd_merge, int skip_mask, FhevcMotionRdPuNode* d_out, int num_cus, hipStream_t stream);
+
 // ---- ... and of the PUs' vectors (k_motion_refine_pu.hip; config 4) --------------------------------------------------
 // fr, max_range (1 .. FHEVC_MOTION_WIDE_MAX_RANGE: up to FHEVC_MOTION_MAX_RANGE the MR = 8 layout, above it the MR = 64 layout with its window in dynamic LDS),
 // cost as fhevc_launch_motion_refine; d_pus / d_out_pus: (num_frames - 1) * band CTUs * 124 entries in the order of fhevc_motion_pu_index, d_pus_small /

@@ -52,6 +52,7 @@ template <> struct Kernel<fhevc_motion_mvp> { using T = FhevcMotionMvp; };
 template <> struct Kernel<fhevc_intra_p_node> { using T = FhevcIntraPNode; };
 template <> struct Kernel<fhevc_motion_rd_node> { using T = FhevcMotionRdNode; };
 template <> struct Kernel<fhevc_motion_rd_pu_node> { using T = FhevcMotionRdPuNode; };
+template <> struct Kernel<fhevc_node_cost> { using T = FhevcNodeCost; };
 template <class P> typename Kernel<P>::T* kn(P* p) { return reinterpret_cast<typename Kernel<P>::T*>(p); }
 template <class P> const typename Kernel<P>::T* kn(const P* p) { return reinterpret_cast<const typename Kernel<P>::T*>(p); }
 static_assert(sizeof(fhevc_motion_node) == 16 && sizeof(FhevcMotionNode) == 16 && sizeof(fhevc_motion_qpel_node) == 16 && sizeof(FhevcMotionQpelNode) == 16, "node layouts");
@@ -71,6 +72,9 @@ static_assert(sizeof(fhevc_motion_rd_pu_node) == 16 && offsetof(fhevc_motion_rd_
               offsetof(fhevc_motion_rd_pu_node, tu_split) == offsetof(fhevc_motion_rd_node, tu_split) && sizeof(FhevcMotionRdPuNode) == 16 &&
               offsetof(fhevc_pu_shape_node, best) == 12 && offsetof(fhevc_pu_shape_node, second) == 13, "RD record of a partition size");
 static_assert(sizeof(fhevc_node_cost) == 16 && offsetof(fhevc_node_cost, satd) == 0 && offsetof(fhevc_node_cost, mode) == 4, "first-pass record layout");
+// the intra candidate's RD record is the partition-size one: the mode lies in pad[0], byte 14, and part holds a number no PartSize has
+static_assert(FHEVC_RD_PART_INTRA == kRdPartIntra && FHEVC_RD_PART_INTRA > 9 && FHEVC_RD_PART_INTRA != 255 && offsetof(fhevc_motion_rd_pu_node, pad) == 14 &&
+              offsetof(FhevcMotionRdPuNode, pad) == 14 && sizeof(FhevcNodeCost) == sizeof(fhevc_node_cost), "RD record of the intra candidate");
 static_assert(FHEVC_PUS_PER_CTU == FHEVC_PUS && FHEVC_PUS_SMALL_PER_CTU == FHEVC_PUS_SMALL, "PU counts");
 static_assert(sizeof(fhevc_motion_mvp) == 8 && offsetof(fhevc_motion_mvp, idx) == 4 && offsetof(fhevc_motion_mvp, bits) == 7 && offsetof(FhevcMotionMvp, bits) == 7,
               "predictor record layout");
@@ -131,13 +135,17 @@ int device_form(fhevc_ctx* c, bool args_ok, const char* bad_args, const Batch& b
 //                                              records in d_merge_pu, the selection's records in d_motion; the folded records in d_qpel, in and out
 //   (fhevc_p_tree_rd_frame)                    fhevc_p_tree_amvp_frame's buffers, with d_amvp_mvp; the merge records' RD records in d_qpel and the folded RD
 //                                              records in the head of d_qpel_pu: the re-pricing has read the refined nodes and PUs by then
+//   (fhevc_intra_rd)                            the picture in the second plane of d_pair, the first-pass records in the head of d_first_p, the merge records' RD
+//                                              records in d_qpel, the folded records in the head of d_qpel_pu, in and out
+//   (fhevc_p_tree_rd_intra_frame)              fhevc_p_tree_rd_frame's buffers and the first-pass records of the current picture in the head of d_first_p
 //   d_first_p                341 (85 + 256)    the first-pass records of the nodes, behind them those of the 4x4 PUs (fhevc_intra_p, fhevc_p_tree_intra_frame)
 //   d_intra_p                85                the intra records made from them
 // fhevc_p_tree_intra_frame keeps its skip records in d_qpel: the re-pricing has read the refined nodes by then, and every later stage reads d_amvp
 //
 // The timing slots (fhevc_kernel_timing) of the launches below: 4 fhevc_motion_search, 5 the P rule, 7 fhevc_motion_refine, 8 / 9 the searches of the PUs / the
 // small PUs, 10 fhevc_motion_refine_pu, 11 / 12 the wide search / refinement, 13 the partition sizes, 15 the centres and everything centred, 17 the tree, 19 the merge stage,
-// 21 the merge stage per PU, 23 the zero-residual test, 25 the re-pricing against neighbour predictors, 27 the intra stage, 29 the RD estimate, 31 the RD estimate under a partition size
+// 21 the merge stage per PU, 23 the zero-residual test, 25 the re-pricing against neighbour predictors, 27 the intra stage, 29 the RD estimate, 31 the RD estimate under a partition size,
+// 33 the RD estimate of the intra candidate
 struct Family { int per_ctu; FhevcMotionNode* fhevc_ctx::*found; FhevcMotionQpelNode* fhevc_ctx::*refined; };
 constexpr Family kNodes = { FHEVC_NODES, &fhevc_ctx::d_motion, &fhevc_ctx::d_qpel }, kPus = { FHEVC_PUS, &fhevc_ctx::d_motion_pu, &fhevc_ctx::d_qpel_pu },
                  kSmall = { FHEVC_PUS_SMALL, &fhevc_ctx::d_motion_pu_small, &fhevc_ctx::d_qpel_pu_small }, kCentres = { 1, &fhevc_ctx::d_centres, nullptr };
@@ -152,11 +160,13 @@ int upload_pair(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, 
 {
   HIP_TRY(c, ensure(c->d_pair, 2 * pair_plane(c) * sizeof(int16_t)));
   HIP_TRY(c, ensure(c->d_motion, (size_t)c->num_ctus * FHEVC_NODES * sizeof(FhevcMotionNode)));
-  const int16_t* src[2] = { ref_luma, cur_luma };
-  for (int i = 0; i < 2; ++i)
+  const int16_t* src[2] = { ref_luma, cur_luma };   // a form of one picture (fhevc_intra_rd) has no reference: its plane stays as it is
+  for (int i = 0; i < 2; ++i) {
+    if (!src[i]) continue;
     HIP_TRY(c, hipMemcpy2DAsync(c->d_pair + i * pair_plane(c), (size_t)c->dev_stride * 2, src[i], (size_t)stride_samples * 2, (size_t)c->cfg.width * 2,
                                 (size_t)c->cfg.height, hipMemcpyHostToDevice, c->stream));
-  c->stats.bytes_h2d += (uint64_t)c->cfg.width * c->cfg.height * 4;
+    c->stats.bytes_h2d += (uint64_t)c->cfg.width * c->cfg.height * 2;
+  }
   return FHEVC_OK;
 }
 
@@ -218,7 +228,7 @@ class HostForm {
 
   fhevc_ctx* c;
   hipError_t e = hipSuccess;
-  Copy ins[10], outs[6];   // at most: the ten arrays of fhevc_motion_rd_pu in; three families of records and of predictor records out (the RD chain: six too)
+  Copy ins[10], outs[7];   // at most: the ten arrays of fhevc_motion_rd_pu in; three families of records and of predictor records out (the RD chain: six too, seven with the intra candidate)
   int n_in = 0, n_out = 0;
 };
 
@@ -628,6 +638,47 @@ int fhevc_motion_rd_pu(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref
   d.fold = h.in(c->d_qpel, bn, in.fold, bn);                       // folded in place on the device: the earlier records go up to where the new ones come from
   fhevc_motion_rd_pu_node* d_out = h.out(c->d_qpel, bn, out, bn);
   return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_rd_pu_device, qp, max_range, part_mode, &d, d_out, c->stream); });
+}
+
+// ---- the RD estimate of the intra candidate per CU node, gated and folded (the intra instances of k_motion_rd.hip) ----
+
+int fhevc_intra_rd_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames,
+                          int ctu_row_begin, int ctu_row_end, int qp, const fhevc_node_cost* d_first, const fhevc_motion_rd_pu_node* d_fold,
+                          const fhevc_motion_rd_node* d_rd_merge, int skip_mask, fhevc_motion_rd_pu_node* d_out, void* stream)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!d_luma || !d_first || !d_out) return fail(c, FHEVC_E_INVALID, "bad intra RD-stage arguments (the planes, the first-pass records, the output)");
+  // pictures, not pairs: the layout is checked as fhevc_intra_first_pass_device checks it
+  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 1, ctu_row_begin, ctu_row_end, qp, false)) return fail(c, FHEVC_E_INVALID, bad);
+  if (skip_mask < 0 || skip_mask > 3) return fail(c, FHEVC_E_INVALID, "bad intra RD-stage arguments (skip_mask 0..3)");
+  if (((uintptr_t)d_first | (uintptr_t)d_fold | (uintptr_t)d_rd_merge | (uintptr_t)d_out) & 3) return fail(c, FHEVC_E_INVALID, "bad intra RD-stage arguments (records are 4-byte aligned)");
+  const long long ctus = (long long)num_frames * (ctu_row_end - ctu_row_begin) * c->ctus_x;
+  if (ctus > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "more than 2^31 - 1 CTUs");
+  // folding in place is one lane reading and writing one record; any other overlap of the two extents is a race between lanes
+  const uintptr_t extent = (uintptr_t)ctus * FHEVC_NODES * sizeof(fhevc_motion_rd_pu_node), f = (uintptr_t)d_fold, o = (uintptr_t)d_out;
+  if (d_fold && f != o && f < o + extent && o < f + extent) return fail(c, FHEVC_E_INVALID, "bad intra RD-stage arguments (fold overlaps the output without being it)");
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;   // an empty band: nothing to launch, nothing written
+  // everything the kernel needs travels with the launch: nothing of the context is read or written by it
+  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
+  return launch_on(c, stream, 33, "fhevc_launch_intra_rd", [&](hipStream_t s) {
+    return fhevc_launch_intra_rd(fr, fhevc_rd_quant(qp, c->cfg.bit_depth), kn(d_first), kn(d_fold), kn(d_rd_merge), skip_mask, kn(d_out), c->num_cus, s);
+  });
+}
+
+int fhevc_intra_rd(fhevc_ctx* c, const int16_t* luma, int stride_samples, int qp, const fhevc_node_cost* first, const fhevc_motion_rd_pu_node* fold,
+                   const fhevc_motion_rd_node* rd_merge, int skip_mask, fhevc_motion_rd_pu_node* out)
+{
+  const int rc = open_host_form(c, luma && first && out && skip_mask >= 0 && skip_mask <= 3, stride_samples, qp, 1, 1, "bad intra RD-stage arguments");
+  if (rc != GO) return rc;
+  HostForm h(c);
+  const size_t bn = h.bytes(kNodes), b4 = (size_t)c->num_ctus * FHEVC_PUS4_PER_CTU * sizeof(fhevc_node_cost);
+  const fhevc_node_cost* d_first = h.in(c->d_first_p, bn + b4, first, bn);
+  const fhevc_motion_rd_node* d_rd_merge = h.in(c->d_qpel, bn, rd_merge, bn);
+  const fhevc_motion_rd_pu_node* d_fold = h.in(c->d_qpel_pu, h.bytes(kPus), fold, bn);   // folded in place on the device, as fhevc_motion_rd_pu does
+  fhevc_motion_rd_pu_node* d_out = h.out(c->d_qpel_pu, h.bytes(kPus), out, bn);
+  return h.run(luma, nullptr, stride_samples, [&] {   // the picture alone: the current plane of the staged pair, as a batch of one frame
+    return fhevc_intra_rd_device(c, c->d_pair + pair_plane(c), 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, d_first, d_fold, d_rd_merge, skip_mask, d_out, c->stream);
+  });
 }
 
 // ---- merge-candidate costs per PU from the refined nodes (k_motion_merge_pu.hip) ----
@@ -1051,7 +1102,9 @@ int fhevc_intra_p(fhevc_ctx* c, int qp, const fhevc_node_cost* first, const fhev
 // with_intra: fhevc_p_tree_intra_frame -- behind the selection the zero-residual stage, the two first passes of the current picture and the intra stage, and the
 // tree that takes all of it; with_rd: fhevc_p_tree_rd_frame -- the re-pricing keeps its predictor records, and behind the selection come the RD estimate of the
 // nodes' merge records, the RD estimates of 2Nx2N and of the selection's best and second size folded into one record per node, and the RD tree
-struct RdFrameOut { fhevc_motion_rd_node* rd_merge; fhevc_motion_rd_pu_node* rd_pu; };
+// (fhevc_p_tree_rd_intra_frame: intra -- behind the folded inter records the first pass of the current picture and the RD estimate of its winners, gated and
+// folded in place)
+struct RdFrameOut { fhevc_motion_rd_node* rd_merge; fhevc_motion_rd_pu_node* rd_pu; bool intra; fhevc_node_cost* first; };
 static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
                            const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes,
                            bool with_merge, fhevc_motion_merge_node* merge, bool with_merge_pu = false, bool with_amvp = false, bool with_intra = false, int skip_mask = 0,
@@ -1097,6 +1150,12 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
     h.out(c->d_qpel, records, with_rd->rd_merge, records);
     h.out(c->d_qpel_pu, h.bytes(kPus), with_rd->rd_pu, records);
   }
+  fhevc_node_cost* d_first_rd = nullptr;
+  if (with_rd && with_rd->intra) {
+    const size_t b4 = (size_t)c->num_ctus * FHEVC_PUS4_PER_CTU * sizeof(fhevc_node_cost);
+    d_first_rd = h.dev<fhevc_node_cost>(c->d_first_p, records + b4);
+    h.out(c->d_first_p, records + b4, with_rd->first, records);
+  }
   fhevc_motion_skip_node* d_skip = nullptr;
   fhevc_node_cost *d_first = nullptr, *d_first4 = nullptr;
   fhevc_intra_p_node* d_intra = nullptr;
@@ -1130,6 +1189,12 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
       in.fold = d_rd_pu;
       if (rc == FHEVC_OK) rc = on_pair(c, fhevc_motion_rd_pu_device, qp, merge_range, 8, &in, d_rd_pu, c->stream);
       if (rc == FHEVC_OK) rc = on_pair(c, fhevc_motion_rd_pu_device, qp, merge_range, 9, &in, d_rd_pu, c->stream);
+      if (rc == FHEVC_OK && with_rd->intra) {
+        const int16_t* d_cur = c->d_pair + pair_plane(c);   // the current picture of the staged pair, as a batch of one frame
+        rc = fhevc_intra_first_pass_device(c, d_cur, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, d_first_rd, c->stream);
+        // intra last, as HM tries it after the inter sizes: the earlier record stays on a tie
+        if (rc == FHEVC_OK) rc = fhevc_intra_rd_device(c, d_cur, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, d_first_rd, d_rd_pu, d_rd_merge, skip_mask, d_rd_pu, c->stream);
+      }
       return rc != FHEVC_OK ? rc : fhevc_p_tree_select_rd_pu_device(c, d_rd_pu, d_rd_merge, skip_mask, 1, 0, c->ctus_y, tree_rule, d_min, d_max, nullptr, c->stream);
     }
     if (rc == FHEVC_OK && with_intra) {
@@ -1183,7 +1248,17 @@ int fhevc_p_tree_rd_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* 
                           const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, int skip_mask, uint8_t* depth_min, uint8_t* depth_max,
                           fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge, fhevc_motion_rd_node* rd_merge, fhevc_motion_rd_pu_node* rd_pu)
 {
-  const RdFrameOut rd = { rd_merge, rd_pu };
+  const RdFrameOut rd = { rd_merge, rd_pu, false, nullptr };
+  return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge, true, true,
+                         false, skip_mask, nullptr, &rd);
+}
+
+int fhevc_p_tree_rd_intra_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                                const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, int skip_mask, uint8_t* depth_min, uint8_t* depth_max,
+                                fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge, fhevc_motion_rd_node* rd_merge, fhevc_motion_rd_pu_node* rd_pu,
+                                fhevc_node_cost* first)
+{
+  const RdFrameOut rd = { rd_merge, rd_pu, true, first };
   return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge, true, true,
                          false, skip_mask, nullptr, &rd);
 }

@@ -29,9 +29,13 @@
 // registers are taken per quadrant: D[4 y + k] holds columns 2 k, 2 k + 1 of row y, so a quadrant is whole registers.  Everything behind the residual is
 // the code above, untouched; the writer lane folds its record into an earlier launch's where one is given.  The PU = false instances keep their argument
 // list (the PU arguments are a pack that is empty there) and their code.
+//
+// The intra instances (fhevc_intra_rd_device; fhevc_intra_rd_kernel further below): the same passes behind another prediction -- the first pass's ONE mode per
+// node, predicted per TU from the first pass's own reference lines, separately for the two TU depths.  No window: the lines and the staged CTU take its place.
 #include "fhevc_internal.h"
 #include "k_had8x8.h"
 #include "k_refine_tile.h"
+#include "k_firstpass_common.h"
 
 namespace {
 
@@ -487,6 +491,294 @@ __global__ __launch_bounds__(256) void fhevc_motion_rd_kernel(FhevcFrames F, int
   }
 }
 
+// ---- the intra candidate on RD costs (fhevc_intra_rd_device): the first pass's lines, ONE mode per node, the transform passes above ----
+//
+// Per CTU: the CTU with its row above and column left staged over the (still dead) transform buffers, the 85 reference lines and their smoothed twins
+// built exactly as k_firstpass.hip builds them (units, HM's substitution walk, smoothing, DC values; the lines keep their own LDS, the staged CTU is dead
+// once the units are copied).  Then per TU depth: every lane predicts its tile at ITS node's mode from the line of the TU of that depth that holds the tile
+// (the mode differs per lane, so nothing is wave-uniform but the TU size: negative angles project per sample, no extended reference is built), the residual
+// against the original goes through rd_depth<DEPTH> unchanged.  The level-3 wave has no depth 1 (4x4 TUs are left out): it runs its depth-0 residual
+// through the depth-1 passes and the writer drops the sums.  The writer lane makes HM's intra choice (dSplitCost < dSingleCost alone), applies the calm
+// gate and the fold.  The matrices lie behind the transform buffers for the whole launch: nothing ever lies over them here.
+namespace ird {
+constexpr int kLineTotal = 257 + 4 * 129 + 16 * 65 + 64 * 33;  // 3 925 samples: all 85 lines of 4 n + 1
+constexpr int kLinePad = 8;                                    // the unconditional second tap may touch one sample past a line
+constexpr int kUnits = 65 + 4 * 33 + 16 * 17 + 64 * 9;         // 1 045 four-sample units (n + 1 per node: the corner is a unit)
+__device__ __forceinline__ int line_off(int level) { return level == 0 ? 0 : (level == 1 ? 257 : (level == 2 ? 773 : 1813)); }
+__device__ __forceinline__ int node_off(int level) { return level == 0 ? 0 : (level == 1 ? 1 : (level == 2 ? 5 : 21)); }
+__device__ __forceinline__ int unit_off(int level) { return level == 0 ? 0 : (level == 1 ? 65 : (level == 2 ? 197 : 469)); }
+__device__ __forceinline__ int level_of_node(int k) { return k < 1 ? 0 : (k < 5 ? 1 : (k < 21 ? 2 : 3)); }
+// unit u of a node at (x0, y0) of size n in HM's walk order: bottom-left first, up the left column, the corner, the row above left to right
+__device__ __forceinline__ void unit_pos(int u, int n, int x0, int y0, int& ux, int& uy)
+{
+  const int L = n >> 1;
+  if (u < L) { ux = x0 - 4; uy = y0 + 4 * (L - 1 - u); }
+  else if (u == L) { ux = x0 - 4; uy = y0 - 4; }
+  else { ux = x0 + 4 * (u - L - 1); uy = y0 - 4; }
+}
+// sample i of HM's refMain (TComPrediction.cpp:278-300) without the copy: i >= 0 lies on the main side, i < 0 is the side reference at the inverse angle
+__device__ __forceinline__ int main_ref(const short* ref, int sgn, int inv_angle, int i)
+{
+  return ref[i >= 0 ? sgn * i : -sgn * ((128 - i * inv_angle) >> 8)];
+}
+// the tile at (bx, by) of the n x n TU (n = 1 << lg <= 32) whose line has its corner at ref[0] (above at +i, left at -i), predicted at mode 0..34 with the
+// edge filters of n <= 16; tab: the angle and inverse-angle tables.  One sample at a time: the mode is this lane's own
+__device__ __forceinline__ void predict_tile(const short* ref, const short* tab, int n, int lg, int bx, int by, int mode, int dc, int maxval, unsigned (&P)[32])
+{
+  if (mode == 0) {
+    const int topRight = ref[n + 1], bottomLeft = ref[-(n + 1)];
+#pragma unroll
+    for (int y = 0; y < 8; ++y) {
+      const int left = ref[-(by + y + 1)];
+#pragma unroll
+      for (int x = 0; x < 8; ++x) {
+        const int top = ref[bx + x + 1];
+        const int hor = (left << lg) + n + (bx + x + 1) * (topRight - left);
+        const int ver = (top << lg) + (by + y + 1) * (bottomLeft - top);
+        const unsigned v = (unsigned)((hor + ver) >> (lg + 1)) & 0xFFFFu;
+        if (x & 1) P[4 * y + (x >> 1)] |= v << 16; else P[4 * y + (x >> 1)] = v;
+      }
+    }
+  } else if (mode == 1) {
+    const bool edge = n <= 16;
+#pragma unroll
+    for (int y = 0; y < 8; ++y)
+#pragma unroll
+      for (int x = 0; x < 8; ++x) {
+        const int X = bx + x, Y = by + y;
+        int v = dc;
+        if (edge && Y == 0) v = (ref[X + 1] + 3 * dc + 2) >> 2;
+        if (edge && X == 0) v = (ref[-(Y + 1)] + 3 * dc + 2) >> 2;
+        if (edge && X == 0 && Y == 0) v = (ref[1] + ref[-1] + 2 * dc + 2) >> 2;
+        const unsigned w = (unsigned)v & 0xFFFFu;
+        if (x & 1) P[4 * y + (x >> 1)] |= w << 16; else P[4 * y + (x >> 1)] = w;
+      }
+  } else {
+    const bool is_ver = mode >= 18;
+    const int ang_mode = is_ver ? mode - 26 : 10 - mode;
+    const int abs_mode = abs(ang_mode);                      // 0..8: mode is 2..34
+    const int angle = ang_mode < 0 ? -(int)tab[abs_mode] : (int)tab[abs_mode];
+    const int inv_angle = tab[9 + abs_mode];
+    const int sgn = is_ver ? 1 : -1;                         // main(i) = ref[sgn i], side(i) = ref[-sgn i]
+    const bool edge = angle == 0 && n <= 16;                 // the pure vertical / horizontal modes: the first column (row) leans on the side reference
+    const int tl = ref[0];
+#pragma unroll
+    for (int y = 0; y < 8; ++y)
+#pragma unroll
+      for (int x = 0; x < 8; ++x) {
+        const int X = bx + x, Y = by + y;
+        const int xx = is_ver ? X : Y, yy = is_ver ? Y : X;   // horizontal modes are the vertical ones of the transposed block
+        const int delta = (yy + 1) * angle, di = delta >> 5, df = delta & 31;
+        const int i = xx + di + 1;
+        int v = ((32 - df) * main_ref(ref, sgn, inv_angle, i) + df * main_ref(ref, sgn, inv_angle, i + 1) + 16) >> 5;
+        if (edge && xx == 0) v = min(maxval, max(0, v + ((ref[-sgn * (yy + 1)] - tl) >> 1)));
+        const unsigned w = (unsigned)v & 0xFFFFu;
+        if (x & 1) P[4 * y + (x >> 1)] |= w << 16; else P[4 * y + (x >> 1)] = w;
+      }
+  }
+}
+}  // namespace ird
+
+// T = int16_t or uint8_t planes.  first: the first pass's records as dwords (satd, mode, the cost's two); fold / rd_merge: RD records as dwords, or null;
+// fold may be out (the writer lane reads its record, then writes it)
+template <typename T>
+__global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, FhevcRdQuant Q, const unsigned* __restrict__ first, const unsigned* fold,
+                                                             const unsigned* __restrict__ rd_merge, int skip_mask, FhevcMotionRdPuNode* out)
+{
+  using namespace ird;
+  __shared__ __attribute__((aligned(16))) short s_t[kTransformShorts + kFwdShorts + kInvShorts];   // the transform buffers (under them, first, the staged CTU) and the matrices
+  __shared__ short s_refbuf[kLinePad + kLineTotal + kLinePad + 1];   // unfiltered lines: line[2 n] the corner, + i above, - j left
+  __shared__ short s_fltbuf[kLinePad + kLineTotal + kLinePad + 1];   // smoothed lines
+  __shared__ short s_above[132], s_left[64], s_tab[18];
+  __shared__ int s_dc[FHEVC_NODES];
+  __shared__ unsigned char s_av[kUnits + 3], s_valid[FHEVC_NODES];
+  __shared__ unsigned s_acc[kAccWords * kTus];
+  static_assert(kTransformShorts >= 64 * 64, "the staged CTU lies under the transform buffers");
+  short* const s_org = s_t;
+  short* const s_ref = s_refbuf + kLinePad;
+  short* const s_flt = s_fltbuf + kLinePad;
+  const int tid = threadIdx.x, lane = tid & 63, lvl = tid >> 6;
+  const int wave = __builtin_amdgcn_readfirstlane(lvl);
+  const int tx = lane & 7, ty = lane >> 3;
+  const int bd = F.bit_depth, maxval = (1 << bd) - 1;
+  const int band_rows = F.row_end - F.row_begin, per_frame = band_rows * F.ctus_x, total = per_frame * F.num_frames;
+  const T* plane = reinterpret_cast<const T*>(F.luma);
+  const RefineNode N(lvl, tx, ty);
+  const int nidx = N.nidx;
+  const int gw = F.width >> (6 - lvl), gh = F.height >> (6 - lvl);   // the level's nodes that lie wholly inside the picture
+  {
+    unsigned* mdst = reinterpret_cast<unsigned*>(s_t + kTransformShorts);
+    const unsigned* msrc = reinterpret_cast<const unsigned*>(&kRdTables);
+    for (int i = tid; i < (kFwdShorts + kInvShorts) / 2; i += 256) mdst[i] = msrc[i];
+    if (tid < 9) {
+      const int ang[9] = { 0, 2, 5, 9, 13, 17, 21, 26, 32 }, inv[9] = { 0, 4096, 1638, 910, 630, 482, 390, 315, 256 };
+      int a = 0, b = 0;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) { a = tid == k ? ang[k] : a; b = tid == k ? inv[k] : b; }
+      s_tab[tid] = (short)a; s_tab[9 + tid] = (short)b;
+    }
+  }
+
+  for (int work = blockIdx.x; work < total; work += gridDim.x) {
+    const int f = work / per_frame, rem = work - f * per_frame;
+    const int cy = F.row_begin + rem / F.ctus_x, cx = rem % F.ctus_x;
+    const long long base = (long long)f * F.frame_stride;
+    const T* frame = plane + base;
+    const int ox = cx * 64, oy = cy * 64;
+    const long long rec = ((long long)(f * band_rows + (cy - F.row_begin)) * F.ctus_x + cx) * FHEVC_NODES + nidx;
+    // ---- the node's input record: satd and the low byte of mode; nothing of it reaches an address ----
+    const bool node_in = cx * N.ncnt + N.nbx < gw && cy * N.ncnt + N.nby < gh;
+    const unsigned rsatd = first[rec * 4], rmode = first[rec * 4 + 1] & 0xFFu;
+    const bool valid = node_in && rsatd != kRdMark && rmode <= 34u;
+    const int mode = valid ? (int)rmode : 0;   // an invalid node predicts with mode 0 and drops the result
+    __syncthreads();   // the previous CTU's readers of the buffers and of the sums are done
+    // ---- the CTU, the row above it and the column left of it; which of the 85 nodes lie inside ----
+    fhevc_fp::stage_ctu<T>(frame, F, ox, oy, tid, s_org, s_above, s_left);
+    if (tid < FHEVC_NODES) {
+      const int level = level_of_node(tid), n = 64 >> level, cnt = 1 << level, ni = tid - node_off(level);
+      s_valid[tid] = ((ox + (ni % cnt) * n + n <= F.width) && (oy + (ni / cnt) * n + n <= F.height)) ? 1 : 0;
+    }
+    for (int i = tid; i < kAccWords * kTus; i += 256) s_acc[i] = 0;
+    __syncthreads();
+    // ---- one thread per 4-sample unit: availability in coding order and, where available, its samples ----
+    for (int ug = 65 + tid; ug < kUnits; ug += 256) {   // from the first unit of level 1 on: a 64x64 block is no TU
+      const int level = ug < 197 ? 1 : (ug < 469 ? 2 : 3);
+      const int n = 64 >> level, cnt = 1 << level, upn = n + 1;
+      const int ni = (ug - unit_off(level)) / upn, u = (ug - unit_off(level)) - ni * upn;
+      const int x0 = ox + (ni % cnt) * n, y0 = oy + (ni / cnt) * n;
+      int ux, uy;
+      unit_pos(u, n, x0, y0, ux, uy);
+      const bool av = s_valid[node_off(level) + ni] && fhevc_fp::unit_available(ux, uy, x0, y0, F.width, F.height, F.ctus_x);
+      s_av[ug] = av ? 1 : 0;
+      if (av) {
+        short* line = s_ref + line_off(level) + ni * (4 * n + 1);
+        const int L = n >> 1;
+        if (u < L) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) line[4 * u + i] = fhevc_fp::staged(s_org, s_above, s_left, x0 - 1, y0 + 2 * n - 1 - (4 * u + i), ox, oy);
+        } else if (u == L) {
+          line[2 * n] = fhevc_fp::staged(s_org, s_above, s_left, x0 - 1, y0 - 1, ox, oy);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) line[4 * u - 3 + i] = fhevc_fp::staged(s_org, s_above, s_left, x0 + 4 * (u - L - 1) + i, y0 - 1, ox, oy);
+        }
+      }
+    }
+    __syncthreads();
+    // ---- HM's substitution walk (TComPattern.cpp:461-524), one thread per node ----
+    if (tid >= 1 && tid < FHEVC_NODES && s_valid[tid]) {
+      const int level = level_of_node(tid), n = 64 >> level, ni = tid - node_off(level), upn = n + 1, L = n >> 1;
+      short* line = s_ref + line_off(level) + ni * (4 * n + 1);
+      const unsigned char* av = s_av + unit_off(level) + ni * upn;
+      int first_av = -1;
+      for (int u = 0; u < upn && first_av < 0; ++u) if (av[u]) first_av = u;
+      if (first_av < 0) {
+        for (int i = 0; i < 4 * n + 1; ++i) line[i] = (short)(1 << (bd - 1));
+      } else {
+        short prev = line[first_av <= L ? 4 * first_av : 4 * first_av - 3];
+        for (int u = 0; u < upn; ++u) {
+          const int s = u <= L ? 4 * u : 4 * u - 3, c = (u == L) ? 1 : 4;
+          if (av[u]) prev = line[s + c - 1];
+          else for (int i = 0; i < c; ++i) line[s + i] = prev;
+        }
+      }
+    }
+    __syncthreads();
+    // ---- the smoothed lines (one thread per sample; level 0 is no TU size and is left out) and the DC values ----
+#pragma unroll
+    for (int level = 1; level < 4; ++level) {
+      const int n = 64 >> level, len = 4 * n + 1, cnt = (1 << (2 * level)) * len;
+      for (int i = tid; i < cnt; i += 256) {
+        const int ni = i / len, k = i - ni * len;
+        if (!s_valid[node_off(level) + ni]) continue;
+        const short* ref = s_ref + line_off(level) + ni * len;
+        int v;
+        if (k == 0 || k == 4 * n) v = ref[k];
+        else {
+          bool strong = false;
+          if (n >= 32) {
+            const int thr = 1 << (bd - 5);
+            const int bl = ref[0], tl = ref[2 * n], tr = ref[4 * n];
+            strong = (abs(bl + tl - 2 * ref[n]) < thr) && (abs(tl + tr - 2 * ref[3 * n]) < thr);
+            if (strong) {
+              if (k < 2 * n) v = ((2 * n - k) * bl + k * tl + n) >> 6;
+              else if (k == 2 * n) v = tl;
+              else v = ((2 * n - (k - 2 * n)) * tl + (k - 2 * n) * tr + n) >> 6;
+            }
+          }
+          if (!strong) v = (ref[k - 1] + 2 * ref[k] + ref[k + 1] + 2) >> 2;
+        }
+        s_flt[line_off(level) + i] = (short)v;
+      }
+    }
+    if (tid >= 1 && tid < FHEVC_NODES && s_valid[tid]) {
+      const int level = level_of_node(tid), n = 64 >> level, ni = tid - node_off(level);
+      const short* ref = s_ref + line_off(level) + ni * (4 * n + 1);   // DC never uses the smoothed line
+      int sum = 0;
+      for (int i = 0; i < n; ++i) sum += ref[2 * n + 1 + i] + ref[2 * n - 1 - i];
+      s_dc[tid] = (sum + n) >> (7 - level);                            // / (2 n)
+    }
+    const int px = ox + tx * 8, py = oy + ty * 8;
+    const bool inside = (px + 8 <= F.width) && (py + 8 <= F.height);
+    __syncthreads();   // the lines stand; the staged CTU is dead: the transform buffers lie over it
+    // ---- per TU depth: this lane's tile predicted at its node's mode from the line of the TU that holds it, the residual through the passes ----
+#pragma unroll 1
+    for (int depth = 0; depth < 2; ++depth) {
+      const int L = min(max(wave, 1) + depth, 3);        // the TU's level (wave 3 has no depth 1: its depth-0 TU again, dropped by the writer)
+      const int n = 64 >> L, lg = 6 - L;
+      const int ni = ((ty >> (3 - L)) << L) + (tx >> (3 - L));
+      const int bx = (tx * 8) & (n - 1), by = (ty * 8) & (n - 1);
+      const int thr = L == 1 ? 0 : (L == 2 ? 1 : 7);     // m_aucIntraFilter of 32, 16, 8
+      const bool use_flt = mode != 1 && min(abs(mode - 10), abs(mode - 26)) > thr;
+      const short* ref = (use_flt ? s_flt : s_ref) + line_off(L) + ni * (4 * n + 1) + 2 * n;
+      unsigned D[32];
+      predict_tile(ref, s_tab, n, lg, bx, by, mode, s_dc[node_off(L) + ni], maxval, D);
+      {
+        unsigned O[32];
+        load_tile8x8(plane, base, F, px, py, inside, O);
+#pragma unroll
+        for (int i = 0; i < 32; ++i) D[i] = pk_sub(O[i], D[i]);
+      }
+      if (depth == 0) rd_depth<0>(s_t, lane, lvl, wave, tx, ty, Q, s_acc, plane, base, F, px, py, inside, D);
+      else rd_depth<1>(s_t, lane, lvl, wave, tx, ty, Q, s_acc, plane, base, F, px, py, inside, D);
+    }
+    if (N.writer) {
+      FhevcMotionRdPuNode u;
+      u.dist = u.cost_rd = kRdMark; u.bits = 0xFFFFu; u.flags = 0; u.tu_split = 0; u.part = 255; u.merged = 0; u.pad[0] = u.pad[1] = 0;
+      const FhevcMotionRdPuNode none = u;
+      if (valid) {
+        const int qi = lvl == 3 ? 1 : (lvl == 2 ? 2 : 3);                // the depth-0 TU size's numbers
+        const int tu0 = lvl == 0 ? 0 : (lvl == 1 ? 4 : lvl == 2 ? 8 : 24) + (nidx - N.first), ntu = lvl == 0 ? 4 : 1;   // a 64x64 node: four TUs
+        const unsigned side = mode == 0 ? 2u : (mode == 1 || mode == 26) ? 3u : 6u;   // bits(m) of fhevc_intra_p
+        unsigned long long j = (unsigned long long)Q.lam_q8 * side, bits = side;
+        unsigned dist = 0, top = 0, any0 = 0, split = 0;
+        for (int i = 0; i < ntu; ++i) {
+          const unsigned* a = &s_acc[kAccWords * (tu0 + i)];
+          const unsigned d0 = a[0], r0 = 1u + a[1], d1 = a[2], r1 = 4u + a[3];
+          const unsigned long long j0 = 256ull * d0 + (unsigned long long)Q.lam_q8 * (1u + r0), j1 = 256ull * d1 + (unsigned long long)Q.lam_q8 * (1u + r1);
+          const bool take = lvl != 3 && j1 < j0;                          // dSplitCost < dSingleCost alone (TEncSearch.cpp:1661); an 8x8 node has one depth
+          j += take ? j1 : j0; dist += take ? d1 : d0; bits += 1u + (take ? r1 : r0);
+          split |= take ? 1u << i : 0u; any0 |= a[1]; top = max(top, a[4]);
+        }
+        const bool zero_half = ((top * Q.scale + Q.add_half[qi]) >> Q.qbits[qi]) == 0u;
+        j >>= 8;
+        u.dist = dist; u.cost_rd = j < 0xFFFFFFFEull ? (unsigned)j : 0xFFFFFFFEu;
+        u.bits = (uint16_t)(bits < 65535ull ? bits : 65535ull);
+        u.flags = (uint8_t)((any0 == 0u ? 1 : 0) | (zero_half ? 2 : 0) | (split ? 4 : 0)); u.tu_split = (uint8_t)split;
+        u.part = kRdPartIntra; u.pad[0] = (uint8_t)mode;
+      }
+      // the earlier record (a marker where there is none), read through the output pointer where the fold is in place
+      const FhevcMotionRdPuNode* const src = reinterpret_cast<const void*>(fold) == reinterpret_cast<const void*>(out) ? out : reinterpret_cast<const FhevcMotionRdPuNode*>(fold);
+      const FhevcMotionRdPuNode fr = fold ? src[rec] : none;
+      // calm: the merge candidate is strictly the cheapest so far and has a masked zero bit -- HM does not try intra there (TEncCu.cpp:799-804)
+      bool calm = false;
+      if (rd_merge) calm = rd_merge[rec * 4 + 1] < fr.cost_rd && (((rd_merge[rec * 4 + 2] >> 16) & 0xFFu) & (unsigned)skip_mask) != 0u;
+      if (calm || (fold && !(valid && u.cost_rd < fr.cost_rd))) u = fr;
+      out[rec] = u;
+    }
+  }
+}
+
 }  // namespace
 
 // what the device keeps resident is the occupancy query's answer in both layouts: two workgroups per CU by the registers (256 VGPRs), which is also what the
@@ -515,4 +807,18 @@ hipError_t fhevc_launch_motion_rd_pu(const FhevcFrames& fr, int max_range, const
     return refine_launch_kernel<&fhevc_motion_rd_kernel<decltype(t), decltype(mr)::value, true, RdPuArgs>>(L, fr, max_range, q, 1, dw(I.nodes), dw(I.mvp_nodes),
                                                                                                          reinterpret_cast<FhevcMotionRdNode*>(d_out), pa);
   });
+}
+
+// the intra instances: no window, so the LDS (61 KB static) leaves room for two workgroups per CU; what is resident is the occupancy query's answer
+hipError_t fhevc_launch_intra_rd(const FhevcFrames& fr, const FhevcRdQuant& q, const FhevcNodeCost* d_first, const FhevcMotionRdPuNode* d_fold,
+                                 const FhevcMotionRdNode* d_rd_merge, int skip_mask, FhevcMotionRdPuNode* d_out, int num_cus, hipStream_t stream)
+{
+  static_assert(sizeof(FhevcNodeCost) == 16 && offsetof(FhevcNodeCost, satd) == 0 && offsetof(FhevcNodeCost, mode) == 4, "first-pass record layout");
+  const long long total = (long long)(fr.row_end - fr.row_begin) * fr.ctus_x * fr.num_frames;
+  if (total <= 0) return hipSuccess;
+  if (!d_first || !d_out || skip_mask < 0 || skip_mask > 3 || total > 0x7FFFFFFF) return hipErrorInvalidValue;
+  const auto dw = [](const void* p) { return reinterpret_cast<const unsigned*>(p); };
+  const RefineLaunch L = { 0, { 4, true }, num_cus, total, stream };
+  if (fr.sample_bytes == 2) return refine_launch_kernel<&fhevc_intra_rd_kernel<int16_t>>(L, fr, q, dw(d_first), dw(d_fold), dw(d_rd_merge), skip_mask, d_out);
+  return refine_launch_kernel<&fhevc_intra_rd_kernel<uint8_t>>(L, fr, q, dw(d_first), dw(d_fold), dw(d_rd_merge), skip_mask, d_out);
 }

@@ -1252,6 +1252,63 @@ int  fhevc_p_tree_rd_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_
                            const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, int skip_mask, uint8_t* depth_min, uint8_t* depth_max,
                            fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge, fhevc_motion_rd_node* rd_merge, fhevc_motion_rd_pu_node* rd_pu);
 
+/* ---- config 4 (P slices): the RD estimate of the intra candidate per CU node, folded per CU (the intra instances of k_motion_rd.hip) --------------
+ * The tree that takes the intra candidate (fhevc_p_tree_select_intra*, further below) compares Hadamard costs; the RD tree above compares SSE + lambda
+ * bits and has no intra candidate, so a node whose content is not in the reference picture can only split there.  This stage prices ONE intra mode per
+ * node -- the first pass's winner -- in the RD stage's unit and folds it into the records the RD tree already reads.
+ *   Input per CTU: the 85 fhevc_node_cost records of fhevc_intra_first_pass_device for the same picture, compact over the band, and the luma planes in the
+ * layout, band and stream arguments of fhevc_intra_first_pass_device.  There is no frame pairing: num_frames pictures give num_frames * band CTUs * 85
+ * records; a caller that folds into the records of picture pairs passes plane and record pointers offset by one picture.
+ *   Of a first-pass record only satd (dword 0) and the low byte of mode (dword 1) are read; any byte content is legal.  A node is valid iff it is INSIDE,
+ * satd != 0xFFFFFFFF and that byte is <= 34.  No input byte reaches an address or a loop bound: an invalid node predicts with mode 0 and its result is
+ * dropped.
+ *   Prediction: for a TU that is node t of size n in {32, 16, 8} and mode m, exactly what the first pass evaluates for (t, m): the reference line from the
+ * ORIGINAL plane with coding-order availability and HM's substitution walk, the smoothing as the first pass applies it, the filter decision by (m, n), the
+ * predictor with its edge filters (the oracle's fho_fill_ref, fho_filter_ref, fho_use_filtered_ref, fho_pred_intra).  The z-order availability of a TU
+ * inside a CU is that of the node of that size at that place, so every line is one of the 85 the first pass builds.
+ *   TUs of a node of level l (s = 64 >> l): the depth-0 TUs are the nodes of level max(l, 1) inside it (N0 = min(s, 32); a 64x64 node has four), the
+ * depth-1 TUs the nodes one level further down (N1 = N0 / 2).  Both depths use the node's one mode; an intra TU is predicted from its own neighbours, so
+ * the two depths have different residuals.  An 8x8 node has depth 0 only (tu_split 0).
+ *   Per TU everything is word for word step 3 of fhevc_motion_rd on r = original - prediction: xTrMxN, the plain quantiser, xDeQuant, xITrMxN, xGetSSE
+ * with its per-sample shift, r(TU) = 1 + sum (3 + 2 floor(log2 |level|)), lam_q8 = fhevc_motion_rd_lambda_q8(qp).
+ *   Per depth-0 TU, in 64 bits: J0 = 256 D0 + lam_q8 (1 + r0), J1 = 256 sum D1 + lam_q8 (1 + sum r1); the split is taken iff J1 < J0, strictly.  This
+ * differs from the inter rule of fhevc_motion_rd, which also asks that some child is coded: HM's intra recursion compares dSplitCost < dSingleCost alone
+ * (TEncSearch.cpp:1661 against :5117).
+ *   Node result: side_bits = bits(m) of fhevc_intra_p (2 / 3 / 6); cost_rd = min((sum J + lam_q8 side_bits) >> 8, 0xFFFFFFFE); bits and dist as in the RD
+ * record; flags bit 0: every depth-0 level is zero under add_plain, bit 1: under add_half, bit 2: some TU split.  The record is a
+ * fhevc_motion_rd_pu_node with part = FHEVC_RD_PART_INTRA, merged = 0, pad[0] = the mode, pad[1] = 0; the marker is that record's marker (part 255).
+ *   Calm gate (fhevc_p_tree_select_intra's rule 1 on RD records): with d_rd_merge given, a node is CALM iff its merge RD record's cost_rd is strictly
+ * smaller than the fold record's (an absent fold or a marker counts as the largest number; a marker merge record is never smaller) and
+ * rd_merge.flags & skip_mask != 0.  HM does not try intra where the best mode so far has no coded residual (TEncCu.cpp:799-804).  A calm node keeps the
+ * fold record's 16 bytes, the marker where there is no fold.
+ *   Fold (fhevc_motion_rd_pu's rule): with d_fold given, the intra record is written iff it is valid and strictly cheaper than the fold record, else the
+ * fold record unchanged: HM tries intra after the inter sizes and keeps the earlier mode on a tie.  d_fold == d_out is allowed: each record is read and
+ * written by the same lane.  Any other overlap of the two extents is rejected.  With d_fold and d_rd_merge NULL and skip_mask 0 the output is the plain
+ * intra RD record of every valid node.
+ *   Asynchronous on `stream` (NULL: the context's), allocates nothing, keeps no HBM state between calls: calls with different QPs may be in flight on two
+ * streams.  The output is written over exactly its extent; an empty band writes nothing.  FHEVC_E_INVALID with a fhevc_last_error text (nothing is launched
+ * or written): what fhevc_intra_first_pass_device rejects; a null d_first or d_out; skip_mask outside 0..3; a pointer that is not 4-byte aligned; the
+ * partial overlap above.  Timed under slot 33 of fhevc_kernel_timing (32 stays rejected).
+ * NOT covered: 4x4 TUs, and with them the DST, NxN and the depth-1 split of 8x8 CUs; the third TU depth, RDOQ, transform skip, chroma and reconstructed
+ * neighbours; HM's RD search over the candidate list and MPMs (the stage takes one mode per node); the mode-flag bits; the margin fit and any hook
+ * consumer.  Nothing here can be pinned to HM's own intra coding, which predicts from reconstructed neighbours. */
+#define FHEVC_RD_PART_INTRA 16
+int  fhevc_intra_rd_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames,
+                           int ctu_row_begin, int ctu_row_end, int qp, const fhevc_node_cost* d_first, const fhevc_motion_rd_pu_node* d_fold,
+                           const fhevc_motion_rd_node* d_rd_merge, int skip_mask, fhevc_motion_rd_pu_node* d_out, void* stream);
+/* one picture, host buffers, synchronous: first, fold (or NULL), rd_merge (or NULL) and out are host arrays of numCtus * 85 records (out == fold is allowed) */
+int  fhevc_intra_rd(fhevc_ctx* ctx, const int16_t* luma, int stride_samples, int qp, const fhevc_node_cost* first, const fhevc_motion_rd_pu_node* fold,
+                    const fhevc_motion_rd_node* rd_merge, int skip_mask, fhevc_motion_rd_pu_node* out);
+/* fhevc_p_tree_rd_frame with the intra candidate.  On the context's stream, in order: the whole chain of fhevc_p_tree_rd_frame up to the folded inter
+ * records; fhevc_intra_first_pass_device on the CURRENT picture; fhevc_intra_rd_device with the folded records as d_fold (in place), the merge RD records
+ * as d_rd_merge, and skip_mask; fhevc_p_tree_select_rd_pu_device.  There is no new tree kernel: the tree reads dword 1 and byte 10 as before.  Downloads
+ * what fhevc_p_tree_rd_frame downloads (rd_pu: the records folded with the intra candidate) and, where asked, the first-pass records, numCtus * 85.  A
+ * rejected call moves nothing. */
+int  fhevc_p_tree_rd_intra_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                                 int coarse_range, const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, int skip_mask, uint8_t* depth_min,
+                                 uint8_t* depth_max, fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge, fhevc_motion_rd_node* rd_merge,
+                                 fhevc_motion_rd_pu_node* rd_pu, fhevc_node_cost* first);
+
 /* ---- config 4 (P slices): intra candidate costs per CU node (k_intra_p.hip) -----------------------------------------------------------------------
  * HM checks intra at every CU of a P slice (TEncCu.cpp:797-816): xCheckRDCostIntra(SIZE_2Nx2N) at every depth, SIZE_NxN at the 8x8 level, both only while
  * the best mode so far has a non-zero CBF.  Without that candidate a node whose content is not in the reference picture -- uncovered background, the second
@@ -1351,6 +1408,7 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
  * -- except 27 = the intra candidate costs of P pictures (fhevc_intra_p*).  26 is not a slot: it stays rejected, as does any number above 27
  * -- except 29 = the RD estimate (fhevc_motion_rd*).  28 is not a slot: it stays rejected, as does any number above 29.
  * -- except 31 = the RD estimate under a partition size (fhevc_motion_rd_pu*).  30 is not a slot: it stays rejected, as does any number above 31.
+ * -- except 33 = the RD estimate of the intra candidate (fhevc_intra_rd*).  32 is not a slot: it stays rejected, as does any number above 33.
  * The tree that stops at a skip (fhevc_p_tree_select_skip_device), the tree that takes the intra candidate (fhevc_p_tree_select_intra_device) and the tree
  * on RD costs (fhevc_p_tree_select_rd_device) are timed under 17 */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
