@@ -49,6 +49,7 @@ SYMBOLS = [
     "fhevc_motion_rd", "fhevc_motion_rd_device", "fhevc_motion_rd_lambda_q8", "fhevc_p_tree_select_rd", "fhevc_p_tree_select_rd_device",
     "fhevc_motion_rd_pu", "fhevc_motion_rd_pu_device", "fhevc_p_tree_select_rd_pu", "fhevc_p_tree_select_rd_pu_device", "fhevc_p_tree_rd_frame",
     "fhevc_intra_rd", "fhevc_intra_rd_device", "fhevc_p_tree_rd_intra_frame",
+    "fhevc_motion_rd_qt", "fhevc_motion_rd_qt_device", "fhevc_motion_rd_pu_qt", "fhevc_motion_rd_pu_qt_device", "fhevc_p_tree_rd_qt_frame",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -282,6 +283,14 @@ def load_library(path=None):
     lib.fhevc_p_tree_select_skip_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp, vp]
     lib.fhevc_motion_rd.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     lib.fhevc_motion_rd_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    if path is None or hasattr(lib, "fhevc_motion_rd_qt"):   # another build (A/B against the parent commit) may predate the entry points with tu_depths
+        lib.fhevc_motion_rd_qt.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]
+        lib.fhevc_motion_rd_qt_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]
+        lib.fhevc_motion_rd_pu_qt.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MotionRdPuInputs), C.c_int, vp]
+        lib.fhevc_motion_rd_pu_qt_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MotionRdPuInputs),
+                                                     C.c_int, vp, vp]
+        lib.fhevc_p_tree_rd_qt_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), C.c_int, C.c_int, vp, vp, vp, vp,
+                                                 vp, vp]
     lib.fhevc_motion_rd_lambda_q8.argtypes = [C.c_int]
     lib.fhevc_motion_rd_lambda_q8.restype = C.c_uint32
     lib.fhevc_p_tree_select_rd.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PTreeRule), vp, vp, vp]
@@ -855,6 +864,11 @@ class Context:
     def motion_rd(self, cur_plane, ref_plane, records, source, mvp=None, origin=0, stride=None, qp=32, max_range=4):
         """config 4: the RD estimate of every CU node at the vector of its record [numCtus, 85] -- source RD_SOURCE_MERGE: MOTION_MERGE_DTYPE, RD_SOURCE_EXPLICIT:
         MOTION_QPEL_DTYPE, with the re-pricing's predictor records mvp [numCtus, 85] MOTION_MVP_DTYPE or None -> [numCtus, 85] MOTION_RD_DTYPE"""
+        return self.motion_rd_qt(cur_plane, ref_plane, records, source, None, mvp, origin, stride, qp, max_range)
+
+    def motion_rd_qt(self, cur_plane, ref_plane, records, source, tu_depths=3, mvp=None, origin=0, stride=None, qp=32, max_range=4):
+        """motion_rd at tu_depths TU depths: 2 -- motion_rd's bytes, 3 -- HM's full residual quad-tree (the 32x32 and 16x16 nodes get their third TU size;
+        tu_split bits 4..7).  None: the entry point without the argument"""
         cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
         records = np.ascontiguousarray(records).reshape(-1)
         assert records.dtype.itemsize == 16 and records.size == self.num_ctus * NODES_PER_CTU
@@ -862,8 +876,8 @@ class Context:
             mvp = np.ascontiguousarray(mvp).reshape(-1)
             assert mvp.dtype.itemsize == 8 and mvp.size == records.size
         out = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_RD_DTYPE)
-        self._check(self.lib.fhevc_motion_rd(self.h, cur, ref, stride, qp, max_range, source, records.ctypes.data, mvp.ctypes.data if mvp is not None else None,
-                                             out.ctypes.data))
+        head = (self.h, cur, ref, stride, qp, max_range, source, records.ctypes.data, mvp.ctypes.data if mvp is not None else None)
+        self._check(self.lib.fhevc_motion_rd(*head, out.ctypes.data) if tu_depths is None else self.lib.fhevc_motion_rd_qt(*head, tu_depths, out.ctypes.data))
         return out.reshape(self.num_ctus, NODES_PER_CTU)
 
     def motion_rd_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, source, d_in, d_out, d_mvp=None, rows=None, stream=None, qp=32, max_range=4):
@@ -873,6 +887,13 @@ class Context:
         rb, re = rows if rows is not None else (0, self.ctus_y)
         self._check(self.lib.fhevc_motion_rd_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range, source,
                                                     d_in, d_mvp, d_out, stream))
+
+    def motion_rd_qt_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, source, d_in, tu_depths, d_out, d_mvp=None, rows=None, stream=None, qp=32,
+                            max_range=4):
+        """motion_rd_device at tu_depths (2 or 3) TU depths.  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_motion_rd_qt_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range, source,
+                                                       d_in, d_mvp, tu_depths, d_out, stream))
 
     @staticmethod
     def rd_pu_inputs(nodes, pus=None, pus_small=None, merge_pus=None, merge_pus_small=None, mvp_nodes=None, mvp_pus=None, mvp_pus_small=None, shapes=None, fold=None):
@@ -885,6 +906,13 @@ class Context:
         prediction composed from the two parts' vectors: nodes / pus / pus_small [numCtus, 85 / 124 / 384] MOTION_QPEL_DTYPE, their merge records
         (MOTION_MERGE_DTYPE) and predictor records (MOTION_MVP_DTYPE) or None, shapes [numCtus, 85] SHAPE_DTYPE, fold: an earlier call's result to fold into
         -> [numCtus, 85] MOTION_RD_PU_DTYPE"""
+        return self.motion_rd_pu_qt(cur_plane, ref_plane, part_mode, nodes, None, pus, pus_small, merge_pus, merge_pus_small, mvp_nodes, mvp_pus, mvp_pus_small, shapes,
+                                    fold, origin, stride, qp, max_range)
+
+    def motion_rd_pu_qt(self, cur_plane, ref_plane, part_mode, nodes, tu_depths=3, pus=None, pus_small=None, merge_pus=None, merge_pus_small=None, mvp_nodes=None,
+                        mvp_pus=None, mvp_pus_small=None, shapes=None, fold=None, origin=0, stride=None, qp=32, max_range=4):
+        """motion_rd_pu at tu_depths TU depths (2: motion_rd_pu's bytes; 3: HM's full residual quad-tree; None: the entry point without the argument); fold may
+        come from a call at either depth count"""
         cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
         keep, ptrs = [], []
         for a, per_ctu, size in ((nodes, 85, 16), (pus, 124, 16), (pus_small, 384, 16), (merge_pus, 124, 16), (merge_pus_small, 384, 16), (mvp_nodes, 85, 8),
@@ -898,7 +926,8 @@ class Context:
             ptrs.append(a.ctypes.data)
         inputs = MotionRdPuInputs(*ptrs)
         out = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_RD_PU_DTYPE)
-        self._check(self.lib.fhevc_motion_rd_pu(self.h, cur, ref, stride, qp, max_range, part_mode, C.byref(inputs), out.ctypes.data))
+        head = (self.h, cur, ref, stride, qp, max_range, part_mode, C.byref(inputs))
+        self._check(self.lib.fhevc_motion_rd_pu(*head, out.ctypes.data) if tu_depths is None else self.lib.fhevc_motion_rd_pu_qt(*head, tu_depths, out.ctypes.data))
         return out.reshape(self.num_ctus, NODES_PER_CTU)
 
     def motion_rd_pu_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, part_mode, inputs, d_out, rows=None, stream=None, qp=32, max_range=4):
@@ -908,6 +937,13 @@ class Context:
         rb, re = rows if rows is not None else (0, self.ctus_y)
         self._check(self.lib.fhevc_motion_rd_pu_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range, part_mode,
                                                        C.byref(inputs) if inputs is not None else None, d_out, stream))
+
+    def motion_rd_pu_qt_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, part_mode, inputs, tu_depths, d_out, rows=None, stream=None, qp=32,
+                               max_range=4):
+        """motion_rd_pu_device at tu_depths (2 or 3) TU depths; inputs.fold may hold records of either depth count.  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_motion_rd_pu_qt_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, max_range, part_mode,
+                                                          C.byref(inputs) if inputs is not None else None, tu_depths, d_out, stream))
 
     def intra_rd(self, plane, first, fold=None, rd_merge=None, skip_mask=0, origin=0, stride=None, qp=32):
         """config 4: the RD estimate of the intra candidate of every CU node of one picture -- first [numCtus, 85] NODE_DTYPE (the first pass's records: the
@@ -1237,13 +1273,20 @@ class Context:
         """p_tree_amvp_frame carried to the RD stage: behind the selection the RD estimate of the nodes' merge records, the RD estimates of 2Nx2N and of the
         selection's best and second size folded per node, and the RD tree -> (depth_min, depth_max) [numCtus, 256], then the records asked for [numCtus, 85]:
         SHAPE_DTYPE, MOTION_MERGE_DTYPE, MOTION_RD_DTYPE (of the merge records), MOTION_RD_PU_DTYPE (folded)"""
+        return self.p_tree_rd_qt_frame(cur_plane, ref_plane, None, origin, stride, qp, search_range, coarse_range, shape_rule, tree_rule, skip_mask, with_shapes,
+                                       with_merge, with_rd_merge, with_rd_pu)
+
+    def p_tree_rd_qt_frame(self, cur_plane, ref_plane, tu_depths=3, origin=0, stride=None, qp=32, search_range=8, coarse_range=0, shape_rule=None, tree_rule=None,
+                           skip_mask=3, with_shapes=False, with_merge=False, with_rd_merge=False, with_rd_pu=False):
+        """p_tree_rd_frame with all four RD launches at tu_depths TU depths (2: p_tree_rd_frame's bytes; None: the entry point without the argument)"""
         cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
         dmin, dmax = np.zeros(self.num_ctus * 256, np.uint8), np.zeros(self.num_ctus * 256, np.uint8)
         wanted = ((with_shapes, SHAPE_DTYPE), (with_merge, MOTION_MERGE_DTYPE), (with_rd_merge, MOTION_RD_DTYPE), (with_rd_pu, MOTION_RD_PU_DTYPE))
         arrays = [np.zeros(self.num_ctus * NODES_PER_CTU, dt) if want else None for want, dt in wanted]
-        self._check(self.lib.fhevc_p_tree_rd_frame(self.h, cur, ref, stride, qp, search_range, coarse_range, C.byref(shape_rule) if shape_rule is not None else None,
-                                                   C.byref(tree_rule) if tree_rule is not None else None, skip_mask, dmin.ctypes.data, dmax.ctypes.data,
-                                                   *[a.ctypes.data if a is not None else None for a in arrays]))
+        head = (self.h, cur, ref, stride, qp, search_range, coarse_range, C.byref(shape_rule) if shape_rule is not None else None,
+                C.byref(tree_rule) if tree_rule is not None else None, skip_mask)
+        tail = (dmin.ctypes.data, dmax.ctypes.data, *[a.ctypes.data if a is not None else None for a in arrays])
+        self._check(self.lib.fhevc_p_tree_rd_frame(*head, *tail) if tu_depths is None else self.lib.fhevc_p_tree_rd_qt_frame(*head, tu_depths, *tail))
         out = (dmin.reshape(self.num_ctus, 256), dmax.reshape(self.num_ctus, 256))
         for a in arrays:
             out += (a.reshape(self.num_ctus, NODES_PER_CTU),) if a is not None else ()

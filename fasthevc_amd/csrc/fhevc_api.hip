@@ -18,8 +18,8 @@ void time_resolve(fhevc_ctx* c)
   for (auto& t : c->pending) {
     float ms = 0;
     if (hipEventSynchronize(t.stop) == hipSuccess && hipEventElapsedTime(&ms, t.start, t.stop) == hipSuccess) {
-      c->sum_ms[t.which] += ms;
-      c->launches[t.which] += 1;
+      c->slot_ms(t.which) += ms;
+      c->slot_launches(t.which) += 1;
       if (t.which == 0) c->stats.last_cnn_ms = ms;
       if (t.which == 1) c->stats.last_hadamard_ms = ms;
       if (t.which == 2) c->stats.last_first_pass_ms = ms;
@@ -187,12 +187,14 @@ int fhevc_kernel_timing(fhevc_ctx* c, int which, int reset, double* avg_ms, uint
 {
   // 14, 16, 18, 20, 22, 24 and 26 stay rejected: callers probe them as the first numbers behind the slots of the partition-size selection, of the centred chain,
   // of the tree, of the two merge stages, of the zero-residual test, of the re-pricing and of the intra stage (28; 29 is the RD estimate); 30 likewise, 31 is the RD estimate under a partition size; 32 likewise, 33 is the RD
-  // estimate of the intra candidate
+  // estimate of the intra candidate; 34 likewise, 35 is the RD estimates at three TU depths: the one slot beside the table
+  if (which != 35)
   if (!c || which < 0 || which > 33 || which == 32 || which == 30 || which == 28 || which == 14 || which == 16 || which == 18 || which == 20 || which == 22 || which == 24 || which == 26) return FHEVC_E_INVALID;
+  if (!c) return FHEVC_E_INVALID;
   time_resolve(c);
-  if (avg_ms) *avg_ms = c->launches[which] ? c->sum_ms[which] / (double)c->launches[which] : 0.0;
-  if (launches) *launches = c->launches[which];
-  if (reset) { c->sum_ms[which] = 0; c->launches[which] = 0; }
+  if (avg_ms) *avg_ms = c->slot_launches(which) ? c->slot_ms(which) / (double)c->slot_launches(which) : 0.0;
+  if (launches) *launches = c->slot_launches(which);
+  if (reset) { c->slot_ms(which) = 0; c->slot_launches(which) = 0; }
   return FHEVC_OK;
 }
 

@@ -51,9 +51,13 @@ struct fhevc_ctx {
   bool timing = false;
   std::vector<TimedLaunch> pending;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-  // per timing slot (14, 16, 18, 20, 22, 24, 26, 28, 30 and 32 are not in use); config 4's slots and its staging buffers d_pair .. d_intra_p: the tables in fhevc_motion_api.hip
+  // per timing slot (14, 16, 18, 20, 22, 24, 26, 28, 30, 32 and 34 are not in use); config 4's slots and its staging buffers d_pair .. d_intra_p: the tables in fhevc_motion_api.hip
   double sum_ms[34] = {};
   uint64_t launches[34] = {};
+  double sum_ms_35 = 0;        // slot 35 (the RD estimates at three TU depths) beside the table: 34 is no slot
+  uint64_t launches_35 = 0;
+  double& slot_ms(int which) { return which == 35 ? sum_ms_35 : sum_ms[which]; }
+  uint64_t& slot_launches(int which) { return which == 35 ? launches_35 : launches[which]; }
   double* d_act = nullptr;
   int16_t* d_pair = nullptr;
   FhevcMotionNode *d_motion = nullptr, *d_motion_pu = nullptr, *d_motion_pu_small = nullptr, *d_centres = nullptr;

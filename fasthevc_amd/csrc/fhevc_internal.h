@@ -349,7 +349,7 @@ inline FhevcRdQuant fhevc_rd_quant(int qp, int bit_depth)
 // fr, max_range as fhevc_launch_motion_skip; source 0: d_in are merge records, 1: refined (or re-priced) nodes, d_mvp (may be null) their predictor records;
 // d_in, d_out: (num_frames - 1) * band CTUs * 85 records
 hipError_t fhevc_launch_motion_rd(const FhevcFrames& fr, int max_range, const FhevcRdQuant& q, int source, const void* d_in, const FhevcMotionMvp* d_mvp,
-                                  FhevcMotionRdNode* d_out, int num_cus, hipStream_t stream);
+                                  FhevcMotionRdNode* d_out, int num_cus, hipStream_t stream, int tu_depths = 2);
 
 // ... of a node under any of HM's seven inter partition sizes, the prediction composed from its two parts' vectors (the PU instances of k_motion_rd.hip):
 // bytes 0..11 as FhevcMotionRdNode, so the tree kernels read cost_rd and flags where they always do
@@ -366,8 +366,12 @@ struct FhevcMotionRdPuInputs {
   const FhevcMotionRdPuNode* fold;
 };
 // part_mode 0, 1, 2, 4..7: that PartSize for every node; 8 / 9: the selection's best / second; I.fold == d_out is allowed
+// tu_depths (both launchers): 2 -- the instances there always were; 3 -- the instances with HM's third TU size for the 32x32 and 16x16 nodes (tu_split bits 4..7)
 hipError_t fhevc_launch_motion_rd_pu(const FhevcFrames& fr, int max_range, const FhevcRdQuant& q, int part_mode, const FhevcMotionRdPuInputs& I, FhevcMotionRdPuNode* d_out,
-                                     int num_cus, hipStream_t stream);
+                                     int num_cus, hipStream_t stream, int tu_depths = 2);
+
+// workgroups of an MR = 64 instance of the RD kernel that the device keeps on one CU (hipOccupancyMaxActiveBlocksPerMultiprocessor; measurement tools)
+hipError_t fhevc_motion_rd_big_residency(int sample_bytes, bool pu, int tu_depths, int* per_cu);
 
 // ... and of the intra candidate (the intra instances of k_motion_rd.hip): ONE mode per node, the first pass's, predicted per TU from the first pass's own
 // lines; the record is a FhevcMotionRdPuNode with part kRdPartIntra and the mode in pad[0].  fr: num_frames pictures, no pairing; d_first: num_frames * band

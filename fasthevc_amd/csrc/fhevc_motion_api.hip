@@ -145,7 +145,8 @@ int device_form(fhevc_ctx* c, bool args_ok, const char* bad_args, const Batch& b
 // The timing slots (fhevc_kernel_timing) of the launches below: 4 fhevc_motion_search, 5 the P rule, 7 fhevc_motion_refine, 8 / 9 the searches of the PUs / the
 // small PUs, 10 fhevc_motion_refine_pu, 11 / 12 the wide search / refinement, 13 the partition sizes, 15 the centres and everything centred, 17 the tree, 19 the merge stage,
 // 21 the merge stage per PU, 23 the zero-residual test, 25 the re-pricing against neighbour predictors, 27 the intra stage, 29 the RD estimate, 31 the RD estimate under a partition size,
-// 33 the RD estimate of the intra candidate
+// 33 the RD estimate of the intra candidate, 35 the RD estimates at three TU depths (fhevc_motion_rd_qt*, fhevc_motion_rd_pu_qt* with tu_depths 3; at 2 they are
+// the launches of slots 29 and 31)
 struct Family { int per_ctu; FhevcMotionNode* fhevc_ctx::*found; FhevcMotionQpelNode* fhevc_ctx::*refined; };
 constexpr Family kNodes = { FHEVC_NODES, &fhevc_ctx::d_motion, &fhevc_ctx::d_qpel }, kPus = { FHEVC_PUS, &fhevc_ctx::d_motion_pu, &fhevc_ctx::d_qpel_pu },
                  kSmall = { FHEVC_PUS_SMALL, &fhevc_ctx::d_motion_pu_small, &fhevc_ctx::d_qpel_pu_small }, kCentres = { 1, &fhevc_ctx::d_centres, nullptr };
@@ -264,6 +265,7 @@ int queue_chain(fhevc_ctx* c, int qp, int search_range, int coarse_range, const 
 }
 
 // what a part mode asks of the inputs of fhevc_motion_rd_pu*, the same for pointers of either kind -> a message, or null
+constexpr const char* kBadTuDepths = "bad RD-stage arguments (tu_depths 2 or 3)";
 const char* rd_pu_mode_error(int part_mode, const fhevc_motion_rd_pu_inputs& in)
 {
   if (part_mode < 0 || part_mode > 9 || part_mode == 3) return "bad partition-size RD-stage arguments (part_mode 0, 1, 2, 4..9)";
@@ -557,16 +559,17 @@ int fhevc_motion_skip(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_
 
 // ---- the RD estimate per CU node at its merge or its explicit vector (k_motion_rd.hip) ----
 
-int fhevc_motion_rd_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
-                           int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, int source, const void* d_in,
-                           const fhevc_motion_mvp* d_mvp, fhevc_motion_rd_node* d_out, void* stream)
+int fhevc_motion_rd_qt_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                              int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, int source, const void* d_in,
+                              const fhevc_motion_mvp* d_mvp, int tu_depths, fhevc_motion_rd_node* d_out, void* stream)
 {
   const Batch b{ d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp };
   // the quantiser's, the dequantiser's and lambda's numbers travel with the launch: nothing of the context is read or written by it
   return device_form(c, d_luma && d_in && d_out, "bad RD-stage arguments", b, max_range, FHEVC_MOTION_WIDE_MAX_RANGE, "bad RD-stage arguments (max_range 1..64)",
-                     stream, 29, "fhevc_launch_motion_rd", [&](const FhevcFrames& fr, hipStream_t s) {
-    return fhevc_launch_motion_rd(fr, max_range, fhevc_rd_quant(qp, c->cfg.bit_depth), source, d_in, kn(d_mvp), kn(d_out), c->num_cus, s);
+                     stream, tu_depths == 3 ? 35 : 29, "fhevc_launch_motion_rd", [&](const FhevcFrames& fr, hipStream_t s) {
+    return fhevc_launch_motion_rd(fr, max_range, fhevc_rd_quant(qp, c->cfg.bit_depth), source, d_in, kn(d_mvp), kn(d_out), c->num_cus, s, tu_depths);
   }, [&]() -> const char* {
+    if (tu_depths != 2 && tu_depths != 3) return kBadTuDepths;
     if (source != FHEVC_RD_SOURCE_MERGE && source != FHEVC_RD_SOURCE_EXPLICIT) return "bad RD-stage arguments (source 0..1)";
     if (d_mvp && source == FHEVC_RD_SOURCE_MERGE) return "bad RD-stage arguments (predictor records go with the explicit source)";
     if (((uintptr_t)d_in | (uintptr_t)d_mvp | (uintptr_t)d_out) & 3) return "bad RD-stage arguments (records are 4-byte aligned)";
@@ -574,38 +577,55 @@ int fhevc_motion_rd_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, i
   });
 }
 
-int fhevc_motion_rd(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range, int source, const void* in,
-                    const fhevc_motion_mvp* mvp, fhevc_motion_rd_node* out)
+// the entry point of two TU depths: the same launch of the same instances
+int fhevc_motion_rd_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
+                           int num_frames, int ctu_row_begin, int ctu_row_end, int qp, int max_range, int source, const void* d_in,
+                           const fhevc_motion_mvp* d_mvp, fhevc_motion_rd_node* d_out, void* stream)
+{
+  return fhevc_motion_rd_qt_device(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp, max_range, source, d_in, d_mvp, 2,
+                                   d_out, stream);
+}
+
+int fhevc_motion_rd_qt(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range, int source, const void* in,
+                       const fhevc_motion_mvp* mvp, int tu_depths, fhevc_motion_rd_node* out)
 {
   const bool source_ok = source == FHEVC_RD_SOURCE_EXPLICIT || (source == FHEVC_RD_SOURCE_MERGE && !mvp);
   const int rc = open_host_form(c, cur_luma && ref_luma && in && out && source_ok, stride_samples, qp, max_range, FHEVC_MOTION_WIDE_MAX_RANGE, "bad RD-stage arguments");
   if (rc != GO) return rc;
+  if (tu_depths != 2 && tu_depths != 3) return fail(c, FHEVC_E_INVALID, kBadTuDepths);   // said before anything is staged
   HostForm h(c);
   const size_t bn = h.bytes(kNodes), all = bn + h.bytes(kPus) + h.bytes(kSmall);
   const void* d_in = h.in(c->d_motion, bn, static_cast<const fhevc_motion_node*>(in), bn);   // 16-byte records of either kind
   const fhevc_motion_mvp* d_mvp = h.in(c->d_amvp_mvp, all / 2, mvp, bn / 2);                  // the head of the re-pricing's predictor records
   fhevc_motion_rd_node* d_out = h.out(c->d_qpel, bn, out, bn);                                // no refined nodes in this call: their buffer is dead
-  return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_rd_device, qp, max_range, source, d_in, d_mvp, d_out, c->stream); });
+  return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_rd_qt_device, qp, max_range, source, d_in, d_mvp, tu_depths, d_out, c->stream); });
+}
+
+int fhevc_motion_rd(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range, int source, const void* in,
+                    const fhevc_motion_mvp* mvp, fhevc_motion_rd_node* out)
+{
+  return fhevc_motion_rd_qt(c, cur_luma, ref_luma, stride_samples, qp, max_range, source, in, mvp, 2, out);
 }
 
 uint32_t fhevc_motion_rd_lambda_q8(int qp) { return fhevc_rd_lambda_q8(qp < 0 ? 0 : (qp > 51 ? 51 : qp)); }
 
 // ---- the RD estimate of a CU node under a partition size, folded over several launches (the PU instances of k_motion_rd.hip) ----
 
-int fhevc_motion_rd_pu_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames,
-                              int ctu_row_begin, int ctu_row_end, int qp, int max_range, int part_mode, const fhevc_motion_rd_pu_inputs* inputs,
-                              fhevc_motion_rd_pu_node* d_out, void* stream)
+int fhevc_motion_rd_pu_qt_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames,
+                                 int ctu_row_begin, int ctu_row_end, int qp, int max_range, int part_mode, const fhevc_motion_rd_pu_inputs* inputs, int tu_depths,
+                                 fhevc_motion_rd_pu_node* d_out, void* stream)
 {
   const Batch b{ d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp };
   fhevc_motion_rd_pu_inputs in{};   // read here, handed to the kernel by value: the caller's struct is free again when this call returns
   if (inputs) in = *inputs;
   // as for the RD stage, everything the kernel needs travels with the launch: nothing of the context is read or written by it
   return device_form(c, d_luma && inputs && in.nodes && d_out, "bad partition-size RD-stage arguments", b, max_range, FHEVC_MOTION_WIDE_MAX_RANGE,
-                     "bad partition-size RD-stage arguments (max_range 1..64)", stream, 31, "fhevc_launch_motion_rd_pu", [&](const FhevcFrames& fr, hipStream_t s) {
+                     "bad partition-size RD-stage arguments (max_range 1..64)", stream, tu_depths == 3 ? 35 : 31, "fhevc_launch_motion_rd_pu", [&](const FhevcFrames& fr, hipStream_t s) {
     const FhevcMotionRdPuInputs k = { kn(in.nodes), kn(in.pus), kn(in.pus_small), kn(in.merge_pus), kn(in.merge_pus_small), kn(in.mvp_nodes), kn(in.mvp_pus),
                                       kn(in.mvp_pus_small), kn(in.shapes), kn(in.fold) };
-    return fhevc_launch_motion_rd_pu(fr, max_range, fhevc_rd_quant(qp, c->cfg.bit_depth), part_mode, k, kn(d_out), c->num_cus, s);
+    return fhevc_launch_motion_rd_pu(fr, max_range, fhevc_rd_quant(qp, c->cfg.bit_depth), part_mode, k, kn(d_out), c->num_cus, s, tu_depths);
   }, [&]() -> const char* {
+    if (tu_depths != 2 && tu_depths != 3) return kBadTuDepths;
     if (const char* bad = rd_pu_mode_error(part_mode, in)) return bad;
     const uintptr_t all = (uintptr_t)in.nodes | (uintptr_t)in.pus | (uintptr_t)in.pus_small | (uintptr_t)in.merge_pus | (uintptr_t)in.merge_pus_small |
                           (uintptr_t)in.mvp_nodes | (uintptr_t)in.mvp_pus | (uintptr_t)in.mvp_pus_small | (uintptr_t)in.shapes | (uintptr_t)in.fold | (uintptr_t)d_out;
@@ -619,13 +639,22 @@ int fhevc_motion_rd_pu_device(fhevc_ctx* c, const void* d_luma, int sample_bytes
   });
 }
 
-int fhevc_motion_rd_pu(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range, int part_mode,
-                       const fhevc_motion_rd_pu_inputs* inputs, fhevc_motion_rd_pu_node* out)
+int fhevc_motion_rd_pu_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames,
+                              int ctu_row_begin, int ctu_row_end, int qp, int max_range, int part_mode, const fhevc_motion_rd_pu_inputs* inputs,
+                              fhevc_motion_rd_pu_node* d_out, void* stream)
+{
+  return fhevc_motion_rd_pu_qt_device(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp, max_range, part_mode, inputs, 2,
+                                      d_out, stream);
+}
+
+int fhevc_motion_rd_pu_qt(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range, int part_mode,
+                          const fhevc_motion_rd_pu_inputs* inputs, int tu_depths, fhevc_motion_rd_pu_node* out)
 {
   const int rc = open_host_form(c, cur_luma && ref_luma && inputs && inputs->nodes && out, stride_samples, qp, max_range, FHEVC_MOTION_WIDE_MAX_RANGE,
                                 "bad partition-size RD-stage arguments");
   if (rc != GO) return rc;
   const fhevc_motion_rd_pu_inputs& in = *inputs;
+  if (tu_depths != 2 && tu_depths != 3) return fail(c, FHEVC_E_INVALID, kBadTuDepths);
   if (const char* bad = rd_pu_mode_error(part_mode, in)) return fail(c, FHEVC_E_INVALID, bad);   // said before anything is staged
   HostForm h(c);
   const size_t bn = h.bytes(kNodes), bp = h.bytes(kPus), bs = h.bytes(kSmall), all = bn + bp + bs;
@@ -637,7 +666,13 @@ int fhevc_motion_rd_pu(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref
   d.shapes = h.in(c->d_motion, bn, in.shapes, bn);
   d.fold = h.in(c->d_qpel, bn, in.fold, bn);                       // folded in place on the device: the earlier records go up to where the new ones come from
   fhevc_motion_rd_pu_node* d_out = h.out(c->d_qpel, bn, out, bn);
-  return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_rd_pu_device, qp, max_range, part_mode, &d, d_out, c->stream); });
+  return h.run(cur_luma, ref_luma, stride_samples, [&] { return on_pair(c, fhevc_motion_rd_pu_qt_device, qp, max_range, part_mode, &d, tu_depths, d_out, c->stream); });
+}
+
+int fhevc_motion_rd_pu(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range, int part_mode,
+                       const fhevc_motion_rd_pu_inputs* inputs, fhevc_motion_rd_pu_node* out)
+{
+  return fhevc_motion_rd_pu_qt(c, cur_luma, ref_luma, stride_samples, qp, max_range, part_mode, inputs, 2, out);
 }
 
 // ---- the RD estimate of the intra candidate per CU node, gated and folded (the intra instances of k_motion_rd.hip) ----
@@ -882,6 +917,15 @@ int fhevc_debug_refine_pu_wide_residency(fhevc_ctx* c, int sample_bytes, int* bl
   return FHEVC_OK;
 }
 
+// measurement tools only (tools/motion_rd_qt_bench.py; not in fasthevc.h): the same answer for an MR = 64 instance of k_motion_rd.hip
+int fhevc_debug_motion_rd_wide_residency(fhevc_ctx* c, int sample_bytes, int pu, int tu_depths, int* blocks_per_cu)
+{
+  if (!c || !blocks_per_cu || (sample_bytes != 1 && sample_bytes != 2) || (tu_depths != 2 && tu_depths != 3)) return FHEVC_E_INVALID;
+  (void)hipSetDevice(c->device);
+  HIP_TRY(c, fhevc_motion_rd_big_residency(sample_bytes, pu != 0, tu_depths, blocks_per_cu));
+  return FHEVC_OK;
+}
+
 // ---- P-picture depth ranges over a device-resident batch (k_p_rule.hip; the host form of the rule: fhevc_host.hip) ----
 int fhevc_p_depth_range_device(fhevc_ctx* c, const fhevc_motion_node* d_nodes, const uint8_t* d_prev_maps, int num_pictures, int ctu_row_begin,
                                int ctu_row_end, int qp, int prev_mode, const fhevc_p_rule* rule, uint8_t* d_depth_min, uint8_t* d_depth_max, void* stream)
@@ -1104,7 +1148,7 @@ int fhevc_intra_p(fhevc_ctx* c, int qp, const fhevc_node_cost* first, const fhev
 // nodes' merge records, the RD estimates of 2Nx2N and of the selection's best and second size folded into one record per node, and the RD tree
 // (fhevc_p_tree_rd_intra_frame: intra -- behind the folded inter records the first pass of the current picture and the RD estimate of its winners, gated and
 // folded in place)
-struct RdFrameOut { fhevc_motion_rd_node* rd_merge; fhevc_motion_rd_pu_node* rd_pu; bool intra; fhevc_node_cost* first; };
+struct RdFrameOut { fhevc_motion_rd_node* rd_merge; fhevc_motion_rd_pu_node* rd_pu; bool intra; fhevc_node_cost* first; int tu_depths = 2; };
 static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
                            const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes,
                            bool with_merge, fhevc_motion_merge_node* merge, bool with_merge_pu = false, bool with_amvp = false, bool with_intra = false, int skip_mask = 0,
@@ -1120,6 +1164,7 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
   if (tree_rule)
     if (const char* bad = fhevc_p_tree_rule_error(*tree_rule)) return fail(c, FHEVC_E_INVALID, bad);
   if ((with_intra || with_rd) && (skip_mask < 0 || skip_mask > 3)) return fail(c, FHEVC_E_INVALID, "bad tree-decision frame arguments (skip_mask 0..3)");
+  if (with_rd && with_rd->tu_depths != 2 && with_rd->tu_depths != 3) return fail(c, FHEVC_E_INVALID, kBadTuDepths);
   HostForm h(c);
   const size_t map = (size_t)c->num_ctus * 256, records = h.bytes(kNodes);
   Chain k = claim_chain(h, coarse_range != 0);
@@ -1181,14 +1226,15 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
       rc = fhevc_pu_shape_select_merge_device(c, k.q_nodes, k.q_pus, k.q_small, d_merge_pus, d_merge_small, 1, 0, c->ctus_y, shape_rule, d_shapes, nullptr, nullptr, c->stream);
     else if (rc == FHEVC_OK) rc = fhevc_pu_shape_select_device(c, k.q_nodes, k.q_pus, k.q_small, 1, 0, c->ctus_y, shape_rule, d_shapes, nullptr, c->stream);
     if (rc == FHEVC_OK && with_rd) {
-      rc = on_pair(c, fhevc_motion_rd_device, qp, merge_range, FHEVC_RD_SOURCE_MERGE, static_cast<const void*>(d_merge), static_cast<const fhevc_motion_mvp*>(nullptr), d_rd_merge,
-                   c->stream);
+      const int tud = with_rd->tu_depths;   // all four RD launches at one depth count: both sides of every comparison of the tree on one footing
+      rc = on_pair(c, fhevc_motion_rd_qt_device, qp, merge_range, FHEVC_RD_SOURCE_MERGE, static_cast<const void*>(d_merge), static_cast<const fhevc_motion_mvp*>(nullptr), tud,
+                   d_rd_merge, c->stream);
       // 2Nx2N first, then the selection's best and its second size: the earlier record stays on a tie, as xCheckBestMode keeps the earlier mode
       fhevc_motion_rd_pu_inputs in = { k.q_nodes, k.q_pus, k.q_small, d_merge_pus, d_merge_small, d_mvp_nodes, d_mvp_pus, d_mvp_small, d_shapes, nullptr };
-      if (rc == FHEVC_OK) rc = on_pair(c, fhevc_motion_rd_pu_device, qp, merge_range, 0, &in, d_rd_pu, c->stream);
+      if (rc == FHEVC_OK) rc = on_pair(c, fhevc_motion_rd_pu_qt_device, qp, merge_range, 0, &in, tud, d_rd_pu, c->stream);
       in.fold = d_rd_pu;
-      if (rc == FHEVC_OK) rc = on_pair(c, fhevc_motion_rd_pu_device, qp, merge_range, 8, &in, d_rd_pu, c->stream);
-      if (rc == FHEVC_OK) rc = on_pair(c, fhevc_motion_rd_pu_device, qp, merge_range, 9, &in, d_rd_pu, c->stream);
+      if (rc == FHEVC_OK) rc = on_pair(c, fhevc_motion_rd_pu_qt_device, qp, merge_range, 8, &in, tud, d_rd_pu, c->stream);
+      if (rc == FHEVC_OK) rc = on_pair(c, fhevc_motion_rd_pu_qt_device, qp, merge_range, 9, &in, tud, d_rd_pu, c->stream);
       if (rc == FHEVC_OK && with_rd->intra) {
         const int16_t* d_cur = c->d_pair + pair_plane(c);   // the current picture of the staged pair, as a batch of one frame
         rc = fhevc_intra_first_pass_device(c, d_cur, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, d_first_rd, c->stream);
@@ -1249,6 +1295,15 @@ int fhevc_p_tree_rd_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* 
                           fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge, fhevc_motion_rd_node* rd_merge, fhevc_motion_rd_pu_node* rd_pu)
 {
   const RdFrameOut rd = { rd_merge, rd_pu, false, nullptr };
+  return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge, true, true,
+                         false, skip_mask, nullptr, &rd);
+}
+
+int fhevc_p_tree_rd_qt_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                             const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, int skip_mask, int tu_depths, uint8_t* depth_min, uint8_t* depth_max,
+                             fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge, fhevc_motion_rd_node* rd_merge, fhevc_motion_rd_pu_node* rd_pu)
+{
+  const RdFrameOut rd = { rd_merge, rd_pu, false, nullptr, tu_depths };
   return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge, true, true,
                          false, skip_mask, nullptr, &rd);
 }

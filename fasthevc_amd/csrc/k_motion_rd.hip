@@ -36,6 +36,7 @@
 #include "k_had8x8.h"
 #include "k_refine_tile.h"
 #include "k_firstpass_common.h"
+#include <type_traits>
 
 namespace {
 
@@ -47,6 +48,8 @@ constexpr int kFwdShorts = 32 * 32;              // the 32-point matrix behind t
 constexpr int kInvShorts = 32 * 32 + 16 * 16 + 8 * 8 + 4 * 4;   // ... and the four transposes behind it
 constexpr int kRowsInFlight = 2;                 // matrix rows the scheduler may fetch ahead of their products
 constexpr int kTus = 88, kAccWords = 5;          // per depth-0 TU: D0, bits0 - 1, sum D1, sum bits1 - 4, max |c| at depth 0
+constexpr int kFineTus = 16 + 64, kFineWords = 4;   // three TU depths: per depth-1 TU of levels 1 and 2: D1, bits1 - 1, sum D2, sum bits2 - 4
+constexpr int kFineShorts = kFineTus * kFineWords * 2;   // ... as shorts: 1 280 B behind the matrices
 enum { ROWS = 0, COLS = 1, INV1 = 2, INV2 = 3 };
 
 constexpr int ilog2(int n) { return n <= 1 ? 0 : 1 + ilog2(n >> 1); }
@@ -120,9 +123,17 @@ __device__ __forceinline__ int dot_row(const short* m, const unsigned (&x)[N / 2
 __device__ __forceinline__ int clip16(int v) { return min(max(v, -32768), 32767); }
 
 // eight neighbouring lanes (rows that share every depth-0 TU) into one, then that lane into the TU's sums
-template <int DEPTH>
+// FINE: tu counts depth-1 TUs (eight rows share those too: two 4x4 TUs of one 8x8 parent at the least) and acc holds their four words
+template <int DEPTH, bool FINE = false>
 __device__ __forceinline__ void rd_commit(unsigned* acc, int tu, int lane, unsigned bits, unsigned top)
 {
+  if constexpr (FINE) {
+    static_assert(DEPTH >= 1, "a depth-1 TU has no depth 0");
+#pragma unroll
+    for (int d = 1; d < 8; d <<= 1) bits += (unsigned)__shfl_xor((int)bits, d);
+    if ((lane & 7) == 0) atomicAdd(&acc[kFineWords * tu + 2 * DEPTH - 1], bits);
+    return;
+  }
 #pragma unroll
   for (int d = 1; d < 8; d <<= 1) {
     bits += (unsigned)__shfl_xor((int)bits, d);
@@ -135,8 +146,8 @@ __device__ __forceinline__ void rd_commit(unsigned* acc, int tu, int lane, unsig
 }
 
 // one pass over one buffer at TU size N: the thread's 16 outputs, packed two to a register until the barrier.  COLS quantises, prices and dequantises them
-// and commits the sums of every unit to its depth-0 TU: tu0 = the buffer's first, l0 = log2 of the buffer's depth-0 TU size
-template <int N, int STAGE, int DEPTH>
+// and commits the sums of every unit to its depth-0 TU: tu0 = the buffer's first, l0 = log2 of the buffer's depth-0 TU size (FINE: of its depth-1 TUs)
+template <int N, int STAGE, int DEPTH, bool FINE = false>
 __device__ __forceinline__ void tu_pass(const short* tables, const short* buf, int lane, int wave, int bd, const FhevcRdQuant& Q, unsigned* acc, int tu0, int l0,
                                         unsigned (&t)[8])
 {
@@ -169,7 +180,11 @@ __device__ __forceinline__ void tu_pass(const short* tables, const short* buf, i
       else t[o >> 1] = (unsigned)a & 0xFFFFu;
       if ((i & (kRowsInFlight - 1)) == kRowsInFlight - 1) __builtin_amdgcn_sched_barrier(0);   // or every matrix row of the pass is fetched ahead, into registers
     }
-    if (STAGE == COLS) rd_commit<DEPTH>(acc, tu0 + ((lane >> l0) << (6 - l0)) + ((seg * N) >> l0), lane, bits, top);
+    if (STAGE == COLS) {
+      int ln = lane;   // FINE: opaque, so that the depth-1 TU's index is worked out here and not kept through the CTU loop beside the depth-0 TU's
+      if constexpr (FINE) asm volatile("" : "+v"(ln));
+      rd_commit<DEPTH, FINE>(acc, tu0 + ((ln >> l0) << (6 - l0)) + ((seg * N) >> l0), ln, bits, top);
+    }
   }
 }
 
@@ -202,41 +217,67 @@ __device__ __forceinline__ void tu_store(short* buf, int lane, int wave, const u
 }
 
 // one pass over the four buffers: levels 0 and 1 at 32 >> DEPTH, level 2 at 16 >> DEPTH, level 3 at 8 >> DEPTH
-template <int STAGE, int DEPTH>
+// QT (three TU depths): the sums of depths 1 and 2 of the level-1 and level-2 buffers go per depth-1 TU into the words behind the matrices; DEPTH 2 is a
+// pass over those two buffers alone, at 8 and 4, by all four waves
+template <int STAGE, int DEPTH, bool QT = false>
 __device__ __forceinline__ void rd_stage(short* s, int lane, int wave, int bd, const FhevcRdQuant& Q, unsigned* acc)
 {
-  constexpr int NA = 32 >> DEPTH, NB = 16 >> DEPTH, NC = 8 >> DEPTH;
+  static_assert(DEPTH < 2 || QT, "the third depth goes with QT");
   const short* tables = s + kTransformShorts;
   short *const b0 = s, *const b1 = s + kLevelBuf, *const b2 = s + 2 * kLevelBuf, *const b3 = s + 3 * kLevelBuf;
-  unsigned t0[8], t1[8], t2[8], t3[8];
-  tu_pass<NA, STAGE, DEPTH>(tables, b0, lane, wave, bd, Q, acc, 0, 5, t0);
-  tu_pass<NA, STAGE, DEPTH>(tables, b1, lane, wave, bd, Q, acc, 4, 5, t1);
-  tu_pass<NB, STAGE, DEPTH>(tables, b2, lane, wave, bd, Q, acc, 8, 4, t2);
-  tu_pass<NC, STAGE, DEPTH>(tables, b3, lane, wave, bd, Q, acc, 24, 3, t3);
-  __syncthreads();   // every thread has read
-  tu_store<NA, STAGE>(b0, lane, wave, t0);
-  tu_store<NA, STAGE>(b1, lane, wave, t1);
-  tu_store<NB, STAGE>(b2, lane, wave, t2);
-  tu_store<NC, STAGE>(b3, lane, wave, t3);
-  __syncthreads();
+  if constexpr (DEPTH == 2) {
+    unsigned* const fine = reinterpret_cast<unsigned*>(s + kTransformShorts + kFwdShorts + kInvShorts);
+    unsigned t1[8], t2[8];
+    tu_pass<8, STAGE, 2, true>(tables, b1, lane, wave, bd, Q, fine, 0, 4, t1);
+    tu_pass<4, STAGE, 2, true>(tables, b2, lane, wave, bd, Q, fine, 16, 3, t2);
+    __syncthreads();   // every thread has read
+    tu_store<8, STAGE>(b1, lane, wave, t1);
+    tu_store<4, STAGE>(b2, lane, wave, t2);
+    __syncthreads();
+  } else {
+    constexpr int NA = 32 >> DEPTH, NB = 16 >> DEPTH, NC = 8 >> DEPTH;
+    unsigned t0[8], t1[8], t2[8], t3[8];
+    tu_pass<NA, STAGE, DEPTH>(tables, b0, lane, wave, bd, Q, acc, 0, 5, t0);
+    if constexpr (QT && DEPTH == 1) {
+      unsigned* const fine = reinterpret_cast<unsigned*>(s + kTransformShorts + kFwdShorts + kInvShorts);
+      tu_pass<NA, STAGE, DEPTH, true>(tables, b1, lane, wave, bd, Q, fine, 0, 4, t1);
+      tu_pass<NB, STAGE, DEPTH, true>(tables, b2, lane, wave, bd, Q, fine, 16, 3, t2);
+    } else {
+      tu_pass<NA, STAGE, DEPTH>(tables, b1, lane, wave, bd, Q, acc, 4, 5, t1);
+      tu_pass<NB, STAGE, DEPTH>(tables, b2, lane, wave, bd, Q, acc, 8, 4, t2);
+    }
+    tu_pass<NC, STAGE, DEPTH>(tables, b3, lane, wave, bd, Q, acc, 24, 3, t3);
+    __syncthreads();   // every thread has read
+    tu_store<NA, STAGE>(b0, lane, wave, t0);
+    tu_store<NA, STAGE>(b1, lane, wave, t1);
+    tu_store<NB, STAGE>(b2, lane, wave, t2);
+    tu_store<NC, STAGE>(b3, lane, wave, t3);
+    __syncthreads();
+  }
 }
 
 // one depth of the TU tree: the residual tiles into the buffers, the four passes, xGetSSE of this lane's tile of the rebuilt block (the per-sample shift
 // of TComRdCost.cpp:1190-1199) summed over the tiles of its depth-0 TU
 // The original tile is loaded a second time here (from the cache): kept in registers across the passes it cost the kernel its second wave per SIMD
-template <int DEPTH, typename T>
+// QT (three TU depths): at depths 1 and 2 the level-1 and level-2 waves sum over the tiles of their depth-1 TU (2 x 2 tiles, the lane's own) and store per
+// depth-1 TU; at depth 2 only they rewrite their tiles and take the squared error -- the other two buffers have no third depth
+template <int DEPTH, typename T, bool QT = false>
 __device__ __forceinline__ void rd_depth(short* s, int lane, int lvl, int wave, int tx, int ty, const FhevcRdQuant& Q, unsigned* acc, const T* plane, long long cur_base,
                                          const FhevcFrames& F, int px, int py, bool inside, const unsigned (&D)[32])
 {
   const int bd = F.bit_depth;
   short* const tile = s + lvl * kLevelBuf + (ty * 8) * kPitch + tx * 8;
+  const bool fine = QT && DEPTH >= 1 && (wave == 1 || wave == 2);   // wave-uniform
+  if (DEPTH < 2 || fine) {
 #pragma unroll
-  for (int y = 0; y < 8; ++y) *reinterpret_cast<uint4*>(tile + y * kPitch) = make_uint4(D[4 * y], D[4 * y + 1], D[4 * y + 2], D[4 * y + 3]);
+    for (int y = 0; y < 8; ++y) *reinterpret_cast<uint4*>(tile + y * kPitch) = make_uint4(D[4 * y], D[4 * y + 1], D[4 * y + 2], D[4 * y + 3]);
+  }
   __syncthreads();
-  rd_stage<ROWS, DEPTH>(s, lane, wave, bd, Q, acc);
-  rd_stage<COLS, DEPTH>(s, lane, wave, bd, Q, acc);
-  rd_stage<INV1, DEPTH>(s, lane, wave, bd, Q, acc);
-  rd_stage<INV2, DEPTH>(s, lane, wave, bd, Q, acc);
+  rd_stage<ROWS, DEPTH, QT>(s, lane, wave, bd, Q, acc);
+  rd_stage<COLS, DEPTH, QT>(s, lane, wave, bd, Q, acc);
+  rd_stage<INV1, DEPTH, QT>(s, lane, wave, bd, Q, acc);
+  rd_stage<INV2, DEPTH, QT>(s, lane, wave, bd, Q, acc);
+  if (DEPTH == 2 && !fine) { __syncthreads(); return; }
   const int top = (1 << bd) - 1, sh = 2 * (bd - 8);
   unsigned O[32];
   load_tile8x8(plane, cur_base, F, px, py, inside, O);
@@ -252,6 +293,21 @@ __device__ __forceinline__ void rd_depth(short* s, int lane, int lvl, int wave, 
       const int e1 = (int)(o >> 16) - min(max((int)(p >> 16) + (int)(short)(r[k] >> 16), 0), top);
       sum += ((unsigned)(e0 * e0) >> sh) + ((unsigned)(e1 * e1) >> sh);
     }
+  }
+  if (fine) {
+    const int lt = 2 - wave;                 // log2 of the depth-1 TU's side in tiles: 16 of 2 x 2 tiles at level 1, 64 of one tile at level 2
+    for (int k = 0; k < lt; ++k) {
+      sum += __shfl_xor(sum, 1 << k);
+      sum += __shfl_xor(sum, 8 << k);
+    }
+    unsigned* const words = reinterpret_cast<unsigned*>(s + kTransformShorts + kFwdShorts + kInvShorts);
+    int ln = lane;   // opaque: where the sum goes is worked out here, not kept through the CTU loop
+    asm volatile("" : "+v"(ln));
+    const int ux = ln & 7, uy = ln >> 3;
+    const int m = (1 << lt) - 1, e = (wave == 1 ? 0 : 16) + (uy >> lt) * (8 >> lt) + (ux >> lt);
+    if ((ux & m) == 0 && (uy & m) == 0) words[kFineWords * e + 2 * DEPTH - 2] = sum;
+    __syncthreads();
+    return;
   }
   const int lt = wave <= 1 ? 2 : 3 - wave;   // log2 of the depth-0 TU's side in tiles
   for (int k = 0; k < lt; ++k) {
@@ -335,17 +391,25 @@ __device__ __forceinline__ RdPuLane rd_pu_lane(const RdPuArgs& A, long long oc, 
   return L;
 }
 
+struct RdThreeDepths {};   // a tag in the kernel's argument pack: it carries nothing
+// where the tag stands in front of the PU arguments, the comma fold that picks the pack's last argument drops it: that is what it is for
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wunused-value"
+
 // T = int16_t or uint8_t planes; MR = 8 or 64: the largest max_range the window is laid out for
 // PU (fhevc_motion_rd_pu_device): the prediction is composed from the two parts of a partition size; A...: ONE RdPuArgs then, empty otherwise -- a pack keeps
 // the plain instances' argument list, and so their code, what it was.  in / mvp are the nodes' own records there (source 1)
+// Three TU depths (fhevc_motion_rd_qt* at tu_depths 3): RdThreeDepths IN FRONT of the pack -- the 32x32 and 16x16 nodes get their third TU size, with sums per
+// depth-1 TU behind the matrices.  Without it the instances are the ones there always were, by name and by code
 template <typename T, int MR, bool PU, class... A>
 __global__ __launch_bounds__(256) void fhevc_motion_rd_kernel(FhevcFrames F, int max_range, FhevcRdQuant Q, int source, const unsigned* __restrict__ in,
                                                               const unsigned* __restrict__ mvp, FhevcMotionRdNode* __restrict__ out, A... pu_args)
 {
-  static_assert(sizeof...(A) == (PU ? 1 : 0), "the PU arguments go with the PU instances");
+  constexpr bool QT = (std::is_same_v<A, RdThreeDepths> || ...);
+  static_assert(sizeof...(A) == (PU ? 1 : 0) + (QT ? 1 : 0), "the PU arguments go with the PU instances, the tag with those of three TU depths");
   constexpr int RP = RefineGeom<MR>::RP;
   constexpr bool BIG = MR > FHEVC_MOTION_MAX_RANGE;
-  constexpr int OVER = kTransformShorts + kFwdShorts + kInvShorts;                          // what lies over the dead window: 41 632 B
+  constexpr int OVER = kTransformShorts + kFwdShorts + kInvShorts + (QT ? kFineShorts : 0);   // what lies over the dead window: 41 632 B (QT: 42 912 B)
   constexpr int SMALL = RefineGeom<MR>::SAMPLES > OVER ? RefineGeom<MR>::SAMPLES : OVER;   // the larger of the two uses
   static_assert(!BIG || RefineGeom<MR>::SAMPLES >= OVER, "the dynamic window holds the transform buffers and the matrices");
   static_assert(sizeof(RdTables) == (kFwdShorts + kInvShorts) * 2 && sizeof(RdTables) / 4 <= 5 * 256, "the tables: five dwords per thread at most");
@@ -387,7 +451,7 @@ __global__ __launch_bounds__(256) void fhevc_motion_rd_kernel(FhevcFrames F, int
     } else side = (unsigned)(eg_bits(vx) + eg_bits(vy));
     RdPuLane L;
     if constexpr (PU) {
-      const RdPuArgs pa = (pu_args, ...);
+      const RdPuArgs pa = (pu_args, ...);   // the pack's last argument
       // the lane number and the level made opaque once per CTU: what the part addresses derive from it is then computed here, inside the loop.  Hoisted out of it, those
       // values lived through the whole loop in nine registers more than the 256 there are.  (One is still missing: DESIGN 4.12)
       int ln = lane, wv = wave;   // the level as the scalar it is
@@ -445,9 +509,13 @@ __global__ __launch_bounds__(256) void fhevc_motion_rd_kernel(FhevcFrames F, int
       unsigned* mdst = reinterpret_cast<unsigned*>(s_ref + kTransformShorts);
       const unsigned* msrc = reinterpret_cast<const unsigned*>(&kRdTables);
       for (int i = tid; i < (kFwdShorts + kInvShorts) / 2; i += 256) mdst[i] = msrc[i];
+      // the sums per depth-1 TU lie behind the matrices, in what was window: zeroed here, not with s_acc during staging
+      if constexpr (QT)
+        for (int i = tid; i < kFineTus * kFineWords; i += 256) mdst[(kFwdShorts + kInvShorts) / 2 + i] = 0u;
     }
-    rd_depth<0>(s_ref, lane, lvl, wave, tx, ty, Q, s_acc, plane, W.cur_base, F, px, py, inside, D);
-    rd_depth<1>(s_ref, lane, lvl, wave, tx, ty, Q, s_acc, plane, W.cur_base, F, px, py, inside, D);
+    rd_depth<0, T, QT>(s_ref, lane, lvl, wave, tx, ty, Q, s_acc, plane, W.cur_base, F, px, py, inside, D);
+    rd_depth<1, T, QT>(s_ref, lane, lvl, wave, tx, ty, Q, s_acc, plane, W.cur_base, F, px, py, inside, D);
+    if constexpr (QT) rd_depth<2, T, QT>(s_ref, lane, lvl, wave, tx, ty, Q, s_acc, plane, W.cur_base, F, px, py, inside, D);
     if (N.writer) {
       FhevcMotionRdNode o;
       o.dist = o.cost_rd = kRdMark; o.bits = 0xFFFFu; o.flags = 0; o.tu_split = 0; o.mvx = o.mvy = 0;
@@ -456,6 +524,35 @@ __global__ __launch_bounds__(256) void fhevc_motion_rd_kernel(FhevcFrames F, int
         const int tu0 = lvl == 0 ? 0 : (lvl == 1 ? 4 : lvl == 2 ? 8 : 24) + (nidx - N.first), ntu = lvl == 0 ? 4 : 1;   // a 64x64 node: four TUs
         unsigned long long j = (unsigned long long)Q.lam_q8 * side, bits = side;
         unsigned dist = 0, top = 0, any0 = 0, split = 0;
+        if (QT && (lvl == 1 || lvl == 2)) {
+          // HM's recursion over three depths (TEncSearch.cpp:5020-5134), bottom-up: per depth-1 TU its own cost with its split flag against its four
+          // children, then the depth-0 TU against the four results.  A split depth-1 TU counts as coded one level up (:5093-5101)
+          const unsigned lam = Q.lam_q8;
+          const unsigned* const fine = reinterpret_cast<const unsigned*>(s_ref + kTransformShorts + kFwdShorts + kInvShorts);
+          const unsigned* a = &s_acc[kAccWords * tu0];
+          // the lane number and the level made opaque, here and where the sums are committed and stored: what the depth-1 TU's place derives from them is then
+          // computed on the spot.  Hoisted out of the CTU loop those values cost the plain instances their second wave per SIMD
+          int ln = lane, wv = wave;
+          asm volatile("" : "+v"(ln), "+s"(wv));
+          const RefineNode M(wv, ln & 7, ln >> 3);
+          const int e0 = wv == 1 ? (2 * M.nby) * 4 + 2 * M.nbx : 16 + (2 * M.nby) * 8 + 2 * M.nbx, row = wv == 1 ? 4 : 8;   // the node's first depth-1 TU
+          const unsigned d0 = a[0], r0 = 1u + a[1];
+          const unsigned long long j0 = 256ull * d0 + (unsigned long long)lam * (1u + r0);
+          unsigned long long j1 = lam;
+          unsigned dsub = 0, rsub = 0, s1 = 0;
+          bool coded = false;
+          for (int i = 0; i < 4; ++i) {
+            const unsigned* b = &fine[kFineWords * (e0 + (i >> 1) * row + (i & 1))];
+            const unsigned d1 = b[0], r1 = 1u + b[1], d2 = b[2], r2 = 4u + b[3];
+            const unsigned long long k1 = 256ull * d1 + (unsigned long long)lam * (1u + r1), k2 = 256ull * d2 + (unsigned long long)lam * (1u + r2);
+            const bool take1 = b[3] != 0u && k2 < k1;
+            j1 += take1 ? k2 : k1; dsub += take1 ? d2 : d1; rsub += 1u + (take1 ? r2 : r1);
+            s1 |= take1 ? 16u << i : 0u; coded = coded || take1 || b[1] != 0u;
+          }
+          const bool take = coded && j1 < j0;
+          j += take ? j1 : j0; dist = take ? dsub : d0; bits += 1u + (take ? rsub : r0);
+          split = take ? 1u | s1 : 0u; any0 = a[1]; top = a[4];
+        } else
         for (int i = 0; i < ntu; ++i) {
           const unsigned* a = &s_acc[kAccWords * (tu0 + i)];
           const unsigned d0 = a[0], r0 = 1u + a[1], d1 = a[2], r1 = 4u + a[3];
@@ -473,7 +570,7 @@ __global__ __launch_bounds__(256) void fhevc_motion_rd_kernel(FhevcFrames F, int
         o.mvx = (short)vx; o.mvy = (short)vy;
       }
       if constexpr (PU) {
-        const RdPuArgs pa = (pu_args, ...);
+        const RdPuArgs pa = (pu_args, ...);   // the pack's last argument
         FhevcMotionRdPuNode u;
         u.dist = o.dist; u.cost_rd = o.cost_rd; u.bits = o.bits; u.flags = o.flags; u.tu_split = o.tu_split;
         u.part = (uint8_t)(valid ? L.p() : 255u); u.merged = (uint8_t)(valid ? L.merged() : 0u); u.pad[0] = u.pad[1] = 0;
@@ -781,15 +878,21 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
 
 }  // namespace
 
+// the instances of three TU depths are launched -- and so instantiated -- at the end of this file, behind every instance there was: the ten keep their code AND
+// their order in the code object
+static hipError_t rd_launch_three_depths(const FhevcFrames& fr, int max_range, const FhevcRdQuant& q, int source, const unsigned* in, const unsigned* mvp, FhevcMotionRdNode* d_out,
+                                         const RdPuArgs* pa, int num_cus, hipStream_t stream);
+
 // what the device keeps resident is the occupancy query's answer in both layouts: two workgroups per CU by the registers (256 VGPRs), which is also what the
 // LDS allows at MR = 64 (1 824 B static + 80 016 B dynamic); the caps are the skip stage's
 hipError_t fhevc_launch_motion_rd(const FhevcFrames& fr, int max_range, const FhevcRdQuant& q, int source, const void* d_in, const FhevcMotionMvp* d_mvp,
-                                  FhevcMotionRdNode* d_out, int num_cus, hipStream_t stream)
+                                  FhevcMotionRdNode* d_out, int num_cus, hipStream_t stream, int tu_depths)
 {
   static_assert(sizeof(FhevcMotionMergeNode) == 16 && sizeof(FhevcMotionQpelNode) == 16 && sizeof(FhevcMotionMvp) == 8 && sizeof(FhevcMotionRdNode) == 16, "record layouts");
   const unsigned* in = reinterpret_cast<const unsigned*>(d_in);
   const unsigned* mvp = reinterpret_cast<const unsigned*>(d_mvp);
-  return refine_launch<FHEVC_MOTION_WIDE_MAX_RANGE>(fr, source == 0 || source == 1, max_range, num_cus, {4, true}, {2, true}, stream, [&](auto t, auto, auto mr, const RefineLaunch& L) {
+  if (tu_depths == 3) return rd_launch_three_depths(fr, max_range, q, source, in, mvp, d_out, nullptr, num_cus, stream);
+  return refine_launch<FHEVC_MOTION_WIDE_MAX_RANGE>(fr, (source == 0 || source == 1) && tu_depths == 2, max_range, num_cus, {4, true}, {2, true}, stream, [&](auto t, auto, auto mr, const RefineLaunch& L) {
     return refine_launch_kernel<&fhevc_motion_rd_kernel<decltype(t), decltype(mr)::value, false>>(L, fr, max_range, q, source, in, mvp, d_out);
   });
 }
@@ -797,12 +900,14 @@ hipError_t fhevc_launch_motion_rd(const FhevcFrames& fr, int max_range, const Fh
 // the PU instances: ONE workgroup per CU by their registers (256 VGPRs + 1 AGPR: the resource table in DESIGN 4.12), which the occupancy query
 // answers; the caps stay.  Every record array as dwords
 hipError_t fhevc_launch_motion_rd_pu(const FhevcFrames& fr, int max_range, const FhevcRdQuant& q, int part_mode, const FhevcMotionRdPuInputs& I, FhevcMotionRdPuNode* d_out,
-                                     int num_cus, hipStream_t stream)
+                                     int num_cus, hipStream_t stream, int tu_depths)
 {
   static_assert(sizeof(FhevcMotionRdPuNode) == 16 && sizeof(FhevcPuShapeNode) == 16, "record layouts");
   const auto dw = [](const void* p) { return reinterpret_cast<const unsigned*>(p); };
   const RdPuArgs pa = { dw(I.pus), dw(I.pus_small), dw(I.merge_pus), dw(I.merge_pus_small), dw(I.mvp_pus), dw(I.mvp_pus_small), dw(I.shapes), dw(I.fold), part_mode };
-  const bool mode_ok = part_mode >= 0 && part_mode <= 9 && part_mode != 3 && (part_mode == 0 || I.pus) && (part_mode < 8 || I.shapes);
+  const bool mode_ok = part_mode >= 0 && part_mode <= 9 && part_mode != 3 && (part_mode == 0 || I.pus) && (part_mode < 8 || I.shapes) && (tu_depths == 2 || tu_depths == 3);
+  if (tu_depths == 3 && I.nodes && d_out && mode_ok)
+    return rd_launch_three_depths(fr, max_range, q, 1, dw(I.nodes), dw(I.mvp_nodes), reinterpret_cast<FhevcMotionRdNode*>(d_out), &pa, num_cus, stream);
   return refine_launch<FHEVC_MOTION_WIDE_MAX_RANGE>(fr, I.nodes && d_out && mode_ok, max_range, num_cus, {4, true}, {2, true}, stream, [&](auto t, auto, auto mr, const RefineLaunch& L) {
     return refine_launch_kernel<&fhevc_motion_rd_kernel<decltype(t), decltype(mr)::value, true, RdPuArgs>>(L, fr, max_range, q, 1, dw(I.nodes), dw(I.mvp_nodes),
                                                                                                          reinterpret_cast<FhevcMotionRdNode*>(d_out), pa);
@@ -822,3 +927,30 @@ hipError_t fhevc_launch_intra_rd(const FhevcFrames& fr, const FhevcRdQuant& q, c
   if (fr.sample_bytes == 2) return refine_launch_kernel<&fhevc_intra_rd_kernel<int16_t>>(L, fr, q, dw(d_first), dw(d_fold), dw(d_rd_merge), skip_mask, d_out);
   return refine_launch_kernel<&fhevc_intra_rd_kernel<uint8_t>>(L, fr, q, dw(d_first), dw(d_fold), dw(d_rd_merge), skip_mask, d_out);
 }
+
+// ---- the instances of three TU depths (fhevc_motion_rd_qt*, fhevc_motion_rd_pu_qt* at tu_depths 3): the plain ones where pa is null ----
+static hipError_t rd_launch_three_depths(const FhevcFrames& fr, int max_range, const FhevcRdQuant& q, int source, const unsigned* in, const unsigned* mvp, FhevcMotionRdNode* d_out,
+                                         const RdPuArgs* pa, int num_cus, hipStream_t stream)
+{
+  return refine_launch<FHEVC_MOTION_WIDE_MAX_RANGE>(fr, source == 0 || source == 1, max_range, num_cus, {4, true}, {2, true}, stream, [&](auto t, auto, auto mr, const RefineLaunch& L) {
+    if (pa)
+      return refine_launch_kernel<&fhevc_motion_rd_kernel<decltype(t), decltype(mr)::value, true, RdThreeDepths, RdPuArgs>>(L, fr, max_range, q, source, in, mvp, d_out, RdThreeDepths{}, *pa);
+    return refine_launch_kernel<&fhevc_motion_rd_kernel<decltype(t), decltype(mr)::value, false, RdThreeDepths>>(L, fr, max_range, q, source, in, mvp, d_out, RdThreeDepths{});
+  });
+}
+
+// workgroups of an MR = 64 instance that the device keeps on one CU (measurement tools): planes of sample_bytes, plain or PU, two or three TU depths
+hipError_t fhevc_motion_rd_big_residency(int sample_bytes, bool pu, int tu_depths, int* per_cu)
+{
+  constexpr int MRB = FHEVC_MOTION_WIDE_MAX_RANGE;
+  constexpr size_t LDS = (size_t)RefineGeom<MRB>::SAMPLES * sizeof(short);  // 80 016 B
+  const auto pick = [&](auto t) -> hipError_t {
+    using T = decltype(t);
+    if (tu_depths == 3) return pu ? refine_resident<&fhevc_motion_rd_kernel<T, MRB, true, RdThreeDepths, RdPuArgs>>(LDS, per_cu)
+                                  : refine_resident<&fhevc_motion_rd_kernel<T, MRB, false, RdThreeDepths>>(LDS, per_cu);
+    return pu ? refine_resident<&fhevc_motion_rd_kernel<T, MRB, true, RdPuArgs>>(LDS, per_cu) : refine_resident<&fhevc_motion_rd_kernel<T, MRB, false>>(LDS, per_cu);
+  };
+  return sample_bytes == 2 ? pick(int16_t()) : pick(uint8_t());
+}
+
+#pragma clang diagnostic pop

@@ -1252,6 +1252,61 @@ int  fhevc_p_tree_rd_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_
                            const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, int skip_mask, uint8_t* depth_min, uint8_t* depth_max,
                            fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge, fhevc_motion_rd_node* rd_merge, fhevc_motion_rd_pu_node* rd_pu);
 
+/* ---- config 4 (P slices): the RD estimates with HM's full residual quad-tree: the third TU depth (further instances of k_motion_rd.hip) -----------
+ * fhevc_motion_rd* and fhevc_motion_rd_pu* price two TU sizes per node.  That is HM's complete residual quad-tree for 64x64 and 8x8 CUs and one depth
+ * short for 32x32 and 16x16 CUs: a 32x32 node can use TUs of 32 and 16 while its four 16x16 children can use 16 and 8, so wherever the smallest transform
+ * pays, the RD tree books that gain as a gain of the CU split.  HM sees the same TU sizes on both sides (xEstimateInterResidualQT,
+ * TEncSearch.cpp:4556-5160).  The entry points below take the depth count as an argument, tu_depths, placed before the output pointer.
+ *   tu_depths 2: every byte is what the entry point without _qt writes; the launch IS that entry point's launch (the same kernel instances, the same timing
+ * slot 29 or 31).
+ *   tu_depths 3: nodes of 64x64 and 8x8 are priced exactly as before -- their bytes equal the tu_depths 2 bytes.  A node of side s = 32 or 16 gets N0 = s,
+ * N1 = s / 2, N2 = s / 4: 32 -> 32, 16, 8 and 16 -> 16, 8, 4.  Per TU of any size, step 3 of fhevc_motion_rd applies word for word, on the same residual:
+ * it yields D, r = 1 + sum (3 + 2 floor(log2 |level|)) and cbf (some level non-zero).  Inter 4x4 takes the DCT.
+ *   The choice is HM's recursion (TEncSearch.cpp:5020-5134), bottom-up, in 64 bits, with lam = lam_q8.
+ *   Per depth-1 TU i, in raster order inside the node (i = 2 * (row half) + (column half)):
+ *     K1_i = 256 D1_i + lam (1 + r1_i) -- the 1 is this TU's own split flag, which exists now that it can split;
+ *     K2_i = 256 sum D2 + lam (1 + sum r2) over its four children;
+ *     take1_i = (some child has a non-zero level) AND K2_i < K1_i, strictly;
+ *     C_i = take1_i ? K2_i : K1_i;
+ *     coded_i = take1_i OR cbf1_i -- HM's uiCbfAny one level up: HM ORs the cbf of a split child into the parent's depth (:5093-5101), so a depth-0 TU
+ *   whose only coded descendants sit at depth 2 counts as coded.
+ *   Per depth-0 TU: J0 = 256 D0 + lam (1 + r0), unchanged; J1 = sum C_i + lam; take0 = (some coded_i) AND J1 < J0, strictly.
+ *   Per node: cost_rd = min((chosen J + lam * side_bits) >> 8, 0xFFFFFFFE); dist is D summed over the chosen TUs; bits is everything lam multiplies in the
+ * chosen J, + side_bits, saturated at 65535.
+ *   With no third depth K1_i carries no flag and never splits: that is J1 of fhevc_motion_rd.  So tu_depths 2 is the special case of this definition, not a
+ * second one.  A node that splits at depth 0 and nowhere at depth 1 therefore costs four flag bits MORE at tu_depths 3 than at 2.
+ *   Record types are unchanged (fhevc_motion_rd_node, fhevc_motion_rd_pu_node: 16 bytes, dword 1 and byte 10 where the tree reads them).  flags keeps its
+ * meaning: bits 0 and 1 are depth-0 properties, bit 2 means depth 0 split.  tu_split gains bits 4..7: bit 4 + i is set when depth-1 TU i of a 32x32 or
+ * 16x16 node is split; these bits are zero unless bit 0 is set.  Bits 1..3 stay the 64x64 node's.  The existing tree kernels and forwarders
+ * (fhevc_p_tree_select_rd*, fhevc_p_tree_select_rd_pu*) read these records as they are; there is no new tree kernel.
+ *   Everything else -- inputs, validity, side bits, the composed prediction, the fold (which works across launches of either depth count, in place where
+ * wanted), planes, band, stream, asynchrony -- is the mirrored entry point's.  FHEVC_E_INVALID with a fhevc_last_error text (nothing is launched or
+ * written): what the mirrored call rejects, and tu_depths outside {2, 3}.  No per-context or HBM state: calls with different tu_depths, QPs and ranges
+ * may be in flight on two streams.  Timed under slot 35 of fhevc_kernel_timing at tu_depths 3 (34 stays rejected); at tu_depths 2 under the mirrored
+ * call's slot.
+ *   The kernel: eight further instances of the RD kernel.  A third pass group runs over the level-1 buffer at N = 8 and the level-2 buffer at N = 4 alone,
+ * by all 256 threads; the sums are kept per depth-1 TU (16 + 64 of them, four words each) in the dead window behind the matrices, and the writer lane makes
+ * the nested choice.  By a count of the code about a quarter more transform work than two depths (an expectation, not a measurement).
+ * NOT covered: the third depth of the intra candidate (fhevc_intra_rd* stays two depths deep; it takes records folded at either depth count as d_fold
+ * unchanged), RDOQ, a fitted bit model, HM's per-TU zero-cost comparison, chroma.  The encoder hook does not consume this output. */
+int  fhevc_motion_rd_qt_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames,
+                               int ctu_row_begin, int ctu_row_end, int qp, int max_range, int source, const void* d_in, const fhevc_motion_mvp* d_mvp /* or NULL */,
+                               int tu_depths, fhevc_motion_rd_node* d_out, void* stream);
+int  fhevc_motion_rd_qt(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range, int source, const void* in,
+                        const fhevc_motion_mvp* mvp /* or NULL */, int tu_depths, fhevc_motion_rd_node* out);
+int  fhevc_motion_rd_pu_qt_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames,
+                                  int ctu_row_begin, int ctu_row_end, int qp, int max_range, int part_mode, const fhevc_motion_rd_pu_inputs* inputs,
+                                  int tu_depths, fhevc_motion_rd_pu_node* d_out, void* stream);
+int  fhevc_motion_rd_pu_qt(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int max_range, int part_mode,
+                           const fhevc_motion_rd_pu_inputs* inputs, int tu_depths, fhevc_motion_rd_pu_node* out);
+/* fhevc_p_tree_rd_frame's chain with all four RD launches (the merge records, part_mode 0 / 8 / 9 folded) at tu_depths: the two sides of every comparison of
+ * the RD tree then stand on one footing.  At tu_depths 2 every byte is fhevc_p_tree_rd_frame's.  Rejects what that call rejects, and tu_depths outside
+ * {2, 3}. */
+int  fhevc_p_tree_rd_qt_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                              const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, int skip_mask, int tu_depths, uint8_t* depth_min,
+                              uint8_t* depth_max, fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge, fhevc_motion_rd_node* rd_merge,
+                              fhevc_motion_rd_pu_node* rd_pu);
+
 /* ---- config 4 (P slices): the RD estimate of the intra candidate per CU node, folded per CU (the intra instances of k_motion_rd.hip) --------------
  * The tree that takes the intra candidate (fhevc_p_tree_select_intra*, further below) compares Hadamard costs; the RD tree above compares SSE + lambda
  * bits and has no intra candidate, so a node whose content is not in the reference picture can only split there.  This stage prices ONE intra mode per
@@ -1409,6 +1464,8 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
  * -- except 29 = the RD estimate (fhevc_motion_rd*).  28 is not a slot: it stays rejected, as does any number above 29.
  * -- except 31 = the RD estimate under a partition size (fhevc_motion_rd_pu*).  30 is not a slot: it stays rejected, as does any number above 31.
  * -- except 33 = the RD estimate of the intra candidate (fhevc_intra_rd*).  32 is not a slot: it stays rejected, as does any number above 33.
+ * -- except 35 = the RD estimates at three TU depths (fhevc_motion_rd_qt*, fhevc_motion_rd_pu_qt* with tu_depths 3).  34 is not a slot: it stays rejected,
+ * as does any number above 35.
  * The tree that stops at a skip (fhevc_p_tree_select_skip_device), the tree that takes the intra candidate (fhevc_p_tree_select_intra_device) and the tree
  * on RD costs (fhevc_p_tree_select_rd_device) are timed under 17 */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
