@@ -50,6 +50,7 @@ SYMBOLS = [
     "fhevc_motion_rd_pu", "fhevc_motion_rd_pu_device", "fhevc_p_tree_select_rd_pu", "fhevc_p_tree_select_rd_pu_device", "fhevc_p_tree_rd_frame",
     "fhevc_intra_rd", "fhevc_intra_rd_device", "fhevc_p_tree_rd_intra_frame",
     "fhevc_motion_rd_qt", "fhevc_motion_rd_qt_device", "fhevc_motion_rd_pu_qt", "fhevc_motion_rd_pu_qt_device", "fhevc_p_tree_rd_qt_frame",
+    "fhevc_intra_rd_qt", "fhevc_intra_rd_qt_device", "fhevc_p_tree_rd_intra_qt_frame",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -313,6 +314,11 @@ def load_library(path=None):
     lib.fhevc_intra_rd.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]
     lib.fhevc_intra_rd_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp]
     lib.fhevc_p_tree_rd_intra_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    if path is None or hasattr(lib, "fhevc_intra_rd_qt"):   # another build (A/B against the parent commit) may predate the intra entry points with tu_depths
+        lib.fhevc_intra_rd_qt.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp]
+        lib.fhevc_intra_rd_qt_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp]
+        lib.fhevc_p_tree_rd_intra_qt_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), C.c_int, C.c_int, vp, vp, vp,
+                                                       vp, vp, vp, vp]
     lib.fhevc_p_tree_intra_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), C.c_int, vp, vp, vp, vp, vp]
     lib.fhevc_predict_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, vp, vp]
     lib.fhevc_alloc_host.argtypes = [vp, C.c_size_t]
@@ -949,6 +955,11 @@ class Context:
         """config 4: the RD estimate of the intra candidate of every CU node of one picture -- first [numCtus, 85] NODE_DTYPE (the first pass's records: the
         mode priced), fold: MOTION_RD_PU_DTYPE records to fold into or None, rd_merge: MOTION_RD_DTYPE records for the calm gate under skip_mask or None
         -> [numCtus, 85] MOTION_RD_PU_DTYPE (part RD_PART_INTRA, the mode in pad[0], where the intra candidate was written)"""
+        return self.intra_rd_qt(plane, first, None, fold, rd_merge, skip_mask, origin, stride, qp)
+
+    def intra_rd_qt(self, plane, first, tu_depths=3, fold=None, rd_merge=None, skip_mask=0, origin=0, stride=None, qp=32):
+        """intra_rd with the number of TU depths: 2 -- intra_rd's bytes; 3 -- HM's full intra TU tree: 32x32 nodes get 8x8 TUs, 16x16 and 8x8 nodes 4x4 TUs
+        on the DST, tu_split bits 4..7 say which depth-1 TU split (None: the entry point without the argument)"""
         flat = np.ascontiguousarray(plane).reshape(-1)
         assert flat.dtype == np.int16
         stride = stride if stride is not None else plane.shape[-1]
@@ -959,8 +970,8 @@ class Context:
                 assert a.dtype.itemsize == 16 and a.size == self.num_ctus * NODES_PER_CTU
             arrays.append(a)
         out = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_RD_PU_DTYPE)
-        self._check(self.lib.fhevc_intra_rd(self.h, flat.ctypes.data + 2 * origin, stride, qp, *[a.ctypes.data if a is not None else None for a in arrays], skip_mask,
-                                            out.ctypes.data))
+        head = (self.h, flat.ctypes.data + 2 * origin, stride, qp, *[a.ctypes.data if a is not None else None for a in arrays], skip_mask)
+        self._check(self.lib.fhevc_intra_rd(*head, out.ctypes.data) if tu_depths is None else self.lib.fhevc_intra_rd_qt(*head, tu_depths, out.ctypes.data))
         return out.reshape(self.num_ctus, NODES_PER_CTU)
 
     def intra_rd_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_first, d_out, d_fold=None, d_rd_merge=None, skip_mask=0, rows=None, stream=None,
@@ -970,6 +981,13 @@ class Context:
         rb, re = rows if rows is not None else (0, self.ctus_y)
         self._check(self.lib.fhevc_intra_rd_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, d_first, d_fold, d_rd_merge, skip_mask,
                                                    d_out, stream))
+
+    def intra_rd_qt_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_first, tu_depths, d_out, d_fold=None, d_rd_merge=None, skip_mask=0, rows=None,
+                           stream=None, qp=32):
+        """intra_rd_device with the number of TU depths (2 or 3) in front of the output.  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_intra_rd_qt_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, d_first, d_fold, d_rd_merge, skip_mask,
+                                                      tu_depths, d_out, stream))
 
     def motion_merge_pu(self, cur_plane, ref_plane, refined, origin=0, stride=None, qp=32, max_range=4, with_pus=True, with_small=True):
         """config 4: the cheapest merge candidate of every PU from the refined square nodes [numCtus, 85] (MOTION_QPEL_DTYPE; only cost_best, mvx, mvy are
@@ -1296,13 +1314,21 @@ class Context:
                               with_shapes=False, with_merge=False, with_rd_merge=False, with_rd_pu=False, with_first=False):
         """p_tree_rd_frame with the intra candidate: behind the folded inter records the first pass of the current picture and intra_rd gated and folded in
         place, then the RD tree -> (depth_min, depth_max) [numCtus, 256], then the records asked for [numCtus, 85]: p_tree_rd_frame's four and NODE_DTYPE"""
+        return self.p_tree_rd_intra_qt_frame(cur_plane, ref_plane, None, origin, stride, qp, search_range, coarse_range, shape_rule, tree_rule, skip_mask, with_shapes,
+                                             with_merge, with_rd_merge, with_rd_pu, with_first)
+
+    def p_tree_rd_intra_qt_frame(self, cur_plane, ref_plane, tu_depths=3, origin=0, stride=None, qp=32, search_range=8, coarse_range=0, shape_rule=None, tree_rule=None,
+                                 skip_mask=3, with_shapes=False, with_merge=False, with_rd_merge=False, with_rd_pu=False, with_first=False):
+        """p_tree_rd_intra_frame with every RD launch, the intra stage included, at tu_depths TU depths (2: p_tree_rd_intra_frame's bytes; None: the entry point
+        without the argument)"""
         cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
         dmin, dmax = np.zeros(self.num_ctus * 256, np.uint8), np.zeros(self.num_ctus * 256, np.uint8)
         wanted = ((with_shapes, SHAPE_DTYPE), (with_merge, MOTION_MERGE_DTYPE), (with_rd_merge, MOTION_RD_DTYPE), (with_rd_pu, MOTION_RD_PU_DTYPE), (with_first, NODE_DTYPE))
         arrays = [np.zeros(self.num_ctus * NODES_PER_CTU, dt) if want else None for want, dt in wanted]
-        self._check(self.lib.fhevc_p_tree_rd_intra_frame(self.h, cur, ref, stride, qp, search_range, coarse_range, C.byref(shape_rule) if shape_rule is not None else None,
-                                                         C.byref(tree_rule) if tree_rule is not None else None, skip_mask, dmin.ctypes.data, dmax.ctypes.data,
-                                                         *[a.ctypes.data if a is not None else None for a in arrays]))
+        head = (self.h, cur, ref, stride, qp, search_range, coarse_range, C.byref(shape_rule) if shape_rule is not None else None,
+                C.byref(tree_rule) if tree_rule is not None else None, skip_mask)
+        tail = (dmin.ctypes.data, dmax.ctypes.data, *[a.ctypes.data if a is not None else None for a in arrays])
+        self._check(self.lib.fhevc_p_tree_rd_intra_frame(*head, *tail) if tu_depths is None else self.lib.fhevc_p_tree_rd_intra_qt_frame(*head, tu_depths, *tail))
         out = (dmin.reshape(self.num_ctus, 256), dmax.reshape(self.num_ctus, 256))
         for a in arrays:
             out += (a.reshape(self.num_ctus, NODES_PER_CTU),) if a is not None else ()

@@ -377,9 +377,11 @@ hipError_t fhevc_motion_rd_big_residency(int sample_bytes, bool pu, int tu_depth
 // lines; the record is a FhevcMotionRdPuNode with part kRdPartIntra and the mode in pad[0].  fr: num_frames pictures, no pairing; d_first: num_frames * band
 // CTUs * 85 first-pass records of which satd and the low byte of mode are read; d_fold (an earlier launch's records; d_fold == d_out is allowed) and
 // d_rd_merge (the merge records' RD records, for the calm gate under skip_mask 0..3) may be null
+// tu_depths: 2 -- the instances there always were; 3 -- the instances with HM's full intra TU tree: the third TU size of the 32x32 and 16x16 nodes, the
+// depth 1 of the 8x8 nodes, the DST of every 4x4 TU (tu_split bits 4..7)
 constexpr int kRdPartIntra = 16;   // FHEVC_RD_PART_INTRA
 hipError_t fhevc_launch_intra_rd(const FhevcFrames& fr, const FhevcRdQuant& q, const FhevcNodeCost* d_first, const FhevcMotionRdPuNode* d_fold,
-                                 const FhevcMotionRdNode* d_rd_merge, int skip_mask, FhevcMotionRdPuNode* d_out, int num_cus, hipStream_t stream);
+                                 const FhevcMotionRdNode* d_rd_merge, int skip_mask, FhevcMotionRdPuNode* d_out, int num_cus, hipStream_t stream, int tu_depths = 2);
 
 // ---- ... and of the PUs' vectors (k_motion_refine_pu.hip; config 4) --------------------------------------------------
 // fr, max_range (1 .. FHEVC_MOTION_WIDE_MAX_RANGE: up to FHEVC_MOTION_MAX_RANGE the MR = 8 layout, above it the MR = 64 layout with its window in dynamic LDS),

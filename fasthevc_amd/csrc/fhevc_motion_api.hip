@@ -145,7 +145,8 @@ int device_form(fhevc_ctx* c, bool args_ok, const char* bad_args, const Batch& b
 // The timing slots (fhevc_kernel_timing) of the launches below: 4 fhevc_motion_search, 5 the P rule, 7 fhevc_motion_refine, 8 / 9 the searches of the PUs / the
 // small PUs, 10 fhevc_motion_refine_pu, 11 / 12 the wide search / refinement, 13 the partition sizes, 15 the centres and everything centred, 17 the tree, 19 the merge stage,
 // 21 the merge stage per PU, 23 the zero-residual test, 25 the re-pricing against neighbour predictors, 27 the intra stage, 29 the RD estimate, 31 the RD estimate under a partition size,
-// 33 the RD estimate of the intra candidate, 35 the RD estimates at three TU depths (fhevc_motion_rd_qt*, fhevc_motion_rd_pu_qt* with tu_depths 3; at 2 they are
+// 33 the RD estimate of the intra candidate, 37 the RD estimate of the intra candidate at three TU depths (fhevc_intra_rd_qt* with tu_depths 3; at 2 it is slot 33's launch),
+// 35 the RD estimates at three TU depths (fhevc_motion_rd_qt*, fhevc_motion_rd_pu_qt* with tu_depths 3; at 2 they are
 // the launches of slots 29 and 31)
 struct Family { int per_ctu; FhevcMotionNode* fhevc_ctx::*found; FhevcMotionQpelNode* fhevc_ctx::*refined; };
 constexpr Family kNodes = { FHEVC_NODES, &fhevc_ctx::d_motion, &fhevc_ctx::d_qpel }, kPus = { FHEVC_PUS, &fhevc_ctx::d_motion_pu, &fhevc_ctx::d_qpel_pu },
@@ -677,11 +678,14 @@ int fhevc_motion_rd_pu(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref
 
 // ---- the RD estimate of the intra candidate per CU node, gated and folded (the intra instances of k_motion_rd.hip) ----
 
-int fhevc_intra_rd_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames,
-                          int ctu_row_begin, int ctu_row_end, int qp, const fhevc_node_cost* d_first, const fhevc_motion_rd_pu_node* d_fold,
-                          const fhevc_motion_rd_node* d_rd_merge, int skip_mask, fhevc_motion_rd_pu_node* d_out, void* stream)
+static bool intra_tu_depths_ok(int tu_depths) { return tu_depths == 2 || tu_depths == 3; }
+
+int fhevc_intra_rd_qt_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames,
+                             int ctu_row_begin, int ctu_row_end, int qp, const fhevc_node_cost* d_first, const fhevc_motion_rd_pu_node* d_fold,
+                             const fhevc_motion_rd_node* d_rd_merge, int skip_mask, int tu_depths, fhevc_motion_rd_pu_node* d_out, void* stream)
 {
   if (!c) return FHEVC_E_INVALID;
+  if (!intra_tu_depths_ok(tu_depths)) return fail(c, FHEVC_E_INVALID, kBadTuDepths);
   if (!d_luma || !d_first || !d_out) return fail(c, FHEVC_E_INVALID, "bad intra RD-stage arguments (the planes, the first-pass records, the output)");
   // pictures, not pairs: the layout is checked as fhevc_intra_first_pass_device checks it
   if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 1, ctu_row_begin, ctu_row_end, qp, false)) return fail(c, FHEVC_E_INVALID, bad);
@@ -695,16 +699,26 @@ int fhevc_intra_rd_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, in
   if (ctu_row_begin == ctu_row_end) return FHEVC_OK;   // an empty band: nothing to launch, nothing written
   // everything the kernel needs travels with the launch: nothing of the context is read or written by it
   const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
-  return launch_on(c, stream, 33, "fhevc_launch_intra_rd", [&](hipStream_t s) {
-    return fhevc_launch_intra_rd(fr, fhevc_rd_quant(qp, c->cfg.bit_depth), kn(d_first), kn(d_fold), kn(d_rd_merge), skip_mask, kn(d_out), c->num_cus, s);
+  return launch_on(c, stream, tu_depths == 3 ? 37 : 33, "fhevc_launch_intra_rd", [&](hipStream_t s) {
+    return fhevc_launch_intra_rd(fr, fhevc_rd_quant(qp, c->cfg.bit_depth), kn(d_first), kn(d_fold), kn(d_rd_merge), skip_mask, kn(d_out), c->num_cus, s, tu_depths);
   });
 }
 
-int fhevc_intra_rd(fhevc_ctx* c, const int16_t* luma, int stride_samples, int qp, const fhevc_node_cost* first, const fhevc_motion_rd_pu_node* fold,
-                   const fhevc_motion_rd_node* rd_merge, int skip_mask, fhevc_motion_rd_pu_node* out)
+// the entry point of two TU depths: the same launch of the same instances
+int fhevc_intra_rd_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames,
+                          int ctu_row_begin, int ctu_row_end, int qp, const fhevc_node_cost* d_first, const fhevc_motion_rd_pu_node* d_fold,
+                          const fhevc_motion_rd_node* d_rd_merge, int skip_mask, fhevc_motion_rd_pu_node* d_out, void* stream)
+{
+  return fhevc_intra_rd_qt_device(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp, d_first, d_fold, d_rd_merge, skip_mask,
+                                  2, d_out, stream);
+}
+
+int fhevc_intra_rd_qt(fhevc_ctx* c, const int16_t* luma, int stride_samples, int qp, const fhevc_node_cost* first, const fhevc_motion_rd_pu_node* fold,
+                      const fhevc_motion_rd_node* rd_merge, int skip_mask, int tu_depths, fhevc_motion_rd_pu_node* out)
 {
   const int rc = open_host_form(c, luma && first && out && skip_mask >= 0 && skip_mask <= 3, stride_samples, qp, 1, 1, "bad intra RD-stage arguments");
   if (rc != GO) return rc;
+  if (!intra_tu_depths_ok(tu_depths)) return fail(c, FHEVC_E_INVALID, kBadTuDepths);   // said before anything is staged
   HostForm h(c);
   const size_t bn = h.bytes(kNodes), b4 = (size_t)c->num_ctus * FHEVC_PUS4_PER_CTU * sizeof(fhevc_node_cost);
   const fhevc_node_cost* d_first = h.in(c->d_first_p, bn + b4, first, bn);
@@ -712,8 +726,14 @@ int fhevc_intra_rd(fhevc_ctx* c, const int16_t* luma, int stride_samples, int qp
   const fhevc_motion_rd_pu_node* d_fold = h.in(c->d_qpel_pu, h.bytes(kPus), fold, bn);   // folded in place on the device, as fhevc_motion_rd_pu does
   fhevc_motion_rd_pu_node* d_out = h.out(c->d_qpel_pu, h.bytes(kPus), out, bn);
   return h.run(luma, nullptr, stride_samples, [&] {   // the picture alone: the current plane of the staged pair, as a batch of one frame
-    return fhevc_intra_rd_device(c, c->d_pair + pair_plane(c), 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, d_first, d_fold, d_rd_merge, skip_mask, d_out, c->stream);
+    return fhevc_intra_rd_qt_device(c, c->d_pair + pair_plane(c), 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, d_first, d_fold, d_rd_merge, skip_mask, tu_depths, d_out, c->stream);
   });
+}
+
+int fhevc_intra_rd(fhevc_ctx* c, const int16_t* luma, int stride_samples, int qp, const fhevc_node_cost* first, const fhevc_motion_rd_pu_node* fold,
+                   const fhevc_motion_rd_node* rd_merge, int skip_mask, fhevc_motion_rd_pu_node* out)
+{
+  return fhevc_intra_rd_qt(c, luma, stride_samples, qp, first, fold, rd_merge, skip_mask, 2, out);
 }
 
 // ---- merge-candidate costs per PU from the refined nodes (k_motion_merge_pu.hip) ----
@@ -1239,7 +1259,7 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
         const int16_t* d_cur = c->d_pair + pair_plane(c);   // the current picture of the staged pair, as a batch of one frame
         rc = fhevc_intra_first_pass_device(c, d_cur, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, d_first_rd, c->stream);
         // intra last, as HM tries it after the inter sizes: the earlier record stays on a tie
-        if (rc == FHEVC_OK) rc = fhevc_intra_rd_device(c, d_cur, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, d_first_rd, d_rd_pu, d_rd_merge, skip_mask, d_rd_pu, c->stream);
+        if (rc == FHEVC_OK) rc = fhevc_intra_rd_qt_device(c, d_cur, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, d_first_rd, d_rd_pu, d_rd_merge, skip_mask, tud, d_rd_pu, c->stream);
       }
       return rc != FHEVC_OK ? rc : fhevc_p_tree_select_rd_pu_device(c, d_rd_pu, d_rd_merge, skip_mask, 1, 0, c->ctus_y, tree_rule, d_min, d_max, nullptr, c->stream);
     }
@@ -1314,6 +1334,16 @@ int fhevc_p_tree_rd_intra_frame(fhevc_ctx* c, const int16_t* cur_luma, const int
                                 fhevc_node_cost* first)
 {
   const RdFrameOut rd = { rd_merge, rd_pu, true, first };
+  return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge, true, true,
+                         false, skip_mask, nullptr, &rd);
+}
+
+int fhevc_p_tree_rd_intra_qt_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                                   const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, int skip_mask, int tu_depths, uint8_t* depth_min,
+                                   uint8_t* depth_max, fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge, fhevc_motion_rd_node* rd_merge,
+                                   fhevc_motion_rd_pu_node* rd_pu, fhevc_node_cost* first)
+{
+  const RdFrameOut rd = { rd_merge, rd_pu, true, first, tu_depths };
   return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge, true, true,
                          false, skip_mask, nullptr, &rd);
 }

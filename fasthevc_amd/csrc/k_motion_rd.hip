@@ -50,6 +50,7 @@ constexpr int kRowsInFlight = 2;                 // matrix rows the scheduler ma
 constexpr int kTus = 88, kAccWords = 5;          // per depth-0 TU: D0, bits0 - 1, sum D1, sum bits1 - 4, max |c| at depth 0
 constexpr int kFineTus = 16 + 64, kFineWords = 4;   // three TU depths: per depth-1 TU of levels 1 and 2: D1, bits1 - 1, sum D2, sum bits2 - 4
 constexpr int kFineShorts = kFineTus * kFineWords * 2;   // ... as shorts: 1 280 B behind the matrices
+constexpr int kDstAt = kFwdShorts + kInvShorts + kFineShorts, kDstShorts = 32;   // the intra instances of three TU depths: the DST-VII of the 4x4 luma TUs, [k][x] then [x][k], behind those sums
 enum { ROWS = 0, COLS = 1, INV1 = 2, INV2 = 3 };
 
 constexpr int ilog2(int n) { return n <= 1 ? 0 : 1 + ilog2(n >> 1); }
@@ -77,6 +78,22 @@ constexpr RdTables make_tables()
   return t;
 }
 __constant__ RdTables kRdTables = make_tables();
+
+// HM's DST-VII of the intra 4x4 luma TUs (g_as_DST_MAT_4, TComRom.cpp:513-517) in the same two forms: the matrix [k][x / 2] and its transpose [x][k / 2].
+// fastForwardDst / fastInverseDst (TComTrQuant.cpp:412-466) are plain products with it, in the index order of the 4-point DCT's passes
+struct DstTables { unsigned fwd[8], inv[8]; };
+constexpr int kDst[4][4] = { { 29, 55, 74, 84 }, { 74, 74, 0, -74 }, { 84, -29, -74, 55 }, { 55, -84, 74, -29 } };
+constexpr DstTables make_dst_tables()
+{
+  DstTables t{};
+  for (int a = 0; a < 4; ++a)
+    for (int j = 0; j < 2; ++j) {
+      t.fwd[a * 2 + j] = pack2(kDst[a][2 * j], kDst[a][2 * j + 1]);
+      t.inv[a * 2 + j] = pack2(kDst[2 * j][a], kDst[2 * j + 1][a]);
+    }
+  return t;
+}
+__constant__ DstTables kDstTables = make_dst_tables();
 
 // which units of an N-point pass over one buffer a thread has: UNITS segments of its row, NK outputs of each from k0 on -- 16 outputs in all
 template <int N> struct TuMap {
@@ -147,14 +164,16 @@ __device__ __forceinline__ void rd_commit(unsigned* acc, int tu, int lane, unsig
 
 // one pass over one buffer at TU size N: the thread's 16 outputs, packed two to a register until the barrier.  COLS quantises, prices and dequantises them
 // and commits the sums of every unit to its depth-0 TU: tu0 = the buffer's first, l0 = log2 of the buffer's depth-0 TU size (FINE: of its depth-1 TUs)
-template <int N, int STAGE, int DEPTH, bool FINE = false>
+// DST (the intra instances of three TU depths): a pass at N = 4 takes the DST matrix instead; the shifts and clips are the 4-point DCT's (xTrMxN, xITrMxN)
+template <int N, int STAGE, int DEPTH, bool FINE = false, bool DST = false>
 __device__ __forceinline__ void tu_pass(const short* tables, const short* buf, int lane, int wave, int bd, const FhevcRdQuant& Q, unsigned* acc, int tu0, int l0,
                                         unsigned (&t)[8])
 {
   using M = TuMap<N>;
   constexpr int LN = ilog2(N), QI = LN - 2;
-  const short* mat = STAGE <= COLS ? tables : tables + kFwdShorts + inv_at(N);
-  constexpr int pitch = STAGE <= COLS ? (32 / N) * 32 : N;
+  constexpr bool D4 = DST && N == 4;
+  const short* mat = D4 ? tables + kDstAt + (STAGE <= COLS ? 0 : 16) : STAGE <= COLS ? tables : tables + kFwdShorts + inv_at(N);
+  constexpr int pitch = D4 ? 4 : STAGE <= COLS ? (32 / N) * 32 : N;
   const int shift = STAGE == ROWS ? LN + bd - 9 : STAGE == COLS ? LN + 6 : STAGE == INV1 ? 7 : 20 - bd;
   const int k0 = M::k0(wave);
 #pragma unroll
@@ -219,7 +238,7 @@ __device__ __forceinline__ void tu_store(short* buf, int lane, int wave, const u
 // one pass over the four buffers: levels 0 and 1 at 32 >> DEPTH, level 2 at 16 >> DEPTH, level 3 at 8 >> DEPTH
 // QT (three TU depths): the sums of depths 1 and 2 of the level-1 and level-2 buffers go per depth-1 TU into the words behind the matrices; DEPTH 2 is a
 // pass over those two buffers alone, at 8 and 4, by all four waves
-template <int STAGE, int DEPTH, bool QT = false>
+template <int STAGE, int DEPTH, bool QT = false, bool DST = false>
 __device__ __forceinline__ void rd_stage(short* s, int lane, int wave, int bd, const FhevcRdQuant& Q, unsigned* acc)
 {
   static_assert(DEPTH < 2 || QT, "the third depth goes with QT");
@@ -229,7 +248,7 @@ __device__ __forceinline__ void rd_stage(short* s, int lane, int wave, int bd, c
     unsigned* const fine = reinterpret_cast<unsigned*>(s + kTransformShorts + kFwdShorts + kInvShorts);
     unsigned t1[8], t2[8];
     tu_pass<8, STAGE, 2, true>(tables, b1, lane, wave, bd, Q, fine, 0, 4, t1);
-    tu_pass<4, STAGE, 2, true>(tables, b2, lane, wave, bd, Q, fine, 16, 3, t2);
+    tu_pass<4, STAGE, 2, true, DST>(tables, b2, lane, wave, bd, Q, fine, 16, 3, t2);
     __syncthreads();   // every thread has read
     tu_store<8, STAGE>(b1, lane, wave, t1);
     tu_store<4, STAGE>(b2, lane, wave, t2);
@@ -246,7 +265,7 @@ __device__ __forceinline__ void rd_stage(short* s, int lane, int wave, int bd, c
       tu_pass<NA, STAGE, DEPTH>(tables, b1, lane, wave, bd, Q, acc, 4, 5, t1);
       tu_pass<NB, STAGE, DEPTH>(tables, b2, lane, wave, bd, Q, acc, 8, 4, t2);
     }
-    tu_pass<NC, STAGE, DEPTH>(tables, b3, lane, wave, bd, Q, acc, 24, 3, t3);
+    tu_pass<NC, STAGE, DEPTH, false, DST>(tables, b3, lane, wave, bd, Q, acc, 24, 3, t3);
     __syncthreads();   // every thread has read
     tu_store<NA, STAGE>(b0, lane, wave, t0);
     tu_store<NA, STAGE>(b1, lane, wave, t1);
@@ -261,7 +280,7 @@ __device__ __forceinline__ void rd_stage(short* s, int lane, int wave, int bd, c
 // The original tile is loaded a second time here (from the cache): kept in registers across the passes it cost the kernel its second wave per SIMD
 // QT (three TU depths): at depths 1 and 2 the level-1 and level-2 waves sum over the tiles of their depth-1 TU (2 x 2 tiles, the lane's own) and store per
 // depth-1 TU; at depth 2 only they rewrite their tiles and take the squared error -- the other two buffers have no third depth
-template <int DEPTH, typename T, bool QT = false>
+template <int DEPTH, typename T, bool QT = false, bool DST = false>
 __device__ __forceinline__ void rd_depth(short* s, int lane, int lvl, int wave, int tx, int ty, const FhevcRdQuant& Q, unsigned* acc, const T* plane, long long cur_base,
                                          const FhevcFrames& F, int px, int py, bool inside, const unsigned (&D)[32])
 {
@@ -273,10 +292,10 @@ __device__ __forceinline__ void rd_depth(short* s, int lane, int lvl, int wave, 
     for (int y = 0; y < 8; ++y) *reinterpret_cast<uint4*>(tile + y * kPitch) = make_uint4(D[4 * y], D[4 * y + 1], D[4 * y + 2], D[4 * y + 3]);
   }
   __syncthreads();
-  rd_stage<ROWS, DEPTH, QT>(s, lane, wave, bd, Q, acc);
-  rd_stage<COLS, DEPTH, QT>(s, lane, wave, bd, Q, acc);
-  rd_stage<INV1, DEPTH, QT>(s, lane, wave, bd, Q, acc);
-  rd_stage<INV2, DEPTH, QT>(s, lane, wave, bd, Q, acc);
+  rd_stage<ROWS, DEPTH, QT, DST>(s, lane, wave, bd, Q, acc);
+  rd_stage<COLS, DEPTH, QT, DST>(s, lane, wave, bd, Q, acc);
+  rd_stage<INV1, DEPTH, QT, DST>(s, lane, wave, bd, Q, acc);
+  rd_stage<INV2, DEPTH, QT, DST>(s, lane, wave, bd, Q, acc);
   if (DEPTH == 2 && !fine) { __syncthreads(); return; }
   const int top = (1 << bd) - 1, sh = 2 * (bd - 8);
   unsigned O[32];
@@ -601,6 +620,11 @@ namespace ird {
 constexpr int kLineTotal = 257 + 4 * 129 + 16 * 65 + 64 * 33;  // 3 925 samples: all 85 lines of 4 n + 1
 constexpr int kLinePad = 8;                                    // the unconditional second tap may touch one sample past a line
 constexpr int kUnits = 65 + 4 * 33 + 16 * 17 + 64 * 9;         // 1 045 four-sample units (n + 1 per node: the corner is a unit)
+// three TU depths: behind the matrices the sums per depth-1 TU and the DST (where rd_stage looks for them), then the unfiltered lines of the CTU's 256 4x4
+// blocks (17 samples each, the corner at 8; a 4x4 block never takes the smoothed line) and their DC values -- which also take the second tap's one sample
+// past the last line
+constexpr int kLine4 = 17, kLines4At = kTransformShorts + kDstAt + kDstShorts, kDc4At = kLines4At + 256 * kLine4;
+constexpr int kQtShorts = kFineShorts + kDstShorts + 256 * kLine4 + 256;   // 10 560 B
 __device__ __forceinline__ int line_off(int level) { return level == 0 ? 0 : (level == 1 ? 257 : (level == 2 ? 773 : 1813)); }
 __device__ __forceinline__ int node_off(int level) { return level == 0 ? 0 : (level == 1 ? 1 : (level == 2 ? 5 : 21)); }
 __device__ __forceinline__ int unit_off(int level) { return level == 0 ? 0 : (level == 1 ? 65 : (level == 2 ? 197 : 469)); }
@@ -620,35 +644,37 @@ __device__ __forceinline__ int main_ref(const short* ref, int sgn, int inv_angle
 }
 // the tile at (bx, by) of the n x n TU (n = 1 << lg <= 32) whose line has its corner at ref[0] (above at +i, left at -i), predicted at mode 0..34 with the
 // edge filters of n <= 16; tab: the angle and inverse-angle tables.  One sample at a time: the mode is this lane's own
+// W, OX, OY (three TU depths, n = 4): the W x W samples go to (OX, OY) of the lane's tile -- one of the four 4x4 TUs it holds, each from its own line
+template <int W = 8, int OX = 0, int OY = 0>
 __device__ __forceinline__ void predict_tile(const short* ref, const short* tab, int n, int lg, int bx, int by, int mode, int dc, int maxval, unsigned (&P)[32])
 {
   if (mode == 0) {
     const int topRight = ref[n + 1], bottomLeft = ref[-(n + 1)];
 #pragma unroll
-    for (int y = 0; y < 8; ++y) {
+    for (int y = 0; y < W; ++y) {
       const int left = ref[-(by + y + 1)];
 #pragma unroll
-      for (int x = 0; x < 8; ++x) {
+      for (int x = 0; x < W; ++x) {
         const int top = ref[bx + x + 1];
         const int hor = (left << lg) + n + (bx + x + 1) * (topRight - left);
         const int ver = (top << lg) + (by + y + 1) * (bottomLeft - top);
         const unsigned v = (unsigned)((hor + ver) >> (lg + 1)) & 0xFFFFu;
-        if (x & 1) P[4 * y + (x >> 1)] |= v << 16; else P[4 * y + (x >> 1)] = v;
+        if (x & 1) P[4 * (OY + y) + ((OX + x) >> 1)] |= v << 16; else P[4 * (OY + y) + ((OX + x) >> 1)] = v;
       }
     }
   } else if (mode == 1) {
     const bool edge = n <= 16;
 #pragma unroll
-    for (int y = 0; y < 8; ++y)
+    for (int y = 0; y < W; ++y)
 #pragma unroll
-      for (int x = 0; x < 8; ++x) {
+      for (int x = 0; x < W; ++x) {
         const int X = bx + x, Y = by + y;
         int v = dc;
         if (edge && Y == 0) v = (ref[X + 1] + 3 * dc + 2) >> 2;
         if (edge && X == 0) v = (ref[-(Y + 1)] + 3 * dc + 2) >> 2;
         if (edge && X == 0 && Y == 0) v = (ref[1] + ref[-1] + 2 * dc + 2) >> 2;
         const unsigned w = (unsigned)v & 0xFFFFu;
-        if (x & 1) P[4 * y + (x >> 1)] |= w << 16; else P[4 * y + (x >> 1)] = w;
+        if (x & 1) P[4 * (OY + y) + ((OX + x) >> 1)] |= w << 16; else P[4 * (OY + y) + ((OX + x) >> 1)] = w;
       }
   } else {
     const bool is_ver = mode >= 18;
@@ -660,9 +686,9 @@ __device__ __forceinline__ void predict_tile(const short* ref, const short* tab,
     const bool edge = angle == 0 && n <= 16;                 // the pure vertical / horizontal modes: the first column (row) leans on the side reference
     const int tl = ref[0];
 #pragma unroll
-    for (int y = 0; y < 8; ++y)
+    for (int y = 0; y < W; ++y)
 #pragma unroll
-      for (int x = 0; x < 8; ++x) {
+      for (int x = 0; x < W; ++x) {
         const int X = bx + x, Y = by + y;
         const int xx = is_ver ? X : Y, yy = is_ver ? Y : X;   // horizontal modes are the vertical ones of the transposed block
         const int delta = (yy + 1) * angle, di = delta >> 5, df = delta & 31;
@@ -670,7 +696,7 @@ __device__ __forceinline__ void predict_tile(const short* ref, const short* tab,
         int v = ((32 - df) * main_ref(ref, sgn, inv_angle, i) + df * main_ref(ref, sgn, inv_angle, i + 1) + 16) >> 5;
         if (edge && xx == 0) v = min(maxval, max(0, v + ((ref[-sgn * (yy + 1)] - tl) >> 1)));
         const unsigned w = (unsigned)v & 0xFFFFu;
-        if (x & 1) P[4 * y + (x >> 1)] |= w << 16; else P[4 * y + (x >> 1)] = w;
+        if (x & 1) P[4 * (OY + y) + ((OX + x) >> 1)] |= w << 16; else P[4 * (OY + y) + ((OX + x) >> 1)] = w;
       }
   }
 }
@@ -678,12 +704,17 @@ __device__ __forceinline__ void predict_tile(const short* ref, const short* tab,
 
 // T = int16_t or uint8_t planes.  first: the first pass's records as dwords (satd, mode, the cost's two); fold / rd_merge: RD records as dwords, or null;
 // fold may be out (the writer lane reads its record, then writes it)
-template <typename T>
+// Three TU depths (fhevc_intra_rd_qt* at tu_depths 3): RdThreeDepths as the pack -- the 32x32 and 16x16 nodes get their third TU size, the 8x8 nodes their
+// depth 1, every 4x4 TU the DST.  With the empty pack the instances are the ones there always were, by code
+template <typename T, class... A>
 __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, FhevcRdQuant Q, const unsigned* __restrict__ first, const unsigned* fold,
-                                                             const unsigned* __restrict__ rd_merge, int skip_mask, FhevcMotionRdPuNode* out)
+                                                             const unsigned* __restrict__ rd_merge, int skip_mask, FhevcMotionRdPuNode* out, A... tag)
 {
   using namespace ird;
-  __shared__ __attribute__((aligned(16))) short s_t[kTransformShorts + kFwdShorts + kInvShorts];   // the transform buffers (under them, first, the staged CTU) and the matrices
+  constexpr bool QT = (std::is_same_v<A, RdThreeDepths> || ...);
+  static_assert(sizeof...(A) == (QT ? 1 : 0), "the pack is the tag of three TU depths or empty");
+  // the transform buffers (under them, first, the staged CTU) and the matrices; QT: behind them the sums per depth-1 TU, the DST, the 4x4 lines and their DC values
+  __shared__ __attribute__((aligned(16))) short s_t[kTransformShorts + kFwdShorts + kInvShorts + (QT ? kQtShorts : 0)];
   __shared__ short s_refbuf[kLinePad + kLineTotal + kLinePad + 1];   // unfiltered lines: line[2 n] the corner, + i above, - j left
   __shared__ short s_fltbuf[kLinePad + kLineTotal + kLinePad + 1];   // smoothed lines
   __shared__ short s_above[132], s_left[64], s_tab[18];
@@ -714,6 +745,8 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
       for (int k = 0; k < 9; ++k) { a = tid == k ? ang[k] : a; b = tid == k ? inv[k] : b; }
       s_tab[tid] = (short)a; s_tab[9 + tid] = (short)b;
     }
+    if constexpr (QT)
+      if (tid < kDstShorts / 2) mdst[kDstAt / 2 + tid] = reinterpret_cast<const unsigned*>(&kDstTables)[tid];
   }
 
   for (int work = blockIdx.x; work < total; work += gridDim.x) {
@@ -736,7 +769,51 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
       s_valid[tid] = ((ox + (ni % cnt) * n + n <= F.width) && (oy + (ni / cnt) * n + n <= F.height)) ? 1 : 0;
     }
     for (int i = tid; i < kAccWords * kTus; i += 256) s_acc[i] = 0;
+    if constexpr (QT)
+      for (int i = tid; i < kFineTus * kFineWords; i += 256) reinterpret_cast<unsigned*>(s_t + kTransformShorts + kFwdShorts + kInvShorts)[i] = 0u;
     __syncthreads();
+    if constexpr (QT) {
+      // ---- one thread per 4x4 block of the CTU: its five units in HM's walk order (below left, left, the corner, above, above right) with z-order
+      // availability in 4-sample units, the substitution walk and the DC value -- what fhevc_intra_first_pass_4x4 evaluates for the block
+      const int x0 = ox + (tid & 15) * 4, y0 = oy + (tid >> 4) * 4;
+      if (x0 + 4 <= F.width && y0 + 4 <= F.height) {
+        short* line = s_t + kLines4At + tid * kLine4;
+        bool av[5];
+        int first_av = -1;
+#pragma unroll
+        for (int u = 4; u >= 0; --u) {
+          int ux, uy;
+          unit_pos(u, 4, x0, y0, ux, uy);
+          av[u] = fhevc_fp::unit_available(ux, uy, x0, y0, F.width, F.height, F.ctus_x);
+          if (av[u]) {
+            first_av = u;
+            if (u == 2) line[8] = fhevc_fp::staged(s_org, s_above, s_left, x0 - 1, y0 - 1, ox, oy);
+            else {
+#pragma unroll
+              for (int i = 0; i < 4; ++i)
+                line[u < 2 ? 4 * u + i : 4 * u - 3 + i] = u < 2 ? fhevc_fp::staged(s_org, s_above, s_left, x0 - 1, y0 + 7 - (4 * u + i), ox, oy)
+                                                                : fhevc_fp::staged(s_org, s_above, s_left, x0 + 4 * (u - 3) + i, y0 - 1, ox, oy);
+            }
+          }
+        }
+        if (first_av < 0) {
+#pragma unroll
+          for (int i = 0; i < kLine4; ++i) line[i] = (short)(1 << (bd - 1));
+        } else {
+          short prev = line[first_av <= 2 ? 4 * first_av : 4 * first_av - 3];
+#pragma unroll
+          for (int u = 0; u < 5; ++u) {
+            const int s = u <= 2 ? 4 * u : 4 * u - 3, c = u == 2 ? 1 : 4;
+            if (av[u]) prev = line[s + c - 1];
+            else for (int i = 0; i < c; ++i) line[s + i] = prev;
+          }
+        }
+        int sum = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sum += line[9 + i] + line[7 - i];
+        s_t[kDc4At + tid] = (short)((sum + 4) >> 3);
+      }
+    }
     // ---- one thread per 4-sample unit: availability in coding order and, where available, its samples ----
     for (int ug = 65 + tid; ug < kUnits; ug += 256) {   // from the first unit of level 1 on: a 64x64 block is no TU
       const int level = ug < 197 ? 1 : (ug < 469 ? 2 : 3);
@@ -820,8 +897,9 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
     __syncthreads();   // the lines stand; the staged CTU is dead: the transform buffers lie over it
     // ---- per TU depth: this lane's tile predicted at its node's mode from the line of the TU that holds it, the residual through the passes ----
 #pragma unroll 1
-    for (int depth = 0; depth < 2; ++depth) {
+    for (int depth = 0; depth < (QT ? 3 : 2); ++depth) {
       const int L = min(max(wave, 1) + depth, 3);        // the TU's level (wave 3 has no depth 1: its depth-0 TU again, dropped by the writer)
+      const bool four = QT && max(wave, 1) + depth == 4;  // three depths: the 4x4 TUs, four to a tile, each with its own line -- L is not used then
       const int n = 64 >> L, lg = 6 - L;
       const int ni = ((ty >> (3 - L)) << L) + (tx >> (3 - L));
       const int bx = (tx * 8) & (n - 1), by = (ty * 8) & (n - 1);
@@ -829,15 +907,28 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
       const bool use_flt = mode != 1 && min(abs(mode - 10), abs(mode - 26)) > thr;
       const short* ref = (use_flt ? s_flt : s_ref) + line_off(L) + ni * (4 * n + 1) + 2 * n;
       unsigned D[32];
+      if (QT && depth == 2 && wave != 1 && wave != 2) {
+        // the 64x64 and the 8x8 nodes have no third depth: rd_depth<2> keeps their waves at the barriers and reads no residual
+#pragma unroll
+        for (int i = 0; i < 32; ++i) D[i] = 0u;
+      } else if (four) {
+        const short* l4 = s_t + kLines4At + ((2 * ty) * 16 + 2 * tx) * kLine4 + 8;   // the tile's first 4x4 block: its line's corner
+        const short* d4 = s_t + kDc4At + (2 * ty) * 16 + 2 * tx;
+        predict_tile<4, 0, 0>(l4, s_tab, 4, 2, 0, 0, mode, d4[0], maxval, D);
+        predict_tile<4, 4, 0>(l4 + kLine4, s_tab, 4, 2, 0, 0, mode, d4[1], maxval, D);
+        predict_tile<4, 0, 4>(l4 + 16 * kLine4, s_tab, 4, 2, 0, 0, mode, d4[16], maxval, D);
+        predict_tile<4, 4, 4>(l4 + 17 * kLine4, s_tab, 4, 2, 0, 0, mode, d4[17], maxval, D);
+      } else
       predict_tile(ref, s_tab, n, lg, bx, by, mode, s_dc[node_off(L) + ni], maxval, D);
-      {
+      if (!(QT && depth == 2 && wave != 1 && wave != 2)) {
         unsigned O[32];
         load_tile8x8(plane, base, F, px, py, inside, O);
 #pragma unroll
         for (int i = 0; i < 32; ++i) D[i] = pk_sub(O[i], D[i]);
       }
-      if (depth == 0) rd_depth<0>(s_t, lane, lvl, wave, tx, ty, Q, s_acc, plane, base, F, px, py, inside, D);
-      else rd_depth<1>(s_t, lane, lvl, wave, tx, ty, Q, s_acc, plane, base, F, px, py, inside, D);
+      if (depth == 0) rd_depth<0, T, QT, QT>(s_t, lane, lvl, wave, tx, ty, Q, s_acc, plane, base, F, px, py, inside, D);
+      else if (!QT || depth == 1) rd_depth<1, T, QT, QT>(s_t, lane, lvl, wave, tx, ty, Q, s_acc, plane, base, F, px, py, inside, D);
+      else if constexpr (QT) rd_depth<2, T, QT, QT>(s_t, lane, lvl, wave, tx, ty, Q, s_acc, plane, base, F, px, py, inside, D);
     }
     if (N.writer) {
       FhevcMotionRdPuNode u;
@@ -849,11 +940,34 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
         const unsigned side = mode == 0 ? 2u : (mode == 1 || mode == 26) ? 3u : 6u;   // bits(m) of fhevc_intra_p
         unsigned long long j = (unsigned long long)Q.lam_q8 * side, bits = side;
         unsigned dist = 0, top = 0, any0 = 0, split = 0;
+        if (QT && (lvl == 1 || lvl == 2)) {
+          // HM's intra recursion over three depths (TEncSearch.cpp:1610-1661), bottom-up: per depth-1 TU its own cost with its split flag against its four
+          // children, then the depth-0 TU against the four results; dSplitCost < dSingleCost alone at both depths
+          const unsigned lam = Q.lam_q8;
+          const unsigned* const fine = reinterpret_cast<const unsigned*>(s_t + kTransformShorts + kFwdShorts + kInvShorts);
+          const unsigned* a = &s_acc[kAccWords * tu0];
+          const int e0 = lvl == 1 ? (2 * N.nby) * 4 + 2 * N.nbx : 16 + (2 * N.nby) * 8 + 2 * N.nbx, row = lvl == 1 ? 4 : 8;   // the node's first depth-1 TU
+          const unsigned d0 = a[0], r0 = 1u + a[1];
+          const unsigned long long j0 = 256ull * d0 + (unsigned long long)lam * (1u + r0);
+          unsigned long long j1 = lam;
+          unsigned dsub = 0, rsub = 0, s1 = 0;
+          for (int i = 0; i < 4; ++i) {
+            const unsigned* b = &fine[kFineWords * (e0 + (i >> 1) * row + (i & 1))];
+            const unsigned d1 = b[0], r1 = 1u + b[1], d2 = b[2], r2 = 4u + b[3];
+            const unsigned long long k1 = 256ull * d1 + (unsigned long long)lam * (1u + r1), k2 = 256ull * d2 + (unsigned long long)lam * (1u + r2);
+            const bool take1 = k2 < k1;
+            j1 += take1 ? k2 : k1; dsub += take1 ? d2 : d1; rsub += 1u + (take1 ? r2 : r1);
+            s1 |= take1 ? 16u << i : 0u;
+          }
+          const bool take = j1 < j0;
+          j += take ? j1 : j0; dist = take ? dsub : d0; bits += 1u + (take ? rsub : r0);
+          split = take ? 1u | s1 : 0u; any0 = a[1]; top = a[4];
+        } else
         for (int i = 0; i < ntu; ++i) {
           const unsigned* a = &s_acc[kAccWords * (tu0 + i)];
           const unsigned d0 = a[0], r0 = 1u + a[1], d1 = a[2], r1 = 4u + a[3];
           const unsigned long long j0 = 256ull * d0 + (unsigned long long)Q.lam_q8 * (1u + r0), j1 = 256ull * d1 + (unsigned long long)Q.lam_q8 * (1u + r1);
-          const bool take = lvl != 3 && j1 < j0;                          // dSplitCost < dSingleCost alone (TEncSearch.cpp:1661); an 8x8 node has one depth
+          const bool take = (QT || lvl != 3) && j1 < j0;                  // dSplitCost < dSingleCost alone (TEncSearch.cpp:1661); at two depths an 8x8 node has one depth
           j += take ? j1 : j0; dist += take ? d1 : d0; bits += 1u + (take ? r1 : r0);
           split |= take ? 1u << i : 0u; any0 |= a[1]; top = max(top, a[4]);
         }
@@ -882,6 +996,8 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
 // their order in the code object
 static hipError_t rd_launch_three_depths(const FhevcFrames& fr, int max_range, const FhevcRdQuant& q, int source, const unsigned* in, const unsigned* mvp, FhevcMotionRdNode* d_out,
                                          const RdPuArgs* pa, int num_cus, hipStream_t stream);
+static hipError_t intra_rd_launch_three_depths(const RefineLaunch& L, const FhevcFrames& fr, const FhevcRdQuant& q, const unsigned* first, const unsigned* fold,
+                                               const unsigned* rd_merge, int skip_mask, FhevcMotionRdPuNode* d_out);
 
 // what the device keeps resident is the occupancy query's answer in both layouts: two workgroups per CU by the registers (256 VGPRs), which is also what the
 // LDS allows at MR = 64 (1 824 B static + 80 016 B dynamic); the caps are the skip stage's
@@ -916,14 +1032,15 @@ hipError_t fhevc_launch_motion_rd_pu(const FhevcFrames& fr, int max_range, const
 
 // the intra instances: no window, so the LDS (61 KB static) leaves room for two workgroups per CU; what is resident is the occupancy query's answer
 hipError_t fhevc_launch_intra_rd(const FhevcFrames& fr, const FhevcRdQuant& q, const FhevcNodeCost* d_first, const FhevcMotionRdPuNode* d_fold,
-                                 const FhevcMotionRdNode* d_rd_merge, int skip_mask, FhevcMotionRdPuNode* d_out, int num_cus, hipStream_t stream)
+                                 const FhevcMotionRdNode* d_rd_merge, int skip_mask, FhevcMotionRdPuNode* d_out, int num_cus, hipStream_t stream, int tu_depths)
 {
   static_assert(sizeof(FhevcNodeCost) == 16 && offsetof(FhevcNodeCost, satd) == 0 && offsetof(FhevcNodeCost, mode) == 4, "first-pass record layout");
   const long long total = (long long)(fr.row_end - fr.row_begin) * fr.ctus_x * fr.num_frames;
   if (total <= 0) return hipSuccess;
-  if (!d_first || !d_out || skip_mask < 0 || skip_mask > 3 || total > 0x7FFFFFFF) return hipErrorInvalidValue;
+  if (!d_first || !d_out || skip_mask < 0 || skip_mask > 3 || total > 0x7FFFFFFF || (tu_depths != 2 && tu_depths != 3)) return hipErrorInvalidValue;
   const auto dw = [](const void* p) { return reinterpret_cast<const unsigned*>(p); };
   const RefineLaunch L = { 0, { 4, true }, num_cus, total, stream };
+  if (tu_depths == 3) return intra_rd_launch_three_depths(L, fr, q, dw(d_first), dw(d_fold), dw(d_rd_merge), skip_mask, d_out);
   if (fr.sample_bytes == 2) return refine_launch_kernel<&fhevc_intra_rd_kernel<int16_t>>(L, fr, q, dw(d_first), dw(d_fold), dw(d_rd_merge), skip_mask, d_out);
   return refine_launch_kernel<&fhevc_intra_rd_kernel<uint8_t>>(L, fr, q, dw(d_first), dw(d_fold), dw(d_rd_merge), skip_mask, d_out);
 }
@@ -937,6 +1054,14 @@ static hipError_t rd_launch_three_depths(const FhevcFrames& fr, int max_range, c
       return refine_launch_kernel<&fhevc_motion_rd_kernel<decltype(t), decltype(mr)::value, true, RdThreeDepths, RdPuArgs>>(L, fr, max_range, q, source, in, mvp, d_out, RdThreeDepths{}, *pa);
     return refine_launch_kernel<&fhevc_motion_rd_kernel<decltype(t), decltype(mr)::value, false, RdThreeDepths>>(L, fr, max_range, q, source, in, mvp, d_out, RdThreeDepths{});
   });
+}
+
+// ---- ... and of the intra candidate (fhevc_intra_rd_qt* at tu_depths 3): 71 668 B of static LDS, which still leaves room for two workgroups per CU ----
+static hipError_t intra_rd_launch_three_depths(const RefineLaunch& L, const FhevcFrames& fr, const FhevcRdQuant& q, const unsigned* first, const unsigned* fold,
+                                               const unsigned* rd_merge, int skip_mask, FhevcMotionRdPuNode* d_out)
+{
+  if (fr.sample_bytes == 2) return refine_launch_kernel<&fhevc_intra_rd_kernel<int16_t, RdThreeDepths>>(L, fr, q, first, fold, rd_merge, skip_mask, d_out, RdThreeDepths{});
+  return refine_launch_kernel<&fhevc_intra_rd_kernel<uint8_t, RdThreeDepths>>(L, fr, q, first, fold, rd_merge, skip_mask, d_out, RdThreeDepths{});
 }
 
 // workgroups of an MR = 64 instance that the device keeps on one CU (measurement tools): planes of sample_bytes, plain or PU, two or three TU depths

@@ -1364,6 +1364,57 @@ int  fhevc_p_tree_rd_intra_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const 
                                  uint8_t* depth_max, fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge, fhevc_motion_rd_node* rd_merge,
                                  fhevc_motion_rd_pu_node* rd_pu, fhevc_node_cost* first);
 
+/* ---- config 4 (P slices): the intra candidate on HM's full TU tree: the third depth, 4x4 TUs, the DST (two further intra instances of k_motion_rd.hip) ----
+ * fhevc_intra_rd* above prices two TU sizes per node and no 4x4 TU, while the inter candidates it is folded with are priced on HM's complete residual
+ * quad-tree at tu_depths 3 (fhevc_motion_rd_qt*).  These entry points take the depth count, as those do: tu_depths stands before the output pointer.
+ *   tu_depths 2: every byte is what the entry point without _qt writes, the launch is that entry point's launch (the same two kernel instances, slot 33);
+ * the entry points without _qt are forwarders with tu_depths 2.
+ *   tu_depths 3 (HM: QuadtreeTUMaxDepthIntra 3, minimum TU 4).  TU sizes: a node of side s has N0 = min(s, 32);
+ *     64x64: 32, 16 -- unchanged, its bytes equal the tu_depths 2 bytes;   32x32: 32, 16, 8;   16x16: 16, 8, 4;   8x8: 8, 4 -- the depth-1 split it never had.
+ *   Prediction: the node's ONE mode at every depth; per TU of size n at (x0, y0) what the oracle composes for that block: fho_fill_ref(x0, y0, n) ->
+ * fho_filter_ref -> fho_use_filtered_ref(m, n) -> fho_pred_intra, n = 4 included.  For n >= 8 the line is one of the 85 the first pass builds, as above.  A
+ * 4x4 TU takes the line of the 4x4 block at that place: 17 samples of the ORIGINAL plane, z-order availability in 4-sample units (what
+ * fhevc_intra_first_pass_4x4 evaluates for the block), HM's substitution walk, the edge filters of n <= 16.  The filter decision at n = 4 never selects the
+ * smoothed line (its threshold is 10 and no mode is further than 8 from modes 10 and 26), so no smoothed 4x4 line is built.
+ *   Transform: per TU step 3 of fhevc_motion_rd word for word, on r = original - prediction of that depth -- except that an intra 4x4 luma TU takes HM's
+ * DST-VII: g_as_DST_MAT_4 = { 29, 55, 74, 84 / 74, 74, 0, -74 / 84, -29, -74, 55 / 55, -84, 74, -29 } (TComRom.cpp:513-517) through fastForwardDst /
+ * fastInverseDst (TComTrQuant.cpp:412-466), selected in xTrMxN / xITrMxN (:876, :898, :945, :969); the shifts and clips are those of the 4-point DCT.
+ * Inter 4x4 TUs (fhevc_motion_rd_qt*) keep the DCT.
+ *   Choice: HM's intra recursion (TEncSearch.cpp:1610-1661), bottom-up, in 64 bits, with lam = lam_q8.  The test is dSplitCost < dSingleCost ALONE at every
+ * depth; the coded-child condition of fhevc_motion_rd_qt is the inter rule's and does not apply.
+ *   Per depth-1 TU i of a 32x32 or 16x16 node, in raster order (i = 2 * (row half) + (column half)):
+ *     K1_i = 256 D1_i + lam (1 + r1_i);   K2_i = 256 sum D2 + lam (1 + sum r2) over its four children;   take1_i = K2_i < K1_i, strictly;
+ *     C_i = take1_i ? K2_i : K1_i.
+ *   Per depth-0 TU: J0 = 256 D0 + lam (1 + r0), unchanged; J1 = sum C_i + lam; take0 = J1 < J0, strictly.
+ *   The depth-1 TUs of an 8x8 node are leaves: J1 = 256 sum D1 + lam (1 + sum r1), the two-depth formula on the residuals of the four 4x4 DST TUs.
+ *   Two depths are the special case in which K1 carries no flag and never splits: this is not a second definition.
+ *   Record: cost_rd = min((sum of the chosen J + lam * bits(m)) >> 8, 0xFFFFFFFE); dist and bits are taken over the chosen TUs; flags bits 0 and 1 stay
+ * depth-0 properties; flags bit 2 and tu_split bit 0 mean depth 0 split; tu_split bits 4..7 mean depth-1 TU i split -- zero unless bit 0 is set, and zero
+ * for 8x8 and 64x64 nodes (bits 1..3 stay the 64x64 node's); part = FHEVC_RD_PART_INTRA, the mode in pad[0], 16 bytes.  The tree kernels read the records
+ * as they are: there is no new tree kernel.
+ *   Everything else is the mirrored entry point's: inputs, validity, bits(m), the calm gate, the fold (in place where wanted; it works across depth
+ * counts), planes, band, stream, asynchrony.  FHEVC_E_INVALID with a fhevc_last_error text (nothing is launched or written): what the mirrored call
+ * rejects, and tu_depths outside {2, 3}.  No per-context or HBM state: calls with different QPs and depth counts may be in flight on two streams.  Timed
+ * under slot 37 of fhevc_kernel_timing at tu_depths 3 (36 stays rejected); at tu_depths 2 under slot 33.
+ *   The kernel: the lines of the CTU's 256 4x4 blocks with their DC values are built from the staged CTU, one thread per block; a third prediction pass
+ * runs at the level below (a lane's 8x8 tile then holds four 4x4 TUs with four lines); the transform passes are those of fhevc_motion_rd_qt's third depth
+ * (N = 8 on the level-1 buffer, N = 4 on the level-2 buffer), the level-3 buffer's depth 1 runs at N = 4 for real, and every 4-point pass takes the DST
+ * matrix.  Sums are kept per depth-1 TU; the writer lane makes the nested choice.
+ * NOT covered: NxN with its four modes, HM's RD search over the candidate list, the mode-flag bits, reconstructed neighbours, transform skip, RDOQ,
+ * chroma; the margin fit and any hook consumer. */
+int  fhevc_intra_rd_qt_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames,
+                              int ctu_row_begin, int ctu_row_end, int qp, const fhevc_node_cost* d_first, const fhevc_motion_rd_pu_node* d_fold,
+                              const fhevc_motion_rd_node* d_rd_merge, int skip_mask, int tu_depths, fhevc_motion_rd_pu_node* d_out, void* stream);
+int  fhevc_intra_rd_qt(fhevc_ctx* ctx, const int16_t* luma, int stride_samples, int qp, const fhevc_node_cost* first, const fhevc_motion_rd_pu_node* fold,
+                       const fhevc_motion_rd_node* rd_merge, int skip_mask, int tu_depths, fhevc_motion_rd_pu_node* out);
+/* fhevc_p_tree_rd_intra_frame with the depth count.  In order: fhevc_p_tree_rd_qt_frame's chain at tu_depths; the first pass of the current picture;
+ * fhevc_intra_rd_qt_device at tu_depths, folding in place under skip_mask; the RD tree.  At tu_depths 2 every byte is fhevc_p_tree_rd_intra_frame's.
+ * Rejects what that call rejects, and tu_depths outside {2, 3}. */
+int  fhevc_p_tree_rd_intra_qt_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                                    int coarse_range, const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, int skip_mask, int tu_depths,
+                                    uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge,
+                                    fhevc_motion_rd_node* rd_merge, fhevc_motion_rd_pu_node* rd_pu, fhevc_node_cost* first);
+
 /* ---- config 4 (P slices): intra candidate costs per CU node (k_intra_p.hip) -----------------------------------------------------------------------
  * HM checks intra at every CU of a P slice (TEncCu.cpp:797-816): xCheckRDCostIntra(SIZE_2Nx2N) at every depth, SIZE_NxN at the 8x8 level, both only while
  * the best mode so far has a non-zero CBF.  Without that candidate a node whose content is not in the reference picture -- uncovered background, the second
@@ -1465,7 +1516,9 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
  * -- except 31 = the RD estimate under a partition size (fhevc_motion_rd_pu*).  30 is not a slot: it stays rejected, as does any number above 31.
  * -- except 33 = the RD estimate of the intra candidate (fhevc_intra_rd*).  32 is not a slot: it stays rejected, as does any number above 33.
  * -- except 35 = the RD estimates at three TU depths (fhevc_motion_rd_qt*, fhevc_motion_rd_pu_qt* with tu_depths 3).  34 is not a slot: it stays rejected,
- * as does any number above 35.
+ * as does any number above 35
+ * -- except 37 = the RD estimate of the intra candidate at three TU depths (fhevc_intra_rd_qt* with tu_depths 3).  36 is not a slot: it stays rejected,
+ * as does any number above 37.
  * The tree that stops at a skip (fhevc_p_tree_select_skip_device), the tree that takes the intra candidate (fhevc_p_tree_select_intra_device) and the tree
  * on RD costs (fhevc_p_tree_select_rd_device) are timed under 17 */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
