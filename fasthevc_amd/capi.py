@@ -51,6 +51,7 @@ SYMBOLS = [
     "fhevc_intra_rd", "fhevc_intra_rd_device", "fhevc_p_tree_rd_intra_frame",
     "fhevc_motion_rd_qt", "fhevc_motion_rd_qt_device", "fhevc_motion_rd_pu_qt", "fhevc_motion_rd_pu_qt_device", "fhevc_p_tree_rd_qt_frame",
     "fhevc_intra_rd_qt", "fhevc_intra_rd_qt_device", "fhevc_p_tree_rd_intra_qt_frame",
+    "fhevc_intra_rd_nxn", "fhevc_intra_rd_nxn_device", "fhevc_p_tree_rd_intra_nxn_frame",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -125,6 +126,11 @@ MOTION_RD_PU_DTYPE = np.dtype([("dist", np.uint32), ("cost_rd", np.uint32), ("bi
 RD_PART_BEST, RD_PART_SECOND = 8, 9
 # part of a record of fhevc_intra_rd*: the intra candidate (FHEVC_RD_PART_INTRA); its mode lies in pad[0]
 RD_PART_INTRA = 16
+# ... and the NxN candidate of an 8x8 node (FHEVC_RD_PART_INTRA_NXN): four 4x4 PUs at the four modes of the 4x4 first pass, tu_split 1, pad zero
+RD_PART_INTRA_NXN = 17
+# fhevc_intra_rd_nxn_node: the plain NxN candidate of an 8x8 node (cbf bit i: TU i has a non-zero level; the marker: 0xFF everywhere but flags = cbf = 0)
+INTRA_RD_NXN_DTYPE = np.dtype([("dist", np.uint32), ("cost_rd", np.uint32), ("bits", np.uint16), ("flags", np.uint8), ("cbf", np.uint8), ("modes", np.uint8, (4,))])
+NXN_PER_CTU = 64
 RD_TU_SPLIT = 4
 # fhevc_motion_mvp: the predictor fhevc_motion_amvp* priced an entry against (src: 0..4 = L, A, AR, BL, AL, 5 = a filled zero; idx = src = 255: no price)
 MOTION_MVP_DTYPE = np.dtype([("px", np.int16), ("py", np.int16), ("idx", np.uint8), ("num_spatial", np.uint8), ("src", np.uint8), ("bits", np.uint8)])
@@ -319,6 +325,11 @@ def load_library(path=None):
         lib.fhevc_intra_rd_qt_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp]
         lib.fhevc_p_tree_rd_intra_qt_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), C.c_int, C.c_int, vp, vp, vp,
                                                        vp, vp, vp, vp]
+    if path is None or hasattr(lib, "fhevc_intra_rd_nxn"):   # another build (A/B against the parent commit) may predate the entry points with the NxN candidate
+        lib.fhevc_intra_rd_nxn.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp]
+        lib.fhevc_intra_rd_nxn_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp]
+        lib.fhevc_p_tree_rd_intra_nxn_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), C.c_int, vp, vp, vp,
+                                                        vp, vp, vp, vp, vp]
     lib.fhevc_p_tree_intra_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), C.c_int, vp, vp, vp, vp, vp]
     lib.fhevc_predict_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, vp, vp]
     lib.fhevc_alloc_host.argtypes = [vp, C.c_size_t]
@@ -989,6 +1000,34 @@ class Context:
         self._check(self.lib.fhevc_intra_rd_qt_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, d_first, d_fold, d_rd_merge, skip_mask,
                                                       tu_depths, d_out, stream))
 
+    def intra_rd_nxn(self, plane, first, first4=None, fold=None, rd_merge=None, skip_mask=0, origin=0, stride=None, qp=32, with_nxn=False):
+        """intra_rd_qt at 3 with the NxN candidate of the 8x8 nodes: first4 [numCtus, 256] NODE_DTYPE (the 4x4 first pass's records: the four modes priced;
+        None: intra_rd_qt's bytes at 3) -> [numCtus, 85] MOTION_RD_PU_DTYPE (part RD_PART_INTRA_NXN where NxN was taken); with_nxn: and the plain candidates
+        [numCtus, 64] INTRA_RD_NXN_DTYPE"""
+        flat = np.ascontiguousarray(plane).reshape(-1)
+        assert flat.dtype == np.int16
+        stride = stride if stride is not None else plane.shape[-1]
+        arrays = []
+        for a, per_ctu in ((first, NODES_PER_CTU), (first4, 256), (fold, NODES_PER_CTU), (rd_merge, NODES_PER_CTU)):
+            if a is not None:
+                a = np.ascontiguousarray(a).reshape(-1)
+                assert a.dtype.itemsize == 16 and a.size == self.num_ctus * per_ctu
+            arrays.append(a)
+        out = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_RD_PU_DTYPE)
+        nxn = np.zeros(self.num_ctus * NXN_PER_CTU, INTRA_RD_NXN_DTYPE) if with_nxn else None
+        self._check(self.lib.fhevc_intra_rd_nxn(self.h, flat.ctypes.data + 2 * origin, stride, qp, *[a.ctypes.data if a is not None else None for a in arrays], skip_mask,
+                                                out.ctypes.data, nxn.ctypes.data if with_nxn else None))
+        out = out.reshape(self.num_ctus, NODES_PER_CTU)
+        return (out, nxn.reshape(self.num_ctus, NXN_PER_CTU)) if with_nxn else out
+
+    def intra_rd_nxn_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_first, d_first4, d_out, d_nxn=None, d_fold=None, d_rd_merge=None, skip_mask=0,
+                            rows=None, stream=None, qp=32):
+        """intra_rd_qt_device at 3 with the NxN candidate: d_first4 num_frames * band CTUs * 256 records of the 4x4 first pass (None: that call's bytes and
+        launch), d_nxn: as many CTUs * 64 NxN records (16 B) or None.  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        self._check(self.lib.fhevc_intra_rd_nxn_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, d_first, d_first4, d_fold, d_rd_merge,
+                                                       skip_mask, d_out, d_nxn, stream))
+
     def motion_merge_pu(self, cur_plane, ref_plane, refined, origin=0, stride=None, qp=32, max_range=4, with_pus=True, with_small=True):
         """config 4: the cheapest merge candidate of every PU from the refined square nodes [numCtus, 85] (MOTION_QPEL_DTYPE; only cost_best, mvx, mvy are
         read) -> ([numCtus, 124], [numCtus, 384]) MOTION_MERGE_DTYPE in the orders of motion_pu_index / motion_pu_small_index; None for a family not asked for"""
@@ -1333,6 +1372,23 @@ class Context:
         for a in arrays:
             out += (a.reshape(self.num_ctus, NODES_PER_CTU),) if a is not None else ()
         return out
+
+    def p_tree_rd_intra_nxn_frame(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=8, coarse_range=0, shape_rule=None, tree_rule=None, skip_mask=3,
+                                  with_shapes=False, with_merge=False, with_rd_merge=False, with_rd_pu=False, with_first=False, with_nxn=False):
+        """p_tree_rd_intra_qt_frame at 3 with the 4x4 first pass of the current picture behind the first pass and intra_rd_nxn in intra_rd_qt's place ->
+        that call's results, then (with_nxn) the NxN records [numCtus, 64] INTRA_RD_NXN_DTYPE"""
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
+        dmin, dmax = np.zeros(self.num_ctus * 256, np.uint8), np.zeros(self.num_ctus * 256, np.uint8)
+        wanted = ((with_shapes, SHAPE_DTYPE), (with_merge, MOTION_MERGE_DTYPE), (with_rd_merge, MOTION_RD_DTYPE), (with_rd_pu, MOTION_RD_PU_DTYPE), (with_first, NODE_DTYPE))
+        arrays = [np.zeros(self.num_ctus * NODES_PER_CTU, dt) if want else None for want, dt in wanted]
+        nxn = np.zeros(self.num_ctus * NXN_PER_CTU, INTRA_RD_NXN_DTYPE) if with_nxn else None
+        self._check(self.lib.fhevc_p_tree_rd_intra_nxn_frame(self.h, cur, ref, stride, qp, search_range, coarse_range, C.byref(shape_rule) if shape_rule is not None else None,
+                                                             C.byref(tree_rule) if tree_rule is not None else None, skip_mask, dmin.ctypes.data, dmax.ctypes.data,
+                                                             *[a.ctypes.data if a is not None else None for a in arrays], nxn.ctypes.data if with_nxn else None))
+        out = (dmin.reshape(self.num_ctus, 256), dmax.reshape(self.num_ctus, 256))
+        for a in arrays:
+            out += (a.reshape(self.num_ctus, NODES_PER_CTU),) if a is not None else ()
+        return out + ((nxn.reshape(self.num_ctus, NXN_PER_CTU),) if with_nxn else ())
 
     def p_tree_merge_pu_frame(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=8, coarse_range=0, shape_rule=None, tree_rule=None,
                               with_shapes=False, with_merge=False):

@@ -382,6 +382,13 @@ hipError_t fhevc_motion_rd_big_residency(int sample_bytes, bool pu, int tu_depth
 constexpr int kRdPartIntra = 16;   // FHEVC_RD_PART_INTRA
 hipError_t fhevc_launch_intra_rd(const FhevcFrames& fr, const FhevcRdQuant& q, const FhevcNodeCost* d_first, const FhevcMotionRdPuNode* d_fold,
                                  const FhevcMotionRdNode* d_rd_merge, int skip_mask, FhevcMotionRdPuNode* d_out, int num_cus, hipStream_t stream, int tu_depths = 2);
+// ... at three depths with the NxN candidate of the 8x8 nodes (two further intra instances): d_first4 the 256 records per CTU of the 4x4 first pass, of which
+// satd and the low byte of mode are read; the node's record is the NxN record (part kRdPartIntraNxN) where that is valid and strictly cheaper than 2Nx2N or
+// that one is invalid.  d_nxn (may be null): the plain candidate of every 8x8 node, 64 records per CTU.  d_first4 null: fhevc_launch_intra_rd's launch at 3
+constexpr int kRdPartIntraNxN = 17;   // FHEVC_RD_PART_INTRA_NXN
+struct FhevcIntraRdNxN { uint32_t dist, cost_rd; uint16_t bits; uint8_t flags, cbf; uint8_t modes[4]; };
+hipError_t fhevc_launch_intra_rd_nxn(const FhevcFrames& fr, const FhevcRdQuant& q, const FhevcNodeCost* d_first, const FhevcNodeCost* d_first4, const FhevcMotionRdPuNode* d_fold,
+                                     const FhevcMotionRdNode* d_rd_merge, int skip_mask, FhevcMotionRdPuNode* d_out, FhevcIntraRdNxN* d_nxn, int num_cus, hipStream_t stream);
 
 // ---- ... and of the PUs' vectors (k_motion_refine_pu.hip; config 4) --------------------------------------------------
 // fr, max_range (1 .. FHEVC_MOTION_WIDE_MAX_RANGE: up to FHEVC_MOTION_MAX_RANGE the MR = 8 layout, above it the MR = 64 layout with its window in dynamic LDS),

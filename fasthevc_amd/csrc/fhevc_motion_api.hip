@@ -75,6 +75,12 @@ static_assert(sizeof(fhevc_node_cost) == 16 && offsetof(fhevc_node_cost, satd) =
 // the intra candidate's RD record is the partition-size one: the mode lies in pad[0], byte 14, and part holds a number no PartSize has
 static_assert(FHEVC_RD_PART_INTRA == kRdPartIntra && FHEVC_RD_PART_INTRA > 9 && FHEVC_RD_PART_INTRA != 255 && offsetof(fhevc_motion_rd_pu_node, pad) == 14 &&
               offsetof(FhevcMotionRdPuNode, pad) == 14 && sizeof(FhevcNodeCost) == sizeof(fhevc_node_cost), "RD record of the intra candidate");
+// ... and the NxN candidate's own record: the costs where every RD record has them, the four modes in its last dword
+template <> struct Kernel<fhevc_intra_rd_nxn_node> { using T = FhevcIntraRdNxN; };
+static_assert(FHEVC_RD_PART_INTRA_NXN == kRdPartIntraNxN && FHEVC_RD_PART_INTRA_NXN == FHEVC_RD_PART_INTRA + 1 && sizeof(fhevc_intra_rd_nxn_node) == 16 &&
+              sizeof(FhevcIntraRdNxN) == 16 && offsetof(fhevc_intra_rd_nxn_node, cost_rd) == 4 && offsetof(fhevc_intra_rd_nxn_node, bits) == 8 &&
+              offsetof(fhevc_intra_rd_nxn_node, flags) == 10 && offsetof(fhevc_intra_rd_nxn_node, cbf) == 11 && offsetof(fhevc_intra_rd_nxn_node, modes) == 12 &&
+              offsetof(FhevcIntraRdNxN, cbf) == 11 && offsetof(FhevcIntraRdNxN, modes) == 12, "record of the NxN candidate");
 static_assert(FHEVC_PUS_PER_CTU == FHEVC_PUS && FHEVC_PUS_SMALL_PER_CTU == FHEVC_PUS_SMALL, "PU counts");
 static_assert(sizeof(fhevc_motion_mvp) == 8 && offsetof(fhevc_motion_mvp, idx) == 4 && offsetof(fhevc_motion_mvp, bits) == 7 && offsetof(FhevcMotionMvp, bits) == 7,
               "predictor record layout");
@@ -138,6 +144,8 @@ int device_form(fhevc_ctx* c, bool args_ok, const char* bad_args, const Batch& b
 //   (fhevc_intra_rd)                            the picture in the second plane of d_pair, the first-pass records in the head of d_first_p, the merge records' RD
 //                                              records in d_qpel, the folded records in the head of d_qpel_pu, in and out
 //   (fhevc_p_tree_rd_intra_frame)              fhevc_p_tree_rd_frame's buffers and the first-pass records of the current picture in the head of d_first_p
+//   (fhevc_intra_rd_nxn,                       fhevc_intra_rd's buffers, the 4x4 PUs' records behind the nodes' in d_first_p and the NxN records (64 per CTU) in the
+//    fhevc_p_tree_rd_intra_nxn_frame)          head of d_intra_p, which those chains do not use
 //   d_first_p                341 (85 + 256)    the first-pass records of the nodes, behind them those of the 4x4 PUs (fhevc_intra_p, fhevc_p_tree_intra_frame)
 //   d_intra_p                85                the intra records made from them
 // fhevc_p_tree_intra_frame keeps its skip records in d_qpel: the re-pricing has read the refined nodes by then, and every later stage reads d_amvp
@@ -146,6 +154,7 @@ int device_form(fhevc_ctx* c, bool args_ok, const char* bad_args, const Batch& b
 // small PUs, 10 fhevc_motion_refine_pu, 11 / 12 the wide search / refinement, 13 the partition sizes, 15 the centres and everything centred, 17 the tree, 19 the merge stage,
 // 21 the merge stage per PU, 23 the zero-residual test, 25 the re-pricing against neighbour predictors, 27 the intra stage, 29 the RD estimate, 31 the RD estimate under a partition size,
 // 33 the RD estimate of the intra candidate, 37 the RD estimate of the intra candidate at three TU depths (fhevc_intra_rd_qt* with tu_depths 3; at 2 it is slot 33's launch),
+// 39 the same with the NxN candidate of the 8x8 nodes (fhevc_intra_rd_nxn* with d_first4; without it, it is slot 37's launch),
 // 35 the RD estimates at three TU depths (fhevc_motion_rd_qt*, fhevc_motion_rd_pu_qt* with tu_depths 3; at 2 they are
 // the launches of slots 29 and 31)
 struct Family { int per_ctu; FhevcMotionNode* fhevc_ctx::*found; FhevcMotionQpelNode* fhevc_ctx::*refined; };
@@ -230,7 +239,7 @@ class HostForm {
 
   fhevc_ctx* c;
   hipError_t e = hipSuccess;
-  Copy ins[10], outs[7];   // at most: the ten arrays of fhevc_motion_rd_pu in; three families of records and of predictor records out (the RD chain: six too, seven with the intra candidate)
+  Copy ins[10], outs[8];   // at most: the ten arrays of fhevc_motion_rd_pu in; three families of records and of predictor records out (the RD chain: six too, seven with the intra candidate, eight with its NxN records)
   int n_in = 0, n_out = 0;
 };
 
@@ -736,6 +745,61 @@ int fhevc_intra_rd(fhevc_ctx* c, const int16_t* luma, int stride_samples, int qp
   return fhevc_intra_rd_qt(c, luma, stride_samples, qp, first, fold, rd_merge, skip_mask, 2, out);
 }
 
+// ---- ... on HM's full TU tree with the NxN candidate of the 8x8 nodes (the NxN instances of k_motion_rd.hip) ----
+
+int fhevc_intra_rd_nxn_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames,
+                              int ctu_row_begin, int ctu_row_end, int qp, const fhevc_node_cost* d_first, const fhevc_node_cost* d_first4,
+                              const fhevc_motion_rd_pu_node* d_fold, const fhevc_motion_rd_node* d_rd_merge, int skip_mask, fhevc_motion_rd_pu_node* d_out,
+                              fhevc_intra_rd_nxn_node* d_nxn, void* stream)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!d_first4) {   // without the 4x4 records there is no candidate: the mirrored call, byte for byte and launch for launch
+    if (d_nxn) return fail(c, FHEVC_E_INVALID, "bad intra NxN RD-stage arguments (the NxN records need the 4x4 first pass's records)");
+    return fhevc_intra_rd_qt_device(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp, d_first, d_fold, d_rd_merge,
+                                    skip_mask, 3, d_out, stream);
+  }
+  if (!d_luma || !d_first || !d_out) return fail(c, FHEVC_E_INVALID, "bad intra RD-stage arguments (the planes, the first-pass records, the output)");
+  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 1, ctu_row_begin, ctu_row_end, qp, false)) return fail(c, FHEVC_E_INVALID, bad);
+  if (skip_mask < 0 || skip_mask > 3) return fail(c, FHEVC_E_INVALID, "bad intra RD-stage arguments (skip_mask 0..3)");
+  if (((uintptr_t)d_first | (uintptr_t)d_first4 | (uintptr_t)d_fold | (uintptr_t)d_rd_merge | (uintptr_t)d_out | (uintptr_t)d_nxn) & 3)
+    return fail(c, FHEVC_E_INVALID, "bad intra RD-stage arguments (records are 4-byte aligned)");
+  const long long ctus = (long long)num_frames * (ctu_row_end - ctu_row_begin) * c->ctus_x;
+  if (ctus > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "more than 2^31 - 1 CTUs");
+  const uintptr_t extent = (uintptr_t)ctus * FHEVC_NODES * sizeof(fhevc_motion_rd_pu_node), f = (uintptr_t)d_fold, o = (uintptr_t)d_out;
+  if (d_fold && f != o && f < o + extent && o < f + extent) return fail(c, FHEVC_E_INVALID, "bad intra RD-stage arguments (fold overlaps the output without being it)");
+  if (d_nxn) {
+    // the NxN records are written by other lanes than anything else is read or written by: no extent may touch theirs
+    const uintptr_t n = (uintptr_t)d_nxn, nn = (uintptr_t)ctus * 64 * sizeof(fhevc_intra_rd_nxn_node), e4 = (uintptr_t)ctus * FHEVC_PUS4_PER_CTU * sizeof(fhevc_node_cost);
+    const uintptr_t planes = (uintptr_t)(((long long)(num_frames - 1) * frame_stride_samples + (long long)(c->cfg.height - 1) * stride_samples + c->cfg.width) * sample_bytes);
+    const uintptr_t at[6] = { o, f, (uintptr_t)d_first, (uintptr_t)d_first4, (uintptr_t)d_rd_merge, (uintptr_t)d_luma }, len[6] = { extent, extent, extent, e4, extent, planes };
+    for (int i = 0; i < 6; ++i)
+      if (at[i] && at[i] < n + nn && n < at[i] + len[i]) return fail(c, FHEVC_E_INVALID, "bad intra NxN RD-stage arguments (the NxN records overlap another array)");
+  }
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;   // an empty band: nothing to launch, nothing written
+  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
+  return launch_on(c, stream, 39, "fhevc_launch_intra_rd_nxn", [&](hipStream_t s) {
+    return fhevc_launch_intra_rd_nxn(fr, fhevc_rd_quant(qp, c->cfg.bit_depth), kn(d_first), kn(d_first4), kn(d_fold), kn(d_rd_merge), skip_mask, kn(d_out), kn(d_nxn), c->num_cus, s);
+  });
+}
+
+int fhevc_intra_rd_nxn(fhevc_ctx* c, const int16_t* luma, int stride_samples, int qp, const fhevc_node_cost* first, const fhevc_node_cost* first4,
+                       const fhevc_motion_rd_pu_node* fold, const fhevc_motion_rd_node* rd_merge, int skip_mask, fhevc_motion_rd_pu_node* out, fhevc_intra_rd_nxn_node* nxn)
+{
+  const int rc = open_host_form(c, luma && first && out && skip_mask >= 0 && skip_mask <= 3, stride_samples, qp, 1, 1, "bad intra RD-stage arguments");
+  if (rc != GO) return rc;
+  if (nxn && !first4) return fail(c, FHEVC_E_INVALID, "bad intra NxN RD-stage arguments (the NxN records need the 4x4 first pass's records)");   // said before anything is staged
+  HostForm h(c);
+  const size_t bn = h.bytes(kNodes), b4 = (size_t)c->num_ctus * FHEVC_PUS4_PER_CTU * sizeof(fhevc_node_cost), bx = (size_t)c->num_ctus * 64 * sizeof(fhevc_intra_rd_nxn_node);
+  const fhevc_node_cost *d_first = h.in(c->d_first_p, bn + b4, first, bn), *d_first4 = h.in(c->d_first_p, bn + b4, first4, b4, bn);
+  const fhevc_motion_rd_node* d_rd_merge = h.in(c->d_qpel, bn, rd_merge, bn);
+  const fhevc_motion_rd_pu_node* d_fold = h.in(c->d_qpel_pu, h.bytes(kPus), fold, bn);   // folded in place on the device, as fhevc_intra_rd_qt does
+  fhevc_motion_rd_pu_node* d_out = h.out(c->d_qpel_pu, h.bytes(kPus), out, bn);
+  fhevc_intra_rd_nxn_node* d_nxn = h.out(c->d_intra_p, bn, nxn, bx);                     // 64 records of 16 bytes per CTU: the head of the intra records' buffer
+  return h.run(luma, nullptr, stride_samples, [&] {
+    return fhevc_intra_rd_nxn_device(c, c->d_pair + pair_plane(c), 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, d_first, d_first4, d_fold, d_rd_merge, skip_mask, d_out, d_nxn, c->stream);
+  });
+}
+
 // ---- merge-candidate costs per PU from the refined nodes (k_motion_merge_pu.hip) ----
 
 int fhevc_motion_merge_pu_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
@@ -1168,7 +1232,10 @@ int fhevc_intra_p(fhevc_ctx* c, int qp, const fhevc_node_cost* first, const fhev
 // nodes' merge records, the RD estimates of 2Nx2N and of the selection's best and second size folded into one record per node, and the RD tree
 // (fhevc_p_tree_rd_intra_frame: intra -- behind the folded inter records the first pass of the current picture and the RD estimate of its winners, gated and
 // folded in place)
-struct RdFrameOut { fhevc_motion_rd_node* rd_merge; fhevc_motion_rd_pu_node* rd_pu; bool intra; fhevc_node_cost* first; int tu_depths = 2; };
+// (fhevc_p_tree_rd_intra_nxn_frame: nxn -- behind the first pass the 4x4 first pass of the current picture, best records only, and the intra stage with the NxN candidate
+// of the 8x8 nodes in the intra stage's place; nxn_out: where its NxN records go, or null)
+struct RdFrameOut { fhevc_motion_rd_node* rd_merge; fhevc_motion_rd_pu_node* rd_pu; bool intra; fhevc_node_cost* first; int tu_depths = 2; bool nxn = false;
+                    fhevc_intra_rd_nxn_node* nxn_out = nullptr; };
 static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
                            const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes,
                            bool with_merge, fhevc_motion_merge_node* merge, bool with_merge_pu = false, bool with_amvp = false, bool with_intra = false, int skip_mask = 0,
@@ -1221,6 +1288,13 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
     d_first_rd = h.dev<fhevc_node_cost>(c->d_first_p, records + b4);
     h.out(c->d_first_p, records + b4, with_rd->first, records);
   }
+  fhevc_node_cost* d_first4_rd = nullptr;
+  fhevc_intra_rd_nxn_node* d_nxn = nullptr;
+  if (with_rd && with_rd->intra && with_rd->nxn) {
+    const size_t b4 = (size_t)c->num_ctus * FHEVC_PUS4_PER_CTU * sizeof(fhevc_node_cost);
+    d_first4_rd = h.dev<fhevc_node_cost>(c->d_first_p, records + b4, records);   // the 4x4 records behind the nodes', where fhevc_p_tree_intra_frame keeps them
+    d_nxn = h.out(c->d_intra_p, records, with_rd->nxn_out, (size_t)c->num_ctus * 64 * sizeof(fhevc_intra_rd_nxn_node));   // the head of the intra records' buffer, unused in this chain
+  }
   fhevc_motion_skip_node* d_skip = nullptr;
   fhevc_node_cost *d_first = nullptr, *d_first4 = nullptr;
   fhevc_intra_p_node* d_intra = nullptr;
@@ -1259,6 +1333,10 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
         const int16_t* d_cur = c->d_pair + pair_plane(c);   // the current picture of the staged pair, as a batch of one frame
         rc = fhevc_intra_first_pass_device(c, d_cur, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, d_first_rd, c->stream);
         // intra last, as HM tries it after the inter sizes: the earlier record stays on a tie
+        if (rc == FHEVC_OK && with_rd->nxn) {
+          rc = fhevc_intra_first_pass_4x4_device(c, d_cur, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, 0, d_first4_rd, nullptr, c->stream);
+          if (rc == FHEVC_OK) rc = fhevc_intra_rd_nxn_device(c, d_cur, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, d_first_rd, d_first4_rd, d_rd_pu, d_rd_merge, skip_mask, d_rd_pu, d_nxn, c->stream);
+        } else
         if (rc == FHEVC_OK) rc = fhevc_intra_rd_qt_device(c, d_cur, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, d_first_rd, d_rd_pu, d_rd_merge, skip_mask, tud, d_rd_pu, c->stream);
       }
       return rc != FHEVC_OK ? rc : fhevc_p_tree_select_rd_pu_device(c, d_rd_pu, d_rd_merge, skip_mask, 1, 0, c->ctus_y, tree_rule, d_min, d_max, nullptr, c->stream);
@@ -1344,6 +1422,16 @@ int fhevc_p_tree_rd_intra_qt_frame(fhevc_ctx* c, const int16_t* cur_luma, const 
                                    fhevc_motion_rd_pu_node* rd_pu, fhevc_node_cost* first)
 {
   const RdFrameOut rd = { rd_merge, rd_pu, true, first, tu_depths };
+  return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge, true, true,
+                         false, skip_mask, nullptr, &rd);
+}
+
+int fhevc_p_tree_rd_intra_nxn_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                                    const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, int skip_mask, uint8_t* depth_min, uint8_t* depth_max,
+                                    fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge, fhevc_motion_rd_node* rd_merge, fhevc_motion_rd_pu_node* rd_pu,
+                                    fhevc_node_cost* first, fhevc_intra_rd_nxn_node* nxn)
+{
+  const RdFrameOut rd = { rd_merge, rd_pu, true, first, 3, true, nxn };
   return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge, true, true,
                          false, skip_mask, nullptr, &rd);
 }

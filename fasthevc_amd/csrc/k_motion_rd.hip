@@ -162,10 +162,30 @@ __device__ __forceinline__ void rd_commit(unsigned* acc, int tu, int lane, unsig
   }
 }
 
+// the NxN candidate of the 8x8 nodes (fhevc_intra_rd_nxn*): three words per 8x8 node behind the sums per depth-0 TU -- the distortion, the level bits of
+// its four 4x4 TUs (low half; bit 16 + i: TU i has a level), max |c|
+constexpr int kNxnWords = 3;
+// one unit of a 4-point COLS pass is one row of ONE 4x4 TU: four neighbouring lanes into one, then that lane into the words of the 8x8 node that holds the TU
+__device__ __forceinline__ void rd_commit_nxn(unsigned* nx, int lane, int seg, unsigned bits, unsigned top)
+{
+#pragma unroll
+  for (int d = 1; d < 4; d <<= 1) {
+    bits += (unsigned)__shfl_xor((int)bits, d);
+    top = max(top, (unsigned)__shfl_xor((int)top, d));
+  }
+  if ((lane & 3) == 0) {
+    unsigned* const w = nx + kNxnWords * ((lane >> 3) * 8 + (seg >> 1));
+    const int i = ((lane >> 2) & 1) * 2 + (seg & 1);   // fhevc_intra_p's order of the four PUs
+    atomicAdd(&w[1], bits | (bits != 0u ? 0x10000u << i : 0u));   // 64 levels of 31 bits at the most: the low half never carries
+    atomicMax(&w[2], top);
+  }
+}
+
 // one pass over one buffer at TU size N: the thread's 16 outputs, packed two to a register until the barrier.  COLS quantises, prices and dequantises them
 // and commits the sums of every unit to its depth-0 TU: tu0 = the buffer's first, l0 = log2 of the buffer's depth-0 TU size (FINE: of its depth-1 TUs)
 // DST (the intra instances of three TU depths): a pass at N = 4 takes the DST matrix instead; the shifts and clips are the 4-point DCT's (xTrMxN, xITrMxN)
-template <int N, int STAGE, int DEPTH, bool FINE = false, bool DST = false>
+// NXN: the pass over the level-3 buffer at N = 4 behind the NxN prediction; acc is the NxN words then
+template <int N, int STAGE, int DEPTH, bool FINE = false, bool DST = false, bool NXN = false>
 __device__ __forceinline__ void tu_pass(const short* tables, const short* buf, int lane, int wave, int bd, const FhevcRdQuant& Q, unsigned* acc, int tu0, int l0,
                                         unsigned (&t)[8])
 {
@@ -199,6 +219,10 @@ __device__ __forceinline__ void tu_pass(const short* tables, const short* buf, i
       else t[o >> 1] = (unsigned)a & 0xFFFFu;
       if ((i & (kRowsInFlight - 1)) == kRowsInFlight - 1) __builtin_amdgcn_sched_barrier(0);   // or every matrix row of the pass is fetched ahead, into registers
     }
+    if constexpr (NXN) {
+      static_assert(N == 4 && !FINE, "the NxN candidate is four 4x4 TUs");
+      if (STAGE == COLS) rd_commit_nxn(acc, lane, seg, bits, top);
+    } else
     if (STAGE == COLS) {
       int ln = lane;   // FINE: opaque, so that the depth-1 TU's index is worked out here and not kept through the CTU loop beside the depth-0 TU's
       if constexpr (FINE) asm volatile("" : "+v"(ln));
@@ -238,7 +262,8 @@ __device__ __forceinline__ void tu_store(short* buf, int lane, int wave, const u
 // one pass over the four buffers: levels 0 and 1 at 32 >> DEPTH, level 2 at 16 >> DEPTH, level 3 at 8 >> DEPTH
 // QT (three TU depths): the sums of depths 1 and 2 of the level-1 and level-2 buffers go per depth-1 TU into the words behind the matrices; DEPTH 2 is a
 // pass over those two buffers alone, at 8 and 4, by all four waves
-template <int STAGE, int DEPTH, bool QT = false, bool DST = false>
+// NXN (fhevc_intra_rd_nxn*): the DEPTH 2 pass takes the level-3 buffer along, at 4: the NxN candidate's four TUs per 8x8 node, their sums behind acc's
+template <int STAGE, int DEPTH, bool QT = false, bool DST = false, bool NXN = false>
 __device__ __forceinline__ void rd_stage(short* s, int lane, int wave, int bd, const FhevcRdQuant& Q, unsigned* acc)
 {
   static_assert(DEPTH < 2 || QT, "the third depth goes with QT");
@@ -249,6 +274,16 @@ __device__ __forceinline__ void rd_stage(short* s, int lane, int wave, int bd, c
     unsigned t1[8], t2[8];
     tu_pass<8, STAGE, 2, true>(tables, b1, lane, wave, bd, Q, fine, 0, 4, t1);
     tu_pass<4, STAGE, 2, true, DST>(tables, b2, lane, wave, bd, Q, fine, 16, 3, t2);
+    if constexpr (NXN) {
+      unsigned t3[8];
+      tu_pass<4, STAGE, 2, false, true, true>(tables, b3, lane, wave, bd, Q, acc + kAccWords * kTus, 0, 0, t3);
+      __syncthreads();   // every thread has read
+      tu_store<8, STAGE>(b1, lane, wave, t1);
+      tu_store<4, STAGE>(b2, lane, wave, t2);
+      tu_store<4, STAGE>(b3, lane, wave, t3);
+      __syncthreads();
+      return;
+    }
     __syncthreads();   // every thread has read
     tu_store<8, STAGE>(b1, lane, wave, t1);
     tu_store<4, STAGE>(b2, lane, wave, t2);
@@ -280,7 +315,8 @@ __device__ __forceinline__ void rd_stage(short* s, int lane, int wave, int bd, c
 // The original tile is loaded a second time here (from the cache): kept in registers across the passes it cost the kernel its second wave per SIMD
 // QT (three TU depths): at depths 1 and 2 the level-1 and level-2 waves sum over the tiles of their depth-1 TU (2 x 2 tiles, the lane's own) and store per
 // depth-1 TU; at depth 2 only they rewrite their tiles and take the squared error -- the other two buffers have no third depth
-template <int DEPTH, typename T, bool QT = false, bool DST = false>
+// NXN (fhevc_intra_rd_nxn*): at depth 2 the level-3 wave writes its tile too -- the NxN prediction's residual -- and stores its squared error per 8x8 node
+template <int DEPTH, typename T, bool QT = false, bool DST = false, bool NXN = false>
 __device__ __forceinline__ void rd_depth(short* s, int lane, int lvl, int wave, int tx, int ty, const FhevcRdQuant& Q, unsigned* acc, const T* plane, long long cur_base,
                                          const FhevcFrames& F, int px, int py, bool inside, const unsigned (&D)[32])
 {
@@ -291,11 +327,20 @@ __device__ __forceinline__ void rd_depth(short* s, int lane, int lvl, int wave, 
 #pragma unroll
     for (int y = 0; y < 8; ++y) *reinterpret_cast<uint4*>(tile + y * kPitch) = make_uint4(D[4 * y], D[4 * y + 1], D[4 * y + 2], D[4 * y + 3]);
   }
+  if constexpr (NXN && DEPTH == 2) {
+    if (wave == 3) {   // wave-uniform
+#pragma unroll
+      for (int y = 0; y < 8; ++y) *reinterpret_cast<uint4*>(tile + y * kPitch) = make_uint4(D[4 * y], D[4 * y + 1], D[4 * y + 2], D[4 * y + 3]);
+    }
+  }
   __syncthreads();
-  rd_stage<ROWS, DEPTH, QT, DST>(s, lane, wave, bd, Q, acc);
-  rd_stage<COLS, DEPTH, QT, DST>(s, lane, wave, bd, Q, acc);
-  rd_stage<INV1, DEPTH, QT, DST>(s, lane, wave, bd, Q, acc);
-  rd_stage<INV2, DEPTH, QT, DST>(s, lane, wave, bd, Q, acc);
+  rd_stage<ROWS, DEPTH, QT, DST, NXN>(s, lane, wave, bd, Q, acc);
+  rd_stage<COLS, DEPTH, QT, DST, NXN>(s, lane, wave, bd, Q, acc);
+  rd_stage<INV1, DEPTH, QT, DST, NXN>(s, lane, wave, bd, Q, acc);
+  rd_stage<INV2, DEPTH, QT, DST, NXN>(s, lane, wave, bd, Q, acc);
+  if constexpr (NXN) {
+    if (DEPTH == 2 && !fine && wave != 3) { __syncthreads(); return; }
+  } else
   if (DEPTH == 2 && !fine) { __syncthreads(); return; }
   const int top = (1 << bd) - 1, sh = 2 * (bd - 8);
   unsigned O[32];
@@ -311,6 +356,13 @@ __device__ __forceinline__ void rd_depth(short* s, int lane, int lvl, int wave, 
       const int e0 = (int)(o & 0xFFFFu) - min(max((int)(p & 0xFFFFu) + (int)(short)(r[k] & 0xFFFFu), 0), top);
       const int e1 = (int)(o >> 16) - min(max((int)(p >> 16) + (int)(short)(r[k] >> 16), 0), top);
       sum += ((unsigned)(e0 * e0) >> sh) + ((unsigned)(e1 * e1) >> sh);
+    }
+  }
+  if constexpr (NXN && DEPTH == 2) {
+    if (wave == 3) {
+      acc[kAccWords * kTus + kNxnWords * lane] = sum;   // the lane's tile is its 8x8 node
+      __syncthreads();
+      return;
     }
   }
   if (fine) {
@@ -411,6 +463,7 @@ __device__ __forceinline__ RdPuLane rd_pu_lane(const RdPuArgs& A, long long oc, 
 }
 
 struct RdThreeDepths {};   // a tag in the kernel's argument pack: it carries nothing
+struct RdNxN { const unsigned* first4; unsigned* nxn; };   // the second tag of the intra instances: the 4x4 first pass's records as dwords, the plain NxN records (or null)
 // where the tag stands in front of the PU arguments, the comma fold that picks the pack's last argument drops it: that is what it is for
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-value"
@@ -702,17 +755,39 @@ __device__ __forceinline__ void predict_tile(const short* ref, const short* tab,
 }
 }  // namespace ird
 
+// the NxN candidate's four PUs of the 8x8 node at (tx, ty) of CTU ctu: units (2 tx + (i & 1), 2 ty + (i >> 1)) of the 16x16 raster of the 4x4 first pass's
+// records (satd, mode, ...).  Byte i is PU i's mode; where the node lies outside or a PU has the marker or a mode byte above 34 the candidate is invalid:
+// all four 0 and bit 31 set.  No byte of the records reaches an address
+__device__ __forceinline__ unsigned nxn_modes(const unsigned* __restrict__ first4, long long ctu, int tx, int ty, bool node_in)
+{
+  const unsigned* r4 = first4 + (ctu * 256 + (2 * ty) * 16 + 2 * tx) * 4;
+  bool ok = node_in;
+  unsigned m = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned* r = r4 + ((i >> 1) * 16 + (i & 1)) * 4;
+    const unsigned sa = r[0], mo = r[1] & 0xFFu;
+    ok = ok && sa != kRdMark && mo <= 34u;
+    m |= mo << (8 * i);
+  }
+  return ok ? m : 0x80000000u;
+}
+
 // T = int16_t or uint8_t planes.  first: the first pass's records as dwords (satd, mode, the cost's two); fold / rd_merge: RD records as dwords, or null;
 // fold may be out (the writer lane reads its record, then writes it)
 // Three TU depths (fhevc_intra_rd_qt* at tu_depths 3): RdThreeDepths as the pack -- the 32x32 and 16x16 nodes get their third TU size, the 8x8 nodes their
 // depth 1, every 4x4 TU the DST.  With the empty pack the instances are the ones there always were, by code
+// The NxN candidate (fhevc_intra_rd_nxn*): RdNxN BEHIND RdThreeDepths -- in the third pass, where the level-3 buffer is idle, the level-3 wave predicts the
+// four 4x4 blocks of its tile each at ITS mode of the 4x4 first pass; the pass over that buffer at 4 with the DST gives the candidate's sums per 8x8 node,
+// and the writer lane of an 8x8 node takes NxN where it is strictly cheaper than its 2Nx2N record (or that one is invalid), before the gate and the fold
 template <typename T, class... A>
 __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, FhevcRdQuant Q, const unsigned* __restrict__ first, const unsigned* fold,
                                                              const unsigned* __restrict__ rd_merge, int skip_mask, FhevcMotionRdPuNode* out, A... tag)
 {
   using namespace ird;
   constexpr bool QT = (std::is_same_v<A, RdThreeDepths> || ...);
-  static_assert(sizeof...(A) == (QT ? 1 : 0), "the pack is the tag of three TU depths or empty");
+  constexpr bool NXN = (std::is_same_v<A, RdNxN> || ...);
+  static_assert(sizeof...(A) == (QT ? 1 : 0) + (NXN ? 1 : 0) && (QT || !NXN), "the pack is empty, the tag of three TU depths, or that tag and the NxN arguments behind it");
   // the transform buffers (under them, first, the staged CTU) and the matrices; QT: behind them the sums per depth-1 TU, the DST, the 4x4 lines and their DC values
   __shared__ __attribute__((aligned(16))) short s_t[kTransformShorts + kFwdShorts + kInvShorts + (QT ? kQtShorts : 0)];
   __shared__ short s_refbuf[kLinePad + kLineTotal + kLinePad + 1];   // unfiltered lines: line[2 n] the corner, + i above, - j left
@@ -720,7 +795,7 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
   __shared__ short s_above[132], s_left[64], s_tab[18];
   __shared__ int s_dc[FHEVC_NODES];
   __shared__ unsigned char s_av[kUnits + 3], s_valid[FHEVC_NODES];
-  __shared__ unsigned s_acc[kAccWords * kTus];
+  __shared__ unsigned s_acc[kAccWords * kTus + (NXN ? kNxnWords * 64 : 0)];   // NXN: behind the sums, the candidate's three words per 8x8 node
   static_assert(kTransformShorts >= 64 * 64, "the staged CTU lies under the transform buffers");
   short* const s_org = s_t;
   short* const s_ref = s_refbuf + kLinePad;
@@ -769,6 +844,8 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
       s_valid[tid] = ((ox + (ni % cnt) * n + n <= F.width) && (oy + (ni / cnt) * n + n <= F.height)) ? 1 : 0;
     }
     for (int i = tid; i < kAccWords * kTus; i += 256) s_acc[i] = 0;
+    if constexpr (NXN)
+      if (tid < kNxnWords * 64) s_acc[kAccWords * kTus + tid] = 0;
     if constexpr (QT)
       for (int i = tid; i < kFineTus * kFineWords; i += 256) reinterpret_cast<unsigned*>(s_t + kTransformShorts + kFwdShorts + kInvShorts)[i] = 0u;
     __syncthreads();
@@ -926,9 +1003,26 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
 #pragma unroll
         for (int i = 0; i < 32; ++i) D[i] = pk_sub(O[i], D[i]);
       }
+      if constexpr (NXN) {
+        if (depth == 2 && wave == 3) {
+          // the level-3 buffer is idle in the third pass: the NxN candidate runs there -- the four 4x4 blocks of the lane's tile, each at ITS mode of the
+          // 4x4 first pass from its own line, as the `four` branch predicts them at the node's one mode
+          const unsigned m4 = nxn_modes((tag, ...).first4, ((long long)(f * band_rows + (cy - F.row_begin)) * F.ctus_x + cx), tx, ty, node_in);
+          const short* l4 = s_t + kLines4At + ((2 * ty) * 16 + 2 * tx) * kLine4 + 8;
+          const short* d4 = s_t + kDc4At + (2 * ty) * 16 + 2 * tx;
+          predict_tile<4, 0, 0>(l4, s_tab, 4, 2, 0, 0, (int)(m4 & 0x7Fu), d4[0], maxval, D);
+          predict_tile<4, 4, 0>(l4 + kLine4, s_tab, 4, 2, 0, 0, (int)((m4 >> 8) & 0xFFu), d4[1], maxval, D);
+          predict_tile<4, 0, 4>(l4 + 16 * kLine4, s_tab, 4, 2, 0, 0, (int)((m4 >> 16) & 0xFFu), d4[16], maxval, D);
+          predict_tile<4, 4, 4>(l4 + 17 * kLine4, s_tab, 4, 2, 0, 0, (int)((m4 >> 24) & 0x7Fu), d4[17], maxval, D);
+          unsigned O[32];
+          load_tile8x8(plane, base, F, px, py, inside, O);
+#pragma unroll
+          for (int i = 0; i < 32; ++i) D[i] = pk_sub(O[i], D[i]);
+        }
+      }
       if (depth == 0) rd_depth<0, T, QT, QT>(s_t, lane, lvl, wave, tx, ty, Q, s_acc, plane, base, F, px, py, inside, D);
       else if (!QT || depth == 1) rd_depth<1, T, QT, QT>(s_t, lane, lvl, wave, tx, ty, Q, s_acc, plane, base, F, px, py, inside, D);
-      else if constexpr (QT) rd_depth<2, T, QT, QT>(s_t, lane, lvl, wave, tx, ty, Q, s_acc, plane, base, F, px, py, inside, D);
+      else if constexpr (QT) rd_depth<2, T, QT, QT, NXN>(s_t, lane, lvl, wave, tx, ty, Q, s_acc, plane, base, F, px, py, inside, D);
     }
     if (N.writer) {
       FhevcMotionRdPuNode u;
@@ -978,12 +1072,46 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
         u.flags = (uint8_t)((any0 == 0u ? 1 : 0) | (zero_half ? 2 : 0) | (split ? 4 : 0)); u.tu_split = (uint8_t)split;
         u.part = kRdPartIntra; u.pad[0] = (uint8_t)mode;
       }
+      if constexpr (NXN) {
+        if (lvl == 3) {
+          // the NxN candidate: four 4x4 TUs, each with its cbf bit and its mode's bits, no split flag (HM infers it); its own record whatever becomes of it,
+          // and the node's record where it is strictly cheaper than 2Nx2N (a marker there loses to anything)
+          const RdNxN X = (tag, ...);   // the pack's last argument
+          const long long ctu = (long long)(f * band_rows + (cy - F.row_begin)) * F.ctus_x + cx;   // compact over the band
+          const unsigned modes4 = nxn_modes(X.first4, ctu, tx, ty, node_in);   // read a second time (from the cache): nothing of it is kept through the passes
+          const bool nv = (modes4 >> 31) == 0u;
+          const unsigned* const w = &s_acc[kAccWords * kTus + kNxnWords * (nidx - N.first)];
+          unsigned side4 = 0;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const unsigned m = (modes4 >> (8 * i)) & 0xFFu;
+            side4 += m == 0u ? 2u : (m == 1u || m == 26u) ? 3u : 6u;
+          }
+          const unsigned nd = w[0], lv = w[1] & 0xFFFFu, cbf = w[1] >> 16, nb = 4u + lv + side4;
+          unsigned long long nj = (256ull * nd + (unsigned long long)Q.lam_q8 * nb) >> 8;
+          const unsigned nc = nj < 0xFFFFFFFEull ? (unsigned)nj : 0xFFFFFFFEu;
+          const unsigned nf = (lv == 0u ? 1u : 0u) | (((w[2] * Q.scale + Q.add_half[0]) >> Q.qbits[0]) == 0u ? 2u : 0u) | 4u;
+          if (X.nxn) {
+            unsigned* const o = X.nxn + (ctu * 64 + (nidx - N.first)) * 4;
+            o[0] = nv ? nd : kRdMark; o[1] = nv ? nc : kRdMark;
+            o[2] = nv ? (nb < 65535u ? nb : 65535u) | nf << 16 | cbf << 24 : 0xFFFFu;
+            o[3] = nv ? modes4 : 0xFFFFFFFFu;
+          }
+          if (nv && nc < u.cost_rd) {
+            u.dist = nd; u.cost_rd = nc; u.bits = (uint16_t)(nb < 65535u ? nb : 65535u); u.flags = (uint8_t)nf; u.tu_split = 1;
+            u.part = kRdPartIntraNxN; u.merged = 0; u.pad[0] = u.pad[1] = 0;
+          }
+        }
+      }
       // the earlier record (a marker where there is none), read through the output pointer where the fold is in place
       const FhevcMotionRdPuNode* const src = reinterpret_cast<const void*>(fold) == reinterpret_cast<const void*>(out) ? out : reinterpret_cast<const FhevcMotionRdPuNode*>(fold);
       const FhevcMotionRdPuNode fr = fold ? src[rec] : none;
       // calm: the merge candidate is strictly the cheapest so far and has a masked zero bit -- HM does not try intra there (TEncCu.cpp:799-804)
       bool calm = false;
       if (rd_merge) calm = rd_merge[rec * 4 + 1] < fr.cost_rd && (((rd_merge[rec * 4 + 2] >> 16) & 0xFFu) & (unsigned)skip_mask) != 0u;
+      if constexpr (NXN) {
+        if (calm || (fold && !(u.cost_rd < fr.cost_rd))) u = fr;   // a marker's cost is below nothing: the test of validity is in the comparison
+      } else
       if (calm || (fold && !(valid && u.cost_rd < fr.cost_rd))) u = fr;
       out[rec] = u;
     }
@@ -1076,6 +1204,24 @@ hipError_t fhevc_motion_rd_big_residency(int sample_bytes, bool pu, int tu_depth
     return pu ? refine_resident<&fhevc_motion_rd_kernel<T, MRB, true, RdPuArgs>>(LDS, per_cu) : refine_resident<&fhevc_motion_rd_kernel<T, MRB, false>>(LDS, per_cu);
   };
   return sample_bytes == 2 ? pick(int16_t()) : pick(uint8_t());
+}
+
+// ---- the intra candidate with the NxN candidate of the 8x8 nodes (fhevc_intra_rd_nxn*): the instances of three TU depths with the second tag, behind every
+// instance there was; 72 436 B of static LDS.  Without the 4x4 records it is fhevc_launch_intra_rd's launch at three depths ----
+hipError_t fhevc_launch_intra_rd_nxn(const FhevcFrames& fr, const FhevcRdQuant& q, const FhevcNodeCost* d_first, const FhevcNodeCost* d_first4, const FhevcMotionRdPuNode* d_fold,
+                                     const FhevcMotionRdNode* d_rd_merge, int skip_mask, FhevcMotionRdPuNode* d_out, FhevcIntraRdNxN* d_nxn, int num_cus, hipStream_t stream)
+{
+  static_assert(sizeof(FhevcIntraRdNxN) == 16, "record layout");
+  if (!d_first4) return d_nxn ? hipErrorInvalidValue : fhevc_launch_intra_rd(fr, q, d_first, d_fold, d_rd_merge, skip_mask, d_out, num_cus, stream, 3);
+  const long long total = (long long)(fr.row_end - fr.row_begin) * fr.ctus_x * fr.num_frames;
+  if (total <= 0) return hipSuccess;
+  if (!d_first || !d_out || skip_mask < 0 || skip_mask > 3 || total > 0x7FFFFFFF) return hipErrorInvalidValue;
+  const auto dw = [](const void* p) { return reinterpret_cast<const unsigned*>(p); };
+  const RefineLaunch L = { 0, { 4, true }, num_cus, total, stream };
+  const RdNxN x = { dw(d_first4), reinterpret_cast<unsigned*>(d_nxn) };
+  if (fr.sample_bytes == 2)
+    return refine_launch_kernel<&fhevc_intra_rd_kernel<int16_t, RdThreeDepths, RdNxN>>(L, fr, q, dw(d_first), dw(d_fold), dw(d_rd_merge), skip_mask, d_out, RdThreeDepths{}, x);
+  return refine_launch_kernel<&fhevc_intra_rd_kernel<uint8_t, RdThreeDepths, RdNxN>>(L, fr, q, dw(d_first), dw(d_fold), dw(d_rd_merge), skip_mask, d_out, RdThreeDepths{}, x);
 }
 
 #pragma clang diagnostic pop

@@ -1415,6 +1415,69 @@ int  fhevc_p_tree_rd_intra_qt_frame(fhevc_ctx* ctx, const int16_t* cur_luma, con
                                     uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge,
                                     fhevc_motion_rd_node* rd_merge, fhevc_motion_rd_pu_node* rd_pu, fhevc_node_cost* first);
 
+/* ---- config 4 (P slices): the intra candidate with the NxN candidate of the 8x8 CUs, four modes (two further intra instances of k_motion_rd.hip) ----------
+ * At the smallest CU HM checks xCheckRDCostIntra(SIZE_NxN) right behind SIZE_2Nx2N (TEncCu.cpp:806-815).  fhevc_intra_rd_qt* prices an 8x8 node with ONE
+ * mode only: what the section above lists as not covered is covered by the entry points of this section.  The stage is fhevc_intra_rd_qt* at tu_depths 3 plus that
+ * candidate; there is no tu_depths argument.  The NxN candidate exists only for 8x8 nodes (nodes 21..84).
+ *   Input: beside everything fhevc_intra_rd_qt_device takes, d_first4: the 256 fhevc_node_cost records per CTU of fhevc_intra_first_pass_4x4_device for the
+ * same pictures, in 16x16 raster of 4x4 units, compact over the band.  Of a record only satd (dword 0) and the low byte of mode (dword 1) are read; any byte
+ * content is legal and none of it reaches an address or a loop bound.  The four PUs of 8x8 node (x, y) of the 8x8 raster are units (2x, 2y), (2x+1, 2y),
+ * (2x, 2y+1), (2x+1, 2y+1): fhevc_intra_p's order.
+ *   Validity: NxN is valid iff the node is INSIDE and each of the four records has satd != 0xFFFFFFFF and a mode byte <= 34.  An invalid candidate predicts
+ * with mode 0 and is dropped.
+ *   Prediction and transform: PU i is one 4x4 TU (uiInitTrDepth = 1, TEncSearch.cpp:2187-2188; 4 is the minimum TU, nothing splits further), predicted at
+ * ITS mode m_i from the line of the 4x4 block at its place -- the line the section above builds: 17 original samples, z-order availability in 4-sample units, the
+ * substitution walk, never smoothed, the edge filters of n <= 16; in oracle terms fho_fill_ref(x, y, 4) -> fho_pred_intra.  Then step 3 of fhevc_motion_rd
+ * with the DST-VII, word for word as the 4x4 intra TUs above.
+ *   Cost, in 64 bits: J = 256 * sum D_i + lam_q8 * (sum r_i + sum bits(m_i)); cost_rd = min(J >> 8, 0xFFFFFFFE); dist = sum D_i;
+ * bits = min(sum r_i + sum bits(m_i), 65535); r_i = 1 + the level bits of TU i; bits(m) is fhevc_intra_p's (2 / 3 / 6).  NO split-flag bit is counted: HM
+ * infers the split of an intra NxN CU at its own depth (TEncEntropy.cpp:241-244).  The part-mode bin is left out as everywhere else: at the smallest CU
+ * both sizes cost one bin.
+ *   Flags bits 0 and 1 are properties of the four TUs priced: every level is zero under add_plain, respectively under add_half, with the 4-point
+ * quantiser's numbers.
+ *   Choice: HM tries 2Nx2N first and xCheckBestMode keeps the earlier mode on a tie.  The stage's intra record is the NxN record iff NxN is valid and either
+ * its cost_rd is STRICTLY smaller than the 2Nx2N record's or 2Nx2N is invalid; otherwise it is the bytes fhevc_intra_rd_qt_device writes at 3.  The calm
+ * gate and the fold then act on that record unchanged; folding in place is allowed.
+ *   The NxN record in the output: a fhevc_motion_rd_pu_node with part = FHEVC_RD_PART_INTRA_NXN (17), tu_split = 1, flags bit 2 set, merged = 0,
+ * pad = {0, 0}.  The four modes are the caller's own d_first4 bytes.  The tree kernels read dword 1 and byte 10 as before: no tree kernel is added.
+ *   d_nxn (or NULL): the plain NxN candidate of every 8x8 node, 64 fhevc_intra_rd_nxn_node per CTU in node order 21..84, compact over the band,
+ * independent of the choice, the gate and the fold; cbf bit i: TU i has a non-zero level.  The marker: dist = cost_rd = 0xFFFFFFFF, bits = 0xFFFF,
+ * flags = cbf = 0, modes 255 four times.  It is written over exactly its extent.
+ *   d_first4 == NULL: every byte and the launch itself are fhevc_intra_rd_qt_device's at 3 (slot 37); d_nxn must then be NULL too, else FHEVC_E_INVALID.
+ *   FHEVC_E_INVALID with nothing launched or written: what the mirrored call rejects, a d_first4 or d_nxn that is not 4-byte aligned, and any overlap of
+ * d_nxn with another array of the call (the planes included).  No per-context or HBM state: calls with different QPs may be in flight on two streams.
+ * Timed under slot 39 of fhevc_kernel_timing (38 stays rejected).
+ *   The kernel: in the third pass the level-3 wave, whose buffer is idle there, predicts the four 4x4 blocks of each lane's tile at their four modes; the
+ * pass takes the level-3 buffer along at N = 4 with the DST; three words per 8x8 node (D, level bits with the four cbf bits, max |c|) lie behind the sums
+ * per depth-0 TU; the writer lane of the node forms J, compares and writes both records.  ONE launch per call.
+ * NOT covered (stated departures): HM predicts PU i+1 from PU i's reconstruction -- here every line is from the original picture, as in every other
+ * stage; HM searches eight candidates plus MPMs per PU -- here there is one mode per PU; transform skip (which HM tries only for NxN,
+ * TEncSearch.cpp:1479), RDOQ, chroma's four PUs and the mode-flag bits; the margin fit and any hook consumer. */
+#define FHEVC_RD_PART_INTRA_NXN 17
+typedef struct fhevc_intra_rd_nxn_node {
+  uint32_t dist;       /* sum D_i of the four 4x4 TUs */
+  uint32_t cost_rd;    /* min(J >> 8, 0xFFFFFFFE) */
+  uint16_t bits;
+  uint8_t  flags;      /* bits 0, 1 as above; bit 2 set */
+  uint8_t  cbf;        /* bit i: TU i has a non-zero level */
+  uint8_t  modes[4];   /* the four modes priced, in fhevc_intra_p's order */
+} fhevc_intra_rd_nxn_node;  /* 16 bytes */
+int  fhevc_intra_rd_nxn_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames,
+                               int ctu_row_begin, int ctu_row_end, int qp, const fhevc_node_cost* d_first, const fhevc_node_cost* d_first4,
+                               const fhevc_motion_rd_pu_node* d_fold, const fhevc_motion_rd_node* d_rd_merge, int skip_mask, fhevc_motion_rd_pu_node* d_out,
+                               fhevc_intra_rd_nxn_node* d_nxn, void* stream);
+/* the host form: one picture, first4 its 256 records per CTU (or NULL), nxn the 64 NxN records per CTU (or NULL; needs first4) */
+int  fhevc_intra_rd_nxn(fhevc_ctx* ctx, const int16_t* luma, int stride_samples, int qp, const fhevc_node_cost* first, const fhevc_node_cost* first4,
+                        const fhevc_motion_rd_pu_node* fold, const fhevc_motion_rd_node* rd_merge, int skip_mask, fhevc_motion_rd_pu_node* out,
+                        fhevc_intra_rd_nxn_node* nxn);
+/* fhevc_p_tree_rd_intra_qt_frame's chain at tu_depths 3 with the NxN candidate.  In order: fhevc_p_tree_rd_qt_frame's chain at 3; the first pass of the
+ * current picture and fhevc_intra_first_pass_4x4_device on it (best records only); fhevc_intra_rd_nxn_device, folding in place under skip_mask; the RD
+ * tree.  nxn (or NULL): the NxN records of the picture.  Rejects what fhevc_p_tree_rd_intra_qt_frame rejects. */
+int  fhevc_p_tree_rd_intra_nxn_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                                     int coarse_range, const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, int skip_mask,
+                                     uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge,
+                                     fhevc_motion_rd_node* rd_merge, fhevc_motion_rd_pu_node* rd_pu, fhevc_node_cost* first, fhevc_intra_rd_nxn_node* nxn);
+
 /* ---- config 4 (P slices): intra candidate costs per CU node (k_intra_p.hip) -----------------------------------------------------------------------
  * HM checks intra at every CU of a P slice (TEncCu.cpp:797-816): xCheckRDCostIntra(SIZE_2Nx2N) at every depth, SIZE_NxN at the 8x8 level, both only while
  * the best mode so far has a non-zero CBF.  Without that candidate a node whose content is not in the reference picture -- uncovered background, the second
@@ -1518,7 +1581,9 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
  * -- except 35 = the RD estimates at three TU depths (fhevc_motion_rd_qt*, fhevc_motion_rd_pu_qt* with tu_depths 3).  34 is not a slot: it stays rejected,
  * as does any number above 35
  * -- except 37 = the RD estimate of the intra candidate at three TU depths (fhevc_intra_rd_qt* with tu_depths 3).  36 is not a slot: it stays rejected,
- * as does any number above 37.
+ * as does any number above 37
+ * -- except 39 = the RD estimate of the intra candidate with the NxN candidate (fhevc_intra_rd_nxn* with d_first4; without it the launch is slot 37's).
+ * 38 is not a slot: it stays rejected, as does any number above 39.
  * The tree that stops at a skip (fhevc_p_tree_select_skip_device), the tree that takes the intra candidate (fhevc_p_tree_select_intra_device) and the tree
  * on RD costs (fhevc_p_tree_select_rd_device) are timed under 17 */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);
