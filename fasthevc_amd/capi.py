@@ -52,6 +52,7 @@ SYMBOLS = [
     "fhevc_motion_rd_qt", "fhevc_motion_rd_qt_device", "fhevc_motion_rd_pu_qt", "fhevc_motion_rd_pu_qt_device", "fhevc_p_tree_rd_qt_frame",
     "fhevc_intra_rd_qt", "fhevc_intra_rd_qt_device", "fhevc_p_tree_rd_intra_qt_frame",
     "fhevc_intra_rd_nxn", "fhevc_intra_rd_nxn_device", "fhevc_p_tree_rd_intra_nxn_frame",
+    "fhevc_intra_search_rule_default", "fhevc_intra_rd_search", "fhevc_intra_rd_search_device", "fhevc_p_tree_rd_intra_search_frame",
 ]
 CNN_ARITH = {"i8": 8, "f16": 16}
 # where fhevc_p_depth_range_device / fhevc_p_predict_frame take the reference picture's depths from (FHEVC_P_PREV_*)
@@ -74,6 +75,15 @@ class PRule(C.Structure):
 class PuShapeRule(C.Structure):
     """fhevc_pu_shape_rule: margins per level (64, 32, 16, 8) and the AMP gate"""
     _fields_ = [("margin_q8", C.c_int32 * 4), ("margin_abs", C.c_int32 * 4), ("amp_mode", C.c_int32)]
+
+
+class IntraSearchRule(C.Structure):
+    """fhevc_intra_search_rule: list entries read per node of level 0..3 and per 4x4 PU, whether planar is appended; 8 bytes"""
+    _fields_ = [("count", C.c_uint8 * 4), ("count4", C.c_uint8), ("append_planar", C.c_uint8), ("pad", C.c_uint8 * 2)]
+
+
+# ... and the same eight bytes as a record
+INTRA_SEARCH_RULE_DTYPE = np.dtype([("count", np.uint8, (4,)), ("count4", np.uint8), ("append_planar", np.uint8), ("pad", np.uint8, (2,))])
 
 
 class PTreeRule(C.Structure):
@@ -330,6 +340,14 @@ def load_library(path=None):
         lib.fhevc_intra_rd_nxn_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp]
         lib.fhevc_p_tree_rd_intra_nxn_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), C.c_int, vp, vp, vp,
                                                         vp, vp, vp, vp, vp]
+    if path is None or hasattr(lib, "fhevc_intra_rd_search"):   # another build (A/B against the parent commit) may predate the candidate search
+        lib.fhevc_intra_search_rule_default.argtypes = [C.POINTER(IntraSearchRule)]
+        lib.fhevc_intra_search_rule_default.restype = None
+        lib.fhevc_intra_rd_search.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(IntraSearchRule), vp, vp, C.c_int, vp, vp]
+        lib.fhevc_intra_rd_search_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int,
+                                                     C.POINTER(IntraSearchRule), vp, vp, C.c_int, vp, vp, vp]
+        lib.fhevc_p_tree_rd_intra_search_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule),
+                                                           C.POINTER(IntraSearchRule), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.fhevc_p_tree_intra_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PuShapeRule), C.POINTER(PTreeRule), C.c_int, vp, vp, vp, vp, vp]
     lib.fhevc_predict_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, vp, vp]
     lib.fhevc_alloc_host.argtypes = [vp, C.c_size_t]
@@ -392,6 +410,19 @@ def pu_shape_rule(margin_q8=0, margin_abs=0, amp_mode=1):
     q8 = [margin_q8] * 4 if np.isscalar(margin_q8) else list(margin_q8)
     ab = [margin_abs] * 4 if np.isscalar(margin_abs) else list(margin_abs)
     return PuShapeRule((C.c_int32 * 4)(*q8), (C.c_int32 * 4)(*ab), amp_mode)
+
+
+def intra_search_rule_default():
+    r = IntraSearchRule()
+    load_library().fhevc_intra_search_rule_default(C.byref(r))
+    return r
+
+
+def intra_search_rule(count=(3, 3, 3, 8), count4=8, append_planar=1):
+    r = IntraSearchRule()
+    r.count[:] = list(count)
+    r.count4, r.append_planar = count4, append_planar
+    return r
 
 
 def p_tree_rule_default():
@@ -1028,6 +1059,41 @@ class Context:
         self._check(self.lib.fhevc_intra_rd_nxn_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, d_first, d_first4, d_fold, d_rd_merge,
                                                        skip_mask, d_out, d_nxn, stream))
 
+    def intra_rd_search(self, plane, modes, modes4=None, rule=None, fold=None, rd_merge=None, skip_mask=0, origin=0, stride=None, qp=32, with_nxn=False):
+        """intra_rd_nxn with the mode searched over the first pass's lists: modes [numCtus, 85, list_stride] uint8, modes4 [numCtus, 256, list_stride4] uint8 (None:
+        no NxN candidate); rule: an IntraSearchRule (None: the default) -> [numCtus, 85] MOTION_RD_PU_DTYPE (pad[1]: the winner's list position); with_nxn: and the
+        plain NxN candidates [numCtus, 64] INTRA_RD_NXN_DTYPE"""
+        flat = np.ascontiguousarray(plane).reshape(-1)
+        assert flat.dtype == np.int16
+        stride = stride if stride is not None else plane.shape[-1]
+        modes = np.ascontiguousarray(modes, np.uint8).reshape(self.num_ctus, NODES_PER_CTU, -1)
+        if modes4 is not None:
+            modes4 = np.ascontiguousarray(modes4, np.uint8).reshape(self.num_ctus, 256, -1)
+        arrays = []
+        for a in (fold, rd_merge):
+            if a is not None:
+                a = np.ascontiguousarray(a).reshape(-1)
+                assert a.dtype.itemsize == 16 and a.size == self.num_ctus * NODES_PER_CTU
+            arrays.append(a)
+        rule = rule if rule is not None else intra_search_rule_default()
+        out = np.zeros(self.num_ctus * NODES_PER_CTU, MOTION_RD_PU_DTYPE)
+        nxn = np.zeros(self.num_ctus * NXN_PER_CTU, INTRA_RD_NXN_DTYPE) if with_nxn else None
+        self._check(self.lib.fhevc_intra_rd_search(self.h, flat.ctypes.data + 2 * origin, stride, qp, modes.ctypes.data, modes.shape[2],
+                                                   modes4.ctypes.data if modes4 is not None else None, modes4.shape[2] if modes4 is not None else 0, C.byref(rule),
+                                                   *[a.ctypes.data if a is not None else None for a in arrays], skip_mask, out.ctypes.data,
+                                                   nxn.ctypes.data if with_nxn else None))
+        out = out.reshape(self.num_ctus, NODES_PER_CTU)
+        return (out, nxn.reshape(self.num_ctus, NXN_PER_CTU)) if with_nxn else out
+
+    def intra_rd_search_device(self, d_luma, sample_bytes, stride, frame_stride, num_frames, d_modes, list_stride, d_modes4, list_stride4, d_out, rule=None, d_nxn=None,
+                               d_fold=None, d_rd_merge=None, skip_mask=0, rows=None, stream=None, qp=32):
+        """intra_rd_nxn_device with the mode searched over the lists: d_modes num_frames * band CTUs * 85 * list_stride bytes, d_modes4 as many CTUs * 256 *
+        list_stride4 bytes or None; rule: an IntraSearchRule (None: the default), read before the call returns.  Asynchronous."""
+        rb, re = rows if rows is not None else (0, self.ctus_y)
+        rule = rule if rule is not None else intra_search_rule_default()
+        self._check(self.lib.fhevc_intra_rd_search_device(self.h, d_luma, sample_bytes, stride, frame_stride, num_frames, rb, re, qp, d_modes, list_stride, d_modes4,
+                                                          list_stride4, C.byref(rule), d_fold, d_rd_merge, skip_mask, d_out, d_nxn, stream))
+
     def motion_merge_pu(self, cur_plane, ref_plane, refined, origin=0, stride=None, qp=32, max_range=4, with_pus=True, with_small=True):
         """config 4: the cheapest merge candidate of every PU from the refined square nodes [numCtus, 85] (MOTION_QPEL_DTYPE; only cost_best, mvx, mvy are
         read) -> ([numCtus, 124], [numCtus, 384]) MOTION_MERGE_DTYPE in the orders of motion_pu_index / motion_pu_small_index; None for a family not asked for"""
@@ -1385,6 +1451,24 @@ class Context:
         self._check(self.lib.fhevc_p_tree_rd_intra_nxn_frame(self.h, cur, ref, stride, qp, search_range, coarse_range, C.byref(shape_rule) if shape_rule is not None else None,
                                                              C.byref(tree_rule) if tree_rule is not None else None, skip_mask, dmin.ctypes.data, dmax.ctypes.data,
                                                              *[a.ctypes.data if a is not None else None for a in arrays], nxn.ctypes.data if with_nxn else None))
+        out = (dmin.reshape(self.num_ctus, 256), dmax.reshape(self.num_ctus, 256))
+        for a in arrays:
+            out += (a.reshape(self.num_ctus, NODES_PER_CTU),) if a is not None else ()
+        return out + ((nxn.reshape(self.num_ctus, NXN_PER_CTU),) if with_nxn else ())
+
+    def p_tree_rd_intra_search_frame(self, cur_plane, ref_plane, origin=0, stride=None, qp=32, search_range=8, coarse_range=0, shape_rule=None, tree_rule=None, rule=None,
+                                     skip_mask=3, with_shapes=False, with_merge=False, with_rd_merge=False, with_rd_pu=False, with_first=False, with_nxn=False):
+        """p_tree_rd_intra_nxn_frame with both first passes' lists (8 candidates) and intra_rd_search under rule (None: the default) in intra_rd_nxn's place ->
+        that call's results"""
+        cur, ref, stride = self._pair(cur_plane, ref_plane, origin, stride)
+        dmin, dmax = np.zeros(self.num_ctus * 256, np.uint8), np.zeros(self.num_ctus * 256, np.uint8)
+        wanted = ((with_shapes, SHAPE_DTYPE), (with_merge, MOTION_MERGE_DTYPE), (with_rd_merge, MOTION_RD_DTYPE), (with_rd_pu, MOTION_RD_PU_DTYPE), (with_first, NODE_DTYPE))
+        arrays = [np.zeros(self.num_ctus * NODES_PER_CTU, dt) if want else None for want, dt in wanted]
+        nxn = np.zeros(self.num_ctus * NXN_PER_CTU, INTRA_RD_NXN_DTYPE) if with_nxn else None
+        self._check(self.lib.fhevc_p_tree_rd_intra_search_frame(self.h, cur, ref, stride, qp, search_range, coarse_range, C.byref(shape_rule) if shape_rule is not None else None,
+                                                                C.byref(tree_rule) if tree_rule is not None else None, C.byref(rule) if rule is not None else None, skip_mask,
+                                                                dmin.ctypes.data, dmax.ctypes.data, *[a.ctypes.data if a is not None else None for a in arrays],
+                                                                nxn.ctypes.data if with_nxn else None))
         out = (dmin.reshape(self.num_ctus, 256), dmax.reshape(self.num_ctus, 256))
         for a in arrays:
             out += (a.reshape(self.num_ctus, NODES_PER_CTU),) if a is not None else ()

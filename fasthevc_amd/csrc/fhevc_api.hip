@@ -189,6 +189,7 @@ int fhevc_kernel_timing(fhevc_ctx* c, int which, int reset, double* avg_ms, uint
   // of the tree, of the two merge stages, of the zero-residual test, of the re-pricing and of the intra stage (28; 29 is the RD estimate); 30 likewise, 31 is the RD estimate under a partition size; 32 likewise, 33 is the RD
   // estimate of the intra candidate; 34 likewise, 35 is the RD estimates at three TU depths: the first slot beside the table; 36 likewise, 37 is the RD estimate
   // of the intra candidate at three TU depths, beside the table too
+  if (which != 41)   // ... and 41 the same searched over the first pass's candidate lists; 40 and 42 likewise rejected
   if (which != 39)   // ... and 39 the RD estimate of the intra candidate with the NxN candidate; 38 and 40 likewise rejected
   if (which != 37)
   if (which != 35)

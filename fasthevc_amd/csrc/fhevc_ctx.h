@@ -60,8 +60,10 @@ struct fhevc_ctx {
   uint64_t launches_37 = 0;
   double sum_ms_39 = 0;        // slot 39 (... with the NxN candidate of the 8x8 nodes), beside the table as well: 38 is no slot
   uint64_t launches_39 = 0;
-  double& slot_ms(int which) { return which == 39 ? sum_ms_39 : which == 37 ? sum_ms_37 : which == 35 ? sum_ms_35 : sum_ms[which]; }
-  uint64_t& slot_launches(int which) { return which == 39 ? launches_39 : which == 37 ? launches_37 : which == 35 ? launches_35 : launches[which]; }
+  double sum_ms_41 = 0;        // slot 41 (... searched over the first pass's candidate lists), beside the table as well: 40 is no slot
+  uint64_t launches_41 = 0;
+  double& slot_ms(int which) { return which == 41 ? sum_ms_41 : which == 39 ? sum_ms_39 : which == 37 ? sum_ms_37 : which == 35 ? sum_ms_35 : sum_ms[which]; }
+  uint64_t& slot_launches(int which) { return which == 41 ? launches_41 : which == 39 ? launches_39 : which == 37 ? launches_37 : which == 35 ? launches_35 : launches[which]; }
   double* d_act = nullptr;
   int16_t* d_pair = nullptr;
   FhevcMotionNode *d_motion = nullptr, *d_motion_pu = nullptr, *d_motion_pu_small = nullptr, *d_centres = nullptr;

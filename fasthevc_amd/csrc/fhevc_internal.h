@@ -389,6 +389,13 @@ constexpr int kRdPartIntraNxN = 17;   // FHEVC_RD_PART_INTRA_NXN
 struct FhevcIntraRdNxN { uint32_t dist, cost_rd; uint16_t bits; uint8_t flags, cbf; uint8_t modes[4]; };
 hipError_t fhevc_launch_intra_rd_nxn(const FhevcFrames& fr, const FhevcRdQuant& q, const FhevcNodeCost* d_first, const FhevcNodeCost* d_first4, const FhevcMotionRdPuNode* d_fold,
                                      const FhevcMotionRdNode* d_rd_merge, int skip_mask, FhevcMotionRdPuNode* d_out, FhevcIntraRdNxN* d_nxn, int num_cus, hipStream_t stream);
+// ... with the mode searched over the first pass's lists (two further intra instances): d_modes the 85 entries of list_stride bytes per CTU, d_modes4 (may be
+// null: no NxN candidate, and d_nxn null) the 256 entries of list_stride4; the rule travels by value.  Step A over a node's list, best and second on the full
+// TU tree, the 4x4 PUs each on its own list.  ONE launch; counts within 1..stride or nothing is launched
+struct FhevcIntraSearchRule { uint8_t count[4], count4, append_planar, pad[2]; };
+hipError_t fhevc_launch_intra_rd_search(const FhevcFrames& fr, const FhevcRdQuant& q, const uint8_t* d_modes, int list_stride, const uint8_t* d_modes4, int list_stride4,
+                                        const FhevcIntraSearchRule& rule, const FhevcMotionRdPuNode* d_fold, const FhevcMotionRdNode* d_rd_merge, int skip_mask,
+                                        FhevcMotionRdPuNode* d_out, FhevcIntraRdNxN* d_nxn, int num_cus, hipStream_t stream);
 
 // ---- ... and of the PUs' vectors (k_motion_refine_pu.hip; config 4) --------------------------------------------------
 // fr, max_range (1 .. FHEVC_MOTION_WIDE_MAX_RANGE: up to FHEVC_MOTION_MAX_RANGE the MR = 8 layout, above it the MR = 64 layout with its window in dynamic LDS),

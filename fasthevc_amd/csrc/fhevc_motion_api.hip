@@ -146,6 +146,8 @@ int device_form(fhevc_ctx* c, bool args_ok, const char* bad_args, const Batch& b
 //   (fhevc_p_tree_rd_intra_frame)              fhevc_p_tree_rd_frame's buffers and the first-pass records of the current picture in the head of d_first_p
 //   (fhevc_intra_rd_nxn,                       fhevc_intra_rd's buffers, the 4x4 PUs' records behind the nodes' in d_first_p and the NxN records (64 per CTU) in the
 //    fhevc_p_tree_rd_intra_nxn_frame)          head of d_intra_p, which those chains do not use
+//   (fhevc_intra_rd_search,                    the same with the lists in the records' place: the nodes' in the head of d_first_p, the 4x4 PUs' where the 4x4
+//    fhevc_p_tree_rd_intra_search_frame)       records begin (the frame chain, which keeps the nodes' records: both lists there)
 //   d_first_p                341 (85 + 256)    the first-pass records of the nodes, behind them those of the 4x4 PUs (fhevc_intra_p, fhevc_p_tree_intra_frame)
 //   d_intra_p                85                the intra records made from them
 // fhevc_p_tree_intra_frame keeps its skip records in d_qpel: the re-pricing has read the refined nodes by then, and every later stage reads d_amvp
@@ -155,6 +157,7 @@ int device_form(fhevc_ctx* c, bool args_ok, const char* bad_args, const Batch& b
 // 21 the merge stage per PU, 23 the zero-residual test, 25 the re-pricing against neighbour predictors, 27 the intra stage, 29 the RD estimate, 31 the RD estimate under a partition size,
 // 33 the RD estimate of the intra candidate, 37 the RD estimate of the intra candidate at three TU depths (fhevc_intra_rd_qt* with tu_depths 3; at 2 it is slot 33's launch),
 // 39 the same with the NxN candidate of the 8x8 nodes (fhevc_intra_rd_nxn* with d_first4; without it, it is slot 37's launch),
+// 41 the same with the mode searched over the first pass's candidate lists (fhevc_intra_rd_search*),
 // 35 the RD estimates at three TU depths (fhevc_motion_rd_qt*, fhevc_motion_rd_pu_qt* with tu_depths 3; at 2 they are
 // the launches of slots 29 and 31)
 struct Family { int per_ctu; FhevcMotionNode* fhevc_ctx::*found; FhevcMotionQpelNode* fhevc_ctx::*refined; };
@@ -800,6 +803,93 @@ int fhevc_intra_rd_nxn(fhevc_ctx* c, const int16_t* luma, int stride_samples, in
   });
 }
 
+// ---- ... with the mode searched over the first pass's candidate lists (the search instances of k_motion_rd.hip) ----
+
+void fhevc_intra_search_rule_default(fhevc_intra_search_rule* rule)
+{
+  if (!rule) return;
+  // HM: 3 modes for PUs of 16 and above, 8 for 8x8 and 4x4 PUs (g_aucIntraModeNumFast_UseMPM), one MPM appended
+  *rule = fhevc_intra_search_rule{ { 3, 3, 3, 8 }, 8, 1, { 0, 0 } };
+}
+
+// what is wrong with a rule under the two strides (with4: the 4x4 lists are there), or null
+static const char* intra_search_rule_error(const fhevc_intra_search_rule& r, int list_stride, bool with4, int list_stride4)
+{
+  if (list_stride < 1 || list_stride > 8 || (with4 && (list_stride4 < 1 || list_stride4 > 8))) return "bad intra search arguments (list strides 1..8)";
+  for (int l = 0; l < 4; ++l)
+    if (r.count[l] < 1 || r.count[l] > list_stride) return "bad intra search rule (counts 1..list_stride)";
+  if (with4 && (r.count4 < 1 || r.count4 > list_stride4)) return "bad intra search rule (count4 1..list_stride4)";
+  if (r.append_planar > 1 || r.pad[0] || r.pad[1]) return "bad intra search rule (append_planar 0 / 1, pad 0)";
+  return nullptr;
+}
+
+int fhevc_intra_rd_search_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames,
+                                 int ctu_row_begin, int ctu_row_end, int qp, const uint8_t* d_modes, int list_stride, const uint8_t* d_modes4, int list_stride4,
+                                 const fhevc_intra_search_rule* rule, const fhevc_motion_rd_pu_node* d_fold, const fhevc_motion_rd_node* d_rd_merge, int skip_mask,
+                                 fhevc_motion_rd_pu_node* d_out, fhevc_intra_rd_nxn_node* d_nxn, void* stream)
+{
+  if (!c) return FHEVC_E_INVALID;
+  if (!d_luma || !d_modes || !rule || !d_out) return fail(c, FHEVC_E_INVALID, "bad intra search arguments (the planes, the lists, the rule, the output)");
+  if (d_nxn && !d_modes4) return fail(c, FHEVC_E_INVALID, "bad intra search arguments (the NxN records need the 4x4 PUs' lists)");
+  if (const char* bad = batch_error(c, sample_bytes, stride_samples, frame_stride_samples, num_frames, 1, ctu_row_begin, ctu_row_end, qp, false)) return fail(c, FHEVC_E_INVALID, bad);
+  if (skip_mask < 0 || skip_mask > 3) return fail(c, FHEVC_E_INVALID, "bad intra RD-stage arguments (skip_mask 0..3)");
+  if (const char* bad = intra_search_rule_error(*rule, list_stride, d_modes4 != nullptr, list_stride4)) return fail(c, FHEVC_E_INVALID, bad);
+  if (((uintptr_t)d_fold | (uintptr_t)d_rd_merge | (uintptr_t)d_out | (uintptr_t)d_nxn) & 3) return fail(c, FHEVC_E_INVALID, "bad intra RD-stage arguments (records are 4-byte aligned)");
+  const long long ctus = (long long)num_frames * (ctu_row_end - ctu_row_begin) * c->ctus_x;
+  if (ctus > 0x7FFFFFFFLL) return fail(c, FHEVC_E_INVALID, "more than 2^31 - 1 CTUs");
+  const uintptr_t extent = (uintptr_t)ctus * FHEVC_NODES * sizeof(fhevc_motion_rd_pu_node), f = (uintptr_t)d_fold, o = (uintptr_t)d_out;
+  if (d_fold && f != o && f < o + extent && o < f + extent) return fail(c, FHEVC_E_INVALID, "bad intra RD-stage arguments (fold overlaps the output without being it)");
+  const uintptr_t n = (uintptr_t)d_nxn, nn = (uintptr_t)ctus * 64 * sizeof(fhevc_intra_rd_nxn_node);
+  if (d_nxn) {
+    // the NxN records are written by other lanes than anything else is read or written by: no extent may touch theirs
+    const uintptr_t planes = (uintptr_t)(((long long)(num_frames - 1) * frame_stride_samples + (long long)(c->cfg.height - 1) * stride_samples + c->cfg.width) * sample_bytes);
+    const uintptr_t at[4] = { o, f, (uintptr_t)d_rd_merge, (uintptr_t)d_luma }, len[4] = { extent, extent, extent, planes };
+    for (int i = 0; i < 4; ++i)
+      if (at[i] && at[i] < n + nn && n < at[i] + len[i]) return fail(c, FHEVC_E_INVALID, "bad intra NxN RD-stage arguments (the NxN records overlap another array)");
+  }
+  // a list is read by every lane of its node through all the positions, an output record is written at the CTU's end: no list may touch an output
+  const uintptr_t lists[2] = { (uintptr_t)d_modes, (uintptr_t)d_modes4 };
+  const uintptr_t list_len[2] = { (uintptr_t)ctus * FHEVC_NODES * (uintptr_t)list_stride, d_modes4 ? (uintptr_t)ctus * FHEVC_PUS4_PER_CTU * (uintptr_t)list_stride4 : 0 };
+  for (int i = 0; i < 2; ++i) {
+    if (!lists[i]) continue;
+    if ((lists[i] < o + extent && o < lists[i] + list_len[i]) || (d_nxn && lists[i] < n + nn && n < lists[i] + list_len[i]))
+      return fail(c, FHEVC_E_INVALID, "bad intra search arguments (a list overlaps an output)");
+  }
+  if (ctu_row_begin == ctu_row_end) return FHEVC_OK;   // an empty band: nothing to launch, nothing written
+  const FhevcFrames fr = frames_of(c, d_luma, sample_bytes, stride_samples, frame_stride_samples, num_frames, ctu_row_begin, ctu_row_end, qp);
+  FhevcIntraSearchRule r;
+  static_assert(sizeof(fhevc_intra_search_rule) == 8 && sizeof(FhevcIntraSearchRule) == 8 && offsetof(fhevc_intra_search_rule, count4) == 4 &&
+                offsetof(fhevc_intra_search_rule, append_planar) == 5 && offsetof(FhevcIntraSearchRule, append_planar) == 5, "the search rule");
+  memcpy(&r, rule, sizeof r);   // by value with the launch: the caller's rule may change once the call has returned
+  return launch_on(c, stream, 41, "fhevc_launch_intra_rd_search", [&](hipStream_t s) {
+    return fhevc_launch_intra_rd_search(fr, fhevc_rd_quant(qp, c->cfg.bit_depth), d_modes, list_stride, d_modes4, list_stride4, r, kn(d_fold), kn(d_rd_merge), skip_mask, kn(d_out),
+                                        kn(d_nxn), c->num_cus, s);
+  });
+}
+
+int fhevc_intra_rd_search(fhevc_ctx* c, const int16_t* luma, int stride_samples, int qp, const uint8_t* modes, int list_stride, const uint8_t* modes4, int list_stride4,
+                          const fhevc_intra_search_rule* rule, const fhevc_motion_rd_pu_node* fold, const fhevc_motion_rd_node* rd_merge, int skip_mask,
+                          fhevc_motion_rd_pu_node* out, fhevc_intra_rd_nxn_node* nxn)
+{
+  const int rc = open_host_form(c, luma && modes && rule && out && skip_mask >= 0 && skip_mask <= 3, stride_samples, qp, 1, 1, "bad intra search arguments");
+  if (rc != GO) return rc;
+  if (nxn && !modes4) return fail(c, FHEVC_E_INVALID, "bad intra search arguments (the NxN records need the 4x4 PUs' lists)");   // said before anything is staged
+  if (const char* bad = intra_search_rule_error(*rule, list_stride, modes4 != nullptr, list_stride4)) return fail(c, FHEVC_E_INVALID, bad);
+  HostForm h(c);
+  const size_t bn = h.bytes(kNodes), b4 = (size_t)c->num_ctus * FHEVC_PUS4_PER_CTU * sizeof(fhevc_node_cost), bx = (size_t)c->num_ctus * 64 * sizeof(fhevc_intra_rd_nxn_node);
+  // the lists lie where fhevc_intra_rd_nxn keeps the first-pass records they stand for: the nodes' in the head of d_first_p, the 4x4 PUs' behind them (8 of the 16 bytes of an entry at the most)
+  const size_t ln = (size_t)c->num_ctus * FHEVC_NODES * list_stride, l4 = modes4 ? (size_t)c->num_ctus * FHEVC_PUS4_PER_CTU * list_stride4 : 0;
+  const uint8_t *d_modes = h.in(c->d_first_p, bn + b4, modes, ln), *d_modes4 = h.in(c->d_first_p, bn + b4, modes4, l4, bn);
+  const fhevc_motion_rd_node* d_rd_merge = h.in(c->d_qpel, bn, rd_merge, bn);
+  const fhevc_motion_rd_pu_node* d_fold = h.in(c->d_qpel_pu, h.bytes(kPus), fold, bn);   // folded in place on the device, as fhevc_intra_rd_qt does
+  fhevc_motion_rd_pu_node* d_out = h.out(c->d_qpel_pu, h.bytes(kPus), out, bn);
+  fhevc_intra_rd_nxn_node* d_nxn = h.out(c->d_intra_p, bn, nxn, bx);                     // 64 records of 16 bytes per CTU: the head of the intra records' buffer
+  return h.run(luma, nullptr, stride_samples, [&] {
+    return fhevc_intra_rd_search_device(c, c->d_pair + pair_plane(c), 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, d_modes, list_stride, d_modes4, list_stride4, rule, d_fold, d_rd_merge,
+                                        skip_mask, d_out, d_nxn, c->stream);
+  });
+}
+
 // ---- merge-candidate costs per PU from the refined nodes (k_motion_merge_pu.hip) ----
 
 int fhevc_motion_merge_pu_device(fhevc_ctx* c, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples,
@@ -1234,8 +1324,10 @@ int fhevc_intra_p(fhevc_ctx* c, int qp, const fhevc_node_cost* first, const fhev
 // folded in place)
 // (fhevc_p_tree_rd_intra_nxn_frame: nxn -- behind the first pass the 4x4 first pass of the current picture, best records only, and the intra stage with the NxN candidate
 // of the 8x8 nodes in the intra stage's place; nxn_out: where its NxN records go, or null)
+// (fhevc_p_tree_rd_intra_search_frame: search, with nxn -- both first passes give their lists at 8 candidates, into the dead 4x4 records' place behind the nodes'
+// records, and the search stage under that rule stands in the NxN stage's place)
 struct RdFrameOut { fhevc_motion_rd_node* rd_merge; fhevc_motion_rd_pu_node* rd_pu; bool intra; fhevc_node_cost* first; int tu_depths = 2; bool nxn = false;
-                    fhevc_intra_rd_nxn_node* nxn_out = nullptr; };
+                    fhevc_intra_rd_nxn_node* nxn_out = nullptr; const fhevc_intra_search_rule* search = nullptr; };
 static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
                            const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes,
                            bool with_merge, fhevc_motion_merge_node* merge, bool with_merge_pu = false, bool with_amvp = false, bool with_intra = false, int skip_mask = 0,
@@ -1252,6 +1344,8 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
     if (const char* bad = fhevc_p_tree_rule_error(*tree_rule)) return fail(c, FHEVC_E_INVALID, bad);
   if ((with_intra || with_rd) && (skip_mask < 0 || skip_mask > 3)) return fail(c, FHEVC_E_INVALID, "bad tree-decision frame arguments (skip_mask 0..3)");
   if (with_rd && with_rd->tu_depths != 2 && with_rd->tu_depths != 3) return fail(c, FHEVC_E_INVALID, kBadTuDepths);
+  if (with_rd && with_rd->search)
+    if (const char* bad = intra_search_rule_error(*with_rd->search, 8, true, 8)) return fail(c, FHEVC_E_INVALID, bad);
   HostForm h(c);
   const size_t map = (size_t)c->num_ctus * 256, records = h.bytes(kNodes);
   Chain k = claim_chain(h, coarse_range != 0);
@@ -1333,6 +1427,14 @@ static int p_tree_frame_on(fhevc_ctx* c, const int16_t* cur_luma, const int16_t*
         const int16_t* d_cur = c->d_pair + pair_plane(c);   // the current picture of the staged pair, as a batch of one frame
         rc = fhevc_intra_first_pass_device(c, d_cur, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, d_first_rd, c->stream);
         // intra last, as HM tries it after the inter sizes: the earlier record stays on a tie
+        if (rc == FHEVC_OK && with_rd->search) {
+          // the lists lie in the 4x4 records' place, which this chain leaves dead: the nodes' (680 B per CTU) and behind them the 4x4 PUs' (2 048 of the 4 096)
+          uint8_t* const d_lists = reinterpret_cast<uint8_t*>(d_first4_rd);
+          uint8_t* const d_lists4 = d_lists + (size_t)c->num_ctus * FHEVC_NODES * 8;
+          rc = fhevc_intra_first_pass_candidates_device(c, d_cur, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, 8, d_lists, c->stream);
+          if (rc == FHEVC_OK) rc = fhevc_intra_first_pass_4x4_device(c, d_cur, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, 8, nullptr, d_lists4, c->stream);
+          if (rc == FHEVC_OK) rc = fhevc_intra_rd_search_device(c, d_cur, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, d_lists, 8, d_lists4, 8, with_rd->search, d_rd_pu, d_rd_merge, skip_mask, d_rd_pu, d_nxn, c->stream);
+        } else
         if (rc == FHEVC_OK && with_rd->nxn) {
           rc = fhevc_intra_first_pass_4x4_device(c, d_cur, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, 0, d_first4_rd, nullptr, c->stream);
           if (rc == FHEVC_OK) rc = fhevc_intra_rd_nxn_device(c, d_cur, 2, c->dev_stride, 0, 1, 0, c->ctus_y, qp, d_first_rd, d_first4_rd, d_rd_pu, d_rd_merge, skip_mask, d_rd_pu, d_nxn, c->stream);
@@ -1432,6 +1534,18 @@ int fhevc_p_tree_rd_intra_nxn_frame(fhevc_ctx* c, const int16_t* cur_luma, const
                                     fhevc_node_cost* first, fhevc_intra_rd_nxn_node* nxn)
 {
   const RdFrameOut rd = { rd_merge, rd_pu, true, first, 3, true, nxn };
+  return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge, true, true,
+                         false, skip_mask, nullptr, &rd);
+}
+
+int fhevc_p_tree_rd_intra_search_frame(fhevc_ctx* c, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range, int coarse_range,
+                                       const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule, const fhevc_intra_search_rule* rule, int skip_mask,
+                                       uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge, fhevc_motion_rd_node* rd_merge,
+                                       fhevc_motion_rd_pu_node* rd_pu, fhevc_node_cost* first, fhevc_intra_rd_nxn_node* nxn)
+{
+  fhevc_intra_search_rule hm;
+  fhevc_intra_search_rule_default(&hm);
+  const RdFrameOut rd = { rd_merge, rd_pu, true, first, 3, true, nxn, rule ? rule : &hm };
   return p_tree_frame_on(c, cur_luma, ref_luma, stride_samples, qp, search_range, coarse_range, shape_rule, tree_rule, depth_min, depth_max, shapes, true, merge, true, true,
                          false, skip_mask, nullptr, &rd);
 }

@@ -181,11 +181,27 @@ __device__ __forceinline__ void rd_commit_nxn(unsigned* nx, int lane, int seg, u
   }
 }
 
+// the candidate search (fhevc_intra_rd_search*): the 4x4 PUs are priced one by one, so the sums of a 4-point COLS pass over the level-3 buffer stay per PU --
+// two words (level bits, max |c|) per unit of the CTU's 16x16 raster.  A 4x4 TU is one segment of four neighbouring rows: one lane holds it all, plain stores
+constexpr int kPuWords = 2;
+__device__ __forceinline__ void rd_commit_pu(unsigned* pw, int lane, int seg, unsigned bits, unsigned top)
+{
+#pragma unroll
+  for (int d = 1; d < 4; d <<= 1) {
+    bits += (unsigned)__shfl_xor((int)bits, d);
+    top = max(top, (unsigned)__shfl_xor((int)top, d));
+  }
+  if ((lane & 3) == 0) {
+    unsigned* const w = pw + kPuWords * ((lane >> 2) * 16 + seg);
+    w[0] = bits; w[1] = top;
+  }
+}
+
 // one pass over one buffer at TU size N: the thread's 16 outputs, packed two to a register until the barrier.  COLS quantises, prices and dequantises them
 // and commits the sums of every unit to its depth-0 TU: tu0 = the buffer's first, l0 = log2 of the buffer's depth-0 TU size (FINE: of its depth-1 TUs)
 // DST (the intra instances of three TU depths): a pass at N = 4 takes the DST matrix instead; the shifts and clips are the 4-point DCT's (xTrMxN, xITrMxN)
-// NXN: the pass over the level-3 buffer at N = 4 behind the NxN prediction; acc is the NxN words then
-template <int N, int STAGE, int DEPTH, bool FINE = false, bool DST = false, bool NXN = false>
+// NXN: the pass over the level-3 buffer at N = 4 behind the NxN prediction; acc is the NxN words then (PERPU: the candidate search's words per 4x4 PU)
+template <int N, int STAGE, int DEPTH, bool FINE = false, bool DST = false, bool NXN = false, bool PERPU = false>
 __device__ __forceinline__ void tu_pass(const short* tables, const short* buf, int lane, int wave, int bd, const FhevcRdQuant& Q, unsigned* acc, int tu0, int l0,
                                         unsigned (&t)[8])
 {
@@ -221,6 +237,7 @@ __device__ __forceinline__ void tu_pass(const short* tables, const short* buf, i
     }
     if constexpr (NXN) {
       static_assert(N == 4 && !FINE, "the NxN candidate is four 4x4 TUs");
+      if constexpr (PERPU) { if (STAGE == COLS) rd_commit_pu(acc, lane, seg, bits, top); } else
       if (STAGE == COLS) rd_commit_nxn(acc, lane, seg, bits, top);
     } else
     if (STAGE == COLS) {
@@ -390,6 +407,67 @@ __device__ __forceinline__ void rd_depth(short* s, int lane, int lvl, int wave, 
   __syncthreads();   // the tiles are read: the next depth rewrites them; the sums are in
 }
 
+// the candidate search (fhevc_intra_rd_search*): ONE position of the 4x4 PUs' lists -- the level-3 wave's tiles (four PUs each, every one predicted at its own
+// candidate: D is that residual) into the level-3 buffer, the four passes over that buffer ALONE at N = 4 with the DST by all four waves, the sums per PU in pw;
+// the lanes of the level-3 wave come back with the squared error of their tile's four PUs (fhevc_intra_p's order), the others with nothing
+template <int STAGE>
+__device__ __forceinline__ void rd_pu_stage(short* s, int lane, int wave, int bd, const FhevcRdQuant& Q, unsigned* pw)
+{
+  unsigned t3[8];
+  tu_pass<4, STAGE, 2, false, true, true, true>(s + kTransformShorts, s + 3 * kLevelBuf, lane, wave, bd, Q, pw, 0, 0, t3);
+  __syncthreads();   // every thread has read
+  tu_store<4, STAGE>(s + 3 * kLevelBuf, lane, wave, t3);
+  __syncthreads();
+}
+template <typename T>
+__device__ __forceinline__ void rd_pu_pass(short* s, int lane, int wave, int tx, int ty, const FhevcRdQuant& Q, unsigned* pw, const T* plane, long long cur_base,
+                                           const FhevcFrames& F, int px, int py, bool inside, const unsigned (&D)[32], unsigned (&sse)[4])
+{
+  const int bd = F.bit_depth;
+  short* const tile = s + 3 * kLevelBuf + (ty * 8) * kPitch + tx * 8;
+  if (wave == 3) {   // wave-uniform
+#pragma unroll
+    for (int y = 0; y < 8; ++y) *reinterpret_cast<uint4*>(tile + y * kPitch) = make_uint4(D[4 * y], D[4 * y + 1], D[4 * y + 2], D[4 * y + 3]);
+  }
+  __syncthreads();
+  rd_pu_stage<ROWS>(s, lane, wave, bd, Q, pw);
+  rd_pu_stage<COLS>(s, lane, wave, bd, Q, pw);
+  rd_pu_stage<INV1>(s, lane, wave, bd, Q, pw);
+  rd_pu_stage<INV2>(s, lane, wave, bd, Q, pw);
+  sse[0] = sse[1] = sse[2] = sse[3] = 0u;
+  if (wave != 3) return;   // the tiles are the level-3 wave's own, read and rewritten by the lane that holds them: no barrier behind this
+  const int top = (1 << bd) - 1, sh = 2 * (bd - 8);
+  unsigned O[32];
+  load_tile8x8(plane, cur_base, F, px, py, inside, O);
+#pragma unroll
+  for (int y = 0; y < 8; ++y) {
+    const uint4 q = *reinterpret_cast<const uint4*>(tile + y * kPitch);
+    const unsigned r[4] = { q.x, q.y, q.z, q.w };
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const unsigned o = O[4 * y + k], p = pk_sub(o, D[4 * y + k]);   // the prediction: original minus residual
+      const int e0 = (int)(o & 0xFFFFu) - min(max((int)(p & 0xFFFFu) + (int)(short)(r[k] & 0xFFFFu), 0), top);
+      const int e1 = (int)(o >> 16) - min(max((int)(p >> 16) + (int)(short)(r[k] >> 16), 0), top);
+      sse[(y >> 2) * 2 + (k >> 1)] += ((unsigned)(e0 * e0) >> sh) + ((unsigned)(e1 * e1) >> sh);
+    }
+  }
+}
+
+// bits(m) of fhevc_intra_p: planar 2, DC and vertical 3, every other mode 6 (the search instances' code; the instances there were keep their own expression)
+__device__ __forceinline__ unsigned intra_mode_bits(unsigned m) { return m == 0u ? 2u : (m == 1u || m == 26u) ? 3u : 6u; }
+
+// the candidate at position pos of the list whose entry begins at e: the byte there while pos < count (255 where it is above 34: skipped); at pos == count the
+// appended planar -- iff append, the first count bytes hold a valid mode and none of them is 0 --; 255 behind that.  count <= the entry's stride, and no byte
+// reaches an address or a loop bound
+__device__ __forceinline__ unsigned search_cand(const unsigned char* __restrict__ e, int count, int append, int pos)
+{
+  if (pos < count) { const unsigned b = e[pos]; return b <= 34u ? b : 255u; }
+  if (pos > count || !append) return 255u;
+  bool any = false, zero = false;
+  for (int i = 0; i < count; ++i) { const unsigned b = e[i]; any = any || b <= 34u; zero = zero || b == 0u; }
+  return any && !zero ? 0u : 255u;
+}
+
 // ---- the PU instances: what one lane knows of its node's partition size ----
 struct RdPuArgs {
   const unsigned *pus, *small;               // the refined (or re-priced) entries of the 124 and of the 384 PUs; small may be null
@@ -464,6 +542,9 @@ __device__ __forceinline__ RdPuLane rd_pu_lane(const RdPuArgs& A, long long oc, 
 
 struct RdThreeDepths {};   // a tag in the kernel's argument pack: it carries nothing
 struct RdNxN { const unsigned* first4; unsigned* nxn; };   // the second tag of the intra instances: the 4x4 first pass's records as dwords, the plain NxN records (or null)
+// the third tag (fhevc_intra_rd_search*), behind RdThreeDepths in RdNxN's place: the node lists (85 entries of stride bytes per CTU), the 4x4 PUs' lists (256 of
+// stride4; or null), the plain NxN records (or null) and the rule: count[l] in byte l of counts
+struct RdSearch { const unsigned char *modes, *modes4; unsigned* nxn; int stride, stride4; unsigned counts; int count4, append; };
 // where the tag stands in front of the PU arguments, the comma fold that picks the pack's last argument drops it: that is what it is for
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-value"
@@ -773,6 +854,58 @@ __device__ __forceinline__ unsigned nxn_modes(const unsigned* __restrict__ first
   return ok ? m : 0x80000000u;
 }
 
+// the candidate search: the record of a valid node at mode m from the sums as they stand -- what the writer lane of the instances of three TU depths makes of
+// them, word for word (s_t: the transform buffers with the sums per depth-1 TU behind the matrices; nfirst, nbx, nby: the node's level's first node and its
+// place in the level's raster); the answer is the unshifted J
+__device__ __forceinline__ unsigned long long intra_search_record(const short* s_t, const unsigned* s_acc, const FhevcRdQuant& Q, int lvl, int nidx, int nfirst, int nbx, int nby, int m,
+                                                                   FhevcMotionRdPuNode& u)
+{
+    const int qi = lvl == 3 ? 1 : (lvl == 2 ? 2 : 3);                // the depth-0 TU size's numbers
+    const int tu0 = lvl == 0 ? 0 : (lvl == 1 ? 4 : lvl == 2 ? 8 : 24) + (nidx - nfirst), ntu = lvl == 0 ? 4 : 1;   // a 64x64 node: four TUs
+    const unsigned side = intra_mode_bits((unsigned)m);
+    unsigned long long j = (unsigned long long)Q.lam_q8 * side, bits = side;
+    unsigned dist = 0, top = 0, any0 = 0, split = 0;
+    if (lvl == 1 || lvl == 2) {
+      // HM's intra recursion over three depths (TEncSearch.cpp:1610-1661), bottom-up: per depth-1 TU its own cost with its split flag against its four
+      // children, then the depth-0 TU against the four results; dSplitCost < dSingleCost alone at both depths
+      const unsigned lam = Q.lam_q8;
+      const unsigned* const fine = reinterpret_cast<const unsigned*>(s_t + kTransformShorts + kFwdShorts + kInvShorts);
+      const unsigned* a = &s_acc[kAccWords * tu0];
+      const int e0 = lvl == 1 ? (2 * nby) * 4 + 2 * nbx : 16 + (2 * nby) * 8 + 2 * nbx, row = lvl == 1 ? 4 : 8;   // the node's first depth-1 TU
+      const unsigned d0 = a[0], r0 = 1u + a[1];
+      const unsigned long long j0 = 256ull * d0 + (unsigned long long)lam * (1u + r0);
+      unsigned long long j1 = lam;
+      unsigned dsub = 0, rsub = 0, s1 = 0;
+      for (int i = 0; i < 4; ++i) {
+        const unsigned* b = &fine[kFineWords * (e0 + (i >> 1) * row + (i & 1))];
+        const unsigned d1 = b[0], r1 = 1u + b[1], d2 = b[2], r2 = 4u + b[3];
+        const unsigned long long k1 = 256ull * d1 + (unsigned long long)lam * (1u + r1), k2 = 256ull * d2 + (unsigned long long)lam * (1u + r2);
+        const bool take1 = k2 < k1;
+        j1 += take1 ? k2 : k1; dsub += take1 ? d2 : d1; rsub += 1u + (take1 ? r2 : r1);
+        s1 |= take1 ? 16u << i : 0u;
+      }
+      const bool take = j1 < j0;
+      j += take ? j1 : j0; dist = take ? dsub : d0; bits += 1u + (take ? rsub : r0);
+      split = take ? 1u | s1 : 0u; any0 = a[1]; top = a[4];
+    } else
+    for (int i = 0; i < ntu; ++i) {
+      const unsigned* a = &s_acc[kAccWords * (tu0 + i)];
+      const unsigned d0 = a[0], r0 = 1u + a[1], d1 = a[2], r1 = 4u + a[3];
+      const unsigned long long j0 = 256ull * d0 + (unsigned long long)Q.lam_q8 * (1u + r0), j1 = 256ull * d1 + (unsigned long long)Q.lam_q8 * (1u + r1);
+      const bool take = j1 < j0;                  // dSplitCost < dSingleCost alone (TEncSearch.cpp:1661)
+      j += take ? j1 : j0; dist += take ? d1 : d0; bits += 1u + (take ? r1 : r0);
+      split |= take ? 1u << i : 0u; any0 |= a[1]; top = max(top, a[4]);
+    }
+    const bool zero_half = ((top * Q.scale + Q.add_half[qi]) >> Q.qbits[qi]) == 0u;
+    const unsigned long long unshifted = j;
+    j >>= 8;
+    u.dist = dist; u.cost_rd = j < 0xFFFFFFFEull ? (unsigned)j : 0xFFFFFFFEu;
+    u.bits = (uint16_t)(bits < 65535ull ? bits : 65535ull);
+    u.flags = (uint8_t)((any0 == 0u ? 1 : 0) | (zero_half ? 2 : 0) | (split ? 4 : 0)); u.tu_split = (uint8_t)split;
+    u.part = kRdPartIntra; u.pad[0] = (uint8_t)m;
+    return unshifted;
+}
+
 // T = int16_t or uint8_t planes.  first: the first pass's records as dwords (satd, mode, the cost's two); fold / rd_merge: RD records as dwords, or null;
 // fold may be out (the writer lane reads its record, then writes it)
 // Three TU depths (fhevc_intra_rd_qt* at tu_depths 3): RdThreeDepths as the pack -- the 32x32 and 16x16 nodes get their third TU size, the 8x8 nodes their
@@ -787,7 +920,13 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
   using namespace ird;
   constexpr bool QT = (std::is_same_v<A, RdThreeDepths> || ...);
   constexpr bool NXN = (std::is_same_v<A, RdNxN> || ...);
-  static_assert(sizeof...(A) == (QT ? 1 : 0) + (NXN ? 1 : 0) && (QT || !NXN), "the pack is empty, the tag of three TU depths, or that tag and the NxN arguments behind it");
+  constexpr bool SEARCH = (std::is_same_v<A, RdSearch> || ...);
+  static_assert(sizeof...(A) == (QT ? 1 : 0) + (NXN ? 1 : 0) + (SEARCH ? 1 : 0) && (QT || !(NXN || SEARCH)) && !(NXN && SEARCH),
+                "the pack is empty, the tag of three TU depths, or that tag and the NxN arguments or the search's behind it");
+  // SEARCH: behind the sums the words of the search -- per 4x4 PU the sums of the position in hand (kPuWords) and its best so far (D, r | mode << 16, max |c|);
+  // per node best and second of step A (the two A in 64 bits; mode and position of each in one word, mode 255: none) and F(best) with its unshifted J
+  constexpr int kPuAt = kAccWords * kTus, kPuBestAt = kPuAt + kPuWords * 256, kNodeAt = kPuBestAt + 3 * 256, kRecAt = kNodeAt + 5 * FHEVC_NODES;
+  constexpr int kSearchWords = kPuWords * 256 + 3 * 256 + 5 * FHEVC_NODES + 6 * FHEVC_NODES;   // 8 860 B: 80 532 B of static LDS in all
   // the transform buffers (under them, first, the staged CTU) and the matrices; QT: behind them the sums per depth-1 TU, the DST, the 4x4 lines and their DC values
   __shared__ __attribute__((aligned(16))) short s_t[kTransformShorts + kFwdShorts + kInvShorts + (QT ? kQtShorts : 0)];
   __shared__ short s_refbuf[kLinePad + kLineTotal + kLinePad + 1];   // unfiltered lines: line[2 n] the corner, + i above, - j left
@@ -795,7 +934,7 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
   __shared__ short s_above[132], s_left[64], s_tab[18];
   __shared__ int s_dc[FHEVC_NODES];
   __shared__ unsigned char s_av[kUnits + 3], s_valid[FHEVC_NODES];
-  __shared__ unsigned s_acc[kAccWords * kTus + (NXN ? kNxnWords * 64 : 0)];   // NXN: behind the sums, the candidate's three words per 8x8 node
+  __shared__ unsigned s_acc[kAccWords * kTus + (NXN ? kNxnWords * 64 : 0) + (SEARCH ? kSearchWords : 0)];   // NXN: behind the sums, the candidate's three words per 8x8 node
   static_assert(kTransformShorts >= 64 * 64, "the staged CTU lies under the transform buffers");
   short* const s_org = s_t;
   short* const s_ref = s_refbuf + kLinePad;
@@ -833,7 +972,8 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
     const long long rec = ((long long)(f * band_rows + (cy - F.row_begin)) * F.ctus_x + cx) * FHEVC_NODES + nidx;
     // ---- the node's input record: satd and the low byte of mode; nothing of it reaches an address ----
     const bool node_in = cx * N.ncnt + N.nbx < gw && cy * N.ncnt + N.nby < gh;
-    const unsigned rsatd = first[rec * 4], rmode = first[rec * 4 + 1] & 0xFFu;
+    unsigned rsatd = kRdMark, rmode = 0;   // SEARCH: there are no records -- the modes come from the lists, position by position, and validity with them
+    if constexpr (!SEARCH) { rsatd = first[rec * 4]; rmode = first[rec * 4 + 1] & 0xFFu; }
     const bool valid = node_in && rsatd != kRdMark && rmode <= 34u;
     const int mode = valid ? (int)rmode : 0;   // an invalid node predicts with mode 0 and drops the result
     __syncthreads();   // the previous CTU's readers of the buffers and of the sums are done
@@ -846,6 +986,10 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
     for (int i = tid; i < kAccWords * kTus; i += 256) s_acc[i] = 0;
     if constexpr (NXN)
       if (tid < kNxnWords * 64) s_acc[kAccWords * kTus + tid] = 0;
+    if constexpr (SEARCH) {
+      s_acc[kPuBestAt + 3 * tid] = 0u; s_acc[kPuBestAt + 3 * tid + 1] = 255u << 16; s_acc[kPuBestAt + 3 * tid + 2] = 0u;   // no PU has a mode yet
+      if (tid < FHEVC_NODES) s_acc[kNodeAt + 5 * tid + 4] = 0x00FF00FFu;                                                  // ... and no node a best or a second
+    }
     if constexpr (QT)
       for (int i = tid; i < kFineTus * kFineWords; i += 256) reinterpret_cast<unsigned*>(s_t + kTransformShorts + kFwdShorts + kInvShorts)[i] = 0u;
     __syncthreads();
@@ -973,15 +1117,89 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
     const bool inside = (px + 8 <= F.width) && (py + 8 <= F.height);
     __syncthreads();   // the lines stand; the staged CTU is dead: the transform buffers lie over it
     // ---- per TU depth: this lane's tile predicted at its node's mode from the line of the TU that holds it, the residual through the passes ----
+    // ---- SEARCH: what the rule gives this launch (uniform) and this wave; the positions of the 4x4 PUs' lists, in passes of their own over the level-3 buffer ----
+    int npos = 0, runs = 1, my_count = 0;
+    if constexpr (SEARCH) {
+      const RdSearch S = (tag, ...);   // the pack's last argument
+      const int c0 = S.counts & 0xFF, c1 = (S.counts >> 8) & 0xFF, c2 = (S.counts >> 16) & 0xFF, c3 = S.counts >> 24;
+      npos = max(max(c0, c1), max(c2, c3)) + S.append;   // 9 at the most
+      runs = npos > 1 ? 2 : 1;                           // one position: nothing can be second
+      my_count = wave == 0 ? c0 : wave == 1 ? c1 : wave == 2 ? c2 : c3;
+      const int n4 = S.modes4 ? S.count4 + S.append : 0;
+      const long long ctu = (long long)(f * band_rows + (cy - F.row_begin)) * F.ctus_x + cx;   // compact over the band
 #pragma unroll 1
-    for (int depth = 0; depth < (QT ? 3 : 2); ++depth) {
+      for (int pos = 0; pos < n4; ++pos) {
+        unsigned D[32], m4 = 0;
+#pragma unroll
+        for (int i = 0; i < 32; ++i) D[i] = 0u;
+        if (wave == 3) {
+          const unsigned char* const e4 = S.modes4 + (ctu * 256 + (2 * ty) * 16 + 2 * tx) * S.stride4;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) m4 |= search_cand(e4 + ((i >> 1) * 16 + (i & 1)) * S.stride4, S.count4, S.append, pos) << (8 * i);
+          const short* l4 = s_t + kLines4At + ((2 * ty) * 16 + 2 * tx) * kLine4 + 8;
+          const short* d4 = s_t + kDc4At + (2 * ty) * 16 + 2 * tx;
+          const auto pm = [&](int i) { const unsigned m = (m4 >> (8 * i)) & 0xFFu; return m <= 34u ? (int)m : 0; };   // a PU without a candidate here predicts with mode 0
+          predict_tile<4, 0, 0>(l4, s_tab, 4, 2, 0, 0, pm(0), d4[0], maxval, D);
+          predict_tile<4, 4, 0>(l4 + kLine4, s_tab, 4, 2, 0, 0, pm(1), d4[1], maxval, D);
+          predict_tile<4, 0, 4>(l4 + 16 * kLine4, s_tab, 4, 2, 0, 0, pm(2), d4[16], maxval, D);
+          predict_tile<4, 4, 4>(l4 + 17 * kLine4, s_tab, 4, 2, 0, 0, pm(3), d4[17], maxval, D);
+          unsigned O[32];
+          load_tile8x8(plane, base, F, px, py, inside, O);
+#pragma unroll
+          for (int i = 0; i < 32; ++i) D[i] = pk_sub(O[i], D[i]);
+        }
+        unsigned sse[4];
+        rd_pu_pass(s_t, lane, wave, tx, ty, Q, &s_acc[kPuAt], plane, base, F, px, py, inside, D, sse);
+        if (wave == 3) {
+          // per PU: 256 D + lam (r + bits(m)) against its best so far, strictly below in list order; r = 1 + the level bits
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int unit = (2 * ty + (i >> 1)) * 16 + 2 * tx + (i & 1);
+            const unsigned m = (m4 >> (8 * i)) & 0xFFu, lv = s_acc[kPuAt + kPuWords * unit], top = s_acc[kPuAt + kPuWords * unit + 1];
+            unsigned* const pb = &s_acc[kPuBestAt + 3 * unit];
+            const unsigned bm = (pb[1] >> 16) & 0xFFu, blv = pb[1] & 0xFFFFu;
+            const unsigned side = intra_mode_bits(m), bside = intra_mode_bits(bm);
+            const unsigned long long j = 256ull * sse[i] + (unsigned long long)Q.lam_q8 * (1u + lv + side), jb = 256ull * pb[0] + (unsigned long long)Q.lam_q8 * (1u + blv + bside);
+            if (node_in && m <= 34u && (bm == 255u || j < jb)) { pb[0] = sse[i]; pb[1] = lv | m << 16; pb[2] = top; }
+          }
+        }
+      }
+    }
+#pragma unroll 1
+    for (int ph = 0; ph < (SEARCH ? npos + 3 * runs : QT ? 3 : 2); ++ph) {
+      int depth = ph, md = mode;
+      [[maybe_unused]] int run = 0, pos = 0;        // SEARCH: the phases are the positions of step A (depth 0 alone), then the three depths at the best and at the second mode
+      [[maybe_unused]] unsigned cand = 255u;
+      if constexpr (SEARCH) {
+        const RdSearch S = (tag, ...);
+        const bool step_a = ph < npos;
+        run = step_a ? 0 : (ph - npos >= 3 ? 1 : 0);
+        depth = step_a ? 0 : ph - npos - 3 * run;
+        pos = step_a ? ph : -1;
+        if (step_a) {
+          const long long ctu = (long long)(f * band_rows + (cy - F.row_begin)) * F.ctus_x + cx;
+          cand = search_cand(S.modes + (ctu * FHEVC_NODES + nidx) * S.stride, my_count, S.append, ph);
+          md = cand <= 34u ? (int)cand : 0;   // a node without a candidate here predicts with mode 0 and drops the result
+        } else {
+          if (depth == 0) {
+            __syncthreads();   // the writer lanes' words of step A (of the first run) stand; the sums are read
+            if (run == 1) {
+              for (int i = tid; i < kAccWords * kTus; i += 256) s_acc[i] = 0;
+              for (int i = tid; i < kFineTus * kFineWords; i += 256) reinterpret_cast<unsigned*>(s_t + kTransformShorts + kFwdShorts + kInvShorts)[i] = 0u;
+              __syncthreads();
+            }
+          }
+          const unsigned m = (s_acc[kNodeAt + 5 * nidx + 4] >> (16 * run)) & 0xFFu;
+          md = m <= 34u ? (int)m : 0;
+        }
+      }
       const int L = min(max(wave, 1) + depth, 3);        // the TU's level (wave 3 has no depth 1: its depth-0 TU again, dropped by the writer)
       const bool four = QT && max(wave, 1) + depth == 4;  // three depths: the 4x4 TUs, four to a tile, each with its own line -- L is not used then
       const int n = 64 >> L, lg = 6 - L;
       const int ni = ((ty >> (3 - L)) << L) + (tx >> (3 - L));
       const int bx = (tx * 8) & (n - 1), by = (ty * 8) & (n - 1);
       const int thr = L == 1 ? 0 : (L == 2 ? 1 : 7);     // m_aucIntraFilter of 32, 16, 8
-      const bool use_flt = mode != 1 && min(abs(mode - 10), abs(mode - 26)) > thr;
+      const bool use_flt = md != 1 && min(abs(md - 10), abs(md - 26)) > thr;
       const short* ref = (use_flt ? s_flt : s_ref) + line_off(L) + ni * (4 * n + 1) + 2 * n;
       unsigned D[32];
       if (QT && depth == 2 && wave != 1 && wave != 2) {
@@ -991,12 +1209,12 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
       } else if (four) {
         const short* l4 = s_t + kLines4At + ((2 * ty) * 16 + 2 * tx) * kLine4 + 8;   // the tile's first 4x4 block: its line's corner
         const short* d4 = s_t + kDc4At + (2 * ty) * 16 + 2 * tx;
-        predict_tile<4, 0, 0>(l4, s_tab, 4, 2, 0, 0, mode, d4[0], maxval, D);
-        predict_tile<4, 4, 0>(l4 + kLine4, s_tab, 4, 2, 0, 0, mode, d4[1], maxval, D);
-        predict_tile<4, 0, 4>(l4 + 16 * kLine4, s_tab, 4, 2, 0, 0, mode, d4[16], maxval, D);
-        predict_tile<4, 4, 4>(l4 + 17 * kLine4, s_tab, 4, 2, 0, 0, mode, d4[17], maxval, D);
+        predict_tile<4, 0, 0>(l4, s_tab, 4, 2, 0, 0, md, d4[0], maxval, D);
+        predict_tile<4, 4, 0>(l4 + kLine4, s_tab, 4, 2, 0, 0, md, d4[1], maxval, D);
+        predict_tile<4, 0, 4>(l4 + 16 * kLine4, s_tab, 4, 2, 0, 0, md, d4[16], maxval, D);
+        predict_tile<4, 4, 4>(l4 + 17 * kLine4, s_tab, 4, 2, 0, 0, md, d4[17], maxval, D);
       } else
-      predict_tile(ref, s_tab, n, lg, bx, by, mode, s_dc[node_off(L) + ni], maxval, D);
+      predict_tile(ref, s_tab, n, lg, bx, by, md, s_dc[node_off(L) + ni], maxval, D);
       if (!(QT && depth == 2 && wave != 1 && wave != 2)) {
         unsigned O[32];
         load_tile8x8(plane, base, F, px, py, inside, O);
@@ -1023,11 +1241,58 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
       if (depth == 0) rd_depth<0, T, QT, QT>(s_t, lane, lvl, wave, tx, ty, Q, s_acc, plane, base, F, px, py, inside, D);
       else if (!QT || depth == 1) rd_depth<1, T, QT, QT>(s_t, lane, lvl, wave, tx, ty, Q, s_acc, plane, base, F, px, py, inside, D);
       else if constexpr (QT) rd_depth<2, T, QT, QT, NXN>(s_t, lane, lvl, wave, tx, ty, Q, s_acc, plane, base, F, px, py, inside, D);
+      if constexpr (SEARCH) {
+        if (N.writer) {
+          unsigned* const nw = &s_acc[kNodeAt + 5 * nidx];
+          unsigned* const rw = &s_acc[kRecAt + 6 * nidx];
+          if (pos >= 0) {
+            // step A (bCheckFirst): A_c = the depth-0 TUs' J0 + lam bits(m_c); best and second as HM keeps them.  The sums that the next position adds
+            // to are cleared here, by the lane that read them (the distortion is a plain store)
+            const int tu0 = lvl == 0 ? 0 : (lvl == 1 ? 4 : lvl == 2 ? 8 : 24) + (nidx - N.first), ntu = lvl == 0 ? 4 : 1;
+            unsigned long long a_c = (unsigned long long)Q.lam_q8 * intra_mode_bits((unsigned)md);
+            for (int i = 0; i < ntu; ++i) {
+              unsigned* const a = &s_acc[kAccWords * (tu0 + i)];
+              a_c += 256ull * a[0] + (unsigned long long)Q.lam_q8 * (2u + a[1]);
+              a[1] = 0u; a[4] = 0u;
+            }
+            if (node_in && cand <= 34u) {
+              const unsigned info = nw[4];
+              const unsigned long long best = (unsigned long long)nw[1] << 32 | nw[0], second = (unsigned long long)nw[3] << 32 | nw[2];
+              const unsigned me = cand | (unsigned)pos << 8;
+              if ((info & 0xFFu) == 255u || a_c < best) {   // strictly below the best: it becomes the best and the old best the second
+                nw[2] = nw[0]; nw[3] = nw[1]; nw[0] = (unsigned)a_c; nw[1] = (unsigned)(a_c >> 32); nw[4] = me | info << 16;
+              } else if (((info >> 16) & 0xFFu) == 255u || a_c < second) {   // otherwise strictly below the second: it becomes the second
+                nw[2] = (unsigned)a_c; nw[3] = (unsigned)(a_c >> 32); nw[4] = (info & 0xFFFFu) | me << 16;
+              }
+            }
+          } else if (depth == 2) {
+            // step B: F(best) is kept with its unshifted J; F(second) takes its place iff there is a second and its J is strictly smaller
+            const unsigned who = (nw[4] >> (16 * run)) & 0xFFFFu;
+            FhevcMotionRdPuNode r;
+            r.dist = r.cost_rd = kRdMark; r.bits = 0xFFFFu; r.flags = 0; r.tu_split = 0; r.part = 255; r.merged = 0; r.pad[0] = r.pad[1] = 0;
+            unsigned long long j = ~0ull;
+            if (node_in && (who & 0xFFu) <= 34u) { j = intra_search_record(s_t, s_acc, Q, lvl, nidx, N.first, N.nbx, N.nby, (int)(who & 0xFFu), r); r.pad[1] = (uint8_t)(who >> 8); }
+            const unsigned long long kept = (unsigned long long)rw[5] << 32 | rw[4];
+            if (run == 0 || j < kept) {   // a node without a second has all ones there: below nothing
+              unsigned w[4];
+              __builtin_memcpy(w, &r, 16);
+              rw[0] = w[0]; rw[1] = w[1]; rw[2] = w[2]; rw[3] = w[3]; rw[4] = (unsigned)j; rw[5] = (unsigned)(j >> 32);
+            }
+          }
+        }
+      }
     }
     if (N.writer) {
       FhevcMotionRdPuNode u;
       u.dist = u.cost_rd = kRdMark; u.bits = 0xFFFFu; u.flags = 0; u.tu_split = 0; u.part = 255; u.merged = 0; u.pad[0] = u.pad[1] = 0;
       const FhevcMotionRdPuNode none = u;
+      if constexpr (SEARCH) {
+        unsigned w[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w[i] = s_acc[kRecAt + 6 * nidx + i];
+        __builtin_memcpy(&u, w, 16);   // the marker where the node lies outside or its list is empty
+      } else
+      // (intra_search_record above is this block at three depths, word for word, for the search instances: a change here is a change there)
       if (valid) {
         const int qi = lvl == 3 ? 1 : (lvl == 2 ? 2 : 3);                // the depth-0 TU size's numbers
         const int tu0 = lvl == 0 ? 0 : (lvl == 1 ? 4 : lvl == 2 ? 8 : 24) + (nidx - N.first), ntu = lvl == 0 ? 4 : 1;   // a 64x64 node: four TUs
@@ -1103,13 +1368,45 @@ __global__ __launch_bounds__(256) void fhevc_intra_rd_kernel(FhevcFrames F, Fhev
           }
         }
       }
+      if constexpr (SEARCH) {
+        const RdSearch S = (tag, ...);
+        if (lvl == 3 && S.modes4) {
+          // the NxN candidate over the four PUs' chosen modes: the record of the NxN instances, from the words per PU (a PU priced alone is the PU priced with
+          // its three neighbours: every line is the original's); valid iff the node lies inside and every PU has a mode
+          const long long ctu = (long long)(f * band_rows + (cy - F.row_begin)) * F.ctus_x + cx;   // compact over the band
+          unsigned nd = 0, lv = 0, cbf = 0, top = 0, side4 = 0, modes4 = 0;
+          bool nv = node_in;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const unsigned* const pb = &s_acc[kPuBestAt + 3 * ((2 * ty + (i >> 1)) * 16 + 2 * tx + (i & 1))];
+            const unsigned m = (pb[1] >> 16) & 0xFFu, l = pb[1] & 0xFFFFu;
+            nv = nv && m <= 34u;
+            nd += pb[0]; lv += l; cbf |= l != 0u ? 1u << i : 0u; top = max(top, pb[2]); modes4 |= m << (8 * i);
+            side4 += intra_mode_bits(m);
+          }
+          const unsigned nb = 4u + lv + side4;
+          unsigned long long nj = (256ull * nd + (unsigned long long)Q.lam_q8 * nb) >> 8;
+          const unsigned nc = nj < 0xFFFFFFFEull ? (unsigned)nj : 0xFFFFFFFEu;
+          const unsigned nf = (lv == 0u ? 1u : 0u) | (((top * Q.scale + Q.add_half[0]) >> Q.qbits[0]) == 0u ? 2u : 0u) | 4u;
+          if (S.nxn) {
+            unsigned* const o = S.nxn + (ctu * 64 + (nidx - N.first)) * 4;
+            o[0] = nv ? nd : kRdMark; o[1] = nv ? nc : kRdMark;
+            o[2] = nv ? (nb < 65535u ? nb : 65535u) | nf << 16 | cbf << 24 : 0xFFFFu;
+            o[3] = nv ? modes4 : 0xFFFFFFFFu;
+          }
+          if (nv && nc < u.cost_rd) {
+            u.dist = nd; u.cost_rd = nc; u.bits = (uint16_t)(nb < 65535u ? nb : 65535u); u.flags = (uint8_t)nf; u.tu_split = 1;
+            u.part = kRdPartIntraNxN; u.merged = 0; u.pad[0] = u.pad[1] = 0;
+          }
+        }
+      }
       // the earlier record (a marker where there is none), read through the output pointer where the fold is in place
       const FhevcMotionRdPuNode* const src = reinterpret_cast<const void*>(fold) == reinterpret_cast<const void*>(out) ? out : reinterpret_cast<const FhevcMotionRdPuNode*>(fold);
       const FhevcMotionRdPuNode fr = fold ? src[rec] : none;
       // calm: the merge candidate is strictly the cheapest so far and has a masked zero bit -- HM does not try intra there (TEncCu.cpp:799-804)
       bool calm = false;
       if (rd_merge) calm = rd_merge[rec * 4 + 1] < fr.cost_rd && (((rd_merge[rec * 4 + 2] >> 16) & 0xFFu) & (unsigned)skip_mask) != 0u;
-      if constexpr (NXN) {
+      if constexpr (NXN || SEARCH) {
         if (calm || (fold && !(u.cost_rd < fr.cost_rd))) u = fr;   // a marker's cost is below nothing: the test of validity is in the comparison
       } else
       if (calm || (fold && !(valid && u.cost_rd < fr.cost_rd))) u = fr;
@@ -1222,6 +1519,29 @@ hipError_t fhevc_launch_intra_rd_nxn(const FhevcFrames& fr, const FhevcRdQuant& 
   if (fr.sample_bytes == 2)
     return refine_launch_kernel<&fhevc_intra_rd_kernel<int16_t, RdThreeDepths, RdNxN>>(L, fr, q, dw(d_first), dw(d_fold), dw(d_rd_merge), skip_mask, d_out, RdThreeDepths{}, x);
   return refine_launch_kernel<&fhevc_intra_rd_kernel<uint8_t, RdThreeDepths, RdNxN>>(L, fr, q, dw(d_first), dw(d_fold), dw(d_rd_merge), skip_mask, d_out, RdThreeDepths{}, x);
+}
+
+// ---- the intra candidate searched over the first pass's lists (fhevc_intra_rd_search*): the instances of three TU depths with the third tag, behind every
+// instance there was; 80 532 B of static LDS, which still leaves room for two workgroups per CU.  ONE launch: step A's positions, the 4x4 PUs' positions
+// (passes of their own over the level-3 buffer) and the two runs of step B are phases of the one kernel ----
+hipError_t fhevc_launch_intra_rd_search(const FhevcFrames& fr, const FhevcRdQuant& q, const uint8_t* d_modes, int list_stride, const uint8_t* d_modes4, int list_stride4,
+                                        const FhevcIntraSearchRule& rule, const FhevcMotionRdPuNode* d_fold, const FhevcMotionRdNode* d_rd_merge, int skip_mask,
+                                        FhevcMotionRdPuNode* d_out, FhevcIntraRdNxN* d_nxn, int num_cus, hipStream_t stream)
+{
+  const long long total = (long long)(fr.row_end - fr.row_begin) * fr.ctus_x * fr.num_frames;
+  if (total <= 0) return hipSuccess;
+  bool ok = d_modes && d_out && skip_mask >= 0 && skip_mask <= 3 && total <= 0x7FFFFFFF && list_stride >= 1 && list_stride <= 8 && rule.append_planar <= 1 && (d_modes4 || !d_nxn);
+  for (int l = 0; l < 4; ++l) ok = ok && rule.count[l] >= 1 && rule.count[l] <= list_stride;
+  if (d_modes4) ok = ok && list_stride4 >= 1 && list_stride4 <= 8 && rule.count4 >= 1 && rule.count4 <= list_stride4;
+  if (!ok) return hipErrorInvalidValue;   // a count above its stride would read the neighbouring entry
+  const auto dw = [](const void* p) { return reinterpret_cast<const unsigned*>(p); };
+  const RefineLaunch L = { 0, { 4, true }, num_cus, total, stream };
+  const RdSearch x = { d_modes, d_modes4, reinterpret_cast<unsigned*>(d_nxn), list_stride, d_modes4 ? list_stride4 : 1,
+                       (unsigned)rule.count[0] | (unsigned)rule.count[1] << 8 | (unsigned)rule.count[2] << 16 | (unsigned)rule.count[3] << 24, d_modes4 ? rule.count4 : 1,
+                       rule.append_planar };
+  if (fr.sample_bytes == 2)
+    return refine_launch_kernel<&fhevc_intra_rd_kernel<int16_t, RdThreeDepths, RdSearch>>(L, fr, q, dw(nullptr), dw(d_fold), dw(d_rd_merge), skip_mask, d_out, RdThreeDepths{}, x);
+  return refine_launch_kernel<&fhevc_intra_rd_kernel<uint8_t, RdThreeDepths, RdSearch>>(L, fr, q, dw(nullptr), dw(d_fold), dw(d_rd_merge), skip_mask, d_out, RdThreeDepths{}, x);
 }
 
 #pragma clang diagnostic pop

@@ -1478,6 +1478,74 @@ int  fhevc_p_tree_rd_intra_nxn_frame(fhevc_ctx* ctx, const int16_t* cur_luma, co
                                      uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes, fhevc_motion_merge_node* merge,
                                      fhevc_motion_rd_node* rd_merge, fhevc_motion_rd_pu_node* rd_pu, fhevc_node_cost* first, fhevc_intra_rd_nxn_node* nxn);
 
+/* ---- config 4 (P slices): the intra candidate searched over the first pass's candidate lists (two further intra instances of k_motion_rd.hip) ----------
+ * fhevc_intra_rd_nxn* prices ONE mode per node and per 4x4 PU: the winner of the Hadamard pass.  HM keeps a list from that pass -- 3 modes for PUs of 16 and
+ * above, 8 for 8x8 and 4x4 PUs (TEncSearch.cpp:2244, g_aucIntraModeNumFast_UseMPM) --, appends most-probable modes (:2297-2320) and decides among them on
+ * RD cost in two steps (:2349-2480).  The stage of this section is fhevc_intra_rd_nxn* (three TU depths, DST, NxN) with the mode taken from a list.
+ * Everything not named below is that stage's: planes, band, prediction per TU, transform, quantiser, bit estimate, lam, calm gate, fold (in place allowed),
+ * record types, markers, asynchrony, no per-context or HBM state.
+ *   Inputs.  d_modes is what fhevc_intra_first_pass_candidates_device writes with num_candidates = list_stride (1..8): 85 * list_stride bytes per CTU, best
+ * first, compact over the band.  d_modes4 (or NULL) is the d_modes of fhevc_intra_first_pass_4x4_device with list_stride4: 256 * list_stride4 bytes per CTU.
+ * Any byte content is legal.  No byte reaches an address or a loop bound.  The lists are byte arrays: no alignment is asked of them.
+ *   The rule travels by value with the launch: count[l] for the nodes of level l (0: 64x64 .. 3: 8x8), count4 for the 4x4 PUs, append_planar 0 / 1, pad 0.
+ *   The list of a node of level l is the first count[l] bytes of its entry; the list of a 4x4 PU is the first count4 bytes of its entry.  Bytes > 34 are
+ * skipped.  With append_planar, mode 0 is appended behind the list iff the list has at least one valid entry and none of them is 0: what
+ * getIntraDirPredictor gives when neither neighbour is intra-coded -- both directions DC, *piMode 1, one MPM appended, PLANAR (TComDataCU.cpp:1403-1421) --,
+ * the common case in a P picture and the neighbourhood that bits(m) = 2 / 3 / 6 already assumes.  MPMs from coded intra neighbours stay a stated departure.
+ * A node is valid iff it is INSIDE and its list is not empty.
+ *   Step A (bCheckFirst): for every list entry c, in order,
+ *     A_c = sum over the node's depth-0 TUs of J0 (the fhevc_intra_rd_qt J0, predicted at m_c) + lam * bits(m_c), in 64 bits.
+ * Best and second are kept as HM keeps them: a candidate strictly below the best becomes the best, and the old best becomes the second; otherwise a
+ * candidate strictly below the second becomes the second.  (The first valid entry is the best; with no second yet, any further entry is below it.)
+ *   Step B: F(m) is the record fhevc_intra_rd_qt_device writes at tu_depths 3 for a node whose mode is m.  The node's record is F(best); it is F(second)
+ * instead iff a second exists and its cost_rd is STRICTLY smaller, compared on the unshifted 64-bit J.  The record has part 16 and pad[0] = the mode;
+ * pad[1] = the winner's position in the list (0 = the first pass's own winner; the appended planar counts as the position behind the last list byte
+ * used, count[l]).
+ *   NxN of the 8x8 nodes (only with d_modes4): a 4x4 PU has no split, so HM's two steps coincide.  Per PU i the candidate with the smallest
+ * 256 D + lam (r + bits(m)) wins, strict < in list order.  The NxN record and the optional d_nxn record are the section above's over the four chosen modes
+ * (NxN is valid iff the node is INSIDE and each of the four lists is not empty).  The choice against 2Nx2N, the gate and the fold are unchanged.  With
+ * d_modes4 NULL there is no NxN candidate, and d_nxn must be NULL.
+ *   FHEVC_E_INVALID with nothing launched or written: what fhevc_intra_rd_nxn_device rejects; a null d_modes or rule; strides outside 1..8; a count of 0,
+ * or a count above its stride; append_planar above 1, or a non-zero pad; d_nxn without d_modes4; any overlap of an input list with an output.
+ * (list_stride4 and count4 are not looked at where d_modes4 is NULL.)
+ *   Timed under slot 41 of fhevc_kernel_timing (40 and 42 stay rejected).
+ *   Identities: (i) with all counts 1 and append_planar 0 every byte of d_out and d_nxn equals fhevc_intra_rd_nxn_device fed records whose modes are the
+ * lists' first bytes, with or without the 4x4 input, through gate and fold; (ii) the output record of any node equals fhevc_intra_rd_qt_device's record at 3
+ * for a `first` array holding the winning mode, in all bytes but pad[1]; (iii) F(m).J <= A(m), so the result never costs more
+ * than step A's cost of the list's first valid entry (not: than F of that entry -- the two steps rank on A, and a mode ranked third there is never tried on the
+ * full tree).
+ *   The kernel: ONE launch per call.  Per CTU, behind the lines: the positions of the 4x4 PUs' lists in passes of their own over the level-3 buffer (N = 4,
+ * DST, all four waves; sums and best per PU in LDS); then one loop of phases -- the positions of step A run the prediction and the depth-0 pass alone,
+ * the writer lane of each node keeps best and second in LDS and clears the sums; then the three depths at the best mode and again at the second (a wave
+ * whose list is exhausted keeps the barriers and its result is dropped).  80 532 B of static LDS, no scratch.
+ * NOT covered (stated departures): MPMs from coded intra neighbours, reconstructed neighbours, transform skip, RDOQ, chroma, the mode-flag bits; the margin
+ * fit and any hook consumer. */
+typedef struct fhevc_intra_search_rule {
+  uint8_t count[4];        /* list entries read per node of level 0..3 */
+  uint8_t count4;          /* ... per 4x4 PU */
+  uint8_t append_planar;   /* 0 / 1 */
+  uint8_t pad[2];          /* 0 */
+} fhevc_intra_search_rule;  /* 8 bytes */
+/* HM: count {3, 3, 3, 8}, count4 8, append_planar 1 */
+void fhevc_intra_search_rule_default(fhevc_intra_search_rule* rule);
+int  fhevc_intra_rd_search_device(fhevc_ctx* ctx, const void* d_luma, int sample_bytes, int stride_samples, long long frame_stride_samples, int num_frames,
+                                  int ctu_row_begin, int ctu_row_end, int qp, const uint8_t* d_modes, int list_stride, const uint8_t* d_modes4, int list_stride4,
+                                  const fhevc_intra_search_rule* rule, const fhevc_motion_rd_pu_node* d_fold, const fhevc_motion_rd_node* d_rd_merge,
+                                  int skip_mask, fhevc_motion_rd_pu_node* d_out, fhevc_intra_rd_nxn_node* d_nxn, void* stream);
+/* the host form: one picture, host buffers, synchronous; modes its 85 * list_stride bytes per CTU, modes4 its 256 * list_stride4 (or NULL) */
+int  fhevc_intra_rd_search(fhevc_ctx* ctx, const int16_t* luma, int stride_samples, int qp, const uint8_t* modes, int list_stride, const uint8_t* modes4,
+                           int list_stride4, const fhevc_intra_search_rule* rule, const fhevc_motion_rd_pu_node* fold, const fhevc_motion_rd_node* rd_merge,
+                           int skip_mask, fhevc_motion_rd_pu_node* out, fhevc_intra_rd_nxn_node* nxn);
+/* fhevc_p_tree_rd_intra_nxn_frame's chain with this stage in the NxN stage's place.  In order: fhevc_p_tree_rd_qt_frame's chain at 3; the first pass of the
+ * current picture; its lists through fhevc_intra_first_pass_candidates_device and those of fhevc_intra_first_pass_4x4_device, both at 8 candidates;
+ * fhevc_intra_rd_search_device under rule (NULL: the default), folding in place under skip_mask; the RD tree.  It downloads what the NxN frame call
+ * downloads.  Rejects what that call rejects, and a bad rule. */
+int  fhevc_p_tree_rd_intra_search_frame(fhevc_ctx* ctx, const int16_t* cur_luma, const int16_t* ref_luma, int stride_samples, int qp, int search_range,
+                                        int coarse_range, const fhevc_pu_shape_rule* shape_rule, const fhevc_p_tree_rule* tree_rule,
+                                        const fhevc_intra_search_rule* rule, int skip_mask, uint8_t* depth_min, uint8_t* depth_max, fhevc_pu_shape_node* shapes,
+                                        fhevc_motion_merge_node* merge, fhevc_motion_rd_node* rd_merge, fhevc_motion_rd_pu_node* rd_pu, fhevc_node_cost* first,
+                                        fhevc_intra_rd_nxn_node* nxn);
+
 /* ---- config 4 (P slices): intra candidate costs per CU node (k_intra_p.hip) -----------------------------------------------------------------------
  * HM checks intra at every CU of a P slice (TEncCu.cpp:797-816): xCheckRDCostIntra(SIZE_2Nx2N) at every depth, SIZE_NxN at the 8x8 level, both only while
  * the best mode so far has a non-zero CBF.  Without that candidate a node whose content is not in the reference picture -- uncovered background, the second
@@ -1584,6 +1652,8 @@ int  fhevc_band(int ctu_rows, int rank, int world, int* begin, int* end);
  * as does any number above 37
  * -- except 39 = the RD estimate of the intra candidate with the NxN candidate (fhevc_intra_rd_nxn* with d_first4; without it the launch is slot 37's).
  * 38 is not a slot: it stays rejected, as does any number above 39.
+ * -- except 41 = the RD estimate of the intra candidate searched over the first pass's candidate lists (fhevc_intra_rd_search*).
+ * 40 is not a slot: it stays rejected, as does any number above 41.
  * The tree that stops at a skip (fhevc_p_tree_select_skip_device), the tree that takes the intra candidate (fhevc_p_tree_select_intra_device) and the tree
  * on RD costs (fhevc_p_tree_select_rd_device) are timed under 17 */
 int  fhevc_kernel_timing(fhevc_ctx* ctx, int which, int reset, double* avg_ms, uint64_t* launches);

@@ -5,8 +5,9 @@
 
 fhevc_motion_rd_device (re-priced nodes with their predictor records) and fhevc_motion_rd_pu_device (part_mode 8) at max_range 8 and 64 on 16 pairs of
 1920 x 1080 uint8 planes (8 160 CTUs per call), and fhevc_intra_rd_device (plain, on the first pass's records of the 16 current pictures: the same CTUs;
-where both builds have it, fhevc_intra_rd_qt_device at tu_depths 3 on the same records, slot 37);
-the average of ten calls through the library's timing slots 29, 31 and 33, after two warm-up calls; three
+where both builds have it, fhevc_intra_rd_qt_device at tu_depths 3 on the same records, slot 37, and fhevc_intra_rd_nxn_device on them and the 4x4
+first pass's records, slot 39);
+the average of ten calls through the library's timing slots 29, 31, 33, 37 and 39, after two warm-up calls; three
 interleaved rounds of parent, this, parent again.  The second parent run of a round gives the band the box has that day: this build passes a round when
 it lies inside the band or within the band's width beyond it.  Both builds give the same bytes, or nothing is timed."""
 import json
@@ -55,6 +56,11 @@ def main(parent_path, this_path, out_path):
     calls = {"intra_rd_ms": (33, lambda c: c.intra_rd_device(*current, p(first), p(out), qp=QP))}
     if all(hasattr(c.lib, "fhevc_intra_rd_qt_device") for c in ctxs.values()):   # both builds have the intra instances of three TU depths: slot 37
         calls["intra_rd_qt_3_ms"] = (37, lambda c: c.intra_rd_qt_device(*current, p(first), 3, p(out), qp=QP))
+    if all(hasattr(c.lib, "fhevc_intra_rd_nxn_device") for c in ctxs.values()):  # both builds have the instances with the NxN candidate: slot 39
+        first4 = buf(256)
+        c0.intra_first_pass_4x4_device(*current, p(first4), None, qp=QP, num_candidates=0)
+        torch.cuda.synchronize()
+        calls["intra_rd_nxn_ms"] = (39, lambda c: c.intra_rd_nxn_device(*current, p(first), p(first4), p(out), qp=QP))
     for R in (8, 64):
         priced, mvp, inputs, _ = chain[R]
         calls[f"rd_{R}_ms"] = (29, lambda c, R=R, q=priced, v=mvp: c.motion_rd_device(*layout, capi.RD_SOURCE_EXPLICIT, p(q[0]), p(out), d_mvp=p(v[0]), qp=QP, max_range=R))
@@ -102,7 +108,7 @@ def main(parent_path, this_path, out_path):
                          "rounds_inside_the_band_or_within_its_width_beyond": int(sum(inside)), "rounds": len(rounds)}
     res = {"what": "existing RD entry points, parent commit against this one: fhevc_motion_rd_device (re-priced nodes with predictor records) and fhevc_motion_rd_pu_device "
                    "(part_mode 8) at max_range 8 and 64, fhevc_intra_rd_device (plain) and, where both builds have it, fhevc_intra_rd_qt_device at tu_depths 3 (plain, slot 37), uint8 planes, 16 pairs of 1920x1080 (8 160 CTUs) per call; average of 10 calls "
-                   "per run through the library's timing slots 29, 31 and 33; three interleaved rounds of parent, this commit, parent again (the second parent run gives the noise band) in one process on one MI355X",
+                   "per run through the library's timing slots 29, 31, 33 and -- fhevc_intra_rd_qt_device at tu_depths 3 and fhevc_intra_rd_nxn_device with the 4x4 first pass's records, where both builds have them -- 37 and 39; three interleaved rounds of parent, this commit, parent again (the second parent run gives the noise band) in one process on one MI355X",
            "unit": "ms per call", "same_bytes_from_both_builds": True, "rounds": rounds, "verdict": verdict}
     print(json.dumps(verdict), flush=True)
     with open(out_path, "w") as f:
